@@ -16,16 +16,22 @@ Patterns U[1,5] s, float32 streams (--sample-type uint8 for the reference's defa
 every N: the time-sorted events are sharded in contiguous blocks over the N ranks (strong scaling), the two streams
 are replicated, one all-gather of 8 bytes per event ends the step.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events on the launch stream.  The oracle leg (rank 0,
-before HIP is initialised in this process: it forks one single-threaded worker per host core) always runs: it is the
-line's `parity` block -- an evenly spaced sample of the job's searches plus every search cut from tie-saturated
-material, compared with the GPU results -- and, unless --no-cpu-baseline, over a larger sample its wall time is the
-`cpu_baseline` (the oracle is an FFT port of cv2.matchTemplate; cv2 itself is not installable here -- where it does
-import, `parity.cv2` holds the same comparison against the real call).
+Rank 0 prints ONE JSON line.  A plain run does what the headline needs and nothing more: it builds the inputs, sets up,
+runs the W warm-up steps, times the K steps (`value`, `ms_per_step`), writes what the last timed step returned if
+--dump-outputs is given, and prints the line.  --full adds everything else the line can carry:
+  * the oracle leg (rank 0, before HIP is initialised in this process: it forks one single-threaded worker per host core):
+    the line's `parity` block -- an evenly spaced sample of the job's searches plus every search cut from tie-saturated
+    material, compared with the GPU results -- and, unless --no-cpu-baseline, over a larger sample its wall time is the
+    `cpu_baseline` (the oracle is an FFT port of cv2.matchTemplate; where cv2 imports, `parity.cv2` holds the same
+    comparison against the real call);
+  * an untimed verification pass before the warm-up (the planted offset must be recovered), whose wall time is
+    `first_step_ms` and the one-shot figures;
+  * `roofline`, measured live with per-stage HIP events on the launch stream;
+  * `shard_emulation` (N = 1): every shard of the G-rank job timed alone on this GPU.
 """
 import argparse
 import hashlib
@@ -242,6 +248,27 @@ def loaded_library():
     return {"path": os.path.relpath(_native.LIB_PATH, ROOT), "sha256_16": sha, "env_override": bool(os.environ.get("SUSHI_HIP_LIB"))}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, idx, score):
+    """--dump-outputs: what the last timed step returned to its caller, one row per event in job order: DIR/index.npy (the
+    position in the search window, float64: exact for every int32) and DIR/score.npy (float32, float64 if the path gave that).
+    A job whose rows exceed 64 MB in all writes a fixed seeded sample of its events instead, their numbers in DIR/event.npy."""
+    os.makedirs(directory, exist_ok=True)
+    score = np.asarray(score)
+    arrays = {"index": np.asarray(idx).astype(np.float64),
+              "score": score.astype(np.float64 if score.dtype == np.float64 else np.float32)}
+    n = arrays["index"].shape[0]
+    row_bytes = sum(a.itemsize for a in arrays.values()) + 8             # + the event number of a sampled row
+    if n * row_bytes > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_LIMIT_BYTES // row_bytes, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["event"] = rows.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 class DryBatch(object):
     """--dry-backend gloo: a stand-in for SearchBatch that answers the planted positions from the host and computes
     nothing -- so that the N > 1 control flow of this file (sharding, gather, per-rank report, max over ranks) can run
@@ -294,25 +321,30 @@ def main():
                     help="fraction of the events cut from digital silence / a held tone / a repeated jingle "
                          "(tie-saturated searches); 0 = the BASELINE workload")
     ap.add_argument("--profile-only", action="store_true",
-                    help="no oracle leg at all (no forked workers: rocprofv3's counter passes hang waiting for them); the line's "
+                    help="--full: no oracle leg at all (no forked workers: rocprofv3's counter passes hang waiting for them); the line's "
                          "parity block then holds the planted-offset check only -- for profiler runs, never for a reported line")
     ap.add_argument("--no-cpu-baseline", action="store_true",
-                    help="skip the TIMING of the oracle (cpu_baseline: null); the parity sample is still run")
-    ap.add_argument("--cpu-sample", type=int, default=64, help="searches of the workload the oracle is run on, at least")
-    ap.add_argument("--cpu-workers", type=int, default=None, help="processes of the oracle leg (default: one per host core)")
+                    help="--full: skip the TIMING of the oracle (cpu_baseline: null); the parity sample is still run")
+    ap.add_argument("--cpu-sample", type=int, default=64, help="--full: searches of the workload the oracle is run on, at least")
+    ap.add_argument("--cpu-workers", type=int, default=None, help="--full: processes of the oracle leg (default: one per host core)")
     ap.add_argument("--variant", type=int, default=None)
     ap.add_argument("--path", choices=("fft", "direct"), default="fft")
     ap.add_argument("--ws-mb", type=int, default=None, help="FFT path scratch per batch (MiB); default: what one "
                                                             "sub-batch for the whole shard needs, at most 160 GiB")
     ap.add_argument("--delta", type=float, default=None)
     ap.add_argument("--emulate-shards", type=int, default=8,
-                    help="N = 1 only: after the measurement, cut the job into the G = 2, 4, .. work-balanced shards the G-rank run "
+                    help="--full, N = 1 only: after the measurement, cut the job into the G = 2, 4, .. work-balanced shards the G-rank run "
                          "would give its ranks (up to this G; 0 = off) and time every shard on THIS GPU -- the slowest shard is "
                          "what a G-GPU step would take, the collective aside (`shard_emulation` in the line)")
     ap.add_argument("--dry-backend", choices=("gloo",), default=None,
                     help="no GPU: run this file's N-rank control flow over gloo with a stand-in batch (tests only)")
     ap.add_argument("--dry-plant-error", type=int, default=0,
                     help="dry runs: the stand-in answers this many samples off the planted position (tests)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the oracle leg (parity, cpu_baseline), the verification pass (first_step_ms, "
+                         "one-shot figures), per-stage timing and the roofline, the shard emulation")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (per event: index, score) as DIR/<name>.npy")
     args = ap.parse_args()
     cfg = dict(CONFIGS[args.config])
     custom = False
@@ -429,11 +461,11 @@ def main():
     del pats
     ev_starts = np.array([s for s, _ in events])
 
-    # ---- oracle leg first (rank 0): fork a pool before CUDA exists in this process --------------
-    # Always: the parity sample (>= --cpu-sample evenly spaced searches + every search cut from tie-saturated material).
+    # ---- --full: oracle leg first (rank 0): fork a pool before CUDA exists in this process ------
+    # The parity sample (>= --cpu-sample evenly spaced searches + every search cut from tie-saturated material).
     # N = 1 and not --no-cpu-baseline: over a larger sample, timed = cpu_baseline.
     cpu, cpu_results = None, {}
-    if rank == 0 and not dry and not args.profile_only:
+    if rank == 0 and not dry and not args.profile_only and args.full:
         timed = world == 1 and not args.no_cpu_baseline
         cpu, cpu_results = oracle_leg(dst.data[0], src.data[0], offs, lens, wst, npos, args.method,
                                       forced=np.nonzero(hard_mask)[0], timed=timed, min_sample=args.cpu_sample,
@@ -511,21 +543,7 @@ def main():
             ev_end.record()
         return sharded.gather(*out)
 
-    # one untimed verification pass before anything is timed: a batch that does not recover the planted offset is
-    # not worth measuring (it also pages the kernels in; the W warm-up steps below are the contract's)
-    sync()
-    t_first = time.perf_counter()
-    v_idx, _ = step()
-    sync()
-    first_step_ms = (time.perf_counter() - t_first) * 1e3          # the batch's FIRST run: what a one-shot job's only step is
-    v_idx = v_idx.cpu().numpy()
-    v_times = np.array(start_times) + v_idx.astype(np.float64) / float(rate)
-    v_err = np.abs((v_times - ev_starts) - args.offset) * rate
-    # An event whose result is more than one sample from the planted offset: with 20 dB of noise on a smooth signal the
-    # true minimum can sit a sample beside the planted one (seen at 24 kHz), on top of the < 1 sample that the two
-    # truncations of wav.py:173-175 contribute.  Beyond two samples the run is refused outright; between one and two the
-    # oracle has to find the very same position.  Every rank holds the same gathered results and reaches the same
-    # verdict by itself (the oracle runs in-process on the few events concerned), so all ranks leave together.
+    # the events whose answer is the planted offset (the verification pass below checks them; the line's config counts them)
     planted_mask = ~hard_mask if not args.unrelated else np.zeros(n_total, bool)      # --unrelated: no planted answer at all
     if args.source == "partial":
         # the second half of the source is other audio: its events have no planted answer (the oracle sample covers them)
@@ -540,29 +558,46 @@ def main():
             a_, b_ = max(0, min(a_, gate.shape[0])), max(0, min(b_, gate.shape[0]))
             if cg[b_] - cg[a_] > 0:
                 planted_mask[k] = False
-    off_planted = [int(k) for k in np.nonzero((v_err > 1.0) & planted_mask)[0]]
-    beyond_planted = {"events": len(off_planted), "confirmed_by_oracle": 0}
-    if off_planted:
-        worst = float(v_err[planted_mask].max())
-        # (below 20 dB the true minimum wanders further from the planted position: the oracle alone decides then)
-        if args.source not in ("dub", "partial") and (len(off_planted) > 32 or (worst > 2.0 and args.snr >= 20.0)):
-            raise SystemExit("verification pass: planted offset not recovered on %d events (max error %.3f samples)"
-                             % (len(off_planted), worst))
-        _cpu_ctx.update(dst=dst.data[0], src=src.data[0], offs=offs, lens=lens, wst=wst, npos=npos, method=args.method)
-        _cpu_ctx.pop("cv2_set", None)
-        for k in off_planted:
-            o = cpu_results.get(k) or _cpu_one(k)
-            if o[0] != int(v_idx[k]):
-                raise SystemExit("verification pass: event %d: position %d, oracle %d, planted offset missed by %.3f "
-                                 "samples" % (k, int(v_idx[k]), o[0], float(v_err[k])))
-            beyond_planted["confirmed_by_oracle"] += 1
+    # --full: one untimed verification pass before anything is timed: a batch that does not recover the planted offset is
+    # not worth measuring (it also pages the kernels in; the W warm-up steps below are the contract's)
+    first_step_ms, beyond_planted = None, None
+    if args.full:
+        sync()
+        t_first = time.perf_counter()
+        v_idx, _ = step()
+        sync()
+        first_step_ms = (time.perf_counter() - t_first) * 1e3          # the batch's FIRST run: what a one-shot job's only step is
+        v_idx = v_idx.cpu().numpy()
+        v_times = np.array(start_times) + v_idx.astype(np.float64) / float(rate)
+        v_err = np.abs((v_times - ev_starts) - args.offset) * rate
+        # An event whose result is more than one sample from the planted offset: with 20 dB of noise on a smooth signal the
+        # true minimum can sit a sample beside the planted one (seen at 24 kHz), on top of the < 1 sample that the two
+        # truncations of wav.py:173-175 contribute.  Beyond two samples the run is refused outright; between one and two the
+        # oracle has to find the very same position.  Every rank holds the same gathered results and reaches the same
+        # verdict by itself (the oracle runs in-process on the few events concerned), so all ranks leave together.
+        off_planted = [int(k) for k in np.nonzero((v_err > 1.0) & planted_mask)[0]]
+        beyond_planted = {"events": len(off_planted), "confirmed_by_oracle": 0}
+        if off_planted:
+            worst = float(v_err[planted_mask].max())
+            # (below 20 dB the true minimum wanders further from the planted position: the oracle alone decides then)
+            if args.source not in ("dub", "partial") and (len(off_planted) > 32 or (worst > 2.0 and args.snr >= 20.0)):
+                raise SystemExit("verification pass: planted offset not recovered on %d events (max error %.3f samples)"
+                                 % (len(off_planted), worst))
+            _cpu_ctx.update(dst=dst.data[0], src=src.data[0], offs=offs, lens=lens, wst=wst, npos=npos, method=args.method)
+            _cpu_ctx.pop("cv2_set", None)
+            for k in off_planted:
+                o = cpu_results.get(k) or _cpu_one(k)
+                if o[0] != int(v_idx[k]):
+                    raise SystemExit("verification pass: event %d: position %d, oracle %d, planted offset missed by %.3f "
+                                     "samples" % (k, int(v_idx[k]), o[0], float(v_err[k])))
+                beyond_planted["confirmed_by_oracle"] += 1
     for _ in range(args.warmup):
         step()
     timer = (lambda: torch.cuda.Event(enable_timing=True)) if not dry else (lambda: None)
     starts = [timer() for _ in range(args.steps)]
     ends = [timer() for _ in range(args.steps)]
     sync()
-    fft_prof = args.path == "fft" and batch is not None and not dry
+    fft_prof = args.full and args.path == "fft" and batch is not None and not dry
     if fft_prof:
         _native.profile_begin()           # per-stage HIP events on the launch stream, read after the final sync
     t0 = time.perf_counter()
@@ -587,9 +622,9 @@ def main():
     idx_all = idx_all.cpu().numpy()
     score_all = score_all.cpu().numpy()
 
-    # ---- what a G-rank run would give each of its ranks, timed on this one GPU ----
+    # ---- --full: what a G-rank run would give each of its ranks, timed on this one GPU ----
     shard_emulation = None
-    if world == 1 and not dry and args.emulate_shards >= 2 and not args.profile_only:
+    if args.full and world == 1 and not dry and args.emulate_shards >= 2 and not args.profile_only:
         from sushi_amd.distributed import weighted_bounds
         w_all = search_work(wst, npos, lens, args.path)
         shard_emulation = {"label": "single-GPU shard emulation: every shard of the G-rank job timed alone on this GPU with the "
@@ -626,171 +661,11 @@ def main():
             torch.cuda.empty_cache()
             g *= 2
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, idx_all, score_all)
+
     if rank == 0:
-        # parity on the whole job: planted offset recovered to +-1 sample on every (ordinary) event
-        times = np.array(start_times) + idx_all.astype(np.float64) / float(rate)
-        shift_err = np.abs((times - ev_starts) - args.offset) * rate
-        max_shift_err_vs_planted = float(shift_err[planted_mask].max()) if planted_mask.any() else None
-        diag_ps = None
-        if fft_prof and world == 1:
-            diag_ps = batch.diagnostics(per_search=True)
-            # every search the exact stages had to finish through the tile kernels belongs in the oracle sample: the ones
-            # the forced set did not foresee are run here, in-process
-            _cpu_ctx.update(dst=dst.data[0], src=src.data[0], offs=offs, lens=lens, wst=wst, npos=npos, method=args.method)
-            _cpu_ctx.pop("cv2_set", None)
-            late = [int(k) for k in np.nonzero(diag_ps["flagged_per_search"])[0] if int(k) not in cpu_results]
-            for k in late[:64]:
-                cpu_results[k] = _cpu_one(k)
-        parity = {"max_shift_err_samples_vs_planted": max_shift_err_vs_planted,
-                  "events_beyond_one_sample_of_planted": beyond_planted,
-                  "oracle_sample_searches": len(cpu_results),
-                  "score_tolerance": "1e-4*score + 2.5e-7 (one float32 ulp of cv2's stored corr)"}
-        ties = 0
-        if cpu_results:
-            ks = sorted(cpu_results)
-            ie = np.array([abs(int(idx_all[k]) - cpu_results[k][0]) for k in ks])
-            if args.sample_type == "float32" and ie.max() > 0:
-                # a different index is a tie, not an error, if the oracle itself scores the two positions within the float32
-                # quantum of cv2's stored cross term (tests/test_gpu_parity.py _check_f32): material that repeats exactly (a
-                # recurring jingle, a held tone) ties exactly, the product returns the FIRST such position from exact
-                # arithmetic, the oracle's float64 FFT may round a later one a quantum lower
-                from oracle import oracle as O
-                for j, k in enumerate(ks):
-                    if ie[j] == 0:
-                        continue
-                    off, m, ws, p = offs[k], lens[k], wst[k], npos[k]
-                    row = O.match_template_fft(dst.data[0][ws:ws + p + m - 1], src.data[0][off:off + m], method=args.method)[0]
-                    if abs(float(row[int(idx_all[k])]) - float(row[cpu_results[k][0]])) <= SCORE_ATOL:
-                        ie[j] = 0
-                        ties += 1
-            ae = np.array([abs(float(score_all[k]) - cpu_results[k][1]) for k in ks])
-            # excess over the parity bound |d| <= 1e-4*score + 2.5e-7 (tests/test_gpu_parity.py); <= 1 passes
-            se = np.array([abs(float(score_all[k]) - cpu_results[k][1]) / (SCORE_RTOL * abs(cpu_results[k][1]) + SCORE_ATOL)
-                           for k in ks])
-            parity.update(max_idx_err_vs_oracle_sample=int(ie.max()),
-                          max_score_err_over_tolerance_vs_oracle_sample=float(se.max()),
-                          max_abs_score_err_vs_oracle_sample=float(ae.max()),
-                          oracle_sample_hard_searches=int(sum(1 for k in ks if hard_mask[k])),
-                          oracle_sample_exact_ties_at_another_index=ties)
-            if diag_ps is not None:
-                fl = diag_ps["flagged_per_search"]
-                parity["oracle_sample_flagged_searches"] = int(sum(1 for k in ks if fl[k]))
-                parity["flagged_searches_not_in_oracle_sample"] = int(sum(1 for k in np.nonzero(fl)[0]
-                                                                          if int(k) not in cpu_results))
-            real = {k: r[3] for k, r in cpu_results.items() if r[3] is not None}
-            if real:
-                import cv2
-                gi = np.array([abs(int(idx_all[k]) - r[0]) for k, r in real.items()])
-                gs = np.array([abs(float(score_all[k]) - r[1]) / (SCORE_RTOL * abs(r[1]) + SCORE_ATOL)
-                               for k, r in real.items()])
-                oi = np.array([abs(cpu_results[k][0] - r[0]) for k, r in real.items()])
-                parity["cv2"] = {"available": True, "version": cv2.__version__, "searches": len(real),
-                                 "max_idx_err_gpu_vs_cv2": int(gi.max()),
-                                 "max_score_err_over_tolerance_gpu_vs_cv2": float(gs.max()),
-                                 "max_idx_err_oracle_vs_cv2": int(oi.max())}
-            else:
-                parity["cv2"] = {"available": False,
-                                 "note": "`import cv2` fails on this machine: parity is against the oracle's restatement"}
         value = n_total * args.steps / elapsed
-        flops_launch = batch.flops
-        if dry:
-            roofline = {"bound": "hbm", "achieved": None, "peak": PEAK_HBM_GBPS, "unit": "GB/s", "frac": None,
-                        "traffic": None, "note": "dry run: nothing was computed"}
-        elif args.path == "fft":
-            # Since round 5 no single kernel dominates the step (three stages of a quarter each, none of which moves the searches'
-            # own bytes: they multiply, bound and transform spectra): the roofline figure is the WHOLE STEP's -- the algorithmic
-            # bytes of one launch of the hot path over the HIP-event time of all its kernels --, the stage with the largest
-            # HIP-event time is reported beside it with its own share and its own measured HBM traffic.
-            stages = {n: float(v) for n, v in zip(_native.STAGE_NAMES, stage_ms)}
-            dom = max(stages, key=stages.get)
-            dom_ms = stages[dom]
-            kname = _native.STAGE_KERNELS[dom]
-            achieved = batch.algorithmic_bytes / (kernel_ms * 1e-3) / 1e9
-            # HBM bytes per step of every kernel from the committed rocprofv3 PMC passes of this very workload
-            # (profiles/pmc_traffic.json, made by tools/make_pmc_traffic.py).  The entry records the digest of the
-            # kernel sources it was measured on: a different digest means the kernels changed since -> null.
-            traffic, dom_traffic_bytes, step_traffic, traffic_note = None, None, None, "no PMC entry for this workload"
-            wl_key = "config%d/fft/%s/%d/w%g/m%g/n%d" % (args.config, args.sample_type, n_total, cfg["window"],
-                                                        cfg["minutes"], world)
-            if args.method != "sqdiff_normed":
-                wl_key += "/" + args.method
-            if args.hard_frac > 0 or args.offset != 7.25:
-                wl_key += "/hard%g/off%g" % (args.hard_frac, args.offset)
-            if args.snr != 20.0 or args.unrelated:
-                wl_key += "/snr%g%s" % (args.snr, "/unrelated" if args.unrelated else "")
-            if args.source != "noise":
-                wl_key += "/source-" + args.source
-            if args.exclusion not in (None, "auto"):
-                wl_key += "/exclusion-" + args.exclusion
-            digest = kernel_source_digest()
-            per_kernel = None
-            try:
-                with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as f:
-                    entry = json.load(f)[wl_key]
-                if os.environ.get("SUSHI_HIP_LIB"):
-                    traffic_note = "SUSHI_HIP_LIB names another build of the library: the committed PMC passes are not of it"
-                elif entry.get("kernel_source_digest") != digest:
-                    traffic_note = "stale: PMC passes were taken on kernel sources %s, this is %s" % (
-                        entry.get("kernel_source_digest"), digest)
-                else:
-                    step_traffic = float(sum(k["fetch_bytes"] + k["write_bytes"] for k in entry["kernels"].values()))
-                    traffic = step_traffic / (kernel_ms * 1e-3) / 1e9
-                    kerns = [entry["kernels"][kn] for kn in _native.STAGE_KERNEL_SETS[dom] if kn in entry["kernels"]]
-                    dom_traffic_bytes = float(sum(kk["fetch_bytes"] + kk["write_bytes"] for kk in kerns)) if kerns else None
-                    per_kernel = {kn: {"read": kk["fetch_bytes"], "written": kk["write_bytes"]} for kn, kk in sorted(entry["kernels"].items())}
-                    traffic_note = "%s @ %s" % (entry.get("source"), entry.get("source_commit"))
-                    # where a kernel's write bytes are not a WRITE_SIZE pass (tools/make_pmc_traffic.py), say what they are
-                    others = sorted(set(k.get("write_source", "WRITE_SIZE") for k in entry["kernels"].values()) - {"WRITE_SIZE"})
-                    if others:
-                        traffic_note += "; reads: FETCH_SIZE; writes: " + " / ".join(others)
-            except Exception:
-                pass
-            roofline = {"bound": "hbm", "achieved": achieved, "peak": PEAK_HBM_GBPS, "unit": "GB/s",
-                        "frac": achieved / PEAK_HBM_GBPS, "traffic": traffic,
-                        "basis": "whole step: algorithmic bytes of one launch of the hot path / HIP-event time of all its kernels; "
-                                 "`traffic` = PMC bytes (FETCH_SIZE x 2 + WRITE_SIZE, all kernels of a step) / the same time",
-                        "kernel": "all kernels of one sushi_hip_batch_run", "kernel_ms": kernel_ms,
-                        "step_traffic_bytes": step_traffic,
-                        "step_traffic_over_algorithmic": None if step_traffic is None else
-                        step_traffic / batch.algorithmic_bytes,
-                        "traffic_bytes_per_kernel_per_step": per_kernel,
-                        # (on lanes the stages of different sub-batches run side by side: their HIP-event times add up to more than
-                        # the step, so a stage's share is its share of their SUM)
-                        "dominant_stage": {"stage": dom, "kernels": kname, "ms": dom_ms,
-                                           "share_of_step": dom_ms / max(sum(stages.values()), kernel_ms),
-                                           "traffic_bytes_per_step": dom_traffic_bytes,
-                                           "traffic_GBps": None if dom_traffic_bytes is None else dom_traffic_bytes / (dom_ms * 1e-3) / 1e9},
-                        "traffic_key": wl_key, "traffic_source": traffic_note,
-                        "kernel_source_digest": digest,
-                        # the binary that actually ran (the digest above is of the sources on disk)
-                        "library": loaded_library(),
-                        "launches_per_step": batch.sub_batches,
-                        "sub_batches": batch.sub_batches, "lanes": batch.lanes,
-                        "stage_ms": stages,
-                        "stage_ms_basis": "HIP events on the stream each sub-batch runs on, summed over the sub-batches" + (
-                            " -- which run side by side on %d HIP streams (lanes): the stages add up to more than the step; "
-                            "SUSHI_HIP_LANES=1:1 gives the one-after-the-other times" % batch.lanes if batch.lanes > 1 else ""),
-                        "step_kernels_ms": kernel_ms,
-                        "step_hbm_achieved_GBps": achieved,
-                        "step_frac": achieved / PEAK_HBM_GBPS,
-                        "algorithmic_bytes_per_launch": batch.algorithmic_bytes,
-                        "direct_form_flop_per_launch": flops_launch,
-                        "direct_form_equivalent_TFLOPs": flops_launch / (kernel_ms * 1e-3) / 1e12,
-                        "fft_pairs": batch.fft_pairs, "fft_segments": batch.fft_segs,
-                        "workspace_bytes": batch.ws_bytes, "delta": batch.delta,
-                        "diagnostics": batch.diagnostics(),
-                        # what a bare streaming kernel reaches on this part (tools/ubench/hbm_bw.hip,
-                        # profiles/r01/hbm_bw.jsonl): the practical ceiling under the 8 TB/s peak
-                        "stream_ceiling_GBps": {"read": 6300.0, "write": 5300.0, "copy": 5500.0}}
-        else:
-            achieved = flops_launch / (kernel_ms * 1e-3) / 1e12
-            hbm_achieved = batch.algorithmic_bytes / (kernel_ms * 1e-3) / 1e9
-            roofline = {"bound": "mfma", "achieved": achieved, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
-                        "frac": achieved / PEAK_F32_MFMA_TFLOPS, "traffic": None,
-                        "kernel": "match_sqdiff_f32_kernel", "kernel_ms": kernel_ms,
-                        "algorithmic_flop_per_launch": flops_launch,
-                        "algorithmic_bytes_per_launch": batch.algorithmic_bytes,
-                        "hbm_achieved_GBps": hbm_achieved, "hbm_frac": hbm_achieved / PEAK_HBM_GBPS}
         out = {
             "metric": METRIC, "value": value, "unit": "events/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
@@ -818,27 +693,193 @@ def main():
                        "parallelism": "events sharded in contiguous blocks over %d GPU(s), streams replicated, "
                                       "one all-gather of (idx, score)" % world,
                        "kernel_variant": batch.variant},
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "parity": parity,
             # paid once per job, before the first step; outside `value` (inputs resident in HBM when the timed region starts)
             "setup_ms": setup_ms,
             # ... and once per PROCESS, whatever the job: the context's first use + the library's code object (sushi_amd.device.
             # warm_up; a one-shot job overlaps it with its demux / decode)
             "process_start_ms": process_start_ms,
-            # `value` is a RESIDENT-STATE rate (streams, spectra, plan and workspace in HBM, the same job every step).  What a
-            # one-shot job -- sushi.py:663-672: two WavStream loads, then one calculate_shifts pass -- gets from this process:
-            # events / (set-up + one step), with the process's start-up behind it -- and with the start-up on the critical path
-            # (its ONE step is the batch's first run -- the exclusion's form is voted on, nothing is warm --: `first_step_ms`, wall
-            # clock around the untimed verification pass; until round 6's last day these two figures took a steady-state step instead,
-            # which a first run was 9 - 13 ms away from: the vote's same-address atomics, the lanes' streams made inside the run)
-            "first_step_ms": first_step_ms,
-            "one_shot_events_per_s": None if not setup_ms else n_total / ((sum(setup_ms.values()) + first_step_ms) * 1e-3),
-            "one_shot_incl_process_start_events_per_s": None if not setup_ms else
-                n_total / ((process_start_ms + sum(setup_ms.values()) + first_step_ms) * 1e-3),
-            "one_shot_with_a_steady_state_step_events_per_s": None if not setup_ms else
-                n_total / ((sum(setup_ms.values()) + elapsed / args.steps * 1e3) * 1e-3),
         }
+        if args.full:
+            # parity on the whole job: planted offset recovered to +-1 sample on every (ordinary) event
+            times = np.array(start_times) + idx_all.astype(np.float64) / float(rate)
+            shift_err = np.abs((times - ev_starts) - args.offset) * rate
+            max_shift_err_vs_planted = float(shift_err[planted_mask].max()) if planted_mask.any() else None
+            diag_ps = None
+            if fft_prof and world == 1:
+                diag_ps = batch.diagnostics(per_search=True)
+                # every search the exact stages had to finish through the tile kernels belongs in the oracle sample: the ones
+                # the forced set did not foresee are run here, in-process
+                _cpu_ctx.update(dst=dst.data[0], src=src.data[0], offs=offs, lens=lens, wst=wst, npos=npos, method=args.method)
+                _cpu_ctx.pop("cv2_set", None)
+                late = [int(k) for k in np.nonzero(diag_ps["flagged_per_search"])[0] if int(k) not in cpu_results]
+                for k in late[:64]:
+                    cpu_results[k] = _cpu_one(k)
+            parity = {"max_shift_err_samples_vs_planted": max_shift_err_vs_planted,
+                      "events_beyond_one_sample_of_planted": beyond_planted,
+                      "oracle_sample_searches": len(cpu_results),
+                      "score_tolerance": "1e-4*score + 2.5e-7 (one float32 ulp of cv2's stored corr)"}
+            ties = 0
+            if cpu_results:
+                ks = sorted(cpu_results)
+                ie = np.array([abs(int(idx_all[k]) - cpu_results[k][0]) for k in ks])
+                if args.sample_type == "float32" and ie.max() > 0:
+                    # a different index is a tie, not an error, if the oracle itself scores the two positions within the float32
+                    # quantum of cv2's stored cross term (tests/test_gpu_parity.py _check_f32): material that repeats exactly (a
+                    # recurring jingle, a held tone) ties exactly, the product returns the FIRST such position from exact
+                    # arithmetic, the oracle's float64 FFT may round a later one a quantum lower
+                    from oracle import oracle as O
+                    for j, k in enumerate(ks):
+                        if ie[j] == 0:
+                            continue
+                        off, m, ws, p = offs[k], lens[k], wst[k], npos[k]
+                        row = O.match_template_fft(dst.data[0][ws:ws + p + m - 1], src.data[0][off:off + m], method=args.method)[0]
+                        if abs(float(row[int(idx_all[k])]) - float(row[cpu_results[k][0]])) <= SCORE_ATOL:
+                            ie[j] = 0
+                            ties += 1
+                ae = np.array([abs(float(score_all[k]) - cpu_results[k][1]) for k in ks])
+                # excess over the parity bound |d| <= 1e-4*score + 2.5e-7 (tests/test_gpu_parity.py); <= 1 passes
+                se = np.array([abs(float(score_all[k]) - cpu_results[k][1]) / (SCORE_RTOL * abs(cpu_results[k][1]) + SCORE_ATOL)
+                               for k in ks])
+                parity.update(max_idx_err_vs_oracle_sample=int(ie.max()),
+                              max_score_err_over_tolerance_vs_oracle_sample=float(se.max()),
+                              max_abs_score_err_vs_oracle_sample=float(ae.max()),
+                              oracle_sample_hard_searches=int(sum(1 for k in ks if hard_mask[k])),
+                              oracle_sample_exact_ties_at_another_index=ties)
+                if diag_ps is not None:
+                    fl = diag_ps["flagged_per_search"]
+                    parity["oracle_sample_flagged_searches"] = int(sum(1 for k in ks if fl[k]))
+                    parity["flagged_searches_not_in_oracle_sample"] = int(sum(1 for k in np.nonzero(fl)[0]
+                                                                              if int(k) not in cpu_results))
+                real = {k: r[3] for k, r in cpu_results.items() if r[3] is not None}
+                if real:
+                    import cv2
+                    gi = np.array([abs(int(idx_all[k]) - r[0]) for k, r in real.items()])
+                    gs = np.array([abs(float(score_all[k]) - r[1]) / (SCORE_RTOL * abs(r[1]) + SCORE_ATOL)
+                                   for k, r in real.items()])
+                    oi = np.array([abs(cpu_results[k][0] - r[0]) for k, r in real.items()])
+                    parity["cv2"] = {"available": True, "version": cv2.__version__, "searches": len(real),
+                                     "max_idx_err_gpu_vs_cv2": int(gi.max()),
+                                     "max_score_err_over_tolerance_gpu_vs_cv2": float(gs.max()),
+                                     "max_idx_err_oracle_vs_cv2": int(oi.max())}
+                else:
+                    parity["cv2"] = {"available": False,
+                                     "note": "`import cv2` fails on this machine: parity is against the oracle's restatement"}
+            flops_launch = batch.flops
+            if dry:
+                roofline = {"bound": "hbm", "achieved": None, "peak": PEAK_HBM_GBPS, "unit": "GB/s", "frac": None,
+                            "traffic": None, "note": "dry run: nothing was computed"}
+            elif args.path == "fft":
+                # Since round 5 no single kernel dominates the step (three stages of a quarter each, none of which moves the searches'
+                # own bytes: they multiply, bound and transform spectra): the roofline figure is the WHOLE STEP's -- the algorithmic
+                # bytes of one launch of the hot path over the HIP-event time of all its kernels --, the stage with the largest
+                # HIP-event time is reported beside it with its own share and its own measured HBM traffic.
+                stages = {n: float(v) for n, v in zip(_native.STAGE_NAMES, stage_ms)}
+                dom = max(stages, key=stages.get)
+                dom_ms = stages[dom]
+                kname = _native.STAGE_KERNELS[dom]
+                achieved = batch.algorithmic_bytes / (kernel_ms * 1e-3) / 1e9
+                # HBM bytes per step of every kernel from the committed rocprofv3 PMC passes of this very workload
+                # (profiles/pmc_traffic.json, made by tools/make_pmc_traffic.py).  The entry records the digest of the
+                # kernel sources it was measured on: a different digest means the kernels changed since -> null.
+                traffic, dom_traffic_bytes, step_traffic, traffic_note = None, None, None, "no PMC entry for this workload"
+                wl_key = "config%d/fft/%s/%d/w%g/m%g/n%d" % (args.config, args.sample_type, n_total, cfg["window"],
+                                                            cfg["minutes"], world)
+                if args.method != "sqdiff_normed":
+                    wl_key += "/" + args.method
+                if args.hard_frac > 0 or args.offset != 7.25:
+                    wl_key += "/hard%g/off%g" % (args.hard_frac, args.offset)
+                if args.snr != 20.0 or args.unrelated:
+                    wl_key += "/snr%g%s" % (args.snr, "/unrelated" if args.unrelated else "")
+                if args.source != "noise":
+                    wl_key += "/source-" + args.source
+                if args.exclusion not in (None, "auto"):
+                    wl_key += "/exclusion-" + args.exclusion
+                digest = kernel_source_digest()
+                per_kernel = None
+                try:
+                    with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as f:
+                        entry = json.load(f)[wl_key]
+                    if os.environ.get("SUSHI_HIP_LIB"):
+                        traffic_note = "SUSHI_HIP_LIB names another build of the library: the committed PMC passes are not of it"
+                    elif entry.get("kernel_source_digest") != digest:
+                        traffic_note = "stale: PMC passes were taken on kernel sources %s, this is %s" % (
+                            entry.get("kernel_source_digest"), digest)
+                    else:
+                        step_traffic = float(sum(k["fetch_bytes"] + k["write_bytes"] for k in entry["kernels"].values()))
+                        traffic = step_traffic / (kernel_ms * 1e-3) / 1e9
+                        kerns = [entry["kernels"][kn] for kn in _native.STAGE_KERNEL_SETS[dom] if kn in entry["kernels"]]
+                        dom_traffic_bytes = float(sum(kk["fetch_bytes"] + kk["write_bytes"] for kk in kerns)) if kerns else None
+                        per_kernel = {kn: {"read": kk["fetch_bytes"], "written": kk["write_bytes"]} for kn, kk in sorted(entry["kernels"].items())}
+                        traffic_note = "%s @ %s" % (entry.get("source"), entry.get("source_commit"))
+                        # where a kernel's write bytes are not a WRITE_SIZE pass (tools/make_pmc_traffic.py), say what they are
+                        others = sorted(set(k.get("write_source", "WRITE_SIZE") for k in entry["kernels"].values()) - {"WRITE_SIZE"})
+                        if others:
+                            traffic_note += "; reads: FETCH_SIZE; writes: " + " / ".join(others)
+                except Exception:
+                    pass
+                roofline = {"bound": "hbm", "achieved": achieved, "peak": PEAK_HBM_GBPS, "unit": "GB/s",
+                            "frac": achieved / PEAK_HBM_GBPS, "traffic": traffic,
+                            "basis": "whole step: algorithmic bytes of one launch of the hot path / HIP-event time of all its kernels; "
+                                     "`traffic` = PMC bytes (FETCH_SIZE x 2 + WRITE_SIZE, all kernels of a step) / the same time",
+                            "kernel": "all kernels of one sushi_hip_batch_run", "kernel_ms": kernel_ms,
+                            "step_traffic_bytes": step_traffic,
+                            "step_traffic_over_algorithmic": None if step_traffic is None else
+                            step_traffic / batch.algorithmic_bytes,
+                            "traffic_bytes_per_kernel_per_step": per_kernel,
+                            # (on lanes the stages of different sub-batches run side by side: their HIP-event times add up to more than
+                            # the step, so a stage's share is its share of their SUM)
+                            "dominant_stage": {"stage": dom, "kernels": kname, "ms": dom_ms,
+                                               "share_of_step": dom_ms / max(sum(stages.values()), kernel_ms),
+                                               "traffic_bytes_per_step": dom_traffic_bytes,
+                                               "traffic_GBps": None if dom_traffic_bytes is None else dom_traffic_bytes / (dom_ms * 1e-3) / 1e9},
+                            "traffic_key": wl_key, "traffic_source": traffic_note,
+                            "kernel_source_digest": digest,
+                            # the binary that actually ran (the digest above is of the sources on disk)
+                            "library": loaded_library(),
+                            "launches_per_step": batch.sub_batches,
+                            "sub_batches": batch.sub_batches, "lanes": batch.lanes,
+                            "stage_ms": stages,
+                            "stage_ms_basis": "HIP events on the stream each sub-batch runs on, summed over the sub-batches" + (
+                                " -- which run side by side on %d HIP streams (lanes): the stages add up to more than the step; "
+                                "SUSHI_HIP_LANES=1:1 gives the one-after-the-other times" % batch.lanes if batch.lanes > 1 else ""),
+                            "step_kernels_ms": kernel_ms,
+                            "step_hbm_achieved_GBps": achieved,
+                            "step_frac": achieved / PEAK_HBM_GBPS,
+                            "algorithmic_bytes_per_launch": batch.algorithmic_bytes,
+                            "direct_form_flop_per_launch": flops_launch,
+                            "direct_form_equivalent_TFLOPs": flops_launch / (kernel_ms * 1e-3) / 1e12,
+                            "fft_pairs": batch.fft_pairs, "fft_segments": batch.fft_segs,
+                            "workspace_bytes": batch.ws_bytes, "delta": batch.delta,
+                            "diagnostics": batch.diagnostics(),
+                            # what a bare streaming kernel reaches on this part (tools/ubench/hbm_bw.hip,
+                            # profiles/r01/hbm_bw.jsonl): the practical ceiling under the 8 TB/s peak
+                            "stream_ceiling_GBps": {"read": 6300.0, "write": 5300.0, "copy": 5500.0}}
+            else:
+                achieved = flops_launch / (kernel_ms * 1e-3) / 1e12
+                hbm_achieved = batch.algorithmic_bytes / (kernel_ms * 1e-3) / 1e9
+                roofline = {"bound": "mfma", "achieved": achieved, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
+                            "frac": achieved / PEAK_F32_MFMA_TFLOPS, "traffic": None,
+                            "kernel": "match_sqdiff_f32_kernel", "kernel_ms": kernel_ms,
+                            "algorithmic_flop_per_launch": flops_launch,
+                            "algorithmic_bytes_per_launch": batch.algorithmic_bytes,
+                            "hbm_achieved_GBps": hbm_achieved, "hbm_frac": hbm_achieved / PEAK_HBM_GBPS}
+            out.update({
+                "roofline": roofline,
+                "cpu_baseline": cpu,
+                "parity": parity,
+                # `value` is a RESIDENT-STATE rate (streams, spectra, plan and workspace in HBM, the same job every step).  What a
+                # one-shot job -- sushi.py:663-672: two WavStream loads, then one calculate_shifts pass -- gets from this process:
+                # events / (set-up + one step), with the process's start-up behind it -- and with the start-up on the critical path
+                # (its ONE step is the batch's first run -- the exclusion's form is voted on, nothing is warm --: `first_step_ms`, wall
+                # clock around the untimed verification pass; until round 6's last day these two figures took a steady-state step instead,
+                # which a first run was 9 - 13 ms away from: the vote's same-address atomics, the lanes' streams made inside the run)
+                "first_step_ms": first_step_ms,
+                "one_shot_events_per_s": None if not setup_ms else n_total / ((sum(setup_ms.values()) + first_step_ms) * 1e-3),
+                "one_shot_incl_process_start_events_per_s": None if not setup_ms else
+                    n_total / ((process_start_ms + sum(setup_ms.values()) + first_step_ms) * 1e-3),
+                "one_shot_with_a_steady_state_step_events_per_s": None if not setup_ms else
+                    n_total / ((sum(setup_ms.values()) + elapsed / args.steps * 1e3) * 1e-3),
+            })
         if dry:
             out["dry_run"] = "control flow only (--dry-backend %s): `value` is not a measurement" % args.dry_backend
         if per_rank is not None:

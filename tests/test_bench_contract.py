@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_roofline_and_cpu_baseline():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full",
            "--config", "1", "--events", "24", "--minutes", "3", "--window", "10", "--cpu-sample", "8"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -41,6 +41,73 @@ def test_bench_prints_one_json_line_with_roofline_and_cpu_baseline():
     # `value` is a resident-state rate; the line also says what a one-shot job gets (set-up + one step)
     assert 0 < d["one_shot_events_per_s"] < d["value"] and sum(d["setup_ms"].values()) > 0
     assert "custom" in d["config"]["workload"]
+
+
+SMALL = ["--config", "1", "--events", "24", "--minutes", "3", "--window", "10"]
+FULL_ONLY = ("roofline", "cpu_baseline", "parity", "first_step_ms", "one_shot_events_per_s", "shard_emulation")
+
+
+def _line(cmd):
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1                                        # exactly one line on stdout
+    return json.loads(lines[0])
+
+
+def _check_plain_line(d, steps, warmup, events):
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert key in d, key
+    assert d["steps"] == steps and d["warmup"] == warmup
+    assert d["unit"] == "events/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] > 0 and abs(d["value"] - events * 1000.0 / d["ms_per_step"]) <= 0.02 * d["value"]
+    for key in FULL_ONLY:                                         # a plain run measures the headline only
+        assert key not in d, key
+
+
+def _dumped(directory, events):
+    import numpy as np
+    idx, score = np.load(os.path.join(directory, "index.npy")), np.load(os.path.join(directory, "score.npy"))
+    assert idx.shape == (events,) and idx.dtype == np.float64 and (idx == np.round(idx)).all() and (idx >= 0).all()
+    assert score.shape == (events,) and score.dtype in (np.float32, np.float64)
+    assert sorted(os.listdir(directory)) == ["index.npy", "score.npy"]
+    return idx, score
+
+
+def test_plain_dry_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """No GPU: the stand-in batch answers the planted positions.  A plain run prints the headline without the --full fields,
+    honours --steps, and --dump-outputs writes what the last timed step returned."""
+    import numpy as np
+    dump = str(tmp_path / "out")
+    d = _line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+               "--dry-backend", "gloo", "--dump-outputs", dump] + SMALL)
+    _check_plain_line(d, 3, 1, 24)
+    idx, score = _dumped(dump, 24)
+    assert (score == 0).all()                                     # the stand-in's scores
+    # --full over the same arguments: the same inputs, the same answers -- and the planted offset checks out on them
+    dump2 = str(tmp_path / "out_full")
+    d2 = _line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0",
+                "--dry-backend", "gloo", "--full", "--dump-outputs", dump2] + SMALL)
+    assert d2["steps"] == 2 and d2["parity"]["max_shift_err_samples_vs_planted"] <= 1.0
+    assert np.array_equal(_dumped(dump2, 24)[0], idx)
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_its_outputs_equal_the_full_runs(tmp_path):
+    """On the GPU: a plain run is the headline alone; what it dumps is what a --full run of the same arguments (verification
+    pass, oracle sample and all) computes."""
+    import numpy as np
+    dump = str(tmp_path / "plain")
+    d = _line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+               "--dump-outputs", dump] + SMALL)
+    _check_plain_line(d, 3, 1, 24)
+    idx, score = _dumped(dump, 24)
+    dump2 = str(tmp_path / "full")
+    d2 = _line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full",
+                "--cpu-sample", "8", "--no-cpu-baseline", "--emulate-shards", "0", "--dump-outputs", dump2] + SMALL)
+    assert d2["parity"]["max_shift_err_samples_vs_planted"] <= 1.0 and d2["parity"]["max_idx_err_vs_oracle_sample"] == 0
+    idx2, score2 = _dumped(dump2, 24)
+    assert np.array_equal(idx, idx2) and np.array_equal(score, score2)
 
 
 def test_bench_default_workload_is_the_north_star_configuration():

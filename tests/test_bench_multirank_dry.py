@@ -21,7 +21,7 @@ def _free_port():
 def _run(nproc, extra=()):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(nproc), "--steps", "2", "--warmup", "1", "--dry-backend", "gloo",
+           "--gpus", str(nproc), "--steps", "2", "--warmup", "1", "--dry-backend", "gloo", "--full",
            "--config", "1", "--events", "25", "--minutes", "3", "--window", "10"] + list(extra)
     env = dict(os.environ, OMP_NUM_THREADS="1")
     return subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 export SUSHI_BENCH_CACHE=/tmp/sushi_bench_cache
 run_wl() {
   name=$1; key=$2; args=$3; steps=${4:-5}
-  B="python bench.py --steps $steps --warmup 1 --profile-only --emulate-shards 0 $args"            # (no forked oracle workers under the profiler)
+  B="python bench.py --full --steps $steps --warmup 1 --profile-only --emulate-shards 0 $args"            # (no forked oracle workers under the profiler)
   timeout 400 $B > $O/warm_$name.json 2> $O/warm_$name.err            # builds the stream cache
   rm -rf gpurun_out/prof_*
   timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_kt -o kt -- $B > $O/kt_$name.log 2>&1
@@ -30,9 +30,9 @@ for w in "${W[@]}"; do
   name=$(echo "$w" | cut -d: -f1); key=$(echo "$w" | cut -d: -f2); args=$(echo "$w" | cut -d: -f3-)
   run_wl "$name" "$key" "$args"
   case "$name" in
-    cfg2) timeout 400 python bench.py --steps 20 --warmup 5 > $O/bench_${name}_n1.json 2> $O/bench_${name}_n1.err ;;
-    cfg4) timeout 900 python bench.py --steps 5 --warmup 2 $args --cpu-sample 256 --emulate-shards 0 > $O/bench_${name}_n1.json 2> $O/bench_${name}_n1.err ;;
-    *) timeout 400 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --emulate-shards 0 $args > $O/bench_${name}_n1.json 2> $O/bench_${name}_n1.err ;;
+    cfg2) timeout 400 python bench.py --full --steps 20 --warmup 5 > $O/bench_${name}_n1.json 2> $O/bench_${name}_n1.err ;;
+    cfg4) timeout 900 python bench.py --full --steps 5 --warmup 2 $args --cpu-sample 256 --emulate-shards 0 > $O/bench_${name}_n1.json 2> $O/bench_${name}_n1.err ;;
+    *) timeout 400 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --emulate-shards 0 $args > $O/bench_${name}_n1.json 2> $O/bench_${name}_n1.err ;;
   esac
 done
 # bench lines without counter passes: the source's noise level, unrelated audio, the forms of the exclusion side by side
@@ -40,9 +40,9 @@ IFS='|' read -ra X <<< "$EXTRA"
 for w in "${X[@]}"; do
   name=$(echo "$w" | cut -d: -f1); args=$(echo "$w" | cut -d: -f2-)
   case "$name" in
-    lanes1*) SUSHI_HIP_LANES=1:1 timeout 400 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --emulate-shards 0 --cpu-sample 128 $args > $O/bench_${name}_n1.json 2> $O/bench_${name}_n1.err ;;
-    stat*) SUSHI_HIP_BOUND_MODEL=statistical timeout 400 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --emulate-shards 0 --cpu-sample 128 $args > $O/bench_${name}_n1.json 2> $O/bench_${name}_n1.err ;;
-    *) timeout 400 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --emulate-shards 0 --cpu-sample 128 $args > $O/bench_${name}_n1.json 2> $O/bench_${name}_n1.err ;;
+    lanes1*) SUSHI_HIP_LANES=1:1 timeout 400 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --emulate-shards 0 --cpu-sample 128 $args > $O/bench_${name}_n1.json 2> $O/bench_${name}_n1.err ;;
+    stat*) SUSHI_HIP_BOUND_MODEL=statistical timeout 400 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --emulate-shards 0 --cpu-sample 128 $args > $O/bench_${name}_n1.json 2> $O/bench_${name}_n1.err ;;
+    *) timeout 400 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --emulate-shards 0 --cpu-sample 128 $args > $O/bench_${name}_n1.json 2> $O/bench_${name}_n1.err ;;
   esac
 done
 cp profiles/pmc_traffic.json $O/pmc_traffic.json
