@@ -138,46 +138,51 @@ static LanePool g_lane_pool;
 
 // The opaque batch handle of the C ABI.
 struct SushiHipBatch {
-    const SushiHipStream* dst;
-    const SushiHipStream* src;
-    int n, path, variant, method, exclusion;
-    int band;                           // the exclusion's form in AUTO / ALWAYS: -1 not decided yet, 0 whole rows (bound_kernel), 1 band-split
-    int band_decided_method;            // ... which was decided for this method (the pattern spectra differ)
-    int band_votes[2];                  // what the decision was taken from: pairs looked at, pairs whose bound leaves room
-    unsigned run_seq;                   // runs so far: rotates which excluded pairs are audited
-    int audit_every;                    // one search in this many has one excluded pair transformed as a check, per run
-    int bound_model;                    // SUSHI_HIP_BOUND_WORST_CASE (default) / _STATISTICAL: how the excluded side's roundings enter slb
-    int last_band;                      // form of the exclusion the last run used (its last sub-batch that went through it; -1: none did)
-    bool last_whole_cut;                // the last run took the plan's one-sub-batch cut (Plan::subs_whole)
+    const SushiHipStream* dst = nullptr;
+    const SushiHipStream* src = nullptr;
+    int n = 0, path = 0, variant = 0, method = SUSHI_HIP_METHOD_SQDIFF_NORMED, exclusion = SUSHI_HIP_EXCLUDE_AUTO;
+    int band = -1;                      // the exclusion's form in AUTO / ALWAYS: -1 not decided yet, 0 whole rows (bound_kernel), 1 band-split
+    int band_decided_method = -1;       // ... which was decided for this method (the pattern spectra differ)
+    int band_votes[2] = {0, 0};         // what the decision was taken from: pairs looked at, pairs whose bound leaves room
+    unsigned run_seq = 0;               // runs so far: rotates which excluded pairs are audited
+    int audit_every = 2;                // one search in this many has one excluded pair transformed as a check, per run
+    int bound_model = SUSHI_HIP_BOUND_WORST_CASE;   // (default) / SUSHI_HIP_BOUND_STATISTICAL: how the excluded side's roundings enter slb
+    int last_band = -1;                 // form of the exclusion the last run used (its last sub-batch that went through it; -1: none did)
+    bool last_whole_cut = false;        // the last run took the plan's one-sub-batch cut (Plan::subs_whole)
     // AUTO learns from its own runs: a batch whose exclusion excluded next to nothing (searches without a match anywhere) runs
     // without it from then on, looking again every 64th run.  The last run's counts come back through 16 bytes of pinned host memory
     // behind an event that is only ever QUERIED: a run never waits for an earlier one.
-    unsigned long long* host_stats;     // [2] pairs transformed, excluded pairs audited
-    hipEvent_t stats_ready;
-    bool stats_pending;
-    unsigned long long last_transformed; // pairs the last finished run transformed (0: not known): sizes the next run's one-workgroup-per-slot launch
-    int suspended;                      // 1: the exclusion is left out (AUTO)
-    unsigned suspended_at;              // run_seq of the run that showed it
-    int last_suspended;                 // whether the last run was one of those
-    int32_t* packed_out;                // NULL, or where every run ALSO leaves its results as 8-byte (index, score bits) records
-    int32_t* early_out;                 // NULL, or sushi_hip_batch_set_early_output's 16-byte records (memory host and device both touch)
-    int64_t n_tiles;
-    int64_t direct_pairs;               // pairs of the last run's sub-batches that were transformed without the exclusion
+    unsigned long long* host_stats = nullptr;   // [2] pairs transformed, excluded pairs audited
+    hipEvent_t stats_ready = nullptr;
+    bool stats_pending = false;
+    unsigned long long last_transformed = 0;    // pairs the last finished run transformed (0: not known): sizes the next run's one-workgroup-per-slot launch
+    int suspended = 0;                  // 1: the exclusion is left out (AUTO)
+    unsigned suspended_at = 0;          // run_seq of the run that showed it
+    int last_suspended = 0;             // whether the last run was one of those
+    int32_t* packed_out = nullptr;      // NULL, or where every run ALSO leaves its results as 8-byte (index, score bits) records
+    int32_t* early_out = nullptr;       // NULL, or sushi_hip_batch_set_early_output's 16-byte records (memory host and device both touch)
+    int64_t n_tiles = 0;
+    int64_t direct_pairs = 0;           // pairs of the last run's sub-batches that were transformed without the exclusion
     std::vector<SearchDesc> descs;
     Plan plan;
-    BatchLayout lay;
+    BatchLayout lay = {};
     std::vector<char> upload;           // descriptors | schedule | work items as they lie in `mem`: one copy per (re)plan
-    size_t mem_bytes, ws_cap;           // what the caller gave: a re-plan (sushi_hip_batch_reset) must fit it
-    char* mem;
-    double flops, algorithmic_bytes;
-    hipStream_t last_stream;
-    bool ran;
-    hipEvent_t uploaded;                // recorded on the create-time stream behind the descriptor / plan uploads
+    size_t mem_bytes = 0, ws_cap = 0;   // what the caller gave: a re-plan (sushi_hip_batch_reset) must fit it
+    char* mem = nullptr;
+    double flops = 0.0, algorithmic_bytes = 0.0;
+    hipStream_t last_stream = nullptr;
+    bool ran = false;
+    hipEvent_t uploaded = nullptr;      // recorded on the create-time stream behind the descriptor / plan uploads
     // lanes (sushi_fft_plan.inc): lane 0 is the stream a run is given; the others are the batch's own, forked off it behind the
     // run's first launch and joined before its last
-    hipStream_t lane_stream[MAX_LANES];
-    hipEvent_t lane_done[MAX_LANES];
-    hipEvent_t fork;
+    hipStream_t lane_stream[MAX_LANES] = {};
+    hipEvent_t lane_done[MAX_LANES] = {};
+    hipEvent_t fork = nullptr;
+    // what the batch has learnt about its searches (a new plan: about other searches now)
+    void forget_learnt() {
+        band = -1; last_band = -1; band_decided_method = -1; band_votes[0] = band_votes[1] = 0;
+        suspended = 0; suspended_at = 0; last_suspended = 0; last_transformed = 0; ran = false; direct_pairs = 0;
+    }
     ~SushiHipBatch() {
         for (int l = 1; l < MAX_LANES; ++l) {
             if (lane_stream[l]) (void)hipStreamSynchronize(lane_stream[l]);          // (the pool's: this batch's work on it has to be through)
@@ -190,6 +195,388 @@ struct SushiHipBatch {
         g_host_slots.give(host_stats);
     }
 };
+
+static SubView last_sub(const SushiHipBatch* b) {                // (of the last run)
+    const std::vector<SubBatch>& subs = b->last_whole_cut ? b->plan.subs_whole : b->plan.subs;
+    return SubView(b->mem, b->lay, b->plan.ws_lane, subs.back(), subs.size() - 1);
+}
+
+// What the stages of one run read besides their sub-batch: the batch, its streams and device memory, the run's own settings.
+struct RunCtx {
+    SushiHipBatch* b;
+    const SushiHipStream *dst, *src;
+    StreamRefs r;
+    const SearchDesc* searches;         // every search of the batch
+    unsigned long long *keys, *gkeys;   // [searches] each: result keys, running thresholds
+    int *flags, *flag_list, *viol;
+    RunCounters* counters;
+    double delta;
+    int method, lanes = 1;
+    unsigned run_seq = 0;
+    ProfCall* pc = nullptr;
+    bool suspended = false, cand_filled = false, excluded_any = false;     // (cand_filled: the run's first launch cleared the candidate rows)
+    RunCtx(SushiHipBatch* bb, double d) : b(bb), dst(bb->dst), src(bb->src), delta(d), method(bb->method) {
+        r = StreamRefs{dst->xc, dst->s1, dst->s2, dst->n, src->xc, src->s1, src->s2, src->n, sushi_hip_centre(dst->dtype), dst->raw, src->raw,
+                       dst->dtype};
+        searches = (const SearchDesc*)(b->mem + b->lay.desc); keys = (unsigned long long*)(b->mem + b->lay.keys); gkeys = keys + b->n;
+        flags = (int*)(b->mem + b->lay.flags); flag_list = (int*)(b->mem + b->lay.flag_list); viol = (int*)(b->mem + b->lay.viol);
+        counters = (RunCounters*)(b->mem + b->lay.counters);
+    }
+};
+
+// The lanes of one run: the batch's own streams start behind the run's first launches; join() puts the stream the run was given
+// behind them again, and the destructor does so on every exit before that.
+struct Lanes {
+    SushiHipBatch* b;
+    hipStream_t st[MAX_LANES];
+    int forked = 1;                     // lanes 1 .. forked - 1 wait for the fork
+    Lanes(SushiHipBatch* bb, hipStream_t st0) : b(bb) { for (hipStream_t& s : st) s = st0; }
+    ~Lanes() { (void)join(); }
+    int fork(int lanes) {
+        if (lanes < 2) return SUSHI_HIP_OK;
+        if ((!b->fork && hipEventCreateWithFlags(&b->fork, hipEventDisableTiming) != hipSuccess) || hipEventRecord(b->fork, st[0]) != hipSuccess)
+            return SUSHI_HIP_ELAUNCH;
+        for (int l = 1; l < lanes; ++l) {
+            // (stream priorities for the lanes -- the batch's own below the caller's, above it, one of each -- and an occupancy cap on
+            // mac_kernel<1024> were measured flat: 8.31 - 8.55 ms whatever the setting, tools/experiments/README.md)
+            if (!b->lane_stream[l] && !(b->lane_stream[l] = g_lane_pool.get(l))) return SUSHI_HIP_ELAUNCH;
+            if (!b->lane_done[l] && hipEventCreateWithFlags(&b->lane_done[l], hipEventDisableTiming) != hipSuccess) return SUSHI_HIP_ELAUNCH;
+            if (hipStreamWaitEvent(b->lane_stream[l], b->fork, 0) != hipSuccess) return SUSHI_HIP_ELAUNCH;
+            st[l] = b->lane_stream[l];
+            forked = l + 1;
+        }
+        return SUSHI_HIP_OK;
+    }
+    int join() {
+        int rc = SUSHI_HIP_OK;
+        for (int l = 1; l < forked; ++l)
+            if (hipEventRecord(b->lane_done[l], st[l]) != hipSuccess || hipStreamWaitEvent(st[0], b->lane_done[l], 0) != hipSuccess) rc = SUSHI_HIP_ELAUNCH;
+        forked = 1;
+        return rc;
+    }
+};
+
+// How this run goes, from what the runs before it left: whether AUTO leaves the exclusion out, which cut of the plan it takes, on
+// how many lanes.
+struct RunForm { bool suspended; const std::vector<SubBatch>* subs; int lanes; };
+static int run_form(SushiHipBatch* b, unsigned run_seq, hipStream_t st0, RunForm* f) {
+    if (b->stats_pending && hipEventQuery(b->stats_ready) == hipSuccess) {
+        b->stats_pending = false;
+        const unsigned long long left = b->host_stats[0] - b->host_stats[1];
+        b->last_transformed = b->host_stats[0];
+        if (b->exclusion == SUSHI_HIP_EXCLUDE_AUTO) {
+            // (three quarters: a batch HALF of whose searches find nothing -- a dub -- still gains from the exclusion on the other half)
+            if ((double)left > 0.75 * (double)b->plan.pairs) { if (!b->suspended) b->suspended_at = run_seq; b->suspended = 1; }
+            else b->suspended = 0;
+        }
+    }
+    // (suspended: every 64th run looks again)
+    f->suspended = b->exclusion == SUSHI_HIP_EXCLUDE_AUTO && b->suspended && ((run_seq - b->suspended_at) & 63u) != 63u;
+    b->last_suspended = f->suspended ? 1 : 0;
+    // The lanes: the batch's own streams start behind the fill, the caller's stream goes on behind them (Lanes).  Side by side pays
+    // where the stages differ in what bounds them -- the band-split form; whole rows for every pair (the whole-row form, no
+    // exclusion at all) are HBM traffic from the first kernel to the last and only contend: those runs keep their sub-batches on
+    // the caller's stream, one after the other (measured at BASELINE configs[2]: unrelated audio 25.1 ms on one stream, 26.8 side by side).
+    const bool whole_rows_throughout = f->suspended || b->exclusion == SUSHI_HIP_EXCLUDE_NEVER || b->exclusion == SUSHI_HIP_EXCLUDE_WHOLE ||
+                                       ((b->exclusion == SUSHI_HIP_EXCLUDE_AUTO || b->exclusion == SUSHI_HIP_EXCLUDE_ALWAYS) && b->band == 0 &&
+                                        b->band_decided_method == b->method);
+    if (whole_rows_throughout && b->plan.whole_pending) {
+        // the first run that wants the one-sub-batch cut makes it (host) and uploads its schedule and items behind the fill
+        if (complete_whole_cut(b->descs, b->plan)) {
+            const size_t o0 = b->plan.whole_order_first, o1 = b->plan.order.size(), i0 = b->plan.whole_items_first, i1 = b->plan.items.size();
+            if (hipMemcpyAsync(b->mem + b->lay.order + o0 * sizeof(int32_t), b->plan.order.data() + o0, (o1 - o0) * sizeof(int32_t), hipMemcpyHostToDevice, st0) != hipSuccess ||
+                hipMemcpyAsync(b->mem + b->lay.items + i0 * sizeof(int32_t), b->plan.items.data() + i0, (i1 - i0) * sizeof(int32_t), hipMemcpyHostToDevice, st0) != hipSuccess)
+                return SUSHI_HIP_ELAUNCH;
+            // (the copies read the handle's own vectors: a re-plan and the destructor wait for this event before they touch them)
+            if (hipEventRecord(b->uploaded, st0) != hipSuccess) return SUSHI_HIP_ELAUNCH;
+        } else {
+            b->plan.whole_pending = false;                       // (cannot happen: the room was sized for it; the parts run one after the other then)
+        }
+    }
+    const bool whole_cut = whole_rows_throughout && !b->plan.subs_whole.empty();
+    f->subs = whole_cut ? &b->plan.subs_whole : &b->plan.subs;
+    f->lanes = whole_rows_throughout ? 1 : b->plan.lanes;
+    b->last_whole_cut = whole_cut;
+    return SUSHI_HIP_OK;
+}
+
+static int stage_tspec(const RunCtx& c, const SubView& v, hipStream_t st) {
+    hipEvent_t t0 = prof_begin(c.pc, st);
+    TspecArgs ta;
+    ta.src_raw = c.src->raw; ta.searches = c.searches + v.sb.a0; ta.n_sub = v.n_sub; ta.sub_first_seg = v.sb.first_seg;
+    ta.tspec = v.tspec; ta.sub_first_pair = v.sb.first_pair; ta.pairmap = v.pairmap; ta.tconst = v.tconst;
+    ta.src_s1 = c.src->s1; ta.src_s2 = c.src->s2; ta.centre = c.r.centre; ta.dst_stats = c.dst->stats; ta.method = c.method;
+    ta.tspec_low = v.tspec_low; ta.tnorm_rest = v.tnorm_rest;
+    if (launch_dtype(c.src->dtype, [&](auto t) {
+            hipLaunchKernelGGL(tspec_kernel<std::remove_pointer_t<decltype(t)>>, dim3((unsigned)v.sb.segs), dim3(FT), 0, st, ta); }) != SUSHI_HIP_OK)
+        return SUSHI_HIP_ELAUNCH;
+    prof_end(c.pc, t0, SUSHI_HIP_STAGE_TSPEC, st);
+    return SUSHI_HIP_OK;
+}
+
+static BoundArgs bound_args(const RunCtx& c, const SubView& v) {
+    const SushiHipStream* dst = c.dst;
+    BoundArgs ba;
+    memset(&ba, 0, sizeof(ba));
+    ba.dst_stats = dst->stats; ba.searches = c.searches + v.sb.a0; ba.sub_first_pair = v.sb.first_pair; ba.first_search = v.sb.a0; ba.dst_len = dst->n;
+    ba.pairmap = v.pairmap; ba.tconst = v.tconst; ba.ubase = dst->base; ba.sbase = dst->base + (dst->blocks + 1); ba.nb = dst->blocks;
+    ba.coarse = dst->coarse; ba.nc = dst->nc; ba.slb = v.slb; ba.n_sub = v.n_sub; ba.n_pairs = (int)v.sb.pairs; ba.plist = v.plist;
+    ba.slist = v.slist; ba.scount = v.scount; ba.order = v.order; ba.gkeys = c.gkeys; ba.pair_lb = v.pair_lb; ba.counters = c.counters; ba.acc = v.acc;
+    ba.sub_first_seg = v.sb.first_seg; ba.tnorm_rest = v.tnorm_rest; ba.znorm_rest = dst->znorm_rest; ba.norm_stride = dst->norm_stride;
+    ba.band_votes = v.votes; ba.audit_mark = v.audit_mark; ba.audit_seq = c.run_seq; ba.audit_every = c.b->audit_every;
+    // What a packed-half transform output (bound_low_kernel / bound_kernel) may be off by, in units of the largest pass-1 value:
+    // every output is a sum of 64 pass-1 values through ROUNDING LEVELS of 2^-11 each -- a level at which the partial sums hold m
+    // terms each costs 2^-11 m per value and 64 / m values meet in an output: 2^-11 64 per level whatever m.  Worst path: pass 1's
+    // own result 1, its half-precision matrix (2^-12 sqrt 2 per entry, sum |inputs| <= 4 max |output| by Parseval) 2.8, pass 2's
+    // twiddle 2 + its radix-16 butterflies 1 + 1 + 2 + 3 (h_bfly_root32: q = 0 / 8 one rounding, 4 / 12 two, others three on the
+    // e - w o side), pass 3's twiddle 2 + radix 4: 1 + 1, four levels of half-precision twiddle constants at 2^-12 each = 2:
+    // 18.8 levels = 0.59.  (Round 5's 0.29 counted 9: about right for independent roundings, not a worst case.)
+    ba.worst_case = c.b->bound_model == SUSHI_HIP_BOUND_WORST_CASE ? 1 : 0;
+    ba.half_err = ba.worst_case ? 0.6f : 0.29f;
+    return ba;
+}
+
+static int launch_slb(const RunCtx& c, const SubView& v, const BoundArgs& x, hipStream_t st) {
+    return launch_method(c.method, [&](auto m) {
+        hipLaunchKernelGGL(slb_kernel<decltype(m)::value>, dim3((unsigned)((v.sb.pairs + 3) / 4)), dim3(256), 0, st, x); });
+}
+
+// Which form of the exclusion: the band-split form multiplies, stores and transforms only the low band of
+// every spectrum and bounds the rest by the rows' norms -- a quarter of the bytes and a third of the instructions, IF the
+// streams keep most of their energy in the band (audio does; white noise does not).  Decided once per batch and method, on
+// the device's own numbers: with nothing at all from the low band, does the rest alone leave the bound room to exclude?
+// (One small kernel over the first excluded sub-batch's pairs and one 8 KB read-back, in the first run only: the one place a run
+// waits for the device.)
+static int decide_band(const RunCtx& c, const SubView& v, hipStream_t st, int* band) {
+    SushiHipBatch* b = c.b;
+    const bool chosen = b->exclusion == SUSHI_HIP_EXCLUDE_BAND || b->exclusion == SUSHI_HIP_EXCLUDE_WHOLE;   // (by the caller)
+    if (!chosen && (b->band < 0 || b->band_decided_method != b->method)) {
+        static_assert(VOTE_SLOTS * VOTE_STRIDE == 64 * 32, "ws_layout keeps room for the prediction's counters");
+        int slots[VOTE_SLOTS * VOTE_STRIDE];
+        if (hipMemsetAsync(v.votes, 0, sizeof(slots), st) != hipSuccess) return SUSHI_HIP_ELAUNCH;
+        BoundArgs bp = bound_args(c, v);
+        bp.band = 2;
+        if (launch_slb(c, v, bp, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+        if (hipMemcpyAsync(slots, v.votes, sizeof(slots), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+            return SUSHI_HIP_ELAUNCH;
+        b->band_votes[0] = b->band_votes[1] = 0;
+        for (int k = 0; k < VOTE_SLOTS; ++k) { b->band_votes[0] += slots[k * VOTE_STRIDE]; b->band_votes[1] += slots[k * VOTE_STRIDE + 1]; }
+        // (measured at BASELINE configs[2]: 97 % of the pairs vote for it at 12 dB of noise on the source -- 9.7 ms against 17.5 for
+        // the whole-row form --, 87 % at 6 dB -- 12.5 against 17.5 --, 14 % at 0 dB -- 28.7 against 18.7)
+        b->band = b->band_votes[0] > 0 && (double)b->band_votes[1] >= 0.75 * (double)b->band_votes[0] ? 1 : 0;
+        b->band_decided_method = b->method;
+    }
+    *band = b->last_band = !chosen ? b->band : b->exclusion == SUSHI_HIP_EXCLUDE_BAND ? 1 : 0;
+    return SUSHI_HIP_OK;
+}
+
+// the multiply-accumulate over ALL pairs: of the low rows (band-split form) or of whole rows; `enable`: a device flag that
+// may call the launch off (the whole-row launch queued behind the survivors' list, exclude_pairs)
+static int launch_mac(const RunCtx& c, const SubView& v, hipStream_t st, const bool low, const int* enable, const int32_t* items_of_the_launch) {
+    const SubBatch& sb = v.sb;
+    MacArgs ma;
+    ma.spec_blocks = c.dst->blocks; ma.searches = c.searches + sb.a0; ma.tconst = v.tconst; ma.sub_first_seg = sb.first_seg;
+    ma.sub_first_pair = sb.first_pair; ma.dummy = v.dummy; ma.enable = enable;
+    if (low) { ma.spec = (const uint4*)c.dst->spec_low; ma.tspec = v.tspec_low; ma.y = v.ylow; }
+    else { ma.spec = (const uint4*)c.dst->spec; ma.tspec = (const uint4*)v.tspec; ma.y = v.y; }
+    for (int kern = 0; kern < 2; ++kern) {
+        if (sb.item_count[kern] == 0) continue;
+        ma.items = items_of_the_launch + (size_t)(sb.item_first[kern] - sb.item_first[0]) * (1 + MAC_SPW);
+        ma.n_items = sb.item_count[kern];
+        const int chunks = (low ? LROWE : ROWE) / MAC_BW;
+        ma.chunk_group = std::min(sb.chunk_group[kern], chunks / 8);
+        const dim3 grid((unsigned)chunks * (unsigned)ma.n_items);
+        auto go = [&](auto row) {
+            if (kern == 0) hipLaunchKernelGGL(mac_kernel<decltype(row)::value>, grid, dim3(MAC_THREADS), 0, st, ma);
+            else hipLaunchKernelGGL(mac_long_kernel<decltype(row)::value>, grid, dim3(MAC_THREADS), 0, st, ma);
+        };
+        if (low) go(std::integral_constant<int, LROWE>()); else go(std::integral_constant<int, ROWE>());
+        if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    }
+    return SUSHI_HIP_OK;
+}
+
+// the whole rows of LISTED pairs (band-split form: nothing but the low band exists until a pair is to be transformed)
+static int launch_mac_list(const RunCtx& c, const SubView& v, hipStream_t st, const int* list, const int* count, int n_list,
+                           const int* dense_search, int long_only) {
+    MacListArgs la;
+    la.dense_search = dense_search; la.long_only = long_only;
+    la.spec = (const uint4*)c.dst->spec; la.spec_blocks = c.dst->blocks; la.tspec = (const uint4*)v.tspec; la.y = v.y;
+    la.searches = c.searches + v.sb.a0; la.tconst = v.tconst; la.pairmap = v.pairmap; la.list = list; la.count = count;
+    la.n_list = n_list; la.sub_first_seg = v.sb.first_seg; la.sub_first_pair = v.sb.first_pair;
+    const int64_t want = (int64_t)n_list * MACL_PARTS;
+    hipLaunchKernelGGL(mac_list_kernel, dim3((unsigned)std::min<int64_t>(want, 256 * 32)), dim3(MACL_THREADS), 0, st, la);
+    return launch_ok();
+}
+
+static int launch_ifft(const RunCtx& c, const IfftArgs& x, unsigned grid, hipStream_t st) {
+    const bool strided = x.count && !x.list_direct;                   // a list whose length only the device knows: a fixed grid strides over its tail
+    return launch_method(c.method, [&](auto m) {
+        if (strided) hipLaunchKernelGGL(ifft_list_kernel<decltype(m)::value>, dim3(grid), dim3(FT), 0, st, x);
+        else hipLaunchKernelGGL(ifft_kernel<decltype(m)::value>, dim3(grid), dim3(FT), 0, st, x);
+    });
+}
+
+// The exclusion: a lower bound of every pair's scores first (three of the transform's four passes, no scoring); then the most
+// promising pair of every search, which leaves the search's threshold; then whatever the bound could not exclude (header of
+// bound_kernel).  `ip` leaves with the list of those pairs, to be transformed; `t0`: the bound's profile span, ended here.
+static int exclude_pairs(const RunCtx& c, const SubView& v, hipStream_t st, const int band, IfftArgs& ip, hipEvent_t& t0) {
+    const SubBatch& sb = v.sb;
+    BoundArgs ba = bound_args(c, v);
+    ba.band = band;
+    ba.y = band ? (const uint2*)v.ylow : (const uint2*)v.y;
+    // (bound_kernel adds to the pairs' accumulators; bound_low_kernel -- a wave per pair -- stores them)
+    if (!band && hipMemsetAsync(ba.acc, 0, (size_t)sb.pairs * 2 * sizeof(float), st) != hipSuccess) return SUSHI_HIP_ELAUNCH;
+    // waves striding over the pairs: a small multiple of what is resident at the kernel's registers (four workgroups of four
+    // waves per CU, three for bound_low_kernel), fewer for a small batch.  Exactly what is resident -- persistent waves --
+    // leaves the hardware nothing to balance with: bound_low_kernel alone 2.41 - 2.44 ms at BASELINE configs[2] with 1 x,
+    // 2.36 with 2 x, 2.30 - 2.32 with 4 x and 8 x; next to other lanes' kernels 2 x is as good as it gets (8 x and more:
+    // the per-workgroup prologue shows)
+    const int per_pair = band ? 1 : 16;                  // bound_low_kernel: a wave per pair
+    const int64_t want = (sb.pairs * per_pair + BOUND_THREADS / 64 - 1) / (BOUND_THREADS / 64);
+    const unsigned grid = (unsigned)std::min<int64_t>(want, 256 * (band ? 3 * (c.lanes > 1 ? 2 : 4) : 4));
+    // (the row energies are the statistical model's: the worst case -- the default -- does without them)
+    auto go = [&](auto energies) {
+        if (band) hipLaunchKernelGGL(bound_low_kernel<decltype(energies)::value>, dim3(grid), dim3(BOUND_THREADS), 0, st, ba);
+        else hipLaunchKernelGGL(bound_kernel<decltype(energies)::value>, dim3(grid), dim3(BOUND_THREADS), 0, st, ba);
+    };
+    if (ba.worst_case) go(std::false_type()); else go(std::true_type());
+    if (launch_ok() != SUSHI_HIP_OK || launch_slb(c, v, ba, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    prof_end(c.pc, t0, SUSHI_HIP_STAGE_BOUND, st);
+    t0 = prof_begin(c.pc, st);
+    hipLaunchKernelGGL(pilot_kernel, dim3((unsigned)v.n_sub), dim3(64), 0, st, ba);
+    if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    ip.slb = ba.slb; ip.audit_mark = nullptr;              // (the pairs transformed first are nobody's excluded pairs)
+    ip.order = ba.plist; ip.count = nullptr;
+    if (band && launch_mac_list(c, v, st, ba.plist, nullptr, v.n_sub, nullptr, 0) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    if (launch_ifft(c, ip, (unsigned)v.n_sub, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    hipLaunchKernelGGL(survivor_kernel, dim3((unsigned)((sb.pairs + 255) / 256)), dim3(256), 0, st, ba);
+    if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    ip.order = ba.slist; ip.count = ba.scount; ip.audit_mark = ba.audit_mark;
+    if (!band) return SUSHI_HIP_OK;
+    // the second look at what the bound left (header of bound_low_exact_kernel): sharper bound, shorter list
+    ba.list = ba.slist; ba.list_count = ba.scount;
+    ba.list2 = v.slist2; ba.list2_count = v.scount + 5;
+    hipLaunchKernelGGL(bound_low_exact_kernel, dim3(256 * 4), dim3(BLE_T), 0, st, ba);
+    if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    if (launch_method(c.method, [&](auto m) { hipLaunchKernelGGL(slb_list_kernel<decltype(m)::value>, dim3(256 * 2), dim3(256), 0, st, ba); }) !=
+        SUSHI_HIP_OK)
+        return SUSHI_HIP_ELAUNCH;
+    hipLaunchKernelGGL(survivor2_kernel, dim3(256), dim3(256), 0, st, ba);
+    if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    ip.order = ba.list2; ip.count = ba.list2_count;
+    // whole rows of what is left: pair by pair for the searches that left few (the usual case), by the dense
+    // multiply-accumulate for the searches the bound could exclude little of (no match anywhere) -- decided per search and
+    // regrouped into items of their own, on the device (dense_search_kernel, dense_repack_kernel)
+    int* any_dense = v.scount + 4;                       // (zero since the run's first launch)
+    hipLaunchKernelGGL(dense_search_kernel, dim3((unsigned)v.n_sub), dim3(64), 0, st, ba, v.dense_search, v.scount + 6);
+    const size_t second = (size_t)(sb.item_first[1] - sb.item_first[0]) * (1 + MAC_SPW);
+    hipLaunchKernelGGL(dense_repack_kernel, dim3(2), dim3(REPACK_THREADS), 0, st, v.items, sb.item_count[0], v.items + second,
+                       sb.item_count[1], v.dense_search, v.n_sub, v.ditems, v.ditems + second, v.scount + 6, (int)(sb.pairs / 8), any_dense);
+    if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    MacRowsArgs ra;
+    ra.spec = (const uint4*)c.dst->spec; ra.spec_blocks = c.dst->blocks; ra.tspec = (const uint4*)v.tspec; ra.y = v.y;
+    ra.searches = c.searches + sb.a0; ra.tconst = v.tconst; ra.mark = ba.audit_mark; ra.n_sub = v.n_sub;
+    ra.sub_first_seg = sb.first_seg; ra.sub_first_pair = sb.first_pair; ra.dense_search = v.dense_search;
+    const int64_t rows_want = (int64_t)v.n_sub * MACL_PARTS;
+    if (sb.item_count[0] > 0) hipLaunchKernelGGL(mac_rows_kernel<0>, dim3((unsigned)std::min<int64_t>(rows_want, 256 * 32)), dim3(MACL_THREADS), 0, st, ra);
+    if (sb.item_count[1] > 0) hipLaunchKernelGGL(mac_rows_kernel<1>, dim3((unsigned)std::min<int64_t>(rows_want, 256 * 16)), dim3(MACL_THREADS), 0, st, ra);
+    if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    if (sb.long_patterns && launch_mac_list(c, v, st, ba.list2, ba.list2_count, (int)sb.pairs, v.dense_search, 1) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    return launch_mac(c, v, st, false, any_dense, v.ditems);
+}
+
+// the transform of the listed pairs
+static int transform_listed(const RunCtx& c, const SubView& v, hipStream_t st, IfftArgs ip) {
+    const SubBatch& sb = v.sb;
+    const SushiHipBatch* b = c.b;
+    // One workgroup per list slot up to what the list usually holds (an eighth of the pairs: empty slots there cost a
+    // workgroup's launch each, ~1 ns), and a fixed grid striding over whatever lies beyond: the striding form alone runs
+    // at half the rate per pair (the loop costs it registers), one workgroup per POSSIBLE slot cost 0.3 ms of empty launches.
+    // (A batch whose LAST run listed more than that -- searches without a match, a dub's own speech -- gets a workgroup per
+    // possible slot instead: 0.3 ms of empty launches at most, against half the rate on everything behind the first eighth.
+    // `ifft` took 31.6 ms at BASELINE configs[2] on a dub with TM_CCOEFF_NORMED, 160 k pairs listed: bench.py --source dub.)
+    int64_t direct64 = std::min<int64_t>(sb.pairs, std::max<int64_t>(4096, sb.pairs / 8));
+    if ((double)b->last_transformed * (double)sb.pairs > (double)direct64 * (double)b->plan.pairs) direct64 = sb.pairs;   // (this sub-batch's share of it)
+    // (nothing known yet -- a batch's first run, which is all a one-shot job has --: half of the pairs get a workgroup each;
+    // 0.15 ms of empty launches where there is a match everywhere, against half the rate on ten times as many pairs where
+    // there is not: a dub's first run 29.7 ms)
+    else if (b->last_transformed == 0) direct64 = std::min<int64_t>(sb.pairs, std::max<int64_t>(4096, sb.pairs / 2));
+    const unsigned direct = (unsigned)direct64;
+    ip.list_first = 0; ip.list_direct = 1;
+    if (launch_ifft(c, ip, direct, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    if ((int64_t)direct >= sb.pairs) return SUSHI_HIP_OK;
+    ip.list_first = (int)direct; ip.list_direct = 0;
+    return launch_ifft(c, ip, (unsigned)std::min<int64_t>(sb.pairs - direct, 1024), st);
+}
+
+static int stage_refine(const RunCtx& c, const SubView& v, hipStream_t st) {
+    hipEvent_t t0 = prof_begin(c.pc, st);
+    RefineParams rp;
+    rp.r = c.r; rp.searches = c.searches; rp.first_search = v.sb.a0; rp.n_sub = v.n_sub; rp.sub_first_pair = v.sb.first_pair;
+    rp.cand = v.cand; rp.pair_lb = v.pair_lb; rp.gkeys = c.gkeys; rp.keys = c.keys; rp.flags = c.flags; rp.flag_list = c.flag_list + v.sb.a0;
+    rp.sub = v.sub; rp.counters = c.counters; rp.delta = (float)c.delta; rp.method = c.method; rp.citems = v.citems; rp.n_citems = v.scount + 1;
+    rp.viol = c.viol; rp.early = reinterpret_cast<int4*>(c.b->early_out);
+    const int rc = launch_refine(rp, st);
+    if (rc == SUSHI_HIP_OK) prof_end(c.pc, t0, SUSHI_HIP_STAGE_REFINE, st);
+    return rc;
+}
+
+// searches the lists could not finish: collect their candidates per tile, evaluate those exactly
+// (both kernels leave after one load when nothing is flagged)
+static int stage_collect(const RunCtx& c, const SubView& v, hipStream_t st, IfftArgs ia) {
+    hipEvent_t t0 = prof_begin(c.pc, st);
+    ia.citems = v.citems; ia.n_citems = v.scount + 1;    // (refine_kernel's list: RefineParams::citems)
+    if (launch_method(c.method, [&](auto m) { hipLaunchKernelGGL(collect_kernel<decltype(m)::value>, dim3(COLLECT_GRID), dim3(FT), 0, st, ia); }) !=
+        SUSHI_HIP_OK)
+        return SUSHI_HIP_ELAUNCH;
+    TileParams tp;
+    tp.r = c.r; tp.searches = c.searches; tp.tiles = v.tiles; tp.cand = v.candbuf; tp.keys = c.keys; tp.counters = c.counters; tp.sub = v.sub; tp.method = c.method;
+    const int rc = launch_tiles(tp, st);
+    if (rc == SUSHI_HIP_OK) prof_end(c.pc, t0, SUSHI_HIP_STAGE_FINISH, st);
+    return rc;
+}
+
+// One sub-batch, its stages in order on stream `st` (the header of this file).
+static int run_sub(RunCtx& c, const SubView& v, hipStream_t st) {
+    SushiHipBatch* b = c.b;
+    const SubBatch& sb = v.sb;
+    int rc = stage_tspec(c, v, st);
+    if (rc != SUSHI_HIP_OK) return rc;
+    // The exclusion costs a pass over Y (~16 ns per pair) and half a dozen launches (~60 us); transforming a pair ~37 ns:
+    // it pays from ~3000 pairs on, plus two per search (the pairs transformed first are transformed either way).
+    const bool exclude = b->exclusion == SUSHI_HIP_EXCLUDE_ALWAYS || b->exclusion == SUSHI_HIP_EXCLUDE_BAND ||
+                         b->exclusion == SUSHI_HIP_EXCLUDE_WHOLE ||
+                         (b->exclusion == SUSHI_HIP_EXCLUDE_AUTO && !c.suspended && sb.pairs > 3000 + 2 * (int64_t)v.n_sub);
+    c.excluded_any = c.excluded_any || exclude;
+    int band = 0;
+    if (exclude && (rc = decide_band(c, v, st, &band)) != SUSHI_HIP_OK) return rc;
+    hipEvent_t t0 = prof_begin(c.pc, st);
+    if (launch_mac(c, v, st, band != 0, nullptr, v.items) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    prof_end(c.pc, t0, SUSHI_HIP_STAGE_MAC, st);
+    t0 = prof_begin(c.pc, st);
+    // the candidate rows start empty: ifft_kernel writes only the entries that exist
+    if (!c.cand_filled && hipMemsetAsync(v.cand, 0xff, (size_t)sb.pairs * FFT_ROW * sizeof(unsigned long long), st) != hipSuccess)
+        return SUSHI_HIP_ELAUNCH;
+    IfftArgs ia;
+    memset(&ia, 0, sizeof(ia));
+    ia.y = (const uint2*)v.y; ia.dst_stats = c.dst->stats; ia.searches = c.searches + sb.a0; ia.n_sub = v.n_sub; ia.first_search = sb.a0;
+    ia.sub_first_pair = sb.first_pair; ia.dst_len = c.dst->n; ia.delta = (float)c.delta; ia.cand = v.cand; ia.pair_lb = v.pair_lb; ia.gkeys = c.gkeys;
+    ia.pairmap = v.pairmap; ia.tconst = v.tconst; ia.order = v.order; ia.urel = c.dst->urel; ia.nb = c.dst->blocks; ia.ubase = c.dst->base;
+    ia.usrel = c.dst->usrel; ia.sbase = c.dst->base + (c.dst->blocks + 1); ia.flags = c.flags; ia.flag_list = c.flag_list + sb.a0; ia.sub = v.sub;
+    ia.tiles = v.tiles; ia.candbuf = v.candbuf; ia.cand_cap = (int)cand_capacity(sb.pairs); ia.counters = c.counters; ia.viol = c.viol;
+    if (!exclude) {
+        // every pair, in the L2-friendly schedule (what round 3 did for every batch)
+        if (launch_ifft(c, ia, (unsigned)sb.pairs, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+        b->direct_pairs += sb.pairs;
+    } else {
+        IfftArgs ip = ia;
+        if ((rc = exclude_pairs(c, v, st, band, ip, t0)) != SUSHI_HIP_OK || (rc = transform_listed(c, v, st, ip)) != SUSHI_HIP_OK) return rc;
+    }
+    prof_end(c.pc, t0, SUSHI_HIP_STAGE_IFFT, st);
+    if ((rc = stage_refine(c, v, st)) != SUSHI_HIP_OK) return rc;
+    return stage_collect(c, v, st, ia);
+}
 
 extern "C" {
 
@@ -234,15 +621,11 @@ int sushi_hip_stream_add_spectra(SushiHipStream* s, void* mem_dev, size_t mem_by
     const size_t rows = (size_t)s->blocks + 1;
     uint4* low = (uint4*)((char*)mem_dev + rows * ROW_BYTES);
     float* zn = (float*)((char*)mem_dev + rows * ROW_BYTES + rows * LROW_BYTES);
-    if (s->dtype == SUSHI_HIP_F32)
-        hipLaunchKernelGGL(spectra_kernel<float>, dim3((unsigned)s->blocks + 1), dim3(FT), 0, (hipStream_t)hip_stream,
-                           (const float*)s->raw, s->n, (uint32_t*)mem_dev, (const double*)s->stats, low, zn,
-                           (int64_t)(align_up(rows * sizeof(float), 256) / sizeof(float)));
-    else
-        hipLaunchKernelGGL(spectra_kernel<uint8_t>, dim3((unsigned)s->blocks + 1), dim3(FT), 0, (hipStream_t)hip_stream,
-                           (const uint8_t*)s->raw, s->n, (uint32_t*)mem_dev, (const double*)s->stats, low, zn,
-                           (int64_t)(align_up(rows * sizeof(float), 256) / sizeof(float)));
-    if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    if (launch_dtype(s->dtype, [&](auto t) {
+            using T = std::remove_pointer_t<decltype(t)>;
+            hipLaunchKernelGGL(spectra_kernel<T>, dim3((unsigned)s->blocks + 1), dim3(FT), 0, (hipStream_t)hip_stream, (const T*)s->raw, s->n,
+                               (uint32_t*)mem_dev, (const double*)s->stats, low, zn, (int64_t)(align_up(rows * sizeof(float), 256) / sizeof(float))); }) != SUSHI_HIP_OK)
+        return SUSHI_HIP_ELAUNCH;
     s->spec = mem_dev;
     s->spec_low = low;
     s->znorm_rest = zn;
@@ -326,9 +709,7 @@ static int plan_and_upload(SushiHipBatch* b, const SushiHipRequest* req_host, in
     // a run may be launched on another stream than this one: it waits for this event first
     if (!b->uploaded && hipEventCreateWithFlags(&b->uploaded, hipEventDisableTiming) != hipSuccess) return SUSHI_HIP_ELAUNCH;
     if (hipEventRecord(b->uploaded, st) != hipSuccess) return SUSHI_HIP_ELAUNCH;
-    // what the batch had learnt about its searches is about other searches now
-    b->band = -1; b->last_band = -1; b->band_decided_method = -1; b->band_votes[0] = b->band_votes[1] = 0;
-    b->suspended = 0; b->suspended_at = 0; b->last_suspended = 0; b->last_transformed = 0; b->ran = false; b->direct_pairs = 0;
+    b->forget_learnt();
     return SUSHI_HIP_OK;
 }
 
@@ -349,25 +730,13 @@ int sushi_hip_batch_create(const SushiHipStream* dst, const SushiHipStream* src,
     SushiHipBatch* b = new (std::nothrow) SushiHipBatch();
     if (!b) return SUSHI_HIP_ENOMEM;
     std::unique_ptr<SushiHipBatch> guard(b);                     // freed on every early return and on an exception
-    b->dst = dst; b->src = src; b->n = n; b->path = path; b->variant = variant; b->method = SUSHI_HIP_METHOD_SQDIFF_NORMED;
-    b->exclusion = SUSHI_HIP_EXCLUDE_AUTO;
-    b->packed_out = nullptr;
-    b->early_out = nullptr;
-    b->last_transformed = 0;
-    b->host_stats = nullptr; b->stats_ready = nullptr; b->stats_pending = false; b->suspended = 0; b->suspended_at = 0; b->last_suspended = 0;
-    b->band = -1; b->last_band = -1; b->band_decided_method = -1; b->band_votes[0] = b->band_votes[1] = 0; b->run_seq = 0; b->audit_every = 2;
-    b->bound_model = SUSHI_HIP_BOUND_WORST_CASE;
-    {
-        // (measurements only, read once per batch: 0 = no excluded pair is audited; "statistical" = round 5's error model)
-        const char* e = getenv("SUSHI_HIP_AUDIT_EVERY");
-        if (e && *e) { const int v = atoi(e); b->audit_every = v < 0 ? 0 : v; }
-        const char* m = getenv("SUSHI_HIP_BOUND_MODEL");
-        if (m && !strcmp(m, "statistical")) b->bound_model = SUSHI_HIP_BOUND_STATISTICAL;
-    }
+    b->dst = dst; b->src = src; b->n = n; b->path = path; b->variant = variant;
     b->mem = (char*)mem_dev; b->mem_bytes = mem_bytes; b->ws_cap = workspace_cap_bytes;
-    b->last_stream = nullptr; b->ran = false; b->uploaded = nullptr; b->n_tiles = 0; b->direct_pairs = 0; b->last_whole_cut = false;
-    for (int l = 0; l < MAX_LANES; ++l) { b->lane_stream[l] = nullptr; b->lane_done[l] = nullptr; }
-    b->fork = nullptr;
+    // (measurements only, read once per batch: 0 = no excluded pair is audited; "statistical" = round 5's error model)
+    const char* e = getenv("SUSHI_HIP_AUDIT_EVERY");
+    if (e && *e) { const int v = atoi(e); b->audit_every = v < 0 ? 0 : v; }
+    const char* m = getenv("SUSHI_HIP_BOUND_MODEL");
+    if (m && !strcmp(m, "statistical")) b->bound_model = SUSHI_HIP_BOUND_STATISTICAL;
     const int rc = plan_and_upload(b, req_host, n, (hipStream_t)hip_stream);
     if (rc != SUSHI_HIP_OK) return rc;
     *out = guard.release();
@@ -432,418 +801,53 @@ int sushi_hip_batch_set_bound_model(SushiHipBatch* b, int model) {
 int sushi_hip_batch_run(SushiHipBatch* b, double delta, int32_t* out_idx_dev, float* out_score_dev, void* hip_stream) try {
     if (!b || !out_idx_dev || !out_score_dev) return SUSHI_HIP_EINVAL;
     const hipStream_t st0 = (hipStream_t)hip_stream;
-    const SushiHipStream* dst = b->dst;
-    const SushiHipStream* src = b->src;
-    const int n_search = b->n;
-    StreamRefs r;
-    r.dst_xc = dst->xc; r.dst_s1 = dst->s1; r.dst_s2 = dst->s2; r.dst_len = dst->n;
-    r.src_xc = src->xc; r.src_s1 = src->s1; r.src_s2 = src->s2; r.src_len = src->n;
-    r.centre = sushi_hip_centre(dst->dtype);
-    r.dst_raw = dst->raw; r.src_raw = src->raw; r.dtype = dst->dtype;
-    const SearchDesc* searches_dev = (const SearchDesc*)(b->mem + b->lay.desc);
-    unsigned long long* keys = (unsigned long long*)(b->mem + b->lay.keys);
+    RunCtx c(b, delta);
     b->last_stream = st0; b->ran = true; b->direct_pairs = 0;
     if (hipStreamWaitEvent(st0, b->uploaded, 0) != hipSuccess) return SUSHI_HIP_ELAUNCH;   // descriptors and plan have landed
     if (b->path == SUSHI_HIP_PATH_DIRECT)
-        return launch_direct(r, searches_dev, n_search, (int)b->n_tiles, b->variant, b->method, keys, out_idx_dev,
-                             out_score_dev, b->packed_out, st0);
+        return launch_direct(c.r, c.searches, b->n, (int)b->n_tiles, b->variant, b->method, c.keys, out_idx_dev, out_score_dev, b->packed_out, st0);
 
     if (!(delta >= 3.8e-6) || delta > 1.0) return SUSHI_HIP_EINVAL;      // the floor covers the scoring arithmetic's own rounding
-    unsigned long long* gkeys = keys + n_search;
-    int* flags = (int*)(b->mem + b->lay.flags);
-    int* flag_list = (int*)(b->mem + b->lay.flag_list);
-    char* subc = b->mem + b->lay.subc;                            // SUBC_BYTES per sub-batch: SubCounters, then its scount words
-    float* tnorm_all = (float*)(b->mem + b->lay.tnorm);           // [all segments] squared norms of the pattern rows outside the band
-    RunCounters* counters = (RunCounters*)(b->mem + b->lay.counters);
-    const int32_t* order = (const int32_t*)(b->mem + b->lay.order);
-    const int32_t* items = (const int32_t*)(b->mem + b->lay.items);
-    ProfCall* pc = nullptr;
-    if (g_prof_on) { g_prof.emplace_back(); pc = &g_prof.back(); }
-    int* viol = (int*)(b->mem + b->lay.viol);
-    // Everything a run clears before its first kernel, in ONE launch: result keys (all ones), flags / violation marks / flag list /
-    // every sub-batch's small counters / the pattern rows' norm accumulators / run counters (one contiguous zero span of the batch's
-    // layout), and -- a batch of one sub-batch, while they are small -- its candidate rows.
-    bool cand_filled = false;
+    if (g_prof_on) { g_prof.emplace_back(); c.pc = &g_prof.back(); }
     {
+        // Everything a run clears before its first kernel, in ONE launch: result keys (all ones), flags / violation marks / flag list /
+        // every sub-batch's small counters / the pattern rows' norm accumulators / run counters (one contiguous zero span of the batch's
+        // layout), and -- a batch of one sub-batch, while they are small -- its candidate rows.
         FillArgs fa;
         memset(&fa, 0, sizeof(fa));
         auto add = [&](void* p, size_t bytes, uint32_t v) { fa.p[fa.n] = (uint32_t*)p; fa.words[fa.n] = (uint32_t)(bytes / 4); fa.value[fa.n] = v; ++fa.n; };
-        add(keys, (size_t)2 * n_search * sizeof(uint64_t), 0xffffffffu);
-        add(flags, b->lay.counters + align_up(sizeof(RunCounters), 256) - b->lay.flags, 0u);
+        add(c.keys, (size_t)2 * b->n * sizeof(uint64_t), 0xffffffffu);
+        add(c.flags, b->lay.counters + align_up(sizeof(RunCounters), 256) - b->lay.flags, 0u);
         if (b->plan.subs.size() == 1) {
-            const SubBatch& s0 = b->plan.subs[0];
-            const WsLayout w0 = ws_layout(s0.pairs, s0.segs, s0.b0 - s0.a0);
-            const size_t cand_bytes = (size_t)s0.pairs * FFT_ROW * sizeof(unsigned long long);
-            if (cand_bytes <= ((size_t)8 << 20)) { add(b->mem + b->lay.ws + w0.cand, cand_bytes, 0xffffffffu); cand_filled = true; }
+            const SubView v0(b->mem, b->lay, b->plan.ws_lane, b->plan.subs[0], 0);
+            const size_t cand_bytes = (size_t)v0.sb.pairs * FFT_ROW * sizeof(unsigned long long);
+            if (cand_bytes <= ((size_t)8 << 20)) { add(v0.cand, cand_bytes, 0xffffffffu); c.cand_filled = true; }
         }
         if (launch_fill(fa, st0) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     }
-    const unsigned run_seq = b->run_seq++;
-    const bool ccm = b->method == SUSHI_HIP_METHOD_CCOEFF_NORMED;
-    if (b->stats_pending && hipEventQuery(b->stats_ready) == hipSuccess) {
-        b->stats_pending = false;
-        const unsigned long long left = b->host_stats[0] - b->host_stats[1];
-        b->last_transformed = b->host_stats[0];
-        if (b->exclusion == SUSHI_HIP_EXCLUDE_AUTO) {
-            // (three quarters: a batch HALF of whose searches find nothing -- a dub -- still gains from the exclusion on the other half)
-            if ((double)left > 0.75 * (double)b->plan.pairs) { if (!b->suspended) b->suspended_at = run_seq; b->suspended = 1; }
-            else b->suspended = 0;
-        }
-    }
-    // (suspended: every 64th run looks again)
-    const bool suspended_now = b->exclusion == SUSHI_HIP_EXCLUDE_AUTO && b->suspended && ((run_seq - b->suspended_at) & 63u) != 63u;
-    b->last_suspended = suspended_now ? 1 : 0;
-    bool excluded_any = false;
-    // The lanes: the batch's own streams start behind the fill, the caller's stream goes on behind them (below).  Side by side pays
-    // where the stages differ in what bounds them -- the band-split form; whole rows for every pair (the whole-row form, no
-    // exclusion at all) are HBM traffic from the first kernel to the last and only contend: those runs keep their sub-batches on
-    // the caller's stream, one after the other (measured at BASELINE configs[2]: unrelated audio 25.1 ms on one stream, 26.8 side by side).
-    const bool whole_rows_throughout = suspended_now || b->exclusion == SUSHI_HIP_EXCLUDE_NEVER || b->exclusion == SUSHI_HIP_EXCLUDE_WHOLE ||
-                                       ((b->exclusion == SUSHI_HIP_EXCLUDE_AUTO || b->exclusion == SUSHI_HIP_EXCLUDE_ALWAYS) && b->band == 0 &&
-                                        b->band_decided_method == b->method);
-    if (whole_rows_throughout && b->plan.whole_pending) {
-        // the first run that wants the one-sub-batch cut makes it (host) and uploads its schedule and items behind the fill
-        if (complete_whole_cut(b->descs, b->plan)) {
-            const size_t o0 = b->plan.whole_order_first, o1 = b->plan.order.size(), i0 = b->plan.whole_items_first, i1 = b->plan.items.size();
-            if (hipMemcpyAsync(b->mem + b->lay.order + o0 * sizeof(int32_t), b->plan.order.data() + o0, (o1 - o0) * sizeof(int32_t), hipMemcpyHostToDevice, st0) != hipSuccess ||
-                hipMemcpyAsync(b->mem + b->lay.items + i0 * sizeof(int32_t), b->plan.items.data() + i0, (i1 - i0) * sizeof(int32_t), hipMemcpyHostToDevice, st0) != hipSuccess)
-                return SUSHI_HIP_ELAUNCH;
-            // (the copies read the handle's own vectors: a re-plan and the destructor wait for this event before they touch them)
-            if (hipEventRecord(b->uploaded, st0) != hipSuccess) return SUSHI_HIP_ELAUNCH;
-        } else {
-            b->plan.whole_pending = false;                       // (cannot happen: the room was sized for it; the parts run one after the other then)
-        }
-    }
-    const bool whole_cut = whole_rows_throughout && !b->plan.subs_whole.empty();
-    const std::vector<SubBatch>& subs = whole_cut ? b->plan.subs_whole : b->plan.subs;
-    const int lanes = whole_rows_throughout ? 1 : b->plan.lanes;
-    b->last_whole_cut = whole_cut;
-    hipStream_t lane_st[MAX_LANES] = {st0, st0, st0, st0};
-    if (lanes > 1) {
-        if (!b->fork && hipEventCreateWithFlags(&b->fork, hipEventDisableTiming) != hipSuccess) return SUSHI_HIP_ELAUNCH;
-        if (hipEventRecord(b->fork, st0) != hipSuccess) return SUSHI_HIP_ELAUNCH;
-        for (int l = 1; l < lanes; ++l) {
-            // (stream priorities for the lanes -- the batch's own below the caller's, above it, one of each -- and an occupancy cap on
-            // mac_kernel<1024> were measured flat: 8.31 - 8.55 ms whatever the setting, tools/experiments/README.md)
-            if (!b->lane_stream[l] && !(b->lane_stream[l] = g_lane_pool.get(l))) return SUSHI_HIP_ELAUNCH;
-            if (!b->lane_done[l] && hipEventCreateWithFlags(&b->lane_done[l], hipEventDisableTiming) != hipSuccess) return SUSHI_HIP_ELAUNCH;
-            if (hipStreamWaitEvent(b->lane_stream[l], b->fork, 0) != hipSuccess) return SUSHI_HIP_ELAUNCH;
-            lane_st[l] = b->lane_stream[l];
-        }
-    }
-
+    c.run_seq = b->run_seq++;
+    RunForm form;
+    int rc = run_form(b, c.run_seq, st0, &form);
+    if (rc != SUSHI_HIP_OK) return rc;
+    c.suspended = form.suspended; c.lanes = form.lanes;
+    Lanes lanes(b, st0);
+    if ((rc = lanes.fork(form.lanes)) != SUSHI_HIP_OK) return rc;
     b->last_band = -1;                                           // (the form of the last sub-batch of this run that went through the exclusion)
     // Sub-batches of a plan on lanes run side by side (sushi_fft_plan.inc "Lanes"); the others one after the other.
-    for (size_t si = 0; si < subs.size(); ++si) {
-        const SubBatch& sbt = subs[si];
-        const hipStream_t st = lane_st[sbt.lane];
-        const int n_sub = sbt.b0 - sbt.a0;
-        const WsLayout wl = ws_layout(sbt.pairs, sbt.segs, n_sub);
-        char* wsp = b->mem + b->lay.ws + (size_t)sbt.lane * b->plan.ws_lane;
-        SubCounters* subcnt = (SubCounters*)(subc + si * SUBC_BYTES);
-        uint32_t* tspec = (uint32_t*)(wsp + wl.tspec);
-        uint4* y = (uint4*)(wsp + wl.y);
-        unsigned long long* cand = (unsigned long long*)(wsp + wl.cand);
-        int* pairmap = (int*)(wsp + wl.pairmap);
-        float* pair_lb = (float*)(wsp + wl.pair_lb);
-        TemplConsts* tconst = (TemplConsts*)(wsp + wl.tconst);
-        TileDesc* tiles = (TileDesc*)(wsp + wl.tiles);
-        int32_t* candbuf = (int32_t*)(wsp + wl.candbuf);
-        uint4* tspec_low = (uint4*)(wsp + wl.tspec_low);
-        uint4* ylow = (uint4*)(wsp + wl.ylow);
-        float* tnorm_rest = tnorm_all + sbt.first_seg;
-        int* scount = (int*)subcnt + SUBC_SCOUNT;
-
-        hipEvent_t t0 = prof_begin(pc, st);
-        TspecArgs ta;
-        ta.src_raw = src->raw; ta.searches = searches_dev + sbt.a0; ta.n_sub = n_sub; ta.sub_first_seg = sbt.first_seg;
-        ta.tspec = tspec; ta.sub_first_pair = sbt.first_pair; ta.pairmap = pairmap; ta.tconst = tconst;
-        ta.src_s1 = src->s1; ta.src_s2 = src->s2; ta.centre = r.centre; ta.dst_stats = dst->stats; ta.method = b->method;
-        ta.tspec_low = tspec_low; ta.tnorm_rest = tnorm_rest;
-        if (src->dtype == SUSHI_HIP_F32) hipLaunchKernelGGL(tspec_kernel<float>, dim3((unsigned)sbt.segs), dim3(FT), 0, st, ta);
-        else hipLaunchKernelGGL(tspec_kernel<uint8_t>, dim3((unsigned)sbt.segs), dim3(FT), 0, st, ta);
-        if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-        prof_end(pc, t0, SUSHI_HIP_STAGE_TSPEC, st);
-
-        // The exclusion costs a pass over Y (~16 ns per pair) and half a dozen launches (~60 us); transforming a pair ~37 ns:
-        // it pays from ~3000 pairs on, plus two per search (the pairs transformed first are transformed either way).
-        const bool exclude = b->exclusion == SUSHI_HIP_EXCLUDE_ALWAYS || b->exclusion == SUSHI_HIP_EXCLUDE_BAND ||
-                             b->exclusion == SUSHI_HIP_EXCLUDE_WHOLE ||
-                             (b->exclusion == SUSHI_HIP_EXCLUDE_AUTO && !suspended_now && sbt.pairs > 3000 + 2 * (int64_t)n_sub);
-        excluded_any = excluded_any || exclude;
-        BoundArgs ba;
-        memset(&ba, 0, sizeof(ba));
-        ba.dst_stats = dst->stats; ba.searches = searches_dev + sbt.a0; ba.sub_first_pair = sbt.first_pair;
-        ba.first_search = sbt.a0; ba.dst_len = dst->n; ba.pairmap = pairmap; ba.tconst = tconst; ba.ubase = dst->base;
-        ba.sbase = dst->base + (dst->blocks + 1); ba.nb = dst->blocks; ba.coarse = dst->coarse; ba.nc = dst->nc;
-        ba.slb = (float*)(wsp + wl.slb); ba.n_sub = n_sub; ba.n_pairs = (int)sbt.pairs; ba.plist = (int*)(wsp + wl.plist);
-        ba.slist = (int*)(wsp + wl.slist); ba.scount = scount; ba.order = order + sbt.order_first;
-        ba.gkeys = gkeys; ba.pair_lb = pair_lb; ba.counters = counters;
-        ba.acc = (float*)(wsp + wl.acc);
-        ba.sub_first_seg = sbt.first_seg; ba.tnorm_rest = tnorm_rest; ba.znorm_rest = dst->znorm_rest; ba.norm_stride = dst->norm_stride;
-        ba.band_votes = (int*)(wsp + wl.votes);
-        ba.audit_mark = (unsigned char*)(wsp + wl.audit_mark); ba.audit_seq = run_seq; ba.audit_every = b->audit_every;
-        // What a packed-half transform output (bound_low_kernel / bound_kernel) may be off by, in units of the largest pass-1 value:
-        // every output is a sum of 64 pass-1 values through ROUNDING LEVELS of 2^-11 each -- a level at which the partial sums hold m
-        // terms each costs 2^-11 m per value and 64 / m values meet in an output: 2^-11 64 per level whatever m.  Worst path: pass 1's
-        // own result 1, its half-precision matrix (2^-12 sqrt 2 per entry, sum |inputs| <= 4 max |output| by Parseval) 2.8, pass 2's
-        // twiddle 2 + its radix-16 butterflies 1 + 1 + 2 + 3 (h_bfly_root32: q = 0 / 8 one rounding, 4 / 12 two, others three on the
-        // e - w o side), pass 3's twiddle 2 + radix 4: 1 + 1, four levels of half-precision twiddle constants at 2^-12 each = 2:
-        // 18.8 levels = 0.59.  (Round 5's 0.29 counted 9: about right for independent roundings, not a worst case.)
-        ba.worst_case = b->bound_model == SUSHI_HIP_BOUND_WORST_CASE ? 1 : 0;
-        ba.half_err = ba.worst_case ? 0.6f : 0.29f;
-        auto launch_slb = [&](const BoundArgs& x) {
-            if (ccm) hipLaunchKernelGGL(slb_kernel<SUSHI_HIP_METHOD_CCOEFF_NORMED>, dim3((unsigned)((sbt.pairs + 3) / 4)), dim3(256), 0, st, x);
-            else hipLaunchKernelGGL(slb_kernel<SUSHI_HIP_METHOD_SQDIFF_NORMED>, dim3((unsigned)((sbt.pairs + 3) / 4)), dim3(256), 0, st, x);
-            return launch_ok();
-        };
-
-        // Which form of the exclusion: the band-split form multiplies, stores and transforms only the low band of
-        // every spectrum and bounds the rest by the rows' norms -- a quarter of the bytes and a third of the instructions, IF the
-        // streams keep most of their energy in the band (audio does; white noise does not).  Decided once per batch and method, on
-        // the device's own numbers: with nothing at all from the low band, does the rest alone leave the bound room to exclude?
-        // (One small kernel over the first excluded sub-batch's pairs and one 8 KB read-back, in the first run only.)
-        int band = 0;
-        if (exclude) {
-            if (b->exclusion == SUSHI_HIP_EXCLUDE_BAND) band = 1;
-            else if (b->exclusion == SUSHI_HIP_EXCLUDE_WHOLE) band = 0;
-            else {
-                if (b->band < 0 || b->band_decided_method != b->method) {
-                    static_assert(VOTE_SLOTS * VOTE_STRIDE == 64 * 32, "ws_layout keeps room for the prediction's counters");
-                    int slots[VOTE_SLOTS * VOTE_STRIDE];
-                    if (hipMemsetAsync(ba.band_votes, 0, sizeof(slots), st) != hipSuccess) return SUSHI_HIP_ELAUNCH;
-                    BoundArgs bp = ba;
-                    bp.band = 2;
-                    if (launch_slb(bp) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-                    if (hipMemcpyAsync(slots, ba.band_votes, sizeof(slots), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                        hipStreamSynchronize(st) != hipSuccess)
-                        return SUSHI_HIP_ELAUNCH;
-                    b->band_votes[0] = b->band_votes[1] = 0;
-                    for (int v = 0; v < VOTE_SLOTS; ++v) { b->band_votes[0] += slots[v * VOTE_STRIDE]; b->band_votes[1] += slots[v * VOTE_STRIDE + 1]; }
-                    // (measured at BASELINE configs[2]: 97 % of the pairs vote for it at 12 dB of noise on the source -- 9.7 ms against 17.5 for
-                    // the whole-row form --, 87 % at 6 dB -- 12.5 against 17.5 --, 14 % at 0 dB -- 28.7 against 18.7)
-                    b->band = b->band_votes[0] > 0 && (double)b->band_votes[1] >= 0.75 * (double)b->band_votes[0] ? 1 : 0;
-                    b->band_decided_method = b->method;
-                }
-                band = b->band;
-            }
-            b->last_band = band;
-        }
-
-        // the multiply-accumulate over ALL pairs: of the low rows (band-split form) or of whole rows; `enable`: a device flag that
-        // may call the launch off (the whole-row launch queued behind the survivors' list, below)
-        auto launch_mac = [&](const bool low, const int* enable, const int* items_of_the_launch) {
-            MacArgs ma;
-            ma.spec_blocks = dst->blocks;
-            ma.searches = searches_dev + sbt.a0; ma.tconst = tconst; ma.sub_first_seg = sbt.first_seg;
-            ma.sub_first_pair = sbt.first_pair;
-            ma.dummy = (uint4*)(wsp + wl.dummy);
-            ma.enable = enable;
-            if (low) { ma.spec = (const uint4*)dst->spec_low; ma.tspec = tspec_low; ma.y = ylow; }
-            else { ma.spec = (const uint4*)dst->spec; ma.tspec = (const uint4*)tspec; ma.y = y; }
-            for (int kern = 0; kern < 2; ++kern) {
-                if (sbt.item_count[kern] == 0) continue;
-                ma.items = items_of_the_launch + (size_t)(sbt.item_first[kern] - sbt.item_first[0]) * (1 + MAC_SPW);
-                ma.n_items = sbt.item_count[kern];
-                const int chunks = (low ? LROWE : ROWE) / MAC_BW;
-                ma.chunk_group = std::min(sbt.chunk_group[kern], chunks / 8);
-                const dim3 grid((unsigned)chunks * (unsigned)ma.n_items);
-                if (low) {
-                    if (kern == 0) hipLaunchKernelGGL(mac_kernel<LROWE>, grid, dim3(MAC_THREADS), 0, st, ma);
-                    else hipLaunchKernelGGL(mac_long_kernel<LROWE>, grid, dim3(MAC_THREADS), 0, st, ma);
-                } else {
-                    if (kern == 0) hipLaunchKernelGGL(mac_kernel<ROWE>, grid, dim3(MAC_THREADS), 0, st, ma);
-                    else hipLaunchKernelGGL(mac_long_kernel<ROWE>, grid, dim3(MAC_THREADS), 0, st, ma);
-                }
-                if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-            }
-            return SUSHI_HIP_OK;
-        };
-        t0 = prof_begin(pc, st);
-        const int32_t* sub_items = items + (size_t)sbt.item_first[0] * (1 + MAC_SPW);         // (the sub-batch's two item lists lie next to each other)
-        if (launch_mac(band != 0, nullptr, sub_items) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-        prof_end(pc, t0, SUSHI_HIP_STAGE_MAC, st);
-
-        t0 = prof_begin(pc, st);
-        // the candidate rows start empty: ifft_kernel writes only the entries that exist
-        if (!cand_filled && hipMemsetAsync(cand, 0xff, (size_t)sbt.pairs * FFT_ROW * sizeof(unsigned long long), st) != hipSuccess)
-            return SUSHI_HIP_ELAUNCH;
-        IfftArgs ia;
-        memset(&ia, 0, sizeof(ia));
-        ia.y = (const uint2*)y; ia.dst_stats = dst->stats; ia.searches = searches_dev + sbt.a0; ia.n_sub = n_sub; ia.first_search = sbt.a0;
-        ia.sub_first_pair = sbt.first_pair; ia.dst_len = dst->n; ia.delta = (float)delta; ia.cand = cand; ia.pair_lb = pair_lb; ia.gkeys = gkeys;
-        ia.pairmap = pairmap; ia.tconst = tconst; ia.order = order + sbt.order_first;
-        ia.urel = dst->urel; ia.nb = dst->blocks; ia.ubase = dst->base;
-        ia.usrel = dst->usrel; ia.sbase = dst->base + (dst->blocks + 1);
-        ia.flags = flags; ia.flag_list = flag_list + sbt.a0; ia.sub = subcnt; ia.tiles = tiles; ia.candbuf = candbuf;
-        ia.cand_cap = (int)cand_capacity(sbt.pairs); ia.counters = counters;
-        ia.viol = viol;
-        auto launch_ifft = [&](const IfftArgs& x, unsigned grid) {
-            if (x.count && !x.list_direct) {                         // a list whose length only the device knows: a fixed grid strides over its tail
-                if (ccm) hipLaunchKernelGGL(ifft_list_kernel<SUSHI_HIP_METHOD_CCOEFF_NORMED>, dim3(grid), dim3(FT), 0, st, x);
-                else hipLaunchKernelGGL(ifft_list_kernel<SUSHI_HIP_METHOD_SQDIFF_NORMED>, dim3(grid), dim3(FT), 0, st, x);
-            } else {
-                if (ccm) hipLaunchKernelGGL(ifft_kernel<SUSHI_HIP_METHOD_CCOEFF_NORMED>, dim3(grid), dim3(FT), 0, st, x);
-                else hipLaunchKernelGGL(ifft_kernel<SUSHI_HIP_METHOD_SQDIFF_NORMED>, dim3(grid), dim3(FT), 0, st, x);
-            }
-            return launch_ok();
-        };
-        // the whole rows of LISTED pairs (band-split form: nothing but the low band exists until a pair is to be transformed)
-        auto launch_mac_list = [&](const int* list, const int* count, int n_list, const int* dense_search, int long_only) {
-            MacListArgs la;
-            la.dense_search = dense_search; la.long_only = long_only;
-            la.spec = (const uint4*)dst->spec; la.spec_blocks = dst->blocks; la.tspec = (const uint4*)tspec; la.y = y;
-            la.searches = searches_dev + sbt.a0; la.tconst = tconst; la.pairmap = pairmap; la.list = list; la.count = count;
-            la.n_list = n_list; la.sub_first_seg = sbt.first_seg; la.sub_first_pair = sbt.first_pair;
-            const int64_t want = (int64_t)n_list * MACL_PARTS;
-            hipLaunchKernelGGL(mac_list_kernel, dim3((unsigned)std::min<int64_t>(want, 256 * 32)), dim3(MACL_THREADS), 0, st, la);
-            return launch_ok();
-        };
-        if (!exclude) {
-            // every pair, in the L2-friendly schedule (what round 3 did for every batch)
-            if (launch_ifft(ia, (unsigned)sbt.pairs) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-            b->direct_pairs += sbt.pairs;
-        } else {
-            // A lower bound of every pair's scores first (three of the transform's four passes, no scoring); then the most
-            // promising pair of every search, which leaves the search's threshold; then whatever the bound could not exclude
-            // (header of bound_kernel)
-            ba.band = band;
-            ba.y = band ? (const uint2*)ylow : (const uint2*)y;
-            // (bound_kernel adds to the pairs' accumulators; bound_low_kernel -- a wave per pair -- stores them)
-            if (!band && hipMemsetAsync(ba.acc, 0, (size_t)sbt.pairs * 2 * sizeof(float), st) != hipSuccess) return SUSHI_HIP_ELAUNCH;
-            {
-                // waves striding over the pairs: a small multiple of what is resident at the kernel's registers (four workgroups of four
-                // waves per CU, three for bound_low_kernel), fewer for a small batch.  Exactly what is resident -- persistent waves --
-                // leaves the hardware nothing to balance with: bound_low_kernel alone 2.41 - 2.44 ms at BASELINE configs[2] with 1 x,
-                // 2.36 with 2 x, 2.30 - 2.32 with 4 x and 8 x; next to other lanes' kernels 2 x is as good as it gets (8 x and more:
-                // the per-workgroup prologue shows)
-                const int per_pair = band ? 1 : 16;                  // bound_low_kernel: a wave per pair
-                const int64_t want = (sbt.pairs * per_pair + BOUND_THREADS / 64 - 1) / (BOUND_THREADS / 64);
-                const unsigned grid = (unsigned)std::min<int64_t>(want, 256 * (band ? 3 * (lanes > 1 ? 2 : 4) : 4));
-                // (the row energies are the statistical model's: the worst case -- the default -- does without them)
-                if (band) {
-                    if (ba.worst_case) hipLaunchKernelGGL(bound_low_kernel<false>, dim3(grid), dim3(BOUND_THREADS), 0, st, ba);
-                    else hipLaunchKernelGGL(bound_low_kernel<true>, dim3(grid), dim3(BOUND_THREADS), 0, st, ba);
-                } else {
-                    if (ba.worst_case) hipLaunchKernelGGL(bound_kernel<false>, dim3(grid), dim3(BOUND_THREADS), 0, st, ba);
-                    else hipLaunchKernelGGL(bound_kernel<true>, dim3(grid), dim3(BOUND_THREADS), 0, st, ba);
-                }
-                if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-                if (launch_slb(ba) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-            }
-            prof_end(pc, t0, SUSHI_HIP_STAGE_BOUND, st);
-            t0 = prof_begin(pc, st);
-            hipLaunchKernelGGL(pilot_kernel, dim3((unsigned)n_sub), dim3(64), 0, st, ba);
-            if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-            IfftArgs ip = ia;
-            ip.slb = ba.slb; ip.audit_mark = nullptr;              // (the pairs transformed first are nobody's excluded pairs)
-            ip.order = ba.plist; ip.count = nullptr;
-            if (band && launch_mac_list(ba.plist, nullptr, n_sub, nullptr, 0) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-            if (launch_ifft(ip, (unsigned)n_sub) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-            hipLaunchKernelGGL(survivor_kernel, dim3((unsigned)((sbt.pairs + 255) / 256)), dim3(256), 0, st, ba);
-            if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-            const int* final_list = ba.slist;
-            const int* final_count = ba.scount;
-            if (band) {
-                // the second look at what the bound left (header of bound_low_exact_kernel): sharper bound, shorter list
-                ba.list = ba.slist; ba.list_count = ba.scount;
-                ba.list2 = (int*)(wsp + wl.slist2); ba.list2_count = scount + 5;
-                hipLaunchKernelGGL(bound_low_exact_kernel, dim3(256 * 4), dim3(BLE_T), 0, st, ba);
-                if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-                if (ccm) hipLaunchKernelGGL(slb_list_kernel<SUSHI_HIP_METHOD_CCOEFF_NORMED>, dim3(256 * 2), dim3(256), 0, st, ba);
-                else hipLaunchKernelGGL(slb_list_kernel<SUSHI_HIP_METHOD_SQDIFF_NORMED>, dim3(256 * 2), dim3(256), 0, st, ba);
-                if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-                hipLaunchKernelGGL(survivor2_kernel, dim3(256), dim3(256), 0, st, ba);
-                if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-                final_list = ba.list2; final_count = ba.list2_count;
-                // whole rows of what is left: pair by pair for the searches that left few (the usual case), by the dense
-                // multiply-accumulate for the searches the bound could exclude little of (no match anywhere) -- decided per search and
-                // regrouped into items of their own, on the device (dense_search_kernel, dense_repack_kernel)
-                int* any_dense = scount + 4;                         // (zero since the run's first launch)
-                int* dense = (int*)(wsp + wl.dense_search);
-                int* ditems = (int*)(wsp + wl.ditems);
-                hipLaunchKernelGGL(dense_search_kernel, dim3((unsigned)n_sub), dim3(64), 0, st, ba, dense, scount + 6);
-                {
-                    const size_t second = (size_t)(sbt.item_first[1] - sbt.item_first[0]) * (1 + MAC_SPW);
-                    hipLaunchKernelGGL(dense_repack_kernel, dim3(2), dim3(REPACK_THREADS), 0, st, sub_items, sbt.item_count[0], sub_items + second,
-                                       sbt.item_count[1], dense, n_sub, ditems, ditems + second, scount + 6, (int)(sbt.pairs / 8), any_dense);
-                }
-                if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-                {
-                    MacRowsArgs ra;
-                    ra.spec = (const uint4*)dst->spec; ra.spec_blocks = dst->blocks; ra.tspec = (const uint4*)tspec; ra.y = y;
-                    ra.searches = searches_dev + sbt.a0; ra.tconst = tconst; ra.mark = ba.audit_mark; ra.n_sub = n_sub;
-                    ra.sub_first_seg = sbt.first_seg; ra.sub_first_pair = sbt.first_pair; ra.dense_search = dense;
-                    const int64_t want = (int64_t)n_sub * MACL_PARTS;
-                    if (sbt.item_count[0] > 0) hipLaunchKernelGGL(mac_rows_kernel<0>, dim3((unsigned)std::min<int64_t>(want, 256 * 32)), dim3(MACL_THREADS), 0, st, ra);
-                    if (sbt.item_count[1] > 0) hipLaunchKernelGGL(mac_rows_kernel<1>, dim3((unsigned)std::min<int64_t>(want, 256 * 16)), dim3(MACL_THREADS), 0, st, ra);
-                    if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-                }
-                if (sbt.long_patterns && launch_mac_list(final_list, final_count, (int)sbt.pairs, dense, 1) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-                if (launch_mac(false, any_dense, ditems) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-            }
-            ip.order = final_list; ip.count = final_count; ip.audit_mark = ba.audit_mark;
-            // One workgroup per list slot up to what the list usually holds (an eighth of the pairs: empty slots there cost a
-            // workgroup's launch each, ~1 ns), and a fixed grid striding over whatever lies beyond: the striding form alone runs
-            // at half the rate per pair (the loop costs it registers), one workgroup per POSSIBLE slot cost 0.3 ms of empty launches.
-            // (A batch whose LAST run listed more than that -- searches without a match, a dub's own speech -- gets a workgroup per
-            // possible slot instead: 0.3 ms of empty launches at most, against half the rate on everything behind the first eighth.
-            // `ifft` took 31.6 ms at BASELINE configs[2] on a dub with TM_CCOEFF_NORMED, 160 k pairs listed: bench.py --source dub.)
-            int64_t direct64 = std::min<int64_t>(sbt.pairs, std::max<int64_t>(4096, sbt.pairs / 8));
-            if ((double)b->last_transformed * (double)sbt.pairs > (double)direct64 * (double)b->plan.pairs) direct64 = sbt.pairs;   // (this sub-batch's share of it)
-            // (nothing known yet -- a batch's first run, which is all a one-shot job has --: half of the pairs get a workgroup each;
-            // 0.15 ms of empty launches where there is a match everywhere, against half the rate on ten times as many pairs where
-            // there is not: a dub's first run 29.7 ms)
-            else if (b->last_transformed == 0) direct64 = std::min<int64_t>(sbt.pairs, std::max<int64_t>(4096, sbt.pairs / 2));
-            const unsigned direct = (unsigned)direct64;
-            ip.list_first = 0; ip.list_direct = 1;
-            if (launch_ifft(ip, direct) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-            if ((int64_t)direct < sbt.pairs) {
-                ip.list_first = (int)direct; ip.list_direct = 0;
-                if (launch_ifft(ip, (unsigned)std::min<int64_t>(sbt.pairs - direct, 1024)) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-            }
-        }
-        prof_end(pc, t0, SUSHI_HIP_STAGE_IFFT, st);
-
-        t0 = prof_begin(pc, st);
-        RefineParams rp;
-        rp.r = r; rp.searches = searches_dev; rp.first_search = sbt.a0; rp.n_sub = n_sub; rp.sub_first_pair = sbt.first_pair;
-        rp.cand = cand; rp.pair_lb = pair_lb; rp.gkeys = gkeys; rp.keys = keys; rp.flags = flags; rp.flag_list = flag_list + sbt.a0;
-        rp.sub = subcnt; rp.counters = counters; rp.delta = (float)delta; rp.method = b->method;
-        rp.citems = (int*)(wsp + wl.citems); rp.n_citems = scount + 1;
-        rp.viol = viol;
-        rp.early = reinterpret_cast<int4*>(b->early_out);
-        ia.citems = rp.citems; ia.n_citems = rp.n_citems;
-        int rc = launch_refine(rp, st);
-        if (rc != SUSHI_HIP_OK) return rc;
-        prof_end(pc, t0, SUSHI_HIP_STAGE_REFINE, st);
-
-        // searches the lists could not finish: collect their candidates per tile, evaluate those exactly
-        // (both kernels leave after one load when nothing is flagged)
-        t0 = prof_begin(pc, st);
-        if (b->method == SUSHI_HIP_METHOD_CCOEFF_NORMED)
-            hipLaunchKernelGGL(collect_kernel<SUSHI_HIP_METHOD_CCOEFF_NORMED>, dim3(COLLECT_GRID), dim3(FT), 0, st, ia);
-        else
-            hipLaunchKernelGGL(collect_kernel<SUSHI_HIP_METHOD_SQDIFF_NORMED>, dim3(COLLECT_GRID), dim3(FT), 0, st, ia);
-        if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-        TileParams tp;
-        tp.r = r; tp.searches = searches_dev; tp.tiles = tiles; tp.cand = candbuf; tp.keys = keys; tp.counters = counters; tp.sub = subcnt;
-        tp.method = b->method;
-        rc = launch_tiles(tp, st);
-        if (rc != SUSHI_HIP_OK) return rc;
-        prof_end(pc, t0, SUSHI_HIP_STAGE_FINISH, st);
+    for (size_t si = 0; si < form.subs->size(); ++si) {
+        const SubBatch& sb = (*form.subs)[si];
+        if ((rc = run_sub(c, SubView(b->mem, b->lay, b->plan.ws_lane, sb, si), lanes.st[sb.lane])) != SUSHI_HIP_OK) return rc;
     }
-    for (int l = 1; l < lanes; ++l)
-        if (hipEventRecord(b->lane_done[l], lane_st[l]) != hipSuccess || hipStreamWaitEvent(st0, b->lane_done[l], 0) != hipSuccess) return SUSHI_HIP_ELAUNCH;
-    hipEvent_t t0 = prof_begin(pc, st0);
-    const int rc = launch_unpack(keys, n_search, b->method, out_idx_dev, out_score_dev, b->packed_out, st0);
-    prof_end(pc, t0, SUSHI_HIP_STAGE_FINISH, st0);
-    if (rc == SUSHI_HIP_OK && excluded_any && !b->stats_pending) {
+    if ((rc = lanes.join()) != SUSHI_HIP_OK) return rc;
+    hipEvent_t t0 = prof_begin(c.pc, st0);
+    rc = launch_unpack(c.keys, b->n, b->method, out_idx_dev, out_score_dev, b->packed_out, st0);
+    prof_end(c.pc, t0, SUSHI_HIP_STAGE_FINISH, st0);
+    if (rc == SUSHI_HIP_OK && c.excluded_any && !b->stats_pending) {
         // what this run's exclusion left, for the runs after it (never waited for: the event is queried)
         if (!b->host_stats) b->host_stats = g_host_slots.take();                 // (none left: this batch's AUTO does not learn)
         if (b->host_stats && !b->stats_ready && hipEventCreateWithFlags(&b->stats_ready, hipEventDisableTiming) != hipSuccess) b->stats_ready = nullptr;
         if (b->host_stats && b->stats_ready &&
-            hipMemcpyAsync(b->host_stats, &counters->pairs_transformed, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st0) == hipSuccess &&
+            hipMemcpyAsync(b->host_stats, &c.counters->pairs_transformed, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st0) == hipSuccess &&
             hipEventRecord(b->stats_ready, st0) == hipSuccess)
             b->stats_pending = true;
     }
@@ -896,14 +900,12 @@ int sushi_hip_batch_pair_bounds(SushiHipBatch* b, float* slb_host, float* acc_ho
     if (!b || !n_pairs) return SUSHI_HIP_EINVAL;
     if (!b->ran || b->path != SUSHI_HIP_PATH_FFT || b->plan.subs.empty()) { *n_pairs = 0; return SUSHI_HIP_OK; }
     if (hipStreamSynchronize(b->last_stream) != hipSuccess) return SUSHI_HIP_ELAUNCH;
-    const SubBatch& sbt = b->last_whole_cut ? b->plan.subs_whole.back() : b->plan.subs.back();
-    const WsLayout wl = ws_layout(sbt.pairs, sbt.segs, sbt.b0 - sbt.a0);
+    const SubView v = last_sub(b);
     const int64_t cap = *n_pairs;
-    *n_pairs = sbt.pairs;
-    if (cap < sbt.pairs) return SUSHI_HIP_ENOSPACE;
-    const char* wsp = b->mem + b->lay.ws + (size_t)sbt.lane * b->plan.ws_lane;
-    if (slb_host && hipMemcpy(slb_host, wsp + wl.slb, (size_t)sbt.pairs * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return SUSHI_HIP_ELAUNCH;
-    if (acc_host && hipMemcpy(acc_host, wsp + wl.acc, (size_t)sbt.pairs * 2 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return SUSHI_HIP_ELAUNCH;
+    *n_pairs = v.sb.pairs;
+    if (cap < v.sb.pairs) return SUSHI_HIP_ENOSPACE;
+    if (slb_host && hipMemcpy(slb_host, v.slb, (size_t)v.sb.pairs * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return SUSHI_HIP_ELAUNCH;
+    if (acc_host && hipMemcpy(acc_host, v.acc, (size_t)v.sb.pairs * 2 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return SUSHI_HIP_ELAUNCH;
     return SUSHI_HIP_OK;
 } catch (const std::bad_alloc&) { return SUSHI_HIP_ENOMEM; } catch (...) { return SUSHI_HIP_EINTERNAL; }
 
@@ -912,14 +914,12 @@ int sushi_hip_batch_workspace_view(SushiHipBatch* b, int which, void** ptr_dev, 
     *ptr_dev = nullptr; *bytes = 0;
     if (!b->ran || b->path != SUSHI_HIP_PATH_FFT || b->plan.subs.empty()) return SUSHI_HIP_OK;
     if (hipStreamSynchronize(b->last_stream) != hipSuccess) return SUSHI_HIP_ELAUNCH;
-    const SubBatch& sbt = b->last_whole_cut ? b->plan.subs_whole.back() : b->plan.subs.back();
-    const WsLayout wl = ws_layout(sbt.pairs, sbt.segs, sbt.b0 - sbt.a0);
-    char* wsp = b->mem + b->lay.ws + (size_t)sbt.lane * b->plan.ws_lane;
+    const SubView v = last_sub(b);
     switch (which) {
-        case SUSHI_HIP_WS_TSPEC: *ptr_dev = wsp + wl.tspec; *bytes = (size_t)sbt.segs * ROW_BYTES; break;
-        case SUSHI_HIP_WS_Y: *ptr_dev = wsp + wl.y; *bytes = (size_t)sbt.pairs * ROW_BYTES; break;
-        case SUSHI_HIP_WS_TSPEC_LOW: *ptr_dev = wsp + wl.tspec_low; *bytes = (size_t)sbt.segs * LROW_BYTES; break;
-        case SUSHI_HIP_WS_Y_LOW: *ptr_dev = wsp + wl.ylow; *bytes = (size_t)sbt.pairs * LROW_BYTES; break;
+        case SUSHI_HIP_WS_TSPEC: *ptr_dev = v.tspec; *bytes = (size_t)v.sb.segs * ROW_BYTES; break;
+        case SUSHI_HIP_WS_Y: *ptr_dev = v.y; *bytes = (size_t)v.sb.pairs * ROW_BYTES; break;
+        case SUSHI_HIP_WS_TSPEC_LOW: *ptr_dev = v.tspec_low; *bytes = (size_t)v.sb.segs * LROW_BYTES; break;
+        case SUSHI_HIP_WS_Y_LOW: *ptr_dev = v.ylow; *bytes = (size_t)v.sb.pairs * LROW_BYTES; break;
         default: return SUSHI_HIP_EINVAL;
     }
     return SUSHI_HIP_OK;

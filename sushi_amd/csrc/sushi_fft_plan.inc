@@ -3,6 +3,19 @@
 
 inline int launch_ok() { return hipGetLastError() == hipSuccess ? SUSHI_HIP_OK : SUSHI_HIP_ELAUNCH; }
 
+// A kernel instantiated per method / per sample type: `f` launches it with the template argument it is given, as a
+// std::integral_constant / a null pointer of the sample type.
+template <typename F> int launch_method(int method, F&& f) {
+    if (method == SUSHI_HIP_METHOD_CCOEFF_NORMED) f(std::integral_constant<int, SUSHI_HIP_METHOD_CCOEFF_NORMED>());
+    else f(std::integral_constant<int, SUSHI_HIP_METHOD_SQDIFF_NORMED>());
+    return launch_ok();
+}
+template <typename F> int launch_dtype(int dtype, F&& f) {
+    if (dtype == SUSHI_HIP_F32) f((float*)nullptr);
+    else f((uint8_t*)nullptr);
+    return launch_ok();
+}
+
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 inline int64_t cand_capacity(int64_t pairs) {
@@ -332,6 +345,28 @@ BatchLayout batch_layout(int n, int path, size_t n_order_ints, size_t n_item_int
     b.total = o;
     return b;
 }
+
+// One sub-batch of a cut of a plan and where it works in the batch's memory `mem`: its lane's workspace (ws_layout, typed), its
+// schedule and items, its small counters (SUBC_BYTES at its index in the cut: SubCounters, then its scount words), its pattern rows' norms.
+struct SubView {
+    const SubBatch& sb;
+    int n_sub;
+    uint32_t* tspec; uint4 *y, *tspec_low, *ylow, *dummy; unsigned long long* cand; TemplConsts* tconst; TileDesc* tiles; int32_t* candbuf;
+    float *pair_lb, *slb, *acc, *tnorm_rest; unsigned char* audit_mark; SubCounters* sub; const int32_t *order, *items;
+    int *pairmap, *plist, *slist, *slist2, *votes, *dense_search, *ditems, *citems, *scount;
+    SubView(char* mem, const BatchLayout& lay, size_t ws_lane, const SubBatch& s, size_t si) : sb(s), n_sub(s.b0 - s.a0) {
+        const WsLayout w = ws_layout(s.pairs, s.segs, n_sub);
+        char* p = mem + lay.ws + (size_t)s.lane * ws_lane;
+        tspec = (uint32_t*)(p + w.tspec); y = (uint4*)(p + w.y); tspec_low = (uint4*)(p + w.tspec_low); ylow = (uint4*)(p + w.ylow); dummy = (uint4*)(p + w.dummy);
+        cand = (unsigned long long*)(p + w.cand); tconst = (TemplConsts*)(p + w.tconst); tiles = (TileDesc*)(p + w.tiles); candbuf = (int32_t*)(p + w.candbuf);
+        pair_lb = (float*)(p + w.pair_lb); slb = (float*)(p + w.slb); acc = (float*)(p + w.acc); tnorm_rest = (float*)(mem + lay.tnorm) + s.first_seg;
+        audit_mark = (unsigned char*)(p + w.audit_mark); sub = (SubCounters*)(mem + lay.subc + si * SUBC_BYTES); scount = (int*)sub + SUBC_SCOUNT;
+        order = (const int32_t*)(mem + lay.order) + s.order_first;
+        items = (const int32_t*)(mem + lay.items) + (size_t)s.item_first[0] * (1 + MAC_SPW);   // (its two item lists lie next to each other)
+        pairmap = (int*)(p + w.pairmap); plist = (int*)(p + w.plist); slist = (int*)(p + w.slist); slist2 = (int*)(p + w.slist2);
+        votes = (int*)(p + w.votes); dense_search = (int*)(p + w.dense_search); ditems = (int*)(p + w.ditems); citems = (int*)(p + w.citems);
+    }
+};
 
 // requests -> descriptors with their running sums; EINVAL for a malformed request
 int make_descs(const SushiHipRequest* req, int n, int variant, std::vector<SearchDesc>& out, int64_t* n_tiles) {
