@@ -40,7 +40,8 @@ extern "C" {
                                      sushi_hip_batch_workspace_view, SUSHI_HIP_ENOMEM / _EINTERNAL;
                                      13: SushiHipBatchInfo.lanes (appended): a large batch's sub-batches run side by side on HIP streams
                                      of the library's own, forked off and joined back into the stream a run is given;
-                                     sushi_hip_batch_set_early_output, sushi_hip_device_prepare */
+                                     sushi_hip_batch_set_early_output, sushi_hip_device_prepare;
+                                     13 (additive): sushi_hip_curve_bytes, sushi_hip_match_curves */
 
 #if defined(__GNUC__)
 #define SUSHI_HIP_API __attribute__((visibility("default")))
@@ -309,6 +310,27 @@ SUSHI_HIP_API void sushi_hip_batch_destroy(SushiHipBatch* batch);
 /* FFT path geometry of one request: block pairs (inverse transforms) and pattern segments (forward transforms). */
 SUSHI_HIP_API int sushi_hip_fft_layout(int64_t win_start, int32_t n_pos, int32_t tmpl_len,
                                        int32_t* n_pairs, int32_t* n_seg);
+
+/* ---- whole score curves (DESIGN.md "Curves") -------------------------------------------------------------
+ * The row cv2.matchTemplate returns (wav.py:185 `result`), not only its extremum.  A request is a SushiHipRequest with the
+ * meaning and validation of sushi_hip_batch_create; the curve of request k is its n_pos float32 values
+ * cv2.matchTemplate(search_source, pattern, method)[0]:
+ *   SUSHI_HIP_METHOD_SQDIFF_NORMED  the TM_SQDIFF_NORMED value;
+ *   SUSHI_HIP_METHOD_CCOEFF_NORMED  the TM_CCOEFF_NORMED value itself (not the 1 - value the ranking minimises): a flat pattern
+ *                                   gives 1, a window cv2 takes for flat 0.
+ * Every value is bit-identical to what the exact stages of sushi_hip_batch_run produce for that position: curve[out_idx] ==
+ * out_score, the first arg-min (arg-max for CCOEFF) of a curve is the batch's out_idx, and uint8 curves equal cv2's direct
+ * (non-FFT) evaluation.  Request k's curve starts at out_dev + off_k, off_k = sum of n_pos of the requests before it (a
+ * 64-bit count).  Only the samples and the float64 prefix sums are read: dst and src need not be searchable, and no batch
+ * handle is involved. */
+/* workspace a curve call needs (request table, tile queue); 0 for n <= 0 */
+SUSHI_HIP_API size_t sushi_hip_curve_bytes(const SushiHipRequest* req_host, int n);
+/* out_dev[off_k + p] = result row of request k (contract above); dst/src need not be searchable; same dtype;
+ * mem_dev 256-byte aligned, >= sushi_hip_curve_bytes; out_dev 4-byte aligned, >= sum of n_pos floats.
+ * EINVAL / EALIGN / ENOSPACE checked before any HIP call; asynchronous; stateless (any thread, own workspace). */
+SUSHI_HIP_API int sushi_hip_match_curves(const SushiHipStream* dst, const SushiHipStream* src,
+                                         const SushiHipRequest* req_host, int n, int method,
+                                         void* mem_dev, size_t mem_bytes, float* out_dev, void* hip_stream);
 
 /* ---- WavStream.__init__ on the GPU (wav.py:64-91 decode + downmix, wav.py:113-156 value pipeline) ----
  * sushi_hip_load_decode   : interleaved little-endian PCM frames (sample_width 2 or 3 bytes, `channels` per frame)

@@ -143,6 +143,10 @@ def lib():
     L.sushi_hip_batch_destroy.argtypes = [vp]
     L.sushi_hip_fft_layout.restype = ci
     L.sushi_hip_fft_layout.argtypes = [i64, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.sushi_hip_curve_bytes.restype = sz
+    L.sushi_hip_curve_bytes.argtypes = [vp, ci]
+    L.sushi_hip_match_curves.restype = ci
+    L.sushi_hip_match_curves.argtypes = [vp, vp, vp, ci, ci, vp, sz, vp, vp]
     L.sushi_hip_load_decode.restype = ci
     L.sushi_hip_load_decode.argtypes = [vp, i64, i32, i32, vp, vp]
     L.sushi_hip_load_resample.restype = ci

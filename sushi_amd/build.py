@@ -1,9 +1,10 @@
 """Build libsushi_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
-Two translation units, compiled separately (the MFMA kernel alone takes ~2 min) and linked:
+The translation units, compiled separately (the MFMA kernel alone takes ~2 min) and linked:
   csrc/sushi_hip.hip  direct MFMA kernel, stream preparation, exact refinement   (-ffp-contract=off)
   csrc/sushi_fft.hip  overlap-save FFT path
   csrc/sushi_load.hip WavStream load pipeline (decimate / pad / median clip / scale / quantise)  (-ffp-contract=off)
+  csrc/sushi_curve.hip whole score curves: i8 MFMA Toeplitz GEMM (uint8), canonical float64 chain (float32)  (-ffp-contract=off)
 """
 import math
 import os
@@ -24,6 +25,7 @@ COMMON_DEPS = [HEADER, os.path.join(CSRC, "sushi_common.hpp"), os.path.join(CSRC
 UNITS = [
     ("sushi_hip", ["-ffp-contract=off"], []),
     ("sushi_load", ["-ffp-contract=off"], []),      # NumPy's float32 operation order, no fused multiply-add
+    ("sushi_curve", ["-ffp-contract=off"], []),     # the epilogue restates cv2's operation order (as sushi_hip.hip's)
     # -fno-slp-vectorize: the SLP pass packs the complex MACs into v_pk_fma_f32 and pays for it in
     # register shuffles (v_mov / accvgpr traffic); plain v_fma_f32 already issues at the f32 peak rate.
     ("sushi_fft", ["-fno-slp-vectorize"],

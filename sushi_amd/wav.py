@@ -343,14 +343,49 @@ class WavStream(object):
         sample index of every match in self.data (what SpeculativeStream caches).
         method: 'sqdiff_normed' = what the reference's find_substream computes (wav.py:185-186: TM_SQDIFF_NORMED, argmin);
         'ccoeff_normed' = cv2.TM_CCOEFF_NORMED with argmax instead (not used by the reference; the method BASELINE.json names)."""
-        from .device import DeviceStream, SearchBatch
+        from .device import SearchBatch
         n = len(patterns)
         if not (len(window_centers) == len(window_sizes) == n) or n == 0:
             raise SushiError('find_substreams: need equally many patterns, centres and sizes (>= 1)')
+        dst_dev = self.device_stream()
+        src_dev, offs, lens, one_owner = self._pattern_source(patterns, dst_dev)
+        start_times, win_start, n_pos = [], [], []
+        for m, c, w in zip(lens, window_centers, window_sizes):
+            st, lo, p = self._window(m, c, w)
+            start_times.append(st)
+            win_start.append(lo)
+            n_pos.append(p)
+        # A drop-in call is a batch of one (a triple of three): its cost is host work and launches, not arithmetic.  Such batches
+        # are kept per (source stream, size, method) and RE-PLANNED in place for the next call (sushi_hip_batch_reset: no
+        # allocation, one upload) instead of being built and torn down every time.
+        batch = None
+        pooled = n <= 4 and one_owner
+        if pooled:
+            pool = self.__dict__.setdefault("_small_batches", {})
+            from .device import default_path
+            key = (id(src_dev), n, method, default_path(), os.environ.get("SUSHI_HIP_EXCLUSION"))   # (what a new batch would read from the environment)
+            batch = pool.get(key)
+            if batch is not None and (batch.dst is not dst_dev or batch.src is not src_dev or not batch.reset(offs, lens, win_start, n_pos)):
+                batch = None
+        if batch is None:
+            batch = SearchBatch(dst_dev, src_dev, offs, lens, win_start, n_pos, method=method, headroom=4.0 if pooled else 1.0)
+            if pooled:
+                pool[key] = batch
+        batch.run()
+        idx, score = batch.results()
+        times = [st + (int(k) / float(self.sample_rate)) for st, k in zip(start_times, idx)]
+        if with_index:
+            return score, times, [int(lo) + int(k) for lo, k in zip(win_start, idx)]
+        return score, times
+
+    def _pattern_source(self, patterns, dst_dev):
+        """Where a batch's patterns live: (source DeviceStream, offsets, lengths, whether they are views of ONE live stream).
+        Patterns that are views of one live stream are read where they are; others are uploaded as one temporary stream."""
+        from .device import DeviceStream
         located = [_locate(p) for p in patterns]
         owners = set(id(l[0]) for l in located if l is not None)
-        dst_dev = self.device_stream()
-        if all(l is not None for l in located) and len(owners) == 1:
+        one_owner = all(l is not None for l in located) and len(owners) == 1
+        if one_owner:
             src_dev = located[0][0].device_stream()
             offs = [l[1] for l in located]
             lens = [l[2] for l in located]
@@ -369,31 +404,31 @@ class WavStream(object):
             if sum(lens) == 0:
                 raise SushiError('empty pattern')
             src_dev = DeviceStream(np.concatenate(rows), device=dst_dev.device)
-        start_times, win_start, n_pos = [], [], []
+        return src_dev, offs, lens, one_owner
+
+    # ------------------------------------------------------------------ whole curves
+    def match_template(self, pattern, window_center, window_size, method="sqdiff_normed"):
+        """wav.py:185's `result` itself: cv2.matchTemplate(search_source, pattern, method) over find_substream's window
+        (wav.py:178-184), as a float32 ndarray of shape (1, P).  method: 'sqdiff_normed' (what the reference calls) or
+        'ccoeff_normed' (the TM_CCOEFF_NORMED value).  Every value is the one the search path computes exactly: the argmin of
+        this row (argmax for 'ccoeff_normed') and its value are what find_substream returns."""
+        return self.match_templates([pattern], [window_center], [window_size], method=method)[0]
+
+    def match_templates(self, patterns, window_centers, window_sizes, method="sqdiff_normed", as_tensor=False):
+        """[match_template(p, c, w) for p, c, w in zip(...)] in one GPU launch (patterns located as find_substreams does).
+        as_tensor=True: a list of (1, P) float32 CUDA tensors -- views of one device buffer, no copy to the host."""
+        from .curves import match_curves
+        n = len(patterns)
+        if not (len(window_centers) == len(window_sizes) == n) or n == 0:
+            raise SushiError('match_templates: need equally many patterns, centres and sizes (>= 1)')
+        dst_dev = self.device_stream()
+        src_dev, offs, lens, _ = self._pattern_source(patterns, dst_dev)
+        win_start, n_pos = [], []
         for m, c, w in zip(lens, window_centers, window_sizes):
-            st, lo, p = self._window(m, c, w)
-            start_times.append(st)
+            _, lo, p = self._window(m, c, w)
             win_start.append(lo)
             n_pos.append(p)
-        # A drop-in call is a batch of one (a triple of three): its cost is host work and launches, not arithmetic.  Such batches
-        # are kept per (source stream, size, method) and RE-PLANNED in place for the next call (sushi_hip_batch_reset: no
-        # allocation, one upload) instead of being built and torn down every time.
-        batch = None
-        pooled = n <= 4 and len(owners) == 1 and all(l is not None for l in located)
-        if pooled:
-            pool = self.__dict__.setdefault("_small_batches", {})
-            from .device import default_path
-            key = (id(src_dev), n, method, default_path(), os.environ.get("SUSHI_HIP_EXCLUSION"))   # (what a new batch would read from the environment)
-            batch = pool.get(key)
-            if batch is not None and (batch.dst is not dst_dev or batch.src is not src_dev or not batch.reset(offs, lens, win_start, n_pos)):
-                batch = None
-        if batch is None:
-            batch = SearchBatch(dst_dev, src_dev, offs, lens, win_start, n_pos, method=method, headroom=4.0 if pooled else 1.0)
-            if pooled:
-                pool[key] = batch
-        batch.run()
-        idx, score = batch.results()
-        times = [st + (int(k) / float(self.sample_rate)) for st, k in zip(start_times, idx)]
-        if with_index:
-            return score, times, [int(lo) + int(k) for lo, k in zip(win_start, idx)]
-        return score, times
+        curves, bounds = match_curves(dst_dev, src_dev, offs, lens, win_start, n_pos, method=method)
+        if not as_tensor:
+            curves = curves.cpu().numpy()
+        return [curves[int(bounds[k]):int(bounds[k + 1])].reshape(1, -1) for k in range(n)]
