@@ -41,7 +41,8 @@ extern "C" {
                                      13: SushiHipBatchInfo.lanes (appended): a large batch's sub-batches run side by side on HIP streams
                                      of the library's own, forked off and joined back into the stream a run is given;
                                      sushi_hip_batch_set_early_output, sushi_hip_device_prepare;
-                                     13 (additive): sushi_hip_curve_bytes, sushi_hip_match_curves */
+                                     13 (additive): sushi_hip_curve_bytes, sushi_hip_match_curves;
+                                     13 (additive): SushiHipHit, sushi_hip_batch_run_threshold */
 
 #if defined(__GNUC__)
 #define SUSHI_HIP_API __attribute__((visibility("default")))
@@ -306,6 +307,36 @@ SUSHI_HIP_API int sushi_hip_batch_pair_bounds(SushiHipBatch* batch, float* slb_h
 #define SUSHI_HIP_WS_Y_LOW 3
 SUSHI_HIP_API int sushi_hip_batch_workspace_view(SushiHipBatch* batch, int which, void** ptr_dev, size_t* bytes);
 SUSHI_HIP_API void sushi_hip_batch_destroy(SushiHipBatch* batch);
+
+/* ---- threshold runs: every position that passes a threshold (13, additive) ----------------------------------
+ * What np.where(result >= t) answers on cv2.matchTemplate's result row: all occurrences of a pattern in its window, not only the
+ * best one.  FFT path only.  For request k of the batch (same requests, streams and method as sushi_hip_batch_run), every index p
+ * in [0, n_pos) whose score passes `threshold`:
+ *   SUSHI_HIP_METHOD_SQDIFF_NORMED  score(p) <= threshold;
+ *   SUSHI_HIP_METHOD_CCOEFF_NORMED  score(p) >= threshold   (the coefficient itself, as sushi_hip_match_curves returns it).
+ * out_hits_dev[k * capacity + j], j < min(count, capacity): the hits of request k in ascending index order, each with its float32
+ * score -- bit-identical to sushi_hip_match_curves at that position; the slots behind them are not written.  out_counts_dev[k]:
+ * how many hits request k has, also when that exceeds `capacity` (then only the first `capacity` by index are written; capacity 0
+ * counts only).  The output depends on nothing but the requests, the method and the threshold: not on sub-batches, lanes, the
+ * exclusion's mode or form, or earlier runs.
+ * Completeness rests on the pair exclusion's WORST_CASE bound alone (the default): a block pair is skipped only if
+ * no exact score in it can pass; every other pair is evaluated exactly at every position.  SUSHI_HIP_EXCLUDE_NEVER evaluates every
+ * pair.  An audited excluded pair (the audit of sushi_hip_batch_run) that is found to hold a hit, or a score below its bound, is a
+ * bound violation (slb_violations): every pair of that search is then evaluated in the same run.
+ * EINVAL before any HIP call: NULL batch or outputs, capacity < 0, a threshold that is not finite, a direct-path batch; EALIGN:
+ * out_hits_dev not 4-byte or out_counts_dev not 8-byte aligned.  Synchronisation as for sushi_hip_batch_run: asynchronous, except
+ * that a threshold run may take the batch's one decision of the exclusion's form (one 8-byte read-back, once per batch and method)
+ * if no run has taken it yet.  No device memory besides the batch's own (sushi_hip_batch_bytes is what it was).  Afterwards
+ * sushi_hip_batch_diagnostics reports pairs_transformed (pairs evaluated exactly), excluded_audited, max_slb_ratio_excluded,
+ * slb_violations and band as for a run, and 0 in every other field.  Neither the early nor the packed records are written, and
+ * what AUTO has learnt from the batch's runs is not changed. */
+typedef struct SushiHipHit {
+    int32_t index;            /* position in the request's result row */
+    float score;              /* its float32 score */
+} SushiHipHit;                /* 8 bytes */
+/* FFT path.  out_hits_dev: [n][capacity] hits; out_counts_dev: [n] int64. */
+SUSHI_HIP_API int sushi_hip_batch_run_threshold(SushiHipBatch* batch, double threshold, int32_t capacity,
+                                                SushiHipHit* out_hits_dev, int64_t* out_counts_dev, void* hip_stream);
 
 /* FFT path geometry of one request: block pairs (inverse transforms) and pattern segments (forward transforms). */
 SUSHI_HIP_API int sushi_hip_fft_layout(int64_t win_start, int32_t n_pos, int32_t tmpl_len,

@@ -40,6 +40,9 @@ STAGE_KERNEL_SETS = {"tspec": ("tspec_kernel",), "mac": ("mac_kernel", "mac_long
 # struct SushiHipRequest, 24 bytes
 REQUEST_DTYPE = np.dtype([("tmpl_off", "<i8"), ("win_start", "<i8"), ("tmpl_len", "<i4"), ("n_pos", "<i4")], align=True)
 assert REQUEST_DTYPE.itemsize == 24
+# struct SushiHipHit, 8 bytes: one position of a threshold run (sushi_hip_batch_run_threshold) and its float32 score
+HIT_DTYPE = np.dtype([("index", "<i4"), ("score", "<f4")], align=True)
+assert HIT_DTYPE.itemsize == 8
 
 
 class BatchInfo(ctypes.Structure):
@@ -125,6 +128,8 @@ def lib():
     L.sushi_hip_batch_set_method.argtypes = [vp, ci]
     L.sushi_hip_batch_run.restype = ci
     L.sushi_hip_batch_run.argtypes = [vp, dbl, vp, vp, vp]
+    L.sushi_hip_batch_run_threshold.restype = ci
+    L.sushi_hip_batch_run_threshold.argtypes = [vp, dbl, i32, vp, vp, vp]
     L.sushi_hip_batch_diagnostics.restype = ci
     L.sushi_hip_batch_diagnostics.argtypes = [vp, ctypes.POINTER(BatchDiag), vp, vp]
     L.sushi_hip_batch_set_packed_output.restype = ci

@@ -4,7 +4,8 @@ The translation units, compiled separately (the MFMA kernel alone takes ~2 min) 
   csrc/sushi_hip.hip  direct MFMA kernel, stream preparation, exact refinement   (-ffp-contract=off)
   csrc/sushi_fft.hip  overlap-save FFT path
   csrc/sushi_load.hip WavStream load pipeline (decimate / pad / median clip / scale / quantise)  (-ffp-contract=off)
-  csrc/sushi_curve.hip whole score curves: i8 MFMA Toeplitz GEMM (uint8), canonical float64 chain (float32)  (-ffp-contract=off)
+  csrc/sushi_curve.hip whole score curves: i8 MFMA Toeplitz GEMM (uint8), canonical float64 chain (float32)  (-ffp-contract=off);
+                       the same tiles (csrc/curve_tiles.hpp) evaluate the listed pairs of a threshold run
 """
 import math
 import os
@@ -25,7 +26,7 @@ COMMON_DEPS = [HEADER, os.path.join(CSRC, "sushi_common.hpp"), os.path.join(CSRC
 UNITS = [
     ("sushi_hip", ["-ffp-contract=off"], []),
     ("sushi_load", ["-ffp-contract=off"], []),      # NumPy's float32 operation order, no fused multiply-add
-    ("sushi_curve", ["-ffp-contract=off"], []),     # the epilogue restates cv2's operation order (as sushi_hip.hip's)
+    ("sushi_curve", ["-ffp-contract=off"], [os.path.join(CSRC, "curve_tiles.hpp")]),     # the epilogue restates cv2's operation order (as sushi_hip.hip's)
     # -fno-slp-vectorize: the SLP pass packs the complex MACs into v_pk_fma_f32 and pays for it in
     # register shuffles (v_mov / accvgpr traffic); plain v_fma_f32 already issues at the f32 peak rate.
     ("sushi_fft", ["-fno-slp-vectorize"],
@@ -33,7 +34,7 @@ UNITS = [
       # the translation unit's parts, by stage (included inside its anonymous namespace)
       os.path.join(CSRC, "sushi_fft_store.inc"), os.path.join(CSRC, "sushi_fft_spectra.inc"), os.path.join(CSRC, "sushi_fft_mac.inc"),
       os.path.join(CSRC, "sushi_fft_ifft.inc"), os.path.join(CSRC, "sushi_fft_bound.inc"), os.path.join(CSRC, "sushi_fft_collect.inc"),
-      os.path.join(CSRC, "sushi_fft_plan.inc"),
+      os.path.join(CSRC, "sushi_fft_plan.inc"), os.path.join(CSRC, "sushi_fft_threshold.inc"),
       os.path.join(CSRC, "_gen_dft16_f16_bound.inc"), os.path.join(CSRC, "_gen_dft16_f16_bound_low.inc")]),
 ]
 

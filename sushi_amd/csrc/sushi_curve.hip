@@ -4,7 +4,9 @@
 //   * uint8 streams: the centred cross term as an exact integer GEMM with one Toeplitz operand on v_mfma_i32_32x32x32_i8;
 //   * float32 streams: the canonical float64 chain of the exact stages (sushi_hip.hip refine_kernel / exact_tiles_kernel)
 //     on the VALU.
-// Either way each value is bit for bit what the exact stages produce for that position.
+// Either way each value is bit for bit what the exact stages produce for that position.  The tile bodies
+// (curve_tiles.hpp) also evaluate the listed block pairs of a threshold run (sushi_hip_batch_run_threshold):
+// threshold_tiles_kernel, launched from sushi_fft.hip through launch_threshold_tiles.
 //
 // Stateless: no handle, no spectra; the request table and the tile queue live in the caller's workspace.
 
@@ -12,19 +14,19 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
 #include <new>
 #include <vector>
 
 #include "../../include/sushi_hip.h"
 #include "sushi_common.hpp"
 #include "sushi_internal.hpp"
+#include "curve_tiles.hpp"
 
 namespace {
 
 using namespace sushi;
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x16 __attribute__((ext_vector_type(16)));
+using namespace sushi_tiles;
 
 // One request on the device: where its pattern and window are, where its curve goes, its first work item.
 struct CurveDesc {
@@ -43,14 +45,11 @@ size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 size_t curve_layout_bytes(int n) { return n <= 0 ? 0 : CURVE_HEAD + align256((size_t)n * sizeof(CurveDesc)); }
 
 struct CurveArgs {
-    const void* dst_raw; const double* dst_s1; const double* dst_s2; int64_t dst_len;
-    const void* src_raw; const double* src_s1; const double* src_s2;
-    double centre;
+    TileSrc src;                      // streams, method
     const CurveDesc* desc;
     int n;
     int64_t n_items;
     unsigned long long* queue;
-    int method;
     float* out;
 };
 
@@ -64,72 +63,12 @@ __device__ __forceinline__ int find_request(const CurveDesc* __restrict__ d, int
     return lo;
 }
 
-__device__ __forceinline__ float curve_value(const CurveArgs& a, const TemplStats& ts, double corr_c_or_u, bool centred,
-                                             const double* __restrict__ w1, const double* __restrict__ w2, int64_t p, int M) {
-    if (a.method == SUSHI_HIP_METHOD_CCOEFF_NORMED)
-        return centred ? score_ccoeff_at(corr_c_or_u, ts, a.centre, w1, w2, p, M)
-                       : finish_ccoeff_normed(corr_c_or_u, w1[p + M] - w1[p], w2[p + M] - w2[p], ts, M);
-    return centred ? score_at(corr_c_or_u, ts, a.centre, w1, w2, p, M) : score_exact(corr_c_or_u, ts, w2, p, M);
-}
-
-// TM_CCOEFF_NORMED: whether any of this thread's positions needs the cross term (a flat pattern, or windows cv2 takes for flat,
-// give their value from the prefix sums alone)
-__device__ __forceinline__ bool needs_corr(const CurveArgs& a, const TemplStats& ts, const double* __restrict__ w1,
-                                           const double* __restrict__ w2, int64_t p, int P, int M) {
-    if (a.method != SUSHI_HIP_METHOD_CCOEFF_NORMED) return p < P;
-    return p < P && !ccoeff_ignores_corr(w1[p + M] - w1[p], w2[p + M] - w2[p], ts, M);
-}
-
-// ------------------------------------------------------------------------------------------------------------------------
-// uint8: Toeplitz GEMM on the i8 matrix pipe.  Positions p = p0 + 32 i + j of one 1024-position tile,
-//     D[i][j] = sum_n A[i][n] B[n][j],   A[i][n] = T'[n - 32 i] (0 outside [0, M)),   B[n][j] = I'[win_start + p0 + j + n],
-// n in [0, M + 992): K steps of 32.  T' = T - 128, I' = I - 128 as int8: the byte x ^ 0x80.
-// Lane l (r = l & 31, h = l >> 5) holds A[r][32 s + 16 h + e] and B[32 s + 16 h + e][r], e = 0..15, in the bytes of its two
-// 4-dword operands; C/D: column r, row (reg & 3) + 8 (reg >> 2) + 4 h (the same for every input type).  Whatever
-// order the instruction gives the 32 k of a step inside a lane's 16 bytes, A and B are staged with the SAME k at the same byte,
-// so the sum over k -- of integers, exact -- does not depend on it; row and column maps are checked bitwise by the GPU tests.
-// The four waves of a workgroup take a quarter of the K steps each; their partial sums meet in LDS (integers: any order).
-//
-// Exactness (the proof obligation): every product is at most 2^14 in magnitude, so an int32 accumulator stays exact for
-// 2^17 / 32 = 4096 steps; it is folded into float64 every FOLD_STEPS < 4096.  |sum T'I'| <= 2^14 M < 2^45 for any int32 M, so
-// the float64 folds add integers below 2^53: exact.  score_at then forms sum T*I = corr_c + 128 (sum T + sum I) - 128^2 M,
-// every term and partial sum an integer below 2^53 (sum T, sum I <= 255 M < 2^39): exact again -- the same integer the exact
-// stages' float64 chain of uint8 products reaches (its partial sums are integers below 2^47: exact).  Equal cross terms through
-// the same finish_* give the same float32.
-// ------------------------------------------------------------------------------------------------------------------------
-constexpr int U8_TILE = 1024;
-constexpr int FOLD_STEPS = 1024;        // 32,768 pattern samples per int32 chain (< 4096 steps: no overflow)
-
-struct __attribute__((packed, aligned(1))) Bytes16 { uint8_t v[16]; };
-
-// 16 centred samples x[k .. k + 16) of a row whose valid part is [lo, hi): the others are 0
-__device__ __forceinline__ i32x4 load_centred16(const uint8_t* __restrict__ row, int64_t k, int64_t lo, int64_t hi) {
-    i32x4 r;
-    if (k >= lo && k + 16 <= hi) {
-        const Bytes16 b = *reinterpret_cast<const Bytes16*>(row + k);
-        memcpy(&r, &b, 16);
-        r ^= (i32x4){(int)0x80808080, (int)0x80808080, (int)0x80808080, (int)0x80808080};
-    } else {
-        unsigned w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int64_t x = k + e;
-            if (x >= lo && x < hi) w[e >> 2] |= (unsigned)(row[x] ^ 0x80u) << (8 * (e & 3));
-        }
-        r = (i32x4){(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
-    }
-    return r;
-}
-
+// uint8: one tile of U8_TILE positions per work item (curve_tiles.hpp u8_tile)
 __global__ __launch_bounds__(256)
 void curve_u8_kernel(CurveArgs a) {
     __shared__ double part[4][U8_TILE];
     __shared__ unsigned long long next_item;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 31, h = lane >> 5;
-    const uint8_t* __restrict__ dst = (const uint8_t*)a.dst_raw;
-    const uint8_t* __restrict__ src = (const uint8_t*)a.src_raw;
+    const int tid = threadIdx.x;
     for (;;) {
         __syncthreads();                                           // the previous item's LDS is consumed
         if (tid == 0) next_item = atomicAdd(a.queue, 1ull);
@@ -138,81 +77,21 @@ void curve_u8_kernel(CurveArgs a) {
         if (item >= a.n_items) break;
         const int k = find_request(a.desc, a.n, item);
         const CurveDesc d = a.desc[k];
-        const int M = d.tmpl_len, P = d.n_pos;
-        const int p0 = (int)(item - d.first_item) * U8_TILE;
-        const TemplStats ts = templ_stats(a.src_s1, a.src_s2, d.tmpl_off, M, a.centre);
-        const double* __restrict__ w1 = a.dst_s1 + d.win_start;
-        const double* __restrict__ w2 = a.dst_s2 + d.win_start;
-        int need = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) need |= needs_corr(a, ts, w1, w2, (int64_t)p0 + tid + 256 * q, P, M);
-        const bool any = __syncthreads_or(need) != 0;              // (uniform)
-
-        double acc2[16];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc2[e] = 0.0;
-        if (any) {
-            const int steps = (M + 32 * 31 + 31) / 32;
-            const int s_lo = (int)((int64_t)steps * wave / 4), s_hi = (int)((int64_t)steps * (wave + 1) / 4);
-            const uint8_t* __restrict__ trow = src + d.tmpl_off;
-            const int64_t g0 = d.win_start + p0 + r + 16 * h;      // dst sample of B's byte 0 at step 0
-            const int64_t t0 = 16 * h - 32 * r;                    // pattern sample of A's byte 0 at step 0
-            for (int f0 = s_lo; f0 < s_hi; f0 += FOLD_STEPS) {
-                const int f1 = min(s_hi, f0 + FOLD_STEPS);
-                i32x16 acc;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[e] = 0;
-                i32x4 A = load_centred16(trow, t0 + 32 * (int64_t)f0, 0, M);
-                i32x4 B = load_centred16(dst, g0 + 32 * (int64_t)f0, 0, a.dst_len);
-                for (int s = f0; s < f1; ++s) {
-                    // the next step's operands are requested before this step's product (the last step re-requests its own)
-                    const int sn = s + 1 < f1 ? s + 1 : s;
-                    const i32x4 An = load_centred16(trow, t0 + 32 * (int64_t)sn, 0, M);
-                    const i32x4 Bn = load_centred16(dst, g0 + 32 * (int64_t)sn, 0, a.dst_len);
-                    acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(A, B, acc, 0, 0, 0);
-                    A = An; B = Bn;
-                }
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc2[e] += (double)acc[e];
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 16; ++e) part[wave][32 * ((e & 3) + 8 * (e >> 2) + 4 * h) + r] = acc2[e];
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int i = tid + 256 * q;
-            const int64_t p = (int64_t)p0 + i;
-            if (p < P) {
-                const double corr_c = ((part[0][i] + part[1][i]) + part[2][i]) + part[3][i];   // integers: exact in any order
-                a.out[d.out_off + p] = curve_value(a, ts, corr_c, true, w1, w2, p, M);
-            }
-        }
+        const int64_t p0 = (item - d.first_item) * U8_TILE;
+        float* __restrict__ out = a.out + d.out_off;
+        u8_tile(a.src, TileReq{d.tmpl_off, d.win_start, d.tmpl_len, d.n_pos}, p0, part,
+                [&](int, int64_t p, float v) { out[p] = v; });
     }
 }
 
-// ------------------------------------------------------------------------------------------------------------------------
-// float32: the canonical chain.  sum T*I over the samples as they are, in float64, XM pattern samples at a time: each chunk
-// summed sequentially from its first sample, one fused multiply-add per sample, the chunk sums added in chunk order (the order
-// sushi_hip.hip's exact stages keep).  A work item is 256 NPOS consecutive positions; a thread owns NPOS consecutive ones,
-// which share its loads: at every sample the NPOS window values it needs are the previous sample's shifted by one.  XG chunks
-// of the pattern and the window samples under them are staged in LDS as float64 at a time.
-// ------------------------------------------------------------------------------------------------------------------------
-constexpr int XM = 512;           // pattern samples per chunk of the canonical sum (sushi_hip.hip XM)
-constexpr int XG = 4;             // chunks staged together
-
+// float32: 256 NPOS positions per work item (curve_tiles.hpp f32_tile)
 template <int NPOS>
 __global__ __launch_bounds__(256)
 void curve_f32_kernel(CurveArgs a) {
-    constexpr int SPAN = 256 * NPOS;
     __shared__ double lt[XG * XM];
-    __shared__ double li[SPAN + XG * XM + (SPAN + XG * XM) / 32 + 1];
+    __shared__ double li[f32_li_doubles<NPOS>()];
     __shared__ unsigned long long next_item;
     const int tid = threadIdx.x;
-    const float* __restrict__ dst = (const float*)a.dst_raw;
-    const float* __restrict__ src = (const float*)a.src_raw;
-    // window samples are staged with one padding element every 32: lanes NPOS samples apart then spread over the banks
-    auto sk = [](const int e) { return e + (e >> 5); };
     for (;;) {
         __syncthreads();
         if (tid == 0) next_item = atomicAdd(a.queue, 1ull);
@@ -221,56 +100,96 @@ void curve_f32_kernel(CurveArgs a) {
         if (item >= a.n_items) break;
         const int k = find_request(a.desc, a.n, item);
         const CurveDesc d = a.desc[k];
-        const int M = d.tmpl_len, P = d.n_pos;
-        const int p0 = (int)(item - d.first_item) * SPAN;
-        const int n_chunks = (M + XM - 1) / XM;
-        const TemplStats ts = templ_stats(a.src_s1, a.src_s2, d.tmpl_off, M, a.centre);
-        const double* __restrict__ w1 = a.dst_s1 + d.win_start;
-        const double* __restrict__ w2 = a.dst_s2 + d.win_start;
-        const float* __restrict__ Tp = src + d.tmpl_off;
-        const int64_t ibase = d.win_start + p0;                    // dst sample under position p0, pattern sample 0
-        int need = 0;
+        const int64_t p0 = (item - d.first_item) * (256 * NPOS);
+        float* __restrict__ out = a.out + d.out_off;
+        f32_tile<NPOS>(a.src, TileReq{d.tmpl_off, d.win_start, d.tmpl_len, d.n_pos}, p0, lt, li,
+                       [&](int, int64_t p, float v) { out[p] = v; });
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Threshold run: every position of the listed block pairs, exactly, a TILE of a pair per work item (item =
+// list slot x TILES_PER_PAIR + tile: the tiles of a pair run side by side and share its pattern in the L2).  The same tile bodies
+// as the curves, so a hit's score is the curve's value at that position, bit for bit.
+//   pass 0: the tile's hit bits (THR_MASK), its hit count (THR_COUNT) and its smallest ranking score (THR_MIN: the bound's audit)
+//           into the pair's row -- every word of the tile, plain stores, so nothing has to be cleared first;
+//   pass 1: tiles with hits, after thr_scan_kernel (sushi_fft_threshold.inc) has left each pair's first output slot (THR_OFF):
+//           evaluated again, every hit to its slot -- the pair's slot + the hits of the tiles before + the set bits before it.
+// A tile is 1024 positions for both sample types (f32_tile<4>).
+// ------------------------------------------------------------------------------------------------------------------------
+static_assert(TILE == U8_TILE && TILE == 256 * 4 && TILE / 32 == 32, "a tile's hit bits are 32 words");
+
+template <bool U8>
+__global__ __launch_bounds__(256)
+void threshold_tiles_kernel(ThresholdTileParams a) {
+    constexpr int LDS_DOUBLES = U8 ? 4 * U8_TILE : XG * XM + f32_li_doubles<4>();
+    __shared__ double lds[LDS_DOUBLES];
+    __shared__ unsigned mask[TILE / 32];
+    __shared__ int wpre[TILE / 32];
+    __shared__ unsigned red_min;
+    const int tid = threadIdx.x;
+    const TileSrc src{a.r.dst_raw, a.r.dst_s1, a.r.dst_s2, a.r.dst_len, a.r.src_raw, a.r.src_s1, a.r.src_s2, a.r.centre, a.method};
+    const bool cc = a.method == SUSHI_HIP_METHOD_CCOEFF_NORMED;
+    const int n_list = a.list_count ? *a.list_count : a.list_max;
+    const int64_t n_items = (int64_t)n_list * TILES_PER_PAIR;
+    for (int64_t it = blockIdx.x; it < n_items; it += gridDim.x) {
+        const int slot = (int)(it / TILES_PER_PAIR), t = (int)(it % TILES_PER_PAIR);
+        const int pr = a.list[slot];
+        const int k = a.pairmap[pr];
+        const SearchDesc sd = a.searches[k];
+        const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
+        const int64_t pairI = lay.pair0 + (a.sub_first_pair + pr - sd.first_pair);
+        const int64_t p0 = pairI * FFT_STEP * (int64_t)FFT_SEG + (int64_t)t * TILE - sd.win_start;   // (request coordinates)
+        const TileReq rq{sd.tmpl_off, sd.win_start, sd.tmpl_len, sd.n_pos};
+        uint32_t* __restrict__ row = a.rows + (size_t)pr * THR_SLOT_WORDS;
+        const bool valid = p0 + TILE > 0 && p0 < sd.n_pos;                 // (uniform) the tile holds a position of the window
+        auto eval = [&](auto&& emit) {
+            if constexpr (U8) u8_tile(src, rq, p0, reinterpret_cast<double(*)[U8_TILE]>(lds), emit);
+            else f32_tile<4>(src, rq, p0, lds, lds + XG * XM, emit);
+        };
+        __syncthreads();                                                    // the previous item's LDS is consumed
+        if (a.pass == 0) {
+            if (tid < TILE / 32) mask[tid] = 0u;
+            if (tid == 0) red_min = 0x7f800000u;                            // +inf (ranking scores are >= 0: uint order is float order)
+            __syncthreads();
+            float my_min = __builtin_inff();
+            if (valid)
+                eval([&](int i, int64_t, float v) {
+                    const bool hit = cc ? (double)v >= a.threshold : (double)v <= a.threshold;
+                    if (hit) atomicOr(&mask[i >> 5], 1u << (i & 31));
+                    my_min = fminf(my_min, cc ? 1.0f - v : v);
+                });
+            atomicMin(&red_min, __float_as_uint(my_min));                 // (LDS: once per thread, after the tile)
+            __syncthreads();
+            if (tid < 64) {
+                const unsigned m = tid < TILE / 32 ? mask[tid] : 0u;
+                if (tid < TILE / 32) row[THR_MASK + t * (TILE / 32) + tid] = m;
+                int c = __popc(m);
 #pragma unroll
-        for (int q = 0; q < NPOS; ++q) need |= needs_corr(a, ts, w1, w2, (int64_t)p0 + NPOS * tid + q, P, M);
-        const bool any = __syncthreads_or(need) != 0;              // (uniform)
-        double tot[NPOS];
-#pragma unroll
-        for (int q = 0; q < NPOS; ++q) tot[q] = 0.0;
-        for (int c0 = 0; any && c0 < n_chunks; c0 += XG) {
-            const int m0 = c0 * XM;
-            const int gm = min(XG * XM, M - m0);                   // pattern samples of this group
-            __syncthreads();                                       // the previous group's reads are done
-            for (int e = tid; e < gm; e += 256) lt[e] = (double)Tp[m0 + e];
-            const int wn = SPAN + gm - 1;                          // window samples the group's positions read
-            for (int e = tid; e < wn; e += 256) {
-                const int64_t g = ibase + m0 + e;
-                li[sk(e)] = g < a.dst_len ? (double)dst[g] : 0.0;
+                for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+                if (tid == 0) { row[THR_COUNT + t] = (uint32_t)c; row[THR_MIN + t] = red_min; }
+            }
+        } else {
+            const int cnt = (int)row[THR_COUNT + t];
+            if (cnt == 0 || !valid) continue;                               // (uniform)
+            int before = (int)row[THR_OFF];
+            for (int u = 0; u < t; ++u) before += (int)row[THR_COUNT + u];
+            if (before >= a.capacity) continue;                             // (uniform) nothing of this tile fits
+            if (tid < TILE / 32) mask[tid] = row[THR_MASK + t * (TILE / 32) + tid];
+            __syncthreads();
+            if (tid == 0) {
+                int s = 0;
+                for (int w = 0; w < TILE / 32; ++w) { wpre[w] = s; s += __popc(mask[w]); }
             }
             __syncthreads();
-            for (int c = 0; c < XG && m0 + c * XM < M; ++c) {
-                const int mb = c * XM;                             // chunk start inside the staged group
-                const int mc = min(XM, M - m0 - mb);
-                double acc[NPOS];
-                double w[NPOS];
-#pragma unroll
-                for (int q = 0; q < NPOS; ++q) { acc[q] = 0.0; w[q] = li[sk(NPOS * tid + mb + q)]; }
-                for (int m = 0; m < mc; ++m) {
-                    const double t = lt[mb + m];
-#pragma unroll
-                    for (int q = 0; q < NPOS; ++q) acc[q] = __builtin_fma(t, w[q], acc[q]);
-                    // slide: position q's next window sample is position q + 1's current one
-#pragma unroll
-                    for (int q = 0; q + 1 < NPOS; ++q) w[q] = w[q + 1];
-                    w[NPOS - 1] = li[sk(NPOS * tid + mb + m + NPOS)];
+            SushiHipHit* __restrict__ out = a.hits + (size_t)(a.first_search + k) * (size_t)a.capacity;
+            eval([&](int i, int64_t p, float v) {
+                const unsigned m = mask[i >> 5];
+                if ((m >> (i & 31)) & 1u) {
+                    const int off = before + wpre[i >> 5] + __popc(m & ((1u << (i & 31)) - 1u));
+                    if (off < a.capacity) out[off] = SushiHipHit{(int32_t)p, v};
                 }
-#pragma unroll
-                for (int q = 0; q < NPOS; ++q) tot[q] += acc[q];   // chunk sums in chunk order
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < NPOS; ++q) {
-            const int64_t p = (int64_t)p0 + NPOS * tid + q;
-            if (p < P) a.out[d.out_off + p] = curve_value(a, ts, tot[q], false, w1, w2, p, M);
+            });
         }
     }
 }
@@ -284,6 +203,19 @@ bool request_ok(const SushiHipRequest& r, const SushiHipStream* dst, const Sushi
 }
 
 }  // namespace
+
+namespace sushi {
+
+int launch_threshold_tiles(const ThresholdTileParams& p, hipStream_t st) {
+    // a fixed grid striding over the items (their number is on the device): 256 CUs, a few workgroups each
+    const int64_t want = (int64_t)std::max(p.list_max, 1) * TILES_PER_PAIR;
+    const unsigned grid = (unsigned)std::min<int64_t>(want, 2048);
+    if (p.r.dtype == SUSHI_HIP_U8) hipLaunchKernelGGL(threshold_tiles_kernel<true>, dim3(grid), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(threshold_tiles_kernel<false>, dim3(grid), dim3(256), 0, st, p);
+    return launch_ok();
+}
+
+}  // namespace sushi
 
 extern "C" {
 
@@ -324,13 +256,10 @@ int sushi_hip_match_curves(const SushiHipStream* dst, const SushiHipStream* src,
     // (a pageable source: the runtime has staged it when the call returns, as for plan_and_upload's descriptors)
     if (hipMemcpyAsync(mem, up.data(), up.size(), hipMemcpyHostToDevice, st) != hipSuccess) return SUSHI_HIP_ELAUNCH;
     CurveArgs a;
-    a.dst_raw = dst->raw; a.dst_s1 = dst->s1; a.dst_s2 = dst->s2; a.dst_len = dst->n;
-    a.src_raw = src->raw; a.src_s1 = src->s1; a.src_s2 = src->s2;
-    a.centre = sushi_hip_centre(dst->dtype);
+    a.src = TileSrc{dst->raw, dst->s1, dst->s2, dst->n, src->raw, src->s1, src->s2, sushi_hip_centre(dst->dtype), method};
     a.desc = reinterpret_cast<const CurveDesc*>(mem + CURVE_HEAD);
     a.n = n; a.n_items = items;
     a.queue = reinterpret_cast<unsigned long long*>(mem);
-    a.method = method;
     a.out = out_dev;
     // a fixed grid that takes the items off the queue: 256 CUs, a few workgroups each
     const unsigned grid = (unsigned)(items < 2048 ? items : 2048);

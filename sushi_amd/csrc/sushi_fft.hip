@@ -44,6 +44,7 @@
 //   sushi_fft_ifft.inc     ifft_kernel / ifft_list_kernel: transform, scoring epilogue, error model, candidates
 //   sushi_fft_bound.inc    the pair exclusion: bound_kernel / bound_low_kernel / slb_kernel / pilot / survivor / second look / mac_rows_kernel
 //   sushi_fft_collect.inc  collect_kernel
+//   sushi_fft_threshold.inc  the threshold run's own kernels: seed, audit, extension, output scan
 //   sushi_fft_plan.inc     host: workspace layout, stage timing, the plan of a batch
 //   (this file)            the batch handle and the C ABI's entry points
 
@@ -56,6 +57,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -89,6 +91,7 @@ constexpr int LDS_FLOATS = sushi_fft::lds_floats<FFT_LOGN>();
 #include "sushi_fft_ifft.inc"
 #include "sushi_fft_bound.inc"
 #include "sushi_fft_collect.inc"
+#include "sushi_fft_threshold.inc"
 #include "sushi_fft_plan.inc"
 
 }  // namespace
@@ -149,6 +152,7 @@ struct SushiHipBatch {
     int bound_model = SUSHI_HIP_BOUND_WORST_CASE;   // (default) / SUSHI_HIP_BOUND_STATISTICAL: how the excluded side's roundings enter slb
     int last_band = -1;                 // form of the exclusion the last run used (its last sub-batch that went through it; -1: none did)
     bool last_whole_cut = false;        // the last run took the plan's one-sub-batch cut (Plan::subs_whole)
+    bool last_threshold = false;        // the last run was a threshold run (sushi_hip_batch_run_threshold)
     // AUTO learns from its own runs: a batch whose exclusion excluded next to nothing (searches without a match anywhere) runs
     // without it from then on, looking again every 64th run.  The last run's counts come back through 16 bytes of pinned host memory
     // behind an event that is only ever QUERIED: a run never waits for an earlier one.
@@ -420,9 +424,10 @@ static int launch_ifft(const RunCtx& c, const IfftArgs& x, unsigned grid, hipStr
 // The exclusion: a lower bound of every pair's scores first (three of the transform's four passes, no scoring); then the most
 // promising pair of every search, which leaves the search's threshold; then whatever the bound could not exclude (header of
 // bound_kernel).  `ip` leaves with the list of those pairs, to be transformed; `t0`: the bound's profile span, ended here.
-static int exclude_pairs(const RunCtx& c, const SubView& v, hipStream_t st, const int band, IfftArgs& ip, hipEvent_t& t0) {
+// the lower bound of every pair's scores (slb)
+static int bound_pairs(const RunCtx& c, const SubView& v, hipStream_t st, const int band, BoundArgs& ba) {
     const SubBatch& sb = v.sb;
-    BoundArgs ba = bound_args(c, v);
+    ba = bound_args(c, v);
     ba.band = band;
     ba.y = band ? (const uint2*)v.ylow : (const uint2*)v.y;
     // (bound_kernel adds to the pairs' accumulators; bound_low_kernel -- a wave per pair -- stores them)
@@ -442,6 +447,27 @@ static int exclude_pairs(const RunCtx& c, const SubView& v, hipStream_t st, cons
     };
     if (ba.worst_case) go(std::false_type()); else go(std::true_type());
     if (launch_ok() != SUSHI_HIP_OK || launch_slb(c, v, ba, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    return SUSHI_HIP_OK;
+}
+
+// the second look at what the band-split bound left (header of bound_low_exact_kernel): sharper bound, shorter list ->
+// ba.list2 / ba.list2_count
+static int second_look(const RunCtx& c, const SubView& v, hipStream_t st, BoundArgs& ba) {
+    ba.list = ba.slist; ba.list_count = ba.scount;
+    ba.list2 = v.slist2; ba.list2_count = v.scount + 5;
+    hipLaunchKernelGGL(bound_low_exact_kernel, dim3(256 * 4), dim3(BLE_T), 0, st, ba);
+    if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    if (launch_method(c.method, [&](auto m) { hipLaunchKernelGGL(slb_list_kernel<decltype(m)::value>, dim3(256 * 2), dim3(256), 0, st, ba); }) !=
+        SUSHI_HIP_OK)
+        return SUSHI_HIP_ELAUNCH;
+    hipLaunchKernelGGL(survivor2_kernel, dim3(256), dim3(256), 0, st, ba);
+    return launch_ok();
+}
+
+static int exclude_pairs(const RunCtx& c, const SubView& v, hipStream_t st, const int band, IfftArgs& ip, hipEvent_t& t0) {
+    const SubBatch& sb = v.sb;
+    BoundArgs ba;
+    if (bound_pairs(c, v, st, band, ba) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     prof_end(c.pc, t0, SUSHI_HIP_STAGE_BOUND, st);
     t0 = prof_begin(c.pc, st);
     hipLaunchKernelGGL(pilot_kernel, dim3((unsigned)v.n_sub), dim3(64), 0, st, ba);
@@ -454,16 +480,8 @@ static int exclude_pairs(const RunCtx& c, const SubView& v, hipStream_t st, cons
     if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     ip.order = ba.slist; ip.count = ba.scount; ip.audit_mark = ba.audit_mark;
     if (!band) return SUSHI_HIP_OK;
-    // the second look at what the bound left (header of bound_low_exact_kernel): sharper bound, shorter list
-    ba.list = ba.slist; ba.list_count = ba.scount;
-    ba.list2 = v.slist2; ba.list2_count = v.scount + 5;
-    hipLaunchKernelGGL(bound_low_exact_kernel, dim3(256 * 4), dim3(BLE_T), 0, st, ba);
-    if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-    if (launch_method(c.method, [&](auto m) { hipLaunchKernelGGL(slb_list_kernel<decltype(m)::value>, dim3(256 * 2), dim3(256), 0, st, ba); }) !=
-        SUSHI_HIP_OK)
-        return SUSHI_HIP_ELAUNCH;
-    hipLaunchKernelGGL(survivor2_kernel, dim3(256), dim3(256), 0, st, ba);
-    if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    // the second look at what the bound left
+    if (second_look(c, v, st, ba) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     ip.order = ba.list2; ip.count = ba.list2_count;
     // whole rows of what is left: pair by pair for the searches that left few (the usual case), by the dense
     // multiply-accumulate for the searches the bound could exclude little of (no match anywhere) -- decided per search and
@@ -576,6 +594,68 @@ static int run_sub(RunCtx& c, const SubView& v, hipStream_t st) {
     prof_end(c.pc, t0, SUSHI_HIP_STAGE_IFFT, st);
     if ((rc = stage_refine(c, v, st)) != SUSHI_HIP_OK) return rc;
     return stage_collect(c, v, st, ia);
+}
+
+// What one threshold run asks for: the threshold in ranking units as a search key (survivor_kernel reads U from it), and the output.
+struct ThresholdRun { double threshold; unsigned long long ukey; int32_t capacity; SushiHipHit* hits; int64_t* counts; };
+
+// One sub-batch of a threshold run (sushi_fft_threshold.inc): the bound, the survivors of U = the threshold, every
+// position of those pairs exactly, the output.  SUSHI_HIP_EXCLUDE_NEVER: every pair, no bound.
+static int run_sub_threshold(RunCtx& c, const SubView& v, hipStream_t st, const ThresholdRun& tr) {
+    SushiHipBatch* b = c.b;
+    const SubBatch& sb = v.sb;
+    const bool exclude = b->exclusion != SUSHI_HIP_EXCLUDE_NEVER;
+    ThresholdTileParams tp;
+    tp.r = c.r; tp.searches = c.searches + sb.a0; tp.pairmap = v.pairmap; tp.sub_first_pair = sb.first_pair; tp.first_search = sb.a0;
+    tp.list = v.order; tp.list_count = nullptr; tp.list_max = (int)sb.pairs; tp.rows = (uint32_t*)v.y; tp.method = c.method;
+    tp.threshold = tr.threshold; tp.pass = 0; tp.hits = tr.hits; tp.capacity = tr.capacity;
+    ThrArgs ta;
+    memset(&ta, 0, sizeof(ta));
+    ta.searches = c.searches + sb.a0; ta.first_search = sb.a0; ta.sub_first_pair = sb.first_pair; ta.n_sub = v.n_sub; ta.n_pairs = (int)sb.pairs;
+    ta.pairmap = v.pairmap; ta.rows = (const uint32_t*)v.y; ta.rows_w = (uint32_t*)v.y; ta.slb = v.slb; ta.viol = c.viol;
+    ta.counters = c.counters; ta.method = c.method; ta.counts_out = tr.counts;
+    // (tspec_kernel also leaves the sub-batch's pair -> search map, which every stage below reads)
+    int rc = stage_tspec(c, v, st);
+    if (rc != SUSHI_HIP_OK) return rc;
+    if (exclude) {
+        hipLaunchKernelGGL(thr_seed_kernel, dim3((unsigned)((v.n_sub + 255) / 256)), dim3(256), 0, st, c.gkeys + sb.a0, v.n_sub, tr.ukey, v.plist);
+        if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+        int band = 0;
+        if ((rc = decide_band(c, v, st, &band)) != SUSHI_HIP_OK) return rc;
+        if (launch_mac(c, v, st, band != 0, nullptr, v.items) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+        BoundArgs ba;
+        if (bound_pairs(c, v, st, band, ba) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+        // (no pilot pair: every pair is listed or excluded on its bound alone; the audit of the exclusion lists one excluded pair
+        // of every audited search all the same)
+        hipLaunchKernelGGL(survivor_kernel, dim3((unsigned)((sb.pairs + 255) / 256)), dim3(256), 0, st, ba);
+        if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+        tp.list = ba.slist; tp.list_count = ba.scount;
+        if (band) {
+            if (second_look(c, v, st, ba) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+            tp.list = ba.list2; tp.list_count = ba.list2_count;
+        }
+        ta.audit_mark = v.audit_mark; ta.list = tp.list; ta.list_count = tp.list_count;
+        // (the first list is free once the second look has read it; the whole-row form never used the second)
+        ta.list3 = band ? v.slist : v.slist2; ta.list3_count = v.scount + 7;
+    } else {
+        b->direct_pairs += sb.pairs;
+    }
+    if (launch_threshold_tiles(tp, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    ThresholdTileParams t3 = tp;
+    if (exclude) {
+        hipLaunchKernelGGL(thr_check_kernel, dim3((unsigned)std::min<int64_t>((sb.pairs + 255) / 256, 256)), dim3(256), 0, st, ta);
+        hipLaunchKernelGGL(thr_extend_kernel, dim3((unsigned)((sb.pairs + 255) / 256)), dim3(256), 0, st, ta);
+        if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+        t3.list = ta.list3; t3.list_count = ta.list3_count;
+        if (launch_threshold_tiles(t3, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    }
+    hipLaunchKernelGGL(thr_scan_kernel, dim3((unsigned)v.n_sub), dim3(256), 0, st, ta);
+    if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    if (tr.capacity == 0) return SUSHI_HIP_OK;                   // (counts only)
+    tp.pass = 1; t3.pass = 1;
+    if (launch_threshold_tiles(tp, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    if (exclude && launch_threshold_tiles(t3, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    return SUSHI_HIP_OK;
 }
 
 extern "C" {
@@ -802,7 +882,7 @@ int sushi_hip_batch_run(SushiHipBatch* b, double delta, int32_t* out_idx_dev, fl
     if (!b || !out_idx_dev || !out_score_dev) return SUSHI_HIP_EINVAL;
     const hipStream_t st0 = (hipStream_t)hip_stream;
     RunCtx c(b, delta);
-    b->last_stream = st0; b->ran = true; b->direct_pairs = 0;
+    b->last_stream = st0; b->ran = true; b->direct_pairs = 0; b->last_threshold = false;
     if (hipStreamWaitEvent(st0, b->uploaded, 0) != hipSuccess) return SUSHI_HIP_ELAUNCH;   // descriptors and plan have landed
     if (b->path == SUSHI_HIP_PATH_DIRECT)
         return launch_direct(c.r, c.searches, b->n, (int)b->n_tiles, b->variant, b->method, c.keys, out_idx_dev, out_score_dev, b->packed_out, st0);
@@ -854,6 +934,44 @@ int sushi_hip_batch_run(SushiHipBatch* b, double delta, int32_t* out_idx_dev, fl
     return rc;
 } catch (const std::bad_alloc&) { return SUSHI_HIP_ENOMEM; } catch (...) { return SUSHI_HIP_EINTERNAL; }     // nothing crosses the C boundary
 
+int sushi_hip_batch_run_threshold(SushiHipBatch* b, double threshold, int32_t capacity, SushiHipHit* out_hits_dev, int64_t* out_counts_dev,
+                                  void* hip_stream) try {
+    if (!b || !out_hits_dev || !out_counts_dev || capacity < 0 || !std::isfinite(threshold) || b->path != SUSHI_HIP_PATH_FFT)
+        return SUSHI_HIP_EINVAL;
+    if (((uintptr_t)out_hits_dev & 3) || ((uintptr_t)out_counts_dev & 7)) return SUSHI_HIP_EALIGN;
+    // U in ranking units (what the bound is a lower bound of: the score, 1 - the coefficient), rounded up to a float: a pair is
+    // excluded only if its bound is above it (survivor_kernel, with its slack)
+    const double u = b->method == SUSHI_HIP_METHOD_CCOEFF_NORMED ? 1.0 - threshold : threshold;
+    float uf = (float)u;
+    if (std::isfinite(uf) && (double)uf < u) uf = std::nextafter(uf, INFINITY);
+    uint32_t ubits;
+    memcpy(&ubits, &uf, sizeof(ubits));
+    const ThresholdRun tr{threshold, ((unsigned long long)ubits << 32) | 0xffffffffull, capacity, out_hits_dev, out_counts_dev};
+    const hipStream_t st0 = (hipStream_t)hip_stream;
+    RunCtx c(b, 0.0);
+    b->last_stream = st0; b->ran = true; b->direct_pairs = 0; b->last_threshold = true;
+    b->last_band = -1; b->last_whole_cut = false; b->last_suspended = 0;
+    if (hipStreamWaitEvent(st0, b->uploaded, 0) != hipSuccess) return SUSHI_HIP_ELAUNCH;   // descriptors and plan have landed
+    {
+        // flags, violation marks, every sub-batch's small counters, the pattern rows' norm accumulators, the run's counters
+        FillArgs fa;
+        memset(&fa, 0, sizeof(fa));
+        fa.p[0] = (uint32_t*)c.flags; fa.words[0] = (uint32_t)((b->lay.counters + align_up(sizeof(RunCounters), 256) - b->lay.flags) / 4);
+        fa.value[0] = 0u; fa.n = 1;
+        if (launch_fill(fa, st0) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    }
+    c.run_seq = b->run_seq++;
+    c.lanes = b->plan.lanes;
+    Lanes lanes(b, st0);
+    int rc = lanes.fork(b->plan.lanes);
+    if (rc != SUSHI_HIP_OK) return rc;
+    for (size_t si = 0; si < b->plan.subs.size(); ++si) {
+        const SubBatch& sb = b->plan.subs[si];
+        if ((rc = run_sub_threshold(c, SubView(b->mem, b->lay, b->plan.ws_lane, sb, si), lanes.st[sb.lane], tr)) != SUSHI_HIP_OK) return rc;
+    }
+    return lanes.join();
+} catch (const std::bad_alloc&) { return SUSHI_HIP_ENOMEM; } catch (...) { return SUSHI_HIP_EINTERNAL; }     // nothing crosses the C boundary
+
 int sushi_hip_batch_diagnostics(SushiHipBatch* b, SushiHipBatchDiag* diag, float* ranking_err_host, int32_t* flagged_host) try {
     if (!b || !diag) return SUSHI_HIP_EINVAL;
     memset(diag, 0, sizeof(*diag));
@@ -879,6 +997,13 @@ int sushi_hip_batch_diagnostics(SushiHipBatch* b, SushiHipBatchDiag* diag, float
     diag->suspended = b->last_suspended;
     diag->band_votes[0] = b->band_votes[0]; diag->band_votes[1] = b->band_votes[1];
     diag->second_look_audited = (int64_t)c.second_look_audited;
+    if (b->last_threshold) {
+        // (a threshold run: the bound's figures only -- its exact stage is not the search's)
+        diag->suspended = 0; diag->band_votes[0] = diag->band_votes[1] = 0; diag->second_look_audited = 0;
+        if (ranking_err_host) memset(ranking_err_host, 0, (size_t)b->n * sizeof(float));
+        if (flagged_host) memset(flagged_host, 0, (size_t)b->n * sizeof(int32_t));
+        return SUSHI_HIP_OK;
+    }
     std::vector<int32_t> fl((size_t)b->n);
     if (hipMemcpy(fl.data(), b->mem + b->lay.flags, (size_t)b->n * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
         return SUSHI_HIP_ELAUNCH;

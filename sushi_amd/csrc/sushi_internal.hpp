@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/sushi_hip.h"
+#include "sushi_common.hpp"
 
 // The opaque stream handle of the C ABI: where the parts of a prepared stream live (all inside the caller's buffer).
 struct SushiHipStream {
@@ -138,6 +139,33 @@ struct TileParams {
     int method;                       // SUSHI_HIP_METHOD_*
 };
 int launch_tiles(const TileParams& p, hipStream_t st);
+
+// FFT path, threshold run (sushi_hip_batch_run_threshold).  A listed block pair is evaluated exactly at each of its
+// 2 FFT_H positions, as TILES_PER_PAIR tiles of TILE consecutive ones (the curves' tile bodies, sushi_curve.hip).  What a pair
+// leaves lies in its own 64 KB row of the sub-batch's Y region (a threshold run forms no whole rows after the bound has read them):
+constexpr int THR_MASK = 0;                                    // [TILES_PER_PAIR * TILE / 32] bit i: position i of the pair passes
+constexpr int THR_COUNT = TILES_PER_PAIR * TILE / 32;          // [TILES_PER_PAIR] hits per tile
+constexpr int THR_MIN = THR_COUNT + TILES_PER_PAIR;            // [TILES_PER_PAIR] float bits: smallest ranking score of the tile
+constexpr int THR_OFF = THR_MIN + TILES_PER_PAIR;              // the pair's first hit in its search's output (thr_scan_kernel)
+constexpr int THR_SLOT_WORDS = FFT_N;                          // 32-bit words of a pair's row (FFT_N packed-half bins)
+static_assert(THR_OFF < THR_SLOT_WORDS, "a pair's hit mask and counts fit its row");
+struct ThresholdTileParams {
+    StreamRefs r;
+    const SearchDesc* searches;       // the sub-batch's searches
+    const int* pairmap;               // [pairs of the sub-batch] -> search of the sub-batch
+    int sub_first_pair;
+    int first_search;                 // global index of searches[0]: its output slot
+    const int* list;                  // the pairs to evaluate: list[0 .. *list_count), or [0 .. list_max) where list_count is NULL
+    const int* list_count;
+    int list_max;
+    uint32_t* rows;                   // [pairs of the sub-batch][THR_SLOT_WORDS]
+    int method;
+    double threshold;                 // SQDIFF_NORMED: score <= threshold; CCOEFF_NORMED: score >= threshold
+    int pass;                         // 0: hit masks, counts and minima; 1: (index, score) of every hit into `hits`
+    SushiHipHit* hits;                // [searches][capacity]
+    int32_t capacity;
+};
+int launch_threshold_tiles(const ThresholdTileParams& p, hipStream_t st);
 int launch_unpack(const unsigned long long* keys_dev, int n, int method, int32_t* out_idx_dev, float* out_score_dev,
                   int32_t* out_packed_dev, hipStream_t st);
 

@@ -419,6 +419,50 @@ class SearchBatch(object):
         _native.check(rc, "sushi_hip_batch_run")
         return self.out_idx, self.out_score
 
+    def run_threshold(self, threshold, capacity, hip_stream=None):
+        """Every position of every request whose score passes `threshold` (sushi_hip_batch_run_threshold; FFT path, asynchronous):
+        score <= threshold for 'sqdiff_normed', score >= threshold for 'ccoeff_normed' (the coefficient itself).  Returns
+        (hits, counts): an int32 CUDA tensor [n, capacity, 2] of (index, score bits) records -- request k's hits in ascending
+        index order in hits[k, :min(counts[k], capacity)], the rest unwritten -- and an int64 CUDA tensor [n] of how many hits
+        each request has (also beyond `capacity`).  Each score is bit-identical to the curve's value at that position."""
+        if self.path != "fft":
+            raise SushiError("threshold runs need the FFT path")
+        capacity = int(capacity)
+        if capacity < 0:
+            raise SushiError("capacity must be >= 0")
+        threshold = float(threshold)
+        if not np.isfinite(threshold):
+            raise SushiError("threshold must be finite")
+        dev = self.dst.device
+        with torch.cuda.device(dev):
+            hits = torch.empty((self.n, capacity, 2), dtype=torch.int32, device=dev)
+            counts = torch.empty(self.n, dtype=torch.int64, device=dev)
+            # (capacity 0: a valid pointer all the same -- nothing is written through it)
+            hp = hits.data_ptr() if hits.numel() else counts.data_ptr()
+            st = _raw_stream(dev) if hip_stream is None else hip_stream
+            rc = _native.lib().sushi_hip_batch_run_threshold(self._handle, threshold, capacity, hp, counts.data_ptr(), st)
+            _native.check(rc, "sushi_hip_batch_run_threshold")
+        return hits, counts
+
+    def occurrences(self, threshold, capacity=None):
+        """[(index int64 ndarray, score float32 ndarray) per request]: every position whose score passes `threshold`
+        (run_threshold), in ascending index order.  capacity: hits kept per request in the first run (None: 4096); where a request
+        has more, the batch runs once more with room for all of them.  Synchronises."""
+        cap = 4096 if capacity is None else int(capacity)
+        hits, counts = self.run_threshold(threshold, cap)
+        cnt = counts.cpu().numpy()
+        need = int(cnt.max()) if cnt.size else 0
+        if need > cap:
+            hits, counts = self.run_threshold(threshold, need)
+            cnt = counts.cpu().numpy()
+            cap = need
+        h = hits.cpu().numpy() if cap else np.zeros((self.n, 0, 2), np.int32)
+        out = []
+        for k in range(self.n):
+            rec = h[k, :int(cnt[k])]
+            out.append((rec[:, 0].astype(np.int64), np.ascontiguousarray(rec[:, 1]).view(np.float32)))
+        return out
+
     def results(self):
         """(idx int32 ndarray, score float32 ndarray) -- synchronises."""
         if self._early_np is not None:

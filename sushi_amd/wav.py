@@ -406,6 +406,55 @@ class WavStream(object):
             src_dev = DeviceStream(np.concatenate(rows), device=dst_dev.device)
         return src_dev, offs, lens, one_owner
 
+    # ------------------------------------------------------------------ every occurrence
+    def find_occurrences(self, pattern, threshold, window_center=None, window_size=None, method="ccoeff_normed",
+                         min_separation=None):
+        """Every position of find_substream's window (wav.py:178-184) whose score passes `threshold` -- all occurrences of the
+        pattern, not only the best one: np.where(result >= threshold) on wav.py:185's row for 'ccoeff_normed' (default; the
+        TM_CCOEFF_NORMED value itself), np.where(result <= threshold) for 'sqdiff_normed'.  No window: the widest _window allows
+        (centre duration / 2, size duration / 2 + PADDING_SECONDS: the whole stream).  min_separation (seconds, or None): keep one
+        hit per occurrence -- the best, no two kept hits closer than that (sushi_amd.occurrences.peaks).  Returns (scores float32
+        ndarray, times list of float) sorted by time; a time is what find_substream returns for that position."""
+        return self.find_occurrences_many([pattern], threshold, [window_center], [window_size], method=method,
+                                          min_separation=min_separation)[0]
+
+    def find_occurrences_many(self, patterns, threshold, window_centers=None, window_sizes=None, method="ccoeff_normed",
+                              min_separation=None, capacity=None):
+        """[find_occurrences(p, threshold, c, w) for p, c, w in zip(...)] in one threshold run (patterns located as
+        find_substreams does).  window_centers / window_sizes: lists (None entries, or None for the list: the widest window)."""
+        from .device import SearchBatch
+        from .occurrences import peaks
+        n = len(patterns)
+        centres = [None] * n if window_centers is None else list(window_centers)
+        sizes = [None] * n if window_sizes is None else list(window_sizes)
+        if not (len(centres) == len(sizes) == n) or n == 0:
+            raise SushiError('find_occurrences_many: need equally many patterns, centres and sizes (>= 1)')
+        dst_dev = self.device_stream()
+        src_dev, offs, lens, _ = self._pattern_source(patterns, dst_dev)
+        start_times, win_start, n_pos = [], [], []
+        for m, c, w in zip(lens, centres, sizes):
+            c, w = self._widest(c, w)
+            st, lo, p = self._window(m, c, w)
+            start_times.append(st)
+            win_start.append(lo)
+            n_pos.append(p)
+        batch = SearchBatch(dst_dev, src_dev, offs, lens, win_start, n_pos, path="fft", method=method)
+        found = batch.occurrences(threshold, capacity)
+        out = []
+        for st, (idx, score) in zip(start_times, found):
+            if min_separation is not None:
+                idx, score = peaks(idx, score, int(round(float(min_separation) * self.sample_rate)), method)
+            out.append((np.asarray(score, np.float32), [st + (int(k) / float(self.sample_rate)) for k in idx]))
+        return out
+
+    def _widest(self, window_center, window_size):
+        """find_occurrences' default window: the widest _window allows -- the whole stream, padding included."""
+        if window_center is None:
+            window_center = self.duration_seconds / 2.0
+        if window_size is None:
+            window_size = self.duration_seconds / 2.0 + self.PADDING_SECONDS
+        return window_center, window_size
+
     # ------------------------------------------------------------------ whole curves
     def match_template(self, pattern, window_center, window_size, method="sqdiff_normed"):
         """wav.py:185's `result` itself: cv2.matchTemplate(search_source, pattern, method) over find_substream's window
