@@ -42,7 +42,8 @@ extern "C" {
                                      of the library's own, forked off and joined back into the stream a run is given;
                                      sushi_hip_batch_set_early_output, sushi_hip_device_prepare;
                                      13 (additive): sushi_hip_curve_bytes, sushi_hip_match_curves;
-                                     13 (additive): SushiHipHit, sushi_hip_batch_run_threshold */
+                                     13 (additive): SushiHipHit, sushi_hip_batch_run_threshold;
+                                     13 (additive): SUSHI_HIP_BEST_MAX_K, sushi_hip_batch_run_best */
 
 #if defined(__GNUC__)
 #define SUSHI_HIP_API __attribute__((visibility("default")))
@@ -337,6 +338,38 @@ typedef struct SushiHipHit {
 /* FFT path.  out_hits_dev: [n][capacity] hits; out_counts_dev: [n] int64. */
 SUSHI_HIP_API int sushi_hip_batch_run_threshold(SushiHipBatch* batch, double threshold, int32_t capacity,
                                                 SushiHipHit* out_hits_dev, int64_t* out_counts_dev, void* hip_stream);
+
+/* ---- the K best distinct matches of every search -----------------------------------------
+ * Is the best match the only one, and if not, where are the others, best first?  FFT path only.  For request k of the batch with
+ * curve c (sushi_hip_match_curves of that request, same method), separation S >= 1 and K in 1 .. SUSHI_HIP_BEST_MAX_K, the first K
+ * picks of greedy suppression over the whole score row:
+ *   eligible positions: all of [0, n_pos), or with a threshold only those that pass it, compared as sushi_hip_batch_run_threshold
+ *   compares (c[p] <= *threshold for SQDIFF_NORMED, c[p] >= *threshold for CCOEFF_NORMED);
+ *   pick j = 1, 2, ...: among the eligible positions at least S away from every earlier pick (|p - g_i| >= S), the best float32
+ *   score VALUE (lowest for SQDIFF_NORMED, highest for CCOEFF_NORMED: the score itself, not 1 - score; -0.0 and 0.0 are one
+ *   value), ties by the lower index; the picks end after K of them or when no position is left.
+ * out_hits_dev[k * K + j], j < out_counts_dev[k]: pick j + 1 of request k (best first), its score bit-identical to c[index];
+ * out_counts_dev[k]: picks made (<= K); the slots behind them are not written.  min_separation 0 means each request's own tmpl_len
+ * (occurrences that do not overlap).  The output depends on the requests, the method, K, S and the threshold only: not on
+ * sub-batches, lanes, the exclusion's mode or form, or earlier runs.  With K = 1 and no threshold, index and score bits are
+ * sushi_hip_batch_run's.
+ * Exactness rests on the pair exclusion's WORST_CASE bound alone: a block pair is left unevaluated only if its bound is above the
+ * score, in ranking units rounded up to a float, of the K-th pick made from the evaluated pairs (or above the threshold); that is
+ * checked again whenever more pairs have been evaluated, since the K-th pick's score is not monotone in the evaluated set.
+ * SUSHI_HIP_EXCLUDE_NEVER evaluates every pair.  An audited excluded pair is evaluated all the same; one that holds a position as
+ * good as its search's K-th pick, or a score below its bound, is a bound violation (slb_violations): every pair of that search is
+ * then evaluated in the same run.
+ * K beyond the number of real occurrences makes the K-th pick a chance-level score that no bound excludes much under: the run then
+ * evaluates most of the window exactly.  Callers who want a runner-up "if there is one" pass a threshold.
+ * EINVAL before any HIP call: NULL batch or outputs, k < 1 or > SUSHI_HIP_BEST_MAX_K, min_separation < 0, a *threshold that is not
+ * finite, a direct-path batch; EALIGN: an output that is not 4-byte aligned.  Synchronisation, device memory, diagnostics, early and
+ * packed records, what AUTO has learnt: as for sushi_hip_batch_run_threshold; flagged_host[k] of sushi_hip_batch_diagnostics is the
+ * last round that evaluated a pair of request k (1: the first pairs, 2 and 3: the rounds behind them, 4: the last stage, which
+ * evaluates every pair of a request still unsettled and the audit's; 0 under SUSHI_HIP_EXCLUDE_NEVER). */
+#define SUSHI_HIP_BEST_MAX_K 32
+/* FFT path.  threshold: NULL = none.  out_hits_dev: [n][k] picks; out_counts_dev: [n] int32. */
+SUSHI_HIP_API int sushi_hip_batch_run_best(SushiHipBatch* batch, int32_t k, int32_t min_separation, const double* threshold,
+                                           SushiHipHit* out_hits_dev, int32_t* out_counts_dev, void* hip_stream);
 
 /* FFT path geometry of one request: block pairs (inverse transforms) and pattern segments (forward transforms). */
 SUSHI_HIP_API int sushi_hip_fft_layout(int64_t win_start, int32_t n_pos, int32_t tmpl_len,

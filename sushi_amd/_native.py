@@ -18,6 +18,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sushi_hip.h")
 U8, F32 = 0, 1
 PATH_FFT, PATH_DIRECT = 0, 1
 METHOD_SQDIFF_NORMED, METHOD_CCOEFF_NORMED = 0, 1       # cv2.TM_SQDIFF_NORMED + argmin (wav.py:185-186) | cv2.TM_CCOEFF_NORMED + argmax
+BEST_MAX_K = 32            # SUSHI_HIP_BEST_MAX_K: picks per request of a best-K run (sushi_hip_batch_run_best)
 METHODS = {"sqdiff_normed": METHOD_SQDIFF_NORMED, "ccoeff_normed": METHOD_CCOEFF_NORMED}
 VIEW_XC, VIEW_S1, VIEW_S2, VIEW_UREL, VIEW_BASE, VIEW_SPECTRA, VIEW_USREL, VIEW_BASE1, VIEW_COARSE, VIEW_SPECTRA_LOW, \
     VIEW_ZNORM_REST = range(11)
@@ -130,6 +131,8 @@ def lib():
     L.sushi_hip_batch_run.argtypes = [vp, dbl, vp, vp, vp]
     L.sushi_hip_batch_run_threshold.restype = ci
     L.sushi_hip_batch_run_threshold.argtypes = [vp, dbl, i32, vp, vp, vp]
+    L.sushi_hip_batch_run_best.restype = ci
+    L.sushi_hip_batch_run_best.argtypes = [vp, i32, i32, ctypes.POINTER(dbl), vp, vp, vp]
     L.sushi_hip_batch_diagnostics.restype = ci
     L.sushi_hip_batch_diagnostics.argtypes = [vp, ctypes.POINTER(BatchDiag), vp, vp]
     L.sushi_hip_batch_set_packed_output.restype = ci

@@ -5,7 +5,7 @@ The translation units, compiled separately (the MFMA kernel alone takes ~2 min) 
   csrc/sushi_fft.hip  overlap-save FFT path
   csrc/sushi_load.hip WavStream load pipeline (decimate / pad / median clip / scale / quantise)  (-ffp-contract=off)
   csrc/sushi_curve.hip whole score curves: i8 MFMA Toeplitz GEMM (uint8), canonical float64 chain (float32)  (-ffp-contract=off);
-                       the same tiles (csrc/curve_tiles.hpp) evaluate the listed pairs of a threshold run
+                       the same tiles (csrc/curve_tiles.hpp) evaluate the listed pairs of a threshold run and of a best-K run
 """
 import math
 import os
@@ -34,7 +34,7 @@ UNITS = [
       # the translation unit's parts, by stage (included inside its anonymous namespace)
       os.path.join(CSRC, "sushi_fft_store.inc"), os.path.join(CSRC, "sushi_fft_spectra.inc"), os.path.join(CSRC, "sushi_fft_mac.inc"),
       os.path.join(CSRC, "sushi_fft_ifft.inc"), os.path.join(CSRC, "sushi_fft_bound.inc"), os.path.join(CSRC, "sushi_fft_collect.inc"),
-      os.path.join(CSRC, "sushi_fft_plan.inc"), os.path.join(CSRC, "sushi_fft_threshold.inc"),
+      os.path.join(CSRC, "sushi_fft_plan.inc"), os.path.join(CSRC, "sushi_fft_threshold.inc"), os.path.join(CSRC, "sushi_fft_best.inc"),
       os.path.join(CSRC, "_gen_dft16_f16_bound.inc"), os.path.join(CSRC, "_gen_dft16_f16_bound_low.inc")]),
 ]
 

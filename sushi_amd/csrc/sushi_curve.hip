@@ -6,7 +6,8 @@
 //     on the VALU.
 // Either way each value is bit for bit what the exact stages produce for that position.  The tile bodies
 // (curve_tiles.hpp) also evaluate the listed block pairs of a threshold run (sushi_hip_batch_run_threshold):
-// threshold_tiles_kernel, launched from sushi_fft.hip through launch_threshold_tiles.
+// threshold_tiles_kernel, launched from sushi_fft.hip through launch_threshold_tiles; and those of a best-K run
+// (sushi_hip_batch_run_best): best_tiles_kernel and best_select_kernel.
 //
 // Stateless: no handle, no spectra; the request table and the tile queue live in the caller's workspace.
 
@@ -194,6 +195,206 @@ void threshold_tiles_kernel(ThresholdTileParams a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------------
+// Best-K run: the first K picks of greedy suppression over every search's whole score row, from the listed block
+// pairs alone.  The same tile bodies again, so a pick's score is the curve's value at that position, bit for bit.
+//   best_tiles_kernel   per tile of a listed pair: its best eligible position as a pick key (BEST_KEY) and its smallest ranking
+//                       score over all positions (THR_MIN) into the pair's row -- plain stores of every word a later kernel reads;
+//   best_select_kernel  a workgroup per search, K rounds: the smallest key over the evaluated pairs' tiles is the pick; tiles
+//                       wholly inside the pick's window (g - S, g + S) are dead, the at most two tiles the window's edges cut are
+//                       evaluated again with every pick so far masked (BEST_WORK is what the rounds read and write; BEST_KEY stays
+//                       as evaluated, for the next selection over more pairs).
+// ------------------------------------------------------------------------------------------------------------------------
+// the smaller key is the better pick: (score under the order-preserving map of float bits, negated for TM_CCOEFF_NORMED) | index
+// | whether the score is -0.0 (0.0 and -0.0 are one value to the order, as to NumPy's; the bit gives the curve's bits back)
+__device__ __forceinline__ unsigned long long pick_key(const float v, const int64_t p, const bool cc) {
+    const unsigned b = __float_as_uint(cc ? -(v + 0.0f) : v + 0.0f);
+    const unsigned u = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    return ((unsigned long long)u << 32) | ((unsigned long long)p << 1) | (__float_as_uint(v) == 0x80000000u ? 1ull : 0ull);
+}
+__device__ __forceinline__ int32_t pick_index(const unsigned long long key) { return (int32_t)((key & 0xffffffffull) >> 1); }
+__device__ __forceinline__ float pick_score(const unsigned long long key, const bool cc) {
+    if (key & 1ull) return -0.0f;
+    const unsigned u = (unsigned)(key >> 32);
+    const float s = __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+    return cc ? -s : s;
+}
+// the ranking score the pair bound is a lower bound of (the score; 1 - the coefficient formed in double), rounded UP to a float
+__device__ __forceinline__ float rank_up(const float v, const bool cc) {
+    if (!cc) return v;
+    const double u = 1.0 - (double)v;
+    float f = (float)u;
+    if ((double)f < u) f = f >= 0.f ? __uint_as_float(__float_as_uint(f + 0.0f) + 1u) : __uint_as_float(__float_as_uint(f) - 1u);
+    return fmaxf(f, 0.f);
+}
+
+__device__ __forceinline__ unsigned long long block_min_u64(unsigned long long v, unsigned long long* red4) {
+    v = wave_min_u64(v);
+    __syncthreads();                                                        // (red4's last readers are through)
+    if ((threadIdx.x & 63) == 0) red4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    unsigned long long m = red4[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) m = red4[w] < m ? red4[w] : m;
+    return m;
+}
+
+template <bool U8>
+__global__ __launch_bounds__(256)
+void best_tiles_kernel(BestParams a) {
+    constexpr int LDS_DOUBLES = U8 ? 4 * U8_TILE : XG * XM + f32_li_doubles<4>();
+    __shared__ double lds[LDS_DOUBLES];
+    __shared__ unsigned long long red4[4];
+    __shared__ unsigned red_min;
+    const int tid = threadIdx.x;
+    const TileSrc src{a.r.dst_raw, a.r.dst_s1, a.r.dst_s2, a.r.dst_len, a.r.src_raw, a.r.src_s1, a.r.src_s2, a.r.centre, a.method};
+    const bool cc = a.method == SUSHI_HIP_METHOD_CCOEFF_NORMED;
+    const int n_list = a.list_count ? min(*a.list_count, a.list_max) : a.list_max;
+    const int64_t n_items = (int64_t)n_list * TILES_PER_PAIR;
+    for (int64_t it = blockIdx.x; it < n_items; it += gridDim.x) {
+        const int slot = (int)(it / TILES_PER_PAIR), t = (int)(it % TILES_PER_PAIR);
+        const int pr = a.list[slot];
+        const int k = a.pairmap[pr];
+        const SearchDesc sd = a.searches[k];
+        const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
+        const int64_t pairI = lay.pair0 + (a.sub_first_pair + pr - sd.first_pair);
+        const int64_t p0 = pairI * FFT_STEP * (int64_t)FFT_SEG + (int64_t)t * TILE - sd.win_start;   // (request coordinates)
+        const TileReq rq{sd.tmpl_off, sd.win_start, sd.tmpl_len, sd.n_pos};
+        uint32_t* __restrict__ row = a.rows + (size_t)pr * THR_SLOT_WORDS;
+        const bool valid = p0 + TILE > 0 && p0 < sd.n_pos;                 // (uniform) the tile holds a position of the window
+        __syncthreads();                                                    // the previous item's LDS is consumed
+        if (tid == 0) red_min = 0x7f800000u;                                // +inf (ranking scores are >= 0: uint order is float order)
+        unsigned long long my_key = NO_KEY;
+        float my_min = __builtin_inff();
+        if (valid) {
+            auto emit = [&](int, int64_t p, float v) {
+                const bool ok = !a.has_threshold || (cc ? (double)v >= a.threshold : (double)v <= a.threshold);
+                const unsigned long long key = pick_key(v, p, cc);
+                if (ok && key < my_key) my_key = key;
+                my_min = fminf(my_min, rank_up(v, cc));
+            };
+            if constexpr (U8) u8_tile(src, rq, p0, reinterpret_cast<double(*)[U8_TILE]>(lds), emit);
+            else f32_tile<4>(src, rq, p0, lds, lds + XG * XM, emit);
+        }
+        const unsigned long long best = block_min_u64(my_key, red4);        // (its barriers also order red_min's reset and use)
+        atomicMin(&red_min, __float_as_uint(my_min));                       // (LDS: once per thread, after the tile)
+        __syncthreads();
+        if (tid == 0) {
+            reinterpret_cast<unsigned long long*>(row + BEST_KEY)[t] = best;
+            row[THR_MIN + t] = red_min;
+        }
+    }
+}
+
+template <bool U8>
+__global__ __launch_bounds__(256)
+void best_select_kernel(BestParams a) {
+    constexpr int LDS_DOUBLES = U8 ? 4 * U8_TILE : XG * XM + f32_li_doubles<4>();
+    __shared__ double lds[LDS_DOUBLES];
+    __shared__ unsigned long long red4[4];
+    __shared__ int64_t picks[BEST_MAX_K];
+    const int tid = threadIdx.x;
+    const int k = blockIdx.x;
+    if (k == 0 && tid == 0) {
+        if (a.reset0) *a.reset0 = 0;
+        if (a.reset1) *a.reset1 = 0;
+    }
+    if (a.stamp_flags && a.stamp_flags[a.first_search + k] != a.stamp) return;      // (uniform) nothing new for this search
+    const TileSrc src{a.r.dst_raw, a.r.dst_s1, a.r.dst_s2, a.r.dst_len, a.r.src_raw, a.r.src_s1, a.r.src_s2, a.r.centre, a.method};
+    const bool cc = a.method == SUSHI_HIP_METHOD_CCOEFF_NORMED;
+    const SearchDesc sd = a.searches[k];
+    const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
+    const TileReq rq{sd.tmpl_off, sd.win_start, sd.tmpl_len, sd.n_pos};
+    const int pr0 = sd.first_pair - a.sub_first_pair;
+    const int64_t S = a.min_separation > 0 ? a.min_separation : sd.tmpl_len;
+    const int K = a.k;
+    SushiHipHit* __restrict__ out = a.hits + (size_t)(a.first_search + k) * (size_t)K;
+    auto evaluated = [&](const int i) { return !a.audit_mark || (a.audit_mark[pr0 + i] & 2) != 0; };
+    auto keys_of = [&](const int i, const int what) {
+        return reinterpret_cast<unsigned long long*>(a.rows + (size_t)(pr0 + i) * THR_SLOT_WORDS + what);
+    };
+    // what the rounds work on: every evaluated tile as it was evaluated
+    for (int i = tid; i < lay.n_pairs; i += 256)
+        if (evaluated(i)) {
+            const unsigned long long* __restrict__ o = keys_of(i, BEST_KEY);
+            unsigned long long* __restrict__ w = keys_of(i, BEST_WORK);
+            for (int t = 0; t < TILES_PER_PAIR; ++t) w[t] = o[t];
+        }
+    __syncthreads();
+    int n_picks = 0;
+    float last = 0.f;
+    for (int j = 0; j < K; ++j) {
+        unsigned long long mine = NO_KEY;
+        for (int i = tid; i < lay.n_pairs; i += 256)
+            if (evaluated(i)) {
+                const unsigned long long* __restrict__ w = keys_of(i, BEST_WORK);
+                for (int t = 0; t < TILES_PER_PAIR; ++t) mine = w[t] < mine ? w[t] : mine;
+            }
+        const unsigned long long best = block_min_u64(mine, red4);
+        if (best == NO_KEY) break;                                          // (uniform) nothing eligible is left
+        const int64_t g = pick_index(best);
+        last = pick_score(best, cc);
+        if (tid == 0) { picks[j] = g; out[j] = SushiHipHit{(int32_t)g, last}; }
+        n_picks = j + 1;
+        if (n_picks == K) break;
+        __syncthreads();                                                    // picks[j] is there
+        // the pick's window (g - S, g + S), cut to the row: tiles wholly inside are dead, the tiles that hold its ends are looked at
+        const int64_t lo = max((int64_t)0, g - S + 1), hi = min((int64_t)sd.n_pos - 1, g + S - 1);
+        const int64_t a_lo = (lo + sd.win_start) / TILE, a_hi = (hi + sd.win_start) / TILE;       // (tiles of the absolute grid)
+        auto tile_keys = [&](const int64_t at, int* t) -> unsigned long long* {
+            const int64_t i = at / TILES_PER_PAIR - lay.pair0;
+            *t = (int)(at % TILES_PER_PAIR);
+            return i >= 0 && i < lay.n_pairs && evaluated((int)i) ? keys_of((int)i, BEST_WORK) : nullptr;
+        };
+        for (int64_t at = a_lo + 1 + tid; at < a_hi; at += 256) {
+            int t;
+            unsigned long long* w = tile_keys(at, &t);
+            if (w) w[t] = NO_KEY;
+        }
+        for (int e = 0; e < (a_hi > a_lo ? 2 : 1); ++e) {
+            const int64_t at = e ? a_hi : a_lo;
+            int t;
+            unsigned long long* w = tile_keys(at, &t);                      // (uniform)
+            if (!w) continue;
+            const int64_t p0 = at * TILE - sd.win_start;
+            const int64_t t_lo = max((int64_t)0, p0), t_hi = min((int64_t)sd.n_pos - 1, p0 + TILE - 1);
+            // (through the reduction: one value for every thread whatever each of them read, and its barriers order the earlier
+            // stores to w[t] and the tile body's use of the LDS)
+            if (block_min_u64(w[t], red4) == NO_KEY) continue;              // dead already, or nothing eligible in it
+            if (t_lo >= lo && t_hi <= hi) {
+                __syncthreads();
+                if (tid == 0) w[t] = NO_KEY;
+                continue;
+            }
+            unsigned long long my_key = NO_KEY;
+            auto emit = [&](int, int64_t p, float v) {
+                bool ok = !a.has_threshold || (cc ? (double)v >= a.threshold : (double)v <= a.threshold);
+                for (int q = 0; q <= j; ++q) {
+                    const int64_t d = p - picks[q];
+                    ok = ok && (d >= S || -d >= S);
+                }
+                const unsigned long long key = pick_key(v, p, cc);
+                if (ok && key < my_key) my_key = key;
+            };
+            if constexpr (U8) u8_tile(src, rq, p0, reinterpret_cast<double(*)[U8_TILE]>(lds), emit);
+            else f32_tile<4>(src, rq, p0, lds, lds + XG * XM, emit);
+            const unsigned long long tb = block_min_u64(my_key, red4);
+            if (tid == 0) w[t] = tb;
+        }
+        __syncthreads();                                                    // the round's stores are there for the next one's loads
+    }
+    if (tid == 0) {
+        a.counts[a.first_search + k] = n_picks;
+        // what a pair's bound has to stay above from now on: the K-th pick's ranking score, or the threshold's where that is tighter
+        unsigned long long key = a.tkey;
+        if (n_picks == K) {
+            const float u = rank_up(last, cc);
+            if (a.tkey == NO_KEY || u < key_score(a.tkey)) key = ((unsigned long long)__float_as_uint(u) << 32) | 0xffffffffull;
+        }
+        a.gkeys[a.first_search + k] = key;
+    }
+}
+
 int launch_ok() { return hipGetLastError() == hipSuccess ? SUSHI_HIP_OK : SUSHI_HIP_ELAUNCH; }
 
 bool request_ok(const SushiHipRequest& r, const SushiHipStream* dst, const SushiHipStream* src) {
@@ -212,6 +413,20 @@ int launch_threshold_tiles(const ThresholdTileParams& p, hipStream_t st) {
     const unsigned grid = (unsigned)std::min<int64_t>(want, 2048);
     if (p.r.dtype == SUSHI_HIP_U8) hipLaunchKernelGGL(threshold_tiles_kernel<true>, dim3(grid), dim3(256), 0, st, p);
     else hipLaunchKernelGGL(threshold_tiles_kernel<false>, dim3(grid), dim3(256), 0, st, p);
+    return launch_ok();
+}
+
+int launch_best_tiles(const BestParams& p, hipStream_t st) {
+    const int64_t want = (int64_t)std::max(p.list_max, 1) * TILES_PER_PAIR;
+    const unsigned grid = (unsigned)std::min<int64_t>(want, 2048);
+    if (p.r.dtype == SUSHI_HIP_U8) hipLaunchKernelGGL(best_tiles_kernel<true>, dim3(grid), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(best_tiles_kernel<false>, dim3(grid), dim3(256), 0, st, p);
+    return launch_ok();
+}
+
+int launch_best_select(const BestParams& p, hipStream_t st) {
+    if (p.r.dtype == SUSHI_HIP_U8) hipLaunchKernelGGL(best_select_kernel<true>, dim3((unsigned)p.n_sub), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(best_select_kernel<false>, dim3((unsigned)p.n_sub), dim3(256), 0, st, p);
     return launch_ok();
 }
 

@@ -45,6 +45,7 @@
 //   sushi_fft_bound.inc    the pair exclusion: bound_kernel / bound_low_kernel / slb_kernel / pilot / survivor / second look / mac_rows_kernel
 //   sushi_fft_collect.inc  collect_kernel
 //   sushi_fft_threshold.inc  the threshold run's own kernels: seed, audit, extension, output scan
+//   sushi_fft_best.inc     the best-K run's own kernels: seed, escalation, audit, extension
 //   sushi_fft_plan.inc     host: workspace layout, stage timing, the plan of a batch
 //   (this file)            the batch handle and the C ABI's entry points
 
@@ -92,6 +93,7 @@ constexpr int LDS_FLOATS = sushi_fft::lds_floats<FFT_LOGN>();
 #include "sushi_fft_bound.inc"
 #include "sushi_fft_collect.inc"
 #include "sushi_fft_threshold.inc"
+#include "sushi_fft_best.inc"
 #include "sushi_fft_plan.inc"
 
 }  // namespace
@@ -152,7 +154,8 @@ struct SushiHipBatch {
     int bound_model = SUSHI_HIP_BOUND_WORST_CASE;   // (default) / SUSHI_HIP_BOUND_STATISTICAL: how the excluded side's roundings enter slb
     int last_band = -1;                 // form of the exclusion the last run used (its last sub-batch that went through it; -1: none did)
     bool last_whole_cut = false;        // the last run took the plan's one-sub-batch cut (Plan::subs_whole)
-    bool last_threshold = false;        // the last run was a threshold run (sushi_hip_batch_run_threshold)
+    bool last_threshold = false;        // the last run was a threshold run (sushi_hip_batch_run_threshold) or a best-K run (sushi_hip_batch_run_best)
+    bool last_best = false;             // ... a best-K run: its flags words hold, per search, the last round that evaluated a pair of it
     // AUTO learns from its own runs: a batch whose exclusion excluded next to nothing (searches without a match anywhere) runs
     // without it from then on, looking again every 64th run.  The last run's counts come back through 16 bytes of pinned host memory
     // behind an event that is only ever QUERIED: a run never waits for an earlier one.
@@ -658,6 +661,77 @@ static int run_sub_threshold(RunCtx& c, const SubView& v, hipStream_t st, const 
     return SUSHI_HIP_OK;
 }
 
+// What one best-K run asks for.
+struct BestRun { int k, min_separation, has_threshold; double threshold; unsigned long long tkey; SushiHipHit* hits; int32_t* counts; };
+
+// One sub-batch of a best-K run (sushi_fft_best.inc): the bound; the pairs of smallest bound evaluated exactly and
+// the K picks made from them, which leave every search's U; rounds of (pairs U does not exclude, evaluated; picks again); the
+// searches still unsettled then, and the audit's, at every pair.  SUSHI_HIP_EXCLUDE_NEVER: every pair, no bound, one selection.
+static int run_sub_best(RunCtx& c, const SubView& v, hipStream_t st, const BestRun& br) {
+    SushiHipBatch* b = c.b;
+    const SubBatch& sb = v.sb;
+    const bool exclude = b->exclusion != SUSHI_HIP_EXCLUDE_NEVER;
+    BestParams bp;
+    memset(&bp, 0, sizeof(bp));
+    bp.r = c.r; bp.searches = c.searches + sb.a0; bp.pairmap = v.pairmap; bp.sub_first_pair = sb.first_pair; bp.first_search = sb.a0;
+    bp.n_sub = v.n_sub; bp.list = v.order; bp.list_count = nullptr; bp.list_max = (int)sb.pairs; bp.rows = (uint32_t*)v.y;
+    bp.method = c.method; bp.has_threshold = br.has_threshold; bp.threshold = br.threshold; bp.tkey = br.tkey; bp.k = br.k;
+    bp.min_separation = br.min_separation; bp.gkeys = c.gkeys; bp.hits = br.hits; bp.counts = br.counts;
+    // (tspec_kernel also leaves the sub-batch's pair -> search map, which every stage below reads)
+    int rc = stage_tspec(c, v, st);
+    if (rc != SUSHI_HIP_OK) return rc;
+    if (!exclude) {
+        b->direct_pairs += sb.pairs;
+        if (launch_best_tiles(bp, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+        return launch_best_select(bp, st);
+    }
+    int band = 0;
+    if ((rc = decide_band(c, v, st, &band)) != SUSHI_HIP_OK) return rc;
+    if (launch_mac(c, v, st, band != 0, nullptr, v.items) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    // (the bounds depend on no threshold: made once)
+    BoundArgs ba;
+    if (bound_pairs(c, v, st, band, ba) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    BestArgs a;
+    memset(&a, 0, sizeof(a));
+    a.searches = c.searches + sb.a0; a.first_search = sb.a0; a.sub_first_pair = sb.first_pair; a.n_sub = v.n_sub; a.n_pairs = (int)sb.pairs;
+    a.k = br.k; a.pairmap = v.pairmap; a.order = v.order; a.rows = (const uint32_t*)v.y; a.slb = v.slb; a.audit_mark = v.audit_mark;
+    a.gkeys = c.gkeys; a.tkey = br.tkey; a.list = v.slist; a.list_count = v.scount; a.flags = c.flags; a.need = c.flag_list; a.viol = c.viol;
+    a.counters = c.counters; a.method = c.method; a.audit_seq = c.run_seq; a.audit_every = b->audit_every;
+    // the two lists and their lengths (zero since the run's first launch; every selection clears them for the round behind it)
+    int* const count2 = v.scount + 5;
+    bp.audit_mark = v.audit_mark; bp.stamp_flags = c.flags; bp.reset0 = v.scount; bp.reset1 = count2;
+    const unsigned per_pair = (unsigned)((sb.pairs + 255) / 256);
+    auto evaluate = [&](const int* list, const int* count) {
+        bp.list = list; bp.list_count = count;
+        return launch_best_tiles(bp, st);
+    };
+    int stamp = 1;
+    a.stamp = bp.stamp = stamp;
+    hipLaunchKernelGGL(best_seed_kernel, dim3((unsigned)v.n_sub), dim3(256), 0, st, a);
+    if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    // (band-split form, with a threshold: the second look drops the seed pairs its sharper bound excludes under the threshold, as
+    // it does in a threshold run; without one there is no U yet and every seed pair is evaluated)
+    const bool seed_look = band && br.has_threshold;
+    if (seed_look && second_look(c, v, st, ba) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    if (evaluate(seed_look ? v.slist2 : v.slist, seed_look ? count2 : v.scount) != SUSHI_HIP_OK || launch_best_select(bp, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    for (int round = 0; round < BEST_ROUNDS; ++round) {
+        a.stamp = bp.stamp = ++stamp;
+        hipLaunchKernelGGL(best_survivor_kernel, dim3(per_pair), dim3(256), 0, st, a);
+        if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+        // (band-split form: the second look at what the bound left, as in every other run)
+        if (band && second_look(c, v, st, ba) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+        if (evaluate(band ? v.slist2 : v.slist, band ? count2 : v.scount) != SUSHI_HIP_OK || launch_best_select(bp, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    }
+    a.stamp = bp.stamp = ++stamp;
+    hipLaunchKernelGGL(best_final_kernel, dim3(per_pair), dim3(256), 0, st, a);
+    if (launch_ok() != SUSHI_HIP_OK || evaluate(v.slist, v.scount) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    hipLaunchKernelGGL(best_check_kernel, dim3(per_pair), dim3(256), 0, st, a);
+    a.list = v.slist2; a.list_count = count2;
+    hipLaunchKernelGGL(best_extend_kernel, dim3(per_pair), dim3(256), 0, st, a);
+    if (launch_ok() != SUSHI_HIP_OK || evaluate(v.slist2, count2) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    return launch_best_select(bp, st);
+}
+
 extern "C" {
 
 int sushi_hip_device_prepare(void) {
@@ -882,7 +956,7 @@ int sushi_hip_batch_run(SushiHipBatch* b, double delta, int32_t* out_idx_dev, fl
     if (!b || !out_idx_dev || !out_score_dev) return SUSHI_HIP_EINVAL;
     const hipStream_t st0 = (hipStream_t)hip_stream;
     RunCtx c(b, delta);
-    b->last_stream = st0; b->ran = true; b->direct_pairs = 0; b->last_threshold = false;
+    b->last_stream = st0; b->ran = true; b->direct_pairs = 0; b->last_threshold = false; b->last_best = false;
     if (hipStreamWaitEvent(st0, b->uploaded, 0) != hipSuccess) return SUSHI_HIP_ELAUNCH;   // descriptors and plan have landed
     if (b->path == SUSHI_HIP_PATH_DIRECT)
         return launch_direct(c.r, c.searches, b->n, (int)b->n_tiles, b->variant, b->method, c.keys, out_idx_dev, out_score_dev, b->packed_out, st0);
@@ -949,7 +1023,7 @@ int sushi_hip_batch_run_threshold(SushiHipBatch* b, double threshold, int32_t ca
     const ThresholdRun tr{threshold, ((unsigned long long)ubits << 32) | 0xffffffffull, capacity, out_hits_dev, out_counts_dev};
     const hipStream_t st0 = (hipStream_t)hip_stream;
     RunCtx c(b, 0.0);
-    b->last_stream = st0; b->ran = true; b->direct_pairs = 0; b->last_threshold = true;
+    b->last_stream = st0; b->ran = true; b->direct_pairs = 0; b->last_threshold = true; b->last_best = false;
     b->last_band = -1; b->last_whole_cut = false; b->last_suspended = 0;
     if (hipStreamWaitEvent(st0, b->uploaded, 0) != hipSuccess) return SUSHI_HIP_ELAUNCH;   // descriptors and plan have landed
     {
@@ -968,6 +1042,48 @@ int sushi_hip_batch_run_threshold(SushiHipBatch* b, double threshold, int32_t ca
     for (size_t si = 0; si < b->plan.subs.size(); ++si) {
         const SubBatch& sb = b->plan.subs[si];
         if ((rc = run_sub_threshold(c, SubView(b->mem, b->lay, b->plan.ws_lane, sb, si), lanes.st[sb.lane], tr)) != SUSHI_HIP_OK) return rc;
+    }
+    return lanes.join();
+} catch (const std::bad_alloc&) { return SUSHI_HIP_ENOMEM; } catch (...) { return SUSHI_HIP_EINTERNAL; }     // nothing crosses the C boundary
+
+int sushi_hip_batch_run_best(SushiHipBatch* b, int32_t k, int32_t min_separation, const double* threshold, SushiHipHit* out_hits_dev,
+                             int32_t* out_counts_dev, void* hip_stream) try {
+    if (!b || !out_hits_dev || !out_counts_dev || k < 1 || k > SUSHI_HIP_BEST_MAX_K || min_separation < 0 ||
+        (threshold && !std::isfinite(*threshold)) || b->path != SUSHI_HIP_PATH_FFT)
+        return SUSHI_HIP_EINVAL;
+    if (((uintptr_t)out_hits_dev & 3) || ((uintptr_t)out_counts_dev & 3)) return SUSHI_HIP_EALIGN;
+    BestRun br{k, min_separation, threshold ? 1 : 0, threshold ? *threshold : 0.0, NO_KEY, out_hits_dev, out_counts_dev};
+    if (threshold) {
+        // the threshold in ranking units, rounded up to a float, as sushi_hip_batch_run_threshold forms it (never below 0: no ranking
+        // score is, and the keys order as unsigned numbers)
+        const double u = std::max(0.0, b->method == SUSHI_HIP_METHOD_CCOEFF_NORMED ? 1.0 - *threshold : *threshold);
+        float uf = (float)u;
+        if (std::isfinite(uf) && (double)uf < u) uf = std::nextafter(uf, INFINITY);
+        uint32_t ubits;
+        memcpy(&ubits, &uf, sizeof(ubits));
+        br.tkey = ((unsigned long long)ubits << 32) | 0xffffffffull;
+    }
+    const hipStream_t st0 = (hipStream_t)hip_stream;
+    RunCtx c(b, 0.0);
+    b->last_stream = st0; b->ran = true; b->direct_pairs = 0; b->last_threshold = true; b->last_best = true;
+    b->last_band = -1; b->last_whole_cut = false; b->last_suspended = 0;
+    if (hipStreamWaitEvent(st0, b->uploaded, 0) != hipSuccess) return SUSHI_HIP_ELAUNCH;   // descriptors and plan have landed
+    {
+        // flags, violation marks, flag list, every sub-batch's small counters, the pattern rows' norm accumulators, the run's counters
+        FillArgs fa;
+        memset(&fa, 0, sizeof(fa));
+        fa.p[0] = (uint32_t*)c.flags; fa.words[0] = (uint32_t)((b->lay.counters + align_up(sizeof(RunCounters), 256) - b->lay.flags) / 4);
+        fa.value[0] = 0u; fa.n = 1;
+        if (launch_fill(fa, st0) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    }
+    c.run_seq = b->run_seq++;
+    c.lanes = b->plan.lanes;
+    Lanes lanes(b, st0);
+    int rc = lanes.fork(b->plan.lanes);
+    if (rc != SUSHI_HIP_OK) return rc;
+    for (size_t si = 0; si < b->plan.subs.size(); ++si) {
+        const SubBatch& sb = b->plan.subs[si];
+        if ((rc = run_sub_best(c, SubView(b->mem, b->lay, b->plan.ws_lane, sb, si), lanes.st[sb.lane], br)) != SUSHI_HIP_OK) return rc;
     }
     return lanes.join();
 } catch (const std::bad_alloc&) { return SUSHI_HIP_ENOMEM; } catch (...) { return SUSHI_HIP_EINTERNAL; }     // nothing crosses the C boundary
@@ -1002,6 +1118,11 @@ int sushi_hip_batch_diagnostics(SushiHipBatch* b, SushiHipBatchDiag* diag, float
         diag->suspended = 0; diag->band_votes[0] = diag->band_votes[1] = 0; diag->second_look_audited = 0;
         if (ranking_err_host) memset(ranking_err_host, 0, (size_t)b->n * sizeof(float));
         if (flagged_host) memset(flagged_host, 0, (size_t)b->n * sizeof(int32_t));
+        // (a best-K run: the last round that evaluated a pair of each search -- 1 the seed, 2 .. the escalation rounds, BEST_ROUNDS + 2
+        // the last stage; 0 without the exclusion)
+        if (b->last_best && flagged_host &&
+            hipMemcpy(flagged_host, b->mem + b->lay.flags, (size_t)b->n * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
+            return SUSHI_HIP_ELAUNCH;
         return SUSHI_HIP_OK;
     }
     std::vector<int32_t> fl((size_t)b->n);

@@ -166,6 +166,43 @@ struct ThresholdTileParams {
     int32_t capacity;
 };
 int launch_threshold_tiles(const ThresholdTileParams& p, hipStream_t st);
+
+// FFT path, best-K run (sushi_hip_batch_run_best).  An evaluated pair's row holds, per tile, the best eligible
+// position of the tile as a 64-bit pick key -- the smaller key is the better pick: the float32 score under the order-preserving map
+// of its bits (negated for TM_CCOEFF_NORMED; -0.0 and 0.0 tie), then the lower index -- once as evaluated (BEST_KEY: no pick
+// masked) and once as the selection works on it (BEST_WORK: dead tiles NO_KEY, tiles a pick's window cuts evaluated again with the
+// picks masked); and the tile's smallest ranking score over ALL its positions (THR_MIN: the bound's audit, as in a threshold run).
+constexpr int BEST_KEY = 0;                                    // [TILES_PER_PAIR] 64-bit keys
+constexpr int BEST_WORK = 2 * TILES_PER_PAIR;                  // [TILES_PER_PAIR] 64-bit keys
+static_assert(BEST_WORK + 2 * TILES_PER_PAIR <= THR_COUNT, "the pick keys lie in front of the tile minima");
+constexpr int BEST_MAX_K = SUSHI_HIP_BEST_MAX_K;
+struct BestParams {
+    StreamRefs r;
+    const SearchDesc* searches;       // the sub-batch's searches
+    const int* pairmap;               // [pairs of the sub-batch] -> search of the sub-batch
+    int sub_first_pair;
+    int first_search;                 // global index of searches[0]
+    int n_sub;
+    const int* list;                  // best_tiles_kernel: the pairs to evaluate, list[0 .. *list_count) or [0 .. list_max) where list_count is NULL
+    const int* list_count;
+    int list_max;
+    uint32_t* rows;                   // [pairs of the sub-batch][THR_SLOT_WORDS]
+    const unsigned char* audit_mark;  // bit 1: the pair is evaluated; NULL: every pair is
+    int method;
+    int has_threshold;
+    double threshold;                 // eligible: score <= threshold (SQDIFF_NORMED) / >= threshold (CCOEFF_NORMED)
+    unsigned long long tkey;          // the threshold in ranking units, rounded up, as a search key; NO_KEY: none
+    int k;                            // picks per search
+    int min_separation;               // 0: the search's own tmpl_len
+    const int* stamp_flags;           // [all searches] best_select_kernel works on the searches whose word is `stamp`; NULL: on all
+    int stamp;
+    unsigned long long* gkeys;        // [all searches] out: what a pair's bound is compared with from now on
+    SushiHipHit* hits;                // [all searches][k]
+    int32_t* counts;                  // [all searches]
+    int* reset0; int* reset1;         // list lengths best_select_kernel clears for the round after it (or NULL)
+};
+int launch_best_tiles(const BestParams& p, hipStream_t st);
+int launch_best_select(const BestParams& p, hipStream_t st);
 int launch_unpack(const unsigned long long* keys_dev, int n, int method, int32_t* out_idx_dev, float* out_score_dev,
                   int32_t* out_packed_dev, hipStream_t st);
 

@@ -463,6 +463,51 @@ class SearchBatch(object):
             out.append((rec[:, 0].astype(np.int64), np.ascontiguousarray(rec[:, 1]).view(np.float32)))
         return out
 
+    def run_best(self, k, min_separation=None, threshold=None, hip_stream=None):
+        """The k best distinct matches of every request (sushi_hip_batch_run_best; FFT path, asynchronous): the first k picks of
+        greedy suppression over the request's whole score row -- the best float32 score first (the lowest for 'sqdiff_normed', the
+        highest for 'ccoeff_normed'; ties by the lower index), every later pick at least `min_separation` positions away from all
+        earlier ones (None: the request's own tmpl_len -- occurrences that do not overlap).  threshold: only positions that pass it
+        are picked (as run_threshold compares).  Returns (hits, counts): an int32 CUDA tensor [n, k, 2] of (index, score bits)
+        records -- request j's picks, best first, in hits[j, :counts[j]], the rest unwritten -- and an int32 CUDA tensor [n] of
+        how many picks each request has.  Each score is bit-identical to the curve's value at that position.
+        Cost: a k beyond the number of real occurrences makes the k-th pick a chance-level score, under which the pair bound
+        excludes little -- most of the window is then evaluated exactly.  Pass a threshold to ask for a
+        runner-up "if there is one"."""
+        if self.path != "fft":
+            raise SushiError("best-k runs need the FFT path")
+        k = int(k)
+        if not 1 <= k <= _native.BEST_MAX_K:
+            raise SushiError("k must be in 1..%d" % _native.BEST_MAX_K)
+        sep = 0 if min_separation is None else int(min_separation)
+        if sep < 1 and min_separation is not None:
+            raise SushiError("min_separation must be >= 1 (None: each request's tmpl_len)")
+        thr = None
+        if threshold is not None:
+            threshold = float(threshold)
+            if not np.isfinite(threshold):
+                raise SushiError("threshold must be finite")
+            thr = ctypes.byref(ctypes.c_double(threshold))
+        dev = self.dst.device
+        with torch.cuda.device(dev):
+            hits = torch.empty((self.n, k, 2), dtype=torch.int32, device=dev)
+            counts = torch.empty(self.n, dtype=torch.int32, device=dev)
+            st = _raw_stream(dev) if hip_stream is None else hip_stream
+            rc = _native.lib().sushi_hip_batch_run_best(self._handle, k, sep, thr, hits.data_ptr(), counts.data_ptr(), st)
+            _native.check(rc, "sushi_hip_batch_run_best")
+        return hits, counts
+
+    def best(self, k, min_separation=None, threshold=None):
+        """[(index int64 ndarray, score float32 ndarray) per request]: run_best's picks, best first.  Synchronises."""
+        hits, counts = self.run_best(k, min_separation, threshold)
+        cnt = counts.cpu().numpy()
+        h = hits.cpu().numpy()
+        out = []
+        for j in range(self.n):
+            rec = h[j, :int(cnt[j])]
+            out.append((rec[:, 0].astype(np.int64), np.ascontiguousarray(rec[:, 1]).view(np.float32)))
+        return out
+
     def results(self):
         """(idx int32 ndarray, score float32 ndarray) -- synchronises."""
         if self._early_np is not None:

@@ -447,6 +447,42 @@ class WavStream(object):
             out.append((np.asarray(score, np.float32), [st + (int(k) / float(self.sample_rate)) for k in idx]))
         return out
 
+    def find_best_matches(self, pattern, k, window_center=None, window_size=None, method="ccoeff_normed", min_separation=None,
+                          threshold=None):
+        """The k best distinct matches of the pattern in find_substream's window (wav.py:178-184), best first: is the best match
+        the only one, and if not, where are the others?  Greedy suppression over wav.py:185's row (sushi_amd.occurrences.best_peaks)
+        without forming it.  No window: the widest _window allows, as find_occurrences.  min_separation (seconds, or None: the
+        pattern's own length -- occurrences that do not overlap); threshold: only positions that pass it.  Returns (scores float32
+        ndarray, times list of float) in pick order; a time is what find_substream returns for that position.
+        A k beyond the number of real occurrences is expensive without a threshold (SearchBatch.run_best)."""
+        return self.find_best_matches_many([pattern], k, [window_center], [window_size], method=method,
+                                           min_separation=min_separation, threshold=threshold)[0]
+
+    def find_best_matches_many(self, patterns, k, window_centers=None, window_sizes=None, method="ccoeff_normed",
+                               min_separation=None, threshold=None):
+        """[find_best_matches(p, k, c, w) for p, c, w in zip(...)] in one best-k run (patterns located as find_substreams does).
+        window_centers / window_sizes: lists (None entries, or None for the list: the widest window)."""
+        from .device import SearchBatch
+        n = len(patterns)
+        centres = [None] * n if window_centers is None else list(window_centers)
+        sizes = [None] * n if window_sizes is None else list(window_sizes)
+        if not (len(centres) == len(sizes) == n) or n == 0:
+            raise SushiError('find_best_matches_many: need equally many patterns, centres and sizes (>= 1)')
+        dst_dev = self.device_stream()
+        src_dev, offs, lens, _ = self._pattern_source(patterns, dst_dev)
+        start_times, win_start, n_pos = [], [], []
+        for m, c, w in zip(lens, centres, sizes):
+            c, w = self._widest(c, w)
+            st, lo, p = self._window(m, c, w)
+            start_times.append(st)
+            win_start.append(lo)
+            n_pos.append(p)
+        batch = SearchBatch(dst_dev, src_dev, offs, lens, win_start, n_pos, path="fft", method=method)
+        sep = None if min_separation is None else max(1, int(round(float(min_separation) * self.sample_rate)))
+        found = batch.best(k, sep, threshold)
+        return [(np.asarray(score, np.float32), [st + (int(i) / float(self.sample_rate)) for i in idx])
+                for st, (idx, score) in zip(start_times, found)]
+
     def _widest(self, window_center, window_size):
         """find_occurrences' default window: the widest _window allows -- the whole stream, padding included."""
         if window_center is None:
