@@ -1,7 +1,8 @@
 // sushi_amd/csrc/curve_tiles.hpp -- the exact tile bodies of the whole-curve kernels (sushi_curve.hip), shared by the curves and by
-// the threshold run's evaluation of listed block pairs.  A body evaluates every valid position p in [0, P) of one
-// tile of consecutive positions exactly and hands each value to an epilogue, emit(i, p, value), i = p - p0 inside the tile: the
-// curves store it, the threshold run compares it.  Same arithmetic in the same order either way, so the values are the same bits.
+// the evaluation of listed block pairs in a threshold run and in a best-K run (§3.11; both through sushi_curve.hip's
+// eval_tile).  A body evaluates every valid position p in [0, P) of one tile of consecutive positions exactly and hands each value
+// to an epilogue, emit(i, p, value), i = p - p0 inside the tile: the curves store it, the threshold run compares it, the best-K
+// run keeps the best.  Same arithmetic in the same order every way, so the values are the same bits.
 //
 // Included by sushi_curve.hip only, which is compiled with -ffp-contract=off (build.py): the epilogue restates cv2's operation
 // order, and a fused multiply-add would round differently.

@@ -62,6 +62,27 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
     return v;                                   // valid in lane 0
 }
 
+// the same over a workgroup of 256 threads, through four words of LDS: valid in every thread.  Two barriers, the first of which
+// also lets red4's last readers through: every thread of the workgroup calls it.
+__device__ __forceinline__ unsigned long long block_min_u64(unsigned long long v, unsigned long long* red4) {
+    v = wave_min_u64(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    unsigned long long m = red4[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) m = red4[w] < m ? red4[w] : m;
+    return m;
+}
+
+// The order-preserving map of float bits to unsigned (any float, negative and -inf included: a < b as floats iff
+// ordered_bits(a) < ordered_bits(b) as unsigned numbers; -0.0 sorts below 0.0), and its inverse.
+__device__ __forceinline__ unsigned ordered_bits(const unsigned b) { return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }   // (of a float's bits)
+__device__ __forceinline__ unsigned ordered_bits(const float v) { return ordered_bits(__float_as_uint(v)); }
+__device__ __forceinline__ float ordered_bits_inv(const unsigned u) {
+    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
@@ -89,15 +110,9 @@ __device__ __forceinline__ unsigned key_pos(unsigned long long key) { return (un
 // arg-MAX through the same atomicMin (TM_CCOEFF_NORMED, scores in [-1, 1]): the key holds -score under the usual
 // order-preserving map of float bits to unsigned, so the smallest key is the largest score at its lowest position.
 __device__ __forceinline__ unsigned long long make_key_max(float score, unsigned pos) {
-    const unsigned b = __float_as_uint(-(score + 0.0f));                  // + 0.0f: -0.0 and 0.0 tie, as in NumPy
-    const unsigned u = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    return ((unsigned long long)u << 32) | pos;
+    return ((unsigned long long)ordered_bits(-(score + 0.0f)) << 32) | pos;      // + 0.0f: -0.0 and 0.0 tie, as in NumPy
 }
-__device__ __forceinline__ float key_score_max(unsigned long long key) {
-    const unsigned u = (unsigned)(key >> 32);
-    const unsigned b = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    return -__uint_as_float(b);
-}
+__device__ __forceinline__ float key_score_max(unsigned long long key) { return -ordered_bits_inv((unsigned)(key >> 32)); }
 
 // Template statistics in the order cv2 derives them (templmatch.cpp common_matchTemplate:
 // meanStdDev -> templSum2 / templNorm), from the float64 prefix sums of the source stream's samples

@@ -7,7 +7,9 @@
 // Either way each value is bit for bit what the exact stages produce for that position.  The tile bodies
 // (curve_tiles.hpp) also evaluate the listed block pairs of a threshold run (sushi_hip_batch_run_threshold):
 // threshold_tiles_kernel, launched from sushi_fft.hip through launch_threshold_tiles; and those of a best-K run
-// (sushi_hip_batch_run_best): best_tiles_kernel and best_select_kernel.
+// (sushi_hip_batch_run_best): best_tiles_kernel and best_select_kernel.  What those three share is written once,
+// in front of them: the decoding of a work item (ListedPairs -> listed_tile), a tile's evaluation with an epilogue (eval_tile),
+// the threshold test (passes), the launch by sample type (launch_by_dtype).
 //
 // Stateless: no handle, no spectra; the request table and the tile queue live in the caller's workspace.
 
@@ -109,55 +111,88 @@ void curve_f32_kernel(CurveArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
-// Threshold run: every position of the listed block pairs, exactly, a TILE of a pair per work item (item =
-// list slot x TILES_PER_PAIR + tile: the tiles of a pair run side by side and share its pattern in the L2).  The same tile bodies
-// as the curves, so a hit's score is the curve's value at that position, bit for bit.
+// The listed block pairs of a threshold run and of a best-K run: every position of them, exactly, a TILE of a pair per work item
+// (item = list slot x TILES_PER_PAIR + tile: the tiles of a pair run side by side and share its pattern in the L2).  The same tile
+// bodies as the curves, so a score is the curve's value at that position, bit for bit.  A tile is 1024 positions for both sample
+// types (f32_tile<4>).  First what the kernels of both runs share: which tile a work item is, and its evaluation.
+// ------------------------------------------------------------------------------------------------------------------------
+static_assert(TILE == U8_TILE && TILE == 256 * 4 && TILE / 32 == 32, "a tile's hit bits are 32 words");
+
+__device__ __forceinline__ TileSrc tile_src(const StreamRefs& r, const int method) {
+    return TileSrc{r.dst_raw, r.dst_s1, r.dst_s2, r.dst_len, r.src_raw, r.src_s1, r.src_s2, r.centre, method};
+}
+__device__ __forceinline__ TileReq tile_req(const SearchDesc& sd) { return TileReq{sd.tmpl_off, sd.win_start, sd.tmpl_len, sd.n_pos}; }
+
+// the work items of a list: every tile of every listed pair.  (Every list holds distinct pairs of the sub-batch and list_max is the
+// sub-batch's pair count, so the clamp never bites.)
+__device__ __forceinline__ int64_t listed_items(const ListedPairs& a) {
+    const int n_list = a.list_count ? min(*a.list_count, a.list_max) : a.list_max;
+    return (int64_t)n_list * TILES_PER_PAIR;
+}
+
+// One work item: tile `t` of the pair `pr` in list slot item / TILES_PER_PAIR, of search `k` (of the sub-batch); p0: the tile's first
+// position in request coordinates; row: the pair's; valid (uniform): the tile holds a position of the window
+struct ListedTile { int pr, k, t; int64_t p0; TileReq rq; uint32_t* row; bool valid; };
+__device__ __forceinline__ ListedTile listed_tile(const ListedPairs& a, const int64_t item) {
+    ListedTile x;
+    x.t = (int)(item % TILES_PER_PAIR);
+    x.pr = a.list[(int)(item / TILES_PER_PAIR)];
+    x.k = a.pairmap[x.pr];
+    const SearchDesc sd = a.searches[x.k];
+    const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
+    const int64_t pairI = lay.pair0 + (a.sub_first_pair + x.pr - sd.first_pair);
+    x.p0 = pairI * FFT_STEP * (int64_t)FFT_SEG + (int64_t)x.t * TILE - sd.win_start;
+    x.rq = tile_req(sd);
+    x.row = a.rows + (size_t)x.pr * THR_SLOT_WORDS;
+    x.valid = x.p0 + TILE > 0 && x.p0 < sd.n_pos;
+    return x;
+}
+
+// A tile evaluated with `emit` (curve_tiles.hpp).  Every thread of the workgroup calls it: the tile bodies hold barriers.  `lds`:
+// LISTED_LDS_DOUBLES<U8> doubles, free of readers (the callers' barrier at the top of an item).
+template <bool U8> constexpr int LISTED_LDS_DOUBLES = U8 ? 4 * U8_TILE : XG * XM + f32_li_doubles<4>();
+template <bool U8, class Emit>
+__device__ __forceinline__ void eval_tile(const TileSrc& src, const TileReq& rq, const int64_t p0, double* lds, Emit&& emit) {
+    if constexpr (U8) u8_tile(src, rq, p0, reinterpret_cast<double(*)[U8_TILE]>(lds), emit);
+    else f32_tile<4>(src, rq, p0, lds, lds + XG * XM, emit);
+}
+
+// whether a score passes the caller's threshold: at most it (TM_SQDIFF_NORMED), at least it (TM_CCOEFF_NORMED)
+__device__ __forceinline__ bool passes(const float v, const double threshold, const bool cc) {
+    return cc ? (double)v >= threshold : (double)v <= threshold;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Threshold run:
 //   pass 0: the tile's hit bits (THR_MASK), its hit count (THR_COUNT) and its smallest ranking score (THR_MIN: the bound's audit)
 //           into the pair's row -- every word of the tile, plain stores, so nothing has to be cleared first;
 //   pass 1: tiles with hits, after thr_scan_kernel (sushi_fft_threshold.inc) has left each pair's first output slot (THR_OFF):
 //           evaluated again, every hit to its slot -- the pair's slot + the hits of the tiles before + the set bits before it.
-// A tile is 1024 positions for both sample types (f32_tile<4>).
 // ------------------------------------------------------------------------------------------------------------------------
-static_assert(TILE == U8_TILE && TILE == 256 * 4 && TILE / 32 == 32, "a tile's hit bits are 32 words");
-
 template <bool U8>
 __global__ __launch_bounds__(256)
 void threshold_tiles_kernel(ThresholdTileParams a) {
-    constexpr int LDS_DOUBLES = U8 ? 4 * U8_TILE : XG * XM + f32_li_doubles<4>();
-    __shared__ double lds[LDS_DOUBLES];
+    __shared__ double lds[LISTED_LDS_DOUBLES<U8>];
     __shared__ unsigned mask[TILE / 32];
     __shared__ int wpre[TILE / 32];
     __shared__ unsigned red_min;
     const int tid = threadIdx.x;
-    const TileSrc src{a.r.dst_raw, a.r.dst_s1, a.r.dst_s2, a.r.dst_len, a.r.src_raw, a.r.src_s1, a.r.src_s2, a.r.centre, a.method};
-    const bool cc = a.method == SUSHI_HIP_METHOD_CCOEFF_NORMED;
-    const int n_list = a.list_count ? *a.list_count : a.list_max;
-    const int64_t n_items = (int64_t)n_list * TILES_PER_PAIR;
+    const TileSrc src = tile_src(a.lp.r, a.lp.method);
+    const bool cc = a.lp.method == SUSHI_HIP_METHOD_CCOEFF_NORMED;
+    const int64_t n_items = listed_items(a.lp);
     for (int64_t it = blockIdx.x; it < n_items; it += gridDim.x) {
-        const int slot = (int)(it / TILES_PER_PAIR), t = (int)(it % TILES_PER_PAIR);
-        const int pr = a.list[slot];
-        const int k = a.pairmap[pr];
-        const SearchDesc sd = a.searches[k];
-        const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
-        const int64_t pairI = lay.pair0 + (a.sub_first_pair + pr - sd.first_pair);
-        const int64_t p0 = pairI * FFT_STEP * (int64_t)FFT_SEG + (int64_t)t * TILE - sd.win_start;   // (request coordinates)
-        const TileReq rq{sd.tmpl_off, sd.win_start, sd.tmpl_len, sd.n_pos};
-        uint32_t* __restrict__ row = a.rows + (size_t)pr * THR_SLOT_WORDS;
-        const bool valid = p0 + TILE > 0 && p0 < sd.n_pos;                 // (uniform) the tile holds a position of the window
-        auto eval = [&](auto&& emit) {
-            if constexpr (U8) u8_tile(src, rq, p0, reinterpret_cast<double(*)[U8_TILE]>(lds), emit);
-            else f32_tile<4>(src, rq, p0, lds, lds + XG * XM, emit);
-        };
+        const ListedTile x = listed_tile(a.lp, it);
+        const int t = x.t;
+        uint32_t* __restrict__ row = x.row;
         __syncthreads();                                                    // the previous item's LDS is consumed
         if (a.pass == 0) {
             if (tid < TILE / 32) mask[tid] = 0u;
             if (tid == 0) red_min = 0x7f800000u;                            // +inf (ranking scores are >= 0: uint order is float order)
             __syncthreads();
             float my_min = __builtin_inff();
-            if (valid)
-                eval([&](int i, int64_t, float v) {
-                    const bool hit = cc ? (double)v >= a.threshold : (double)v <= a.threshold;
-                    if (hit) atomicOr(&mask[i >> 5], 1u << (i & 31));
+            if (x.valid)
+                eval_tile<U8>(src, x.rq, x.p0, lds, [&](int i, int64_t, float v) {
+                    if (passes(v, a.threshold, cc)) atomicOr(&mask[i >> 5], 1u << (i & 31));
                     my_min = fminf(my_min, cc ? 1.0f - v : v);
                 });
             atomicMin(&red_min, __float_as_uint(my_min));                 // (LDS: once per thread, after the tile)
@@ -172,7 +207,7 @@ void threshold_tiles_kernel(ThresholdTileParams a) {
             }
         } else {
             const int cnt = (int)row[THR_COUNT + t];
-            if (cnt == 0 || !valid) continue;                               // (uniform)
+            if (cnt == 0 || !x.valid) continue;                             // (uniform)
             int before = (int)row[THR_OFF];
             for (int u = 0; u < t; ++u) before += (int)row[THR_COUNT + u];
             if (before >= a.capacity) continue;                             // (uniform) nothing of this tile fits
@@ -183,8 +218,8 @@ void threshold_tiles_kernel(ThresholdTileParams a) {
                 for (int w = 0; w < TILE / 32; ++w) { wpre[w] = s; s += __popc(mask[w]); }
             }
             __syncthreads();
-            SushiHipHit* __restrict__ out = a.hits + (size_t)(a.first_search + k) * (size_t)a.capacity;
-            eval([&](int i, int64_t p, float v) {
+            SushiHipHit* __restrict__ out = a.hits + (size_t)(a.lp.first_search + x.k) * (size_t)a.capacity;
+            eval_tile<U8>(src, x.rq, x.p0, lds, [&](int i, int64_t p, float v) {
                 const unsigned m = mask[i >> 5];
                 if ((m >> (i & 31)) & 1u) {
                     const int off = before + wpre[i >> 5] + __popc(m & ((1u << (i & 31)) - 1u));
@@ -197,7 +232,7 @@ void threshold_tiles_kernel(ThresholdTileParams a) {
 
 // ------------------------------------------------------------------------------------------------------------------------
 // Best-K run: the first K picks of greedy suppression over every search's whole score row, from the listed block
-// pairs alone.  The same tile bodies again, so a pick's score is the curve's value at that position, bit for bit.
+// pairs alone.
 //   best_tiles_kernel   per tile of a listed pair: its best eligible position as a pick key (BEST_KEY) and its smallest ranking
 //                       score over all positions (THR_MIN) into the pair's row -- plain stores of every word a later kernel reads;
 //   best_select_kernel  a workgroup per search, K rounds: the smallest key over the evaluated pairs' tiles is the pick; tiles
@@ -208,15 +243,13 @@ void threshold_tiles_kernel(ThresholdTileParams a) {
 // the smaller key is the better pick: (score under the order-preserving map of float bits, negated for TM_CCOEFF_NORMED) | index
 // | whether the score is -0.0 (0.0 and -0.0 are one value to the order, as to NumPy's; the bit gives the curve's bits back)
 __device__ __forceinline__ unsigned long long pick_key(const float v, const int64_t p, const bool cc) {
-    const unsigned b = __float_as_uint(cc ? -(v + 0.0f) : v + 0.0f);
-    const unsigned u = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    const unsigned u = ordered_bits(cc ? -(v + 0.0f) : v + 0.0f);
     return ((unsigned long long)u << 32) | ((unsigned long long)p << 1) | (__float_as_uint(v) == 0x80000000u ? 1ull : 0ull);
 }
 __device__ __forceinline__ int32_t pick_index(const unsigned long long key) { return (int32_t)((key & 0xffffffffull) >> 1); }
 __device__ __forceinline__ float pick_score(const unsigned long long key, const bool cc) {
     if (key & 1ull) return -0.0f;
-    const unsigned u = (unsigned)(key >> 32);
-    const float s = __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+    const float s = ordered_bits_inv((unsigned)(key >> 32));
     return cc ? -s : s;
 }
 // the ranking score the pair bound is a lower bound of (the score; 1 - the coefficient formed in double), rounded UP to a float
@@ -228,60 +261,35 @@ __device__ __forceinline__ float rank_up(const float v, const bool cc) {
     return fmaxf(f, 0.f);
 }
 
-__device__ __forceinline__ unsigned long long block_min_u64(unsigned long long v, unsigned long long* red4) {
-    v = wave_min_u64(v);
-    __syncthreads();                                                        // (red4's last readers are through)
-    if ((threadIdx.x & 63) == 0) red4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    unsigned long long m = red4[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) m = red4[w] < m ? red4[w] : m;
-    return m;
-}
-
 template <bool U8>
 __global__ __launch_bounds__(256)
 void best_tiles_kernel(BestParams a) {
-    constexpr int LDS_DOUBLES = U8 ? 4 * U8_TILE : XG * XM + f32_li_doubles<4>();
-    __shared__ double lds[LDS_DOUBLES];
+    __shared__ double lds[LISTED_LDS_DOUBLES<U8>];
     __shared__ unsigned long long red4[4];
     __shared__ unsigned red_min;
     const int tid = threadIdx.x;
-    const TileSrc src{a.r.dst_raw, a.r.dst_s1, a.r.dst_s2, a.r.dst_len, a.r.src_raw, a.r.src_s1, a.r.src_s2, a.r.centre, a.method};
-    const bool cc = a.method == SUSHI_HIP_METHOD_CCOEFF_NORMED;
-    const int n_list = a.list_count ? min(*a.list_count, a.list_max) : a.list_max;
-    const int64_t n_items = (int64_t)n_list * TILES_PER_PAIR;
+    const TileSrc src = tile_src(a.lp.r, a.lp.method);
+    const bool cc = a.lp.method == SUSHI_HIP_METHOD_CCOEFF_NORMED;
+    const int64_t n_items = listed_items(a.lp);
     for (int64_t it = blockIdx.x; it < n_items; it += gridDim.x) {
-        const int slot = (int)(it / TILES_PER_PAIR), t = (int)(it % TILES_PER_PAIR);
-        const int pr = a.list[slot];
-        const int k = a.pairmap[pr];
-        const SearchDesc sd = a.searches[k];
-        const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
-        const int64_t pairI = lay.pair0 + (a.sub_first_pair + pr - sd.first_pair);
-        const int64_t p0 = pairI * FFT_STEP * (int64_t)FFT_SEG + (int64_t)t * TILE - sd.win_start;   // (request coordinates)
-        const TileReq rq{sd.tmpl_off, sd.win_start, sd.tmpl_len, sd.n_pos};
-        uint32_t* __restrict__ row = a.rows + (size_t)pr * THR_SLOT_WORDS;
-        const bool valid = p0 + TILE > 0 && p0 < sd.n_pos;                 // (uniform) the tile holds a position of the window
+        const ListedTile x = listed_tile(a.lp, it);
         __syncthreads();                                                    // the previous item's LDS is consumed
         if (tid == 0) red_min = 0x7f800000u;                                // +inf (ranking scores are >= 0: uint order is float order)
         unsigned long long my_key = NO_KEY;
         float my_min = __builtin_inff();
-        if (valid) {
-            auto emit = [&](int, int64_t p, float v) {
-                const bool ok = !a.has_threshold || (cc ? (double)v >= a.threshold : (double)v <= a.threshold);
+        if (x.valid)
+            eval_tile<U8>(src, x.rq, x.p0, lds, [&](int, int64_t p, float v) {
+                const bool ok = !a.has_threshold || passes(v, a.threshold, cc);
                 const unsigned long long key = pick_key(v, p, cc);
                 if (ok && key < my_key) my_key = key;
                 my_min = fminf(my_min, rank_up(v, cc));
-            };
-            if constexpr (U8) u8_tile(src, rq, p0, reinterpret_cast<double(*)[U8_TILE]>(lds), emit);
-            else f32_tile<4>(src, rq, p0, lds, lds + XG * XM, emit);
-        }
+            });
         const unsigned long long best = block_min_u64(my_key, red4);        // (its barriers also order red_min's reset and use)
         atomicMin(&red_min, __float_as_uint(my_min));                       // (LDS: once per thread, after the tile)
         __syncthreads();
         if (tid == 0) {
-            reinterpret_cast<unsigned long long*>(row + BEST_KEY)[t] = best;
-            row[THR_MIN + t] = red_min;
+            reinterpret_cast<unsigned long long*>(x.row + BEST_KEY)[x.t] = best;
+            x.row[THR_MIN + x.t] = red_min;
         }
     }
 }
@@ -289,8 +297,7 @@ void best_tiles_kernel(BestParams a) {
 template <bool U8>
 __global__ __launch_bounds__(256)
 void best_select_kernel(BestParams a) {
-    constexpr int LDS_DOUBLES = U8 ? 4 * U8_TILE : XG * XM + f32_li_doubles<4>();
-    __shared__ double lds[LDS_DOUBLES];
+    __shared__ double lds[LISTED_LDS_DOUBLES<U8>];
     __shared__ unsigned long long red4[4];
     __shared__ int64_t picks[BEST_MAX_K];
     const int tid = threadIdx.x;
@@ -299,19 +306,20 @@ void best_select_kernel(BestParams a) {
         if (a.reset0) *a.reset0 = 0;
         if (a.reset1) *a.reset1 = 0;
     }
-    if (a.stamp_flags && a.stamp_flags[a.first_search + k] != a.stamp) return;      // (uniform) nothing new for this search
-    const TileSrc src{a.r.dst_raw, a.r.dst_s1, a.r.dst_s2, a.r.dst_len, a.r.src_raw, a.r.src_s1, a.r.src_s2, a.r.centre, a.method};
-    const bool cc = a.method == SUSHI_HIP_METHOD_CCOEFF_NORMED;
-    const SearchDesc sd = a.searches[k];
+    const int gk = a.lp.first_search + k;                                   // the search's global index
+    if (a.stamp_flags && a.stamp_flags[gk] != a.stamp) return;              // (uniform) nothing new for this search
+    const TileSrc src = tile_src(a.lp.r, a.lp.method);
+    const bool cc = a.lp.method == SUSHI_HIP_METHOD_CCOEFF_NORMED;
+    const SearchDesc sd = a.lp.searches[k];
     const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
-    const TileReq rq{sd.tmpl_off, sd.win_start, sd.tmpl_len, sd.n_pos};
-    const int pr0 = sd.first_pair - a.sub_first_pair;
+    const TileReq rq = tile_req(sd);
+    const int pr0 = sd.first_pair - a.lp.sub_first_pair;
     const int64_t S = a.min_separation > 0 ? a.min_separation : sd.tmpl_len;
     const int K = a.k;
-    SushiHipHit* __restrict__ out = a.hits + (size_t)(a.first_search + k) * (size_t)K;
+    SushiHipHit* __restrict__ out = a.hits + (size_t)gk * (size_t)K;
     auto evaluated = [&](const int i) { return !a.audit_mark || (a.audit_mark[pr0 + i] & 2) != 0; };
     auto keys_of = [&](const int i, const int what) {
-        return reinterpret_cast<unsigned long long*>(a.rows + (size_t)(pr0 + i) * THR_SLOT_WORDS + what);
+        return reinterpret_cast<unsigned long long*>(a.lp.rows + (size_t)(pr0 + i) * THR_SLOT_WORDS + what);
     };
     // what the rounds work on: every evaluated tile as it was evaluated
     for (int i = tid; i < lay.n_pairs; i += 256)
@@ -367,35 +375,45 @@ void best_select_kernel(BestParams a) {
                 continue;
             }
             unsigned long long my_key = NO_KEY;
-            auto emit = [&](int, int64_t p, float v) {
-                bool ok = !a.has_threshold || (cc ? (double)v >= a.threshold : (double)v <= a.threshold);
+            eval_tile<U8>(src, rq, p0, lds, [&](int, int64_t p, float v) {
+                bool ok = !a.has_threshold || passes(v, a.threshold, cc);
                 for (int q = 0; q <= j; ++q) {
                     const int64_t d = p - picks[q];
                     ok = ok && (d >= S || -d >= S);
                 }
                 const unsigned long long key = pick_key(v, p, cc);
                 if (ok && key < my_key) my_key = key;
-            };
-            if constexpr (U8) u8_tile(src, rq, p0, reinterpret_cast<double(*)[U8_TILE]>(lds), emit);
-            else f32_tile<4>(src, rq, p0, lds, lds + XG * XM, emit);
+            });
             const unsigned long long tb = block_min_u64(my_key, red4);
             if (tid == 0) w[t] = tb;
         }
         __syncthreads();                                                    // the round's stores are there for the next one's loads
     }
     if (tid == 0) {
-        a.counts[a.first_search + k] = n_picks;
+        a.counts[gk] = n_picks;
         // what a pair's bound has to stay above from now on: the K-th pick's ranking score, or the threshold's where that is tighter
         unsigned long long key = a.tkey;
         if (n_picks == K) {
             const float u = rank_up(last, cc);
             if (a.tkey == NO_KEY || u < key_score(a.tkey)) key = ((unsigned long long)__float_as_uint(u) << 32) | 0xffffffffull;
         }
-        a.gkeys[a.first_search + k] = key;
+        a.gkeys[gk] = key;
     }
 }
 
 int launch_ok() { return hipGetLastError() == hipSuccess ? SUSHI_HIP_OK : SUSHI_HIP_ELAUNCH; }
+
+// a kernel of 256 threads in its uint8 or its float32 form, by the streams' sample type
+template <class Params>
+int launch_by_dtype(const int dtype, void (*u8)(Params), void (*f32)(Params), const unsigned grid, const Params& p, hipStream_t st) {
+    hipLaunchKernelGGL(dtype == SUSHI_HIP_U8 ? u8 : f32, dim3(grid), dim3(256), 0, st, p);
+    return launch_ok();
+}
+
+// a fixed grid striding over a list's items (their number is on the device): 256 CUs, a few workgroups each
+unsigned listed_grid(const ListedPairs& lp) {
+    return (unsigned)std::min<int64_t>((int64_t)std::max(lp.list_max, 1) * TILES_PER_PAIR, 2048);
+}
 
 bool request_ok(const SushiHipRequest& r, const SushiHipStream* dst, const SushiHipStream* src) {
     if (r.tmpl_len < 1 || r.n_pos < 1 || r.win_start < 0 || r.tmpl_off < 0) return false;
@@ -408,26 +426,15 @@ bool request_ok(const SushiHipRequest& r, const SushiHipStream* dst, const Sushi
 namespace sushi {
 
 int launch_threshold_tiles(const ThresholdTileParams& p, hipStream_t st) {
-    // a fixed grid striding over the items (their number is on the device): 256 CUs, a few workgroups each
-    const int64_t want = (int64_t)std::max(p.list_max, 1) * TILES_PER_PAIR;
-    const unsigned grid = (unsigned)std::min<int64_t>(want, 2048);
-    if (p.r.dtype == SUSHI_HIP_U8) hipLaunchKernelGGL(threshold_tiles_kernel<true>, dim3(grid), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(threshold_tiles_kernel<false>, dim3(grid), dim3(256), 0, st, p);
-    return launch_ok();
+    return launch_by_dtype(p.lp.r.dtype, threshold_tiles_kernel<true>, threshold_tiles_kernel<false>, listed_grid(p.lp), p, st);
 }
 
 int launch_best_tiles(const BestParams& p, hipStream_t st) {
-    const int64_t want = (int64_t)std::max(p.list_max, 1) * TILES_PER_PAIR;
-    const unsigned grid = (unsigned)std::min<int64_t>(want, 2048);
-    if (p.r.dtype == SUSHI_HIP_U8) hipLaunchKernelGGL(best_tiles_kernel<true>, dim3(grid), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(best_tiles_kernel<false>, dim3(grid), dim3(256), 0, st, p);
-    return launch_ok();
+    return launch_by_dtype(p.lp.r.dtype, best_tiles_kernel<true>, best_tiles_kernel<false>, listed_grid(p.lp), p, st);
 }
 
 int launch_best_select(const BestParams& p, hipStream_t st) {
-    if (p.r.dtype == SUSHI_HIP_U8) hipLaunchKernelGGL(best_select_kernel<true>, dim3((unsigned)p.n_sub), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(best_select_kernel<false>, dim3((unsigned)p.n_sub), dim3(256), 0, st, p);
-    return launch_ok();
+    return launch_by_dtype(p.lp.r.dtype, best_select_kernel<true>, best_select_kernel<false>, (unsigned)p.n_sub, p, st);
 }
 
 }  // namespace sushi

@@ -42,12 +42,13 @@
 //   sushi_fft_spectra.inc  spectra_kernel, tspec_kernel
 //   sushi_fft_mac.inc      mac_kernel / mac_long_kernel / mac_list_kernel
 //   sushi_fft_ifft.inc     ifft_kernel / ifft_list_kernel: transform, scoring epilogue, error model, candidates
-//   sushi_fft_bound.inc    the pair exclusion: bound_kernel / bound_low_kernel / slb_kernel / pilot / survivor / second look / mac_rows_kernel
+//   sushi_fft_bound.inc    the pair exclusion: bound_kernel / bound_low_kernel / slb_kernel / pilot / survivor / second look / mac_rows_kernel;
+//                          the rules every run kind shares: bound_excludes, is_audit_pair, append_pairs
 //   sushi_fft_collect.inc  collect_kernel
 //   sushi_fft_threshold.inc  the threshold run's own kernels: seed, audit, extension, output scan
 //   sushi_fft_best.inc     the best-K run's own kernels: seed, escalation, audit, extension
 //   sushi_fft_plan.inc     host: workspace layout, stage timing, the plan of a batch
-//   (this file)            the batch handle and the C ABI's entry points
+//   (this file)            the batch handle, the skeleton of a run around its sub-batches (run_sub_batches) and the C ABI's entry points
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -305,6 +306,42 @@ static int run_form(SushiHipBatch* b, unsigned run_seq, hipStream_t st0, RunForm
     f->lanes = whole_rows_throughout ? 1 : b->plan.lanes;
     b->last_whole_cut = whole_cut;
     return SUSHI_HIP_OK;
+}
+
+// One run of the FFT path around its sub-batches, whatever its kind: the handle notes what kind of run its last one was, the run's
+// stream waits for the plan's upload, ONE launch clears what a run starts from (flags, violation marks, flag list, every sub-batch's
+// small counters, the pattern rows' norm accumulators, the run's counters: one contiguous zero span of the batch's layout -- and
+// the ranges `fa` arrives with), the run takes its sequence number, the lanes fork, every sub-batch goes through `per_sub` on its
+// lane, the lanes join.  An argmin run asks run_form which cut of the plan it takes and on how many lanes; the other kinds take
+// the plan's own.  Every return before the join still joins (Lanes' destructor).
+enum RunKind { RUN_ARGMIN, RUN_THRESHOLD, RUN_BEST };
+static void fill_add(FillArgs& fa, void* p, size_t bytes, uint32_t v) { fa.p[fa.n] = (uint32_t*)p; fa.words[fa.n] = (uint32_t)(bytes / 4); fa.value[fa.n] = v; ++fa.n; }
+// (the first two steps, which a direct-path run takes too)
+static int begin_run(SushiHipBatch* b, const hipStream_t st0, const RunKind kind) {
+    b->last_stream = st0; b->ran = true; b->direct_pairs = 0; b->last_threshold = kind != RUN_ARGMIN; b->last_best = kind == RUN_BEST;
+    if (kind != RUN_ARGMIN) { b->last_band = -1; b->last_whole_cut = false; b->last_suspended = 0; }      // (an argmin run: run_form's)
+    return hipStreamWaitEvent(st0, b->uploaded, 0) == hipSuccess ? SUSHI_HIP_OK : SUSHI_HIP_ELAUNCH;     // descriptors and plan have landed
+}
+template <class PerSub>
+static int run_sub_batches(RunCtx& c, const hipStream_t st0, const RunKind kind, FillArgs fa, PerSub&& per_sub) {
+    SushiHipBatch* b = c.b;
+    int rc = begin_run(b, st0, kind);
+    if (rc != SUSHI_HIP_OK) return rc;
+    fill_add(fa, c.flags, b->lay.counters + align_up(sizeof(RunCounters), 256) - b->lay.flags, 0u);
+    if (launch_fill(fa, st0) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    c.run_seq = b->run_seq++;
+    RunForm form{false, &b->plan.subs, b->plan.lanes};
+    if (kind == RUN_ARGMIN && (rc = run_form(b, c.run_seq, st0, &form)) != SUSHI_HIP_OK) return rc;
+    c.suspended = form.suspended; c.lanes = form.lanes;
+    Lanes lanes(b, st0);
+    if ((rc = lanes.fork(form.lanes)) != SUSHI_HIP_OK) return rc;
+    if (kind == RUN_ARGMIN) b->last_band = -1;                   // (the form of the last sub-batch of this run that went through the exclusion)
+    // Sub-batches of a plan on lanes run side by side (sushi_fft_plan.inc "Lanes"); the others one after the other.
+    for (size_t si = 0; si < form.subs->size(); ++si) {
+        const SubBatch& sb = (*form.subs)[si];
+        if ((rc = per_sub(SubView(b->mem, b->lay, b->plan.ws_lane, sb, si), lanes.st[sb.lane])) != SUSHI_HIP_OK) return rc;
+    }
+    return lanes.join();
 }
 
 static int stage_tspec(const RunCtx& c, const SubView& v, hipStream_t st) {
@@ -599,6 +636,44 @@ static int run_sub(RunCtx& c, const SubView& v, hipStream_t st) {
     return stage_collect(c, v, st, ia);
 }
 
+// ---- the listed-pair runs (threshold, best-K): what their sub-batches share ----
+// a threshold in ranking units (what the bound is a lower bound of: the score, 1 - the coefficient), rounded UP to a float, as a
+// search key: a pair is excluded only if its bound is above it (bound_excludes, with its slack).  `clamp_at_zero`: never below 0 --
+// no ranking score is, and the best-K run orders these keys as unsigned numbers.
+static unsigned long long ranking_key(const int method, const double threshold, const bool clamp_at_zero) {
+    double u = method == SUSHI_HIP_METHOD_CCOEFF_NORMED ? 1.0 - threshold : threshold;
+    if (clamp_at_zero) u = std::max(0.0, u);
+    float uf = (float)u;
+    if (std::isfinite(uf) && (double)uf < u) uf = std::nextafter(uf, INFINITY);
+    uint32_t ubits;
+    memcpy(&ubits, &uf, sizeof(ubits));
+    return ((unsigned long long)ubits << 32) | 0xffffffffull;
+}
+
+// what the tile kernels read (sushi_curve.hip): every pair of the sub-batch in the L2-friendly schedule, until a list replaces it
+static ListedPairs listed_pairs(const RunCtx& c, const SubView& v) {
+    ListedPairs lp;
+    lp.r = c.r; lp.searches = c.searches + v.sb.a0; lp.pairmap = v.pairmap; lp.sub_first_pair = v.sb.first_pair; lp.first_search = v.sb.a0;
+    lp.list = v.order; lp.list_count = nullptr; lp.list_max = (int)v.sb.pairs; lp.rows = (uint32_t*)v.y; lp.method = c.method;
+    return lp;
+}
+
+// ... and the runs' own kernels (sushi_fft_threshold.inc, sushi_fft_best.inc): `a` arrives zeroed
+static void pair_run_args(const RunCtx& c, const SubView& v, PairRunArgs& a) {
+    a.searches = c.searches + v.sb.a0; a.first_search = v.sb.a0; a.sub_first_pair = v.sb.first_pair; a.n_sub = v.n_sub; a.n_pairs = (int)v.sb.pairs;
+    a.pairmap = v.pairmap; a.rows = (const uint32_t*)v.y; a.slb = v.slb; a.audit_mark = v.audit_mark; a.viol = c.viol;
+    a.counters = c.counters; a.method = c.method;
+}
+
+// the lower bound of every pair: the form of the exclusion, the multiply-accumulate that form needs, the bound (run_sub does the
+// same between its profile spans)
+static int mac_and_bound(const RunCtx& c, const SubView& v, hipStream_t st, int* band, BoundArgs& ba) {
+    const int rc = decide_band(c, v, st, band);
+    if (rc != SUSHI_HIP_OK) return rc;
+    if (launch_mac(c, v, st, *band != 0, nullptr, v.items) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    return bound_pairs(c, v, st, *band, ba);
+}
+
 // What one threshold run asks for: the threshold in ranking units as a search key (survivor_kernel reads U from it), and the output.
 struct ThresholdRun { double threshold; unsigned long long ukey; int32_t capacity; SushiHipHit* hits; int64_t* counts; };
 
@@ -609,14 +684,13 @@ static int run_sub_threshold(RunCtx& c, const SubView& v, hipStream_t st, const 
     const SubBatch& sb = v.sb;
     const bool exclude = b->exclusion != SUSHI_HIP_EXCLUDE_NEVER;
     ThresholdTileParams tp;
-    tp.r = c.r; tp.searches = c.searches + sb.a0; tp.pairmap = v.pairmap; tp.sub_first_pair = sb.first_pair; tp.first_search = sb.a0;
-    tp.list = v.order; tp.list_count = nullptr; tp.list_max = (int)sb.pairs; tp.rows = (uint32_t*)v.y; tp.method = c.method;
+    tp.lp = listed_pairs(c, v);
     tp.threshold = tr.threshold; tp.pass = 0; tp.hits = tr.hits; tp.capacity = tr.capacity;
     ThrArgs ta;
     memset(&ta, 0, sizeof(ta));
-    ta.searches = c.searches + sb.a0; ta.first_search = sb.a0; ta.sub_first_pair = sb.first_pair; ta.n_sub = v.n_sub; ta.n_pairs = (int)sb.pairs;
-    ta.pairmap = v.pairmap; ta.rows = (const uint32_t*)v.y; ta.rows_w = (uint32_t*)v.y; ta.slb = v.slb; ta.viol = c.viol;
-    ta.counters = c.counters; ta.method = c.method; ta.counts_out = tr.counts;
+    pair_run_args(c, v, ta);
+    ta.rows_w = (uint32_t*)v.y; ta.counts_out = tr.counts;
+    if (!exclude) ta.audit_mark = nullptr;                       // (every pair is evaluated)
     // (tspec_kernel also leaves the sub-batch's pair -> search map, which every stage below reads)
     int rc = stage_tspec(c, v, st);
     if (rc != SUSHI_HIP_OK) return rc;
@@ -624,20 +698,18 @@ static int run_sub_threshold(RunCtx& c, const SubView& v, hipStream_t st, const 
         hipLaunchKernelGGL(thr_seed_kernel, dim3((unsigned)((v.n_sub + 255) / 256)), dim3(256), 0, st, c.gkeys + sb.a0, v.n_sub, tr.ukey, v.plist);
         if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
         int band = 0;
-        if ((rc = decide_band(c, v, st, &band)) != SUSHI_HIP_OK) return rc;
-        if (launch_mac(c, v, st, band != 0, nullptr, v.items) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
         BoundArgs ba;
-        if (bound_pairs(c, v, st, band, ba) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+        if ((rc = mac_and_bound(c, v, st, &band, ba)) != SUSHI_HIP_OK) return rc;
         // (no pilot pair: every pair is listed or excluded on its bound alone; the audit of the exclusion lists one excluded pair
         // of every audited search all the same)
         hipLaunchKernelGGL(survivor_kernel, dim3((unsigned)((sb.pairs + 255) / 256)), dim3(256), 0, st, ba);
         if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-        tp.list = ba.slist; tp.list_count = ba.scount;
+        tp.lp.list = ba.slist; tp.lp.list_count = ba.scount;
         if (band) {
             if (second_look(c, v, st, ba) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-            tp.list = ba.list2; tp.list_count = ba.list2_count;
+            tp.lp.list = ba.list2; tp.lp.list_count = ba.list2_count;
         }
-        ta.audit_mark = v.audit_mark; ta.list = tp.list; ta.list_count = tp.list_count;
+        ta.list = tp.lp.list; ta.list_count = tp.lp.list_count;
         // (the first list is free once the second look has read it; the whole-row form never used the second)
         ta.list3 = band ? v.slist : v.slist2; ta.list3_count = v.scount + 7;
     } else {
@@ -649,7 +721,7 @@ static int run_sub_threshold(RunCtx& c, const SubView& v, hipStream_t st, const 
         hipLaunchKernelGGL(thr_check_kernel, dim3((unsigned)std::min<int64_t>((sb.pairs + 255) / 256, 256)), dim3(256), 0, st, ta);
         hipLaunchKernelGGL(thr_extend_kernel, dim3((unsigned)((sb.pairs + 255) / 256)), dim3(256), 0, st, ta);
         if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-        t3.list = ta.list3; t3.list_count = ta.list3_count;
+        t3.lp.list = ta.list3; t3.lp.list_count = ta.list3_count;
         if (launch_threshold_tiles(t3, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     }
     hipLaunchKernelGGL(thr_scan_kernel, dim3((unsigned)v.n_sub), dim3(256), 0, st, ta);
@@ -673,9 +745,8 @@ static int run_sub_best(RunCtx& c, const SubView& v, hipStream_t st, const BestR
     const bool exclude = b->exclusion != SUSHI_HIP_EXCLUDE_NEVER;
     BestParams bp;
     memset(&bp, 0, sizeof(bp));
-    bp.r = c.r; bp.searches = c.searches + sb.a0; bp.pairmap = v.pairmap; bp.sub_first_pair = sb.first_pair; bp.first_search = sb.a0;
-    bp.n_sub = v.n_sub; bp.list = v.order; bp.list_count = nullptr; bp.list_max = (int)sb.pairs; bp.rows = (uint32_t*)v.y;
-    bp.method = c.method; bp.has_threshold = br.has_threshold; bp.threshold = br.threshold; bp.tkey = br.tkey; bp.k = br.k;
+    bp.lp = listed_pairs(c, v);
+    bp.n_sub = v.n_sub; bp.has_threshold = br.has_threshold; bp.threshold = br.threshold; bp.tkey = br.tkey; bp.k = br.k;
     bp.min_separation = br.min_separation; bp.gkeys = c.gkeys; bp.hits = br.hits; bp.counts = br.counts;
     // (tspec_kernel also leaves the sub-batch's pair -> search map, which every stage below reads)
     int rc = stage_tspec(c, v, st);
@@ -685,24 +756,21 @@ static int run_sub_best(RunCtx& c, const SubView& v, hipStream_t st, const BestR
         if (launch_best_tiles(bp, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
         return launch_best_select(bp, st);
     }
-    int band = 0;
-    if ((rc = decide_band(c, v, st, &band)) != SUSHI_HIP_OK) return rc;
-    if (launch_mac(c, v, st, band != 0, nullptr, v.items) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     // (the bounds depend on no threshold: made once)
+    int band = 0;
     BoundArgs ba;
-    if (bound_pairs(c, v, st, band, ba) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    if ((rc = mac_and_bound(c, v, st, &band, ba)) != SUSHI_HIP_OK) return rc;
     BestArgs a;
     memset(&a, 0, sizeof(a));
-    a.searches = c.searches + sb.a0; a.first_search = sb.a0; a.sub_first_pair = sb.first_pair; a.n_sub = v.n_sub; a.n_pairs = (int)sb.pairs;
-    a.k = br.k; a.pairmap = v.pairmap; a.order = v.order; a.rows = (const uint32_t*)v.y; a.slb = v.slb; a.audit_mark = v.audit_mark;
-    a.gkeys = c.gkeys; a.tkey = br.tkey; a.list = v.slist; a.list_count = v.scount; a.flags = c.flags; a.need = c.flag_list; a.viol = c.viol;
-    a.counters = c.counters; a.method = c.method; a.audit_seq = c.run_seq; a.audit_every = b->audit_every;
+    pair_run_args(c, v, a);
+    a.k = br.k; a.order = v.order; a.gkeys = c.gkeys; a.tkey = br.tkey; a.list = v.slist; a.list_count = v.scount; a.flags = c.flags;
+    a.need = c.flag_list; a.audit_seq = c.run_seq; a.audit_every = b->audit_every;
     // the two lists and their lengths (zero since the run's first launch; every selection clears them for the round behind it)
     int* const count2 = v.scount + 5;
     bp.audit_mark = v.audit_mark; bp.stamp_flags = c.flags; bp.reset0 = v.scount; bp.reset1 = count2;
     const unsigned per_pair = (unsigned)((sb.pairs + 255) / 256);
     auto evaluate = [&](const int* list, const int* count) {
-        bp.list = list; bp.list_count = count;
+        bp.lp.list = list; bp.lp.list_count = count;
         return launch_best_tiles(bp, st);
     };
     int stamp = 1;
@@ -956,43 +1024,23 @@ int sushi_hip_batch_run(SushiHipBatch* b, double delta, int32_t* out_idx_dev, fl
     if (!b || !out_idx_dev || !out_score_dev) return SUSHI_HIP_EINVAL;
     const hipStream_t st0 = (hipStream_t)hip_stream;
     RunCtx c(b, delta);
-    b->last_stream = st0; b->ran = true; b->direct_pairs = 0; b->last_threshold = false; b->last_best = false;
-    if (hipStreamWaitEvent(st0, b->uploaded, 0) != hipSuccess) return SUSHI_HIP_ELAUNCH;   // descriptors and plan have landed
-    if (b->path == SUSHI_HIP_PATH_DIRECT)
+    if (b->path == SUSHI_HIP_PATH_DIRECT) {
+        if (begin_run(b, st0, RUN_ARGMIN) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
         return launch_direct(c.r, c.searches, b->n, (int)b->n_tiles, b->variant, b->method, c.keys, out_idx_dev, out_score_dev, b->packed_out, st0);
-
+    }
     if (!(delta >= 3.8e-6) || delta > 1.0) return SUSHI_HIP_EINVAL;      // the floor covers the scoring arithmetic's own rounding
     if (g_prof_on) { g_prof.emplace_back(); c.pc = &g_prof.back(); }
-    {
-        // Everything a run clears before its first kernel, in ONE launch: result keys (all ones), flags / violation marks / flag list /
-        // every sub-batch's small counters / the pattern rows' norm accumulators / run counters (one contiguous zero span of the batch's
-        // layout), and -- a batch of one sub-batch, while they are small -- its candidate rows.
-        FillArgs fa;
-        memset(&fa, 0, sizeof(fa));
-        auto add = [&](void* p, size_t bytes, uint32_t v) { fa.p[fa.n] = (uint32_t*)p; fa.words[fa.n] = (uint32_t)(bytes / 4); fa.value[fa.n] = v; ++fa.n; };
-        add(c.keys, (size_t)2 * b->n * sizeof(uint64_t), 0xffffffffu);
-        add(c.flags, b->lay.counters + align_up(sizeof(RunCounters), 256) - b->lay.flags, 0u);
-        if (b->plan.subs.size() == 1) {
-            const SubView v0(b->mem, b->lay, b->plan.ws_lane, b->plan.subs[0], 0);
-            const size_t cand_bytes = (size_t)v0.sb.pairs * FFT_ROW * sizeof(unsigned long long);
-            if (cand_bytes <= ((size_t)8 << 20)) { add(v0.cand, cand_bytes, 0xffffffffu); c.cand_filled = true; }
-        }
-        if (launch_fill(fa, st0) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    // What an argmin run clears besides: the result keys (all ones) and -- a batch of one sub-batch, while they are small -- its
+    // candidate rows.
+    FillArgs fa{};
+    fill_add(fa, c.keys, (size_t)2 * b->n * sizeof(uint64_t), 0xffffffffu);
+    if (b->plan.subs.size() == 1) {
+        const SubView v0(b->mem, b->lay, b->plan.ws_lane, b->plan.subs[0], 0);
+        const size_t cand_bytes = (size_t)v0.sb.pairs * FFT_ROW * sizeof(unsigned long long);
+        if (cand_bytes <= ((size_t)8 << 20)) { fill_add(fa, v0.cand, cand_bytes, 0xffffffffu); c.cand_filled = true; }
     }
-    c.run_seq = b->run_seq++;
-    RunForm form;
-    int rc = run_form(b, c.run_seq, st0, &form);
+    int rc = run_sub_batches(c, st0, RUN_ARGMIN, fa, [&](const SubView& v, hipStream_t st) { return run_sub(c, v, st); });
     if (rc != SUSHI_HIP_OK) return rc;
-    c.suspended = form.suspended; c.lanes = form.lanes;
-    Lanes lanes(b, st0);
-    if ((rc = lanes.fork(form.lanes)) != SUSHI_HIP_OK) return rc;
-    b->last_band = -1;                                           // (the form of the last sub-batch of this run that went through the exclusion)
-    // Sub-batches of a plan on lanes run side by side (sushi_fft_plan.inc "Lanes"); the others one after the other.
-    for (size_t si = 0; si < form.subs->size(); ++si) {
-        const SubBatch& sb = (*form.subs)[si];
-        if ((rc = run_sub(c, SubView(b->mem, b->lay, b->plan.ws_lane, sb, si), lanes.st[sb.lane])) != SUSHI_HIP_OK) return rc;
-    }
-    if ((rc = lanes.join()) != SUSHI_HIP_OK) return rc;
     hipEvent_t t0 = prof_begin(c.pc, st0);
     rc = launch_unpack(c.keys, b->n, b->method, out_idx_dev, out_score_dev, b->packed_out, st0);
     prof_end(c.pc, t0, SUSHI_HIP_STAGE_FINISH, st0);
@@ -1013,37 +1061,10 @@ int sushi_hip_batch_run_threshold(SushiHipBatch* b, double threshold, int32_t ca
     if (!b || !out_hits_dev || !out_counts_dev || capacity < 0 || !std::isfinite(threshold) || b->path != SUSHI_HIP_PATH_FFT)
         return SUSHI_HIP_EINVAL;
     if (((uintptr_t)out_hits_dev & 3) || ((uintptr_t)out_counts_dev & 7)) return SUSHI_HIP_EALIGN;
-    // U in ranking units (what the bound is a lower bound of: the score, 1 - the coefficient), rounded up to a float: a pair is
-    // excluded only if its bound is above it (survivor_kernel, with its slack)
-    const double u = b->method == SUSHI_HIP_METHOD_CCOEFF_NORMED ? 1.0 - threshold : threshold;
-    float uf = (float)u;
-    if (std::isfinite(uf) && (double)uf < u) uf = std::nextafter(uf, INFINITY);
-    uint32_t ubits;
-    memcpy(&ubits, &uf, sizeof(ubits));
-    const ThresholdRun tr{threshold, ((unsigned long long)ubits << 32) | 0xffffffffull, capacity, out_hits_dev, out_counts_dev};
-    const hipStream_t st0 = (hipStream_t)hip_stream;
+    const ThresholdRun tr{threshold, ranking_key(b->method, threshold, false), capacity, out_hits_dev, out_counts_dev};
     RunCtx c(b, 0.0);
-    b->last_stream = st0; b->ran = true; b->direct_pairs = 0; b->last_threshold = true; b->last_best = false;
-    b->last_band = -1; b->last_whole_cut = false; b->last_suspended = 0;
-    if (hipStreamWaitEvent(st0, b->uploaded, 0) != hipSuccess) return SUSHI_HIP_ELAUNCH;   // descriptors and plan have landed
-    {
-        // flags, violation marks, every sub-batch's small counters, the pattern rows' norm accumulators, the run's counters
-        FillArgs fa;
-        memset(&fa, 0, sizeof(fa));
-        fa.p[0] = (uint32_t*)c.flags; fa.words[0] = (uint32_t)((b->lay.counters + align_up(sizeof(RunCounters), 256) - b->lay.flags) / 4);
-        fa.value[0] = 0u; fa.n = 1;
-        if (launch_fill(fa, st0) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-    }
-    c.run_seq = b->run_seq++;
-    c.lanes = b->plan.lanes;
-    Lanes lanes(b, st0);
-    int rc = lanes.fork(b->plan.lanes);
-    if (rc != SUSHI_HIP_OK) return rc;
-    for (size_t si = 0; si < b->plan.subs.size(); ++si) {
-        const SubBatch& sb = b->plan.subs[si];
-        if ((rc = run_sub_threshold(c, SubView(b->mem, b->lay, b->plan.ws_lane, sb, si), lanes.st[sb.lane], tr)) != SUSHI_HIP_OK) return rc;
-    }
-    return lanes.join();
+    return run_sub_batches(c, (hipStream_t)hip_stream, RUN_THRESHOLD, FillArgs{},
+                           [&](const SubView& v, hipStream_t st) { return run_sub_threshold(c, v, st, tr); });
 } catch (const std::bad_alloc&) { return SUSHI_HIP_ENOMEM; } catch (...) { return SUSHI_HIP_EINTERNAL; }     // nothing crosses the C boundary
 
 int sushi_hip_batch_run_best(SushiHipBatch* b, int32_t k, int32_t min_separation, const double* threshold, SushiHipHit* out_hits_dev,
@@ -1052,40 +1073,12 @@ int sushi_hip_batch_run_best(SushiHipBatch* b, int32_t k, int32_t min_separation
         (threshold && !std::isfinite(*threshold)) || b->path != SUSHI_HIP_PATH_FFT)
         return SUSHI_HIP_EINVAL;
     if (((uintptr_t)out_hits_dev & 3) || ((uintptr_t)out_counts_dev & 3)) return SUSHI_HIP_EALIGN;
-    BestRun br{k, min_separation, threshold ? 1 : 0, threshold ? *threshold : 0.0, NO_KEY, out_hits_dev, out_counts_dev};
-    if (threshold) {
-        // the threshold in ranking units, rounded up to a float, as sushi_hip_batch_run_threshold forms it (never below 0: no ranking
-        // score is, and the keys order as unsigned numbers)
-        const double u = std::max(0.0, b->method == SUSHI_HIP_METHOD_CCOEFF_NORMED ? 1.0 - *threshold : *threshold);
-        float uf = (float)u;
-        if (std::isfinite(uf) && (double)uf < u) uf = std::nextafter(uf, INFINITY);
-        uint32_t ubits;
-        memcpy(&ubits, &uf, sizeof(ubits));
-        br.tkey = ((unsigned long long)ubits << 32) | 0xffffffffull;
-    }
-    const hipStream_t st0 = (hipStream_t)hip_stream;
+    // (the threshold's key never below 0, unlike a threshold run's: ranking_key)
+    const BestRun br{k, min_separation, threshold ? 1 : 0, threshold ? *threshold : 0.0,
+                     threshold ? ranking_key(b->method, *threshold, true) : NO_KEY, out_hits_dev, out_counts_dev};
     RunCtx c(b, 0.0);
-    b->last_stream = st0; b->ran = true; b->direct_pairs = 0; b->last_threshold = true; b->last_best = true;
-    b->last_band = -1; b->last_whole_cut = false; b->last_suspended = 0;
-    if (hipStreamWaitEvent(st0, b->uploaded, 0) != hipSuccess) return SUSHI_HIP_ELAUNCH;   // descriptors and plan have landed
-    {
-        // flags, violation marks, flag list, every sub-batch's small counters, the pattern rows' norm accumulators, the run's counters
-        FillArgs fa;
-        memset(&fa, 0, sizeof(fa));
-        fa.p[0] = (uint32_t*)c.flags; fa.words[0] = (uint32_t)((b->lay.counters + align_up(sizeof(RunCounters), 256) - b->lay.flags) / 4);
-        fa.value[0] = 0u; fa.n = 1;
-        if (launch_fill(fa, st0) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-    }
-    c.run_seq = b->run_seq++;
-    c.lanes = b->plan.lanes;
-    Lanes lanes(b, st0);
-    int rc = lanes.fork(b->plan.lanes);
-    if (rc != SUSHI_HIP_OK) return rc;
-    for (size_t si = 0; si < b->plan.subs.size(); ++si) {
-        const SubBatch& sb = b->plan.subs[si];
-        if ((rc = run_sub_best(c, SubView(b->mem, b->lay, b->plan.ws_lane, sb, si), lanes.st[sb.lane], br)) != SUSHI_HIP_OK) return rc;
-    }
-    return lanes.join();
+    return run_sub_batches(c, (hipStream_t)hip_stream, RUN_BEST, FillArgs{},
+                           [&](const SubView& v, hipStream_t st) { return run_sub_best(c, v, st, br); });
 } catch (const std::bad_alloc&) { return SUSHI_HIP_ENOMEM; } catch (...) { return SUSHI_HIP_EINTERNAL; }     // nothing crosses the C boundary
 
 int sushi_hip_batch_diagnostics(SushiHipBatch* b, SushiHipBatchDiag* diag, float* ranking_err_host, int32_t* flagged_host) try {

@@ -415,9 +415,7 @@ void pilot_kernel(BoundArgs a) {
     for (int i = lane; i < lay.n_pairs; i += 64) {
         const float s = a.slb[p0 + i];
         // order-preserving key of a float that may be negative or -inf
-        const unsigned b = __float_as_uint(s);
-        const unsigned ord = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-        const unsigned long long key = ((unsigned long long)ord << 32) | (unsigned)i;
+        const unsigned long long key = ((unsigned long long)ordered_bits(__float_as_uint(s)) << 32) | (unsigned)i;
         best = key < best ? key : best;
     }
     best = wave_min_u64(best);
@@ -426,6 +424,48 @@ void pilot_kernel(BoundArgs a) {
         if (k == 0) *a.scount = 0;
         atomicAdd(&a.counters->pairs_transformed, 1ull);
     }
+}
+
+// ---- the rules every run kind shares (argmin, threshold, best-K) ----
+// THE exclusion rule (DESIGN.md 3.2): a pair is excluded only if its lower bound, with the slack, is above its search's running
+// threshold U (`gkey`, a search key; NO_KEY: none yet).  A search whose U is 1 -- no match anywhere, every score clamped to 1 --
+// ties everywhere: nothing of it is excluded.  (Array and index, not the value: the bound is loaded only where U can exclude.)
+__device__ __forceinline__ bool bound_excludes(const float* slb, const int pr, const unsigned long long gkey) {
+    const float U = gkey == NO_KEY ? __builtin_inff() : key_score(gkey);
+    return U < 0.9999f && slb[pr] > U * 1.000001f + 1e-7f;
+}
+
+// The audit of the exclusion: one search in `audit_every` is audited per run -- other ones every run --, and of it one hashed pair:
+// if the bound excluded that pair, it is evaluated all the same and its bound held to what it really scores.  Whether search `k`
+// (of the sub-batch) is audited in this run; which of its own pairs then; both: whether pair `pr` (of the sub-batch) is that pair.
+template <class Args>
+__device__ __forceinline__ bool audited_search(const Args& a, const int k) {
+    return a.audit_every > 0 && ((unsigned)(a.first_search + k) + a.audit_seq) % (unsigned)a.audit_every == 0u;
+}
+template <class Args>
+__device__ __forceinline__ int audit_pair_of(const Args& a, const SearchDesc& sd, const int k) {
+    const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
+    const unsigned h = ((unsigned)(a.first_search + k) * 2654435761u + a.audit_seq * 40503u) >> 9;
+    return (int)(h % (unsigned)lay.n_pairs);
+}
+template <class Args>
+__device__ __forceinline__ bool is_audit_pair(const Args& a, const int pr, const int k) {
+    if (!audited_search(a, k)) return false;
+    const SearchDesc sd = a.searches[k];
+    return audit_pair_of(a, sd, k) == a.sub_first_pair + pr - sd.first_pair;
+}
+
+// the pairs `pr` of the lanes with `add` set to the end of a list, in lane order: one atomicAdd per wave (every lane calls it)
+__device__ __forceinline__ void append_pairs(int* list, int* count, RunCounters* counters, const bool add, const int pr) {
+    const unsigned long long m = __ballot(add);
+    const int lane = threadIdx.x & 63;
+    int base = 0;
+    if (lane == 0 && m) {
+        base = atomicAdd(count, __popcll(m));
+        atomicAdd(&counters->pairs_transformed, (unsigned long long)__popcll(m));
+    }
+    base = __shfl(base, 0, 64);
+    if (add) list[base + __popcll(m & ((1ull << lane) - 1ull))] = pr;
 }
 
 // every pair but the pilots: excluded (its lower bound is above what the search has already found: pair_lb = +inf, what
@@ -440,32 +480,19 @@ void survivor_kernel(BoundArgs a) {
         const int k = a.pairmap[pr];
         bool audit = false;
         if (a.plist[k] != pr) {
-            const unsigned long long g = a.gkeys[a.first_search + k];
-            const float U = g == NO_KEY ? __builtin_inff() : key_score(g);
-            // (a search whose best score is 1 -- no match anywhere, every score clamped to 1 -- ties everywhere: nothing is excluded)
-            const bool excluded = U < 0.9999f && a.slb[pr] > U * 1.000001f + 1e-7f;
-            if (excluded && a.audit_every > 0 && ((unsigned)(a.first_search + k) + a.audit_seq) % (unsigned)a.audit_every == 0u) {
-                // the audit of the exclusion: one hashed pair of the search; if the bound excluded it, it is transformed all the
-                // same and ifft_kernel holds its bound to what it really scores
+            const bool excluded = bound_excludes(a.slb, pr, a.gkeys[a.first_search + k]);
+            // (is_audit_pair, from its two parts: with the flag coming back through the one helper two operands of an s_or_b64 change
+            // places in this kernel's code, and the bench path's recorded counters stand on identical code)
+            if (excluded && audited_search(a, k)) {
                 const SearchDesc sd = a.searches[k];
-                const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
-                const unsigned h = ((unsigned)(a.first_search + k) * 2654435761u + a.audit_seq * 40503u) >> 9;
-                audit = (int)(h % (unsigned)lay.n_pairs) == a.sub_first_pair + pr - sd.first_pair;
+                audit = audit_pair_of(a, sd, k) == a.sub_first_pair + pr - sd.first_pair;
             }
             if (excluded && !audit) a.pair_lb[pr] = __builtin_inff();
             keep = !excluded || audit;
         }
         if (a.audit_mark) a.audit_mark[pr] = (audit ? 1 : 0) | (keep ? 2 : 0);          // bit 0: audited, bit 1: listed
     }
-    const unsigned long long m = __ballot(keep);
-    const int lane = threadIdx.x & 63;
-    int base = 0;
-    if (lane == 0 && m) {
-        base = atomicAdd(a.scount, __popcll(m));
-        atomicAdd(&a.counters->pairs_transformed, (unsigned long long)__popcll(m));
-    }
-    base = __shfl(base, 0, 64);
-    if (keep) a.slist[base + __popcll(m & ((1ull << lane) - 1ull))] = pr;
+    append_pairs(a.slist, a.scount, a.counters, keep, pr);
 }
 
 // The whole rows of the LISTED pairs, search by search (band-split form, the pairs the bound left): a workgroup = 256 consecutive
@@ -632,9 +659,7 @@ void survivor2_kernel(BoundArgs a) {
             keep = true;
             if (second_look && !(a.audit_mark[pr] & 1)) {
                 const int k = a.pairmap[pr];
-                const unsigned long long g = a.gkeys[a.first_search + k];
-                const float U = g == NO_KEY ? __builtin_inff() : key_score(g);
-                if (U < 0.9999f && a.slb[pr] > U * 1.000001f + 1e-7f) {
+                if (bound_excludes(a.slb, pr, a.gkeys[a.first_search + k])) {
                     // the audit of THIS bound: a hashed sample of the pairs it excludes -- other ones every run -- stays listed, is
                     // transformed all the same, and ifft_kernel holds the pair's (second) lower bound to what it really scores
                     const unsigned h = ((unsigned)(a.sub_first_pair + pr) * 2654435761u + a.audit_seq * 40503u) >> 11;

@@ -140,16 +140,14 @@ struct TileParams {
 };
 int launch_tiles(const TileParams& p, hipStream_t st);
 
-// FFT path, threshold run (sushi_hip_batch_run_threshold).  A listed block pair is evaluated exactly at each of its
-// 2 FFT_H positions, as TILES_PER_PAIR tiles of TILE consecutive ones (the curves' tile bodies, sushi_curve.hip).  What a pair
-// leaves lies in its own 64 KB row of the sub-batch's Y region (a threshold run forms no whole rows after the bound has read them):
-constexpr int THR_MASK = 0;                                    // [TILES_PER_PAIR * TILE / 32] bit i: position i of the pair passes
-constexpr int THR_COUNT = TILES_PER_PAIR * TILE / 32;          // [TILES_PER_PAIR] hits per tile
-constexpr int THR_MIN = THR_COUNT + TILES_PER_PAIR;            // [TILES_PER_PAIR] float bits: smallest ranking score of the tile
-constexpr int THR_OFF = THR_MIN + TILES_PER_PAIR;              // the pair's first hit in its search's output (thr_scan_kernel)
+// FFT path, the listed-pair runs: threshold (sushi_hip_batch_run_threshold) and best-K (sushi_hip_batch_run_best;
+// DESIGN.md 3.11).  A listed block pair is evaluated exactly at each of its 2 FFT_H positions, as TILES_PER_PAIR tiles of TILE
+// consecutive ones (the curves' tile bodies, sushi_curve.hip).  What a pair leaves lies in its own 64 KB row of the sub-batch's Y
+// region (neither run forms whole rows after the bound has read them).
 constexpr int THR_SLOT_WORDS = FFT_N;                          // 32-bit words of a pair's row (FFT_N packed-half bins)
-static_assert(THR_OFF < THR_SLOT_WORDS, "a pair's hit mask and counts fit its row");
-struct ThresholdTileParams {
+// What the tile kernels of both runs read to find their work (sushi_fft.hip listed_pairs fills it, sushi_curve.hip listed_tile
+// decodes a work item from it): the streams, the sub-batch's searches, the list of pairs to evaluate, the pairs' rows.
+struct ListedPairs {
     StreamRefs r;
     const SearchDesc* searches;       // the sub-batch's searches
     const int* pairmap;               // [pairs of the sub-batch] -> search of the sub-batch
@@ -157,9 +155,19 @@ struct ThresholdTileParams {
     int first_search;                 // global index of searches[0]: its output slot
     const int* list;                  // the pairs to evaluate: list[0 .. *list_count), or [0 .. list_max) where list_count is NULL
     const int* list_count;
-    int list_max;
+    int list_max;                     // the sub-batch's pairs: every list holds distinct pairs of it, so no list is longer
     uint32_t* rows;                   // [pairs of the sub-batch][THR_SLOT_WORDS]
     int method;
+};
+
+// Threshold run: a pair's row
+constexpr int THR_MASK = 0;                                    // [TILES_PER_PAIR * TILE / 32] bit i: position i of the pair passes
+constexpr int THR_COUNT = TILES_PER_PAIR * TILE / 32;          // [TILES_PER_PAIR] hits per tile
+constexpr int THR_MIN = THR_COUNT + TILES_PER_PAIR;            // [TILES_PER_PAIR] float bits: smallest ranking score of the tile
+constexpr int THR_OFF = THR_MIN + TILES_PER_PAIR;              // the pair's first hit in its search's output (thr_scan_kernel)
+static_assert(THR_OFF < THR_SLOT_WORDS, "a pair's hit mask and counts fit its row");
+struct ThresholdTileParams {
+    ListedPairs lp;
     double threshold;                 // SQDIFF_NORMED: score <= threshold; CCOEFF_NORMED: score >= threshold
     int pass;                         // 0: hit masks, counts and minima; 1: (index, score) of every hit into `hits`
     SushiHipHit* hits;                // [searches][capacity]
@@ -167,28 +175,19 @@ struct ThresholdTileParams {
 };
 int launch_threshold_tiles(const ThresholdTileParams& p, hipStream_t st);
 
-// FFT path, best-K run (sushi_hip_batch_run_best).  An evaluated pair's row holds, per tile, the best eligible
-// position of the tile as a 64-bit pick key -- the smaller key is the better pick: the float32 score under the order-preserving map
-// of its bits (negated for TM_CCOEFF_NORMED; -0.0 and 0.0 tie), then the lower index -- once as evaluated (BEST_KEY: no pick
-// masked) and once as the selection works on it (BEST_WORK: dead tiles NO_KEY, tiles a pick's window cuts evaluated again with the
-// picks masked); and the tile's smallest ranking score over ALL its positions (THR_MIN: the bound's audit, as in a threshold run).
+// Best-K run.  An evaluated pair's row holds, per tile, the best eligible position of the tile as a 64-bit pick key -- the smaller
+// key is the better pick: the float32 score under the order-preserving map of its bits (ordered_bits; negated for TM_CCOEFF_NORMED;
+// -0.0 and 0.0 tie), then the lower index -- once as evaluated (BEST_KEY: no pick masked) and once as the selection works on it
+// (BEST_WORK: dead tiles NO_KEY, tiles a pick's window cuts evaluated again with the picks masked); and the tile's smallest ranking
+// score over ALL its positions (THR_MIN: the bound's audit, as in a threshold run).
 constexpr int BEST_KEY = 0;                                    // [TILES_PER_PAIR] 64-bit keys
 constexpr int BEST_WORK = 2 * TILES_PER_PAIR;                  // [TILES_PER_PAIR] 64-bit keys
 static_assert(BEST_WORK + 2 * TILES_PER_PAIR <= THR_COUNT, "the pick keys lie in front of the tile minima");
 constexpr int BEST_MAX_K = SUSHI_HIP_BEST_MAX_K;
 struct BestParams {
-    StreamRefs r;
-    const SearchDesc* searches;       // the sub-batch's searches
-    const int* pairmap;               // [pairs of the sub-batch] -> search of the sub-batch
-    int sub_first_pair;
-    int first_search;                 // global index of searches[0]
+    ListedPairs lp;                   // (the list: best_tiles_kernel's)
     int n_sub;
-    const int* list;                  // best_tiles_kernel: the pairs to evaluate, list[0 .. *list_count) or [0 .. list_max) where list_count is NULL
-    const int* list_count;
-    int list_max;
-    uint32_t* rows;                   // [pairs of the sub-batch][THR_SLOT_WORDS]
     const unsigned char* audit_mark;  // bit 1: the pair is evaluated; NULL: every pair is
-    int method;
     int has_threshold;
     double threshold;                 // eligible: score <= threshold (SQDIFF_NORMED) / >= threshold (CCOEFF_NORMED)
     unsigned long long tkey;          // the threshold in ranking units, rounded up, as a search key; NO_KEY: none

@@ -248,6 +248,16 @@ def _checked_requests(dst, src, tmpl_off, tmpl_len, win_start, n_pos):
     return req
 
 
+def _hit_lists(records, counts):
+    """[(index int64 ndarray, score float32 ndarray) per request] from a run's (index, score bits) records [n, capacity, 2] and
+    its counts [n] (SearchBatch.run_threshold / run_best, on the host)."""
+    out = []
+    for k in range(records.shape[0]):
+        rec = records[k, :int(counts[k])]
+        out.append((rec[:, 0].astype(np.int64), np.ascontiguousarray(rec[:, 1]).view(np.float32)))
+    return out
+
+
 class SearchBatch(object):
     """Requests of a batch of searches, resident in HBM, plus the output buffers.
 
@@ -456,12 +466,7 @@ class SearchBatch(object):
             hits, counts = self.run_threshold(threshold, need)
             cnt = counts.cpu().numpy()
             cap = need
-        h = hits.cpu().numpy() if cap else np.zeros((self.n, 0, 2), np.int32)
-        out = []
-        for k in range(self.n):
-            rec = h[k, :int(cnt[k])]
-            out.append((rec[:, 0].astype(np.int64), np.ascontiguousarray(rec[:, 1]).view(np.float32)))
-        return out
+        return _hit_lists(hits.cpu().numpy() if cap else np.zeros((self.n, 0, 2), np.int32), cnt)
 
     def run_best(self, k, min_separation=None, threshold=None, hip_stream=None):
         """The k best distinct matches of every request (sushi_hip_batch_run_best; FFT path, asynchronous): the first k picks of
@@ -500,13 +505,7 @@ class SearchBatch(object):
     def best(self, k, min_separation=None, threshold=None):
         """[(index int64 ndarray, score float32 ndarray) per request]: run_best's picks, best first.  Synchronises."""
         hits, counts = self.run_best(k, min_separation, threshold)
-        cnt = counts.cpu().numpy()
-        h = hits.cpu().numpy()
-        out = []
-        for j in range(self.n):
-            rec = h[j, :int(cnt[j])]
-            out.append((rec[:, 0].astype(np.int64), np.ascontiguousarray(rec[:, 1]).view(np.float32)))
-        return out
+        return _hit_lists(hits.cpu().numpy(), counts.cpu().numpy())
 
     def results(self):
         """(idx int32 ndarray, score float32 ndarray) -- synchronises."""

@@ -15,23 +15,27 @@ from .common import SushiError
 from .device import SearchBatch, _checked_requests
 
 
-def find_occurrences(dst, src, tmpl_off, tmpl_len, win_start, n_pos, threshold, method="ccoeff_normed", capacity=None):
-    """Hits of a batch of requests (the arrays of ``SearchBatch``) on the DeviceStreams ``dst`` / ``src``: a list of
-    ``(index int64 ndarray, score float32 ndarray)`` per request, in ascending index order.  method 'ccoeff_normed' (default):
-    score >= threshold, the TM_CCOEFF_NORMED value itself; 'sqdiff_normed': score <= threshold.  Every score is bit-identical to
-    ``match_curves`` at that index.  capacity: hits kept per request in a first pass (SearchBatch.occurrences)."""
+def _fft_batch(dst, src, tmpl_off, tmpl_len, win_start, n_pos, method, threshold):
+    """The argument checks find_occurrences and find_best share, and the FFT-path batch of their requests."""
     if method not in _native.METHODS:
         raise SushiError("method must be one of %s" % sorted(_native.METHODS))
     if dst.device != src.device:
         raise SushiError("dst and src streams live on different devices")
     if dst.dtype != src.dtype:
         raise SushiError("pattern and stream sample types differ (cv2.matchTemplate asserts equal types)")
-    threshold = float(threshold)
-    if not np.isfinite(threshold):
+    if threshold is not None and not np.isfinite(float(threshold)):
         raise SushiError("threshold must be finite")
     req = _checked_requests(dst, src, tmpl_off, tmpl_len, win_start, n_pos)
-    batch = SearchBatch(dst, src, req["tmpl_off"], req["tmpl_len"], req["win_start"], req["n_pos"], path="fft", method=method)
-    return batch.occurrences(threshold, capacity)
+    return SearchBatch(dst, src, req["tmpl_off"], req["tmpl_len"], req["win_start"], req["n_pos"], path="fft", method=method)
+
+
+def find_occurrences(dst, src, tmpl_off, tmpl_len, win_start, n_pos, threshold, method="ccoeff_normed", capacity=None):
+    """Hits of a batch of requests (the arrays of ``SearchBatch``) on the DeviceStreams ``dst`` / ``src``: a list of
+    ``(index int64 ndarray, score float32 ndarray)`` per request, in ascending index order.  method 'ccoeff_normed' (default):
+    score >= threshold, the TM_CCOEFF_NORMED value itself; 'sqdiff_normed': score <= threshold.  Every score is bit-identical to
+    ``match_curves`` at that index.  capacity: hits kept per request in a first pass (SearchBatch.occurrences)."""
+    threshold = float(threshold)
+    return _fft_batch(dst, src, tmpl_off, tmpl_len, win_start, n_pos, method, threshold).occurrences(threshold, capacity)
 
 
 def peaks(index, score, min_separation, method="ccoeff_normed"):
@@ -72,15 +76,7 @@ def find_best(dst, src, tmpl_off, tmpl_len, win_start, n_pos, k, min_separation=
     it (score >= threshold for 'ccoeff_normed', <= for 'sqdiff_normed').  Every score is bit-identical to ``match_curves`` at
     that index.  A k beyond the number of real occurrences costs an exact evaluation of most of the window unless a threshold
     keeps chance-level scores out (SearchBatch.run_best)."""
-    if method not in _native.METHODS:
-        raise SushiError("method must be one of %s" % sorted(_native.METHODS))
-    if dst.device != src.device:
-        raise SushiError("dst and src streams live on different devices")
-    if dst.dtype != src.dtype:
-        raise SushiError("pattern and stream sample types differ (cv2.matchTemplate asserts equal types)")
-    req = _checked_requests(dst, src, tmpl_off, tmpl_len, win_start, n_pos)
-    batch = SearchBatch(dst, src, req["tmpl_off"], req["tmpl_len"], req["win_start"], req["n_pos"], path="fft", method=method)
-    return batch.best(k, min_separation, threshold)
+    return _fft_batch(dst, src, tmpl_off, tmpl_len, win_start, n_pos, method, threshold).best(k, min_separation, threshold)
 
 
 def best_peaks(curve, k, min_separation, method="ccoeff_normed", threshold=None):

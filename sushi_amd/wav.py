@@ -345,16 +345,8 @@ class WavStream(object):
         'ccoeff_normed' = cv2.TM_CCOEFF_NORMED with argmax instead (not used by the reference; the method BASELINE.json names)."""
         from .device import SearchBatch
         n = len(patterns)
-        if not (len(window_centers) == len(window_sizes) == n) or n == 0:
-            raise SushiError('find_substreams: need equally many patterns, centres and sizes (>= 1)')
-        dst_dev = self.device_stream()
-        src_dev, offs, lens, one_owner = self._pattern_source(patterns, dst_dev)
-        start_times, win_start, n_pos = [], [], []
-        for m, c, w in zip(lens, window_centers, window_sizes):
-            st, lo, p = self._window(m, c, w)
-            start_times.append(st)
-            win_start.append(lo)
-            n_pos.append(p)
+        dst_dev, src_dev, offs, lens, one_owner, start_times, win_start, n_pos = self._requests(
+            'find_substreams', patterns, window_centers, window_sizes)
         # A drop-in call is a batch of one (a triple of three): its cost is host work and launches, not arithmetic.  Such batches
         # are kept per (source stream, size, method) and RE-PLANNED in place for the next call (sushi_hip_batch_reset: no
         # allocation, one upload) instead of being built and torn down every time.
@@ -377,6 +369,29 @@ class WavStream(object):
         if with_index:
             return score, times, [int(lo) + int(k) for lo, k in zip(win_start, idx)]
         return score, times
+
+    def _requests(self, who, patterns, window_centers, window_sizes, widest=False):
+        """What the batched methods (`who`: the public one's name, for the error) ask of the device for their patterns and
+        windows: (destination DeviceStream, source DeviceStream, offsets, lengths, whether the patterns are views of ONE live
+        stream; per request: start time, first sample of search_source, result length P).  widest: None for a centre or a size
+        (or for the whole list) is the widest window (_widest)."""
+        n = len(patterns)
+        if widest:
+            window_centers = [None] * n if window_centers is None else list(window_centers)
+            window_sizes = [None] * n if window_sizes is None else list(window_sizes)
+        if not (len(window_centers) == len(window_sizes) == n) or n == 0:
+            raise SushiError('%s: need equally many patterns, centres and sizes (>= 1)' % who)
+        dst_dev = self.device_stream()
+        src_dev, offs, lens, one_owner = self._pattern_source(patterns, dst_dev)
+        start_times, win_start, n_pos = [], [], []
+        for m, c, w in zip(lens, window_centers, window_sizes):
+            if widest:
+                c, w = self._widest(c, w)
+            st, lo, p = self._window(m, c, w)
+            start_times.append(st)
+            win_start.append(lo)
+            n_pos.append(p)
+        return dst_dev, src_dev, offs, lens, one_owner, start_times, win_start, n_pos
 
     def _pattern_source(self, patterns, dst_dev):
         """Where a batch's patterns live: (source DeviceStream, offsets, lengths, whether they are views of ONE live stream).
@@ -424,20 +439,8 @@ class WavStream(object):
         find_substreams does).  window_centers / window_sizes: lists (None entries, or None for the list: the widest window)."""
         from .device import SearchBatch
         from .occurrences import peaks
-        n = len(patterns)
-        centres = [None] * n if window_centers is None else list(window_centers)
-        sizes = [None] * n if window_sizes is None else list(window_sizes)
-        if not (len(centres) == len(sizes) == n) or n == 0:
-            raise SushiError('find_occurrences_many: need equally many patterns, centres and sizes (>= 1)')
-        dst_dev = self.device_stream()
-        src_dev, offs, lens, _ = self._pattern_source(patterns, dst_dev)
-        start_times, win_start, n_pos = [], [], []
-        for m, c, w in zip(lens, centres, sizes):
-            c, w = self._widest(c, w)
-            st, lo, p = self._window(m, c, w)
-            start_times.append(st)
-            win_start.append(lo)
-            n_pos.append(p)
+        dst_dev, src_dev, offs, lens, _, start_times, win_start, n_pos = self._requests(
+            'find_occurrences_many', patterns, window_centers, window_sizes, widest=True)
         batch = SearchBatch(dst_dev, src_dev, offs, lens, win_start, n_pos, path="fft", method=method)
         found = batch.occurrences(threshold, capacity)
         out = []
@@ -463,20 +466,8 @@ class WavStream(object):
         """[find_best_matches(p, k, c, w) for p, c, w in zip(...)] in one best-k run (patterns located as find_substreams does).
         window_centers / window_sizes: lists (None entries, or None for the list: the widest window)."""
         from .device import SearchBatch
-        n = len(patterns)
-        centres = [None] * n if window_centers is None else list(window_centers)
-        sizes = [None] * n if window_sizes is None else list(window_sizes)
-        if not (len(centres) == len(sizes) == n) or n == 0:
-            raise SushiError('find_best_matches_many: need equally many patterns, centres and sizes (>= 1)')
-        dst_dev = self.device_stream()
-        src_dev, offs, lens, _ = self._pattern_source(patterns, dst_dev)
-        start_times, win_start, n_pos = [], [], []
-        for m, c, w in zip(lens, centres, sizes):
-            c, w = self._widest(c, w)
-            st, lo, p = self._window(m, c, w)
-            start_times.append(st)
-            win_start.append(lo)
-            n_pos.append(p)
+        dst_dev, src_dev, offs, lens, _, start_times, win_start, n_pos = self._requests(
+            'find_best_matches_many', patterns, window_centers, window_sizes, widest=True)
         batch = SearchBatch(dst_dev, src_dev, offs, lens, win_start, n_pos, path="fft", method=method)
         sep = None if min_separation is None else max(1, int(round(float(min_separation) * self.sample_rate)))
         found = batch.best(k, sep, threshold)
@@ -504,15 +495,7 @@ class WavStream(object):
         as_tensor=True: a list of (1, P) float32 CUDA tensors -- views of one device buffer, no copy to the host."""
         from .curves import match_curves
         n = len(patterns)
-        if not (len(window_centers) == len(window_sizes) == n) or n == 0:
-            raise SushiError('match_templates: need equally many patterns, centres and sizes (>= 1)')
-        dst_dev = self.device_stream()
-        src_dev, offs, lens, _ = self._pattern_source(patterns, dst_dev)
-        win_start, n_pos = [], []
-        for m, c, w in zip(lens, window_centers, window_sizes):
-            _, lo, p = self._window(m, c, w)
-            win_start.append(lo)
-            n_pos.append(p)
+        dst_dev, src_dev, offs, lens, _, _, win_start, n_pos = self._requests('match_templates', patterns, window_centers, window_sizes)
         curves, bounds = match_curves(dst_dev, src_dev, offs, lens, win_start, n_pos, method=method)
         if not as_tensor:
             curves = curves.cpu().numpy()

@@ -1,0 +1,111 @@
+#!/usr/bin/env python3
+"""Which kernels of a translation unit compile to the same gfx950 code in two trees: the evidence a refactor needs before it
+carries profiles/pmc_traffic.json's source digest forward.  Every unit is compiled to device assembly with the flags of
+build.UNITS (`--cuda-device-only -S`; works without a GPU), cut into its functions, and the BODIES are compared -- from a
+function's label to its .Lfunc_end, with the function number of local labels (.LBB12_3) normalised, since a new helper renumbers
+them; data symbols, kernel descriptors and the metadata notes are left out.
+
+usage: kernel_asm_diff.py A B UNIT [UNIT ...] [--show NAME]
+  A, B    a directory that holds sushi_amd/ and include/ (a checkout, an export), or a commit (exported to a scratch copy);
+          `.` is the working tree
+  UNIT    sushi_fft, sushi_curve, ... (build.UNITS)
+  --show NAME   also print a unified diff of the bodies of the functions whose name contains NAME
+prints per function `same`, `differs` (with the bodies' line counts), `only in A`, `only in B`; exit status 1 if anything differs
+example: tools/kernel_asm_diff.py HEAD . sushi_fft sushi_curve"""
+import argparse
+import difflib
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from sushi_amd import build  # noqa: E402
+
+
+def tree_of(spec, scratch):
+    """The directory of a tree: `spec` itself, or an export of the commit `spec`."""
+    if os.path.isdir(os.path.join(spec, "sushi_amd", "csrc")):
+        return os.path.abspath(spec)
+    out = os.path.join(scratch, "tree_" + re.sub(r"\W", "_", spec))
+    os.makedirs(out)
+    tar = subprocess.Popen(["git", "-C", ROOT, "archive", spec, "sushi_amd", "include"], stdout=subprocess.PIPE)
+    subprocess.check_call(["tar", "-x", "-C", out], stdin=tar.stdout)
+    if tar.wait() != 0:
+        raise SystemExit("git archive %s failed" % spec)
+    return out
+
+
+def assembly(tree, unit, out):
+    """Device assembly of one unit of `tree`, by that tree's own build.py (its flags, its generated tables)."""
+    code = ("from sushi_amd import build as b; import subprocess, sys\n"
+            "b.write_twiddles(); b.write_dft16_operands(); b.write_dft16_bound_operands(); b.write_dft16_bound_low_operands()\n"
+            "flags = next(f for n, f, _ in b.UNITS if n == sys.argv[1])\n"
+            "sys.exit(subprocess.call([b._hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fvisibility=hidden',\n"
+            "                          '-Wall'] + flags + ['--cuda-device-only', '-S', b.CSRC + '/' + sys.argv[1] + '.hip', '-o', sys.argv[2]]))\n")
+    subprocess.check_call([sys.executable, "-c", code, unit, out], cwd=tree)
+    return open(out).read()
+
+
+def demangle(names):
+    if not names:
+        return {}
+    out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
+    return {n: re.sub(r"\(anonymous namespace\)::|^void ", "", d).split("(")[0] for n, d in zip(names, out)}
+
+
+def functions(text):
+    """{demangled name: body lines} of every function of an assembly file (kernels and the device functions left out of line)."""
+    lines = text.split("\n")
+    types = set(re.findall(r"^\s*\.type\s+(\S+),@function", text, re.M))
+    names = demangle(sorted(types))
+    out, cur, body = {}, None, []
+    for line in lines:
+        m = re.match(r"^([A-Za-z_$.][\w$.]*):", line)
+        if cur is None:
+            if m and m.group(1) in types:
+                cur, body = m.group(1), []
+            continue
+        if re.match(r"^\.Lfunc_end\d+:", line):
+            out[names[cur]] = body
+            cur = None
+            continue
+        line = re.sub(r"\.L(BB|JTI|tmp|func_begin)\d+(_\d+)?", lambda k: ".L%s#%s" % (k.group(1), k.group(2) or ""), line)
+        line = re.sub(r"\s*;.*$", "", line).rstrip()            # (comments name source lines and basic blocks)
+        if line.strip() and not re.match(r"^\s*\.(loc|file|cfi_\w+|p2align)\b", line):
+            body.append(line)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("a")
+    ap.add_argument("b")
+    ap.add_argument("units", nargs="+")
+    ap.add_argument("--show", action="append", default=[])
+    args = ap.parse_args()
+    differs = 0
+    with tempfile.TemporaryDirectory(prefix="sushi_asm_diff_") as scratch:
+        ta, tb = tree_of(args.a, scratch), tree_of(args.b, scratch)
+        for unit in args.units:
+            fa = functions(assembly(ta, unit, os.path.join(scratch, unit + "_a.s")))
+            fb = functions(assembly(tb, unit, os.path.join(scratch, unit + "_b.s")))
+            print("%s: %d functions in A, %d in B" % (unit, len(fa), len(fb)))
+            for name in sorted(set(fa) | set(fb)):
+                if name not in fb or name not in fa:
+                    verdict = "only in A" if name in fa else "only in B"
+                elif fa[name] == fb[name]:
+                    verdict = "same"
+                else:
+                    verdict = "differs (%d lines against %d)" % (len(fa[name]), len(fb[name]))
+                differs += verdict != "same"
+                print("  %-60s %s" % (name[:60], verdict))
+                if name in fa and name in fb and fa[name] != fb[name] and any(s in name for s in args.show):
+                    print("\n".join(difflib.unified_diff(fa[name], fb[name], "A", "B", lineterm="", n=2)))
+    return 1 if differs else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
