@@ -153,6 +153,7 @@ struct SushiHipBatch {
     unsigned run_seq = 0;               // runs so far: rotates which excluded pairs are audited
     int audit_every = 2;                // one search in this many has one excluded pair transformed as a check, per run
     int bound_model = SUSHI_HIP_BOUND_WORST_CASE;   // (default) / SUSHI_HIP_BOUND_STATISTICAL: how the excluded side's roundings enter slb
+    BoundFault fault;                   // the tests' seam (SUSHI_HIP_TEST_BOUND_FAULT; period 0, the default: none)
     int last_band = -1;                 // form of the exclusion the last run used (its last sub-batch that went through it; -1: none did)
     bool last_whole_cut = false;        // the last run took the plan's one-sub-batch cut (Plan::subs_whole)
     bool last_threshold = false;        // the last run was a threshold run (sushi_hip_batch_run_threshold) or a best-K run (sushi_hip_batch_run_best)
@@ -385,6 +386,36 @@ static int launch_slb(const RunCtx& c, const SubView& v, const BoundArgs& x, hip
         hipLaunchKernelGGL(slb_kernel<decltype(m)::value>, dim3((unsigned)((v.sb.pairs + 3) / 4)), dim3(256), 0, st, x); });
 }
 
+// SUSHI_HIP_TEST_BOUND_FAULT=<period>:<phase>[:<pair>] -- decimal digits only, period >= 1, 0 <= phase < period, pair >= 0, nothing
+// behind the last field; false: malformed
+static bool parse_bound_fault(const char* s, BoundFault* out) {
+    long field[3] = {0, 0, -1};
+    int n = 0;
+    for (;;) {
+        if (n == 3 || *s < '0' || *s > '9') return false;
+        char* end = nullptr;
+        field[n] = strtol(s, &end, 10);
+        if (field[n] > INT_MAX) return false;                     // (no sign was read: never negative; LONG_MAX on overflow)
+        ++n;
+        if (!*end) break;
+        if (*end != ':') return false;
+        s = end + 1;
+    }
+    if (n < 2 || field[0] < 1 || field[1] >= field[0]) return false;
+    out->period = (int)field[0]; out->phase = (int)field[1]; out->pair = n == 3 ? (int)field[2] : -1;
+    return true;
+}
+
+// the tests' seam: the stored bounds of the batch's faulted pairs read +inf from here on (bound_fault_kernel); called behind every
+// launch that writes slb, and only by a batch that carries a fault
+static int launch_bound_fault(const RunCtx& c, const SubView& v, hipStream_t st) {
+    BoundFaultArgs fa;
+    fa.searches = c.searches + v.sb.a0; fa.pairmap = v.pairmap; fa.slb = v.slb; fa.first_search = v.sb.a0;
+    fa.sub_first_pair = v.sb.first_pair; fa.n_pairs = (int)v.sb.pairs; fa.f = c.b->fault;
+    hipLaunchKernelGGL(bound_fault_kernel, dim3((unsigned)((v.sb.pairs + 255) / 256)), dim3(256), 0, st, fa);
+    return launch_ok();
+}
+
 // Which form of the exclusion: the band-split form multiplies, stores and transforms only the low band of
 // every spectrum and bounds the rest by the rows' norms -- a quarter of the bytes and a third of the instructions, IF the
 // streams keep most of their energy in the band (audio does; white noise does not).  Decided once per batch and method, on
@@ -487,6 +518,7 @@ static int bound_pairs(const RunCtx& c, const SubView& v, hipStream_t st, const 
     };
     if (ba.worst_case) go(std::false_type()); else go(std::true_type());
     if (launch_ok() != SUSHI_HIP_OK || launch_slb(c, v, ba, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    if (c.b->fault.period > 0) return launch_bound_fault(c, v, st);
     return SUSHI_HIP_OK;
 }
 
@@ -500,6 +532,8 @@ static int second_look(const RunCtx& c, const SubView& v, hipStream_t st, BoundA
     if (launch_method(c.method, [&](auto m) { hipLaunchKernelGGL(slb_list_kernel<decltype(m)::value>, dim3(256 * 2), dim3(256), 0, st, ba); }) !=
         SUSHI_HIP_OK)
         return SUSHI_HIP_ELAUNCH;
+    // (slb_list_kernel has just redone the listed pairs' bounds: a faulted audit pair's would be sound again, and the audit blind)
+    if (c.b->fault.period > 0 && launch_bound_fault(c, v, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     hipLaunchKernelGGL(survivor2_kernel, dim3(256), dim3(256), 0, st, ba);
     return launch_ok();
 }
@@ -959,6 +993,9 @@ int sushi_hip_batch_create(const SushiHipStream* dst, const SushiHipStream* src,
     if (e && *e) { const int v = atoi(e); b->audit_every = v < 0 ? 0 : v; }
     const char* m = getenv("SUSHI_HIP_BOUND_MODEL");
     if (m && !strcmp(m, "statistical")) b->bound_model = SUSHI_HIP_BOUND_STATISTICAL;
+    // (the tests' seam, DESIGN.md 3.2: a value that does not parse is refused -- a typo must not turn a fault test into a no-fault test)
+    const char* f = getenv("SUSHI_HIP_TEST_BOUND_FAULT");
+    if (f && *f && !parse_bound_fault(f, &b->fault)) return SUSHI_HIP_EINVAL;
     const int rc = plan_and_upload(b, req_host, n, (hipStream_t)hip_stream);
     if (rc != SUSHI_HIP_OK) return rc;
     *out = guard.release();

@@ -404,6 +404,30 @@ void slb_list_kernel(BoundArgs a) {
         slb_one<METHOD>(a, __builtin_amdgcn_readfirstlane(a.list[slot]), threadIdx.x & 63);
 }
 
+// THE TESTS' SEAM (SUSHI_HIP_TEST_BOUND_FAULT=<period>:<phase>[:<pair>], DESIGN.md 3.2; sushi_hip_batch_create parses it): the
+// bounds of chosen pairs made WRONG on purpose, so that the suite can see the audit catch a wrong bound and every run kind
+// recover from it.  The stored bound of every pair (`pair` < 0) or of the pair with index `pair` inside its search, of every
+// search whose batch-wide index g has g % period == phase, becomes +inf: "no score of this pair can be any good".  A kernel
+// of its own, launched behind slb_kernel and slb_list_kernel only by a batch that carries a fault (period > 0): without the
+// variable no launch, no argument and no kernel differs.
+struct BoundFault { int period = 0, phase = 0, pair = -1; };
+struct BoundFaultArgs {
+    const SearchDesc* searches;       // the sub-batch's searches
+    const int* pairmap;
+    float* slb;
+    int first_search, sub_first_pair, n_pairs;
+    BoundFault f;
+};
+__global__ __launch_bounds__(256)
+void bound_fault_kernel(BoundFaultArgs a) {
+    const int pr = blockIdx.x * 256 + threadIdx.x;
+    if (pr >= a.n_pairs) return;
+    const int k = a.pairmap[pr];
+    if ((unsigned)(a.first_search + k) % (unsigned)a.f.period != (unsigned)a.f.phase) return;
+    if (a.f.pair >= 0 && a.sub_first_pair + pr - a.searches[k].first_pair != a.f.pair) return;
+    a.slb[pr] = __builtin_inff();
+}
+
 // per search: the pair with the smallest lower bound (the first of them) is transformed first
 __global__ __launch_bounds__(64)
 void pilot_kernel(BoundArgs a) {
