@@ -1,7 +1,9 @@
 """Build libsushi_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
-The translation units, compiled separately (the MFMA kernel alone takes ~2 min) and linked:
-  csrc/sushi_hip.hip  direct MFMA kernel, stream preparation, exact refinement   (-ffp-contract=off)
+The translation units, compiled separately (the direct MFMA kernel alone takes ~3 min, the FFT unit ~35 s, the others seconds) and linked:
+  csrc/sushi_direct.hip direct path: the MFMA kernel and its launcher   (-ffp-contract=off)
+  csrc/sushi_exact.hip  FFT path's exact stages (refinement, tiles), unpack and fill kernels   (-ffp-contract=off)
+  csrc/sushi_stream.hip stream preparation (prefix sums) and the stream C ABI   (-ffp-contract=off)
   csrc/sushi_fft.hip  overlap-save FFT path
   csrc/sushi_load.hip WavStream load pipeline (decimate / pad / median clip / scale / quantise)  (-ffp-contract=off)
   csrc/sushi_curve.hip whole score curves: i8 MFMA Toeplitz GEMM (uint8), canonical float64 chain (float32)  (-ffp-contract=off);
@@ -21,12 +23,14 @@ LIB = os.path.join(LIB_DIR, "libsushi_hip.so")
 TWIDDLE_INC = os.path.join(CSRC, "_gen_twiddle16384.inc")
 
 COMMON_DEPS = [HEADER, os.path.join(CSRC, "sushi_common.hpp"), os.path.join(CSRC, "sushi_internal.hpp")]
-# -ffp-contract=off for sushi_hip.hip: its float64 epilogue restates cv2's operation order; a fused
-# a*b-c*d would round differently from the reference (the hot loop is MFMA builtins, unaffected).
+# -ffp-contract=off for the three units cut from one (direct, exact, stream): their float64 epilogues and prefix sums restate
+# cv2's operation order; a fused a*b-c*d would round differently from the reference (the hot loop is MFMA builtins, unaffected).
 UNITS = [
-    ("sushi_hip", ["-ffp-contract=off"], []),
+    ("sushi_direct", ["-ffp-contract=off"], []),
+    ("sushi_exact", ["-ffp-contract=off"], []),
+    ("sushi_stream", ["-ffp-contract=off"], []),
     ("sushi_load", ["-ffp-contract=off"], []),      # NumPy's float32 operation order, no fused multiply-add
-    ("sushi_curve", ["-ffp-contract=off"], [os.path.join(CSRC, "curve_tiles.hpp")]),     # the epilogue restates cv2's operation order (as sushi_hip.hip's)
+    ("sushi_curve", ["-ffp-contract=off"], [os.path.join(CSRC, "curve_tiles.hpp")]),     # the epilogue restates cv2's operation order (as sushi_direct.hip's)
     # -fno-slp-vectorize: the SLP pass packs the complex MACs into v_pk_fma_f32 and pays for it in
     # register shuffles (v_mov / accvgpr traffic); plain v_fma_f32 already issues at the f32 peak rate.
     ("sushi_fft", ["-fno-slp-vectorize"],

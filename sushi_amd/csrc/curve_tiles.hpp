@@ -155,11 +155,11 @@ __device__ __forceinline__ void u8_tile(const TileSrc& a, const TileReq& d, int6
 // ------------------------------------------------------------------------------------------------------------------------
 // float32: the canonical chain.  sum T*I over the samples as they are, in float64, XM pattern samples at a time: each chunk
 // summed sequentially from its first sample, one fused multiply-add per sample, the chunk sums added in chunk order (the order
-// sushi_hip.hip's exact stages keep).  A tile is 256 NPOS consecutive positions; a thread owns NPOS consecutive ones,
+// sushi_exact.hip's exact stages keep).  A tile is 256 NPOS consecutive positions; a thread owns NPOS consecutive ones,
 // which share its loads: at every sample the NPOS window values it needs are the previous sample's shifted by one.  XG chunks
 // of the pattern and the window samples under them are staged in LDS as float64 at a time.
 // ------------------------------------------------------------------------------------------------------------------------
-constexpr int XM = 512;           // pattern samples per chunk of the canonical sum (sushi_hip.hip XM)
+constexpr int XM = 512;           // pattern samples per chunk of the canonical sum (sushi_exact.hip XM)
 constexpr int XG = 4;             // chunks staged together
 template <int NPOS> constexpr int f32_li_doubles() { return 256 * NPOS + XG * XM + (256 * NPOS + XG * XM) / 32 + 1; }
 

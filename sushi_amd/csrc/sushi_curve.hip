@@ -2,7 +2,7 @@
 // only its arg-min.  Every position of a curve is computed; none can be excluded, so the work is O(P M) and runs on the
 // pipe that suits the sample type:
 //   * uint8 streams: the centred cross term as an exact integer GEMM with one Toeplitz operand on v_mfma_i32_32x32x32_i8;
-//   * float32 streams: the canonical float64 chain of the exact stages (sushi_hip.hip refine_kernel / exact_tiles_kernel)
+//   * float32 streams: the canonical float64 chain of the exact stages (sushi_exact.hip refine_kernel / exact_tiles_kernel)
 //     on the VALU.
 // Either way each value is bit for bit what the exact stages produce for that position.  The tile bodies
 // (curve_tiles.hpp) also evaluate the listed block pairs of a threshold run (sushi_hip_batch_run_threshold):
@@ -44,8 +44,7 @@ static_assert(sizeof(CurveDesc) == 40, "CurveDesc layout");
 
 // workspace: [queue head (u64) | padding to 256 B][CurveDesc x n], uploaded in one copy
 constexpr size_t CURVE_HEAD = 256;
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-size_t curve_layout_bytes(int n) { return n <= 0 ? 0 : CURVE_HEAD + align256((size_t)n * sizeof(CurveDesc)); }
+size_t curve_layout_bytes(int n) { return n <= 0 ? 0 : CURVE_HEAD + align_up((size_t)n * sizeof(CurveDesc), 256); }
 
 struct CurveArgs {
     TileSrc src;                      // streams, method
@@ -140,7 +139,7 @@ __device__ __forceinline__ ListedTile listed_tile(const ListedPairs& a, const in
     x.k = a.pairmap[x.pr];
     const SearchDesc sd = a.searches[x.k];
     const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
-    const int64_t pairI = lay.pair0 + (a.sub_first_pair + x.pr - sd.first_pair);
+    const int64_t pairI = absolute_pair(lay, a.sub_first_pair, x.pr, sd);
     x.p0 = pairI * FFT_STEP * (int64_t)FFT_SEG + (int64_t)x.t * TILE - sd.win_start;
     x.rq = tile_req(sd);
     x.row = a.rows + (size_t)x.pr * THR_SLOT_WORDS;
@@ -317,7 +316,7 @@ void best_select_kernel(BestParams a) {
     const int64_t S = a.min_separation > 0 ? a.min_separation : sd.tmpl_len;
     const int K = a.k;
     SushiHipHit* __restrict__ out = a.hits + (size_t)gk * (size_t)K;
-    auto evaluated = [&](const int i) { return !a.audit_mark || (a.audit_mark[pr0 + i] & 2) != 0; };
+    auto evaluated = [&](const int i) { return !a.audit_mark || (a.audit_mark[pr0 + i] & MARK_LISTED) != 0; };
     auto keys_of = [&](const int i, const int what) {
         return reinterpret_cast<unsigned long long*>(a.lp.rows + (size_t)(pr0 + i) * THR_SLOT_WORDS + what);
     };
@@ -400,8 +399,6 @@ void best_select_kernel(BestParams a) {
         a.gkeys[gk] = key;
     }
 }
-
-int launch_ok() { return hipGetLastError() == hipSuccess ? SUSHI_HIP_OK : SUSHI_HIP_ELAUNCH; }
 
 // a kernel of 256 threads in its uint8 or its float32 form, by the streams' sample type
 template <class Params>

@@ -1,35 +1,15 @@
-// sushi_amd/csrc/sushi_hip.hip -- gfx950 (MI355X, CDNA4) kernels + C ABI for Sushi's audio template match.
+// sushi_amd/csrc/sushi_exact.hip -- gfx950 (MI355X, CDNA4): the exact stages of the FFT path and a run's utility kernels.
 //
-// Replaces, for a whole batch of (pattern, window) pairs, what the reference does per call in
-//   wav.py:185  result = cv2.matchTemplate(search_source, pattern, cv2.TM_SQDIFF_NORMED)
-//   wav.py:186  min_idx = result.argmin(axis=1)[0]
-// i.e. R[p] = sum_m (T[m]-I[p+m])^2 / sqrt(sum T^2 * sum_m I[p+m]^2) with OpenCV's clamp, then first argmin.
-//
-// Formulation (DESIGN.md "Kernel K1"):
-//   * streams are stored centred (xc = x - c, c = 0.5 | 128) so the cross term is small and the
-//     sum-of-squares identity  sum (T-I)^2 = sum T'^2 - 2 sum T'I' + sum I'^2  loses nothing;
-//     sum T'^2, sum I'^2, sum T', sum I' come from float64 prefix arrays built once per stream.
-//   * the sliding dot product corr[p] = sum_m T'[m] I'[p+m] is computed as a GEMM with one
-//     Toeplitz operand, on the exact-f32 matrix pipe (v_mfma_f32_32x32x2_f32):
-//         p = base + 32 i + j ,   D[i][j] += sum_n A[i][n] B[n][j]
-//         A[i][n] = T'[n - 32 i]  (zero outside [0,M))      B[n][j] = I'[base + j + n]
-//     One MFMA tile therefore owns 1024 consecutive positions.  A is read from an LDS copy of
-//     the template chunk laid out with a +1 skew every 32 floats (lane stride 33 -> no bank
-//     conflict), B from a plain contiguous LDS copy of the search tile (lane stride 1).
-//   * f32 accumulation is restarted every FLUSH template samples and folded into float64
-//     accumulators, so the error of the f32 chains stays below cv2's own float32 quantum of corr.
-//   * epilogue: OpenCV common_matchTemplate() in float64, result rounded to float32, packed with
-//     the position into a 64-bit key; wave shuffles + LDS + one atomicMin per workgroup give the
-//     first-index argmin (NumPy argmin semantics).
-//
-// gfx950 only: wave64, 4 SIMDs/CU, 160 KiB LDS/CU.  No CUDA compatibility paths.
+// FFT path, exact stages.  One accumulation order everywhere (refine_kernel, both modes of exact_tiles_kernel):
+// sum T*I over the samples as they are, in float64 (every product of two float32 or uint8 values is exact there),
+// XM pattern samples at a time -- each chunk summed sequentially from 0 with one fused multiply-add per sample,
+// the chunk sums added in order.  The value of a position therefore does not depend on which kernel, which tile
+// or which window evaluated it.
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <stdint.h>
 #include <float.h>
-
-#include <new>
 
 #include "../../include/sushi_hip.h"
 #include "sushi_common.hpp"
@@ -39,206 +19,6 @@ namespace {
 
 using namespace sushi;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int KC = 512;          // template samples per LDS chunk
-constexpr int FLUSH = 128;       // length of one f32 accumulation chain before it is folded into float64
-constexpr int ROWSPAN = 32 * 31; // 992: largest row shift 32*i of the Toeplitz operand
-constexpr int TLEN = KC + ROWSPAN;              // template samples staged per chunk
-constexpr int TLDS = TLEN + TLEN / 32 + 1;      // with the +1-per-32 skew
-
-struct MatchArgs {
-    const float* dst_xc;
-    const double* dst_s1;
-    const double* dst_s2;
-    int64_t dst_len;
-    const float* src_xc;
-    const double* src_s1;
-    const double* src_s2;
-    int64_t src_len;
-    double centre;
-    const SearchDesc* searches;
-    int n_search;
-    int n_tiles;
-    int method;                   // SUSHI_HIP_METHOD_*
-    unsigned long long* keys;
-};
-
-template <int WAVES, int NB> struct TileShape {
-    static constexpr int NT = WAVES * 64;
-    static constexpr int TP = WAVES * NB * 1024;        // positions per workgroup
-    static constexpr int ILEN = TP + KC - 984;          // search samples staged per chunk: TP-1024+32 columns + KC rows + align slack, multiple of 4
-    static constexpr int LDS_FLOATS = ILEN + TLDS;
-};
-
-// One tile (TP consecutive result positions) of one search.  `lds` holds LDS_FLOATS floats, `red` WAVES keys.
-template <int WAVES, int NB>
-__device__ __forceinline__ void match_tile(const MatchArgs& a, const int s_idx, const SearchDesc sd,
-                                           const int tile_in_search, float* lds, unsigned long long* red) {
-    constexpr int NT = TileShape<WAVES, NB>::NT;
-    constexpr int TP = TileShape<WAVES, NB>::TP;
-    constexpr int ILEN = TileShape<WAVES, NB>::ILEN;
-    float* I_lds = lds;
-    float* T_lds = lds + ILEN;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int i = lane & 31;                     // MFMA row (A) / column (B) index of this lane
-    const int h = lane >> 5;                     // MFMA k index of this lane
-
-    const int M = sd.tmpl_len;
-    const int P = sd.n_pos;
-    const int p0 = tile_in_search * TP;          // first position of this workgroup
-    const int wb = wave * (NB * 1024);           // first position of this wave inside the tile
-    const bool wave_active = (p0 + wb) < P;
-
-    const float* __restrict__ src = a.src_xc + sd.tmpl_off;
-    const int64_t gwin = sd.win_start + p0;      // dst sample under position p0, template sample 0
-
-    f32x16 acc[NB];
-    double acc2[NB][16];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { acc[b][r] = 0.f; acc2[b][r] = 0.0; }
-    }
-
-    const int nchunks = (M + ROWSPAN + KC - 1) / KC;
-    for (int c = 0; c < nchunks; ++c) {
-        const int n1 = c * KC;
-        // ---- stage the search tile: dst[gwin + n1 .. + TP + KC) as aligned float4 ---------
-        const int64_t g = gwin + n1;
-        const int64_t gA = g & ~(int64_t)3;
-        const int ioff = (int)(g - gA);
-        __syncthreads();                          // previous chunk's LDS reads are done
-        for (int v = tid; v < ILEN / 4; v += NT) {
-            const int64_t e = gA + 4 * (int64_t)v;
-            float4 val;
-            if (e + 3 < a.dst_len) {
-                val = *reinterpret_cast<const float4*>(a.dst_xc + e);
-            } else {
-                val.x = (e + 0 < a.dst_len) ? a.dst_xc[e + 0] : 0.f;
-                val.y = (e + 1 < a.dst_len) ? a.dst_xc[e + 1] : 0.f;
-                val.z = (e + 2 < a.dst_len) ? a.dst_xc[e + 2] : 0.f;
-                val.w = 0.f;
-            }
-            *reinterpret_cast<float4*>(I_lds + 4 * v) = val;
-        }
-        // ---- stage the template chunk T'[n1-992 .. n1+KC), zero outside [0,M), skewed ------
-        for (int y = tid; y < TLEN; y += NT) {
-            const int x = n1 - ROWSPAN + y;
-            const float v = (x >= 0 && x < M) ? src[x] : 0.f;
-            T_lds[y + (y >> 5)] = v;
-        }
-        __syncthreads();
-
-        if (wave_active) {
-            const float* tp = T_lds + (h + 33 * (31 - i));
-            const float* ip = I_lds + (ioff + wb + i + h);
-            for (int nf = 0; nf < KC; nf += FLUSH) {
-                // FLUSH/4 groups of two k-steps (= 4 template samples, 2*NB MFMAs).  The operands of
-                // group g+1 are read from LDS before the MFMAs of group g are issued (register
-                // double buffer); sched_group_barrier pins that order so the matrix pipe never waits
-                // on an LDS round trip.
-                const float* tq = tp + nf + (nf >> 5);
-                const float* iq = ip + nf;
-                float a_cur[2], b_cur[NB][2], a_nxt[2], b_nxt[NB][2];
-                a_cur[0] = tq[0]; a_cur[1] = tq[2];
-#pragma unroll
-                for (int b = 0; b < NB; ++b) { b_cur[b][0] = iq[1024 * b]; b_cur[b][1] = iq[1024 * b + 2]; }
-#pragma unroll
-                for (int g = 0; g < FLUSH / 4; ++g) {
-                    if (g + 1 < FLUSH / 4) {
-                        const int n = 4 * (g + 1);                   // offset inside the flush block
-                        const int tn = n + (n >> 5);                 // skewed template offset (nf % 32 == 0)
-                        a_nxt[0] = tq[tn]; a_nxt[1] = tq[tn + 2];
-#pragma unroll
-                        for (int b = 0; b < NB; ++b) {
-                            b_nxt[b][0] = iq[n + 1024 * b]; b_nxt[b][1] = iq[n + 1024 * b + 2];
-                        }
-                        __builtin_amdgcn_sched_group_barrier(0x100, NB + 1, 0);   // DS reads of group g+1
-                    }
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-#pragma unroll
-                        for (int b = 0; b < NB; ++b)
-                            acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur[k], b_cur[b][k], acc[b], 0, 0, 0);
-                    }
-                    __builtin_amdgcn_sched_group_barrier(0x8, 2 * NB, 0);         // MFMAs of group g
-                    if (g + 1 < FLUSH / 4) {
-                        a_cur[0] = a_nxt[0]; a_cur[1] = a_nxt[1];
-#pragma unroll
-                        for (int b = 0; b < NB; ++b) { b_cur[b][0] = b_nxt[b][0]; b_cur[b][1] = b_nxt[b][1]; }
-                    }
-                }
-                // fold the f32 chain (FLUSH products long) into the float64 accumulators
-#pragma unroll
-                for (int b = 0; b < NB; ++b) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) { acc2[b][r] += (double)acc[b][r]; acc[b][r] = 0.f; }
-                }
-            }
-        }
-    }
-
-    // ---- epilogue: normalise, pack (score, position), arg-min ------------------------------
-    unsigned long long best = ~0ull;
-    if (wave_active) {
-        const TemplStats ts = templ_stats(a.src_s1, a.src_s2, sd.tmpl_off, M, a.centre);
-        const double* __restrict__ w1 = a.dst_s1 + sd.win_start;
-        const double* __restrict__ w2 = a.dst_s2 + sd.win_start;
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                // C/D layout of 32x32 MFMA: col = lane & 31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-                const int p = p0 + wb + 1024 * b + 32 * row + i;
-                if (p < P) {
-                    const unsigned long long key = a.method == SUSHI_HIP_METHOD_CCOEFF_NORMED
-                        ? make_key_max(score_ccoeff_at(acc2[b][r], ts, a.centre, w1, w2, p, M), (unsigned)p)
-                        : make_key(score_at(acc2[b][r], ts, a.centre, w1, w2, p, M), (unsigned)p);
-                    best = key < best ? key : best;
-                }
-            }
-        }
-    }
-    best = wave_min_u64(best);
-    if (lane == 0) red[wave] = best;
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long m = red[0];
-#pragma unroll
-        for (int w = 1; w < WAVES; ++w) m = red[w] < m ? red[w] : m;
-        if (m != NO_KEY) atomicMin(a.keys + s_idx, m);
-    }
-}
-
-
-template <int WAVES, int NB>
-__global__ __launch_bounds__(WAVES * 64, 2)
-void match_sqdiff_f32_kernel(MatchArgs a) {
-    __shared__ __attribute__((aligned(16))) float lds[TileShape<WAVES, NB>::LDS_FLOATS];
-    __shared__ unsigned long long red[WAVES];
-    // ---- which search / which tile ------------------------------------------------------
-    const int tile = xcd_remap(blockIdx.x, a.n_tiles);
-    int lo = 0, hi = a.n_search - 1;             // last search with first_tile <= tile
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (a.searches[mid].first_tile <= tile) lo = mid; else hi = mid - 1;
-    }
-    const SearchDesc sd = a.searches[lo];
-    match_tile<WAVES, NB>(a, lo, sd, tile - sd.first_tile, lds, red);
-}
-
-// ------------------------------------------------------------------------------------------
-// FFT path, exact stages.  One accumulation order everywhere (refine_kernel, both modes of exact_tiles_kernel):
-// sum T*I over the samples as they are, in float64 (every product of two float32 or uint8 values is exact there),
-// XM pattern samples at a time -- each chunk summed sequentially from 0 with one fused multiply-add per sample,
-// the chunk sums added in order.  The value of a position therefore does not depend on which kernel, which tile
-// or which window evaluated it.
-// ------------------------------------------------------------------------------------------
 constexpr int XT = TILE;         // positions per tile
 constexpr int XM = 512;          // pattern samples per chunk of the canonical sum
 static_assert(XT == 1024 && XM % 4 == 0, "exact_tiles_kernel: 256 threads x 4 consecutive positions, steps of 4 samples");
@@ -733,8 +513,8 @@ void refine_kernel(RefineParams a) {
     __syncthreads();
     // none: TM_CCOEFF_NORMED with every window uncertain -- then every listed position is a candidate
     const float U = a.gkeys[s_idx] == NO_KEY ? 4.0f : key_score(a.gkeys[s_idx]);
-    const unsigned long long* __restrict__ rows = a.cand + (size_t)(sd.first_pair - a.sub_first_pair) * FFT_ROW;
-    const float* __restrict__ plb = a.pair_lb + (sd.first_pair - a.sub_first_pair);
+    const unsigned long long* __restrict__ rows = a.cand + (size_t)first_pair_in_sub(a.sub_first_pair, sd) * FFT_ROW;
+    const float* __restrict__ plb = a.pair_lb + first_pair_in_sub(a.sub_first_pair, sd);
     for (int i = tid; i < lay.n_pairs; i += REFINE_THREADS) {
         // (a transformed pair left its error bound: noted here, by every thread for its own pairs, for the audit's choice below --
         // one thread walking the rows one dependent load at a time was a seventh of this kernel)
@@ -824,7 +604,7 @@ void refine_kernel(RefineParams a) {
         // this search goes to the collection pass: list its pairs that can hold a candidate (every pair when every position is
         // to be evaluated) -- what collect_kernel's workgroups stride over
         for (int i = tid; i < lay.n_pairs; i += REFINE_THREADS)
-            if (violated || plb[i] <= U) a.citems[atomicAdd(a.n_citems, 1)] = (sd.first_pair - a.sub_first_pair) + i;
+            if (violated || plb[i] <= U) a.citems[atomicAdd(a.n_citems, 1)] = first_pair_in_sub(a.sub_first_pair, sd) + i;
     }
     if (tid == 0) {
         // the run's maxima: one global atomic per search only where it raises the value -- every workgroup hitting the same two
@@ -855,263 +635,15 @@ void refine_kernel(RefineParams a) {
     }
 }
 
-// ------------------------------------------------------------------------------------------
-// Stream preparation: centred float32 copy + float64 exclusive prefix sums of xc and xc^2.
-// Three passes over blocks of PB samples (block totals -> scan of totals -> in-block scan).
-// ------------------------------------------------------------------------------------------
-constexpr int PB_THREADS = 256;
-constexpr int PB_PER_THREAD = 16;
-constexpr int PB = PB_THREADS * PB_PER_THREAD;   // 4096 samples per block
-static_assert(PB == FFT_HOP, "the relative prefix sums are per FFT block");
-
-template <typename T> __device__ __forceinline__ float centred(T x);
-template <> __device__ __forceinline__ float centred<float>(float x) { return x - 0.5f; }
-template <> __device__ __forceinline__ float centred<uint8_t>(uint8_t x) { return (float)((int)x - 128); }
-
-template <typename T>
-__global__ __launch_bounds__(PB_THREADS)
-void centre_blocksum_kernel(const T* __restrict__ raw, int64_t n, float* __restrict__ xc,
-                            double* __restrict__ bs1, double* __restrict__ bs2) {
-    __shared__ double r1[PB_THREADS / 64], r2[PB_THREADS / 64];
-    const int64_t base = (int64_t)blockIdx.x * PB;
-    double s1 = 0.0, s2 = 0.0;
-#pragma unroll 4
-    for (int k = 0; k < PB_PER_THREAD; ++k) {
-        const int64_t e = base + (int64_t)k * PB_THREADS + threadIdx.x;   // coalesced
-        if (e < n) {
-            const T x = raw[e];
-            const double u = (double)x;                                   // the sample as it is
-            xc[e] = centred<T>(x);                                        // what the direct kernel multiplies
-            s1 += u;
-            s2 += u * u;
-        }
-    }
-    s1 = wave_sum(s1);
-    s2 = wave_sum(s2);
-    if ((threadIdx.x & 63) == 0) { r1[threadIdx.x >> 6] = s1; r2[threadIdx.x >> 6] = s2; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t1 = 0.0, t2 = 0.0;
-        for (int w = 0; w < PB_THREADS / 64; ++w) { t1 += r1[w]; t2 += r2[w]; }
-        bs1[blockIdx.x] = t1;
-        bs2[blockIdx.x] = t2;
-    }
-}
-
-// single workgroup: in-place exclusive scan of the per-block totals of NA arrays; entry [nb] of each
-// receives the grand total, so that bs[b] = prefix sum at sample min(b * PB, n) for b = 0 .. nb
-template <int NA>
-__global__ __launch_bounds__(1024)
-void scan_blocksums_kernel(double* __restrict__ bs, int stride, int nb) {
-    __shared__ double wt[NA][16];
-    __shared__ double carry[NA];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (tid < NA) carry[tid] = 0.0;
-    __syncthreads();
-    for (int base = 0; base < nb; base += 1024) {
-        const int k = base + tid;
-        double v[NA], e[NA], o[NA];
-#pragma unroll
-        for (int a = 0; a < NA; ++a) {
-            v[a] = k < nb ? bs[a * stride + k] : 0.0;
-            double t;
-            e[a] = wave_excl_scan(v[a], &t);
-            if (lane == 0) wt[a][wv] = t;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int a = 0; a < NA; ++a) {
-            o[a] = carry[a];
-            for (int w = 0; w < wv; ++w) o[a] += wt[a][w];
-            if (k < nb) bs[a * stride + k] = o[a] + e[a];
-        }
-        __syncthreads();
-        if (tid == 1023) {
-#pragma unroll
-            for (int a = 0; a < NA; ++a) carry[a] = o[a] + e[a] + v[a];
-        }
-        __syncthreads();
-    }
-    if (tid < NA) bs[tid * stride + nb] = carry[tid];
-}
-
-// prefix sums s1 = sum x, s2 = sum x^2 of the samples as they are (float64, absolute: exact for uint8) and,
-// for the FFT path's scoring, s2 again as float32 relative to the base of the sample's PB-block:
-//     s2[e] = base2[e / PB] + urel[e]          (e = 0 .. n)
-template <typename T>
-__global__ __launch_bounds__(PB_THREADS)
-void final_scan_kernel(const T* __restrict__ raw, int64_t n, const double* __restrict__ bs1,
-                       const double* __restrict__ bs2, double* __restrict__ s1, double* __restrict__ s2,
-                       float* __restrict__ urel, float* __restrict__ usrel) {
-    // A thread scans PB_PER_THREAD consecutive samples, but global memory is touched a workgroup-wide row at a
-    // time: samples come in and prefix values go out through a padded LDS tile (index + index / 16: the
-    // 16-element runs of neighbouring threads start in different banks).
-    __shared__ double tile[PB + PB / PB_PER_THREAD];
-    __shared__ double w1[PB_THREADS / 64], w2[PB_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int64_t blk = (int64_t)blockIdx.x * PB;
-    auto pad = [](const int i) { return i + i / PB_PER_THREAD; };
-#pragma unroll
-    for (int k = 0; k < PB_PER_THREAD; ++k) {
-        const int i = k * PB_THREADS + tid;                              // coalesced
-        const int64_t e = blk + i;
-        tile[pad(i)] = e < n ? (double)raw[e] : 0.0;
-    }
-    __syncthreads();
-    double v[PB_PER_THREAD];
-    double l1 = 0.0, l2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < PB_PER_THREAD; ++k) {
-        v[k] = tile[pad(tid * PB_PER_THREAD + k)];
-        l1 += v[k];
-        l2 += v[k] * v[k];
-    }
-    double t1, t2;
-    double e1 = wave_excl_scan(l1, &t1);
-    double e2 = wave_excl_scan(l2, &t2);
-    if (lane == 0) { w1[wv] = t1; w2[wv] = t2; }
-    __syncthreads();                                                     // also: everyone has read its samples
-    for (int w = 0; w < wv; ++w) { e1 += w1[w]; e2 += w2[w]; }           // prefix inside the block, before the thread's run
-    const double o1 = bs1[blockIdx.x], o2 = bs2[blockIdx.x];             // block bases
-    if (blockIdx.x == 0 && tid == 0) {
-        s1[0] = 0.0; s2[0] = 0.0;
-        if (n % PB == 0) { urel[n] = 0.f; usrel[2 * n] = 0.f; usrel[2 * n + 1] = 0.f; }   // sample n opens a block of its own: base[n / PB] = total
-    }
-    // s1[e + 1], s2[e + 1] (inclusive sums) and urel[e] (exclusive, relative to the block), one array at a time
-    {
-        double r = e1;
-#pragma unroll
-        for (int k = 0; k < PB_PER_THREAD; ++k) { r += v[k]; tile[pad(tid * PB_PER_THREAD + k)] = o1 + r; }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < PB_PER_THREAD; ++k) {
-        const int i = k * PB_THREADS + tid;
-        if (blk + i < n) s1[blk + i + 1] = tile[pad(i)];
-    }
-    __syncthreads();
-    {
-        double r = e2;
-#pragma unroll
-        for (int k = 0; k < PB_PER_THREAD; ++k) { r += v[k] * v[k]; tile[pad(tid * PB_PER_THREAD + k)] = o2 + r; }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < PB_PER_THREAD; ++k) {
-        const int i = k * PB_THREADS + tid;
-        if (blk + i < n) s2[blk + i + 1] = tile[pad(i)];
-    }
-    __syncthreads();
-    // urel[e] (exclusive, relative to the block) and the same for the sum of the samples (TM_CCOEFF_NORMED's window means:
-    // s1[e] = base1[e / PB] + srel[e]); the pair goes out twice: urel alone (TM_SQDIFF_NORMED reads nothing else) and
-    // interleaved as usrel[e] = (urel[e], srel[e]), so that TM_CCOEFF_NORMED's scoring takes both with ONE 8-byte load per
-    // window end instead of two 4-byte ones
-    struct f2 { float u, s; };
-    f2* __restrict__ ftile = reinterpret_cast<f2*>(tile);
-    {
-        double r2 = e2, r1 = e1;
-#pragma unroll
-        for (int k = 0; k < PB_PER_THREAD; ++k) {
-            ftile[pad(tid * PB_PER_THREAD + k)] = f2{(float)r2, (float)r1};
-            r2 += v[k] * v[k];
-            r1 += v[k];
-        }
-    }
-    __syncthreads();
-    f2* __restrict__ us = reinterpret_cast<f2*>(usrel);
-#pragma unroll
-    for (int k = 0; k < PB_PER_THREAD; ++k) {
-        const int i = k * PB_THREADS + tid;
-        // e == n inside this block (n % PB != 0): samples past the end are zeros, so the running sum there is the total
-        if (blk + i <= n) {
-            const f2 x = ftile[pad(i)];
-            urel[blk + i] = x.u;
-            us[blk + i] = x;
-        }
-    }
-}
-
-// s2 and s1 at every COARSE_G-th sample (entries past the end: the totals) -- a table small enough to live in the L2s, from which
-// bound_kernel takes a lower bound of the window energies of a whole block pair
-__global__ void coarse_prefix_kernel(const double* __restrict__ s1, const double* __restrict__ s2, int64_t n, int64_t nc,
-                                     double* __restrict__ coarse) {
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < nc) {
-        const int64_t e = j * COARSE_G < n ? j * COARSE_G : n;
-        coarse[j] = s2[e];
-        coarse[nc + j] = s1[e];
-    }
-}
-
-// What the FFT path needs to know about a stream as a whole (sushi_fft.hip, "packed halves"): the constant its block
-// spectra are centred by -- the stream's own mean, as a float: any constant is exact (sum T I = sum T (I - c) + c sum T),
-// the mean keeps DC out of the products whatever level the data sits at -- and the largest centred energy of FFT_STEP + 1
-// consecutive blocks (what one block pair's transform can hold at most: the scale of the packed products is derived
-// from it).  One workgroup; bs2 / bs1 are the scanned block bases of sum x^2 / sum x.
-__global__ __launch_bounds__(1024)
-void fft_stats_kernel(const double* __restrict__ bs2, const double* __restrict__ bs1, int nb, int64_t n, double* __restrict__ stats) {
-    __shared__ double red[16];
-    const int tid = threadIdx.x;
-    const double c = (double)(float)(bs1[nb] / (double)n);
-    double emax = 0.0;
-    for (int j = tid; j < nb; j += 1024) {
-        const int je = min(j + FFT_STEP + 1, nb);
-        const int64_t lo = (int64_t)j * PB, hi = min((int64_t)je * PB, n);
-        const double e = (bs2[je] - bs2[j]) - 2.0 * c * (bs1[je] - bs1[j]) + c * c * (double)(hi - lo);
-        emax = e > emax ? e : emax;
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const double o = __shfl_down(emax, d, 64); emax = o > emax ? o : emax; }
-    if ((tid & 63) == 0) red[tid >> 6] = emax;
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < 16; ++w) emax = red[w] > emax ? red[w] : emax;
-        stats[0] = emax;
-        stats[1] = c;
-    }
-}
-
-inline int launch_ok() { return hipGetLastError() == hipSuccess ? SUSHI_HIP_OK : SUSHI_HIP_ELAUNCH; }
-
-struct Variant { int waves, nb; };
-constexpr Variant kVariants[] = {{1, 1}, {4, 1}, {4, 4}};
-constexpr int kNumVariants = 3;
-
 }  // namespace
 
 namespace sushi {
-
-int direct_variant_count() { return kNumVariants; }
-
-int direct_variant_tile(int variant) {
-    if (variant < 0 || variant >= kNumVariants) return 0;
-    return kVariants[variant].waves * kVariants[variant].nb * 1024;
-}
 
 int launch_unpack(const unsigned long long* keys_dev, int n, int method, int32_t* out_idx_dev, float* out_score_dev,
                   int32_t* out_packed_dev, hipStream_t st) {
     hipLaunchKernelGGL(unpack_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, st, keys_dev, n, method, out_idx_dev,
                        out_score_dev, reinterpret_cast<int2*>(out_packed_dev));
     return launch_ok();
-}
-
-int launch_direct(const StreamRefs& r, const SearchDesc* searches_dev, int n_search, int n_tiles, int variant, int method,
-                  unsigned long long* keys_dev, int32_t* out_idx_dev, float* out_score_dev, int32_t* out_packed_dev, hipStream_t st) {
-    if (n_tiles < n_search || variant < 0 || variant >= kNumVariants) return SUSHI_HIP_EINVAL;
-    if (method != SUSHI_HIP_METHOD_SQDIFF_NORMED && method != SUSHI_HIP_METHOD_CCOEFF_NORMED) return SUSHI_HIP_EINVAL;
-    if (hipMemsetAsync(keys_dev, 0xff, (size_t)n_search * sizeof(uint64_t), st) != hipSuccess) return SUSHI_HIP_ELAUNCH;
-    MatchArgs a;
-    a.dst_xc = r.dst_xc; a.dst_s1 = r.dst_s1; a.dst_s2 = r.dst_s2; a.dst_len = r.dst_len;
-    a.src_xc = r.src_xc; a.src_s1 = r.src_s1; a.src_s2 = r.src_s2; a.src_len = r.src_len;
-    a.centre = r.centre; a.searches = searches_dev; a.n_search = n_search; a.n_tiles = n_tiles;
-    a.keys = keys_dev; a.method = method;
-    switch (variant) {
-        case 0: hipLaunchKernelGGL((match_sqdiff_f32_kernel<1, 1>), dim3(n_tiles), dim3(64), 0, st, a); break;
-        case 1: hipLaunchKernelGGL((match_sqdiff_f32_kernel<4, 1>), dim3(n_tiles), dim3(256), 0, st, a); break;
-        default: hipLaunchKernelGGL((match_sqdiff_f32_kernel<4, 4>), dim3(n_tiles), dim3(256), 0, st, a); break;
-    }
-    if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-    return launch_unpack(keys_dev, n_search, method, out_idx_dev, out_score_dev, out_packed_dev, st);
 }
 
 __global__ __launch_bounds__(256)
@@ -1148,148 +680,3 @@ int launch_tiles(const TileParams& p, hipStream_t st) {
 }
 
 }  // namespace sushi
-
-using namespace sushi;
-
-namespace {
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-// where the parts of a prepared stream go inside the caller's buffer
-struct StreamLayout { size_t xc, s1, s2, urel, srel, base, base_bytes, coarse, spec, total; };
-
-StreamLayout stream_layout(int64_t n, int searchable) {
-    StreamLayout l;
-    const int64_t nb = (n + PB - 1) / PB;
-    size_t o = 0;
-    l.xc = o; o += align_up((size_t)n * sizeof(float), 256);
-    l.s1 = o; o += align_up((size_t)(n + 1) * sizeof(double), 256);
-    l.s2 = o; o += align_up((size_t)(n + 1) * sizeof(double), 256);
-    l.urel = o; o += align_up((size_t)(n + 1) * sizeof(float), 256);
-    l.srel = o; o += align_up((size_t)(n + 1) * 2 * sizeof(float), 256);     // usrel: (urel, srel) interleaved
-    l.base_bytes = (size_t)(2 * (nb + 1) + 2) * sizeof(double);  // block bases of sum x^2, then of sum x, then the FFT path's stats
-    l.base = o; o += align_up(l.base_bytes, 256);
-    l.coarse = o; o += align_up((size_t)2 * (size_t)(n / COARSE_G + 2) * sizeof(double), 256);
-    l.spec = o; o += searchable ? align_up(sushi_hip_stream_spectra_bytes(n), 256) : 0;
-    l.total = o;
-    return l;
-}
-
-}  // namespace
-
-extern "C" {
-
-int sushi_hip_abi_version(void) { return SUSHI_HIP_ABI_VERSION; }
-
-const char* sushi_hip_strerror(int code) {
-    switch (code) {
-        case SUSHI_HIP_OK: return "ok";
-        case SUSHI_HIP_EINVAL: return "invalid argument";
-        case SUSHI_HIP_EALIGN: return "device pointer not aligned";
-        case SUSHI_HIP_ELAUNCH: return "HIP launch failed";
-        case SUSHI_HIP_ENOSPACE: return "buffer or workspace too small";
-        case SUSHI_HIP_ENODEV: return "no gfx950 device";
-        case SUSHI_HIP_ENOMEM: return "out of host memory";
-        case SUSHI_HIP_EINTERNAL: return "internal error (a C++ exception was caught at the boundary)";
-        default: return "unknown sushi_hip error";
-    }
-}
-
-int sushi_hip_device_ok(void) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return SUSHI_HIP_ENODEV;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return SUSHI_HIP_ENODEV;
-    const char* arch = prop.gcnArchName;
-    // "gfx950:sramecc+:xnack-"
-    if (arch[0] == 'g' && arch[1] == 'f' && arch[2] == 'x' && arch[3] == '9' && arch[4] == '5' && arch[5] == '0')
-        return SUSHI_HIP_OK;
-    return SUSHI_HIP_ENODEV;
-}
-
-double sushi_hip_centre(int dtype) { return dtype == SUSHI_HIP_U8 ? 128.0 : 0.5; }
-
-size_t sushi_hip_stream_bytes(int64_t n, int dtype, int searchable) {
-    if (n <= 0 || (dtype != SUSHI_HIP_U8 && dtype != SUSHI_HIP_F32)) return 0;
-    return stream_layout(n, searchable).total;
-}
-
-int sushi_hip_stream_create(const void* raw_dev, int dtype, int64_t n, int searchable, void* mem_dev, size_t mem_bytes,
-                            void* hip_stream, SushiHipStream** out) {
-    if (!raw_dev || !mem_dev || !out || n <= 0) return SUSHI_HIP_EINVAL;
-    if (dtype != SUSHI_HIP_U8 && dtype != SUSHI_HIP_F32) return SUSHI_HIP_EINVAL;
-    if (((uintptr_t)mem_dev & 255) || (dtype == SUSHI_HIP_F32 && ((uintptr_t)raw_dev & 3))) return SUSHI_HIP_EALIGN;
-    const StreamLayout l = stream_layout(n, searchable);
-    if (mem_bytes < l.total) return SUSHI_HIP_ENOSPACE;
-    const int64_t nb64 = (n + PB - 1) / PB;
-    if (nb64 > 0x7ffffffe) return SUSHI_HIP_EINVAL;
-    const int nb = (int)nb64;
-    SushiHipStream* s = new (std::nothrow) SushiHipStream();
-    if (!s) return SUSHI_HIP_EINVAL;
-    char* m = (char*)mem_dev;
-    s->raw = raw_dev; s->dtype = dtype; s->n = n;
-    s->xc = (float*)(m + l.xc); s->s1 = (double*)(m + l.s1); s->s2 = (double*)(m + l.s2);
-    s->urel = (float*)(m + l.urel); s->usrel = (float*)(m + l.srel); s->base = (double*)(m + l.base); s->base_bytes = l.base_bytes;
-    s->spec = nullptr; s->spec_low = nullptr; s->znorm_rest = nullptr; s->norm_stride = 0; s->spec_bytes = 0; s->blocks = nb; s->stats = s->base + 2 * (nb + 1);
-    s->coarse = (double*)(m + l.coarse); s->nc = n / COARSE_G + 2;
-    hipStream_t st = (hipStream_t)hip_stream;
-    double* bs2 = s->base;                       // block bases of sum x^2 (what the FFT path's scoring reads)
-    double* bs1 = s->base + (nb + 1);            // block bases of sum x
-    if (dtype == SUSHI_HIP_F32)
-        hipLaunchKernelGGL(centre_blocksum_kernel<float>, dim3(nb), dim3(PB_THREADS), 0, st,
-                           (const float*)raw_dev, n, s->xc, bs1, bs2);
-    else
-        hipLaunchKernelGGL(centre_blocksum_kernel<uint8_t>, dim3(nb), dim3(PB_THREADS), 0, st,
-                           (const uint8_t*)raw_dev, n, s->xc, bs1, bs2);
-    int rc = launch_ok();
-    if (rc == SUSHI_HIP_OK) {
-        hipLaunchKernelGGL(scan_blocksums_kernel<2>, dim3(1), dim3(1024), 0, st, s->base, nb + 1, nb);
-        rc = launch_ok();
-    }
-    if (rc == SUSHI_HIP_OK) {
-        if (dtype == SUSHI_HIP_F32)
-            hipLaunchKernelGGL(final_scan_kernel<float>, dim3(nb), dim3(PB_THREADS), 0, st, (const float*)raw_dev, n,
-                               (const double*)bs1, (const double*)bs2, s->s1, s->s2, s->urel, s->usrel);
-        else
-            hipLaunchKernelGGL(final_scan_kernel<uint8_t>, dim3(nb), dim3(PB_THREADS), 0, st, (const uint8_t*)raw_dev, n,
-                               (const double*)bs1, (const double*)bs2, s->s1, s->s2, s->urel, s->usrel);
-        rc = launch_ok();
-    }
-    if (rc == SUSHI_HIP_OK) {
-        hipLaunchKernelGGL(fft_stats_kernel, dim3(1), dim3(1024), 0, st, (const double*)bs2, (const double*)bs1, nb, n, s->stats);
-        rc = launch_ok();
-    }
-    if (rc == SUSHI_HIP_OK) {
-        hipLaunchKernelGGL(coarse_prefix_kernel, dim3((unsigned)((s->nc + 255) / 256)), dim3(256), 0, st, (const double*)s->s1,
-                           (const double*)s->s2, n, s->nc, s->coarse);
-        rc = launch_ok();
-    }
-    if (rc == SUSHI_HIP_OK && searchable)
-        rc = sushi_hip_stream_add_spectra(s, m + l.spec, mem_bytes - l.spec, hip_stream);
-    if (rc != SUSHI_HIP_OK) { delete s; return rc; }
-    *out = s;
-    return SUSHI_HIP_OK;
-}
-
-int sushi_hip_stream_view(const SushiHipStream* s, int which, const void** ptr_dev, size_t* bytes) {
-    if (!s || !ptr_dev || !bytes) return SUSHI_HIP_EINVAL;
-    switch (which) {
-        case SUSHI_HIP_VIEW_XC: *ptr_dev = s->xc; *bytes = (size_t)s->n * sizeof(float); break;
-        case SUSHI_HIP_VIEW_S1: *ptr_dev = s->s1; *bytes = (size_t)(s->n + 1) * sizeof(double); break;
-        case SUSHI_HIP_VIEW_S2: *ptr_dev = s->s2; *bytes = (size_t)(s->n + 1) * sizeof(double); break;
-        case SUSHI_HIP_VIEW_UREL: *ptr_dev = s->urel; *bytes = (size_t)(s->n + 1) * sizeof(float); break;
-        case SUSHI_HIP_VIEW_BASE: *ptr_dev = s->base; *bytes = (size_t)(s->blocks + 1) * sizeof(double); break;
-        case SUSHI_HIP_VIEW_SPECTRA: *ptr_dev = s->spec; *bytes = s->spec_bytes; break;
-        case SUSHI_HIP_VIEW_SPECTRA_LOW: *ptr_dev = s->spec_low; *bytes = s->spec ? s->spec_bytes / 4 : 0; break;
-        case SUSHI_HIP_VIEW_ZNORM_REST: *ptr_dev = s->znorm_rest; *bytes = s->spec ? (size_t)3 * (size_t)s->norm_stride * sizeof(float) : 0; break;
-        case SUSHI_HIP_VIEW_USREL: *ptr_dev = s->usrel; *bytes = (size_t)(s->n + 1) * 2 * sizeof(float); break;
-        case SUSHI_HIP_VIEW_BASE1: *ptr_dev = s->base + (s->blocks + 1); *bytes = (size_t)(s->blocks + 1) * sizeof(double); break;
-        case SUSHI_HIP_VIEW_COARSE: *ptr_dev = s->coarse; *bytes = (size_t)2 * (size_t)s->nc * sizeof(double); break;
-        default: return SUSHI_HIP_EINVAL;
-    }
-    return SUSHI_HIP_OK;
-}
-
-void sushi_hip_stream_destroy(SushiHipStream* s) { delete s; }
-
-}  // extern "C"

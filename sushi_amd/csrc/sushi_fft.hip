@@ -26,10 +26,10 @@
 //                    FFT_STEP*I*B + r and FFT_STEP*I*B + H + r.  Fused epilogue: window energies, normalised f32
 //                    score, the pair's error bound, arg-min, and the list of positions that can still be the
 //                    minimum (candidates); the pair's lower bound held to what it really scores (the exclusion's audit).
-//   refine_kernel    (sushi_hip.hip) exact float64 re-evaluation of the candidates -> final (index, score);
+//   refine_kernel    (sushi_exact.hip) exact float64 re-evaluation of the candidates -> final (index, score);
 //   collect + tiles  searches with more candidates than the lists hold: the inverse transforms of their pairs
 //                    are redone with the search's final threshold, every candidate goes to a per-tile list
-//                    (a tile = 1024 positions) and exact_tiles_kernel (sushi_hip.hip) evaluates those exactly.
+//                    (a tile = 1024 positions) and exact_tiles_kernel (sushi_exact.hip) evaluates those exactly.
 //
 // Pairing two real blocks as one complex block makes every N-point complex DFT produce 2H useful
 // results and needs no real-FFT untangling pass: the pattern is real, so correlation is linear
@@ -366,7 +366,7 @@ static BoundArgs bound_args(const RunCtx& c, const SubView& v) {
     ba.dst_stats = dst->stats; ba.searches = c.searches + v.sb.a0; ba.sub_first_pair = v.sb.first_pair; ba.first_search = v.sb.a0; ba.dst_len = dst->n;
     ba.pairmap = v.pairmap; ba.tconst = v.tconst; ba.ubase = dst->base; ba.sbase = dst->base + (dst->blocks + 1); ba.nb = dst->blocks;
     ba.coarse = dst->coarse; ba.nc = dst->nc; ba.slb = v.slb; ba.n_sub = v.n_sub; ba.n_pairs = (int)v.sb.pairs; ba.plist = v.plist;
-    ba.slist = v.slist; ba.scount = v.scount; ba.order = v.order; ba.gkeys = c.gkeys; ba.pair_lb = v.pair_lb; ba.counters = c.counters; ba.acc = v.acc;
+    ba.slist = v.slist; ba.scount = v.n_slist; ba.order = v.order; ba.gkeys = c.gkeys; ba.pair_lb = v.pair_lb; ba.counters = c.counters; ba.acc = v.acc;
     ba.sub_first_seg = v.sb.first_seg; ba.tnorm_rest = v.tnorm_rest; ba.znorm_rest = dst->znorm_rest; ba.norm_stride = dst->norm_stride;
     ba.band_votes = v.votes; ba.audit_mark = v.audit_mark; ba.audit_seq = c.run_seq; ba.audit_every = c.b->audit_every;
     // What a packed-half transform output (bound_low_kernel / bound_kernel) may be off by, in units of the largest pass-1 value:
@@ -526,7 +526,7 @@ static int bound_pairs(const RunCtx& c, const SubView& v, hipStream_t st, const 
 // ba.list2 / ba.list2_count
 static int second_look(const RunCtx& c, const SubView& v, hipStream_t st, BoundArgs& ba) {
     ba.list = ba.slist; ba.list_count = ba.scount;
-    ba.list2 = v.slist2; ba.list2_count = v.scount + 5;
+    ba.list2 = v.slist2; ba.list2_count = v.n_slist2;
     hipLaunchKernelGGL(bound_low_exact_kernel, dim3(256 * 4), dim3(BLE_T), 0, st, ba);
     if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     if (launch_method(c.method, [&](auto m) { hipLaunchKernelGGL(slb_list_kernel<decltype(m)::value>, dim3(256 * 2), dim3(256), 0, st, ba); }) !=
@@ -560,11 +560,11 @@ static int exclude_pairs(const RunCtx& c, const SubView& v, hipStream_t st, cons
     // whole rows of what is left: pair by pair for the searches that left few (the usual case), by the dense
     // multiply-accumulate for the searches the bound could exclude little of (no match anywhere) -- decided per search and
     // regrouped into items of their own, on the device (dense_search_kernel, dense_repack_kernel)
-    int* any_dense = v.scount + 4;                       // (zero since the run's first launch)
-    hipLaunchKernelGGL(dense_search_kernel, dim3((unsigned)v.n_sub), dim3(64), 0, st, ba, v.dense_search, v.scount + 6);
+    hipLaunchKernelGGL(dense_search_kernel, dim3((unsigned)v.n_sub), dim3(64), 0, st, ba, v.dense_search, v.n_dense_listed);
     const size_t second = (size_t)(sb.item_first[1] - sb.item_first[0]) * (1 + MAC_SPW);
     hipLaunchKernelGGL(dense_repack_kernel, dim3(2), dim3(REPACK_THREADS), 0, st, v.items, sb.item_count[0], v.items + second,
-                       sb.item_count[1], v.dense_search, v.n_sub, v.ditems, v.ditems + second, v.scount + 6, (int)(sb.pairs / 8), any_dense);
+                       sb.item_count[1], v.dense_search, v.n_sub, v.ditems, v.ditems + second, v.n_dense_listed, (int)(sb.pairs / 8),
+                       v.any_dense);                             // (zero since the run's first launch)
     if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     MacRowsArgs ra;
     ra.spec = (const uint4*)c.dst->spec; ra.spec_blocks = c.dst->blocks; ra.tspec = (const uint4*)v.tspec; ra.y = v.y;
@@ -575,7 +575,7 @@ static int exclude_pairs(const RunCtx& c, const SubView& v, hipStream_t st, cons
     if (sb.item_count[1] > 0) hipLaunchKernelGGL(mac_rows_kernel<1>, dim3((unsigned)std::min<int64_t>(rows_want, 256 * 16)), dim3(MACL_THREADS), 0, st, ra);
     if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     if (sb.long_patterns && launch_mac_list(c, v, st, ba.list2, ba.list2_count, (int)sb.pairs, v.dense_search, 1) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-    return launch_mac(c, v, st, false, any_dense, v.ditems);
+    return launch_mac(c, v, st, false, v.any_dense, v.ditems);
 }
 
 // the transform of the listed pairs
@@ -607,7 +607,7 @@ static int stage_refine(const RunCtx& c, const SubView& v, hipStream_t st) {
     RefineParams rp;
     rp.r = c.r; rp.searches = c.searches; rp.first_search = v.sb.a0; rp.n_sub = v.n_sub; rp.sub_first_pair = v.sb.first_pair;
     rp.cand = v.cand; rp.pair_lb = v.pair_lb; rp.gkeys = c.gkeys; rp.keys = c.keys; rp.flags = c.flags; rp.flag_list = c.flag_list + v.sb.a0;
-    rp.sub = v.sub; rp.counters = c.counters; rp.delta = (float)c.delta; rp.method = c.method; rp.citems = v.citems; rp.n_citems = v.scount + 1;
+    rp.sub = v.sub; rp.counters = c.counters; rp.delta = (float)c.delta; rp.method = c.method; rp.citems = v.citems; rp.n_citems = v.n_citems;
     rp.viol = c.viol; rp.early = reinterpret_cast<int4*>(c.b->early_out);
     const int rc = launch_refine(rp, st);
     if (rc == SUSHI_HIP_OK) prof_end(c.pc, t0, SUSHI_HIP_STAGE_REFINE, st);
@@ -618,7 +618,7 @@ static int stage_refine(const RunCtx& c, const SubView& v, hipStream_t st) {
 // (both kernels leave after one load when nothing is flagged)
 static int stage_collect(const RunCtx& c, const SubView& v, hipStream_t st, IfftArgs ia) {
     hipEvent_t t0 = prof_begin(c.pc, st);
-    ia.citems = v.citems; ia.n_citems = v.scount + 1;    // (refine_kernel's list: RefineParams::citems)
+    ia.citems = v.citems; ia.n_citems = v.n_citems;    // (refine_kernel's list: RefineParams::citems)
     if (launch_method(c.method, [&](auto m) { hipLaunchKernelGGL(collect_kernel<decltype(m)::value>, dim3(COLLECT_GRID), dim3(FT), 0, st, ia); }) !=
         SUSHI_HIP_OK)
         return SUSHI_HIP_ELAUNCH;
@@ -745,7 +745,7 @@ static int run_sub_threshold(RunCtx& c, const SubView& v, hipStream_t st, const 
         }
         ta.list = tp.lp.list; ta.list_count = tp.lp.list_count;
         // (the first list is free once the second look has read it; the whole-row form never used the second)
-        ta.list3 = band ? v.slist : v.slist2; ta.list3_count = v.scount + 7;
+        ta.list3 = band ? v.slist : v.slist2; ta.list3_count = v.n_list3;
     } else {
         b->direct_pairs += sb.pairs;
     }
@@ -797,11 +797,10 @@ static int run_sub_best(RunCtx& c, const SubView& v, hipStream_t st, const BestR
     BestArgs a;
     memset(&a, 0, sizeof(a));
     pair_run_args(c, v, a);
-    a.k = br.k; a.order = v.order; a.gkeys = c.gkeys; a.tkey = br.tkey; a.list = v.slist; a.list_count = v.scount; a.flags = c.flags;
+    a.k = br.k; a.order = v.order; a.gkeys = c.gkeys; a.tkey = br.tkey; a.list = v.slist; a.list_count = v.n_slist; a.flags = c.flags;
     a.need = c.flag_list; a.audit_seq = c.run_seq; a.audit_every = b->audit_every;
     // the two lists and their lengths (zero since the run's first launch; every selection clears them for the round behind it)
-    int* const count2 = v.scount + 5;
-    bp.audit_mark = v.audit_mark; bp.stamp_flags = c.flags; bp.reset0 = v.scount; bp.reset1 = count2;
+    bp.audit_mark = v.audit_mark; bp.stamp_flags = c.flags; bp.reset0 = v.n_slist; bp.reset1 = v.n_slist2;
     const unsigned per_pair = (unsigned)((sb.pairs + 255) / 256);
     auto evaluate = [&](const int* list, const int* count) {
         bp.lp.list = list; bp.lp.list_count = count;
@@ -815,22 +814,22 @@ static int run_sub_best(RunCtx& c, const SubView& v, hipStream_t st, const BestR
     // it does in a threshold run; without one there is no U yet and every seed pair is evaluated)
     const bool seed_look = band && br.has_threshold;
     if (seed_look && second_look(c, v, st, ba) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-    if (evaluate(seed_look ? v.slist2 : v.slist, seed_look ? count2 : v.scount) != SUSHI_HIP_OK || launch_best_select(bp, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    if (evaluate(seed_look ? v.slist2 : v.slist, seed_look ? v.n_slist2 : v.n_slist) != SUSHI_HIP_OK || launch_best_select(bp, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     for (int round = 0; round < BEST_ROUNDS; ++round) {
         a.stamp = bp.stamp = ++stamp;
         hipLaunchKernelGGL(best_survivor_kernel, dim3(per_pair), dim3(256), 0, st, a);
         if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
         // (band-split form: the second look at what the bound left, as in every other run)
         if (band && second_look(c, v, st, ba) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-        if (evaluate(band ? v.slist2 : v.slist, band ? count2 : v.scount) != SUSHI_HIP_OK || launch_best_select(bp, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+        if (evaluate(band ? v.slist2 : v.slist, band ? v.n_slist2 : v.n_slist) != SUSHI_HIP_OK || launch_best_select(bp, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     }
     a.stamp = bp.stamp = ++stamp;
     hipLaunchKernelGGL(best_final_kernel, dim3(per_pair), dim3(256), 0, st, a);
-    if (launch_ok() != SUSHI_HIP_OK || evaluate(v.slist, v.scount) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    if (launch_ok() != SUSHI_HIP_OK || evaluate(v.slist, v.n_slist) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     hipLaunchKernelGGL(best_check_kernel, dim3(per_pair), dim3(256), 0, st, a);
-    a.list = v.slist2; a.list_count = count2;
+    a.list = v.slist2; a.list_count = v.n_slist2;
     hipLaunchKernelGGL(best_extend_kernel, dim3(per_pair), dim3(256), 0, st, a);
-    if (launch_ok() != SUSHI_HIP_OK || evaluate(v.slist2, count2) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    if (launch_ok() != SUSHI_HIP_OK || evaluate(v.slist2, v.n_slist2) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     return launch_best_select(bp, st);
 }
 

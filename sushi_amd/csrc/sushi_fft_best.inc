@@ -4,7 +4,7 @@
 // search's running threshold U FOUND by the run itself: the ranking score of the K-th pick that greedy suppression makes from the
 // pairs evaluated so far (best_select_kernel, sushi_curve.hip, leaves it in gkeys).  A pair is listed for exact evaluation
 // (best_tiles_kernel) as soon as its bound does not exclude it under the U of the moment, and a pair once evaluated stays so:
-// audit_mark bit 1.  Per sub-batch, a fixed launch sequence, every list length a count on the device:
+// audit_mark's MARK_LISTED.  Per sub-batch, a fixed launch sequence, every list length a count on the device:
 //   best_seed_kernel      per search: its BEST_SEED_EXTRA + K pairs of smallest bound are evaluated first
 //   best_survivor_kernel  a round of escalation: the pairs not yet evaluated that their search's U does not exclude
 //                         (band-split form: then the second look, survivor2_kernel)
@@ -17,7 +17,7 @@
 constexpr int BEST_SEED_EXTRA = 2;     // pairs seeded beyond K: K picks S apart lie in at most K pairs; two more for picks next to a pair's ends
 constexpr int BEST_ROUNDS = 2;         // escalation rounds before the last one, which settles whatever is left
 
-struct BestArgs : PairRunArgs {       // (audit_mark: bit 2 by the second look, bit 3 by best_final_kernel)
+struct BestArgs : PairRunArgs {       // (audit_mark: MARK_SECOND_LOOK by the second look, MARK_BEST_FINAL by best_final_kernel)
     int k;
     const int* order;                 // the L2-friendly schedule of all pairs (lists keep its order)
     unsigned long long* gkeys;        // [all searches]
@@ -37,7 +37,7 @@ void best_seed_kernel(BestArgs a) {
     const int k = blockIdx.x, tid = threadIdx.x;
     const SearchDesc sd = a.searches[k];
     const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
-    const int p0 = sd.first_pair - a.sub_first_pair;
+    const int p0 = first_pair_in_sub(a.sub_first_pair, sd);
     for (int i = tid; i < lay.n_pairs; i += 256) a.audit_mark[p0 + i] = 0;
     if (tid == 0) { a.gkeys[a.first_search + k] = a.tkey; a.flags[a.first_search + k] = a.stamp; }
     __syncthreads();
@@ -55,7 +55,7 @@ void best_seed_kernel(BestArgs a) {
         prev = best;
         const int pr = p0 + (int)(best & 0xffffffffull);
         if (tid == 0 && !bound_excludes(a.slb, pr, a.gkeys[a.first_search + k])) {
-            a.audit_mark[pr] = 2;
+            a.audit_mark[pr] = MARK_LISTED;
             a.list[atomicAdd(a.list_count, 1)] = pr;
             ++n;
         }
@@ -72,9 +72,9 @@ void best_survivor_kernel(BestArgs a) {
     if (b < a.n_pairs) {
         pr = a.order[b];
         const int k = a.pairmap[pr];
-        if (!(a.audit_mark[pr] & 2) && !bound_excludes(a.slb, pr, a.gkeys[a.first_search + k])) {
+        if (!(a.audit_mark[pr] & MARK_LISTED) && !bound_excludes(a.slb, pr, a.gkeys[a.first_search + k])) {
             add = true;
-            a.audit_mark[pr] = 2;
+            a.audit_mark[pr] = MARK_LISTED;
             a.flags[a.first_search + k] = a.stamp;
         }
     }
@@ -91,12 +91,12 @@ void best_final_kernel(BestArgs a) {
     if (b < a.n_pairs) {
         pr = a.order[b];
         const int k = a.pairmap[pr];
-        if (!(a.audit_mark[pr] & 2)) {
+        if (!(a.audit_mark[pr] & MARK_LISTED)) {
             if (!bound_excludes(a.slb, pr, a.gkeys[a.first_search + k])) {
                 a.need[a.first_search + k] = 1;
             } else if (is_audit_pair(a, pr, k)) {
                 add = true;
-                a.audit_mark[pr] = 1 | 2 | 8;
+                a.audit_mark[pr] = MARK_AUDITED | MARK_LISTED | MARK_BEST_FINAL;
             }
         }
     }
@@ -110,11 +110,11 @@ void best_check_kernel(BestArgs a) {
     const int pr = blockIdx.x * 256 + threadIdx.x;
     if (pr >= a.n_pairs) return;
     const unsigned char am = a.audit_mark[pr];
-    if (!(am & 1)) return;
+    if (!(am & MARK_AUDITED)) return;
     const int gk = a.first_search + a.pairmap[pr];
     const bool violated = audit_pair(a, pr, true, [&](const float ub) {
         const unsigned long long g = a.gkeys[gk];
-        return (am & 8) && g != NO_KEY && ub <= key_score(g);
+        return (am & MARK_BEST_FINAL) && g != NO_KEY && ub <= key_score(g);
     });
     if (violated) a.flags[gk] = a.stamp;
 }
@@ -128,9 +128,9 @@ void best_extend_kernel(BestArgs a) {
     if (b < a.n_pairs) {
         pr = a.order[b];
         const int k = a.first_search + a.pairmap[pr];
-        if (!(a.audit_mark[pr] & 2) && (a.need[k] || a.viol[k])) {
+        if (!(a.audit_mark[pr] & MARK_LISTED) && (a.need[k] || a.viol[k])) {
             add = true;
-            a.audit_mark[pr] |= 2;
+            a.audit_mark[pr] |= MARK_LISTED;
             a.flags[k] = a.stamp;
         }
     }

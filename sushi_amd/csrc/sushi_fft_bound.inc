@@ -56,7 +56,7 @@ struct BoundArgs {
     const float* znorm_rest;          // [3][norm_stride] block spectra: norm outside the band of Z, of its real block at j B, of the one H on
     int64_t norm_stride;
     int* band_votes;                  // [VOTE_SLOTS][VOTE_STRIDE] prediction: per slot [0] pairs looked at, [1] pairs whose bound leaves room
-    unsigned char* audit_mark;        // [pairs of the sub-batch] bit 0 = excluded, transformed all the same (the audit of the exclusion); bit 1 = listed; bit 2 = excluded by the second look
+    unsigned char* audit_mark;        // [pairs of the sub-batch] MARK_* bits (sushi_internal.hpp): MARK_AUDITED, MARK_LISTED, MARK_SECOND_LOOK
     unsigned audit_seq;               // changes from run to run: which excluded pair of a search is audited
     int audit_every;                  // one search in this many is audited per run (0: none)
     int worst_case;                   // 1: every rounding on the excluded side enters at its WORST CASE (slb_one; the default); 0: round 5's statistical model
@@ -224,7 +224,7 @@ __device__ __forceinline__ void slb_one(const BoundArgs& a, const int pr, const 
     const int k = __builtin_amdgcn_readfirstlane(a.pairmap[pr]);
     const SearchDesc sd = a.searches[k];
     const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
-    const int64_t pairI = lay.pair0 + (a.sub_first_pair + pr - sd.first_pair);
+    const int64_t pairI = absolute_pair(lay, a.sub_first_pair, pr, sd);
     const int64_t qbase = pairI * FFT_STEP * (int64_t)FFT_SEG;
     const int M = sd.tmpl_len;
     const TemplConsts tc = a.tconst[k];
@@ -424,7 +424,7 @@ void bound_fault_kernel(BoundFaultArgs a) {
     if (pr >= a.n_pairs) return;
     const int k = a.pairmap[pr];
     if ((unsigned)(a.first_search + k) % (unsigned)a.f.period != (unsigned)a.f.phase) return;
-    if (a.f.pair >= 0 && a.sub_first_pair + pr - a.searches[k].first_pair != a.f.pair) return;
+    if (a.f.pair >= 0 && pair_of_search(a.sub_first_pair, pr, a.searches[k]) != a.f.pair) return;
     a.slb[pr] = __builtin_inff();
 }
 
@@ -434,7 +434,7 @@ void pilot_kernel(BoundArgs a) {
     const int k = blockIdx.x, lane = threadIdx.x;
     const SearchDesc sd = a.searches[k];
     const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
-    const int p0 = sd.first_pair - a.sub_first_pair;
+    const int p0 = first_pair_in_sub(a.sub_first_pair, sd);
     unsigned long long best = NO_KEY;
     for (int i = lane; i < lay.n_pairs; i += 64) {
         const float s = a.slb[p0 + i];
@@ -476,7 +476,7 @@ template <class Args>
 __device__ __forceinline__ bool is_audit_pair(const Args& a, const int pr, const int k) {
     if (!audited_search(a, k)) return false;
     const SearchDesc sd = a.searches[k];
-    return audit_pair_of(a, sd, k) == a.sub_first_pair + pr - sd.first_pair;
+    return audit_pair_of(a, sd, k) == pair_of_search(a.sub_first_pair, pr, sd);
 }
 
 // the pairs `pr` of the lanes with `add` set to the end of a list, in lane order: one atomicAdd per wave (every lane calls it)
@@ -506,7 +506,8 @@ void survivor_kernel(BoundArgs a) {
         if (a.plist[k] != pr) {
             const bool excluded = bound_excludes(a.slb, pr, a.gkeys[a.first_search + k]);
             // (is_audit_pair, from its two parts: with the flag coming back through the one helper two operands of an s_or_b64 change
-            // places in this kernel's code, and the bench path's recorded counters stand on identical code)
+            // places in this kernel's code, and the bench path's recorded counters stand on identical code; pair_of_search is
+            // written out below for the same reason)
             if (excluded && audited_search(a, k)) {
                 const SearchDesc sd = a.searches[k];
                 audit = audit_pair_of(a, sd, k) == a.sub_first_pair + pr - sd.first_pair;
@@ -514,7 +515,7 @@ void survivor_kernel(BoundArgs a) {
             if (excluded && !audit) a.pair_lb[pr] = __builtin_inff();
             keep = !excluded || audit;
         }
-        if (a.audit_mark) a.audit_mark[pr] = (audit ? 1 : 0) | (keep ? 2 : 0);          // bit 0: audited, bit 1: listed
+        if (a.audit_mark) a.audit_mark[pr] = (audit ? MARK_AUDITED : 0) | (keep ? MARK_LISTED : 0);
     }
     append_pairs(a.slist, a.scount, a.counters, keep, pr);
 }
@@ -532,7 +533,7 @@ struct MacRowsArgs {
     uint4* y;
     const SearchDesc* searches;
     const TemplConsts* tconst;
-    const unsigned char* mark;        // [pairs of the sub-batch] bit 1: listed
+    const unsigned char* mark;        // [pairs of the sub-batch] MARK_LISTED: the pair's row is formed
     int n_sub;
     int sub_first_seg;
     int sub_first_pair;
@@ -544,7 +545,7 @@ __device__ __forceinline__ void mac_rows_of_search(const MacRowsArgs& a, const S
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
     const uint4* __restrict__ tsp = a.tspec + (size_t)(sd.first_seg - a.sub_first_seg) * ROWE + e;
     const uint4* __restrict__ zsp = a.spec + e;
-    const int p0 = sd.first_pair - a.sub_first_pair;
+    const int p0 = first_pair_in_sub(a.sub_first_pair, sd);
     sushi_mac::h8 tt[SMAX];
 #pragma unroll
     for (int s = 0; s < SMAX; ++s) tt[s] = s < lay.n_seg ? as_h8(tsp[(size_t)s * ROWE]) : sushi_mac::zero_h8();
@@ -553,7 +554,7 @@ __device__ __forceinline__ void mac_rows_of_search(const MacRowsArgs& a, const S
         // which of these 256 pairs are listed: one flag per thread, a ballot per wave
         __syncthreads();
         const int i = base + tid;
-        const bool on = i < lay.n_pairs && (a.mark[p0 + i] & 2);
+        const bool on = i < lay.n_pairs && (a.mark[p0 + i] & MARK_LISTED);
         const unsigned long long bm = __ballot(on);
         if ((tid & 63) == 0) (*masks)[tid >> 6] = bm;
         __syncthreads();
@@ -681,14 +682,14 @@ void survivor2_kernel(BoundArgs a) {
         if (slot < n) {
             pr = a.list[slot];
             keep = true;
-            if (second_look && !(a.audit_mark[pr] & 1)) {
+            if (second_look && !(a.audit_mark[pr] & MARK_AUDITED)) {
                 const int k = a.pairmap[pr];
                 if (bound_excludes(a.slb, pr, a.gkeys[a.first_search + k])) {
                     // the audit of THIS bound: a hashed sample of the pairs it excludes -- other ones every run -- stays listed, is
                     // transformed all the same, and ifft_kernel holds the pair's (second) lower bound to what it really scores
                     const unsigned h = ((unsigned)(a.sub_first_pair + pr) * 2654435761u + a.audit_seq * 40503u) >> 11;
                     if (a.audit_every > 0 && h % (16u * (unsigned)a.audit_every) == 0u) {
-                        a.audit_mark[pr] = 1 | 2 | 4;                   // audited, listed, by the second look
+                        a.audit_mark[pr] = MARK_AUDITED | MARK_LISTED | MARK_SECOND_LOOK;
                     } else {
                         keep = false;
                         a.pair_lb[pr] = __builtin_inff();
@@ -730,9 +731,9 @@ void dense_search_kernel(BoundArgs a, int* __restrict__ dense_search, int* __res
     const int k = blockIdx.x;
     const SearchDesc sd = a.searches[k];
     const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
-    const int p0 = sd.first_pair - a.sub_first_pair;
+    const int p0 = first_pair_in_sub(a.sub_first_pair, sd);
     int listed = 0;
-    for (int i = lane; i < lay.n_pairs; i += 64) listed += (a.audit_mark[p0 + i] & 2) ? 1 : 0;
+    for (int i = lane; i < lay.n_pairs; i += 64) listed += (a.audit_mark[p0 + i] & MARK_LISTED) ? 1 : 0;
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) listed += __shfl_xor(listed, d, 64);
     if (lane == 0) {

@@ -34,7 +34,7 @@ void collect_kernel(IfftArgs a) {
             const bool everything = a.flags[s_idx] == 2;
             // smallest (score + bound) of the search; none (TM_CCOEFF_NORMED: every window uncertain): everything is a candidate
             const float U = a.gkeys[s_idx] == NO_KEY ? 4.0f : key_score(a.gkeys[s_idx]);
-            const int i = a.sub_first_pair + pr - sd.first_pair;
+            const int i = pair_of_search(a.sub_first_pair, pr, sd);
             const int64_t qbase = (lay.pair0 + i) * (int64_t)FFT_STEP * FFT_SEG;
             const int64_t rel0 = qbase - sd.win_start;                     // position (relative to the window) of pos 0
             __syncthreads();                                               // previous item's shared state is consumed

@@ -37,7 +37,7 @@ struct IfftArgs {
     RunCounters* counters;
     // the audit of the exclusion: every transformed pair's lower bound against what the pair really scores
     const float* slb;                 // [pairs of the sub-batch] or NULL (no exclusion in this run)
-    const unsigned char* audit_mark;  // [pairs of the sub-batch] bit 0 = the bound had EXCLUDED this pair (transformed as a check)
+    const unsigned char* audit_mark;  // [pairs of the sub-batch] MARK_AUDITED = the bound had EXCLUDED this pair (transformed as a check)
     int* viol;                        // [all searches] set to 1 where a lower bound turns out above a real score
     int list_first;                   // with `count`: the first list slot this launch takes ...
     int list_direct;                  // ... one workgroup per slot (ifft_kernel), or a fixed grid striding from there on (ifft_list_kernel)
@@ -433,7 +433,7 @@ __device__ __forceinline__ void ifft_one(const IfftArgs& a, const int slot, floa
     }
     const int k = __builtin_amdgcn_readfirstlane(a.pairmap[pr]);       // wave-uniform: everything derived from it is scalar
     const SearchDesc sd = a.searches[k];
-    const int i = a.sub_first_pair + pr - sd.first_pair;
+    const int i = pair_of_search(a.sub_first_pair, pr, sd);
     const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
     const TemplConsts tc = a.tconst[k];
     // the pair's row of the candidate array starts as all NO_KEY (memset at the start of the run): only what exists is written
@@ -480,14 +480,14 @@ __device__ __forceinline__ void ifft_one(const IfftArgs& a, const int slot, floa
             // a bound in the thousands and every score 1)
             const float s = METHOD == SUSHI_HIP_METHOD_CCOEFF_NORMED ? a.slb[pr] : fminf(a.slb[pr], 1.0f), ub = lmin_s + e_pair;
             const unsigned char am = a.audit_mark ? a.audit_mark[pr] : (unsigned char)0;
-            const bool audit = (am & 1) != 0;
+            const bool audit = (am & MARK_AUDITED) != 0;
             if (s > ub * 1.00001f + 1e-7f) {
                 a.viol[a.first_search + k] = 1;
                 atomicAdd(&a.counters->slb_violations, 1);
             }
             if (audit) {
                 atomicAdd(&a.counters->excluded_audited, 1ull);
-                if (am & 4) atomicAdd(&a.counters->second_look_audited, 1ull);
+                if (am & MARK_SECOND_LOOK) atomicAdd(&a.counters->second_look_audited, 1ull);
                 const float ratio = s > 0.f ? s / fmaxf(ub, 1e-30f) : 0.f;
                 if (__float_as_uint(ratio) > *(volatile uint32_t*)&a.counters->max_slb_ratio_bits)
                     atomicMax(&a.counters->max_slb_ratio_bits, __float_as_uint(ratio));

@@ -177,7 +177,7 @@ __device__ __forceinline__ void mac_item(const MacArgs& a, const int* __restrict
         const SearchDesc sd = a.searches[k];
         const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
         pair_lo = lay.pair0; pair_hi = lay.pair0 + lay.n_pairs; n_seg = lay.n_seg;
-        first_seg = sd.first_seg - a.sub_first_seg; first_pair = sd.first_pair - a.sub_first_pair;
+        first_seg = sd.first_seg - a.sub_first_seg; first_pair = first_pair_in_sub(a.sub_first_pair, sd);
         sy = a.tconst[k].mac_scale;
         long long g0, g1;
         sushi_mac::group_range<SMAX, STEP>(pair_lo, pair_hi, &g0, &g1);
@@ -298,7 +298,7 @@ void mac_list_kernel(MacListArgs a) {
         const SearchDesc sd = a.searches[k];
         const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
         if (a.long_only && lay.n_seg <= MAC_SMAX_LONG) continue;
-        const long long I = lay.pair0 + (a.sub_first_pair + pr - sd.first_pair);
+        const long long I = absolute_pair(lay, a.sub_first_pair, pr, sd);
         const float sy = a.tconst[k].mac_scale;
         const uint4* __restrict__ tsp = a.tspec + (size_t)(sd.first_seg - a.sub_first_seg) * ROWE + e;
         const uint4* __restrict__ zsp = a.spec + e;

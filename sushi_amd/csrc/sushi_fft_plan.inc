@@ -1,8 +1,6 @@
 // sushi_amd/csrc/sushi_fft_plan.inc -- part of sushi_fft.hip (included there, inside its anonymous namespace; not a header of its own):
 // host side: workspace layout, per-stage timing, the plan of a batch, its device-memory layout.
 
-inline int launch_ok() { return hipGetLastError() == hipSuccess ? SUSHI_HIP_OK : SUSHI_HIP_ELAUNCH; }
-
 // A kernel instantiated per method / per sample type: `f` launches it with the template argument it is given, as a
 // std::integral_constant / a null pointer of the sample type.
 template <typename F> int launch_method(int method, F&& f) {
@@ -15,8 +13,6 @@ template <typename F> int launch_dtype(int dtype, F&& f) {
     else f((uint8_t*)nullptr);
     return launch_ok();
 }
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 inline int64_t cand_capacity(int64_t pairs) {
     const int64_t want = pairs * 64;
@@ -325,8 +321,20 @@ struct BatchLayout { size_t desc, keys, flags, viol, flag_list, subc, tnorm, cou
 // (flags .. counters is ONE span of zeros at the start of a run: flags, violation marks, flag list, every sub-batch's small counters
 // (SUBC_BYTES each: SubCounters, then the `scount` words), the pattern rows' norm accumulators of the whole batch, the run's counters)
 constexpr size_t SUBC_BYTES = 256;
-constexpr int SUBC_SCOUNT = 8;          // int index inside a sub-batch's block: [0] survivors, [1] collect items, [2..3] band prediction votes, [4] dense whole rows, [5] pairs left after the second look, [6] listed pairs of the searches that would take the dense form
+constexpr int SUBC_SCOUNT = 8;          // int index inside a sub-batch's block of its first `scount` word
 static_assert(sizeof(SubCounters) <= SUBC_SCOUNT * sizeof(int), "the scount words lie behind the SubCounters");
+// The `scount` words of a sub-batch: list lengths and marks the kernels of a run count with (SubView names a pointer to each).
+enum ScountSlot {
+    SC_SLIST = 0,           // survivors: entries of slist
+    SC_CITEMS = 1,          // collect items: entries of citems (refine_kernel's list for collect_kernel)
+    // 2, 3: free
+    SC_ANY_DENSE = 4,       // dense whole rows: 1 where some search takes the dense form (dense_repack_kernel; enables that launch)
+    SC_SLIST2 = 5,          // pairs left after the second look: entries of slist2
+    SC_DENSE_LISTED = 6,    // listed pairs of the searches that would take the dense form
+    SC_LIST3 = 7,           // the threshold run's extension list
+    SC_WORDS = 8
+};
+static_assert((SUBC_SCOUNT + SC_WORDS) * sizeof(int) <= SUBC_BYTES, "the scount words fit the sub-batch's block");
 BatchLayout batch_layout(int n, int path, size_t n_order_ints, size_t n_item_ints, size_t ws_bytes, size_t n_subs, int64_t total_segs) {
     BatchLayout b;
     size_t o = 0;
@@ -353,14 +361,18 @@ struct SubView {
     int n_sub;
     uint32_t* tspec; uint4 *y, *tspec_low, *ylow, *dummy; unsigned long long* cand; TemplConsts* tconst; TileDesc* tiles; int32_t* candbuf;
     float *pair_lb, *slb, *acc, *tnorm_rest; unsigned char* audit_mark; SubCounters* sub; const int32_t *order, *items;
-    int *pairmap, *plist, *slist, *slist2, *votes, *dense_search, *ditems, *citems, *scount;
+    int *pairmap, *plist, *slist, *slist2, *votes, *dense_search, *ditems, *citems;
+    int *n_slist, *n_citems, *any_dense, *n_slist2, *n_dense_listed, *n_list3;     // the scount words (ScountSlot)
     SubView(char* mem, const BatchLayout& lay, size_t ws_lane, const SubBatch& s, size_t si) : sb(s), n_sub(s.b0 - s.a0) {
         const WsLayout w = ws_layout(s.pairs, s.segs, n_sub);
         char* p = mem + lay.ws + (size_t)s.lane * ws_lane;
         tspec = (uint32_t*)(p + w.tspec); y = (uint4*)(p + w.y); tspec_low = (uint4*)(p + w.tspec_low); ylow = (uint4*)(p + w.ylow); dummy = (uint4*)(p + w.dummy);
         cand = (unsigned long long*)(p + w.cand); tconst = (TemplConsts*)(p + w.tconst); tiles = (TileDesc*)(p + w.tiles); candbuf = (int32_t*)(p + w.candbuf);
         pair_lb = (float*)(p + w.pair_lb); slb = (float*)(p + w.slb); acc = (float*)(p + w.acc); tnorm_rest = (float*)(mem + lay.tnorm) + s.first_seg;
-        audit_mark = (unsigned char*)(p + w.audit_mark); sub = (SubCounters*)(mem + lay.subc + si * SUBC_BYTES); scount = (int*)sub + SUBC_SCOUNT;
+        audit_mark = (unsigned char*)(p + w.audit_mark); sub = (SubCounters*)(mem + lay.subc + si * SUBC_BYTES);
+        int* const scount = (int*)sub + SUBC_SCOUNT;
+        n_slist = scount + SC_SLIST; n_citems = scount + SC_CITEMS; any_dense = scount + SC_ANY_DENSE; n_slist2 = scount + SC_SLIST2;
+        n_dense_listed = scount + SC_DENSE_LISTED; n_list3 = scount + SC_LIST3;
         order = (const int32_t*)(mem + lay.order) + s.order_first;
         items = (const int32_t*)(mem + lay.items) + (size_t)s.item_first[0] * (1 + MAC_SPW);   // (its two item lists lie next to each other)
         pairmap = (int*)(p + w.pairmap); plist = (int*)(p + w.plist); slist = (int*)(p + w.slist); slist2 = (int*)(p + w.slist2);

@@ -109,7 +109,7 @@ void tspec_kernel(TspecArgs a) {
     const float t_scale = t_scale_for(tn_spec);
     if (s == 0) {
         const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, M);
-        int* __restrict__ pm = a.pairmap + (sd.first_pair - a.sub_first_pair);
+        int* __restrict__ pm = a.pairmap + first_pair_in_sub(a.sub_first_pair, sd);
         for (int i = tid; i < lay.n_pairs; i += FT) pm[i] = k;
         if (tid == 0) {
             const TemplStats ts = templ_stats(a.src_s1, a.src_s2, sd.tmpl_off, M, a.centre);

@@ -29,7 +29,7 @@ struct PairRunArgs {
     const int* pairmap;
     const uint32_t* rows;             // [pairs][THR_SLOT_WORDS] (the tile kernels' output)
     const float* slb;
-    unsigned char* audit_mark;        // bit 0 audited (excluded all the same), bit 1 evaluated; the run kinds' own bits: their kernels
+    unsigned char* audit_mark;        // MARK_* bits (sushi_internal.hpp): MARK_AUDITED, MARK_LISTED (= evaluated); the run kinds' own bits: their kernels
     int* viol;                        // [all searches]
     RunCounters* counters;
     int method;
@@ -71,7 +71,7 @@ void thr_check_kernel(ThrArgs a) {
     const int n = *a.list_count;
     for (int slot = blockIdx.x * 256 + threadIdx.x; slot < n; slot += gridDim.x * 256) {
         const int pr = a.list[slot];
-        const bool audit = (a.audit_mark[pr] & 1) != 0;
+        const bool audit = (a.audit_mark[pr] & MARK_AUDITED) != 0;
         // an audited pair was excluded: a hit in it is a violation whatever its margin
         audit_pair(a, pr, audit, [&](float) {
             if (!audit) return false;
@@ -88,9 +88,9 @@ __global__ __launch_bounds__(256)
 void thr_extend_kernel(ThrArgs a) {
     const int pr = blockIdx.x * 256 + threadIdx.x;
     bool add = false;
-    if (pr < a.n_pairs && a.viol[a.first_search + a.pairmap[pr]] && !(a.audit_mark[pr] & 2)) {
+    if (pr < a.n_pairs && a.viol[a.first_search + a.pairmap[pr]] && !(a.audit_mark[pr] & MARK_LISTED)) {
         add = true;
-        a.audit_mark[pr] |= 2;
+        a.audit_mark[pr] |= MARK_LISTED;
     }
     append_pairs(a.list3, a.list3_count, a.counters, add, pr);
 }
@@ -102,12 +102,12 @@ void thr_scan_kernel(ThrArgs a) {
     const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const SearchDesc sd = a.searches[k];
     const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
-    const int p0 = sd.first_pair - a.sub_first_pair;
+    const int p0 = first_pair_in_sub(a.sub_first_pair, sd);
     int running = 0;
     for (int base = 0; base < lay.n_pairs; base += 256) {
         const int i = base + tid;
         const int pr = p0 + i;
-        const bool evaluated = i < lay.n_pairs && (!a.audit_mark || (a.audit_mark[pr] & 2));
+        const bool evaluated = i < lay.n_pairs && (!a.audit_mark || (a.audit_mark[pr] & MARK_LISTED));
         int c = 0;
         if (evaluated) {
             const uint32_t* __restrict__ row = a.rows + (size_t)pr * THR_SLOT_WORDS;

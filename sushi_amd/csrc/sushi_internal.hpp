@@ -36,6 +36,12 @@ struct SushiHipStream {
 
 namespace sushi {
 
+// what every launcher returns after its last launch
+inline int launch_ok() { return hipGetLastError() == hipSuccess ? SUSHI_HIP_OK : SUSHI_HIP_ELAUNCH; }
+
+// sizes of device-memory parts are rounded up to 256 bytes
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
 // One search on the device: a SushiHipRequest plus the running sums that let a workgroup find its work.
 struct SearchDesc {
     int64_t tmpl_off;
@@ -48,6 +54,17 @@ struct SearchDesc {
     int32_t reserved;
 };
 static_assert(sizeof(SearchDesc) == 40, "SearchDesc layout");
+
+// FFT path: the pairs of a sub-batch are numbered from its first search's first pair (`sub_first_pair`: that pair's number in the
+// batch); `pr` is a pair of the sub-batch, `sd` its search.
+// pair `pr` as a pair of its search (0 .. n_pairs - 1)
+__host__ __device__ inline int pair_of_search(int sub_first_pair, int pr, const SearchDesc& sd) { return sub_first_pair + pr - sd.first_pair; }
+// the search's first pair as a pair of the sub-batch
+__host__ __device__ inline int first_pair_in_sub(int sub_first_pair, const SearchDesc& sd) { return sd.first_pair - sub_first_pair; }
+// pair `pr` on the absolute pair grid (fft_layout)
+__host__ __device__ inline int64_t absolute_pair(const FftLayout& lay, int sub_first_pair, int pr, const SearchDesc& sd) {
+    return lay.pair0 + (sub_first_pair + pr - sd.first_pair);
+}
 
 struct StreamRefs {
     const float* dst_xc; const double* dst_s1; const double* dst_s2; int64_t dst_len;
@@ -93,11 +110,11 @@ struct RunCounters {
 int direct_variant_count();
 int direct_variant_tile(int variant);
 
-// direct path: one launch of the MFMA kernel + unpack
+// direct path (sushi_direct.hip): one launch of the MFMA kernel + unpack
 int launch_direct(const StreamRefs& r, const SearchDesc* searches_dev, int n_search, int n_tiles, int variant, int method,
                   unsigned long long* keys_dev, int32_t* out_idx_dev, float* out_score_dev, int32_t* out_packed_dev, hipStream_t st);
 
-// FFT path, exact stages (sushi_hip.hip):
+// FFT path, exact stages (sushi_exact.hip):
 // refine: exact float64 evaluation of the listed candidates of searches [first_search, first_search + n_sub).
 // flags_dev[s] = 0 done / 1 needs tiles / 2 every position; flag_list_dev receives the flagged searches of this sub-batch.
 struct RefineParams {
@@ -139,6 +156,12 @@ struct TileParams {
     int method;                       // SUSHI_HIP_METHOD_*
 };
 int launch_tiles(const TileParams& p, hipStream_t st);
+
+// A pair's byte of a sub-batch's `audit_mark` array (FFT path: what the bound decided about the pair in this run), as bits:
+constexpr int MARK_AUDITED = 1;        // the bound had excluded the pair; it is transformed / evaluated all the same, as a check of the bound
+constexpr int MARK_LISTED = 2;         // the pair is listed: its row is formed, or (a listed-pair run) it is evaluated
+constexpr int MARK_SECOND_LOOK = 4;    // an audited pair that the second look (not the first bound) had excluded
+constexpr int MARK_BEST_FINAL = 8;     // a best-K run: an audited pair that best_final_kernel listed
 
 // FFT path, the listed-pair runs: threshold (sushi_hip_batch_run_threshold) and best-K (sushi_hip_batch_run_best;
 // DESIGN.md 3.11).  A listed block pair is evaluated exactly at each of its 2 FFT_H positions, as TILES_PER_PAIR tiles of TILE
@@ -187,7 +210,7 @@ constexpr int BEST_MAX_K = SUSHI_HIP_BEST_MAX_K;
 struct BestParams {
     ListedPairs lp;                   // (the list: best_tiles_kernel's)
     int n_sub;
-    const unsigned char* audit_mark;  // bit 1: the pair is evaluated; NULL: every pair is
+    const unsigned char* audit_mark;  // MARK_LISTED: the pair is evaluated; NULL: every pair is
     int has_threshold;
     double threshold;                 // eligible: score <= threshold (SQDIFF_NORMED) / >= threshold (CCOEFF_NORMED)
     unsigned long long tkey;          // the threshold in ranking units, rounded up, as a search key; NO_KEY: none

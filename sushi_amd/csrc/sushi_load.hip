@@ -14,10 +14,11 @@
 #include <stdint.h>
 
 #include "../../include/sushi_hip.h"
+#include "sushi_internal.hpp"
 
 namespace {
 
-inline int launch_ok() { return hipGetLastError() == hipSuccess ? SUSHI_HIP_OK : SUSHI_HIP_ELAUNCH; }
+using sushi::launch_ok;
 
 // wav.py:64-91 DownmixedWavFile.readframes for a run of frames: every channel's sample as int16 (24-bit samples keep
 // their top two bytes, wav.py:70-74) -> float32; channels summed left to right in float32 and divided by

@@ -23,6 +23,22 @@ def test_library_builds_and_exports_all_declared_symbols():
     assert exported == declared                      # nothing undeclared leaks out either
 
 
+def test_every_source_file_is_in_the_build_lists():
+    """A unit missing from build.UNITS is never compiled; a header or part missing from the dependency lists leaves a stale
+    library without an error when it is edited."""
+    names = set(os.listdir(build.CSRC))
+    units = {name + ".hip" for name, _flags, _extra in build.UNITS}
+    assert {f for f in names if f.endswith(".hip")} == units
+    deps = {os.path.abspath(p) for p in build.COMMON_DEPS}
+    for _name, _flags, extra in build.UNITS:
+        deps |= {os.path.abspath(p) for p in extra}
+    assert os.path.abspath(build.HEADER) in deps
+    written = sorted(f for f in names if f.endswith(".hpp") or (f.endswith(".inc") and not f.startswith("_gen_")))
+    assert len(written) >= 14                       # (the listing saw the directory: 5 headers and 9 parts of the FFT unit)
+    missing = [f for f in written if os.path.abspath(os.path.join(build.CSRC, f)) not in deps]
+    assert missing == []
+
+
 def test_host_only_entry_points():
     L = _native.lib()
     C = ctypes

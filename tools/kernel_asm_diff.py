@@ -1,17 +1,20 @@
 #!/usr/bin/env python3
-"""Which kernels of a translation unit compile to the same gfx950 code in two trees: the evidence a refactor needs before it
-carries profiles/pmc_traffic.json's source digest forward.  Every unit is compiled to device assembly with the flags of
+"""Which kernels compile to the same gfx950 code in two trees: the evidence a refactor needs before it carries
+profiles/pmc_traffic.json's source digest forward.  Every unit is compiled to device assembly with the flags of its tree's
 build.UNITS (`--cuda-device-only -S`; works without a GPU), cut into its functions, and the BODIES are compared -- from a
 function's label to its .Lfunc_end, with the function number of local labels (.LBB12_3) normalised, since a new helper renumbers
-them; data symbols, kernel descriptors and the metadata notes are left out.
+them; data symbols, kernel descriptors and the metadata notes are left out.  The functions of all units given are POOLED per tree
+and compared by name, so a kernel that moved to another unit is still compared with itself; of the units given, a tree compiles
+those its own build.UNITS has.  A name that occurs in two units of one tree is keyed `name [unit]`.
 
 usage: kernel_asm_diff.py A B UNIT [UNIT ...] [--show NAME]
   A, B    a directory that holds sushi_amd/ and include/ (a checkout, an export), or a commit (exported to a scratch copy);
           `.` is the working tree
-  UNIT    sushi_fft, sushi_curve, ... (build.UNITS)
+  UNIT    sushi_fft, sushi_curve, ... (build.UNITS of either tree)
   --show NAME   also print a unified diff of the bodies of the functions whose name contains NAME
 prints per function `same`, `differs` (with the bodies' line counts), `only in A`, `only in B`; exit status 1 if anything differs
 example: tools/kernel_asm_diff.py HEAD . sushi_fft sushi_curve"""
+import collections
 import argparse
 import difflib
 import os
@@ -47,6 +50,23 @@ def assembly(tree, unit, out):
             "                          '-Wall'] + flags + ['--cuda-device-only', '-S', b.CSRC + '/' + sys.argv[1] + '.hip', '-o', sys.argv[2]]))\n")
     subprocess.check_call([sys.executable, "-c", code, unit, out], cwd=tree)
     return open(out).read()
+
+
+def units_of(tree):
+    """The unit names of `tree`'s own build.UNITS."""
+    code = "from sushi_amd import build as b; print(' '.join(n for n, _, _ in b.UNITS))"
+    return subprocess.check_output([sys.executable, "-c", code], cwd=tree, text=True).split()
+
+
+def pooled(tree, units, scratch, tag):
+    """[(unit, name, body)] of every function of those of `units` that `tree` has."""
+    have = units_of(tree)
+    return [(unit, name, body) for unit in units if unit in have
+            for name, body in functions(assembly(tree, unit, os.path.join(scratch, "%s_%s.s" % (unit, tag)))).items()]
+
+
+def keyed(pool, by_unit):
+    return {("%s [%s]" % (name, unit) if name in by_unit else name): body for unit, name, body in pool}
 
 
 def demangle(names):
@@ -89,21 +109,23 @@ def main():
     differs = 0
     with tempfile.TemporaryDirectory(prefix="sushi_asm_diff_") as scratch:
         ta, tb = tree_of(args.a, scratch), tree_of(args.b, scratch)
-        for unit in args.units:
-            fa = functions(assembly(ta, unit, os.path.join(scratch, unit + "_a.s")))
-            fb = functions(assembly(tb, unit, os.path.join(scratch, unit + "_b.s")))
-            print("%s: %d functions in A, %d in B" % (unit, len(fa), len(fb)))
-            for name in sorted(set(fa) | set(fb)):
-                if name not in fb or name not in fa:
-                    verdict = "only in A" if name in fa else "only in B"
-                elif fa[name] == fb[name]:
-                    verdict = "same"
-                else:
-                    verdict = "differs (%d lines against %d)" % (len(fa[name]), len(fb[name]))
-                differs += verdict != "same"
-                print("  %-60s %s" % (name[:60], verdict))
-                if name in fa and name in fb and fa[name] != fb[name] and any(s in name for s in args.show):
-                    print("\n".join(difflib.unified_diff(fa[name], fb[name], "A", "B", lineterm="", n=2)))
+        pa, pb = pooled(ta, args.units, scratch, "a"), pooled(tb, args.units, scratch, "b")
+        # (a name in two units of one tree: keyed by its unit, in both trees)
+        by_unit = {name for pool in (pa, pb) for name, n in collections.Counter(name for _, name, _ in pool).items() if n > 1}
+        fa, fb = keyed(pa, by_unit), keyed(pb, by_unit)
+        for tag, pool in (("A", pa), ("B", pb)):
+            print("%s: %d functions in %s" % (tag, len(pool), ", ".join(sorted({unit for unit, _, _ in pool}))))
+        for name in sorted(set(fa) | set(fb)):
+            if name not in fb or name not in fa:
+                verdict = "only in A" if name in fa else "only in B"
+            elif fa[name] == fb[name]:
+                verdict = "same"
+            else:
+                verdict = "differs (%d lines against %d)" % (len(fa[name]), len(fb[name]))
+            differs += verdict != "same"
+            print("  %-60s %s" % (name[:60], verdict))
+            if name in fa and name in fb and fa[name] != fb[name] and any(s in name for s in args.show):
+                print("\n".join(difflib.unified_diff(fa[name], fb[name], "A", "B", lineterm="", n=2)))
     return 1 if differs else 0
 
 
