@@ -43,7 +43,8 @@ extern "C" {
                                      sushi_hip_batch_set_early_output, sushi_hip_device_prepare;
                                      13 (additive): sushi_hip_curve_bytes, sushi_hip_match_curves;
                                      13 (additive): SushiHipHit, sushi_hip_batch_run_threshold;
-                                     13 (additive): SUSHI_HIP_BEST_MAX_K, sushi_hip_batch_run_best */
+                                     13 (additive): SUSHI_HIP_BEST_MAX_K, sushi_hip_batch_run_best;
+                                     13 (additive): SushiHipRetimeSegment, sushi_hip_retime_bytes, sushi_hip_retime */
 
 #if defined(__GNUC__)
 #define SUSHI_HIP_API __attribute__((visibility("default")))
@@ -395,6 +396,39 @@ SUSHI_HIP_API size_t sushi_hip_curve_bytes(const SushiHipRequest* req_host, int 
 SUSHI_HIP_API int sushi_hip_match_curves(const SushiHipStream* dst, const SushiHipStream* src,
                                          const SushiHipRequest* req_host, int n, int method,
                                          void* mem_dev, size_t mem_bytes, float* out_dev, void* hip_stream);
+
+/* ---- retiming: a stream read at another speed (13, additive) -----------------------------------
+ * A source that plays faster or slower than the destination (PAL / NTSC: 25/24, 1001/960, 1001/1000 and their inverses) is put on
+ * the destination's clock by reading it at a rational step: linear interpolation, in an arithmetic stated to the bit.  A segment
+ * reads in_dev[in_start ...] at `num / den` input samples per output sample and writes out_len outputs from out_dev[out_off] on.
+ * Output i of a segment, 0 <= i < out_len:
+ *     t = i * num                          (int64)
+ *     j = in_start + t / den,  r = t % den,  j1 = min(j + 1, n_in - 1)
+ *     w = (double)r / (double)den
+ *     y = x[j] + w * (x[j1] - x[j])        (x[.] converted to double; the product and the sum round separately, no fused multiply-add)
+ *     SUSHI_HIP_F32: out = (float)y        SUSHI_HIP_U8: out = (uint8_t)(y + 0.5)
+ * so a NumPy float64 restatement equals the result bit for bit, and a step of 1 / 1 copies (uint8: always; float32: every finite
+ * sample but -0.0, which y = x + 0 * 0 turns into 0.0).  in_dev / out_dev: n_in / n_out samples of `dtype`, naturally aligned,
+ * not overlapping.  Output ranges of different segments that overlap are the caller's business: which segment's value such a
+ * sample ends with is not defined.  Samples of out_dev outside every segment are not written. */
+typedef struct SushiHipRetimeSegment {
+    int64_t in_start;   /* first input sample read */
+    int64_t out_off;    /* where the segment's outputs go in out_dev */
+    int64_t out_len;    /* outputs of this segment */
+    int32_t num, den;   /* input samples advanced per output sample = num / den */
+} SushiHipRetimeSegment;    /* 32 bytes */
+/* workspace a retime call needs (the segment table); 0 for n_seg <= 0 */
+SUSHI_HIP_API size_t sushi_hip_retime_bytes(int n_seg);
+/* One launch for the whole table (many short segments, or one of 10^8 samples).  No device allocation: the table is uploaded
+ * into mem_dev (256-byte aligned, >= sushi_hip_retime_bytes(n_seg)).  Asynchronous; stateless (any thread, own workspace).
+ * Checked before any HIP call -- EINVAL: a null pointer, an unknown dtype, n_seg < 1, n_in < 1, n_out < 1; a segment with num or
+ * den outside [1, 2^20], num / den outside [1/8, 8], out_len < 1 or >= 2^40, in_start < 0, a last read
+ * in_start + ((out_len - 1) * num) / den beyond n_in - 1, or outputs outside [0, n_out); EALIGN: mem_dev not 256-byte aligned
+ * (in_dev / out_dev not aligned to their sample type); ENOSPACE: mem_bytes too small. */
+SUSHI_HIP_API int sushi_hip_retime(const void* in_dev, int dtype, int64_t n_in,
+                                   const SushiHipRetimeSegment* seg_host, int n_seg,
+                                   void* out_dev, int64_t n_out,
+                                   void* mem_dev, size_t mem_bytes, void* hip_stream);
 
 /* ---- WavStream.__init__ on the GPU (wav.py:64-91 decode + downmix, wav.py:113-156 value pipeline) ----
  * sushi_hip_load_decode   : interleaved little-endian PCM frames (sample_width 2 or 3 bytes, `channels` per frame)

@@ -44,6 +44,9 @@ assert REQUEST_DTYPE.itemsize == 24
 # struct SushiHipHit, 8 bytes: one position of a threshold run (sushi_hip_batch_run_threshold) and its float32 score
 HIT_DTYPE = np.dtype([("index", "<i4"), ("score", "<f4")], align=True)
 assert HIT_DTYPE.itemsize == 8
+# struct SushiHipRetimeSegment, 32 bytes: one segment of a retime call (sushi_hip_retime)
+RETIME_SEGMENT_DTYPE = np.dtype([("in_start", "<i8"), ("out_off", "<i8"), ("out_len", "<i8"), ("num", "<i4"), ("den", "<i4")], align=True)
+assert RETIME_SEGMENT_DTYPE.itemsize == 32
 
 
 class BatchInfo(ctypes.Structure):
@@ -155,6 +158,10 @@ def lib():
     L.sushi_hip_curve_bytes.argtypes = [vp, ci]
     L.sushi_hip_match_curves.restype = ci
     L.sushi_hip_match_curves.argtypes = [vp, vp, vp, ci, ci, vp, sz, vp, vp]
+    L.sushi_hip_retime_bytes.restype = sz
+    L.sushi_hip_retime_bytes.argtypes = [ci]
+    L.sushi_hip_retime.restype = ci
+    L.sushi_hip_retime.argtypes = [vp, ci, i64, vp, ci, vp, i64, vp, sz, vp]
     L.sushi_hip_load_decode.restype = ci
     L.sushi_hip_load_decode.argtypes = [vp, i64, i32, i32, vp, vp]
     L.sushi_hip_load_resample.restype = ci

@@ -329,3 +329,40 @@ def calculate_shifts_batched(src_stream, dst_stream, groups_list, normal_window,
     proxy = SpeculativeStream(dst_stream, src_stream, groups_list, lookahead=lookahead, max_lookahead=max_lookahead)
     calculate_shifts(src_stream, proxy, groups_list, normal_window, max_window, rewind_thresh)
     return proxy
+
+
+def calculate_shifts_at_speed(src_stream, dst_stream, groups_list, speed, normal_window, max_window, rewind_thresh, batched=True):
+    """calculate_shifts for a source that plays `speed` times as fast as the destination (sushi_amd.retime: a source instant t lies
+    at t * speed on the destination's clock).  The source is put on the destination's clock (``src_stream.retimed(speed)``), every
+    event gets a shadow ``ScriptEvent(start * speed, end * speed)``, and the unmodified ``calculate_shifts_batched`` (or, with
+    batched=False, ``calculate_shifts``) runs on the shadows.  An original event e then gets the shift that carries it to where its
+    shadow landed, ``shadow.start + shadow.shift - e.start`` (formed as shadow.shift + (shadow.start - e.start), so that speed 1
+    leaves the shift as it is), and the shadow's diff; an event whose shadow was linked is linked to the original of the shadow's
+    target.  With speed 1 shifts and diffs are exactly the unmodified function's.  A linked event follows its target's SHIFT, as in
+    the reference; at a speed other than 1 that places it only approximately -- off by (speed - 1) * (e.start - target.start)
+    from where its own shadow would lie, 0.2 s for an event 5 s from its target at 25/24 (links are made only for groups past the
+    destination's end).  Returns what that function returns."""
+    from .retime import as_ratio
+    ratio = as_ratio(speed)
+    factor = ratio.numerator / float(ratio.denominator)
+    retimed = src_stream.retimed(ratio)
+    original = {}
+    shadow_groups = []
+    for group in groups_list:
+        shadows = []
+        for e in group:
+            sh = ScriptEvent(e.start * factor, e.end * factor, e.source_index, e.text, e.is_comment)
+            original[id(sh)] = e
+            shadows.append(sh)
+        shadow_groups.append(shadows)
+    if batched:
+        result = calculate_shifts_batched(retimed, dst_stream, shadow_groups, normal_window, max_window, rewind_thresh)
+    else:
+        result = calculate_shifts(retimed, dst_stream, shadow_groups, normal_window, max_window, rewind_thresh)
+    for shadows, group in zip(shadow_groups, groups_list):
+        for sh, e in zip(shadows, group):
+            if sh.linked:
+                e.link_event(original[id(sh._linked_event)])
+            else:
+                e.set_shift(sh.shift + (sh.start - e.start), sh.diff)
+    return result

@@ -500,3 +500,51 @@ class WavStream(object):
         if not as_tensor:
             curves = curves.cpu().numpy()
         return [curves[int(bounds[k]):int(bounds[k + 1])].reshape(1, -1) for k in range(n)]
+
+    # ------------------------------------------------------------------ another clock
+    def retimed(self, speed):
+        """This stream on the clock of a destination it plays `speed` times as fast as (sushi_amd.retime: 25/24 for PAL-sped-up
+        audio against a 24 fps destination): a new live WavStream whose instant t * speed is this one's instant t.  Same sample rate,
+        padding and sample type; the body has floor((sample_count - 1) * speed) + 1 samples, read from this row at a step of
+        1 / speed by linear interpolation (one segment from padding_size on; a read that touches the right pad sees the edge
+        value), and both pads are filled as the loader fills them.  On the GPU when there is one (sushi_hip_retime; the row stays
+        in HBM for the matching), else in NumPy -- bit for bit the same.  retimed(1) holds the same samples.  Patterns cut from the
+        result are ordinary views: every search method and SpeculativeStream take them as they are."""
+        from .retime import as_ratio, retime_device, retime_host, speed_segment
+        s = as_ratio(speed)
+        pad, count, total = int(self.padding_size), int(self.sample_count), int(self.data.shape[1])
+        if count < 1 or pad < 0 or pad + count > total:
+            raise SushiError('retimed: the stream has no body inside its row')
+        new_count = ((count - 1) * s.numerator) // s.denominator + 1
+        segment = [speed_segment(s, pad, pad, new_count)]
+        new = self.__class__.__new__(self.__class__)
+        new._dev_row = None
+        if self._use_gpu():
+            import torch
+            dev = torch_device("cuda" if self._device is None else self._device)
+            if self._dev is not None and self._dev.device == dev:
+                row = self._dev.raw
+            elif getattr(self, "_dev_row", None) is not None and self._dev_row.device == dev:
+                row = self._dev_row
+            else:
+                row = torch.from_numpy(self.data[0]).to(dev)
+            with torch.cuda.device(dev):
+                out = torch.empty(2 * pad + new_count, dtype=row.dtype, device=dev)
+                retime_device(row, segment, out=out)
+                if pad:
+                    out[:pad] = out[pad]
+                    out[pad + new_count:] = out[pad + new_count - 1]
+                new.data = out.cpu().numpy().reshape(1, -1)
+            new._dev_row = out
+        else:
+            out = np.zeros(2 * pad + new_count, self.data.dtype)
+            retime_host(self.data[0], segment, out=out)
+            if pad:
+                out[:pad] = out[pad]
+                out[pad + new_count:] = out[pad + new_count - 1]
+            new.data = out.reshape(1, -1)
+        new.sample_rate, new.sample_count, new.padding_size = self.sample_rate, new_count, self.padding_size
+        new._device = self._device
+        new._dev = None
+        _live_streams.add(new)
+        return new
