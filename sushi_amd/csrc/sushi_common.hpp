@@ -7,28 +7,10 @@
 #include <stdint.h>
 
 #include "../../include/sushi_hip.h"
+#include "sushi_geometry.hpp"      // the FFT_* / TILE constants, fft_layout, mac_class
 
 namespace sushi {
 
-// ---- overlap-save geometry ------------------------------------------------------------
-// Transform length N = 2^FFT_LOGN complex points; patterns are cut into segments of FFT_SEG samples, so a real
-// block of N samples yields FFT_H = N - FFT_SEG valid positions; two real blocks FFT_H apart are packed into one
-// complex block (a "pair": 2 * FFT_H positions per transform).  Spectra are kept at every multiple of FFT_SEG
-// ("block" j = samples from j * FFT_SEG on); consecutive pairs of a search are FFT_STEP blocks apart.
-constexpr int FFT_LOGN = 14;
-constexpr int FFT_N = 1 << FFT_LOGN;
-constexpr int FFT_SEG = 4096;
-constexpr int FFT_HOP = FFT_SEG;                   // also the block size of the relative window-energy prefix (urel / base)
-constexpr int FFT_VB = FFT_N / FFT_SEG - 1;        // valid blocks per half of a pair: 3
-constexpr int FFT_H = FFT_VB * FFT_SEG;            // result positions per half
-constexpr int FFT_STEP = 2 * FFT_VB;               // blocks between consecutive pairs
-constexpr int FFT_CAND = 8;                        // candidate slots per block pair (+ overflow marker + error bound + audit positions)
-constexpr int FFT_AUDIT = 4;                       // positions of an audit run: consecutive (one exact evaluation's worth of loads)
-constexpr int AUDIT_RUNS = 4;                      // audit runs a transformed pair leaves, and audit runs refine_kernel evaluates per search
-constexpr int FFT_ROW = 32;                        // 64-bit entries per pair in the candidate array: two 128-byte lines
-static_assert(FFT_CAND + 2 + AUDIT_RUNS * FFT_AUDIT <= FFT_ROW, "candidates, overflow marker, error bound, audit runs");
-constexpr int TILE = 1024;                         // positions per exact-evaluation tile (aligned to the absolute grid)
-constexpr int TILES_PER_PAIR = 2 * FFT_H / TILE;
 // error model of the f32 FFT stage: |corr_f32 - corr| <= FFT_KE * 2^-24 * |T| * |Z|, Z = the samples that enter the
 // pair's transforms (n_seg + 2 * FFT_VB blocks).  Calibrated: the largest ratio measured over the parity and property
 // tests is recorded by refine_kernel (diagnostics) and stays below FFT_KE / 3; a candidate whose exact score
@@ -226,32 +208,6 @@ __device__ __forceinline__ float score_ccoeff_at(double corr_c, const TemplStats
 __device__ __forceinline__ float score_exact(double corr_u, const TemplStats& t, const double* __restrict__ w2,
                                              int64_t p, int M) {
     return finish_sqdiff_normed(corr_u, w2[p + M] - w2[p], t.tU, t.tnorm);
-}
-
-// Overlap-save layout of one search (DESIGN.md "FFT path"): its block pairs sit on the ABSOLUTE pair grid (pair I
-// starts at block FFT_STEP * I), from the pair holding the window's first position to the one holding its last.
-struct FftLayout { int64_t pair0; int n_pairs; int n_seg; };
-__host__ __device__ inline FftLayout fft_layout(int64_t win_start, int n_pos, int tmpl_len) {
-    FftLayout l;
-    l.pair0 = (win_start / FFT_SEG) / FFT_STEP;
-    const int64_t pair_last = ((win_start + n_pos - 1) / FFT_SEG) / FFT_STEP;
-    l.n_pairs = (int)(pair_last - l.pair0 + 1);
-    l.n_seg = (tmpl_len + FFT_SEG - 1) / FFT_SEG;
-    return l;
-}
-
-// segment-count class of a search: the smallest SMAX (a multiple of FFT_STEP) that holds the whole pattern.  Classes
-// 0 .. MAC_SHORT_CLASSES-1 (up to 18 segments) run in mac_kernel, the others (up to 30: a 5 s pattern at 24 kHz, BASELINE
-// configs[4]'s longest) in mac_long_kernel, which keeps more pattern spectra per lane at a lower occupancy; still longer
-// patterns use the largest class and several chunks of its SMAX segments, the output accumulating.  (A sixth class of 36
-// segments made mac_long_kernel spill at its 256 registers: 144 of them were pattern spectra.)
-constexpr int MAC_CLASSES = 5;
-constexpr int MAC_SHORT_CLASSES = 3;
-__host__ __device__ constexpr int mac_class_smax(int c) { return FFT_STEP * (c + 1); }
-__host__ __device__ inline int mac_class(int n_seg) {
-    for (int c = 0; c < MAC_CLASSES - 1; ++c)
-        if (n_seg <= mac_class_smax(c)) return c;
-    return MAC_CLASSES - 1;
 }
 
 }  // namespace sushi

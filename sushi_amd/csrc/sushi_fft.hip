@@ -38,6 +38,9 @@
 // gfx950 only: wave64, 160 KiB LDS/CU.  No CUDA compatibility paths.
 //
 // ONE translation unit, cut by stage (every part is included below, inside this file's anonymous namespace):
+//   sushi_geometry.hpp     (a header: every unit's) the sizes and records host plan and device code agree on
+//   plan_core.hpp          (a header: host only, checked on the CPU by tests/host_plan_check.cpp) the plan of a batch, its
+//                          workspace and device-memory layouts, parse_bound_fault, ranking_key
 //   sushi_fft_store.inc    packed-half storage: scales, stored bin order, the low band of a row and the norms outside it
 //   sushi_fft_spectra.inc  spectra_kernel, tspec_kernel
 //   sushi_fft_mac.inc      mac_kernel / mac_long_kernel / mac_list_kernel
@@ -47,7 +50,7 @@
 //   sushi_fft_collect.inc  collect_kernel
 //   sushi_fft_threshold.inc  the threshold run's own kernels: seed, audit, extension, output scan
 //   sushi_fft_best.inc     the best-K run's own kernels: seed, escalation, audit, extension
-//   sushi_fft_plan.inc     host: workspace layout, stage timing, the plan of a batch
+//   sushi_fft_plan.inc     host: launches by method / sample type, stage timing, a sub-batch's view of the batch's memory (SubView)
 //   (this file)            the batch handle, the skeleton of a run around its sub-batches (run_sub_batches) and the C ABI's entry points
 
 #include <hip/hip_runtime.h>
@@ -72,6 +75,7 @@
 #include "sushi_internal.hpp"
 #include "fft_core.hpp"
 #include "mac_core.hpp"
+#include "plan_core.hpp"
 
 namespace {
 
@@ -182,7 +186,7 @@ struct SushiHipBatch {
     hipStream_t last_stream = nullptr;
     bool ran = false;
     hipEvent_t uploaded = nullptr;      // recorded on the create-time stream behind the descriptor / plan uploads
-    // lanes (sushi_fft_plan.inc): lane 0 is the stream a run is given; the others are the batch's own, forked off it behind the
+    // lanes (plan_core.hpp): lane 0 is the stream a run is given; the others are the batch's own, forked off it behind the
     // run's first launch and joined before its last
     hipStream_t lane_stream[MAX_LANES] = {};
     hipEvent_t lane_done[MAX_LANES] = {};
@@ -299,7 +303,7 @@ static int run_form(SushiHipBatch* b, unsigned run_seq, hipStream_t st0, RunForm
             // (the copies read the handle's own vectors: a re-plan and the destructor wait for this event before they touch them)
             if (hipEventRecord(b->uploaded, st0) != hipSuccess) return SUSHI_HIP_ELAUNCH;
         } else {
-            b->plan.whole_pending = false;                       // (cannot happen: the room was sized for it; the parts run one after the other then)
+            b->plan.whole_pending = false;                       // (on no case of tests/host_plan_check.cpp: the room was sized for it; the parts run one after the other then)
         }
     }
     const bool whole_cut = whole_rows_throughout && !b->plan.subs_whole.empty();
@@ -337,7 +341,7 @@ static int run_sub_batches(RunCtx& c, const hipStream_t st0, const RunKind kind,
     Lanes lanes(b, st0);
     if ((rc = lanes.fork(form.lanes)) != SUSHI_HIP_OK) return rc;
     if (kind == RUN_ARGMIN) b->last_band = -1;                   // (the form of the last sub-batch of this run that went through the exclusion)
-    // Sub-batches of a plan on lanes run side by side (sushi_fft_plan.inc "Lanes"); the others one after the other.
+    // Sub-batches of a plan on lanes run side by side (plan_core.hpp "Lanes"); the others one after the other.
     for (size_t si = 0; si < form.subs->size(); ++si) {
         const SubBatch& sb = (*form.subs)[si];
         if ((rc = per_sub(SubView(b->mem, b->lay, b->plan.ws_lane, sb, si), lanes.st[sb.lane])) != SUSHI_HIP_OK) return rc;
@@ -386,26 +390,6 @@ static int launch_slb(const RunCtx& c, const SubView& v, const BoundArgs& x, hip
         hipLaunchKernelGGL(slb_kernel<decltype(m)::value>, dim3((unsigned)((v.sb.pairs + 3) / 4)), dim3(256), 0, st, x); });
 }
 
-// SUSHI_HIP_TEST_BOUND_FAULT=<period>:<phase>[:<pair>] -- decimal digits only, period >= 1, 0 <= phase < period, pair >= 0, nothing
-// behind the last field; false: malformed
-static bool parse_bound_fault(const char* s, BoundFault* out) {
-    long field[3] = {0, 0, -1};
-    int n = 0;
-    for (;;) {
-        if (n == 3 || *s < '0' || *s > '9') return false;
-        char* end = nullptr;
-        field[n] = strtol(s, &end, 10);
-        if (field[n] > INT_MAX) return false;                     // (no sign was read: never negative; LONG_MAX on overflow)
-        ++n;
-        if (!*end) break;
-        if (*end != ':') return false;
-        s = end + 1;
-    }
-    if (n < 2 || field[0] < 1 || field[1] >= field[0]) return false;
-    out->period = (int)field[0]; out->phase = (int)field[1]; out->pair = n == 3 ? (int)field[2] : -1;
-    return true;
-}
-
 // the tests' seam: the stored bounds of the batch's faulted pairs read +inf from here on (bound_fault_kernel); called behind every
 // launch that writes slb, and only by a batch that carries a fault
 static int launch_bound_fault(const RunCtx& c, const SubView& v, hipStream_t st) {
@@ -426,7 +410,6 @@ static int decide_band(const RunCtx& c, const SubView& v, hipStream_t st, int* b
     SushiHipBatch* b = c.b;
     const bool chosen = b->exclusion == SUSHI_HIP_EXCLUDE_BAND || b->exclusion == SUSHI_HIP_EXCLUDE_WHOLE;   // (by the caller)
     if (!chosen && (b->band < 0 || b->band_decided_method != b->method)) {
-        static_assert(VOTE_SLOTS * VOTE_STRIDE == 64 * 32, "ws_layout keeps room for the prediction's counters");
         int slots[VOTE_SLOTS * VOTE_STRIDE];
         if (hipMemsetAsync(v.votes, 0, sizeof(slots), st) != hipSuccess) return SUSHI_HIP_ELAUNCH;
         BoundArgs bp = bound_args(c, v);
@@ -671,19 +654,6 @@ static int run_sub(RunCtx& c, const SubView& v, hipStream_t st) {
 }
 
 // ---- the listed-pair runs (threshold, best-K): what their sub-batches share ----
-// a threshold in ranking units (what the bound is a lower bound of: the score, 1 - the coefficient), rounded UP to a float, as a
-// search key: a pair is excluded only if its bound is above it (bound_excludes, with its slack).  `clamp_at_zero`: never below 0 --
-// no ranking score is, and the best-K run orders these keys as unsigned numbers.
-static unsigned long long ranking_key(const int method, const double threshold, const bool clamp_at_zero) {
-    double u = method == SUSHI_HIP_METHOD_CCOEFF_NORMED ? 1.0 - threshold : threshold;
-    if (clamp_at_zero) u = std::max(0.0, u);
-    float uf = (float)u;
-    if (std::isfinite(uf) && (double)uf < u) uf = std::nextafter(uf, INFINITY);
-    uint32_t ubits;
-    memcpy(&ubits, &uf, sizeof(ubits));
-    return ((unsigned long long)ubits << 32) | 0xffffffffull;
-}
-
 // what the tile kernels read (sushi_curve.hip): every pair of the sub-batch in the L2-friendly schedule, until a list replaces it
 static ListedPairs listed_pairs(const RunCtx& c, const SubView& v) {
     ListedPairs lp;
@@ -899,7 +869,8 @@ struct PlanCache {
     Plan plan;
 };
 static thread_local PlanCache g_plan_cache;
-static std::string lanes_env_now() { const char* e = getenv("SUSHI_HIP_LANES"); return e ? std::string(e) : std::string(); }
+// SUSHI_HIP_LANES, read once per ABI call: the planner and the cache's key get the same value
+static std::string lanes_override_now() { const char* e = getenv("SUSHI_HIP_LANES"); return e ? std::string(e) : std::string(); }
 
 size_t sushi_hip_batch_bytes(const SushiHipRequest* req_host, int n, int path, int variant, size_t workspace_cap_bytes) try {
     if (!req_host || n <= 0 || (path != SUSHI_HIP_PATH_FFT && path != SUSHI_HIP_PATH_DIRECT)) return 0;
@@ -908,13 +879,14 @@ size_t sushi_hip_batch_bytes(const SushiHipRequest* req_host, int n, int path, i
     if (variant >= direct_variant_count()) return 0;
     std::vector<SearchDesc> descs;
     int64_t tiles;
-    if (make_descs(req_host, n, variant, descs, &tiles) != SUSHI_HIP_OK) return 0;
+    if (make_descs(req_host, n, direct_variant_tile(variant), descs, &tiles) != SUSHI_HIP_OK) return 0;
     if (path == SUSHI_HIP_PATH_DIRECT) return batch_layout(n, path, 0, 0, 0, 0, 0).total;
     Plan plan;
-    if (make_plan(descs, workspace_cap_bytes, plan) != SUSHI_HIP_OK) return 0;
+    std::string lanes = lanes_override_now();
+    if (make_plan(descs, workspace_cap_bytes, lanes.c_str(), plan) != SUSHI_HIP_OK) return 0;
     const size_t total = batch_layout(n, path, plan.order.size(), plan.items.size(), plan.ws_bytes, plan.subs.size(), plan.segs).total;
     PlanCache& pc = g_plan_cache;
-    pc.valid = true; pc.cap = workspace_cap_bytes; pc.lanes_env = lanes_env_now();
+    pc.valid = true; pc.cap = workspace_cap_bytes; pc.lanes_env = std::move(lanes);
     pc.req.assign(req_host, req_host + n);
     pc.plan = std::move(plan);
     return total;
@@ -925,7 +897,7 @@ size_t sushi_hip_batch_bytes(const SushiHipRequest* req_host, int n, int path, i
 static int plan_and_upload(SushiHipBatch* b, const SushiHipRequest* req_host, int n, hipStream_t st) {
     std::vector<SearchDesc> descs;
     int64_t n_tiles = 0;
-    int rc = make_descs(req_host, n, b->variant, descs, &n_tiles);
+    int rc = make_descs(req_host, n, direct_variant_tile(b->variant), descs, &n_tiles);
     if (rc != SUSHI_HIP_OK) return rc;
     double flops = 0.0, abytes = 0.0;
     const double width = b->dst->dtype == SUSHI_HIP_F32 ? 4.0 : 1.0;
@@ -938,12 +910,13 @@ static int plan_and_upload(SushiHipBatch* b, const SushiHipRequest* req_host, in
     Plan plan;
     if (b->path == SUSHI_HIP_PATH_FFT) {
         PlanCache& pc = g_plan_cache;
+        const std::string lanes = lanes_override_now();
         if (pc.valid && pc.cap == b->ws_cap && (int)pc.req.size() == n && memcmp(pc.req.data(), req_host, (size_t)n * sizeof(SushiHipRequest)) == 0 &&
-            pc.lanes_env == lanes_env_now()) {
+            pc.lanes_env == lanes) {
             plan = std::move(pc.plan);                      // (the plan sushi_hip_batch_bytes made for these very requests)
             pc.valid = false;
         } else {
-            rc = make_plan(descs, b->ws_cap, plan);
+            rc = make_plan(descs, b->ws_cap, lanes.c_str(), plan);
             if (rc != SUSHI_HIP_OK) return rc;
         }
     }

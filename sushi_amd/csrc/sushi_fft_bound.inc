@@ -22,7 +22,6 @@
 // transformed as before; all others are done: slb > U means every exact score of the pair is above the exact score of a position
 // already found.  (U >= 1 -- nothing matches anywhere, every score clamps to 1 and TIES -- excludes nothing.)
 // ------------------------------------------------------------------------------------------
-constexpr int VOTE_SLOTS = 64, VOTE_STRIDE = 32;      // the prediction's counters: 64 pairs of ints, 128 bytes apart
 struct BoundArgs {
     const uint2* y;
     const double* dst_stats;
@@ -410,7 +409,6 @@ void slb_list_kernel(BoundArgs a) {
 // search whose batch-wide index g has g % period == phase, becomes +inf: "no score of this pair can be any good".  A kernel
 // of its own, launched behind slb_kernel and slb_list_kernel only by a batch that carries a fault (period > 0): without the
 // variable no launch, no argument and no kernel differs.
-struct BoundFault { int period = 0, phase = 0, pair = -1; };
 struct BoundFaultArgs {
     const SearchDesc* searches;       // the sub-batch's searches
     const int* pairmap;

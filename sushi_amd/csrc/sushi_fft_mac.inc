@@ -12,12 +12,6 @@
 // What bounds the kernel is the bytes a CU's L1 passes (~10 B per clock): with every operand a packed half a byte through
 // the L1 feeds twice the multiply-adds it fed as float32, and they are two to an instruction.
 // ------------------------------------------------------------------------------------------
-constexpr int MAC_SPW = 8;                       // searches per wave
-constexpr int MAC_BPW = 64 / MAC_SPW;            // 4-bin entries per wave
-constexpr int MAC_WAVES = 4;
-constexpr int MAC_THREADS = MAC_WAVES * 64;
-constexpr int MAC_BW = MAC_BPW * MAC_WAVES;      // entries per workgroup
-
 struct MacArgs {
     const uint4* spec;                // destination spectra, as 4-bin entries of packed halves
     int64_t spec_blocks;              // blocks of the stream; block `spec_blocks` is all zero
@@ -34,9 +28,6 @@ struct MacArgs {
     const int* enable;                // NULL, or a device flag: 0 = this launch is not needed (every workgroup leaves at once)
 };
 
-constexpr int MAC_DUMMY_LINES = 1024;
-constexpr int MAC_CHUNKS = ROWE / MAC_BW;
-static_assert(MAC_CHUNKS % 8 == 0, "every XCD owns the same number of bin chunks");
 constexpr int MAC_ZR = 6;                        // rows per load instruction: divides every SMAX
 
 __device__ __forceinline__ int wave_min_i32(int v) {

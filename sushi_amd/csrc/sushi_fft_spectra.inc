@@ -49,21 +49,6 @@ __device__ __forceinline__ int find_search_by_seg(const SearchDesc* __restrict__
     return lo;
 }
 
-// per-search constants of the f32 scoring epilogue, computed once (float64) by tspec_kernel
-struct TemplConsts {
-    double tU;           // sum T^2 (uncentred)
-    float inv_tnorm;     // 1 / sqrt(sum T^2)
-    float tnorm;         // sqrt(sum T^2)
-    // TM_CCOEFF_NORMED (cv2's numType == 1 statistics, sushi_common.hpp templ_stats)
-    float tmean;         // mean T
-    float inv_tnorm_c;   // 1 / sqrt(sum (T - mean T)^2); 0 for a flat pattern
-    float inv_m;         // 1 / M
-    int flat;            // the pattern has no variance: cv2's result is all ones
-    float c_sum_t;       // c * sum T: sum T I = y' + c_sum_t (block spectra are of the centred destination samples)
-    float inv_scale;     // 1 / the power-of-two scale of this search's stored products Y
-    float mac_scale;     // what mac_kernel multiplies its float32 sums by when it stores them: scale of Y / (scale of Tt * scale of Z)
-};
-
 // ------------------------------------------------------------------------------------------
 // Pattern-segment spectra: Tt = conj(DFT(t_s zero padded)) / N, stored as the packed halves (Re Tt, -Im Tt) mac_kernel's
 // dot products take (mac_core.hpp) -- the scaled forward transform itself.  The workgroup of a search's first
@@ -77,7 +62,7 @@ struct TspecArgs {
     int sub_first_pair;
     uint32_t* tspec;                  // [segments of the sub-batch][FN] packed halves
     int* pairmap;                     // [pairs of the sub-batch] -> search index inside the sub-batch
-    struct TemplConsts* tconst;       // [searches of the sub-batch]
+    TemplConsts* tconst;      // [searches of the sub-batch]
     const double* src_s1;
     const double* src_s2;
     double centre;

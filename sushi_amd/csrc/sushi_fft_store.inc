@@ -51,13 +51,8 @@ __device__ __forceinline__ float add_abs2_entry(const sushi_fft::uint4v e, float
     acc = __builtin_amdgcn_fdot2(v.s45, v.s45, acc, false);
     return __builtin_amdgcn_fdot2(v.s67, v.s67, acc, false);
 }
-constexpr int ROW_BYTES = FN * 4;              // a stored spectrum: one 32-bit word per bin
-constexpr int ROWE = FN / sushi_mac::BINS;     // ... as 16-byte entries (four bins: what a lane of mac_kernel owns)
+static_assert(ROWE == FN / sushi_mac::BINS && LROWE == sushi_fft::LB_ENTRIES, "sushi_geometry.hpp's rows are mac_core's lanes and fft_core's low band");
 constexpr float Y_KQ = 8.0f;                  // the quantisation term of a pair's bound, in standard deviations
-// The low band of every spectrum (bins |f| < N/8) is kept a second time, as rows of LROWE entries in the order bound_low_kernel
-// loads them (fft_core.hpp "LOW BAND"): the band-split exclusion multiplies, stores and transforms only these.
-constexpr int LROWE = sushi_fft::LB_ENTRIES;   // 16-byte entries of a low row
-constexpr int LROW_BYTES = LROWE * 16;
 static_assert(FFT_LOGN == 14 && sushi_fft::W_LDS_FLOATS <= LDS_FLOATS && FT == sushi_fft::WNT, "the wave plan is the 16384-point inverse");
 
 // Spectra are STORED in the order the inverse transform loads them (fft_core.hpp "Wave plan": wslot_of_bin): block

@@ -39,22 +39,6 @@ namespace sushi {
 // what every launcher returns after its last launch
 inline int launch_ok() { return hipGetLastError() == hipSuccess ? SUSHI_HIP_OK : SUSHI_HIP_ELAUNCH; }
 
-// sizes of device-memory parts are rounded up to 256 bytes
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-// One search on the device: a SushiHipRequest plus the running sums that let a workgroup find its work.
-struct SearchDesc {
-    int64_t tmpl_off;
-    int64_t win_start;
-    int32_t tmpl_len;
-    int32_t n_pos;
-    int32_t first_tile;   // direct path: tiles of the searches before this one
-    int32_t first_pair;   // FFT path: block pairs of the searches before this one
-    int32_t first_seg;    // FFT path: pattern segments of the searches before this one
-    int32_t reserved;
-};
-static_assert(sizeof(SearchDesc) == 40, "SearchDesc layout");
-
 // FFT path: the pairs of a sub-batch are numbered from its first search's first pair (`sub_first_pair`: that pair's number in the
 // batch); `pr` is a pair of the sub-batch, `sd` its search.
 // pair `pr` as a pair of its search (0 .. n_pairs - 1)
@@ -71,40 +55,6 @@ struct StreamRefs {
     const float* src_xc; const double* src_s1; const double* src_s2; int64_t src_len;
     double centre;
     const void* dst_raw; const void* src_raw; int dtype;     // the samples as they are (exact evaluation)
-};
-
-// One exact-evaluation work item: TILE consecutive positions of one search, aligned to the absolute grid.
-constexpr int SPARSE_TILE_MAX = 256;   // candidates per tile up to which collect_kernel lists them; beyond: every position of the tile
-constexpr int SPARSE_UNIT = 64;        // a listed tile is handed to exact_tiles_kernel in entries of at most this many candidates
-struct TileDesc {
-    int32_t search;       // global search index
-    int32_t p0;           // first position of the tile relative to the search's window (may be < 0 for the first tile)
-    int32_t off;          // sparse: first entry of the tile's candidate list in the candidate buffer
-    int32_t cnt;          // sparse: candidates of this entry (<= SPARSE_UNIT: a tile of more is several entries); dense (every valid position of the tile): -1
-};
-
-// Counters of one run, in device memory (zeroed at the start of a run).
-// What the exact stages of ONE sub-batch count with: every sub-batch of a plan has its own (sub-batches of a batch may run side by
-// side on several HIP streams: sushi_fft.hip "lanes"); cleared by the run's first launch.
-struct SubCounters {
-    int32_t n_tiles;          // entries of the tile list
-    int32_t tile_next;        // exact_tiles_kernel's queue: the next entry to hand out
-    int32_t n_cand;           // entries of the candidate buffer
-    int32_t sub_flagged;      // searches of this sub-batch refine_kernel flagged (entries of its part of the flag list)
-};
-
-struct RunCounters {
-    int32_t n_flagged;        // searches refine_kernel could not finish from the per-pair lists
-    int32_t n_all_positions;  // of those: every position (bound violated)
-    unsigned long long tiles_dense, tiles_sparse, candidates;    // totals of the run
-    uint32_t max_ratio_bits;  // float bits of SushiHipBatchDiag.max_bound_ratio
-    uint32_t max_ratio_audit_bits;  // float bits of SushiHipBatchDiag.max_bound_ratio_noncandidate
-    unsigned long long audited;     // non-candidate positions evaluated exactly (SushiHipBatchDiag.audited)
-    unsigned long long pairs_transformed;   // block pairs whose inverse transform was run (the others were excluded by bound_kernel's bound)
-    unsigned long long excluded_audited;    // of those: pairs the bound HAD excluded, transformed as a check of the bound
-    uint32_t max_slb_ratio_bits;            // float bits: largest (lower bound / upper bound of the pair's real best score) over the audited excluded pairs
-    int32_t slb_violations;                 // pairs whose lower bound turned out above a real score (their searches go to every position)
-    unsigned long long second_look_audited; // of excluded_audited: pairs the second look had excluded (survivor2_kernel's sample)
 };
 
 int direct_variant_count();

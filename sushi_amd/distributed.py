@@ -12,11 +12,11 @@ import torch
 import torch.distributed as dist
 
 
-FFT_SEG, FFT_STEP = 4096, 6          # csrc/sushi_common.hpp: samples per block / pattern segment, blocks between block pairs
+FFT_SEG, FFT_STEP = 4096, 6          # csrc/sushi_geometry.hpp: samples per block / pattern segment, blocks between block pairs
 
 
 def fft_layout_host(win_start, n_pos, tmpl_len):
-    """(block pairs, pattern segments) of each request on the FFT path: sushi_common.hpp fft_layout in NumPy -- the block
+    """(block pairs, pattern segments) of each request on the FFT path: sushi_geometry.hpp fft_layout in NumPy -- the block
     pairs of a search sit on the absolute pair grid, from the pair holding its first position to the one holding its last.
     No library, no GPU (tests/test_distributed_cpu.py holds it to sushi_hip_fft_layout)."""
     ws = np.asarray(win_start, dtype=np.int64).reshape(-1)

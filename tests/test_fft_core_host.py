@@ -53,7 +53,7 @@ def test_overlap_save_formulation_matches_definition(oracle, ratio):
     """NumPy model of the FFT path's block arithmetic (packing of two real blocks H = N - B apart into one complex
     block, segmenting of patterns, the absolute pair grid, which output goes where) against the definition, for
     N = 2 B (one valid block per half) and N = 4 B (three: the product's geometry).  The HIP kernels implement exactly
-    this layout (csrc/sushi_common.hpp fft_layout)."""
+    this layout (csrc/sushi_geometry.hpp fft_layout)."""
     B = 256
     N = ratio * B
     H = N - B

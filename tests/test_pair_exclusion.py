@@ -430,7 +430,7 @@ def test_worst_case_and_statistical_bounds_give_the_same_results(oracle):
 @pytest.mark.parametrize("method", ["sqdiff_normed", "ccoeff_normed"])
 @pytest.mark.parametrize("lanes", ["6:3", "5:2", "4:4", "7:1"])
 def test_sub_batches_side_by_side_on_lanes_give_the_same_bits(monkeypatch, oracle, method, lanes):
-    """A large batch is cut into sub-batches that run side by side on HIP streams of the batch's own (sushi_fft_plan.inc "Lanes",
+    """A large batch is cut into sub-batches that run side by side on HIP streams of the batch's own (plan_core.hpp "Lanes",
     SushiHipBatchInfo.lanes): every sub-batch has its own counters and every lane its own workspace, so the results are the bits of
     the one-sub-batch run -- on the first run (which decides the exclusion's form on lane 0 while the others wait for nothing but
     the fill), on the runs after it (a run's first launch must wait for ALL lanes of the run before), and on a lane that carries
