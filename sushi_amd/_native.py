@@ -24,6 +24,7 @@ VIEW_XC, VIEW_S1, VIEW_S2, VIEW_UREL, VIEW_BASE, VIEW_SPECTRA, VIEW_USREL, VIEW_
     VIEW_ZNORM_REST = range(11)
 
 ABI_VERSION = 13
+ENOSPACE = -4              # SUSHI_HIP_ENOSPACE: buffer or workspace too small
 NSTAGES = 6
 STAGE_NAMES = ("tspec", "mac", "ifft", "refine", "finish", "bound")
 STAGE_KERNELS = {"tspec": "tspec_kernel", "mac": "mac_kernel", "ifft": "mac_list_kernel+mac_rows_kernel+ifft_kernel", "refine": "refine_kernel",

@@ -4,7 +4,8 @@ The translation units, compiled separately (the direct MFMA kernel alone takes ~
   csrc/sushi_direct.hip direct path: the MFMA kernel and its launcher   (-ffp-contract=off)
   csrc/sushi_exact.hip  FFT path's exact stages (refinement, tiles), unpack and fill kernels   (-ffp-contract=off)
   csrc/sushi_stream.hip stream preparation (prefix sums) and the stream C ABI   (-ffp-contract=off)
-  csrc/sushi_fft.hip  overlap-save FFT path (its parts: csrc/sushi_fft_*.inc; the plan of a batch: csrc/plan_core.hpp, host only)
+  csrc/sushi_fft.hip  overlap-save FFT path (its parts: csrc/sushi_fft_*.inc; the plan of a batch: csrc/plan_core.hpp, what a run decides:
+                      csrc/run_policy.hpp, both host only)
   csrc/sushi_load.hip WavStream load pipeline (decimate / pad / median clip / scale / quantise)  (-ffp-contract=off)
   csrc/sushi_curve.hip whole score curves: i8 MFMA Toeplitz GEMM (uint8), canonical float64 chain (float32)  (-ffp-contract=off);
                        the same tiles (csrc/curve_tiles.hpp) evaluate the listed pairs of a threshold run and of a best-K run
@@ -38,7 +39,7 @@ UNITS = [
     # -fno-slp-vectorize: the SLP pass packs the complex MACs into v_pk_fma_f32 and pays for it in
     # register shuffles (v_mov / accvgpr traffic); plain v_fma_f32 already issues at the f32 peak rate.
     ("sushi_fft", ["-fno-slp-vectorize"],
-     [os.path.join(CSRC, "fft_core.hpp"), os.path.join(CSRC, "mac_core.hpp"), os.path.join(CSRC, "plan_core.hpp"), TWIDDLE_INC, os.path.join(CSRC, "_gen_dft16_f16.inc"),
+     [os.path.join(CSRC, "fft_core.hpp"), os.path.join(CSRC, "mac_core.hpp"), os.path.join(CSRC, "plan_core.hpp"), os.path.join(CSRC, "run_policy.hpp"), TWIDDLE_INC, os.path.join(CSRC, "_gen_dft16_f16.inc"),
       # the translation unit's parts, by stage (included inside its anonymous namespace)
       os.path.join(CSRC, "sushi_fft_store.inc"), os.path.join(CSRC, "sushi_fft_spectra.inc"), os.path.join(CSRC, "sushi_fft_mac.inc"),
       os.path.join(CSRC, "sushi_fft_ifft.inc"), os.path.join(CSRC, "sushi_fft_bound.inc"), os.path.join(CSRC, "sushi_fft_collect.inc"),

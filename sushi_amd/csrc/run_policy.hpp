@@ -1,0 +1,149 @@
+// sushi_amd/csrc/run_policy.hpp -- what a run of the FFT path DECIDES, host only: no HIP header, no environment, no globals.
+// Every rule is a function of the exclusion mode, the method, a few counts and what earlier runs left behind; sushi_fft.hip makes
+// the HIP calls around them (the event query, the vote's read-back, the uploads, the launches).  Built with plain g++ by
+// tests/host_policy_check.cpp, which states the rules as checks on the CPU; sushi_fft.hip includes the same file.
+//   Learnt                        what a batch has learnt about its searches
+//   LastRun                       what its last run was (what the diagnostics entry points read)
+//   absorb_counts, run_suspended  AUTO suspends an exclusion that excludes next to nothing, and looks again
+//   whole_rows_throughout, takes_whole_cut, run_lanes     which cut of the plan a run takes, on how many lanes
+//   sub_excludes, listed_run_excludes                     does a sub-batch go through the exclusion
+//   vote_due, decide_form, exclusion_form                 band-split or whole rows
+//   direct_slots                  slots of a listed transform that get a workgroup each
+//   begin_run, report_last_run    what a handle remembers of a run, what each run kind reports
+#ifndef SUSHI_RUN_POLICY_HPP
+#define SUSHI_RUN_POLICY_HPP
+
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "sushi_geometry.hpp"
+
+namespace sushi {
+
+enum RunKind { RUN_ARGMIN, RUN_THRESHOLD, RUN_BEST };
+
+// What the batch has learnt about its searches (a new plan: about other searches now).
+struct Learnt {
+    int band = -1;                      // the exclusion's form in AUTO / ALWAYS: -1 not decided yet, 0 whole rows (bound_kernel), 1 band-split
+    int band_decided_method = -1;       // ... which was decided for this method (the pattern spectra differ)
+    int band_votes[2] = {0, 0};         // what the decision was taken from: pairs looked at, pairs whose bound leaves room
+    // AUTO learns from its own runs: a batch whose exclusion excluded next to nothing (searches without a match anywhere) runs
+    // without it from then on, looking again every 64th run.
+    int suspended = 0;                  // 1: the exclusion is left out (AUTO)
+    unsigned suspended_at = 0;          // run_seq of the run that showed it
+    unsigned long long last_transformed = 0;    // pairs the last finished run transformed (0: not known): sizes the next run's one-workgroup-per-slot launch
+    void forget() { *this = Learnt(); }
+};
+
+// What the last run was.
+struct LastRun {
+    RunKind kind = RUN_ARGMIN;          // (a best-K run's flags words hold, per search, the last round that evaluated a pair of it)
+    int band = -1;                      // form of the exclusion it used (its last sub-batch that went through it; -1: none did)
+    bool whole_cut = false;             // it took the plan's one-sub-batch cut (Plan::subs_whole)
+    bool suspended = false;             // it was one of the runs AUTO leaves the exclusion out of
+    int64_t direct_pairs = 0;           // pairs of its sub-batches that were transformed without the exclusion
+    bool ran = false;
+};
+
+// (three quarters: a batch HALF of whose searches find nothing -- a dub -- still gains from the exclusion on the other half)
+constexpr double SUSPEND_LEFT_SHARE = 0.75;
+// (suspended: every 64th run looks again)
+constexpr unsigned LOOK_AGAIN_MASK = 63u;
+// The exclusion costs a pass over Y (~16 ns per pair) and half a dozen launches (~60 us); transforming a pair ~37 ns:
+// it pays from ~3000 pairs on, plus two per search (the pairs transformed first are transformed either way).
+constexpr int64_t EXCLUDE_FROM_PAIRS = 3000, EXCLUDE_PAIRS_PER_SEARCH = 2;
+// (measured at BASELINE configs[2]: 97 % of the pairs vote for it at 12 dB of noise on the source -- 9.7 ms against 17.5 for
+// the whole-row form --, 87 % at 6 dB -- 12.5 against 17.5 --, 14 % at 0 dB -- 28.7 against 18.7)
+constexpr double BAND_VOTE_SHARE = 0.75;
+// One workgroup per list slot up to what the list usually holds (an eighth of the pairs: empty slots there cost a
+// workgroup's launch each, ~1 ns), and a fixed grid striding over whatever lies beyond: the striding form alone runs
+// at half the rate per pair (the loop costs it registers), one workgroup per POSSIBLE slot cost 0.3 ms of empty launches.
+constexpr int64_t DIRECT_SLOTS_MIN = 4096, DIRECT_USUAL_PART = 8;
+// (nothing known yet -- a batch's first run, which is all a one-shot job has --: half of the pairs get a workgroup each;
+// 0.15 ms of empty launches where there is a match everywhere, against half the rate on ten times as many pairs where
+// there is not: a dub's first run 29.7 ms)
+constexpr int64_t DIRECT_FIRST_RUN_PART = 2;
+
+// The counts of a finished run (pairs transformed, excluded pairs audited), read by run `run_seq` of a plan of `plan_pairs`.
+inline void absorb_counts(Learnt& l, int exclusion, unsigned run_seq, unsigned long long transformed, unsigned long long audited,
+                          int64_t plan_pairs) {
+    const unsigned long long left = transformed - audited;
+    l.last_transformed = transformed;
+    if (exclusion == SUSHI_HIP_EXCLUDE_AUTO) {
+        if ((double)left > SUSPEND_LEFT_SHARE * (double)plan_pairs) { if (!l.suspended) l.suspended_at = run_seq; l.suspended = 1; }
+        else l.suspended = 0;
+    }
+}
+
+// Does AUTO leave the exclusion out of run `run_seq`.
+inline bool run_suspended(const Learnt& l, int exclusion, unsigned run_seq) {
+    return exclusion == SUSHI_HIP_EXCLUDE_AUTO && l.suspended && ((run_seq - l.suspended_at) & LOOK_AGAIN_MASK) != LOOK_AGAIN_MASK;
+}
+
+// The lanes: the batch's own streams start behind the fill, the caller's stream goes on behind them.  Side by side pays
+// where the stages differ in what bounds them -- the band-split form; whole rows for every pair (the whole-row form, no
+// exclusion at all) are HBM traffic from the first kernel to the last and only contend: those runs keep their sub-batches on
+// the caller's stream, one after the other (measured at BASELINE configs[2]: unrelated audio 25.1 ms on one stream, 26.8 side by side).
+inline bool whole_rows_throughout(const Learnt& l, int exclusion, int method, bool suspended) {
+    return suspended || exclusion == SUSHI_HIP_EXCLUDE_NEVER || exclusion == SUSHI_HIP_EXCLUDE_WHOLE ||
+           ((exclusion == SUSHI_HIP_EXCLUDE_AUTO || exclusion == SUSHI_HIP_EXCLUDE_ALWAYS) && l.band == 0 && l.band_decided_method == method);
+}
+inline bool takes_whole_cut(bool whole_rows, bool whole_cut_exists) { return whole_rows && whole_cut_exists; }
+inline int run_lanes(bool whole_rows, int plan_lanes) { return whole_rows ? 1 : plan_lanes; }
+
+// Does a sub-batch of `pairs` pairs and `n_sub` searches go through the exclusion (an argmin run).
+inline bool sub_excludes(int exclusion, bool suspended, int64_t pairs, int n_sub) {
+    return exclusion == SUSHI_HIP_EXCLUDE_ALWAYS || exclusion == SUSHI_HIP_EXCLUDE_BAND || exclusion == SUSHI_HIP_EXCLUDE_WHOLE ||
+           (exclusion == SUSHI_HIP_EXCLUDE_AUTO && !suspended && pairs > EXCLUDE_FROM_PAIRS + EXCLUDE_PAIRS_PER_SEARCH * (int64_t)n_sub);
+}
+
+// ... and a sub-batch of a threshold or best-K run: every pair is listed or excluded on its bound alone, whatever the batch's size.
+inline bool listed_run_excludes(int exclusion) { return exclusion != SUSHI_HIP_EXCLUDE_NEVER; }
+
+// Which form of the exclusion: chosen by the caller (BAND / WHOLE), or decided once per batch and method by a
+// vote of the pairs -- due while there is none, or none for this method.
+inline bool form_chosen(int exclusion) { return exclusion == SUSHI_HIP_EXCLUDE_BAND || exclusion == SUSHI_HIP_EXCLUDE_WHOLE; }
+inline bool vote_due(const Learnt& l, int exclusion, int method) {
+    return !form_chosen(exclusion) && (l.band < 0 || l.band_decided_method != method);
+}
+inline void decide_form(Learnt& l, int method, int looked_at, int with_room) {
+    l.band_votes[0] = looked_at; l.band_votes[1] = with_room;
+    l.band = l.band_votes[0] > 0 && (double)l.band_votes[1] >= BAND_VOTE_SHARE * (double)l.band_votes[0] ? 1 : 0;
+    l.band_decided_method = method;
+}
+inline int exclusion_form(const Learnt& l, int exclusion) {
+    return !form_chosen(exclusion) ? l.band : exclusion == SUSHI_HIP_EXCLUDE_BAND ? 1 : 0;
+}
+
+// How many of a listed transform's `pairs` possible slots get a workgroup each (the comments at DIRECT_SLOTS_MIN).
+// (A batch whose LAST run listed more than an eighth -- searches without a match, a dub's own speech -- gets a workgroup per
+// possible slot instead: 0.3 ms of empty launches at most, against half the rate on everything behind the first eighth.
+// `ifft` took 31.6 ms at BASELINE configs[2] on a dub with TM_CCOEFF_NORMED, 160 k pairs listed: bench.py --source dub.)
+inline int64_t direct_slots(unsigned long long last_transformed, int64_t pairs, int64_t plan_pairs) {
+    int64_t direct64 = std::min<int64_t>(pairs, std::max<int64_t>(DIRECT_SLOTS_MIN, pairs / DIRECT_USUAL_PART));
+    if ((double)last_transformed * (double)pairs > (double)direct64 * (double)plan_pairs) direct64 = pairs;   // (this sub-batch's share of it)
+    else if (last_transformed == 0) direct64 = std::min<int64_t>(pairs, std::max<int64_t>(DIRECT_SLOTS_MIN, pairs / DIRECT_FIRST_RUN_PART));
+    return direct64;
+}
+
+// What a handle notes when a run of `kind` starts: run_form fills in the cut and the suspension of an argmin run, the sub-batches
+// that go through the exclusion its form and those that do not their pairs.
+inline void begin_run(LastRun& last, RunKind kind) {
+    last = LastRun();
+    last.kind = kind; last.ran = true;
+}
+
+// What the diagnostics say of the last run besides its device counters `c`.
+// (a threshold or best-K run: the bound's figures only -- its exact stage is not the search's)
+inline void report_last_run(const LastRun& last, const Learnt& l, const RunCounters& c, SushiHipBatchDiag* diag) {
+    const bool argmin = last.kind == RUN_ARGMIN;
+    diag->pairs_transformed = (int64_t)c.pairs_transformed + last.direct_pairs;
+    diag->band = last.band;
+    diag->suspended = argmin && last.suspended ? 1 : 0;
+    diag->band_votes[0] = argmin ? l.band_votes[0] : 0; diag->band_votes[1] = argmin ? l.band_votes[1] : 0;
+    diag->second_look_audited = argmin ? (int64_t)c.second_look_audited : 0;
+}
+
+}  // namespace sushi
+#endif

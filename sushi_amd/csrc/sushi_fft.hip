@@ -41,6 +41,8 @@
 //   sushi_geometry.hpp     (a header: every unit's) the sizes and records host plan and device code agree on
 //   plan_core.hpp          (a header: host only, checked on the CPU by tests/host_plan_check.cpp) the plan of a batch, its
 //                          workspace and device-memory layouts, parse_bound_fault, ranking_key
+//   run_policy.hpp         (a header: host only, checked on the CPU by tests/host_policy_check.cpp) what a run decides from the
+//                          exclusion mode and from what earlier runs left: Learnt, LastRun, one function per rule
 //   sushi_fft_store.inc    packed-half storage: scales, stored bin order, the low band of a row and the norms outside it
 //   sushi_fft_spectra.inc  spectra_kernel, tspec_kernel
 //   sushi_fft_mac.inc      mac_kernel / mac_long_kernel / mac_list_kernel
@@ -76,6 +78,7 @@
 #include "fft_core.hpp"
 #include "mac_core.hpp"
 #include "plan_core.hpp"
+#include "run_policy.hpp"
 
 namespace {
 
@@ -151,31 +154,20 @@ struct SushiHipBatch {
     const SushiHipStream* dst = nullptr;
     const SushiHipStream* src = nullptr;
     int n = 0, path = 0, variant = 0, method = SUSHI_HIP_METHOD_SQDIFF_NORMED, exclusion = SUSHI_HIP_EXCLUDE_AUTO;
-    int band = -1;                      // the exclusion's form in AUTO / ALWAYS: -1 not decided yet, 0 whole rows (bound_kernel), 1 band-split
-    int band_decided_method = -1;       // ... which was decided for this method (the pattern spectra differ)
-    int band_votes[2] = {0, 0};         // what the decision was taken from: pairs looked at, pairs whose bound leaves room
+    Learnt learnt;                      // what the batch has learnt about its searches (run_policy.hpp; a new plan: about other searches now)
+    LastRun last;                       // what its last run was
     unsigned run_seq = 0;               // runs so far: rotates which excluded pairs are audited
     int audit_every = 2;                // one search in this many has one excluded pair transformed as a check, per run
     int bound_model = SUSHI_HIP_BOUND_WORST_CASE;   // (default) / SUSHI_HIP_BOUND_STATISTICAL: how the excluded side's roundings enter slb
     BoundFault fault;                   // the tests' seam (SUSHI_HIP_TEST_BOUND_FAULT; period 0, the default: none)
-    int last_band = -1;                 // form of the exclusion the last run used (its last sub-batch that went through it; -1: none did)
-    bool last_whole_cut = false;        // the last run took the plan's one-sub-batch cut (Plan::subs_whole)
-    bool last_threshold = false;        // the last run was a threshold run (sushi_hip_batch_run_threshold) or a best-K run (sushi_hip_batch_run_best)
-    bool last_best = false;             // ... a best-K run: its flags words hold, per search, the last round that evaluated a pair of it
-    // AUTO learns from its own runs: a batch whose exclusion excluded next to nothing (searches without a match anywhere) runs
-    // without it from then on, looking again every 64th run.  The last run's counts come back through 16 bytes of pinned host memory
-    // behind an event that is only ever QUERIED: a run never waits for an earlier one.
+    // AUTO learns from its own runs (Learnt): the last run's counts come back through 16 bytes of pinned host memory behind an
+    // event that is only ever QUERIED: a run never waits for an earlier one.
     unsigned long long* host_stats = nullptr;   // [2] pairs transformed, excluded pairs audited
     hipEvent_t stats_ready = nullptr;
     bool stats_pending = false;
-    unsigned long long last_transformed = 0;    // pairs the last finished run transformed (0: not known): sizes the next run's one-workgroup-per-slot launch
-    int suspended = 0;                  // 1: the exclusion is left out (AUTO)
-    unsigned suspended_at = 0;          // run_seq of the run that showed it
-    int last_suspended = 0;             // whether the last run was one of those
     int32_t* packed_out = nullptr;      // NULL, or where every run ALSO leaves its results as 8-byte (index, score bits) records
     int32_t* early_out = nullptr;       // NULL, or sushi_hip_batch_set_early_output's 16-byte records (memory host and device both touch)
     int64_t n_tiles = 0;
-    int64_t direct_pairs = 0;           // pairs of the last run's sub-batches that were transformed without the exclusion
     std::vector<SearchDesc> descs;
     Plan plan;
     BatchLayout lay = {};
@@ -184,18 +176,13 @@ struct SushiHipBatch {
     char* mem = nullptr;
     double flops = 0.0, algorithmic_bytes = 0.0;
     hipStream_t last_stream = nullptr;
-    bool ran = false;
     hipEvent_t uploaded = nullptr;      // recorded on the create-time stream behind the descriptor / plan uploads
     // lanes (plan_core.hpp): lane 0 is the stream a run is given; the others are the batch's own, forked off it behind the
     // run's first launch and joined before its last
     hipStream_t lane_stream[MAX_LANES] = {};
     hipEvent_t lane_done[MAX_LANES] = {};
     hipEvent_t fork = nullptr;
-    // what the batch has learnt about its searches (a new plan: about other searches now)
-    void forget_learnt() {
-        band = -1; last_band = -1; band_decided_method = -1; band_votes[0] = band_votes[1] = 0;
-        suspended = 0; suspended_at = 0; last_suspended = 0; last_transformed = 0; ran = false; direct_pairs = 0;
-    }
+    void forget_learnt() { learnt.forget(); last = LastRun(); }
     ~SushiHipBatch() {
         for (int l = 1; l < MAX_LANES; ++l) {
             if (lane_stream[l]) (void)hipStreamSynchronize(lane_stream[l]);          // (the pool's: this batch's work on it has to be through)
@@ -210,7 +197,7 @@ struct SushiHipBatch {
 };
 
 static SubView last_sub(const SushiHipBatch* b) {                // (of the last run)
-    const std::vector<SubBatch>& subs = b->last_whole_cut ? b->plan.subs_whole : b->plan.subs;
+    const std::vector<SubBatch>& subs = b->last.whole_cut ? b->plan.subs_whole : b->plan.subs;
     return SubView(b->mem, b->lay, b->plan.ws_lane, subs.back(), subs.size() - 1);
 }
 
@@ -275,25 +262,11 @@ struct RunForm { bool suspended; const std::vector<SubBatch>* subs; int lanes; }
 static int run_form(SushiHipBatch* b, unsigned run_seq, hipStream_t st0, RunForm* f) {
     if (b->stats_pending && hipEventQuery(b->stats_ready) == hipSuccess) {
         b->stats_pending = false;
-        const unsigned long long left = b->host_stats[0] - b->host_stats[1];
-        b->last_transformed = b->host_stats[0];
-        if (b->exclusion == SUSHI_HIP_EXCLUDE_AUTO) {
-            // (three quarters: a batch HALF of whose searches find nothing -- a dub -- still gains from the exclusion on the other half)
-            if ((double)left > 0.75 * (double)b->plan.pairs) { if (!b->suspended) b->suspended_at = run_seq; b->suspended = 1; }
-            else b->suspended = 0;
-        }
+        absorb_counts(b->learnt, b->exclusion, run_seq, b->host_stats[0], b->host_stats[1], b->plan.pairs);
     }
-    // (suspended: every 64th run looks again)
-    f->suspended = b->exclusion == SUSHI_HIP_EXCLUDE_AUTO && b->suspended && ((run_seq - b->suspended_at) & 63u) != 63u;
-    b->last_suspended = f->suspended ? 1 : 0;
-    // The lanes: the batch's own streams start behind the fill, the caller's stream goes on behind them (Lanes).  Side by side pays
-    // where the stages differ in what bounds them -- the band-split form; whole rows for every pair (the whole-row form, no
-    // exclusion at all) are HBM traffic from the first kernel to the last and only contend: those runs keep their sub-batches on
-    // the caller's stream, one after the other (measured at BASELINE configs[2]: unrelated audio 25.1 ms on one stream, 26.8 side by side).
-    const bool whole_rows_throughout = f->suspended || b->exclusion == SUSHI_HIP_EXCLUDE_NEVER || b->exclusion == SUSHI_HIP_EXCLUDE_WHOLE ||
-                                       ((b->exclusion == SUSHI_HIP_EXCLUDE_AUTO || b->exclusion == SUSHI_HIP_EXCLUDE_ALWAYS) && b->band == 0 &&
-                                        b->band_decided_method == b->method);
-    if (whole_rows_throughout && b->plan.whole_pending) {
+    f->suspended = run_suspended(b->learnt, b->exclusion, run_seq);
+    const bool whole_rows = whole_rows_throughout(b->learnt, b->exclusion, b->method, f->suspended);
+    if (whole_rows && b->plan.whole_pending) {
         // the first run that wants the one-sub-batch cut makes it (host) and uploads its schedule and items behind the fill
         if (complete_whole_cut(b->descs, b->plan)) {
             const size_t o0 = b->plan.whole_order_first, o1 = b->plan.order.size(), i0 = b->plan.whole_items_first, i1 = b->plan.items.size();
@@ -306,10 +279,10 @@ static int run_form(SushiHipBatch* b, unsigned run_seq, hipStream_t st0, RunForm
             b->plan.whole_pending = false;                       // (on no case of tests/host_plan_check.cpp: the room was sized for it; the parts run one after the other then)
         }
     }
-    const bool whole_cut = whole_rows_throughout && !b->plan.subs_whole.empty();
+    const bool whole_cut = takes_whole_cut(whole_rows, !b->plan.subs_whole.empty());
     f->subs = whole_cut ? &b->plan.subs_whole : &b->plan.subs;
-    f->lanes = whole_rows_throughout ? 1 : b->plan.lanes;
-    b->last_whole_cut = whole_cut;
+    f->lanes = run_lanes(whole_rows, b->plan.lanes);
+    b->last.suspended = f->suspended; b->last.whole_cut = whole_cut;
     return SUSHI_HIP_OK;
 }
 
@@ -319,12 +292,11 @@ static int run_form(SushiHipBatch* b, unsigned run_seq, hipStream_t st0, RunForm
 // the ranges `fa` arrives with), the run takes its sequence number, the lanes fork, every sub-batch goes through `per_sub` on its
 // lane, the lanes join.  An argmin run asks run_form which cut of the plan it takes and on how many lanes; the other kinds take
 // the plan's own.  Every return before the join still joins (Lanes' destructor).
-enum RunKind { RUN_ARGMIN, RUN_THRESHOLD, RUN_BEST };
 static void fill_add(FillArgs& fa, void* p, size_t bytes, uint32_t v) { fa.p[fa.n] = (uint32_t*)p; fa.words[fa.n] = (uint32_t)(bytes / 4); fa.value[fa.n] = v; ++fa.n; }
 // (the first two steps, which a direct-path run takes too)
 static int begin_run(SushiHipBatch* b, const hipStream_t st0, const RunKind kind) {
-    b->last_stream = st0; b->ran = true; b->direct_pairs = 0; b->last_threshold = kind != RUN_ARGMIN; b->last_best = kind == RUN_BEST;
-    if (kind != RUN_ARGMIN) { b->last_band = -1; b->last_whole_cut = false; b->last_suspended = 0; }      // (an argmin run: run_form's)
+    b->last_stream = st0;
+    begin_run(b->last, kind);
     return hipStreamWaitEvent(st0, b->uploaded, 0) == hipSuccess ? SUSHI_HIP_OK : SUSHI_HIP_ELAUNCH;     // descriptors and plan have landed
 }
 template <class PerSub>
@@ -340,7 +312,6 @@ static int run_sub_batches(RunCtx& c, const hipStream_t st0, const RunKind kind,
     c.suspended = form.suspended; c.lanes = form.lanes;
     Lanes lanes(b, st0);
     if ((rc = lanes.fork(form.lanes)) != SUSHI_HIP_OK) return rc;
-    if (kind == RUN_ARGMIN) b->last_band = -1;                   // (the form of the last sub-batch of this run that went through the exclusion)
     // Sub-batches of a plan on lanes run side by side (plan_core.hpp "Lanes"); the others one after the other.
     for (size_t si = 0; si < form.subs->size(); ++si) {
         const SubBatch& sb = (*form.subs)[si];
@@ -408,8 +379,7 @@ static int launch_bound_fault(const RunCtx& c, const SubView& v, hipStream_t st)
 // waits for the device.)
 static int decide_band(const RunCtx& c, const SubView& v, hipStream_t st, int* band) {
     SushiHipBatch* b = c.b;
-    const bool chosen = b->exclusion == SUSHI_HIP_EXCLUDE_BAND || b->exclusion == SUSHI_HIP_EXCLUDE_WHOLE;   // (by the caller)
-    if (!chosen && (b->band < 0 || b->band_decided_method != b->method)) {
+    if (vote_due(b->learnt, b->exclusion, b->method)) {
         int slots[VOTE_SLOTS * VOTE_STRIDE];
         if (hipMemsetAsync(v.votes, 0, sizeof(slots), st) != hipSuccess) return SUSHI_HIP_ELAUNCH;
         BoundArgs bp = bound_args(c, v);
@@ -417,14 +387,11 @@ static int decide_band(const RunCtx& c, const SubView& v, hipStream_t st, int* b
         if (launch_slb(c, v, bp, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
         if (hipMemcpyAsync(slots, v.votes, sizeof(slots), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
             return SUSHI_HIP_ELAUNCH;
-        b->band_votes[0] = b->band_votes[1] = 0;
-        for (int k = 0; k < VOTE_SLOTS; ++k) { b->band_votes[0] += slots[k * VOTE_STRIDE]; b->band_votes[1] += slots[k * VOTE_STRIDE + 1]; }
-        // (measured at BASELINE configs[2]: 97 % of the pairs vote for it at 12 dB of noise on the source -- 9.7 ms against 17.5 for
-        // the whole-row form --, 87 % at 6 dB -- 12.5 against 17.5 --, 14 % at 0 dB -- 28.7 against 18.7)
-        b->band = b->band_votes[0] > 0 && (double)b->band_votes[1] >= 0.75 * (double)b->band_votes[0] ? 1 : 0;
-        b->band_decided_method = b->method;
+        int looked_at = 0, with_room = 0;
+        for (int k = 0; k < VOTE_SLOTS; ++k) { looked_at += slots[k * VOTE_STRIDE]; with_room += slots[k * VOTE_STRIDE + 1]; }
+        decide_form(b->learnt, b->method, looked_at, with_room);
     }
-    *band = b->last_band = !chosen ? b->band : b->exclusion == SUSHI_HIP_EXCLUDE_BAND ? 1 : 0;
+    *band = b->last.band = exclusion_form(b->learnt, b->exclusion);
     return SUSHI_HIP_OK;
 }
 
@@ -475,9 +442,6 @@ static int launch_ifft(const RunCtx& c, const IfftArgs& x, unsigned grid, hipStr
     });
 }
 
-// The exclusion: a lower bound of every pair's scores first (three of the transform's four passes, no scoring); then the most
-// promising pair of every search, which leaves the search's threshold; then whatever the bound could not exclude (header of
-// bound_kernel).  `ip` leaves with the list of those pairs, to be transformed; `t0`: the bound's profile span, ended here.
 // the lower bound of every pair's scores (slb)
 static int bound_pairs(const RunCtx& c, const SubView& v, hipStream_t st, const int band, BoundArgs& ba) {
     const SubBatch& sb = v.sb;
@@ -521,6 +485,9 @@ static int second_look(const RunCtx& c, const SubView& v, hipStream_t st, BoundA
     return launch_ok();
 }
 
+// The exclusion: a lower bound of every pair's scores first (three of the transform's four passes, no scoring); then the most
+// promising pair of every search, which leaves the search's threshold; then whatever the bound could not exclude (header of
+// bound_kernel).  `ip` leaves with the list of those pairs, to be transformed; `t0`: the bound's profile span, ended here.
 static int exclude_pairs(const RunCtx& c, const SubView& v, hipStream_t st, const int band, IfftArgs& ip, hipEvent_t& t0) {
     const SubBatch& sb = v.sb;
     BoundArgs ba;
@@ -565,19 +532,8 @@ static int exclude_pairs(const RunCtx& c, const SubView& v, hipStream_t st, cons
 static int transform_listed(const RunCtx& c, const SubView& v, hipStream_t st, IfftArgs ip) {
     const SubBatch& sb = v.sb;
     const SushiHipBatch* b = c.b;
-    // One workgroup per list slot up to what the list usually holds (an eighth of the pairs: empty slots there cost a
-    // workgroup's launch each, ~1 ns), and a fixed grid striding over whatever lies beyond: the striding form alone runs
-    // at half the rate per pair (the loop costs it registers), one workgroup per POSSIBLE slot cost 0.3 ms of empty launches.
-    // (A batch whose LAST run listed more than that -- searches without a match, a dub's own speech -- gets a workgroup per
-    // possible slot instead: 0.3 ms of empty launches at most, against half the rate on everything behind the first eighth.
-    // `ifft` took 31.6 ms at BASELINE configs[2] on a dub with TM_CCOEFF_NORMED, 160 k pairs listed: bench.py --source dub.)
-    int64_t direct64 = std::min<int64_t>(sb.pairs, std::max<int64_t>(4096, sb.pairs / 8));
-    if ((double)b->last_transformed * (double)sb.pairs > (double)direct64 * (double)b->plan.pairs) direct64 = sb.pairs;   // (this sub-batch's share of it)
-    // (nothing known yet -- a batch's first run, which is all a one-shot job has --: half of the pairs get a workgroup each;
-    // 0.15 ms of empty launches where there is a match everywhere, against half the rate on ten times as many pairs where
-    // there is not: a dub's first run 29.7 ms)
-    else if (b->last_transformed == 0) direct64 = std::min<int64_t>(sb.pairs, std::max<int64_t>(4096, sb.pairs / 2));
-    const unsigned direct = (unsigned)direct64;
+    // one workgroup per list slot up to `direct`, a fixed grid striding over whatever lies beyond (run_policy.hpp direct_slots)
+    const unsigned direct = (unsigned)direct_slots(b->learnt.last_transformed, sb.pairs, b->plan.pairs);
     ip.list_first = 0; ip.list_direct = 1;
     if (launch_ifft(c, ip, direct, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     if ((int64_t)direct >= sb.pairs) return SUSHI_HIP_OK;
@@ -618,11 +574,7 @@ static int run_sub(RunCtx& c, const SubView& v, hipStream_t st) {
     const SubBatch& sb = v.sb;
     int rc = stage_tspec(c, v, st);
     if (rc != SUSHI_HIP_OK) return rc;
-    // The exclusion costs a pass over Y (~16 ns per pair) and half a dozen launches (~60 us); transforming a pair ~37 ns:
-    // it pays from ~3000 pairs on, plus two per search (the pairs transformed first are transformed either way).
-    const bool exclude = b->exclusion == SUSHI_HIP_EXCLUDE_ALWAYS || b->exclusion == SUSHI_HIP_EXCLUDE_BAND ||
-                         b->exclusion == SUSHI_HIP_EXCLUDE_WHOLE ||
-                         (b->exclusion == SUSHI_HIP_EXCLUDE_AUTO && !c.suspended && sb.pairs > 3000 + 2 * (int64_t)v.n_sub);
+    const bool exclude = sub_excludes(b->exclusion, c.suspended, sb.pairs, v.n_sub);
     c.excluded_any = c.excluded_any || exclude;
     int band = 0;
     if (exclude && (rc = decide_band(c, v, st, &band)) != SUSHI_HIP_OK) return rc;
@@ -643,7 +595,7 @@ static int run_sub(RunCtx& c, const SubView& v, hipStream_t st) {
     if (!exclude) {
         // every pair, in the L2-friendly schedule (what round 3 did for every batch)
         if (launch_ifft(c, ia, (unsigned)sb.pairs, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-        b->direct_pairs += sb.pairs;
+        b->last.direct_pairs += sb.pairs;
     } else {
         IfftArgs ip = ia;
         if ((rc = exclude_pairs(c, v, st, band, ip, t0)) != SUSHI_HIP_OK || (rc = transform_listed(c, v, st, ip)) != SUSHI_HIP_OK) return rc;
@@ -686,7 +638,7 @@ struct ThresholdRun { double threshold; unsigned long long ukey; int32_t capacit
 static int run_sub_threshold(RunCtx& c, const SubView& v, hipStream_t st, const ThresholdRun& tr) {
     SushiHipBatch* b = c.b;
     const SubBatch& sb = v.sb;
-    const bool exclude = b->exclusion != SUSHI_HIP_EXCLUDE_NEVER;
+    const bool exclude = listed_run_excludes(b->exclusion);
     ThresholdTileParams tp;
     tp.lp = listed_pairs(c, v);
     tp.threshold = tr.threshold; tp.pass = 0; tp.hits = tr.hits; tp.capacity = tr.capacity;
@@ -717,7 +669,7 @@ static int run_sub_threshold(RunCtx& c, const SubView& v, hipStream_t st, const 
         // (the first list is free once the second look has read it; the whole-row form never used the second)
         ta.list3 = band ? v.slist : v.slist2; ta.list3_count = v.n_list3;
     } else {
-        b->direct_pairs += sb.pairs;
+        b->last.direct_pairs += sb.pairs;
     }
     if (launch_threshold_tiles(tp, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     ThresholdTileParams t3 = tp;
@@ -746,7 +698,7 @@ struct BestRun { int k, min_separation, has_threshold; double threshold; unsigne
 static int run_sub_best(RunCtx& c, const SubView& v, hipStream_t st, const BestRun& br) {
     SushiHipBatch* b = c.b;
     const SubBatch& sb = v.sb;
-    const bool exclude = b->exclusion != SUSHI_HIP_EXCLUDE_NEVER;
+    const bool exclude = listed_run_excludes(b->exclusion);
     BestParams bp;
     memset(&bp, 0, sizeof(bp));
     bp.lp = listed_pairs(c, v);
@@ -756,7 +708,7 @@ static int run_sub_best(RunCtx& c, const SubView& v, hipStream_t st, const BestR
     int rc = stage_tspec(c, v, st);
     if (rc != SUSHI_HIP_OK) return rc;
     if (!exclude) {
-        b->direct_pairs += sb.pairs;
+        b->last.direct_pairs += sb.pairs;
         if (launch_best_tiles(bp, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
         return launch_best_select(bp, st);
     }
@@ -1093,7 +1045,7 @@ int sushi_hip_batch_run_best(SushiHipBatch* b, int32_t k, int32_t min_separation
 int sushi_hip_batch_diagnostics(SushiHipBatch* b, SushiHipBatchDiag* diag, float* ranking_err_host, int32_t* flagged_host) try {
     if (!b || !diag) return SUSHI_HIP_EINVAL;
     memset(diag, 0, sizeof(*diag));
-    if (!b->ran || b->path != SUSHI_HIP_PATH_FFT) {
+    if (!b->last.ran || b->path != SUSHI_HIP_PATH_FFT) {
         if (ranking_err_host) memset(ranking_err_host, 0, (size_t)b->n * sizeof(float));
         if (flagged_host) memset(flagged_host, 0, (size_t)b->n * sizeof(int32_t));
         return SUSHI_HIP_OK;
@@ -1107,22 +1059,17 @@ int sushi_hip_batch_diagnostics(SushiHipBatch* b, SushiHipBatchDiag* diag, float
     memcpy(&diag->max_bound_ratio, &c.max_ratio_bits, sizeof(float));
     memcpy(&diag->max_bound_ratio_noncandidate, &c.max_ratio_audit_bits, sizeof(float));
     diag->audited = (int64_t)c.audited;
-    diag->pairs_transformed = (int64_t)c.pairs_transformed + b->direct_pairs;
     diag->excluded_audited = (int64_t)c.excluded_audited;
     memcpy(&diag->max_slb_ratio_excluded, &c.max_slb_ratio_bits, sizeof(float));
     diag->slb_violations = c.slb_violations;
-    diag->band = b->last_band;
-    diag->suspended = b->last_suspended;
-    diag->band_votes[0] = b->band_votes[0]; diag->band_votes[1] = b->band_votes[1];
-    diag->second_look_audited = (int64_t)c.second_look_audited;
-    if (b->last_threshold) {
-        // (a threshold run: the bound's figures only -- its exact stage is not the search's)
-        diag->suspended = 0; diag->band_votes[0] = diag->band_votes[1] = 0; diag->second_look_audited = 0;
+    report_last_run(b->last, b->learnt, c, diag);
+    if (b->last.kind != RUN_ARGMIN) {
+        // (a threshold or best-K run: the bound's figures only -- its exact stage is not the search's)
         if (ranking_err_host) memset(ranking_err_host, 0, (size_t)b->n * sizeof(float));
         if (flagged_host) memset(flagged_host, 0, (size_t)b->n * sizeof(int32_t));
         // (a best-K run: the last round that evaluated a pair of each search -- 1 the seed, 2 .. the escalation rounds, BEST_ROUNDS + 2
         // the last stage; 0 without the exclusion)
-        if (b->last_best && flagged_host &&
+        if (b->last.kind == RUN_BEST && flagged_host &&
             hipMemcpy(flagged_host, b->mem + b->lay.flags, (size_t)b->n * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
             return SUSHI_HIP_ELAUNCH;
         return SUSHI_HIP_OK;
@@ -1146,7 +1093,7 @@ int sushi_hip_batch_diagnostics(SushiHipBatch* b, SushiHipBatchDiag* diag, float
 
 int sushi_hip_batch_pair_bounds(SushiHipBatch* b, float* slb_host, float* acc_host, int64_t* n_pairs) try {
     if (!b || !n_pairs) return SUSHI_HIP_EINVAL;
-    if (!b->ran || b->path != SUSHI_HIP_PATH_FFT || b->plan.subs.empty()) { *n_pairs = 0; return SUSHI_HIP_OK; }
+    if (!b->last.ran || b->path != SUSHI_HIP_PATH_FFT || b->plan.subs.empty()) { *n_pairs = 0; return SUSHI_HIP_OK; }
     if (hipStreamSynchronize(b->last_stream) != hipSuccess) return SUSHI_HIP_ELAUNCH;
     const SubView v = last_sub(b);
     const int64_t cap = *n_pairs;
@@ -1160,7 +1107,7 @@ int sushi_hip_batch_pair_bounds(SushiHipBatch* b, float* slb_host, float* acc_ho
 int sushi_hip_batch_workspace_view(SushiHipBatch* b, int which, void** ptr_dev, size_t* bytes) {
     if (!b || !ptr_dev || !bytes) return SUSHI_HIP_EINVAL;
     *ptr_dev = nullptr; *bytes = 0;
-    if (!b->ran || b->path != SUSHI_HIP_PATH_FFT || b->plan.subs.empty()) return SUSHI_HIP_OK;
+    if (!b->last.ran || b->path != SUSHI_HIP_PATH_FFT || b->plan.subs.empty()) return SUSHI_HIP_OK;
     if (hipStreamSynchronize(b->last_stream) != hipSuccess) return SUSHI_HIP_ELAUNCH;
     const SubView v = last_sub(b);
     switch (which) {

@@ -380,7 +380,7 @@ class SearchBatch(object):
             raise SushiError("reset: a batch keeps its number of searches")
         with torch.cuda.device(self.dst.device):
             rc = _native.lib().sushi_hip_batch_reset(self._handle, req.ctypes.data, self.n, _raw_stream(self.dst.device))
-        if rc == -4:                                              # SUSHI_HIP_ENOSPACE
+        if rc == _native.ENOSPACE:
             return False
         _native.check(rc, "sushi_hip_batch_reset")
         self.requests = req

@@ -398,6 +398,41 @@ def test_auto_across_a_method_switch_a_suspension_and_the_look_again(oracle):
     assert d["suspended"] == 1
 
 
+def test_auto_tries_the_exclusion_from_3000_pairs_and_two_per_search_on(monkeypatch):
+    """AUTO's limit (run_policy.hpp sub_excludes): a sub-batch goes through the exclusion when it has MORE than 3000 + 2 n pairs.
+    Searches of about 120 pairs each on a noisy copy of the destination; the largest batch of them at or below the limit runs
+    without the exclusion, one search more and it is tried -- and the searches both batches hold get the same bits."""
+    from sushi_amd.device import DeviceStream, SearchBatch, fft_layout_host
+    monkeypatch.setenv("SUSHI_HIP_LANES", "1:1")                 # (the rule counts a SUB-batch's pairs: one sub-batch)
+    n = 130 * PAIR
+    dst = _stream(n, 61)
+    rng = np.random.default_rng(62)
+    src = (dst + rng.standard_normal(n).astype(np.float32) * 0.02).clip(0, 1).astype(np.float32)
+    offs, lens, wst, npos = [], [], [], []
+    for k in range(30):
+        m = int(rng.integers(12000, 40000))
+        ws = int(rng.integers(0, 4 * PAIR))
+        offs.append(ws + int(rng.integers(0, 119 * PAIR))); lens.append(m); wst.append(ws); npos.append(120 * PAIR)
+    pairs = np.cumsum(fft_layout_host(np.array(wst), np.array(npos), np.array(lens))[0])       # pairs of the first k + 1 searches
+    over = [k + 1 for k in range(30) if pairs[k] > 3000 + 2 * (k + 1)]
+    above = over[0]                                              # the smallest batch above the limit ...
+    below = above - 1                                            # ... and the largest one at or below it
+    assert 24 <= below < above <= 29 and pairs[below - 1] <= 3000 + 2 * below, (below, pairs)
+    d_dst, d_src = DeviceStream(dst), DeviceStream(src)
+    res = {}
+    for count in (below, above):
+        b = SearchBatch(d_dst, d_src, offs[:count], lens[:count], wst[:count], npos[:count], path="fft", exclusion="auto")
+        assert b.fft_pairs == pairs[count - 1] and b.sub_batches == 1
+        b.run()
+        idx, score = b.results()
+        res[count] = (idx.copy(), score.copy().view(np.uint32), b.diagnostics(), b.fft_pairs)
+    d = res[below][2]
+    assert d["band"] == -1 and d["suspended"] == 0 and d["pairs_transformed"] == res[below][3] and d["slb_violations"] == 0, d
+    d = res[above][2]
+    assert d["band"] in (0, 1) and d["band_votes"][0] > 0 and d["slb_violations"] == 0, d
+    assert (res[above][0][:below] == res[below][0]).all() and (res[above][1][:below] == res[below][1]).all()
+
+
 def test_worst_case_and_statistical_bounds_give_the_same_results(oracle):
     """The excluded side's bound is a worst case by default (sushi_hip_batch_set_bound_model); round 5's statistical model is kept
     for A/B.  Same results either way, the oracle's; the worst case can only leave MORE pairs to transform, and on audio-like
