@@ -44,7 +44,8 @@ extern "C" {
                                      13 (additive): sushi_hip_curve_bytes, sushi_hip_match_curves;
                                      13 (additive): SushiHipHit, sushi_hip_batch_run_threshold;
                                      13 (additive): SUSHI_HIP_BEST_MAX_K, sushi_hip_batch_run_best;
-                                     13 (additive): SushiHipRetimeSegment, sushi_hip_retime_bytes, sushi_hip_retime */
+                                     13 (additive): SushiHipRetimeSegment, sushi_hip_retime_bytes, sushi_hip_retime;
+                                     13 (additive): SUSHI_HIP_MIX_MAX_CHANNELS / _OUTPUTS, sushi_hip_load_decode_mix */
 
 #if defined(__GNUC__)
 #define SUSHI_HIP_API __attribute__((visibility("default")))
@@ -447,6 +448,26 @@ SUSHI_HIP_API int sushi_hip_retime(const void* in_dev, int dtype, int64_t n_in,
  *     if u8_dev != NULL also v * 255 + 0.5 truncated to uint8 (wav.py:153-156). */
 SUSHI_HIP_API int sushi_hip_load_decode(const void* pcm_dev, int64_t n_frames, int32_t channels, int32_t sample_width,
                             float* mono_dev, void* hip_stream);
+/* ---- weighted downmix: several mixes of a file's channels in one decode pass (13, additive) ----
+ * sushi_hip_load_decode's decode with weights instead of the mean.  s_c: channel c's sample of a frame as sushi_hip_load_decode
+ * takes it (the int16 value, for 24-bit samples the top two bytes, as float32).  Output row o of that frame, with the float32
+ * weights w[o][0 .. channels):
+ *     acc = w[o][0] * s_0                                  (float32 product, rounded)
+ *     for c = 1 .. channels - 1:  acc = acc + w[o][c] * s_c    (the product rounded to float32, then the sum: no fused multiply-add)
+ * Every channel takes part, in file order, zero weights included, so a NumPy float32 restatement (sushi_amd.downmix.mix_host)
+ * equals the result bit for bit, signed zeros too.  Weights {0.5, 0.5} on 16-bit stereo give sushi_hip_load_decode's bits.
+ * weights_host: n_out x channels float32, row-major, in HOST memory; it travels in the kernel's arguments: no device allocation,
+ * no upload, no synchronisation.  Row o of frames [0, n_frames) goes to out_dev + o * out_stride; nothing else of out_dev is
+ * touched.  pcm_dev may have any byte alignment; only its n_frames * channels * sample_width bytes are read.  One pass over the PCM
+ * bytes serves all n_out rows.  Asynchronous; stateless.
+ * Checked before any HIP call -- EINVAL: a null pointer, n_frames < 0, channels outside [1, SUSHI_HIP_MIX_MAX_CHANNELS], n_out
+ * outside [1, SUSHI_HIP_MIX_MAX_OUTPUTS], sample_width not 2 or 3, out_stride < n_frames, a weight that is not finite; EALIGN:
+ * out_dev not 4-byte aligned.  n_frames == 0 returns SUSHI_HIP_OK without a launch. */
+#define SUSHI_HIP_MIX_MAX_CHANNELS 32
+#define SUSHI_HIP_MIX_MAX_OUTPUTS 8
+SUSHI_HIP_API int sushi_hip_load_decode_mix(const void* pcm_dev, int64_t n_frames, int32_t channels, int32_t sample_width,
+                              const float* weights_host, int32_t n_out, float* out_dev, int64_t out_stride,
+                              void* hip_stream);
 SUSHI_HIP_API int sushi_hip_load_resample(const float* raw_dev, int64_t n_raw, int32_t chunk, int32_t nl_full, double scale_full,
                             int64_t n_full, int32_t rest, int32_t nl_rest, double scale_rest,
                             int64_t pad, int64_t total, float* data_dev, void* hip_stream);

@@ -18,6 +18,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sushi_hip.h")
 U8, F32 = 0, 1
 PATH_FFT, PATH_DIRECT = 0, 1
 METHOD_SQDIFF_NORMED, METHOD_CCOEFF_NORMED = 0, 1       # cv2.TM_SQDIFF_NORMED + argmin (wav.py:185-186) | cv2.TM_CCOEFF_NORMED + argmax
+MIX_MAX_CHANNELS, MIX_MAX_OUTPUTS = 32, 8    # SUSHI_HIP_MIX_MAX_*: channels and output rows of sushi_hip_load_decode_mix
 BEST_MAX_K = 32            # SUSHI_HIP_BEST_MAX_K: picks per request of a best-K run (sushi_hip_batch_run_best)
 METHODS = {"sqdiff_normed": METHOD_SQDIFF_NORMED, "ccoeff_normed": METHOD_CCOEFF_NORMED}
 VIEW_XC, VIEW_S1, VIEW_S2, VIEW_UREL, VIEW_BASE, VIEW_SPECTRA, VIEW_USREL, VIEW_BASE1, VIEW_COARSE, VIEW_SPECTRA_LOW, \
@@ -165,6 +166,8 @@ def lib():
     L.sushi_hip_retime.argtypes = [vp, ci, i64, vp, ci, vp, i64, vp, sz, vp]
     L.sushi_hip_load_decode.restype = ci
     L.sushi_hip_load_decode.argtypes = [vp, i64, i32, i32, vp, vp]
+    L.sushi_hip_load_decode_mix.restype = ci
+    L.sushi_hip_load_decode_mix.argtypes = [vp, i64, i32, i32, vp, i32, vp, i64, vp]
     L.sushi_hip_load_resample.restype = ci
     L.sushi_hip_load_resample.argtypes = [vp, i64, i32, i32, dbl, i64, i32, i32, dbl, i64, i64, vp, vp]
     L.sushi_hip_load_histogram.restype = ci

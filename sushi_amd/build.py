@@ -6,7 +6,8 @@ The translation units, compiled separately (the direct MFMA kernel alone takes ~
   csrc/sushi_stream.hip stream preparation (prefix sums) and the stream C ABI   (-ffp-contract=off)
   csrc/sushi_fft.hip  overlap-save FFT path (its parts: csrc/sushi_fft_*.inc; the plan of a batch: csrc/plan_core.hpp, what a run decides:
                       csrc/run_policy.hpp, both host only)
-  csrc/sushi_load.hip WavStream load pipeline (decimate / pad / median clip / scale / quantise)  (-ffp-contract=off)
+  csrc/sushi_load.hip WavStream load pipeline (decode / downmix, weighted: csrc/downmix_core.hpp / decimate / pad / median clip / scale /
+                      quantise)  (-ffp-contract=off)
   csrc/sushi_curve.hip whole score curves: i8 MFMA Toeplitz GEMM (uint8), canonical float64 chain (float32)  (-ffp-contract=off);
                        the same tiles (csrc/curve_tiles.hpp) evaluate the listed pairs of a threshold run and of a best-K run
   csrc/sushi_retime.hip a stream read at another speed: linear interpolation at a rational step (csrc/retime_core.hpp)  (-ffp-contract=off)
@@ -33,7 +34,7 @@ UNITS = [
     ("sushi_direct", ["-ffp-contract=off"], []),
     ("sushi_exact", ["-ffp-contract=off"], []),
     ("sushi_stream", ["-ffp-contract=off"], []),
-    ("sushi_load", ["-ffp-contract=off"], []),      # NumPy's float32 operation order, no fused multiply-add
+    ("sushi_load", ["-ffp-contract=off"], [os.path.join(CSRC, "downmix_core.hpp")]),      # NumPy's float32 operation order, no fused multiply-add
     ("sushi_curve", ["-ffp-contract=off"], [os.path.join(CSRC, "curve_tiles.hpp")]),     # the epilogue restates cv2's operation order (as sushi_direct.hip's)
     ("sushi_retime", ["-ffp-contract=off"], [os.path.join(CSRC, "retime_core.hpp")]),    # NumPy's float64 operation order: product and sum round separately
     # -fno-slp-vectorize: the SLP pass packs the complex MACs into v_pk_fma_f32 and pays for it in

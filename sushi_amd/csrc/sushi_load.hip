@@ -13,8 +13,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
+
 #include "../../include/sushi_hip.h"
 #include "sushi_internal.hpp"
+#include "downmix_core.hpp"
 
 namespace {
 
@@ -36,6 +39,37 @@ void decode_downmix_kernel(const uint8_t* __restrict__ pcm, int64_t n_frames, in
         }
         if (channels > 1) acc /= (float)channels;
         mono[f] = acc;
+    }
+}
+
+// sushi_hip_load_decode_mix: the same decode, but every output row o is a weighted sum of the channels (downmix_core.hpp states
+// the arithmetic), and one pass over the PCM bytes writes all n_out rows.  The weights travel in the kernel's arguments
+// (w[c * 8 + o], wave-uniform: scalar loads).
+struct MixArgs {
+    const uint8_t* pcm;     // any byte alignment
+    int64_t n_frames;
+    float* out;             // row o: out + o * out_stride
+    int64_t out_stride;
+    int32_t channels, n_out;
+    float w[sushi::DOWNMIX_MAX_CHANNELS * sushi::DOWNMIX_MAX_OUTPUTS];
+};
+static_assert(sizeof(MixArgs) <= 1280, "MixArgs travels as kernel arguments");
+
+constexpr int MIX_TILE = 256;     // frames per workgroup: one per thread
+
+// One thread per frame, as decode_downmix_kernel: a wave reads 64 consecutive frames = one contiguous run of bytes (byte loads, so
+// the PCM may lie at any address), and stores n_out rows of 64 consecutive floats.  The channel loop loads a channel's eight
+// weights with one scalar load and forms all eight sums (downmix_core.hpp); only the rows in use are stored.
+template <int WIDTH>
+__global__ __launch_bounds__(MIX_TILE)
+void decode_mix_kernel(MixArgs a) {
+    const int fs = a.channels * WIDTH;
+    for (int64_t f = (int64_t)blockIdx.x * MIX_TILE + threadIdx.x; f < a.n_frames; f += (int64_t)gridDim.x * MIX_TILE) {
+        float acc[sushi::DOWNMIX_MAX_OUTPUTS];
+        sushi::downmix_frame<WIDTH>(a.pcm + f * fs, a.channels, a.w, acc);
+#pragma unroll
+        for (int k = 0; k < sushi::DOWNMIX_MAX_OUTPUTS; ++k)
+            if (k < a.n_out) a.out[k * a.out_stride + f] = acc[k];
     }
 }
 
@@ -153,6 +187,30 @@ int sushi_hip_load_decode(const void* pcm_dev, int64_t n_frames, int32_t channel
     else
         hipLaunchKernelGGL(decode_downmix_kernel<3>, dim3(grid), dim3(256), 0, (hipStream_t)hip_stream,
                            (const uint8_t*)pcm_dev, n_frames, channels, mono_dev);
+    return launch_ok();
+}
+
+int sushi_hip_load_decode_mix(const void* pcm_dev, int64_t n_frames, int32_t channels, int32_t sample_width,
+                              const float* weights_host, int32_t n_out, float* out_dev, int64_t out_stride, void* hip_stream) {
+    if (!pcm_dev || !weights_host || !out_dev || n_frames < 0) return SUSHI_HIP_EINVAL;
+    if (channels < 1 || channels > SUSHI_HIP_MIX_MAX_CHANNELS || n_out < 1 || n_out > SUSHI_HIP_MIX_MAX_OUTPUTS) return SUSHI_HIP_EINVAL;
+    if (sample_width != 2 && sample_width != 3) return SUSHI_HIP_EINVAL;
+    if (out_stride < n_frames) return SUSHI_HIP_EINVAL;
+    for (int k = 0; k < n_out * channels; ++k)
+        if (!std::isfinite(weights_host[k])) return SUSHI_HIP_EINVAL;
+    if ((uintptr_t)out_dev & 3) return SUSHI_HIP_EALIGN;
+    if (n_frames == 0) return SUSHI_HIP_OK;
+    MixArgs a;
+    a.pcm = (const uint8_t*)pcm_dev; a.n_frames = n_frames; a.out = out_dev; a.out_stride = out_stride;
+    a.channels = channels; a.n_out = n_out;
+    for (int c = 0; c < sushi::DOWNMIX_MAX_CHANNELS; ++c)
+        for (int o = 0; o < sushi::DOWNMIX_MAX_OUTPUTS; ++o)
+            a.w[c * sushi::DOWNMIX_MAX_OUTPUTS + o] = c < channels && o < n_out ? weights_host[o * channels + c] : 0.f;
+    const int64_t want = (n_frames + MIX_TILE - 1) / MIX_TILE;
+    const unsigned grid = (unsigned)(want < 65536 ? want : 65536);
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (sample_width == 2) hipLaunchKernelGGL(decode_mix_kernel<2>, dim3(grid), dim3(MIX_TILE), 0, st, a);
+    else hipLaunchKernelGGL(decode_mix_kernel<3>, dim3(grid), dim3(MIX_TILE), 0, st, a);
     return launch_ok();
 }
 

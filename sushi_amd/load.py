@@ -57,19 +57,37 @@ def _median(L, data, n, side, hist, stream):
 UPLOAD_CHUNK_BYTES = 32 << 20      # PCM bytes uploaded and decoded per step: bounds the host memory of a load
 
 
-def decode_file_on_device(wavfile, dev):
+def decode_mix_on_device(L, staged, n_frames, channels, sample_width, weights, rows, first, st):
+    """One sushi_hip_load_decode_mix launch: frames [0, n_frames) of the uploaded PCM bytes `staged` under the float32 weights
+    [n_out, channels] (a C-contiguous host array) go to rows[o, first : first + n_frames] of the float32 CUDA tensor `rows`."""
+    _native.check(L.sushi_hip_load_decode_mix(staged.data_ptr(), n_frames, channels, sample_width, weights.ctypes.data,
+                                              weights.shape[0], rows.data_ptr() + 4 * first, rows.stride(0), st),
+                  "sushi_hip_load_decode_mix")
+
+
+def decode_file_on_device(wavfile, dev, weights=None, with_mean=False):
     """wav.py:64-91 on the GPU: the data chunk of `wavfile` (a DownmixedWavFile positioned at its first frame) is
     read UPLOAD_CHUNK_BYTES at a time, uploaded, decoded and downmixed by sushi_hip_load_decode into one float32
-    mono tensor.  Returns (tensor [frames], frames).  Host memory: one chunk of file bytes."""
+    mono tensor.  Returns (tensor [frames], frames).  Host memory: one chunk of file bytes.
+    weights (float32 [n_out, channels], sushi_amd.downmix.weight_matrix): every chunk is still read and uploaded once, and one
+    sushi_hip_load_decode_mix launch on it writes all n_out weighted rows; with_mean=True adds the channel mean by the existing entry on
+    the same uploaded chunk.  Returns (mean tensor or None, rows tensor [n_out, frames], frames).  Device memory: one float32 row at
+    the file's frame rate per mix."""
     L = _native.lib()
     frame_size = wavfile.frame_size
     if wavfile.sample_width not in (2, 3):
         raise SushiError('Unsupported sample width: {0}'.format(wavfile.sample_width))
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, dtype=np.float32)
+        if weights.ndim != 2 or weights.shape[1] != wavfile.channels_count or not 1 <= weights.shape[0] <= _native.MIX_MAX_OUTPUTS:
+            raise SushiError('downmix: weights must be [1 .. %d, channels]' % _native.MIX_MAX_OUTPUTS)
+    want_mean = weights is None or with_mean
     frames_total = int(wavfile.frames_available)           # never more than the file holds, whatever the header says
     frames_per_chunk = max(1, UPLOAD_CHUNK_BYTES // frame_size)
     with torch.cuda.device(dev):
         st = torch.cuda.current_stream(dev).cuda_stream
-        mono = torch.zeros(max(frames_total, 1), dtype=torch.float32, device=dev)
+        mono = torch.zeros(max(frames_total, 1), dtype=torch.float32, device=dev) if want_mean else None
+        rows = None if weights is None else torch.zeros((weights.shape[0], max(frames_total, 1)), dtype=torch.float32, device=dev)
         stage = bytearray(min(frames_per_chunk, max(frames_total, 1)) * frame_size)     # the one host buffer of the load
         done = 0
         while done < frames_total:
@@ -82,11 +100,16 @@ def decode_file_on_device(wavfile, dev):
                 logging.error("Length of audio channels didn't match. This might result in broken output")
             # (a pageable-memory upload returns when the bytes have left `stage`: it can be refilled right away)
             staged = torch.frombuffer(stage, dtype=torch.uint8, count=got * frame_size).to(dev)
-            _native.check(L.sushi_hip_load_decode(staged.data_ptr(), got, wavfile.channels_count, wavfile.sample_width,
-                                                  mono.data_ptr() + 4 * done, st), "sushi_hip_load_decode")
+            if want_mean:
+                _native.check(L.sushi_hip_load_decode(staged.data_ptr(), got, wavfile.channels_count, wavfile.sample_width,
+                                                      mono.data_ptr() + 4 * done, st), "sushi_hip_load_decode")
+            if rows is not None:
+                decode_mix_on_device(L, staged, got, wavfile.channels_count, wavfile.sample_width, weights, rows, done, st)
             done += got
-            del staged                                           # stream-ordered free: the kernel above is queued first
-    return mono[:max(done, 1)], done                          # the frames that were there (n_raw of the pipeline)
+            del staged                                           # stream-ordered free: the kernels above are queued first
+    if weights is None:
+        return mono[:max(done, 1)], done                      # the frames that were there (n_raw of the pipeline)
+    return (None if mono is None else mono[:max(done, 1)]), rows[:, :max(done, 1)], done
 
 
 def build_on_device(samples, framerate, frames_count, sample_rate, sample_type, device=None, read_chunk_size=1,

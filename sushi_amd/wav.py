@@ -2,7 +2,8 @@
 
 Same constructor, attributes and methods as reference wav.py:104-188; ``find_substream`` runs on
 the GPU (libsushi_hip.so) instead of ``cv2.matchTemplate`` + ``argmin`` (wav.py:185-186).
-Extensions: ``WavStream.from_samples`` (in-memory PCM), ``find_substreams`` (batched).
+Extensions: ``WavStream.from_samples`` (in-memory PCM), ``find_substreams`` (batched), ``downmix=`` / ``WavStream.load_mixes`` /
+``WavStream.from_channels`` (the channels mixed by weight instead of averaged: sushi_amd/downmix.py).
 
 The load pipeline (wav.py:64-162): the RIFF header walk on the host; PCM decode, channel downmix, decimation,
 padding, the two medians, clip / scale / quantise on the GPU when one is present (the file is uploaded in bounded
@@ -26,8 +27,10 @@ WAVE_FORMAT_EXTENSIBLE = 0xFFFE
 
 
 class DownmixedWavFile(object):
-    """RIFF/WAVE reader with channel-mean downmix to float32 (reference wav.py:15-101)."""
+    """RIFF/WAVE reader with channel-mean downmix to float32 (reference wav.py:15-101).
+    channel_mask: the dwChannelMask of an EXTENSIBLE fmt chunk that is long enough to hold one (an int), else None."""
     _file = None
+    channel_mask = None
 
     def __init__(self, path):
         super(DownmixedWavFile, self).__init__()
@@ -89,6 +92,17 @@ class DownmixedWavFile(object):
         else:
             raise SushiError('unknown format: {0}'.format(wFormatTag))
         self.frame_size = self.channels_count * self.sample_width
+        if wFormatTag == WAVE_FORMAT_EXTENSIBLE and len(body) >= 24:      # cbSize, wValidBitsPerSample, then the mask
+            self.channel_mask = struct.unpack('<L', body[20:24])[0]
+
+    def frames_int16(self, data):
+        """Raw frame bytes as int16 [n, channels]: what _decode averages, before it does (24-bit samples: their top two bytes)."""
+        from .downmix import frames_from_bytes
+        return frames_from_bytes(data, self.channels_count, self.sample_width)
+
+    def read_raw(self, count):
+        """The raw bytes of the next `count` frames (fewer at the end of the file)."""
+        return self._file.read(count * self.frame_size) if count else b''
 
     def _decode(self, data):
         if self.sample_width == 2:
@@ -144,6 +158,10 @@ def torch_device(device):
     return torch.device("cuda", torch.cuda.current_device()) if d.type == "cuda" and d.index is None else d
 
 
+def _is_mean(downmix):
+    return isinstance(downmix, str) and downmix == 'mean'
+
+
 def _locate(pattern):
     """If `pattern` is a view into a live WavStream's host data (what get_substream and np.split
     of it return, sushi.py:417,445), return (stream, offset, length); else None."""
@@ -164,9 +182,15 @@ class WavStream(object):
     READ_CHUNK_SIZE = 1  # one second, seems to be the fastest
     PADDING_SECONDS = 10
 
-    def __init__(self, path, sample_rate=12000, sample_type='uint8', device=None):
+    def __init__(self, path, sample_rate=12000, sample_type='uint8', device=None, downmix='mean'):
+        """downmix: 'mean' (the reference's channel average, wav.py:80-91), a named mix or one weight per channel
+        (sushi_amd.downmix.weights_for): the channels are then mixed by weight in the decode -- on the GPU when there is one
+        (sushi_hip_load_decode_mix), in NumPy otherwise, bit for bit the same -- and everything after it is unchanged."""
         if sample_type not in ('float32', 'uint8'):
             raise SushiError('Unknown sample type of WAV stream, must be uint8 or float32')
+        if not _is_mean(downmix):
+            self._load_mixes(path, [downmix], sample_rate, sample_type, device, first=self)
+            return
         before_read = time()
         stream = DownmixedWavFile(path)
         try:
@@ -209,6 +233,127 @@ class WavStream(object):
         self = cls.__new__(cls)
         samples = np.asarray(samples).astype(np.float32).reshape(-1)
         self._build(samples, int(framerate), samples.shape[0], sample_rate, sample_type)
+        self._device = device
+        self._dev = None
+        _live_streams.add(self)
+        return self
+
+    @classmethod
+    def load_mixes(cls, path, mixes, sample_rate=12000, sample_type='uint8', device=None):
+        """[WavStream(path, downmix=m) for m in mixes] -- live streams, bit for bit those -- with the file read once: each chunk is
+        uploaded once and one decode launch per chunk serves every weighted mix ('mean' in the list: the existing decode on the same
+        uploaded chunk).  At most 8 weighted mixes.  Memory: one float32 row at the FILE's frame rate per mix (in HBM on the GPU path)
+        until the last of them has been decimated."""
+        if sample_type not in ('float32', 'uint8'):
+            raise SushiError('Unknown sample type of WAV stream, must be uint8 or float32')
+        mixes = list(mixes)
+        if not mixes:
+            raise SushiError('load_mixes: at least one mix')
+        return cls._load_mixes(path, mixes, sample_rate, sample_type, device)
+
+    @classmethod
+    def _load_mixes(cls, path, mixes, sample_rate, sample_type, device, first=None):
+        """One stream per mix from one pass over the file; `first`: the instance to fill for mixes[0] (the constructor's)."""
+        from .downmix import mix_host, weight_matrix
+        before_read = time()
+        stream = DownmixedWavFile(path)
+        streams = [first if (k == 0 and first is not None) else cls.__new__(cls) for k in range(len(mixes))]
+        try:
+            weighted = [k for k, m in enumerate(mixes) if not _is_mean(m)]
+            with_mean = len(weighted) < len(mixes)
+            W = weight_matrix([mixes[k] for k in weighted], stream.channels_count, stream.channel_mask) if weighted else None
+            if cls._use_gpu():
+                from .load import build_on_device, decode_file_on_device
+                dev = torch_device("cuda" if device is None else device)
+                if W is None:
+                    mono, got = decode_file_on_device(stream, dev)
+                    rows = None
+                else:
+                    mono, rows, got = decode_file_on_device(stream, dev, weights=W, with_mean=with_mean)
+            else:
+                # the NumPy path: the same single pass, ten seconds of frames at a time
+                n = stream.frames_available
+                mono = np.zeros(n, np.float32) if with_mean else None
+                rows = np.zeros((len(weighted), n), np.float32) if weighted else None
+                got = 0
+                while got < n:
+                    data = stream.read_raw(min(10 * stream.framerate, n - got))
+                    m = len(data) // stream.frame_size
+                    if m == 0:
+                        break
+                    data = data[:m * stream.frame_size]
+                    if with_mean:
+                        mono[got:got + m] = stream._decode(data)
+                    if weighted:
+                        rows[:, got:got + m] = mix_host(stream.frames_int16(data), W)
+                    got += m
+            if got == 0:
+                raise SushiError('no audio frames in the data chunk')
+            for k, new in enumerate(streams):
+                samples = mono if k not in weighted else rows[weighted.index(k)]
+                samples = samples[:got]
+                new._dev_row = None
+                if cls._use_gpu():
+                    new.data, new._dev_row, new.sample_count, new.padding_size = build_on_device(
+                        samples, stream.framerate, stream.frames_count, sample_rate, sample_type,
+                        read_chunk_size=cls.READ_CHUNK_SIZE, padding_seconds=cls.PADDING_SECONDS)
+                    new.sample_rate = sample_rate
+                else:
+                    new._build_host(np.ascontiguousarray(samples), stream.framerate, stream.frames_count, sample_rate, sample_type)
+        except Exception as e:
+            raise SushiError('Error while loading {0}: {1}'.format(path, e))
+        finally:
+            stream.close()
+        for new in streams:
+            new._device = device
+            new._dev = None
+            _live_streams.add(new)
+        logging.info('Done reading WAV {0} ({1} mixes) in {2}s'.format(path, len(mixes), time() - before_read))
+        return streams
+
+    @classmethod
+    def from_channels(cls, frames, framerate, downmix, sample_rate=12000, sample_type='uint8', device=None, channel_mask=None):
+        """Build a stream from PCM frames already in memory -- int16 [n, channels], as DownmixedWavFile.frames_int16 returns them --
+        mixed by `downmix` ('mean', a named mix or weights; channel_mask: the speaker layout a named mix reads, None: the WAV default
+        order), running the same pipeline as the constructor."""
+        from .downmix import mix_host, weight_matrix
+        if sample_type not in ('float32', 'uint8'):
+            raise SushiError('Unknown sample type of WAV stream, must be uint8 or float32')
+        frames = np.ascontiguousarray(frames)
+        if frames.ndim != 2 or frames.dtype != np.int16 or frames.shape[0] < 1 or frames.shape[1] < 1:
+            raise SushiError('from_channels: int16 frames [n, channels]')
+        n, channels = frames.shape
+        self = cls.__new__(cls)
+        if _is_mean(downmix):
+            samples = frames.astype(np.float32)
+            acc = samples[:, 0].copy()
+            for c in range(1, channels):         # DownmixedWavFile._decode's sum and division
+                acc += samples[:, c]
+            if channels > 1:
+                acc /= float(channels)
+            samples = acc
+        else:
+            W = weight_matrix([downmix], channels, channel_mask)
+            if cls._use_gpu():
+                import torch
+                from . import _native
+                from .load import decode_mix_on_device
+                dev = torch_device("cuda" if device is None else device)
+                with torch.cuda.device(dev):
+                    staged = torch.from_numpy(frames.reshape(-1).view(np.uint8)).to(dev)
+                    rows = torch.empty((1, n), dtype=torch.float32, device=dev)
+                    decode_mix_on_device(_native.lib(), staged, n, channels, 2, W, rows, 0, torch.cuda.current_stream(dev).cuda_stream)
+                samples = rows[0]
+            else:
+                samples = mix_host(frames, W)[0]
+        if isinstance(samples, np.ndarray):
+            self._build(samples, int(framerate), n, sample_rate, sample_type)
+        else:
+            from .load import build_on_device
+            self.data, self._dev_row, self.sample_count, self.padding_size = build_on_device(
+                samples, int(framerate), n, sample_rate, sample_type, read_chunk_size=self.READ_CHUNK_SIZE,
+                padding_seconds=self.PADDING_SECONDS)
+            self.sample_rate = sample_rate
         self._device = device
         self._dev = None
         _live_streams.add(self)
