@@ -45,7 +45,8 @@ extern "C" {
                                      13 (additive): SushiHipHit, sushi_hip_batch_run_threshold;
                                      13 (additive): SUSHI_HIP_BEST_MAX_K, sushi_hip_batch_run_best;
                                      13 (additive): SushiHipRetimeSegment, sushi_hip_retime_bytes, sushi_hip_retime;
-                                     13 (additive): SUSHI_HIP_MIX_MAX_CHANNELS / _OUTPUTS, sushi_hip_load_decode_mix */
+                                     13 (additive): SUSHI_HIP_MIX_MAX_CHANNELS / _OUTPUTS, sushi_hip_load_decode_mix;
+                                     13 (additive): sushi_hip_load_resample_fir */
 
 #if defined(__GNUC__)
 #define SUSHI_HIP_API __attribute__((visibility("default")))
@@ -471,6 +472,24 @@ SUSHI_HIP_API int sushi_hip_load_decode_mix(const void* pcm_dev, int64_t n_frame
 SUSHI_HIP_API int sushi_hip_load_resample(const float* raw_dev, int64_t n_raw, int32_t chunk, int32_t nl_full, double scale_full,
                             int64_t n_full, int32_t rest, int32_t nl_rest, double scale_rest,
                             int64_t pad, int64_t total, float* data_dev, void* hip_stream);
+/* ---- filtered decimation: a low-pass in front of the decimator (13, additive) ----
+ * sushi_hip_load_resample's row with a zero-phase polyphase FIR filter in place of the nearest-neighbour read.  num / den: input
+ * frames per output sample in lowest terms (frame rate / sample rate); table_dev: float64 [den][2 * half_width], row r the filter
+ * for an output that lies r / den behind an input frame, every row summing to 1 (sushi_amd.resample.fir_table builds it on the
+ * host; the library only applies it).  Body sample i, 0 <= i < n_body, W = half_width:
+ *     t = i * num (int64);  j = t / den;  r = t % den;  acc = 0.0
+ *     for c = 0 .. 2W - 1, in that order:  acc = acc + table[r][c] * (double)raw[clamp(j - W + 1 + c, 0, n_raw - 1)]
+ *                                          (float64; the product rounded, then the sum: no fused multiply-add)
+ *     data[pad + i] = (float)acc
+ * so a NumPy float64 restatement (sushi_amd.resample.resample_host) equals the result bit for bit.  The rest of the row is what
+ * sushi_hip_load_resample writes: zeros from pad + n_body to total - pad, data[0 .. pad) = data[pad], data[total - pad .. total)
+ * = data[total - pad - 1].  All of [0, total) is written and nothing else.  Asynchronous; stateless.
+ * Checked before any HIP call -- EINVAL: a null pointer, n_raw < 1, n_body < 1 or >= 2^40, num or den outside [1, 2^20],
+ * half_width < 1, den * 2 * half_width > 65536, a last read (n_body - 1) * num / den > n_raw - 1, pad < 0,
+ * pad + n_body > total - pad; EALIGN: table_dev not 8-byte aligned, raw_dev or data_dev not 4-byte aligned. */
+SUSHI_HIP_API int sushi_hip_load_resample_fir(const float* raw_dev, int64_t n_raw, int32_t num, int32_t den,
+                                const double* table_dev, int32_t half_width, int64_t n_body,
+                                int64_t pad, int64_t total, float* data_dev, void* hip_stream);
 SUSHI_HIP_API int sushi_hip_load_histogram(const float* data_dev, int64_t n, int side, uint32_t prefix, uint32_t mask, int shift,
                              uint64_t* hist_dev, void* hip_stream);
 SUSHI_HIP_API int sushi_hip_load_normalise(float* data_dev, int64_t n, float lo, float hi, float range, uint8_t* u8_dev,

@@ -170,6 +170,8 @@ def lib():
     L.sushi_hip_load_decode_mix.argtypes = [vp, i64, i32, i32, vp, i32, vp, i64, vp]
     L.sushi_hip_load_resample.restype = ci
     L.sushi_hip_load_resample.argtypes = [vp, i64, i32, i32, dbl, i64, i32, i32, dbl, i64, i64, vp, vp]
+    L.sushi_hip_load_resample_fir.restype = ci
+    L.sushi_hip_load_resample_fir.argtypes = [vp, i64, i32, i32, vp, i32, i64, i64, i64, vp, vp]
     L.sushi_hip_load_histogram.restype = ci
     L.sushi_hip_load_histogram.argtypes = [vp, i64, ci, u32, u32, ci, vp, vp]
     L.sushi_hip_load_normalise.restype = ci

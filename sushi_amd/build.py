@@ -11,6 +11,7 @@ The translation units, compiled separately (the direct MFMA kernel alone takes ~
   csrc/sushi_curve.hip whole score curves: i8 MFMA Toeplitz GEMM (uint8), canonical float64 chain (float32)  (-ffp-contract=off);
                        the same tiles (csrc/curve_tiles.hpp) evaluate the listed pairs of a threshold run and of a best-K run
   csrc/sushi_retime.hip a stream read at another speed: linear interpolation at a rational step (csrc/retime_core.hpp)  (-ffp-contract=off)
+  csrc/sushi_resample.hip a low-pass in front of the load pipeline's decimator: polyphase FIR at the file's rate (csrc/resample_core.hpp)  (-ffp-contract=off)
 Every unit sees csrc/sushi_geometry.hpp (through sushi_common.hpp): the sizes and records the host's plan and the device code share.
 """
 import math
@@ -37,6 +38,7 @@ UNITS = [
     ("sushi_load", ["-ffp-contract=off"], [os.path.join(CSRC, "downmix_core.hpp")]),      # NumPy's float32 operation order, no fused multiply-add
     ("sushi_curve", ["-ffp-contract=off"], [os.path.join(CSRC, "curve_tiles.hpp")]),     # the epilogue restates cv2's operation order (as sushi_direct.hip's)
     ("sushi_retime", ["-ffp-contract=off"], [os.path.join(CSRC, "retime_core.hpp")]),    # NumPy's float64 operation order: product and sum round separately
+    ("sushi_resample", ["-ffp-contract=off"], [os.path.join(CSRC, "resample_core.hpp")]),    # float64 taps: product and sum round separately, as NumPy's
     # -fno-slp-vectorize: the SLP pass packs the complex MACs into v_pk_fma_f32 and pays for it in
     # register shuffles (v_mov / accvgpr traffic); plain v_fma_f32 already issues at the f32 peak rate.
     ("sushi_fft", ["-fno-slp-vectorize"],

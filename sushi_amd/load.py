@@ -113,9 +113,13 @@ def decode_file_on_device(wavfile, dev, weights=None, with_mean=False):
 
 
 def build_on_device(samples, framerate, frames_count, sample_rate, sample_type, device=None, read_chunk_size=1,
-                    padding_seconds=10):
+                    padding_seconds=10, resample='nearest'):
     """-> (host data ndarray (1, L) of dtype uint8/float32, device tensor of the same row, sample_count, padding_size)
-    `samples`: downmixed frames, a float32 host array or a float32 CUDA tensor (decode_file_on_device)."""
+    `samples`: downmixed frames, a float32 host array or a float32 CUDA tensor (decode_file_on_device).
+    resample='fir': the decimation step alone is sushi_hip_load_resample_fir (sushi_amd/resample.py) -- the same layout, a low-pass
+    in front of the decimator; the medians, the normalisation and the hand-over are the code below either way."""
+    from .resample import check_mode, resample_device
+    check_mode(resample)
     if sample_type not in ('float32', 'uint8'):
         raise SushiError('Unknown sample type of WAV stream, must be uint8 or float32')
     L = _native.lib()
@@ -142,9 +146,12 @@ def build_on_device(samples, framerate, frames_count, sample_rate, sample_type, 
         st = torch.cuda.current_stream(dev).cuda_stream
         raw = samples if on_device else torch.from_numpy(np.ascontiguousarray(samples, dtype=np.float32)).to(dev)
         data = torch.empty(total, dtype=torch.float32, device=dev)
-        _native.check(L.sushi_hip_load_resample(raw.data_ptr(), n_raw, chunk, nl_full, scale_full, n_full, rest, nl_rest,
-                                                scale_rest, padding_size, total, data.data_ptr(), st),
-                      "sushi_hip_load_resample")
+        if resample == 'fir' and downsample_rate != 1:
+            resample_device(raw, framerate, sample_rate, n_full * nl_full + nl_rest, padding_size, total, out=data)
+        else:
+            _native.check(L.sushi_hip_load_resample(raw.data_ptr(), n_raw, chunk, nl_full, scale_full, n_full, rest, nl_rest,
+                                                    scale_rest, padding_size, total, data.data_ptr(), st),
+                          "sushi_hip_load_resample")
         hist = torch.empty(256, dtype=torch.int64, device=dev)
         max_value = _median(L, data, total, 0, hist, st) * 3
         min_value = _median(L, data, total, 1, hist, st) * 3

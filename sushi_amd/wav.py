@@ -158,6 +158,11 @@ def torch_device(device):
     return torch.device("cuda", torch.cuda.current_device()) if d.type == "cuda" and d.index is None else d
 
 
+def _check_resample(resample):
+    from .resample import check_mode
+    return check_mode(resample)
+
+
 def _is_mean(downmix):
     return isinstance(downmix, str) and downmix == 'mean'
 
@@ -182,14 +187,18 @@ class WavStream(object):
     READ_CHUNK_SIZE = 1  # one second, seems to be the fastest
     PADDING_SECONDS = 10
 
-    def __init__(self, path, sample_rate=12000, sample_type='uint8', device=None, downmix='mean'):
-        """downmix: 'mean' (the reference's channel average, wav.py:80-91), a named mix or one weight per channel
+    def __init__(self, path, sample_rate=12000, sample_type='uint8', device=None, downmix='mean', resample='nearest'):
+        """resample: 'nearest' (the reference's decimation, wav.py:125-137: the nearest frame, no filter) or 'fir': a zero-phase
+        windowed-sinc low-pass at the file's rate in front of the decimator (sushi_amd.resample) -- on the GPU when there is one
+        (sushi_hip_load_resample_fir), in NumPy otherwise, bit for bit the same; shape, time axis and everything after it unchanged.
+        downmix: 'mean' (the reference's channel average, wav.py:80-91), a named mix or one weight per channel
         (sushi_amd.downmix.weights_for): the channels are then mixed by weight in the decode -- on the GPU when there is one
         (sushi_hip_load_decode_mix), in NumPy otherwise, bit for bit the same -- and everything after it is unchanged."""
         if sample_type not in ('float32', 'uint8'):
             raise SushiError('Unknown sample type of WAV stream, must be uint8 or float32')
+        _check_resample(resample)
         if not _is_mean(downmix):
-            self._load_mixes(path, [downmix], sample_rate, sample_type, device, first=self)
+            self._load_mixes(path, [downmix], sample_rate, sample_type, device, first=self, resample=resample)
             return
         before_read = time()
         stream = DownmixedWavFile(path)
@@ -203,7 +212,7 @@ class WavStream(object):
                 self._dev_row = None
                 self.data, self._dev_row, self.sample_count, self.padding_size = build_on_device(
                     mono, stream.framerate, stream.frames_count, sample_rate, sample_type,
-                    read_chunk_size=self.READ_CHUNK_SIZE, padding_seconds=self.PADDING_SECONDS)
+                    read_chunk_size=self.READ_CHUNK_SIZE, padding_seconds=self.PADDING_SECONDS, resample=resample)
                 self.sample_rate = sample_rate
             else:
                 samples = np.zeros(stream.frames_available, np.float32)
@@ -214,7 +223,7 @@ class WavStream(object):
                 # short last chunk by its own length, wav.py:127-134); what the reference leaves as uninitialised memory
                 # (np.empty, wav.py:119) is zero here
                 samples = samples[:got]
-                self._build_host(samples, stream.framerate, stream.frames_count, sample_rate, sample_type)
+                self._build_host(samples, stream.framerate, stream.frames_count, sample_rate, sample_type, resample)
         except Exception as e:
             raise SushiError('Error while loading {0}: {1}'.format(path, e))
         finally:
@@ -225,35 +234,38 @@ class WavStream(object):
         logging.info('Done reading WAV {0} in {1}s'.format(path, time() - before_read))
 
     @classmethod
-    def from_samples(cls, samples, framerate, sample_rate=12000, sample_type='uint8', device=None):
+    def from_samples(cls, samples, framerate, sample_rate=12000, sample_type='uint8', device=None, resample='nearest'):
         """Build a stream from downmixed PCM samples already in memory (any real dtype; values as
         DownmixedWavFile would return them), running the same pipeline as the constructor."""
         if sample_type not in ('float32', 'uint8'):
             raise SushiError('Unknown sample type of WAV stream, must be uint8 or float32')
+        _check_resample(resample)
         self = cls.__new__(cls)
         samples = np.asarray(samples).astype(np.float32).reshape(-1)
-        self._build(samples, int(framerate), samples.shape[0], sample_rate, sample_type)
+        self._build(samples, int(framerate), samples.shape[0], sample_rate, sample_type, resample)
         self._device = device
         self._dev = None
         _live_streams.add(self)
         return self
 
     @classmethod
-    def load_mixes(cls, path, mixes, sample_rate=12000, sample_type='uint8', device=None):
-        """[WavStream(path, downmix=m) for m in mixes] -- live streams, bit for bit those -- with the file read once: each chunk is
+    def load_mixes(cls, path, mixes, sample_rate=12000, sample_type='uint8', device=None, resample='nearest'):
+        """[WavStream(path, downmix=m, resample=resample) for m in mixes] -- live streams, bit for bit those -- with the file read once: each chunk is
         uploaded once and one decode launch per chunk serves every weighted mix ('mean' in the list: the existing decode on the same
         uploaded chunk).  At most 8 weighted mixes.  Memory: one float32 row at the FILE's frame rate per mix (in HBM on the GPU path)
         until the last of them has been decimated."""
         if sample_type not in ('float32', 'uint8'):
             raise SushiError('Unknown sample type of WAV stream, must be uint8 or float32')
+        _check_resample(resample)
         mixes = list(mixes)
         if not mixes:
             raise SushiError('load_mixes: at least one mix')
-        return cls._load_mixes(path, mixes, sample_rate, sample_type, device)
+        return cls._load_mixes(path, mixes, sample_rate, sample_type, device, resample=resample)
 
     @classmethod
-    def _load_mixes(cls, path, mixes, sample_rate, sample_type, device, first=None):
-        """One stream per mix from one pass over the file; `first`: the instance to fill for mixes[0] (the constructor's)."""
+    def _load_mixes(cls, path, mixes, sample_rate, sample_type, device, first=None, resample='nearest'):
+        """One stream per mix from one pass over the file; `first`: the instance to fill for mixes[0] (the constructor's).
+        resample: every mix row is decimated on its own, so 'fir' filters each separately."""
         from .downmix import mix_host, weight_matrix
         before_read = time()
         stream = DownmixedWavFile(path)
@@ -296,10 +308,11 @@ class WavStream(object):
                 if cls._use_gpu():
                     new.data, new._dev_row, new.sample_count, new.padding_size = build_on_device(
                         samples, stream.framerate, stream.frames_count, sample_rate, sample_type,
-                        read_chunk_size=cls.READ_CHUNK_SIZE, padding_seconds=cls.PADDING_SECONDS)
+                        read_chunk_size=cls.READ_CHUNK_SIZE, padding_seconds=cls.PADDING_SECONDS, resample=resample)
                     new.sample_rate = sample_rate
                 else:
-                    new._build_host(np.ascontiguousarray(samples), stream.framerate, stream.frames_count, sample_rate, sample_type)
+                    new._build_host(np.ascontiguousarray(samples), stream.framerate, stream.frames_count, sample_rate, sample_type,
+                                    resample)
         except Exception as e:
             raise SushiError('Error while loading {0}: {1}'.format(path, e))
         finally:
@@ -312,13 +325,15 @@ class WavStream(object):
         return streams
 
     @classmethod
-    def from_channels(cls, frames, framerate, downmix, sample_rate=12000, sample_type='uint8', device=None, channel_mask=None):
+    def from_channels(cls, frames, framerate, downmix, sample_rate=12000, sample_type='uint8', device=None, channel_mask=None,
+                      resample='nearest'):
         """Build a stream from PCM frames already in memory -- int16 [n, channels], as DownmixedWavFile.frames_int16 returns them --
         mixed by `downmix` ('mean', a named mix or weights; channel_mask: the speaker layout a named mix reads, None: the WAV default
         order), running the same pipeline as the constructor."""
         from .downmix import mix_host, weight_matrix
         if sample_type not in ('float32', 'uint8'):
             raise SushiError('Unknown sample type of WAV stream, must be uint8 or float32')
+        _check_resample(resample)
         frames = np.ascontiguousarray(frames)
         if frames.ndim != 2 or frames.dtype != np.int16 or frames.shape[0] < 1 or frames.shape[1] < 1:
             raise SushiError('from_channels: int16 frames [n, channels]')
@@ -347,12 +362,12 @@ class WavStream(object):
             else:
                 samples = mix_host(frames, W)[0]
         if isinstance(samples, np.ndarray):
-            self._build(samples, int(framerate), n, sample_rate, sample_type)
+            self._build(samples, int(framerate), n, sample_rate, sample_type, resample)
         else:
             from .load import build_on_device
             self.data, self._dev_row, self.sample_count, self.padding_size = build_on_device(
                 samples, int(framerate), n, sample_rate, sample_type, read_chunk_size=self.READ_CHUNK_SIZE,
-                padding_seconds=self.PADDING_SECONDS)
+                padding_seconds=self.PADDING_SECONDS, resample=resample)
             self.sample_rate = sample_rate
         self._device = device
         self._dev = None
@@ -385,20 +400,21 @@ class WavStream(object):
         except ImportError:
             return False
 
-    def _build(self, samples, framerate, frames_count, sample_rate, sample_type):
+    def _build(self, samples, framerate, frames_count, sample_rate, sample_type, resample='nearest'):
         """wav.py:113-156: on the GPU if there is one (the normalised row then stays in HBM for the
         matching), else in NumPy."""
         self._dev_row = None
         if not self._use_gpu():
-            return self._build_host(samples, framerate, frames_count, sample_rate, sample_type)
+            return self._build_host(samples, framerate, frames_count, sample_rate, sample_type, resample)
         from .load import build_on_device
         self.data, self._dev_row, self.sample_count, self.padding_size = build_on_device(
             samples, framerate, frames_count, sample_rate, sample_type,
-            read_chunk_size=self.READ_CHUNK_SIZE, padding_seconds=self.PADDING_SECONDS)
+            read_chunk_size=self.READ_CHUNK_SIZE, padding_seconds=self.PADDING_SECONDS, resample=resample)
         self.sample_rate = sample_rate
 
     # wav.py:113-156 (value pipeline) in NumPy, whole-stream instead of chunk-by-chunk
-    def _build_host(self, samples, framerate, frames_count, sample_rate, sample_type):
+    def _build_host(self, samples, framerate, frames_count, sample_rate, sample_type, resample='nearest'):
+        _check_resample(resample)
         self._dev_row = None
         total_seconds = frames_count / float(framerate)
         downsample_rate = sample_rate / float(framerate)
@@ -415,6 +431,18 @@ class WavStream(object):
             # cv2.resize(..., INTER_NEAREST) per one-second chunk (wav.py:125-137):
             # x_ofs[x] = min(floor(x * (1 / (new_len / len))), len - 1)
             n_full, rest = divmod(samples.shape[0], chunk)
+            if resample == 'fir':
+                # the nearest path's body length, filled by the filter instead (sushi_amd/resample.py): same layout, same time axis
+                from .resample import resample_host
+                nl_full = max(int(py2_round(chunk * downsample_rate)), 0)
+                nl_rest = max(int(py2_round(rest * downsample_rate)), 0) if rest else 0
+                n_body = n_full * nl_full + nl_rest
+                if n_body > data.shape[1] - 2 * self.padding_size:
+                    raise SushiError('decimated stream does not fit its buffer')
+                data[0, pos:pos + n_body] = resample_host(np.ascontiguousarray(samples, dtype=np.float32), framerate, sample_rate,
+                                                          n_body)
+                pos += n_body
+                n_full = rest = 0
             for length, count, start in ((chunk, n_full, 0), (rest, 1 if rest else 0, n_full * chunk)):
                 if count == 0 or length == 0:
                     continue
