@@ -5,6 +5,7 @@ stereo downmix of it.  Speech is centre-panned, so ``(L - R) / 2`` of a stereo f
 leaves what they share; 'stereo' folds a 5.1 / 7.1 layout down the way a stereo release was made.
 
 * ``channel_positions`` / ``weights_for`` -- named mixes as float32 weights per channel, from the file's speaker layout.
+* ``mean_host`` -- the reference's channel mean of a chunk's frames (what ``'mean'`` is on the CPU path).
 * ``mix_host`` -- the arithmetic of ``sushi_hip_load_decode_mix`` (include/sushi_hip.h) in NumPy, and the CPU path: bit for bit
   what the kernel writes.
 * ``compare_mixes`` / ``rank_mixes`` -- which mix matches best between two releases: probes of the source searched in the whole
@@ -114,6 +115,18 @@ def frames_from_bytes(data, channels, sample_width):
     out.view(np.uint8)[0::2] = raw[1::3]
     out.view(np.uint8)[1::2] = raw[2::3]
     return out.reshape(n, channels)
+
+
+def mean_host(frames):
+    """The reference's channel mean (wav.py:78-91) of int16 frames [n, C]: the channels as float32 summed left to right, the sum
+    divided by float(C) -- one channel: no division.  Returns float32[n]."""
+    s = frames.astype(np.float32)
+    acc = s[:, 0].copy()
+    for c in range(1, s.shape[1]):
+        acc += s[:, c]
+    if s.shape[1] > 1:
+        acc /= float(s.shape[1])
+    return acc
 
 
 def mix_host(frames, weights):

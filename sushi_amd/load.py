@@ -8,13 +8,14 @@ normalised stream never crosses PCIe twice: the device copy is handed to ``Devic
 """
 import ctypes
 import logging
-import math
 
 import numpy as np
 import torch
 
 from . import _native
-from .common import SushiError, py2_round
+from .common import SushiError
+from .row import row_layout
+from .wav import _check_args
 
 
 def _select(L, data, n, side, rank, hist, stream):
@@ -68,11 +69,11 @@ def decode_mix_on_device(L, staged, n_frames, channels, sample_width, weights, r
 def decode_file_on_device(wavfile, dev, weights=None, with_mean=False):
     """wav.py:64-91 on the GPU: the data chunk of `wavfile` (a DownmixedWavFile positioned at its first frame) is
     read UPLOAD_CHUNK_BYTES at a time, uploaded, decoded and downmixed by sushi_hip_load_decode into one float32
-    mono tensor.  Returns (tensor [frames], frames).  Host memory: one chunk of file bytes.
+    mono tensor.  Host memory: one chunk of file bytes.
     weights (float32 [n_out, channels], sushi_amd.downmix.weight_matrix): every chunk is still read and uploaded once, and one
-    sushi_hip_load_decode_mix launch on it writes all n_out weighted rows; with_mean=True adds the channel mean by the existing entry on
-    the same uploaded chunk.  Returns (mean tensor or None, rows tensor [n_out, frames], frames).  Device memory: one float32 row at
-    the file's frame rate per mix."""
+    sushi_hip_load_decode_mix launch on it writes all n_out weighted rows; the channel mean is then decoded only with with_mean=True,
+    by the existing entry on the same uploaded chunk.  Returns (mean tensor [frames] or None, rows tensor [n_out, frames] or None,
+    frames).  Device memory: one float32 row at the file's frame rate per mix."""
     L = _native.lib()
     frame_size = wavfile.frame_size
     if wavfile.sample_width not in (2, 3):
@@ -107,9 +108,19 @@ def decode_file_on_device(wavfile, dev, weights=None, with_mean=False):
                 decode_mix_on_device(L, staged, got, wavfile.channels_count, wavfile.sample_width, weights, rows, done, st)
             done += got
             del staged                                           # stream-ordered free: the kernels above are queued first
-    if weights is None:
-        return mono[:max(done, 1)], done                      # the frames that were there (n_raw of the pipeline)
-    return (None if mono is None else mono[:max(done, 1)]), rows[:, :max(done, 1)], done
+    keep = max(done, 1)                                       # the frames that were there (n_raw of the pipeline)
+    return (None if mono is None else mono[:keep]), (None if rows is None else rows[:, :keep]), done
+
+
+def mix_frames_on_device(frames, weights, dev):
+    """mix_host on the GPU for frames already in memory: int16 frames [n, channels] (C-contiguous) under the float32 weights
+    [n_out, channels] -> a float32 CUDA tensor [n_out, n] on `dev`.  One upload, one sushi_hip_load_decode_mix launch."""
+    n, channels = frames.shape
+    with torch.cuda.device(dev):
+        staged = torch.from_numpy(frames.reshape(-1).view(np.uint8)).to(dev)
+        rows = torch.empty((weights.shape[0], n), dtype=torch.float32, device=dev)
+        decode_mix_on_device(_native.lib(), staged, n, channels, 2, weights, rows, 0, torch.cuda.current_stream(dev).cuda_stream)
+    return rows
 
 
 def build_on_device(samples, framerate, frames_count, sample_rate, sample_type, device=None, read_chunk_size=1,
@@ -118,39 +129,28 @@ def build_on_device(samples, framerate, frames_count, sample_rate, sample_type, 
     `samples`: downmixed frames, a float32 host array or a float32 CUDA tensor (decode_file_on_device).
     resample='fir': the decimation step alone is sushi_hip_load_resample_fir (sushi_amd/resample.py) -- the same layout, a low-pass
     in front of the decimator; the medians, the normalisation and the hand-over are the code below either way."""
-    from .resample import check_mode, resample_device
-    check_mode(resample)
-    if sample_type not in ('float32', 'uint8'):
-        raise SushiError('Unknown sample type of WAV stream, must be uint8 or float32')
+    from .resample import resample_device
+    _check_args(sample_type, resample)
     L = _native.lib()
     on_device = isinstance(samples, torch.Tensor)
     dev = samples.device if on_device else \
         (torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device))
-    total_seconds = frames_count / float(framerate)
-    downsample_rate = sample_rate / float(framerate)
-    sample_count = math.ceil(total_seconds * sample_rate)
-    padding_size = 10 * framerate
-    total = int(padding_seconds * 2 * framerate + sample_count)
-    chunk = int(read_chunk_size * framerate)
     n_raw = int(samples.shape[0])
-    n_full, rest = divmod(n_raw, chunk)
-    nl_full = int(py2_round(chunk * downsample_rate))
-    nl_rest = int(py2_round(rest * downsample_rate)) if rest else 0
-    if downsample_rate != 1 and (nl_full <= 0):
+    lay = row_layout(n_raw, framerate, frames_count, sample_rate, read_chunk_size, padding_seconds)
+    total, padding_size = lay.total, lay.padding_size
+    if lay.downsample_rate != 1 and lay.nl_full <= 0:
         raise SushiError('sample rate too low for one-second chunks')
-    scale_full = 1.0 / (float(nl_full) / float(chunk)) if nl_full > 0 else 0.0
-    scale_rest = 1.0 / (float(nl_rest) / float(rest)) if nl_rest > 0 else 0.0
-    if total - 2 * padding_size < n_full * nl_full + nl_rest:
+    if total - 2 * padding_size < lay.n_body:
         raise SushiError('decimated stream does not fit its buffer')         # np.copyto would raise in the reference
     with torch.cuda.device(dev):
         st = torch.cuda.current_stream(dev).cuda_stream
         raw = samples if on_device else torch.from_numpy(np.ascontiguousarray(samples, dtype=np.float32)).to(dev)
         data = torch.empty(total, dtype=torch.float32, device=dev)
-        if resample == 'fir' and downsample_rate != 1:
-            resample_device(raw, framerate, sample_rate, n_full * nl_full + nl_rest, padding_size, total, out=data)
+        if resample == 'fir' and lay.downsample_rate != 1:
+            resample_device(raw, framerate, sample_rate, lay.n_body, padding_size, total, out=data)
         else:
-            _native.check(L.sushi_hip_load_resample(raw.data_ptr(), n_raw, chunk, nl_full, scale_full, n_full, rest, nl_rest,
-                                                    scale_rest, padding_size, total, data.data_ptr(), st),
+            _native.check(L.sushi_hip_load_resample(raw.data_ptr(), n_raw, lay.chunk, lay.nl_full, lay.scale_full, lay.n_full,
+                                                    lay.rest, lay.nl_rest, lay.scale_rest, padding_size, total, data.data_ptr(), st),
                           "sushi_hip_load_resample")
         hist = torch.empty(256, dtype=torch.int64, device=dev)
         max_value = _median(L, data, total, 0, hist, st) * 3
@@ -162,4 +162,4 @@ def build_on_device(samples, framerate, frames_count, sample_rate, sample_type, 
                       "sushi_hip_load_normalise")
         row = u8 if u8 is not None else data
         host = row.cpu().numpy().reshape(1, -1)
-    return host, row, sample_count, padding_size
+    return host, row, lay.sample_count, padding_size

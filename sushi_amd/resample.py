@@ -18,6 +18,7 @@ import numpy as np
 
 from . import _native
 from .common import SushiError
+from .row import fill_pads
 
 ZEROS = 16                   # zero crossings of the sinc on each side of its centre
 ROLLOFF = 0.9                # the cut-off as a fraction of the lower of the two Nyquist frequencies
@@ -149,9 +150,7 @@ def resample_device(tensor, fr, sr, n_body, pad=0, total=None, out=None):
         if num == den:
             out[pad:pad + n_body] = tensor[:n_body]
             out[pad + n_body:total - pad] = 0
-            if pad:
-                out[:pad] = out[pad]
-                out[total - pad:] = out[total - pad - 1]
+            fill_pads(out, pad)
             return out
         _, _, W, H = fir_table(fr, sr)
         table = torch.from_numpy(np.array(H)).to(dev)          # (a pageable upload: the bytes have left the host when it returns)

@@ -10,9 +10,12 @@ padding, the two medians, clip / scale / quantise on the GPU when one is present
 chunks; sushi_amd/load.py, csrc/sushi_load.hip) and otherwise in NumPy, chunk by chunk (``_build_host``,
 bit-identical; it is what the CPU tests compare with the reference-generated goldens).
 ``SUSHI_HIP_LOAD=host`` forces the NumPy pipeline.
+
+How a stream comes into being: every file is read by ``_load_mixes`` (one pass, one row of frames per mix), every row of frames
+becomes a stream's row in ``_build`` (the GPU or ``_build_host``; the numbers of the row's layout are ``row.row_layout``'s on both),
+and every finished row is taken over by ``_adopt``, which alone makes an instance a live stream.
 """
 import logging
-import math
 import os
 import struct
 import weakref
@@ -20,7 +23,8 @@ from time import time
 
 import numpy as np
 
-from .common import SushiError, clip, py2_round
+from .common import SushiError, clip
+from .row import fill_pads, row_layout
 
 WAVE_FORMAT_PCM = 0x0001
 WAVE_FORMAT_EXTENSIBLE = 0xFFFE
@@ -105,27 +109,11 @@ class DownmixedWavFile(object):
         return self._file.read(count * self.frame_size) if count else b''
 
     def _decode(self, data):
-        if self.sample_width == 2:
-            unpacked = np.frombuffer(data, dtype='<i2')
-        elif self.sample_width == 3:
-            raw_bytes = np.frombuffer(data, dtype=np.int8)
-            unpacked = np.zeros(len(data) // 3, np.int16)
-            unpacked.view(dtype='int8')[0::2] = raw_bytes[1::3]
-            unpacked.view(dtype='int8')[1::2] = raw_bytes[2::3]
-        else:
-            raise SushiError('Unsupported sample width: {0}'.format(self.sample_width))
-        unpacked = unpacked.astype('float32')
-        if self.channels_count == 1:
-            return unpacked
-        min_length = len(unpacked) // self.channels_count
-        if min_length * self.channels_count != len(unpacked):
+        from .downmix import mean_host
+        frames = self.frames_int16(data)
+        if (len(data) // self.sample_width) % self.channels_count:
             logging.error("Length of audio channels didn't match. This might result in broken output")
-        frames = unpacked[:min_length * self.channels_count].reshape(min_length, self.channels_count)
-        acc = frames[:, 0].copy()
-        for c in range(1, self.channels_count):     # same left-to-right float32 sum as the reference
-            acc += frames[:, c]
-        acc /= float(self.channels_count)
-        return acc
+        return mean_host(frames)
 
     def readframes(self, count):
         if not count:
@@ -135,18 +123,6 @@ class DownmixedWavFile(object):
     def read_bytes_into(self, view):
         """Fill `view` (a writable bytes-like object) with the next raw frame bytes; returns how many were read."""
         return self._file.readinto(view)
-
-    def read_into(self, out, chunk_frames):
-        """Decode and downmix the frames from the current position on into the float32 array `out`,
-        `chunk_frames` at a time (bounded host memory, like the reference's one-second reads).  Returns the frames read."""
-        done = 0
-        while done < out.shape[0]:
-            data = self.readframes(min(chunk_frames, out.shape[0] - done))
-            if data.shape[0] == 0:
-                break
-            out[done:done + data.shape[0]] = data
-            done += data.shape[0]
-        return done
 
 
 _live_streams = weakref.WeakSet()
@@ -158,9 +134,12 @@ def torch_device(device):
     return torch.device("cuda", torch.cuda.current_device()) if d.type == "cuda" and d.index is None else d
 
 
-def _check_resample(resample):
+def _check_args(sample_type, resample):
+    """What every way of building a stream checks before anything else."""
+    if sample_type not in ('float32', 'uint8'):
+        raise SushiError('Unknown sample type of WAV stream, must be uint8 or float32')
     from .resample import check_mode
-    return check_mode(resample)
+    check_mode(resample)
 
 
 def _is_mean(downmix):
@@ -194,58 +173,17 @@ class WavStream(object):
         downmix: 'mean' (the reference's channel average, wav.py:80-91), a named mix or one weight per channel
         (sushi_amd.downmix.weights_for): the channels are then mixed by weight in the decode -- on the GPU when there is one
         (sushi_hip_load_decode_mix), in NumPy otherwise, bit for bit the same -- and everything after it is unchanged."""
-        if sample_type not in ('float32', 'uint8'):
-            raise SushiError('Unknown sample type of WAV stream, must be uint8 or float32')
-        _check_resample(resample)
-        if not _is_mean(downmix):
-            self._load_mixes(path, [downmix], sample_rate, sample_type, device, first=self, resample=resample)
-            return
-        before_read = time()
-        stream = DownmixedWavFile(path)
-        try:
-            if self._use_gpu():
-                # decode + downmix on the GPU, the file uploaded in bounded chunks (sushi_amd/load.py)
-                from .load import build_on_device, decode_file_on_device
-                mono, got = decode_file_on_device(stream, torch_device("cuda" if device is None else device))
-                if got == 0:
-                    raise SushiError('no audio frames in the data chunk')
-                self._dev_row = None
-                self.data, self._dev_row, self.sample_count, self.padding_size = build_on_device(
-                    mono, stream.framerate, stream.frames_count, sample_rate, sample_type,
-                    read_chunk_size=self.READ_CHUNK_SIZE, padding_seconds=self.PADDING_SECONDS, resample=resample)
-                self.sample_rate = sample_rate
-            else:
-                samples = np.zeros(stream.frames_available, np.float32)
-                got = stream.read_into(samples, 10 * stream.framerate)
-                if got == 0:
-                    raise SushiError('no audio frames in the data chunk')
-                # a file shorter than its header says: the frames that exist are decimated as the reference does (a
-                # short last chunk by its own length, wav.py:127-134); what the reference leaves as uninitialised memory
-                # (np.empty, wav.py:119) is zero here
-                samples = samples[:got]
-                self._build_host(samples, stream.framerate, stream.frames_count, sample_rate, sample_type, resample)
-        except Exception as e:
-            raise SushiError('Error while loading {0}: {1}'.format(path, e))
-        finally:
-            stream.close()
-        self._device = device
-        self._dev = None
-        _live_streams.add(self)
-        logging.info('Done reading WAV {0} in {1}s'.format(path, time() - before_read))
+        _check_args(sample_type, resample)
+        self._load_mixes(path, [downmix], sample_rate, sample_type, device, resample, first=self)
 
     @classmethod
     def from_samples(cls, samples, framerate, sample_rate=12000, sample_type='uint8', device=None, resample='nearest'):
         """Build a stream from downmixed PCM samples already in memory (any real dtype; values as
         DownmixedWavFile would return them), running the same pipeline as the constructor."""
-        if sample_type not in ('float32', 'uint8'):
-            raise SushiError('Unknown sample type of WAV stream, must be uint8 or float32')
-        _check_resample(resample)
+        _check_args(sample_type, resample)
         self = cls.__new__(cls)
         samples = np.asarray(samples).astype(np.float32).reshape(-1)
-        self._build(samples, int(framerate), samples.shape[0], sample_rate, sample_type, resample)
-        self._device = device
-        self._dev = None
-        _live_streams.add(self)
+        self._build(samples, int(framerate), samples.shape[0], sample_rate, sample_type, resample, device)
         return self
 
     @classmethod
@@ -254,18 +192,16 @@ class WavStream(object):
         uploaded once and one decode launch per chunk serves every weighted mix ('mean' in the list: the existing decode on the same
         uploaded chunk).  At most 8 weighted mixes.  Memory: one float32 row at the FILE's frame rate per mix (in HBM on the GPU path)
         until the last of them has been decimated."""
-        if sample_type not in ('float32', 'uint8'):
-            raise SushiError('Unknown sample type of WAV stream, must be uint8 or float32')
-        _check_resample(resample)
+        _check_args(sample_type, resample)
         mixes = list(mixes)
         if not mixes:
             raise SushiError('load_mixes: at least one mix')
-        return cls._load_mixes(path, mixes, sample_rate, sample_type, device, resample=resample)
+        return cls._load_mixes(path, mixes, sample_rate, sample_type, device, resample)
 
     @classmethod
-    def _load_mixes(cls, path, mixes, sample_rate, sample_type, device, first=None, resample='nearest'):
-        """One stream per mix from one pass over the file; `first`: the instance to fill for mixes[0] (the constructor's).
-        resample: every mix row is decimated on its own, so 'fir' filters each separately."""
+    def _load_mixes(cls, path, mixes, sample_rate, sample_type, device, resample, first=None):
+        """One stream per mix from one pass over the file -- the one place a file is read; `first`: the instance to fill for
+        mixes[0] (the constructor's).  resample: every mix row is decimated on its own, so 'fir' filters each separately."""
         from .downmix import mix_host, weight_matrix
         before_read = time()
         stream = DownmixedWavFile(path)
@@ -275,15 +211,12 @@ class WavStream(object):
             with_mean = len(weighted) < len(mixes)
             W = weight_matrix([mixes[k] for k in weighted], stream.channels_count, stream.channel_mask) if weighted else None
             if cls._use_gpu():
-                from .load import build_on_device, decode_file_on_device
-                dev = torch_device("cuda" if device is None else device)
-                if W is None:
-                    mono, got = decode_file_on_device(stream, dev)
-                    rows = None
-                else:
-                    mono, rows, got = decode_file_on_device(stream, dev, weights=W, with_mean=with_mean)
+                # decode + downmix on the GPU, the file uploaded in bounded chunks (sushi_amd/load.py)
+                from .load import decode_file_on_device
+                mono, rows, got = decode_file_on_device(stream, torch_device("cuda" if device is None else device), weights=W,
+                                                        with_mean=with_mean)
             else:
-                # the NumPy path: the same single pass, ten seconds of frames at a time
+                # the NumPy path: the same single pass, ten seconds of frames at a time, into one row per mix
                 n = stream.frames_available
                 mono = np.zeros(n, np.float32) if with_mean else None
                 rows = np.zeros((len(weighted), n), np.float32) if weighted else None
@@ -301,27 +234,19 @@ class WavStream(object):
                     got += m
             if got == 0:
                 raise SushiError('no audio frames in the data chunk')
+            # a file shorter than its header says: the frames that exist are decimated as the reference does (a short last
+            # chunk by its own length, wav.py:127-134); what the reference leaves as uninitialised memory (np.empty,
+            # wav.py:119) is zero here
             for k, new in enumerate(streams):
                 samples = mono if k not in weighted else rows[weighted.index(k)]
-                samples = samples[:got]
-                new._dev_row = None
-                if cls._use_gpu():
-                    new.data, new._dev_row, new.sample_count, new.padding_size = build_on_device(
-                        samples, stream.framerate, stream.frames_count, sample_rate, sample_type,
-                        read_chunk_size=cls.READ_CHUNK_SIZE, padding_seconds=cls.PADDING_SECONDS, resample=resample)
-                    new.sample_rate = sample_rate
-                else:
-                    new._build_host(np.ascontiguousarray(samples), stream.framerate, stream.frames_count, sample_rate, sample_type,
-                                    resample)
+                new._build(samples[:got], stream.framerate, stream.frames_count, sample_rate, sample_type, resample, device)
         except Exception as e:
             raise SushiError('Error while loading {0}: {1}'.format(path, e))
         finally:
             stream.close()
-        for new in streams:
-            new._device = device
-            new._dev = None
-            _live_streams.add(new)
-        logging.info('Done reading WAV {0} ({1} mixes) in {2}s'.format(path, len(mixes), time() - before_read))
+        plain = first is not None and _is_mean(mixes[0])        # the reference's log line for what the reference loads
+        logging.info('Done reading WAV {0} in {1}s'.format(path if plain else '{0} ({1} mixes)'.format(path, len(mixes)),
+                                                          time() - before_read))
         return streams
 
     @classmethod
@@ -330,48 +255,22 @@ class WavStream(object):
         """Build a stream from PCM frames already in memory -- int16 [n, channels], as DownmixedWavFile.frames_int16 returns them --
         mixed by `downmix` ('mean', a named mix or weights; channel_mask: the speaker layout a named mix reads, None: the WAV default
         order), running the same pipeline as the constructor."""
-        from .downmix import mix_host, weight_matrix
-        if sample_type not in ('float32', 'uint8'):
-            raise SushiError('Unknown sample type of WAV stream, must be uint8 or float32')
-        _check_resample(resample)
+        from .downmix import mean_host, mix_host, weight_matrix
+        _check_args(sample_type, resample)
         frames = np.ascontiguousarray(frames)
         if frames.ndim != 2 or frames.dtype != np.int16 or frames.shape[0] < 1 or frames.shape[1] < 1:
             raise SushiError('from_channels: int16 frames [n, channels]')
-        n, channels = frames.shape
-        self = cls.__new__(cls)
         if _is_mean(downmix):
-            samples = frames.astype(np.float32)
-            acc = samples[:, 0].copy()
-            for c in range(1, channels):         # DownmixedWavFile._decode's sum and division
-                acc += samples[:, c]
-            if channels > 1:
-                acc /= float(channels)
-            samples = acc
+            samples = mean_host(frames)
         else:
-            W = weight_matrix([downmix], channels, channel_mask)
+            W = weight_matrix([downmix], frames.shape[1], channel_mask)
             if cls._use_gpu():
-                import torch
-                from . import _native
-                from .load import decode_mix_on_device
-                dev = torch_device("cuda" if device is None else device)
-                with torch.cuda.device(dev):
-                    staged = torch.from_numpy(frames.reshape(-1).view(np.uint8)).to(dev)
-                    rows = torch.empty((1, n), dtype=torch.float32, device=dev)
-                    decode_mix_on_device(_native.lib(), staged, n, channels, 2, W, rows, 0, torch.cuda.current_stream(dev).cuda_stream)
-                samples = rows[0]
+                from .load import mix_frames_on_device
+                samples = mix_frames_on_device(frames, W, torch_device("cuda" if device is None else device))[0]
             else:
                 samples = mix_host(frames, W)[0]
-        if isinstance(samples, np.ndarray):
-            self._build(samples, int(framerate), n, sample_rate, sample_type, resample)
-        else:
-            from .load import build_on_device
-            self.data, self._dev_row, self.sample_count, self.padding_size = build_on_device(
-                samples, int(framerate), n, sample_rate, sample_type, read_chunk_size=self.READ_CHUNK_SIZE,
-                padding_seconds=self.PADDING_SECONDS, resample=resample)
-            self.sample_rate = sample_rate
-        self._device = device
-        self._dev = None
-        _live_streams.add(self)
+        self = cls.__new__(cls)
+        self._build(samples, int(framerate), frames.shape[0], sample_rate, sample_type, resample, device)
         return self
 
     @classmethod
@@ -381,11 +280,7 @@ class WavStream(object):
         if data.ndim != 2 or data.shape[0] != 1 or data.dtype not in (np.dtype(np.uint8), np.dtype(np.float32)):
             raise SushiError('Unknown sample type of WAV stream, must be uint8 or float32')
         self = cls.__new__(cls)
-        self.data, self.sample_rate, self.sample_count, self.padding_size = data, sample_rate, sample_count, padding_size
-        self._dev_row = None
-        self._device = device
-        self._dev = None
-        _live_streams.add(self)
+        self._adopt(data, None, sample_rate, sample_count, padding_size, device)
         return self
 
     @staticmethod
@@ -400,64 +295,55 @@ class WavStream(object):
         except ImportError:
             return False
 
-    def _build(self, samples, framerate, frames_count, sample_rate, sample_type, resample='nearest'):
-        """wav.py:113-156: on the GPU if there is one (the normalised row then stays in HBM for the
-        matching), else in NumPy."""
-        self._dev_row = None
-        if not self._use_gpu():
-            return self._build_host(samples, framerate, frames_count, sample_rate, sample_type, resample)
+    def _adopt(self, data, dev_row, sample_rate, sample_count, padding_size, device):
+        """Become a live stream around a finished row -- every way of making a stream ends here.  data: the (1, N) host row;
+        dev_row: the same row as a CUDA tensor where the GPU built it (device_stream hands it on without an upload), else None;
+        device: where the matching is to run (None: the current device)."""
+        self.data, self._dev_row = data, dev_row
+        self.sample_rate, self.sample_count, self.padding_size = sample_rate, sample_count, padding_size
+        self._device, self._dev = device, None
+        _live_streams.add(self)
+
+    def _build(self, samples, framerate, frames_count, sample_rate, sample_type, resample='nearest', device=None):
+        """wav.py:113-156 on downmixed frames, a float32 host array or a float32 CUDA tensor: on the GPU if there is one -- a
+        tensor always, on its own device -- (the normalised row then stays in HBM for the matching), else in NumPy."""
+        if isinstance(samples, np.ndarray) and not self._use_gpu():
+            return self._build_host(samples, framerate, frames_count, sample_rate, sample_type, resample, device)
         from .load import build_on_device
-        self.data, self._dev_row, self.sample_count, self.padding_size = build_on_device(
+        data, dev_row, sample_count, padding_size = build_on_device(
             samples, framerate, frames_count, sample_rate, sample_type,
             read_chunk_size=self.READ_CHUNK_SIZE, padding_seconds=self.PADDING_SECONDS, resample=resample)
-        self.sample_rate = sample_rate
+        self._adopt(data, dev_row, sample_rate, sample_count, padding_size, device)
 
     # wav.py:113-156 (value pipeline) in NumPy, whole-stream instead of chunk-by-chunk
-    def _build_host(self, samples, framerate, frames_count, sample_rate, sample_type, resample='nearest'):
-        _check_resample(resample)
-        self._dev_row = None
-        total_seconds = frames_count / float(framerate)
-        downsample_rate = sample_rate / float(framerate)
-        self.sample_count = math.ceil(total_seconds * sample_rate)
-        self.sample_rate = sample_rate
-        self.padding_size = 10 * framerate
-        data = np.zeros((1, int(self.PADDING_SECONDS * 2 * framerate + self.sample_count)), np.float32)
-        chunk = int(self.READ_CHUNK_SIZE * framerate)
-        pos = self.padding_size
-        if downsample_rate == 1:
+    def _build_host(self, samples, framerate, frames_count, sample_rate, sample_type, resample='nearest', device=None):
+        _check_args(sample_type, resample)
+        lay = row_layout(samples.shape[0], framerate, frames_count, sample_rate, self.READ_CHUNK_SIZE, self.PADDING_SECONDS)
+        data = np.zeros((1, lay.total), np.float32)
+        pos = lay.padding_size
+        if lay.downsample_rate == 1:
             data[0, pos:pos + samples.shape[0]] = samples
-            pos += samples.shape[0]
+        elif resample == 'fir':
+            # the nearest path's body length, filled by the filter instead (sushi_amd/resample.py): same layout, same time axis
+            from .resample import resample_host
+            if lay.n_body > lay.total - 2 * lay.padding_size:
+                raise SushiError('decimated stream does not fit its buffer')
+            data[0, pos:pos + lay.n_body] = resample_host(np.ascontiguousarray(samples, dtype=np.float32), framerate, sample_rate,
+                                                          lay.n_body)
         else:
             # cv2.resize(..., INTER_NEAREST) per one-second chunk (wav.py:125-137):
             # x_ofs[x] = min(floor(x * (1 / (new_len / len))), len - 1)
-            n_full, rest = divmod(samples.shape[0], chunk)
-            if resample == 'fir':
-                # the nearest path's body length, filled by the filter instead (sushi_amd/resample.py): same layout, same time axis
-                from .resample import resample_host
-                nl_full = max(int(py2_round(chunk * downsample_rate)), 0)
-                nl_rest = max(int(py2_round(rest * downsample_rate)), 0) if rest else 0
-                n_body = n_full * nl_full + nl_rest
-                if n_body > data.shape[1] - 2 * self.padding_size:
-                    raise SushiError('decimated stream does not fit its buffer')
-                data[0, pos:pos + n_body] = resample_host(np.ascontiguousarray(samples, dtype=np.float32), framerate, sample_rate,
-                                                          n_body)
-                pos += n_body
-                n_full = rest = 0
-            for length, count, start in ((chunk, n_full, 0), (rest, 1 if rest else 0, n_full * chunk)):
-                if count == 0 or length == 0:
+            for length, count, start, new_length, scale_x in ((lay.chunk, lay.n_full, 0, lay.nl_full, lay.scale_full),
+                                                              (lay.rest, 1, lay.n_full * lay.chunk, lay.nl_rest, lay.scale_rest)):
+                if count == 0 or new_length == 0:
                     continue
-                new_length = int(py2_round(length * downsample_rate))
-                if new_length <= 0:
-                    continue
-                scale_x = 1.0 / (float(new_length) / float(length))
                 sx = np.minimum(np.floor(np.arange(new_length, dtype=np.float64) * scale_x).astype(np.int64),
                                 length - 1)
                 block = samples[start:start + count * length].reshape(count, length)[:, sx]
                 data[0, pos:pos + count * new_length] = block.reshape(-1)
                 pos += count * new_length
         # padding the audio from both sides
-        data[0][0:self.padding_size].fill(data[0][self.padding_size])
-        data[0][-self.padding_size:].fill(data[0][-self.padding_size - 1])
+        fill_pads(data[0], lay.padding_size)
         # normalizing; also clipping the stream by 3*median value from both sides of zero
         max_value = float(np.median(data[data >= 0])) * 3
         min_value = float(np.median(data[data <= 0])) * 3
@@ -468,7 +354,7 @@ class WavStream(object):
             data *= 255.0
             data += 0.5
             data = data.astype('uint8')
-        self.data = data
+        self._adopt(data, None, sample_rate, lay.sample_count, lay.padding_size, device)
 
     # ------------------------------------------------------------------ reference API
     @property
@@ -493,7 +379,7 @@ class WavStream(object):
         """The HBM mirror of self.data (created on first use)."""
         if self._dev is None:
             from .device import DeviceStream
-            row = getattr(self, "_dev_row", None)
+            row = self._dev_row
             if row is not None and (self._device is None or str(row.device) == str(torch_device(self._device))):
                 self._dev = DeviceStream(row)           # already in HBM (GPU load pipeline): no H2D
             else:
@@ -690,34 +576,23 @@ class WavStream(object):
             raise SushiError('retimed: the stream has no body inside its row')
         new_count = ((count - 1) * s.numerator) // s.denominator + 1
         segment = [speed_segment(s, pad, pad, new_count)]
-        new = self.__class__.__new__(self.__class__)
-        new._dev_row = None
         if self._use_gpu():
             import torch
             dev = torch_device("cuda" if self._device is None else self._device)
             if self._dev is not None and self._dev.device == dev:
                 row = self._dev.raw
-            elif getattr(self, "_dev_row", None) is not None and self._dev_row.device == dev:
+            elif self._dev_row is not None and self._dev_row.device == dev:
                 row = self._dev_row
             else:
                 row = torch.from_numpy(self.data[0]).to(dev)
             with torch.cuda.device(dev):
-                out = torch.empty(2 * pad + new_count, dtype=row.dtype, device=dev)
-                retime_device(row, segment, out=out)
-                if pad:
-                    out[:pad] = out[pad]
-                    out[pad + new_count:] = out[pad + new_count - 1]
-                new.data = out.cpu().numpy().reshape(1, -1)
-            new._dev_row = out
+                dev_row = retime_device(row, segment, out=torch.empty(2 * pad + new_count, dtype=row.dtype, device=dev))
+                fill_pads(dev_row, pad)
+                data = dev_row.cpu().numpy().reshape(1, -1)
         else:
-            out = np.zeros(2 * pad + new_count, self.data.dtype)
-            retime_host(self.data[0], segment, out=out)
-            if pad:
-                out[:pad] = out[pad]
-                out[pad + new_count:] = out[pad + new_count - 1]
-            new.data = out.reshape(1, -1)
-        new.sample_rate, new.sample_count, new.padding_size = self.sample_rate, new_count, self.padding_size
-        new._device = self._device
-        new._dev = None
-        _live_streams.add(new)
+            dev_row = None
+            data = retime_host(self.data[0], segment, out=np.zeros(2 * pad + new_count, self.data.dtype)).reshape(1, -1)
+            fill_pads(data[0], pad)
+        new = self.__class__.__new__(self.__class__)
+        new._adopt(data, dev_row, self.sample_rate, new_count, self.padding_size, self._device)
         return new
