@@ -9,11 +9,13 @@ regenerate it only for a change that is MEANT to change a plan, and say so.  Nee
 import json
 import os
 import subprocess
+import sys
 import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(HERE, "plan_cases.json")
-SRC = os.path.join(os.path.dirname(HERE), "host_plan_check.cpp")
+sys.path.insert(0, os.path.dirname(HERE))
+from host_checks import build_check  # noqa: E402
 
 
 def dump_cases(exe):
@@ -24,9 +26,7 @@ def dump_cases(exe):
 
 def main():
     with tempfile.TemporaryDirectory() as tmp:
-        exe = os.path.join(tmp, "host_plan_check")
-        subprocess.check_call(["g++", "-O2", "-std=c++17", SRC, "-o", exe])
-        cases = dump_cases(exe)
+        cases = dump_cases(build_check("host_plan_check", tmp))
     with open(OUT, "w") as f:
         f.write('{"generator":"tests/golden/gen_plan_golden.py","cases":[\n')
         f.write(",\n".join(json.dumps(c, separators=(",", ":")) for c in cases))

@@ -8,18 +8,18 @@ MEANT to change a decision, and say so.  Needs g++ only.
 """
 import os
 import subprocess
+import sys
 import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(HERE, "policy_trace.json")
-SRC = os.path.join(os.path.dirname(HERE), "host_policy_check.cpp")
+sys.path.insert(0, os.path.dirname(HERE))
+from host_checks import build_check  # noqa: E402
 
 
 def main():
     with tempfile.TemporaryDirectory() as tmp:
-        exe = os.path.join(tmp, "host_policy_check")
-        subprocess.check_call(["g++", "-O2", "-std=c++17", SRC, "-o", exe])
-        out = subprocess.check_output([exe, "--dump"])
+        out = subprocess.check_output([build_check("host_policy_check", tmp), "--dump"])
     with open(OUT, "wb") as f:
         f.write(out)
     print(OUT, len(out.splitlines()), "runs", len(out), "bytes")

@@ -10,11 +10,11 @@ import numpy as np
 import pytest
 
 import downmix_cases as cases
+from host_checks import build_check
 from sushi_amd import _native, downmix
 from sushi_amd.common import SushiError
 from sushi_amd.wav import DownmixedWavFile, WavStream
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 F = np.float32
 A, B = F(0.70710678), F(0.35355339)
 
@@ -143,10 +143,7 @@ def test_half_half_is_the_mean_of_stereo(tmp_path, width):
 # ---------------------------------------------------------------------------------------------- the kernel's arithmetic on the CPU
 @pytest.fixture(scope="module")
 def host_check(tmp_path_factory):
-    exe = os.path.join(tmp_path_factory.mktemp("downmix"), "host_downmix_check")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", os.path.join(HERE, "host_downmix_check.cpp"), "-o", exe])
-    return exe
+    return build_check("host_downmix_check", tmp_path_factory.mktemp("downmix"))
 
 
 @pytest.mark.parametrize("width", [2, 3])

@@ -1,19 +1,17 @@
 """The FFT path's device code that can run on the CPU: sushi_amd/csrc/fft_core.hpp (workgroup
 FFT, emulated one thread at a time) and mac_core.hpp (ring-buffered frequency-domain
 multiply-accumulate), compiled with g++ and checked against float64 definitions."""
-import os
+import hashlib
 import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+from host_checks import build_check
 
 
 def _build_and_run(tmp_path, name):
-    exe = os.path.join(tmp_path, name)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", os.path.join(HERE, name + ".cpp"), "-o", exe])
-    return subprocess.run([exe], capture_output=True, text=True)
+    return subprocess.run([build_check(name, tmp_path)], capture_output=True, text=True)
 
 
 def test_workgroup_fft_on_host(tmp_path):
@@ -46,6 +44,22 @@ def test_twiddle_table_is_correctly_rounded():
     k = np.arange(16384)
     assert (vals[0::2].astype(np.float32) == np.cos(2 * np.pi * k / 16384).astype(np.float32)).all()
     assert (vals[1::2].astype(np.float32) == (-np.sin(2 * np.pi * k / 16384)).astype(np.float32)).all()
+
+
+DFT16_TABLES = {    # file: (length, sha256), computed once from the three separate writers these tables came from
+    "_gen_dft16_f16.inc": (13312, "707e6278d0566bbc1e62bd7a08fd85d292719d43f0dcdf519821d1c6cc5077a4"),
+    "_gen_dft16_f16_bound.inc": (6656, "eb7f89d612375f3d31ebe0f2d85cd31727fdaeeb7d13788007c2a37b406297f5"),
+    "_gen_dft16_f16_bound_low.inc": (3328, "98aca06c01de8a1a20b21dbf7a8ef406c3f489912b565e6ea8e8c0e2614ee436"),
+}
+
+
+@pytest.mark.parametrize("name", sorted(DFT16_TABLES))
+def test_dft16_operand_tables_are_the_recorded_ones(name):
+    from sushi_amd import build
+    assert sorted(t[0] for t in build.DFT16_TABLES) == sorted(DFT16_TABLES)
+    (table,) = [t for t in build.DFT16_TABLES if t[0] == name]
+    text = build._dft16_table(*table[1:]).encode()
+    assert (len(text), hashlib.sha256(text).hexdigest()) == DFT16_TABLES[name]
 
 
 @pytest.mark.parametrize("ratio", [2, 4])

@@ -24,19 +24,49 @@ def test_library_builds_and_exports_all_declared_symbols():
 
 
 def test_every_source_file_is_in_the_build_lists():
-    """A unit missing from build.UNITS is never compiled; a header or part missing from the dependency lists leaves a stale
-    library without an error when it is edited."""
+    """A unit missing from build.UNITS is never compiled; a header or part that no unit's scan reaches is dead, and one reached by
+    another unit than the one that includes it would leave a stale library without an error when it is edited."""
     names = set(os.listdir(build.CSRC))
-    units = {name + ".hip" for name, _flags, _extra in build.UNITS}
-    assert {f for f in names if f.endswith(".hip")} == units
-    deps = {os.path.abspath(p) for p in build.COMMON_DEPS}
-    for _name, _flags, extra in build.UNITS:
-        deps |= {os.path.abspath(p) for p in extra}
-    assert os.path.abspath(build.HEADER) in deps
+    deps = {name: {os.path.relpath(p, build.CSRC) for p in build.unit_deps(name)} for name, _flags in build.UNITS}
+    assert {f for f in names if f.endswith(".hip")} == {name + ".hip" for name in deps}
+    header = os.path.relpath(build.HEADER, build.CSRC)
+    assert all(header in d and name + ".hip" in d for name, d in deps.items())
     written = sorted(f for f in names if f.endswith(".hpp") or (f.endswith(".inc") and not f.startswith("_gen_")))
     assert len(written) >= 14                       # (the listing saw the directory: 5 headers and 9 parts of the FFT unit)
-    missing = [f for f in written if os.path.abspath(os.path.join(build.CSRC, f)) not in deps]
-    assert missing == []
+    assert [f for f in written if not any(f in d for d in deps.values())] == []
+    # the scan is per unit: two units' exact sets
+    common = {header, "sushi_common.hpp", "sushi_internal.hpp", "sushi_geometry.hpp"}
+    generated = {os.path.relpath(p, build.CSRC) for p, _writer in build.GENERATED}
+    assert len(generated) == 4 and all(f.startswith("_gen_") for f in generated)
+    assert deps["sushi_load"] == common | {"sushi_load.hip", "downmix_core.hpp"}
+    parts = {"sushi_fft_%s.inc" % s for s in ("store", "spectra", "mac", "ifft", "bound", "collect", "plan", "threshold", "best")}
+    assert deps["sushi_fft"] == common | generated | parts | {"sushi_fft.hip", "fft_core.hpp", "mac_core.hpp", "plan_core.hpp",
+                                                               "run_policy.hpp"}
+
+
+def test_unit_deps_on_a_small_tree(tmp_path, monkeypatch):
+    """a.hip -> b.inc -> c.hpp and a generated table that is not written yet; an include that resolves nowhere; a cycle."""
+    tree = str(tmp_path)
+    monkeypatch.setattr(build, "GENERATED", build.GENERATED + [(os.path.join(tree, "_gen_x.inc"), None)])
+
+    def write(name, *includes):
+        with open(os.path.join(tree, name), "w") as f:
+            f.write("// %s\n" % name + "".join('#include "%s"\n' % i for i in includes) + "#include <vector>\n")
+
+    write("a.hip", "b.inc", "_gen_x.inc")
+    write("b.inc", "sub/../c.hpp")
+    write("c.hpp")
+    assert sorted(os.path.relpath(p, tree) for p in build.unit_deps("a", tree)) == ["_gen_x.inc", "a.hip", "b.inc", "c.hpp"]
+    assert not os.path.exists(os.path.join(tree, "_gen_x.inc"))
+    write("c.hpp", "a.hip", "b.inc")                                    # a cycle: the same closure
+    assert sorted(os.path.relpath(p, tree) for p in build.unit_deps("a", tree)) == ["_gen_x.inc", "a.hip", "b.inc", "c.hpp"]
+    write("c.hpp", "gone.hpp")
+    with pytest.raises(FileNotFoundError) as e:
+        build.unit_deps("a", tree)
+    assert os.path.join(tree, "c.hpp") in str(e.value) and '"gone.hpp"' in str(e.value)
+    write("c.hpp", "_gen_y.inc")                                        # a _gen_ name that is not listed is an ordinary include
+    with pytest.raises(FileNotFoundError):
+        build.unit_deps("a", tree)
 
 
 def test_host_only_entry_points():

@@ -8,21 +8,15 @@ import subprocess
 import numpy as np
 import pytest
 
+from host_checks import build_check
 from sushi_amd import _native
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "host_plan_check.cpp")
-
-
-def _build(tmp_path, flags, name="host_plan_check"):
-    exe = os.path.join(tmp_path, name)
-    subprocess.check_call(["g++", "-std=c++17"] + flags + [SRC, "-o", exe])
-    return exe
 
 
 @pytest.fixture(scope="module")
 def check_exe(tmp_path_factory):
-    return _build(str(tmp_path_factory.mktemp("plan_check")), ["-O2"])
+    return build_check("host_plan_check", tmp_path_factory.mktemp("plan_check"))
 
 
 @pytest.fixture(scope="module")
@@ -70,6 +64,6 @@ def test_library_sizes_every_case_as_recorded(check_exe, golden, tmp_path):
 
 def test_checks_are_clean_under_address_and_undefined_sanitizers(tmp_path):
     """The same program with its own sanitizer runtime, run stand-alone (no environment, no preload): exit 0, nothing on stderr."""
-    exe = _build(str(tmp_path), ["-O1", "-g", "-fsanitize=address,undefined"], "host_plan_check_san")
+    exe = build_check("host_plan_check", tmp_path, sanitize=True)
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0 and r.stderr == "", r.stdout + r.stderr

@@ -7,19 +7,14 @@ import subprocess
 
 import pytest
 
+from host_checks import build_check
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "host_policy_check.cpp")
-
-
-def _build(tmp_path, flags, name="host_policy_check"):
-    exe = os.path.join(tmp_path, name)
-    subprocess.check_call(["g++", "-std=c++17"] + flags + [SRC, "-o", exe])
-    return exe
 
 
 @pytest.fixture(scope="module")
 def check_exe(tmp_path_factory):
-    return _build(str(tmp_path_factory.mktemp("policy_check")), ["-O2"])
+    return build_check("host_policy_check", tmp_path_factory.mktemp("policy_check"))
 
 
 def test_every_rule_passes_its_checks(check_exe):
@@ -47,7 +42,7 @@ def test_dump_equals_the_recorded_decisions(check_exe):
 
 def test_checks_are_clean_under_address_and_undefined_sanitizers(tmp_path):
     """The same program with its own sanitizer runtime, run stand-alone (no environment, no preload): exit 0, nothing on stderr."""
-    exe = _build(str(tmp_path), ["-O1", "-g", "-fsanitize=address,undefined"], "host_policy_check_san")
+    exe = build_check("host_policy_check", tmp_path, sanitize=True)
     for args in ([], ["--dump"]):
         r = subprocess.run([exe] + args, capture_output=True, text=True)
         assert r.returncode == 0 and r.stderr == "", r.stdout[-2000:] + r.stderr

@@ -10,10 +10,10 @@ import numpy as np
 import pytest
 
 import resample_cases as cases
+from host_checks import build_check
 from sushi_amd import _native, resample
 from sushi_amd.common import SushiError, py2_round
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 TRIPLES = {(48000, 12000): (4, 1, 72), (44100, 12000): (147, 40, 66), (44100, 8000): (441, 80, 98), (22050, 12000): (147, 80, 33),
            (96000, 12000): (8, 1, 143), (32000, 12000): (8, 3, 48), (11025, 12000): (147, 160, 18), (8000, 12000): (2, 3, 18)}
 
@@ -204,10 +204,7 @@ def test_resample_fir_entry_point_validates_before_any_hip_call():
 # ---------------------------------------------------------------------------------------------- the kernel's arithmetic on the CPU
 @pytest.fixture(scope="module")
 def host_check(tmp_path_factory):
-    exe = os.path.join(tmp_path_factory.mktemp("resample"), "host_resample_check")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", os.path.join(HERE, "host_resample_check.cpp"), "-o", exe])
-    return exe
+    return build_check("host_resample_check", tmp_path_factory.mktemp("resample"))
 
 
 @pytest.mark.parametrize("rates", [(48000, 12000), (44100, 12000), (44100, 8000), (11025, 12000)])

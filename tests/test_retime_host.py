@@ -9,6 +9,7 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+from host_checks import build_check
 from sushi_amd import _native, retime, synth
 from sushi_amd.common import SushiError
 
@@ -196,10 +197,7 @@ def test_retime_segment_layout_matches_header(tmp_path):
 # ---------------------------------------------------------------------------------------------- the kernel's arithmetic on the CPU
 @pytest.fixture(scope="module")
 def host_check(tmp_path_factory):
-    exe = os.path.join(tmp_path_factory.mktemp("retime"), "host_retime_check")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", os.path.join(HERE, "host_retime_check.cpp"), "-o", exe])
-    return exe
+    return build_check("host_retime_check", tmp_path_factory.mktemp("retime"))
 
 
 @pytest.mark.parametrize("dtype", [np.uint8, np.float32])

@@ -41,20 +41,32 @@ def tree_of(spec, scratch):
     return out
 
 
+# what `tree`'s own build.py is asked, in a process of its own (argv: unit, output file)
+ASSEMBLE = """
+import subprocess, sys
+from sushi_amd import build as b
+unit, out = sys.argv[1:]
+if hasattr(b, "compile_command"):
+    b.write_generated()
+    cmd = b.compile_command(unit, out, "asm")
+else:       # a commit before build.compile_command: its four writers by name, its flags from UNITS, the command spelled out
+    b.write_twiddles(); b.write_dft16_operands(); b.write_dft16_bound_operands(); b.write_dft16_bound_low_operands()
+    flags = next(u[1] for u in b.UNITS if u[0] == unit)
+    cmd = [b._hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall"] + flags + \\
+          ["--cuda-device-only", "-S", b.CSRC + "/" + unit + ".hip", "-o", out]
+sys.exit(subprocess.call(cmd))
+"""
+
+
 def assembly(tree, unit, out):
     """Device assembly of one unit of `tree`, by that tree's own build.py (its flags, its generated tables)."""
-    code = ("from sushi_amd import build as b; import subprocess, sys\n"
-            "b.write_twiddles(); b.write_dft16_operands(); b.write_dft16_bound_operands(); b.write_dft16_bound_low_operands()\n"
-            "flags = next(f for n, f, _ in b.UNITS if n == sys.argv[1])\n"
-            "sys.exit(subprocess.call([b._hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fvisibility=hidden',\n"
-            "                          '-Wall'] + flags + ['--cuda-device-only', '-S', b.CSRC + '/' + sys.argv[1] + '.hip', '-o', sys.argv[2]]))\n")
-    subprocess.check_call([sys.executable, "-c", code, unit, out], cwd=tree)
+    subprocess.check_call([sys.executable, "-c", ASSEMBLE, unit, out], cwd=tree)
     return open(out).read()
 
 
 def units_of(tree):
-    """The unit names of `tree`'s own build.UNITS."""
-    code = "from sushi_amd import build as b; print(' '.join(n for n, _, _ in b.UNITS))"
+    """The unit names of `tree`'s own build.UNITS ((name, flags) pairs; (name, flags, deps) before build.unit_deps)."""
+    code = "from sushi_amd import build as b; print(' '.join(u[0] for u in b.UNITS))"
     return subprocess.check_output([sys.executable, "-c", code], cwd=tree, text=True).split()
 
 

@@ -5,17 +5,17 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from sushi_amd import build  # noqa: E402
 
 unit = sys.argv[1]
-flags = next(f for n, f, _ in build.UNITS if n == unit)
-cmd = [build._hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall"] + flags + \
-      sys.argv[2:] + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(build.CSRC, unit + ".hip"), "-o", "/tmp/_kr.o"]
-build.write_twiddles()
-err = subprocess.run(cmd, capture_output=True, text=True).stderr
+build.write_generated()
+with tempfile.TemporaryDirectory() as tmp:
+    cmd = build.compile_command(unit, os.path.join(tmp, unit + ".o"), "remarks", extra=sys.argv[2:])
+    err = subprocess.run(cmd, capture_output=True, text=True).stderr
 rows, cur = [], None
 for line in err.splitlines():
     m = re.search(r"remark: +(?:Function )?Name: (\S+)", line)
