@@ -228,8 +228,11 @@ SUSHI_HIP_API int sushi_hip_batch_create(const SushiHipStream* dst, const SushiH
 /* The same handle for OTHER requests (equally many, same streams, path and settings): descriptors, plan and schedule are redone
  * in place and uploaded in one copy -- what a caller that issues one small batch after another (sushi.calculate_shifts: one
  * find_substream call at a time, sushi.py:432,450-452) does instead of destroy + create.  ENOSPACE if the new requests need more
- * than the memory the batch was created in (the handle is then unchanged and still runs its old requests); a run still in flight on
- * another stream than `hip_stream` must have finished.  What the batch had learnt about its searches (exclusion form, suspension) is reset. */
+ * than the memory the batch was created in (the handle is then unchanged and still runs its old requests); so is it after EINVAL,
+ * and after an ELAUNCH from the wait for the previous upload.  Only the new plan's own upload comes after the point of no return:
+ * if the HIP runtime rejects that copy (ELAUNCH), the handle holds a plan the device has not got -- every run entry point returns
+ * EINVAL until a sushi_hip_batch_reset succeeds.  A run still in flight on another stream than `hip_stream` must have finished.
+ * What the batch had learnt about its searches (exclusion form, suspension) is reset. */
 SUSHI_HIP_API int sushi_hip_batch_reset(SushiHipBatch* batch, const SushiHipRequest* req_host, int n, void* hip_stream);
 SUSHI_HIP_API int sushi_hip_batch_info(const SushiHipBatch* batch, SushiHipBatchInfo* info);
 /* Matching method of the following runs (default after create: SUSHI_HIP_METHOD_SQDIFF_NORMED).

@@ -38,7 +38,8 @@ UNITS = [
     # a low-pass in front of the load pipeline's decimator: polyphase FIR at the file's rate (resample_core.hpp)
     ("sushi_resample", ["-ffp-contract=off"]),  # float64 taps: product and sum round separately, as NumPy's
     # overlap-save FFT path; its parts, by stage, are csrc/sushi_fft_*.inc (included inside its anonymous namespace); the plan of
-    # a batch (plan_core.hpp) and what a run decides (run_policy.hpp) are host only
+    # a batch (plan_core.hpp), what a handle holds about its requests and how it is staged (batch_core.hpp) and what a run decides
+    # (run_policy.hpp) are host only
     # -fno-slp-vectorize: the SLP pass packs the complex MACs into v_pk_fma_f32 and pays for it in
     # register shuffles (v_mov / accvgpr traffic); plain v_fma_f32 already issues at the f32 peak rate.
     ("sushi_fft", ["-fno-slp-vectorize"]),

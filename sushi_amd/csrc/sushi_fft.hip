@@ -41,6 +41,9 @@
 //   sushi_geometry.hpp     (a header: every unit's) the sizes and records host plan and device code agree on
 //   plan_core.hpp          (a header: host only, checked on the CPU by tests/host_plan_check.cpp) the plan of a batch, its
 //                          workspace and device-memory layouts, parse_bound_fault, ranking_key
+//   batch_core.hpp         (a header: host only, checked on the CPU by tests/host_batch_check.cpp) what a handle holds about its
+//                          requests and how it is staged: BatchPlanState, stage_batch, PlanCache, resolve_variant, the spans a run
+//                          uploads and clears
 //   run_policy.hpp         (a header: host only, checked on the CPU by tests/host_policy_check.cpp) what a run decides from the
 //                          exclusion mode and from what earlier runs left: Learnt, LastRun, one function per rule
 //   sushi_fft_store.inc    packed-half storage: scales, stored bin order, the low band of a row and the norms outside it
@@ -53,7 +56,8 @@
 //   sushi_fft_threshold.inc  the threshold run's own kernels: seed, audit, extension, output scan
 //   sushi_fft_best.inc     the best-K run's own kernels: seed, escalation, audit, extension
 //   sushi_fft_plan.inc     host: launches by method / sample type, stage timing, a sub-batch's view of the batch's memory (SubView)
-//   (this file)            the batch handle, the skeleton of a run around its sub-batches (run_sub_batches) and the C ABI's entry points
+//   (this file)            the batch handle and the HIP calls of its life (plan_and_upload: stage, wait, commit, upload), the skeleton
+//                          of a run around its sub-batches (run_sub_batches) and the C ABI's entry points
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -78,6 +82,7 @@
 #include "fft_core.hpp"
 #include "mac_core.hpp"
 #include "plan_core.hpp"
+#include "batch_core.hpp"
 #include "run_policy.hpp"
 
 namespace {
@@ -167,14 +172,13 @@ struct SushiHipBatch {
     bool stats_pending = false;
     int32_t* packed_out = nullptr;      // NULL, or where every run ALSO leaves its results as 8-byte (index, score bits) records
     int32_t* early_out = nullptr;       // NULL, or sushi_hip_batch_set_early_output's 16-byte records (memory host and device both touch)
-    int64_t n_tiles = 0;
-    std::vector<SearchDesc> descs;
-    Plan plan;
-    BatchLayout lay = {};
-    std::vector<char> upload;           // descriptors | schedule | work items as they lie in `mem`: one copy per (re)plan
+    // what it holds about its requests (batch_core.hpp): `now` is what runs; the next requests are staged into `spare`, and the two
+    // change places once nothing can refuse them any more (plan_and_upload)
+    BatchPlanState states[2];
+    BatchPlanState *now = &states[0], *spare = &states[1];
+    bool planned = false;               // false: a plan was taken but its upload failed -- no run until a reset succeeds
     size_t mem_bytes = 0, ws_cap = 0;   // what the caller gave: a re-plan (sushi_hip_batch_reset) must fit it
     char* mem = nullptr;
-    double flops = 0.0, algorithmic_bytes = 0.0;
     hipStream_t last_stream = nullptr;
     hipEvent_t uploaded = nullptr;      // recorded on the create-time stream behind the descriptor / plan uploads
     // lanes (plan_core.hpp): lane 0 is the stream a run is given; the others are the batch's own, forked off it behind the
@@ -197,8 +201,8 @@ struct SushiHipBatch {
 };
 
 static SubView last_sub(const SushiHipBatch* b) {                // (of the last run)
-    const std::vector<SubBatch>& subs = b->last.whole_cut ? b->plan.subs_whole : b->plan.subs;
-    return SubView(b->mem, b->lay, b->plan.ws_lane, subs.back(), subs.size() - 1);
+    const std::vector<SubBatch>& subs = b->last.whole_cut ? b->now->plan.subs_whole : b->now->plan.subs;
+    return SubView(b->mem, b->now->lay, b->now->plan.ws_lane, subs.back(), subs.size() - 1);
 }
 
 // What the stages of one run read besides their sub-batch: the batch, its streams and device memory, the run's own settings.
@@ -218,9 +222,9 @@ struct RunCtx {
     RunCtx(SushiHipBatch* bb, double d) : b(bb), dst(bb->dst), src(bb->src), delta(d), method(bb->method) {
         r = StreamRefs{dst->xc, dst->s1, dst->s2, dst->n, src->xc, src->s1, src->s2, src->n, sushi_hip_centre(dst->dtype), dst->raw, src->raw,
                        dst->dtype};
-        searches = (const SearchDesc*)(b->mem + b->lay.desc); keys = (unsigned long long*)(b->mem + b->lay.keys); gkeys = keys + b->n;
-        flags = (int*)(b->mem + b->lay.flags); flag_list = (int*)(b->mem + b->lay.flag_list); viol = (int*)(b->mem + b->lay.viol);
-        counters = (RunCounters*)(b->mem + b->lay.counters);
+        searches = (const SearchDesc*)(b->mem + b->now->lay.desc); keys = (unsigned long long*)(b->mem + b->now->lay.keys); gkeys = keys + b->n;
+        flags = (int*)(b->mem + b->now->lay.flags); flag_list = (int*)(b->mem + b->now->lay.flag_list); viol = (int*)(b->mem + b->now->lay.viol);
+        counters = (RunCounters*)(b->mem + b->now->lay.counters);
     }
 };
 
@@ -262,26 +266,24 @@ struct RunForm { bool suspended; const std::vector<SubBatch>* subs; int lanes; }
 static int run_form(SushiHipBatch* b, unsigned run_seq, hipStream_t st0, RunForm* f) {
     if (b->stats_pending && hipEventQuery(b->stats_ready) == hipSuccess) {
         b->stats_pending = false;
-        absorb_counts(b->learnt, b->exclusion, run_seq, b->host_stats[0], b->host_stats[1], b->plan.pairs);
+        absorb_counts(b->learnt, b->exclusion, run_seq, b->host_stats[0], b->host_stats[1], b->now->plan.pairs);
     }
     f->suspended = run_suspended(b->learnt, b->exclusion, run_seq);
     const bool whole_rows = whole_rows_throughout(b->learnt, b->exclusion, b->method, f->suspended);
-    if (whole_rows && b->plan.whole_pending) {
+    if (whole_rows && b->now->plan.whole_pending) {
         // the first run that wants the one-sub-batch cut makes it (host) and uploads its schedule and items behind the fill
-        if (complete_whole_cut(b->descs, b->plan)) {
-            const size_t o0 = b->plan.whole_order_first, o1 = b->plan.order.size(), i0 = b->plan.whole_items_first, i1 = b->plan.items.size();
-            if (hipMemcpyAsync(b->mem + b->lay.order + o0 * sizeof(int32_t), b->plan.order.data() + o0, (o1 - o0) * sizeof(int32_t), hipMemcpyHostToDevice, st0) != hipSuccess ||
-                hipMemcpyAsync(b->mem + b->lay.items + i0 * sizeof(int32_t), b->plan.items.data() + i0, (i1 - i0) * sizeof(int32_t), hipMemcpyHostToDevice, st0) != hipSuccess)
-                return SUSHI_HIP_ELAUNCH;
+        if (complete_whole_cut(b->now->descs, b->now->plan)) {
+            for (const UploadSpan& u : whole_cut_upload(b->now->plan, b->now->lay))
+                if (hipMemcpyAsync(b->mem + u.dev_off, u.host, u.bytes, hipMemcpyHostToDevice, st0) != hipSuccess) return SUSHI_HIP_ELAUNCH;
             // (the copies read the handle's own vectors: a re-plan and the destructor wait for this event before they touch them)
             if (hipEventRecord(b->uploaded, st0) != hipSuccess) return SUSHI_HIP_ELAUNCH;
         } else {
-            b->plan.whole_pending = false;                       // (on no case of tests/host_plan_check.cpp: the room was sized for it; the parts run one after the other then)
+            b->now->plan.whole_pending = false;                       // (on no case of tests/host_plan_check.cpp: the room was sized for it; the parts run one after the other then)
         }
     }
-    const bool whole_cut = takes_whole_cut(whole_rows, !b->plan.subs_whole.empty());
-    f->subs = whole_cut ? &b->plan.subs_whole : &b->plan.subs;
-    f->lanes = run_lanes(whole_rows, b->plan.lanes);
+    const bool whole_cut = takes_whole_cut(whole_rows, !b->now->plan.subs_whole.empty());
+    f->subs = whole_cut ? &b->now->plan.subs_whole : &b->now->plan.subs;
+    f->lanes = run_lanes(whole_rows, b->now->plan.lanes);
     b->last.suspended = f->suspended; b->last.whole_cut = whole_cut;
     return SUSHI_HIP_OK;
 }
@@ -304,10 +306,11 @@ static int run_sub_batches(RunCtx& c, const hipStream_t st0, const RunKind kind,
     SushiHipBatch* b = c.b;
     int rc = begin_run(b, st0, kind);
     if (rc != SUSHI_HIP_OK) return rc;
-    fill_add(fa, c.flags, b->lay.counters + align_up(sizeof(RunCounters), 256) - b->lay.flags, 0u);
+    const MemSpan zeros = run_fill_span(b->now->lay);
+    fill_add(fa, b->mem + zeros.off, zeros.bytes, 0u);
     if (launch_fill(fa, st0) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     c.run_seq = b->run_seq++;
-    RunForm form{false, &b->plan.subs, b->plan.lanes};
+    RunForm form{false, &b->now->plan.subs, b->now->plan.lanes};
     if (kind == RUN_ARGMIN && (rc = run_form(b, c.run_seq, st0, &form)) != SUSHI_HIP_OK) return rc;
     c.suspended = form.suspended; c.lanes = form.lanes;
     Lanes lanes(b, st0);
@@ -315,7 +318,7 @@ static int run_sub_batches(RunCtx& c, const hipStream_t st0, const RunKind kind,
     // Sub-batches of a plan on lanes run side by side (plan_core.hpp "Lanes"); the others one after the other.
     for (size_t si = 0; si < form.subs->size(); ++si) {
         const SubBatch& sb = (*form.subs)[si];
-        if ((rc = per_sub(SubView(b->mem, b->lay, b->plan.ws_lane, sb, si), lanes.st[sb.lane])) != SUSHI_HIP_OK) return rc;
+        if ((rc = per_sub(SubView(b->mem, b->now->lay, b->now->plan.ws_lane, sb, si), lanes.st[sb.lane])) != SUSHI_HIP_OK) return rc;
     }
     return lanes.join();
 }
@@ -533,7 +536,7 @@ static int transform_listed(const RunCtx& c, const SubView& v, hipStream_t st, I
     const SubBatch& sb = v.sb;
     const SushiHipBatch* b = c.b;
     // one workgroup per list slot up to `direct`, a fixed grid striding over whatever lies beyond (run_policy.hpp direct_slots)
-    const unsigned direct = (unsigned)direct_slots(b->learnt.last_transformed, sb.pairs, b->plan.pairs);
+    const unsigned direct = (unsigned)direct_slots(b->learnt.last_transformed, sb.pairs, b->now->plan.pairs);
     ip.list_first = 0; ip.list_direct = 1;
     if (launch_ifft(c, ip, direct, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     if ((int64_t)direct >= sb.pairs) return SUSHI_HIP_OK;
@@ -583,7 +586,7 @@ static int run_sub(RunCtx& c, const SubView& v, hipStream_t st) {
     prof_end(c.pc, t0, SUSHI_HIP_STAGE_MAC, st);
     t0 = prof_begin(c.pc, st);
     // the candidate rows start empty: ifft_kernel writes only the entries that exist
-    if (!c.cand_filled && hipMemsetAsync(v.cand, 0xff, (size_t)sb.pairs * FFT_ROW * sizeof(unsigned long long), st) != hipSuccess)
+    if (!c.cand_filled && hipMemsetAsync(v.cand, 0xff, cand_rows_bytes(sb.pairs), st) != hipSuccess)
         return SUSHI_HIP_ELAUNCH;
     IfftArgs ia;
     memset(&ia, 0, sizeof(ia));
@@ -755,6 +758,23 @@ static int run_sub_best(RunCtx& c, const SubView& v, hipStream_t st, const BestR
     return launch_best_select(bp, st);
 }
 
+// Nothing crosses the C boundary: an entry point that may allocate runs its body in here.
+template <class F, class R = decltype(std::declval<F>()())>
+static R c_boundary(F&& body, std::common_type_t<R> no_memory = SUSHI_HIP_ENOMEM, std::common_type_t<R> other = SUSHI_HIP_EINTERNAL) {   // (R: the body's alone)
+    try { return body(); } catch (const std::bad_alloc&) { return no_memory; } catch (...) { return other; }
+}
+
+// the plan sushi_hip_batch_bytes made, for the sushi_hip_batch_create behind it (batch_core.hpp PlanCache); SUSHI_HIP_LANES is
+// read once per ABI call: the planner and the cache's key get the same value
+static thread_local PlanCache g_plan_cache;
+
+// (batch_core.hpp resolve_variant; -1: refused)
+static int variant_of(int path, int variant, const SushiHipRequest* req, int n) {
+    int tiles[DIRECT_CHOICES];
+    for (int v = 0; v < DIRECT_CHOICES; ++v) tiles[v] = direct_variant_tile(v);
+    return resolve_variant(path, variant, req, n, direct_variant_count(), tiles);
+}
+
 extern "C" {
 
 int sushi_hip_device_prepare(void) {
@@ -774,11 +794,7 @@ int sushi_hip_fft_slot_of_bin(int bin) { return (bin < 0 || bin >= FN) ? -1 : su
 
 int sushi_hip_fft_low_slot_of_bin(int bin) { return sushi_fft::lslot_of_bin(bin); }
 
-size_t sushi_hip_stream_spectra_bytes(int64_t n) {
-    if (n <= 0) return 0;
-    const size_t rows = (size_t)((n + FFT_SEG - 1) / FFT_SEG + 1);
-    return rows * ROW_BYTES + rows * LROW_BYTES + 3 * align_up(rows * sizeof(float), 256);   // norms outside the band: of Z, of its two real blocks
-}
+size_t sushi_hip_stream_spectra_bytes(int64_t n) { return n <= 0 ? 0 : spectra_layout(n).total; }
 
 int sushi_hip_fft_layout(int64_t win_start, int32_t n_pos, int32_t tmpl_len, int32_t* n_pairs, int32_t* n_seg) {
     if (win_start < 0 || n_pos < 1 || tmpl_len < 1 || !n_pairs || !n_seg) return SUSHI_HIP_EINVAL;
@@ -794,119 +810,65 @@ int sushi_hip_stream_add_spectra(SushiHipStream* s, void* mem_dev, size_t mem_by
     const size_t need = sushi_hip_stream_spectra_bytes(s->n);
     if (mem_bytes < need) return SUSHI_HIP_ENOSPACE;
     if (s->blocks >= 0x7fffffff) return SUSHI_HIP_EINVAL;
-    // one block more than the stream has: its samples are all past the end, so its spectrum is zero
-    const size_t rows = (size_t)s->blocks + 1;
-    uint4* low = (uint4*)((char*)mem_dev + rows * ROW_BYTES);
-    float* zn = (float*)((char*)mem_dev + rows * ROW_BYTES + rows * LROW_BYTES);
+    const SpectraLayout l = spectra_layout(s->n);
+    uint4* low = (uint4*)((char*)mem_dev + l.low);
+    float* zn = (float*)((char*)mem_dev + l.norms);
     if (launch_dtype(s->dtype, [&](auto t) {
             using T = std::remove_pointer_t<decltype(t)>;
             hipLaunchKernelGGL(spectra_kernel<T>, dim3((unsigned)s->blocks + 1), dim3(FT), 0, (hipStream_t)hip_stream, (const T*)s->raw, s->n,
-                               (uint32_t*)mem_dev, (const double*)s->stats, low, zn, (int64_t)(align_up(rows * sizeof(float), 256) / sizeof(float))); }) != SUSHI_HIP_OK)
+                               (uint32_t*)mem_dev, (const double*)s->stats, low, zn, l.norm_stride); }) != SUSHI_HIP_OK)
         return SUSHI_HIP_ELAUNCH;
     s->spec = mem_dev;
     s->spec_low = low;
     s->znorm_rest = zn;
-    s->norm_stride = (int64_t)(align_up(rows * sizeof(float), 256) / sizeof(float));
-    s->spec_bytes = rows * ROW_BYTES;
+    s->norm_stride = l.norm_stride;
+    s->spec_bytes = l.low;                                       // (the whole rows)
     return SUSHI_HIP_OK;
 }
 
-// A caller sizes a batch (sushi_hip_batch_bytes) and then creates it from the same requests: the plan made for the first call is
-// kept for the second (per host thread; compared request by request, so a changed request list simply plans again).
-struct PlanCache {
-    bool valid = false;
-    size_t cap = 0;
-    std::string lanes_env;
-    std::vector<SushiHipRequest> req;
-    Plan plan;
-};
-static thread_local PlanCache g_plan_cache;
-// SUSHI_HIP_LANES, read once per ABI call: the planner and the cache's key get the same value
-static std::string lanes_override_now() { const char* e = getenv("SUSHI_HIP_LANES"); return e ? std::string(e) : std::string(); }
-
-size_t sushi_hip_batch_bytes(const SushiHipRequest* req_host, int n, int path, int variant, size_t workspace_cap_bytes) try {
+size_t sushi_hip_batch_bytes(const SushiHipRequest* req_host, int n, int path, int variant, size_t workspace_cap_bytes) { return c_boundary([&]() -> size_t {
     if (!req_host || n <= 0 || (path != SUSHI_HIP_PATH_FFT && path != SUSHI_HIP_PATH_DIRECT)) return 0;
-    if (path == SUSHI_HIP_PATH_FFT) variant = direct_variant_count() - 1;
-    else if (variant < 0) variant = choose_direct_variant(req_host, n);
-    if (variant >= direct_variant_count()) return 0;
+    if ((variant = variant_of(path, variant, req_host, n)) < 0) return 0;
     std::vector<SearchDesc> descs;
     int64_t tiles;
     if (make_descs(req_host, n, direct_variant_tile(variant), descs, &tiles) != SUSHI_HIP_OK) return 0;
     if (path == SUSHI_HIP_PATH_DIRECT) return batch_layout(n, path, 0, 0, 0, 0, 0).total;
     Plan plan;
-    std::string lanes = lanes_override_now();
-    if (make_plan(descs, workspace_cap_bytes, lanes.c_str(), plan) != SUSHI_HIP_OK) return 0;
+    const char* lanes = getenv("SUSHI_HIP_LANES");
+    if (make_plan(descs, workspace_cap_bytes, lanes, plan) != SUSHI_HIP_OK) return 0;
     const size_t total = batch_layout(n, path, plan.order.size(), plan.items.size(), plan.ws_bytes, plan.subs.size(), plan.segs).total;
-    PlanCache& pc = g_plan_cache;
-    pc.valid = true; pc.cap = workspace_cap_bytes; pc.lanes_env = std::move(lanes);
-    pc.req.assign(req_host, req_host + n);
-    pc.plan = std::move(plan);
+    g_plan_cache.remember(req_host, n, workspace_cap_bytes, lanes, std::move(plan));
     return total;
-} catch (...) { return 0; }        // std::bad_alloc etc.: nothing crosses the C boundary
+}, 0, 0); }
 
-// requests -> descriptors, plan and layout of `b` (all three replaced together or not at all), uploaded on `st`.
-// ENOSPACE: they do not fit the memory the batch was created in (nothing is changed then).
+// requests -> the handle's descriptors, plan, layout and upload image, uploaded on `st`.  Staged into the spare state first: every
+// refusal up to the commit -- EINVAL, ENOSPACE, a plan's own, an event that cannot be made or waited for -- leaves the handle as
+// it was.  Behind the commit only the copy's enqueue and the event's record are left; should one fail, the handle is not planned.
 static int plan_and_upload(SushiHipBatch* b, const SushiHipRequest* req_host, int n, hipStream_t st) {
-    std::vector<SearchDesc> descs;
-    int64_t n_tiles = 0;
-    int rc = make_descs(req_host, n, direct_variant_tile(b->variant), descs, &n_tiles);
+    const BatchSpec spec{b->path, direct_variant_tile(b->variant), b->ws_cap, b->mem_bytes, b->dst->n, b->src->n, b->dst->dtype == SUSHI_HIP_F32 ? 4.0 : 1.0};
+    const int rc = stage_batch(req_host, n, spec, getenv("SUSHI_HIP_LANES"), g_plan_cache, *b->spare);
     if (rc != SUSHI_HIP_OK) return rc;
-    double flops = 0.0, abytes = 0.0;
-    const double width = b->dst->dtype == SUSHI_HIP_F32 ? 4.0 : 1.0;
-    for (int k = 0; k < n; ++k) {
-        const SushiHipRequest& r = req_host[k];
-        if (r.tmpl_off + r.tmpl_len > b->src->n || r.win_start + (int64_t)r.n_pos + r.tmpl_len - 1 > b->dst->n) return SUSHI_HIP_EINVAL;
-        flops += 2.0 * (double)r.n_pos * (double)r.tmpl_len;
-        abytes += width * ((double)r.n_pos + r.tmpl_len - 1) + width * r.tmpl_len + 8.0;
-    }
-    Plan plan;
-    if (b->path == SUSHI_HIP_PATH_FFT) {
-        PlanCache& pc = g_plan_cache;
-        const std::string lanes = lanes_override_now();
-        if (pc.valid && pc.cap == b->ws_cap && (int)pc.req.size() == n && memcmp(pc.req.data(), req_host, (size_t)n * sizeof(SushiHipRequest)) == 0 &&
-            pc.lanes_env == lanes) {
-            plan = std::move(pc.plan);                      // (the plan sushi_hip_batch_bytes made for these very requests)
-            pc.valid = false;
-        } else {
-            rc = make_plan(descs, b->ws_cap, lanes.c_str(), plan);
-            if (rc != SUSHI_HIP_OK) return rc;
-        }
-    }
-    const BatchLayout lay = batch_layout(n, b->path, plan.order.size(), plan.items.size(), plan.ws_bytes, plan.subs.size(), plan.segs);
-    if (b->mem_bytes < lay.total) return SUSHI_HIP_ENOSPACE;
-    // an earlier plan's upload reads the handle's host buffer until its event has passed
-    if (b->uploaded && hipEventSynchronize(b->uploaded) != hipSuccess) return SUSHI_HIP_ELAUNCH;
-    b->descs.swap(descs); b->plan = std::move(plan); b->lay = lay; b->n_tiles = n_tiles;
-    b->flops = flops; b->algorithmic_bytes = abytes;
-    const size_t up_bytes = b->path == SUSHI_HIP_PATH_FFT ? lay.items + align_up(b->plan.items.size() * sizeof(int32_t), 256) - lay.desc
-                                                          : align_up((size_t)n * sizeof(SearchDesc), 256);
-    b->upload.assign(up_bytes, 0);
-    memcpy(b->upload.data(), b->descs.data(), (size_t)n * sizeof(SearchDesc));
-    if (!b->plan.order.empty()) memcpy(b->upload.data() + (lay.order - lay.desc), b->plan.order.data(), b->plan.order.size() * sizeof(int32_t));
-    if (!b->plan.items.empty()) memcpy(b->upload.data() + (lay.items - lay.desc), b->plan.items.data(), b->plan.items.size() * sizeof(int32_t));
-    // (the host buffer lives in the handle: the copy may still be in flight when this returns)
-    if (hipMemcpyAsync(b->mem + lay.desc, b->upload.data(), up_bytes, hipMemcpyHostToDevice, st) != hipSuccess) return SUSHI_HIP_ELAUNCH;
-    // a run may be launched on another stream than this one: it waits for this event first
-    if (!b->uploaded && hipEventCreateWithFlags(&b->uploaded, hipEventDisableTiming) != hipSuccess) return SUSHI_HIP_ELAUNCH;
-    if (hipEventRecord(b->uploaded, st) != hipSuccess) return SUSHI_HIP_ELAUNCH;
+    // a run may be launched on another stream than `st`: it waits for this event first; and an earlier plan's upload (a run's, of
+    // the whole cut) reads the handle's host buffers until the event has passed
+    if (b->uploaded ? hipEventSynchronize(b->uploaded) != hipSuccess : hipEventCreateWithFlags(&b->uploaded, hipEventDisableTiming) != hipSuccess)
+        return SUSHI_HIP_ELAUNCH;
+    std::swap(b->now, b->spare);
     b->forget_learnt();
-    return SUSHI_HIP_OK;
+    // (the host buffer lives in the handle: the copy may still be in flight when this returns)
+    b->planned = hipMemcpyAsync(b->mem + b->now->lay.desc, b->now->upload.data(), b->now->upload.size(), hipMemcpyHostToDevice, st) == hipSuccess &&
+                 hipEventRecord(b->uploaded, st) == hipSuccess;
+    return b->planned ? SUSHI_HIP_OK : SUSHI_HIP_ELAUNCH;
 }
 
 int sushi_hip_batch_create(const SushiHipStream* dst, const SushiHipStream* src, const SushiHipRequest* req_host, int n,
                            int path, int variant, size_t workspace_cap_bytes, void* mem_dev, size_t mem_bytes,
-                           void* hip_stream, SushiHipBatch** out) try {
+                           void* hip_stream, SushiHipBatch** out) { return c_boundary([&]() -> int {
     if (!dst || !src || !req_host || !mem_dev || !out || n <= 0) return SUSHI_HIP_EINVAL;
     if (path != SUSHI_HIP_PATH_FFT && path != SUSHI_HIP_PATH_DIRECT) return SUSHI_HIP_EINVAL;
     if (dst->dtype != src->dtype) return SUSHI_HIP_EINVAL;       // cv2.matchTemplate asserts equal types
     if ((uintptr_t)mem_dev & 255) return SUSHI_HIP_EALIGN;
-    if (path == SUSHI_HIP_PATH_FFT) {
-        if (!dst->spec) return SUSHI_HIP_EINVAL;                 // not searchable: sushi_hip_stream_add_spectra first
-        variant = direct_variant_count() - 1;
-    } else if (variant < 0) {
-        variant = choose_direct_variant(req_host, n);
-    }
-    if (variant >= direct_variant_count()) return SUSHI_HIP_EINVAL;
+    if (path == SUSHI_HIP_PATH_FFT && !dst->spec) return SUSHI_HIP_EINVAL;     // not searchable: sushi_hip_stream_add_spectra first
+    if ((variant = variant_of(path, variant, req_host, n)) < 0) return SUSHI_HIP_EINVAL;
     SushiHipBatch* b = new (std::nothrow) SushiHipBatch();
     if (!b) return SUSHI_HIP_ENOMEM;
     std::unique_ptr<SushiHipBatch> guard(b);                     // freed on every early return and on an exception
@@ -924,25 +886,25 @@ int sushi_hip_batch_create(const SushiHipStream* dst, const SushiHipStream* src,
     if (rc != SUSHI_HIP_OK) return rc;
     *out = guard.release();
     return SUSHI_HIP_OK;
-} catch (const std::bad_alloc&) { return SUSHI_HIP_ENOMEM; } catch (...) { return SUSHI_HIP_EINTERNAL; }     // nothing crosses the C boundary
+}); }
 
-int sushi_hip_batch_reset(SushiHipBatch* b, const SushiHipRequest* req_host, int n, void* hip_stream) try {
+int sushi_hip_batch_reset(SushiHipBatch* b, const SushiHipRequest* req_host, int n, void* hip_stream) { return c_boundary([&]() -> int {
     if (!b || !req_host || n != b->n) return SUSHI_HIP_EINVAL;
     // the last run's counts may still be on their way into the handle's pinned words
     if (b->stats_pending && b->stats_ready) { (void)hipEventSynchronize(b->stats_ready); b->stats_pending = false; }
     return plan_and_upload(b, req_host, n, (hipStream_t)hip_stream);
-} catch (const std::bad_alloc&) { return SUSHI_HIP_ENOMEM; } catch (...) { return SUSHI_HIP_EINTERNAL; }
+}); }
 
 int sushi_hip_batch_info(const SushiHipBatch* b, SushiHipBatchInfo* info) {
     if (!b || !info) return SUSHI_HIP_EINVAL;
     memset(info, 0, sizeof(*info));
     info->n_search = b->n; info->path = b->path; info->variant = b->variant;
-    info->sub_batches = b->path == SUSHI_HIP_PATH_FFT ? (int32_t)b->plan.subs.size() : 1;
-    info->direct_tiles = b->n_tiles;
-    info->fft_pairs = b->plan.pairs; info->fft_segments = b->plan.segs;
-    info->workspace_bytes = b->plan.ws_bytes; info->mem_bytes = b->lay.total;
-    info->flops = b->flops; info->algorithmic_bytes = b->algorithmic_bytes;
-    info->lanes = b->path == SUSHI_HIP_PATH_FFT ? b->plan.lanes : 1;
+    info->sub_batches = b->path == SUSHI_HIP_PATH_FFT ? (int32_t)b->now->plan.subs.size() : 1;
+    info->direct_tiles = b->now->n_tiles;
+    info->fft_pairs = b->now->plan.pairs; info->fft_segments = b->now->plan.segs;
+    info->workspace_bytes = b->now->plan.ws_bytes; info->mem_bytes = b->now->lay.total;
+    info->flops = b->now->flops; info->algorithmic_bytes = b->now->algorithmic_bytes;
+    info->lanes = b->path == SUSHI_HIP_PATH_FFT ? b->now->plan.lanes : 1;
     return SUSHI_HIP_OK;
 }
 
@@ -981,13 +943,13 @@ int sushi_hip_batch_set_bound_model(SushiHipBatch* b, int model) {
     return SUSHI_HIP_OK;
 }
 
-int sushi_hip_batch_run(SushiHipBatch* b, double delta, int32_t* out_idx_dev, float* out_score_dev, void* hip_stream) try {
-    if (!b || !out_idx_dev || !out_score_dev) return SUSHI_HIP_EINVAL;
+int sushi_hip_batch_run(SushiHipBatch* b, double delta, int32_t* out_idx_dev, float* out_score_dev, void* hip_stream) { return c_boundary([&]() -> int {
+    if (!b || !out_idx_dev || !out_score_dev || !b->planned) return SUSHI_HIP_EINVAL;
     const hipStream_t st0 = (hipStream_t)hip_stream;
     RunCtx c(b, delta);
     if (b->path == SUSHI_HIP_PATH_DIRECT) {
         if (begin_run(b, st0, RUN_ARGMIN) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-        return launch_direct(c.r, c.searches, b->n, (int)b->n_tiles, b->variant, b->method, c.keys, out_idx_dev, out_score_dev, b->packed_out, st0);
+        return launch_direct(c.r, c.searches, b->n, (int)b->now->n_tiles, b->variant, b->method, c.keys, out_idx_dev, out_score_dev, b->packed_out, st0);
     }
     if (!(delta >= 3.8e-6) || delta > 1.0) return SUSHI_HIP_EINVAL;      // the floor covers the scoring arithmetic's own rounding
     if (g_prof_on) { g_prof.emplace_back(); c.pc = &g_prof.back(); }
@@ -995,10 +957,9 @@ int sushi_hip_batch_run(SushiHipBatch* b, double delta, int32_t* out_idx_dev, fl
     // candidate rows.
     FillArgs fa{};
     fill_add(fa, c.keys, (size_t)2 * b->n * sizeof(uint64_t), 0xffffffffu);
-    if (b->plan.subs.size() == 1) {
-        const SubView v0(b->mem, b->lay, b->plan.ws_lane, b->plan.subs[0], 0);
-        const size_t cand_bytes = (size_t)v0.sb.pairs * FFT_ROW * sizeof(unsigned long long);
-        if (cand_bytes <= ((size_t)8 << 20)) { fill_add(fa, v0.cand, cand_bytes, 0xffffffffu); c.cand_filled = true; }
+    if ((c.cand_filled = fills_candidate_rows(b->now->plan))) {
+        const SubView v0(b->mem, b->now->lay, b->now->plan.ws_lane, b->now->plan.subs[0], 0);
+        fill_add(fa, v0.cand, cand_rows_bytes(v0.sb.pairs), 0xffffffffu);
     }
     int rc = run_sub_batches(c, st0, RUN_ARGMIN, fa, [&](const SubView& v, hipStream_t st) { return run_sub(c, v, st); });
     if (rc != SUSHI_HIP_OK) return rc;
@@ -1015,23 +976,23 @@ int sushi_hip_batch_run(SushiHipBatch* b, double delta, int32_t* out_idx_dev, fl
             b->stats_pending = true;
     }
     return rc;
-} catch (const std::bad_alloc&) { return SUSHI_HIP_ENOMEM; } catch (...) { return SUSHI_HIP_EINTERNAL; }     // nothing crosses the C boundary
+}); }
 
 int sushi_hip_batch_run_threshold(SushiHipBatch* b, double threshold, int32_t capacity, SushiHipHit* out_hits_dev, int64_t* out_counts_dev,
-                                  void* hip_stream) try {
-    if (!b || !out_hits_dev || !out_counts_dev || capacity < 0 || !std::isfinite(threshold) || b->path != SUSHI_HIP_PATH_FFT)
+                                  void* hip_stream) { return c_boundary([&]() -> int {
+    if (!b || !out_hits_dev || !out_counts_dev || capacity < 0 || !std::isfinite(threshold) || b->path != SUSHI_HIP_PATH_FFT || !b->planned)
         return SUSHI_HIP_EINVAL;
     if (((uintptr_t)out_hits_dev & 3) || ((uintptr_t)out_counts_dev & 7)) return SUSHI_HIP_EALIGN;
     const ThresholdRun tr{threshold, ranking_key(b->method, threshold, false), capacity, out_hits_dev, out_counts_dev};
     RunCtx c(b, 0.0);
     return run_sub_batches(c, (hipStream_t)hip_stream, RUN_THRESHOLD, FillArgs{},
                            [&](const SubView& v, hipStream_t st) { return run_sub_threshold(c, v, st, tr); });
-} catch (const std::bad_alloc&) { return SUSHI_HIP_ENOMEM; } catch (...) { return SUSHI_HIP_EINTERNAL; }     // nothing crosses the C boundary
+}); }
 
 int sushi_hip_batch_run_best(SushiHipBatch* b, int32_t k, int32_t min_separation, const double* threshold, SushiHipHit* out_hits_dev,
-                             int32_t* out_counts_dev, void* hip_stream) try {
+                             int32_t* out_counts_dev, void* hip_stream) { return c_boundary([&]() -> int {
     if (!b || !out_hits_dev || !out_counts_dev || k < 1 || k > SUSHI_HIP_BEST_MAX_K || min_separation < 0 ||
-        (threshold && !std::isfinite(*threshold)) || b->path != SUSHI_HIP_PATH_FFT)
+        (threshold && !std::isfinite(*threshold)) || b->path != SUSHI_HIP_PATH_FFT || !b->planned)
         return SUSHI_HIP_EINVAL;
     if (((uintptr_t)out_hits_dev & 3) || ((uintptr_t)out_counts_dev & 3)) return SUSHI_HIP_EALIGN;
     // (the threshold's key never below 0, unlike a threshold run's: ranking_key)
@@ -1040,9 +1001,9 @@ int sushi_hip_batch_run_best(SushiHipBatch* b, int32_t k, int32_t min_separation
     RunCtx c(b, 0.0);
     return run_sub_batches(c, (hipStream_t)hip_stream, RUN_BEST, FillArgs{},
                            [&](const SubView& v, hipStream_t st) { return run_sub_best(c, v, st, br); });
-} catch (const std::bad_alloc&) { return SUSHI_HIP_ENOMEM; } catch (...) { return SUSHI_HIP_EINTERNAL; }     // nothing crosses the C boundary
+}); }
 
-int sushi_hip_batch_diagnostics(SushiHipBatch* b, SushiHipBatchDiag* diag, float* ranking_err_host, int32_t* flagged_host) try {
+int sushi_hip_batch_diagnostics(SushiHipBatch* b, SushiHipBatchDiag* diag, float* ranking_err_host, int32_t* flagged_host) { return c_boundary([&]() -> int {
     if (!b || !diag) return SUSHI_HIP_EINVAL;
     memset(diag, 0, sizeof(*diag));
     if (!b->last.ran || b->path != SUSHI_HIP_PATH_FFT) {
@@ -1052,7 +1013,7 @@ int sushi_hip_batch_diagnostics(SushiHipBatch* b, SushiHipBatchDiag* diag, float
     }
     if (hipStreamSynchronize(b->last_stream) != hipSuccess) return SUSHI_HIP_ELAUNCH;
     RunCounters c;
-    if (hipMemcpy(&c, b->mem + b->lay.counters, sizeof(c), hipMemcpyDeviceToHost) != hipSuccess) return SUSHI_HIP_ELAUNCH;
+    if (hipMemcpy(&c, b->mem + b->now->lay.counters, sizeof(c), hipMemcpyDeviceToHost) != hipSuccess) return SUSHI_HIP_ELAUNCH;
     diag->flagged = c.n_flagged; diag->all_positions = c.n_all_positions;
     diag->tiles_dense = (int64_t)c.tiles_dense; diag->tiles_sparse = (int64_t)c.tiles_sparse;
     diag->candidates = (int64_t)c.candidates;
@@ -1070,17 +1031,17 @@ int sushi_hip_batch_diagnostics(SushiHipBatch* b, SushiHipBatchDiag* diag, float
         // (a best-K run: the last round that evaluated a pair of each search -- 1 the seed, 2 .. the escalation rounds, BEST_ROUNDS + 2
         // the last stage; 0 without the exclusion)
         if (b->last.kind == RUN_BEST && flagged_host &&
-            hipMemcpy(flagged_host, b->mem + b->lay.flags, (size_t)b->n * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
+            hipMemcpy(flagged_host, b->mem + b->now->lay.flags, (size_t)b->n * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
             return SUSHI_HIP_ELAUNCH;
         return SUSHI_HIP_OK;
     }
     std::vector<int32_t> fl((size_t)b->n);
-    if (hipMemcpy(fl.data(), b->mem + b->lay.flags, (size_t)b->n * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
+    if (hipMemcpy(fl.data(), b->mem + b->now->lay.flags, (size_t)b->n * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
         return SUSHI_HIP_ELAUNCH;
     if (flagged_host) memcpy(flagged_host, fl.data(), (size_t)b->n * sizeof(int32_t));
     if (ranking_err_host) {
         std::vector<unsigned long long> g((size_t)b->n);
-        if (hipMemcpy(g.data(), b->mem + b->lay.keys + (size_t)b->n * sizeof(unsigned long long),
+        if (hipMemcpy(g.data(), b->mem + b->now->lay.keys + (size_t)b->n * sizeof(unsigned long long),
                       (size_t)b->n * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess)
             return SUSHI_HIP_ELAUNCH;
         for (int k = 0; k < b->n; ++k) {
@@ -1089,11 +1050,11 @@ int sushi_hip_batch_diagnostics(SushiHipBatch* b, SushiHipBatchDiag* diag, float
         }
     }
     return SUSHI_HIP_OK;
-} catch (const std::bad_alloc&) { return SUSHI_HIP_ENOMEM; } catch (...) { return SUSHI_HIP_EINTERNAL; }     // nothing crosses the C boundary
+}); }
 
-int sushi_hip_batch_pair_bounds(SushiHipBatch* b, float* slb_host, float* acc_host, int64_t* n_pairs) try {
+int sushi_hip_batch_pair_bounds(SushiHipBatch* b, float* slb_host, float* acc_host, int64_t* n_pairs) { return c_boundary([&]() -> int {
     if (!b || !n_pairs) return SUSHI_HIP_EINVAL;
-    if (!b->last.ran || b->path != SUSHI_HIP_PATH_FFT || b->plan.subs.empty()) { *n_pairs = 0; return SUSHI_HIP_OK; }
+    if (!b->last.ran || b->path != SUSHI_HIP_PATH_FFT || b->now->plan.subs.empty()) { *n_pairs = 0; return SUSHI_HIP_OK; }
     if (hipStreamSynchronize(b->last_stream) != hipSuccess) return SUSHI_HIP_ELAUNCH;
     const SubView v = last_sub(b);
     const int64_t cap = *n_pairs;
@@ -1102,12 +1063,12 @@ int sushi_hip_batch_pair_bounds(SushiHipBatch* b, float* slb_host, float* acc_ho
     if (slb_host && hipMemcpy(slb_host, v.slb, (size_t)v.sb.pairs * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return SUSHI_HIP_ELAUNCH;
     if (acc_host && hipMemcpy(acc_host, v.acc, (size_t)v.sb.pairs * 2 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return SUSHI_HIP_ELAUNCH;
     return SUSHI_HIP_OK;
-} catch (const std::bad_alloc&) { return SUSHI_HIP_ENOMEM; } catch (...) { return SUSHI_HIP_EINTERNAL; }
+}); }
 
 int sushi_hip_batch_workspace_view(SushiHipBatch* b, int which, void** ptr_dev, size_t* bytes) {
     if (!b || !ptr_dev || !bytes) return SUSHI_HIP_EINVAL;
     *ptr_dev = nullptr; *bytes = 0;
-    if (!b->last.ran || b->path != SUSHI_HIP_PATH_FFT || b->plan.subs.empty()) return SUSHI_HIP_OK;
+    if (!b->last.ran || b->path != SUSHI_HIP_PATH_FFT || b->now->plan.subs.empty()) return SUSHI_HIP_OK;
     if (hipStreamSynchronize(b->last_stream) != hipSuccess) return SUSHI_HIP_ELAUNCH;
     const SubView v = last_sub(b);
     switch (which) {
@@ -1128,7 +1089,7 @@ int sushi_hip_profile_begin(void) {
     return SUSHI_HIP_OK;
 }
 
-int sushi_hip_profile_end(float* stage_ms, int max_calls, int* n_calls) try {
+int sushi_hip_profile_end(float* stage_ms, int max_calls, int* n_calls) { return c_boundary([&]() -> int {
     g_prof_on = false;
     if (!stage_ms || !n_calls || max_calls < 0) return SUSHI_HIP_EINVAL;
     int out = 0;
@@ -1152,6 +1113,6 @@ int sushi_hip_profile_end(float* stage_ms, int max_calls, int* n_calls) try {
     g_prof.clear();
     *n_calls = out;
     return rc;
-} catch (const std::bad_alloc&) { return SUSHI_HIP_ENOMEM; } catch (...) { return SUSHI_HIP_EINTERNAL; }     // nothing crosses the C boundary
+}); }
 
 }  // extern "C"

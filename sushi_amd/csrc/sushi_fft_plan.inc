@@ -1,6 +1,6 @@
 // sushi_amd/csrc/sushi_fft_plan.inc -- part of sushi_fft.hip (included there, inside its anonymous namespace; not a header of its own):
-// the host side's glue between a plan (plan_core.hpp, which is host only and checked on the CPU) and the device: kernel launches by
-// method / sample type, per-stage timing, the direct path's tile variant, a sub-batch's typed view of the batch's memory.
+// the host side's glue between a plan (plan_core.hpp and batch_core.hpp, which are host only and checked on the CPU) and the device:
+// kernel launches by method / sample type, per-stage timing, a sub-batch's typed view of the batch's memory.
 
 // A kernel instantiated per method / per sample type: `f` launches it with the template argument it is given, as a
 // std::integral_constant / a null pointer of the sample type.
@@ -34,19 +34,6 @@ inline void prof_end(ProfCall* pc, hipEvent_t t0, int stage, hipStream_t st) {
     if (hipEventCreate(&e) != hipSuccess) return;
     (void)hipEventRecord(e, st);
     pc->spans.push_back(ProfSpan{t0, e, stage});
-}
-
-// largest tile variant whose grid still gives the chip (256 CUs x 4 SIMDs) a few waves per SIMD
-int choose_direct_variant(const SushiHipRequest* req, int n) {
-    const int waves[3] = {1, 4, 4};
-    int best = 0;
-    for (int v = 0; v < direct_variant_count() && v < 3; ++v) {
-        const int tp = direct_variant_tile(v);
-        int64_t nt = 0;
-        for (int k = 0; k < n; ++k) nt += (req[k].n_pos + tp - 1) / tp;
-        if (nt * waves[v] >= 4096) best = v;
-    }
-    return best;
 }
 
 // One sub-batch of a cut of a plan and where it works in the batch's memory `mem`: its lane's workspace (ws_layout, typed), its

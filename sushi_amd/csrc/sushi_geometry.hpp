@@ -137,6 +137,17 @@ constexpr int ROWE = FFT_N / 4;                // ... as 16-byte entries (four b
 // loads them (fft_core.hpp "LOW BAND"): the band-split exclusion multiplies, stores and transforms only these.
 constexpr int LROWE = FFT_N / 16;              // 16-byte entries of a low row (sushi_fft::LB_ENTRIES)
 constexpr int LROW_BYTES = LROWE * 16;
+// The spectra of a searchable stream of n samples (sushi_hip_stream_add_spectra), as they lie in the memory it is given: a whole
+// row per block and one more (its samples are all past the end, so its spectrum is zero), from `low` on their low rows, from
+// `norms` on three arrays of `norm_stride` floats -- the rows' norms outside the band: of Z, of its two real blocks.
+struct SpectraLayout { size_t low, norms, total; int64_t norm_stride; };
+inline SpectraLayout spectra_layout(int64_t n) {
+    const size_t rows = (size_t)((n + FFT_SEG - 1) / FFT_SEG + 1), norm_bytes = align_up(rows * sizeof(float), 256);
+    SpectraLayout l;
+    l.low = rows * ROW_BYTES; l.norms = l.low + rows * LROW_BYTES; l.total = l.norms + 3 * norm_bytes;
+    l.norm_stride = (int64_t)(norm_bytes / sizeof(float));
+    return l;
+}
 
 // ---- the multiply-accumulate's work items (sushi_fft_mac.inc) ----
 constexpr int MAC_SPW = 8;                       // searches per wave

@@ -41,7 +41,7 @@ def test_every_source_file_is_in_the_build_lists():
     assert deps["sushi_load"] == common | {"sushi_load.hip", "downmix_core.hpp"}
     parts = {"sushi_fft_%s.inc" % s for s in ("store", "spectra", "mac", "ifft", "bound", "collect", "plan", "threshold", "best")}
     assert deps["sushi_fft"] == common | generated | parts | {"sushi_fft.hip", "fft_core.hpp", "mac_core.hpp", "plan_core.hpp",
-                                                               "run_policy.hpp"}
+                                                               "batch_core.hpp", "run_policy.hpp"}
 
 
 def test_unit_deps_on_a_small_tree(tmp_path, monkeypatch):
