@@ -61,7 +61,8 @@ extern "C" {
 #define SUSHI_HIP_ELAUNCH (-3)   /* the HIP runtime rejected a launch / copy / memset (see hipGetLastError) */
 #define SUSHI_HIP_ENOSPACE (-4)  /* buffer or workspace too small */
 #define SUSHI_HIP_ENODEV (-5)    /* no gfx950 device visible */
-#define SUSHI_HIP_ENOMEM (-6)    /* the host ran out of memory while a plan was built (std::bad_alloc caught at the boundary) */
+#define SUSHI_HIP_ENOMEM (-6)    /* the host ran out of memory while a handle, a plan or an upload was built (std::bad_alloc caught at the
+                                    boundary; sushi_hip_stream_create and sushi_hip_batch_create alike) */
 #define SUSHI_HIP_EINTERNAL (-7) /* any other C++ exception caught at the boundary: a bug, never a property of the input */
 
 /* sample types of WavStream.data (wav.py:109: 'uint8' or 'float32') */

@@ -27,13 +27,14 @@ TWIDDLE_INC = os.path.join(CSRC, "_gen_twiddle16384.inc")
 UNITS = [
     ("sushi_direct", ["-ffp-contract=off"]),    # direct path: the MFMA kernel and its launcher
     ("sushi_exact", ["-ffp-contract=off"]),     # FFT path's exact stages (refinement, tiles), unpack and fill kernels
-    ("sushi_stream", ["-ffp-contract=off"]),    # stream preparation (prefix sums) and the stream C ABI
+    ("sushi_stream", ["-ffp-contract=off"]),    # stream preparation (prefix sums) and the stream C ABI (its parts: stream_core.hpp)
     # WavStream load pipeline (decode / downmix, weighted: downmix_core.hpp / decimate / pad / median clip / scale / quantise)
     ("sushi_load", ["-ffp-contract=off"]),      # NumPy's float32 operation order, no fused multiply-add
     # whole score curves: i8 MFMA Toeplitz GEMM (uint8), canonical float64 chain (float32); the same tiles (curve_tiles.hpp)
-    # evaluate the listed pairs of a threshold run and of a best-K run
+    # evaluate the listed pairs of a threshold run and of a best-K run; what a curve call uploads and launches is host only
+    # (curve_core.hpp)
     ("sushi_curve", ["-ffp-contract=off"]),     # the epilogue restates cv2's operation order (as sushi_direct.hip's)
-    # a stream read at another speed: linear interpolation at a rational step (retime_core.hpp)
+    # a stream read at another speed: linear interpolation at a rational step (retime_core.hpp: the arithmetic, and the call's host side)
     ("sushi_retime", ["-ffp-contract=off"]),    # NumPy's float64 operation order: product and sum round separately
     # a low-pass in front of the load pipeline's decimator: polyphase FIR at the file's rate (resample_core.hpp)
     ("sushi_resample", ["-ffp-contract=off"]),  # float64 taps: product and sum round separately, as NumPy's

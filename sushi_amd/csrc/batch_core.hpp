@@ -88,12 +88,11 @@ struct BatchSpec {
 // before and keeps its vectors' room (a re-plan allocates nothing for them).  EINVAL: a malformed request, or one outside its
 // stream; ENOSPACE: they do not fit spec.mem_bytes; make_plan's own.  A refusal leaves `out` half written: it is the SPARE state.
 inline int stage_batch(const SushiHipRequest* req, int n, const BatchSpec& spec, const char* lanes_env, PlanCache& cache, BatchPlanState& out) {
-    int rc = make_descs(req, n, spec.tile, out.descs, &out.n_tiles);
+    int rc = make_descs(req, n, spec.tile, out.descs, &out.n_tiles, spec.dst_len, spec.src_len);
     if (rc != SUSHI_HIP_OK) return rc;
     out.flops = out.algorithmic_bytes = 0.0;
     for (int k = 0; k < n; ++k) {
         const SushiHipRequest& r = req[k];
-        if (r.tmpl_off + r.tmpl_len > spec.src_len || r.win_start + (int64_t)r.n_pos + r.tmpl_len - 1 > spec.dst_len) return SUSHI_HIP_EINVAL;
         out.flops += 2.0 * (double)r.n_pos * (double)r.tmpl_len;
         out.algorithmic_bytes += spec.width * ((double)r.n_pos + r.tmpl_len - 1) + spec.width * r.tmpl_len + 8.0;
     }

@@ -341,15 +341,16 @@ inline BatchLayout batch_layout(int n, int path, size_t n_order_ints, size_t n_i
     return b;
 }
 
-// requests -> descriptors with their running sums; EINVAL for a malformed request
+// requests -> descriptors with their running sums; EINVAL for a request that request_fits refuses -- malformed, or outside streams
+// of `dst_n` / `src_n` samples (the default: no streams yet, a batch that is only sized)
 // (`tp`: positions per tile of the direct path's kernel variant)
-inline int make_descs(const SushiHipRequest* req, int n, int tp, std::vector<SearchDesc>& out, int64_t* n_tiles) {
+inline int make_descs(const SushiHipRequest* req, int n, int tp, std::vector<SearchDesc>& out, int64_t* n_tiles,
+                      int64_t dst_n = INT64_MAX, int64_t src_n = INT64_MAX) {
     out.resize(n);
     int64_t tiles = 0, pairs = 0, segs = 0;
     for (int k = 0; k < n; ++k) {
         const SushiHipRequest& r = req[k];
-        if (r.tmpl_len < 1 || r.n_pos < 1 || r.win_start < 0 || r.tmpl_off < 0) return SUSHI_HIP_EINVAL;
-        if (r.n_pos > 0x7fffffff - 65536 || r.tmpl_len > 0x7fffffff - 65536) return SUSHI_HIP_EINVAL;
+        if (!request_fits(r, dst_n, src_n)) return SUSHI_HIP_EINVAL;
         SearchDesc d;
         d.tmpl_off = r.tmpl_off; d.win_start = r.win_start; d.tmpl_len = r.tmpl_len; d.n_pos = r.n_pos;
         if (tiles > 0x7fffffff || pairs > 0x7fffffff || segs > 0x7fffffff) return SUSHI_HIP_EINVAL;

@@ -15,7 +15,6 @@ namespace sushi {
 // pair's transforms (n_seg + 2 * FFT_VB blocks).  Calibrated: the largest ratio measured over the parity and property
 // tests is recorded by refine_kernel (diagnostics) and stays below FFT_KE / 3; a candidate whose exact score
 // violates its bound sends the whole search to exact evaluation.
-constexpr int COARSE_G = 256;                      // granularity of the coarse prefix table (SushiHipStream.coarse)
 constexpr float FFT_KE = 32.0f;
 constexpr unsigned long long NO_KEY = ~0ull;
 

@@ -18,33 +18,17 @@
 #include <string.h>
 
 #include <algorithm>
-#include <new>
-#include <vector>
 
 #include "../../include/sushi_hip.h"
 #include "sushi_common.hpp"
 #include "sushi_internal.hpp"
 #include "curve_tiles.hpp"
+#include "curve_core.hpp"
 
 namespace {
 
 using namespace sushi;
 using namespace sushi_tiles;
-
-// One request on the device: where its pattern and window are, where its curve goes, its first work item.
-struct CurveDesc {
-    int64_t tmpl_off;
-    int64_t win_start;
-    int64_t out_off;        // first float of its curve in out_dev: sum of n_pos of the requests before it
-    int64_t first_item;     // work items of the requests before it
-    int32_t tmpl_len;
-    int32_t n_pos;
-};
-static_assert(sizeof(CurveDesc) == 40, "CurveDesc layout");
-
-// workspace: [queue head (u64) | padding to 256 B][CurveDesc x n], uploaded in one copy
-constexpr size_t CURVE_HEAD = 256;
-size_t curve_layout_bytes(int n) { return n <= 0 ? 0 : CURVE_HEAD + align_up((size_t)n * sizeof(CurveDesc), 256); }
 
 struct CurveArgs {
     TileSrc src;                      // streams, method
@@ -412,12 +396,6 @@ unsigned listed_grid(const ListedPairs& lp) {
     return (unsigned)std::min<int64_t>((int64_t)std::max(lp.list_max, 1) * TILES_PER_PAIR, 2048);
 }
 
-bool request_ok(const SushiHipRequest& r, const SushiHipStream* dst, const SushiHipStream* src) {
-    if (r.tmpl_len < 1 || r.n_pos < 1 || r.win_start < 0 || r.tmpl_off < 0) return false;
-    if (r.n_pos > 0x7fffffff - 65536 || r.tmpl_len > 0x7fffffff - 65536) return false;
-    return r.tmpl_off + r.tmpl_len <= src->n && r.win_start + (int64_t)r.n_pos + r.tmpl_len - 1 <= dst->n;
-}
-
 }  // namespace
 
 namespace sushi {
@@ -444,48 +422,32 @@ size_t sushi_hip_curve_bytes(const SushiHipRequest* req_host, int n) {
 }
 
 int sushi_hip_match_curves(const SushiHipStream* dst, const SushiHipStream* src, const SushiHipRequest* req_host, int n,
-                           int method, void* mem_dev, size_t mem_bytes, float* out_dev, void* hip_stream) try {
+                           int method, void* mem_dev, size_t mem_bytes, float* out_dev, void* hip_stream) { return c_boundary([&]() -> int {
     if (!dst || !src || !req_host || !mem_dev || !out_dev || n < 0) return SUSHI_HIP_EINVAL;
     if (method != SUSHI_HIP_METHOD_SQDIFF_NORMED && method != SUSHI_HIP_METHOD_CCOEFF_NORMED) return SUSHI_HIP_EINVAL;
     if (n == 0) return SUSHI_HIP_OK;
     if (dst->dtype != src->dtype) return SUSHI_HIP_EINVAL;           // cv2.matchTemplate asserts equal types
-    for (int k = 0; k < n; ++k)
-        if (!request_ok(req_host[k], dst, src)) return SUSHI_HIP_EINVAL;
+    CurveStage staged;
+    const int rc = stage_curves(req_host, n, dst->dtype, dst->n, src->n, staged);
+    if (rc != SUSHI_HIP_OK) return rc;
     if (((uintptr_t)mem_dev & 255) || ((uintptr_t)out_dev & 3)) return SUSHI_HIP_EALIGN;
-    if (mem_bytes < curve_layout_bytes(n)) return SUSHI_HIP_ENOSPACE;
+    if (mem_bytes < staged.image.size()) return SUSHI_HIP_ENOSPACE;
 
-    const bool u8 = dst->dtype == SUSHI_HIP_U8;
-    // float32: 1024 positions per item where there are enough of them to fill the GPU, else 256 (a quarter of the chains' length
-    // each, four times the items)
-    int64_t items1024 = 0;
-    for (int k = 0; k < n; ++k) items1024 += (req_host[k].n_pos + 1023) / 1024;
-    const int per_item = u8 ? U8_TILE : (items1024 >= 2048 ? 1024 : 256);
-    std::vector<char> up(curve_layout_bytes(n), 0);                  // queue head 0, then the descriptors
-    CurveDesc* d = reinterpret_cast<CurveDesc*>(up.data() + CURVE_HEAD);
-    int64_t out_off = 0, items = 0;
-    for (int k = 0; k < n; ++k) {
-        const SushiHipRequest& r = req_host[k];
-        d[k].tmpl_off = r.tmpl_off; d[k].win_start = r.win_start; d[k].tmpl_len = r.tmpl_len; d[k].n_pos = r.n_pos;
-        d[k].out_off = out_off; d[k].first_item = items;
-        out_off += r.n_pos;
-        items += (r.n_pos + per_item - 1) / per_item;
-    }
     hipStream_t st = (hipStream_t)hip_stream;
     char* mem = (char*)mem_dev;
-    // (a pageable source: the runtime has staged it when the call returns, as for plan_and_upload's descriptors)
-    if (hipMemcpyAsync(mem, up.data(), up.size(), hipMemcpyHostToDevice, st) != hipSuccess) return SUSHI_HIP_ELAUNCH;
+    // (The source is pageable host memory that dies with this call.  ASSUMED: the runtime has taken its copy of such a source when
+    // hipMemcpyAsync returns.)
+    if (hipMemcpyAsync(mem, staged.image.data(), staged.image.size(), hipMemcpyHostToDevice, st) != hipSuccess) return SUSHI_HIP_ELAUNCH;
     CurveArgs a;
     a.src = TileSrc{dst->raw, dst->s1, dst->s2, dst->n, src->raw, src->s1, src->s2, sushi_hip_centre(dst->dtype), method};
     a.desc = reinterpret_cast<const CurveDesc*>(mem + CURVE_HEAD);
-    a.n = n; a.n_items = items;
+    a.n = n; a.n_items = staged.n_items;
     a.queue = reinterpret_cast<unsigned long long*>(mem);
     a.out = out_dev;
-    // a fixed grid that takes the items off the queue: 256 CUs, a few workgroups each
-    const unsigned grid = (unsigned)(items < 2048 ? items : 2048);
-    if (u8) hipLaunchKernelGGL(curve_u8_kernel, dim3(grid), dim3(256), 0, st, a);
-    else if (per_item == 1024) hipLaunchKernelGGL(curve_f32_kernel<4>, dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(curve_f32_kernel<1>, dim3(grid), dim3(256), 0, st, a);
+    if (dst->dtype == SUSHI_HIP_U8) hipLaunchKernelGGL(curve_u8_kernel, dim3(staged.grid), dim3(256), 0, st, a);
+    else if (staged.per_item == CURVE_F32_ITEM) hipLaunchKernelGGL(curve_f32_kernel<CURVE_F32_ITEM / 256>, dim3(staged.grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(curve_f32_kernel<CURVE_F32_SMALL_ITEM / 256>, dim3(staged.grid), dim3(256), 0, st, a);
     return launch_ok();
-} catch (const std::bad_alloc&) { return SUSHI_HIP_ENOMEM; } catch (...) { return SUSHI_HIP_EINTERNAL; }
+}); }
 
 }  // extern "C"

@@ -38,7 +38,11 @@
 // gfx950 only: wave64, 160 KiB LDS/CU.  No CUDA compatibility paths.
 //
 // ONE translation unit, cut by stage (every part is included below, inside this file's anonymous namespace):
-//   sushi_geometry.hpp     (a header: every unit's) the sizes and records host plan and device code agree on
+//   sushi_geometry.hpp     (a header: every unit's) the sizes and records host plan and device code agree on, and the one rule of
+//                          what a request may be (request_fits)
+//   stream_core.hpp        (a header: every unit's, host only, checked on the CPU by tests/host_stream_check.cpp) the stream handle and
+//                          the table of a stream's parts: its buffer's size, the handle's pointers, sushi_hip_stream_view's answers
+//                          (the curves' and the retime unit's host sides are checked there too: curve_core.hpp, retime_core.hpp)
 //   plan_core.hpp          (a header: host only, checked on the CPU by tests/host_plan_check.cpp) the plan of a batch, its
 //                          workspace and device-memory layouts, parse_bound_fault, ranking_key
 //   batch_core.hpp         (a header: host only, checked on the CPU by tests/host_batch_check.cpp) what a handle holds about its
@@ -342,7 +346,7 @@ static BoundArgs bound_args(const RunCtx& c, const SubView& v) {
     BoundArgs ba;
     memset(&ba, 0, sizeof(ba));
     ba.dst_stats = dst->stats; ba.searches = c.searches + v.sb.a0; ba.sub_first_pair = v.sb.first_pair; ba.first_search = v.sb.a0; ba.dst_len = dst->n;
-    ba.pairmap = v.pairmap; ba.tconst = v.tconst; ba.ubase = dst->base; ba.sbase = dst->base + (dst->blocks + 1); ba.nb = dst->blocks;
+    ba.pairmap = v.pairmap; ba.tconst = v.tconst; ba.ubase = dst->base; ba.sbase = dst->base1; ba.nb = dst->blocks;
     ba.coarse = dst->coarse; ba.nc = dst->nc; ba.slb = v.slb; ba.n_sub = v.n_sub; ba.n_pairs = (int)v.sb.pairs; ba.plist = v.plist;
     ba.slist = v.slist; ba.scount = v.n_slist; ba.order = v.order; ba.gkeys = c.gkeys; ba.pair_lb = v.pair_lb; ba.counters = c.counters; ba.acc = v.acc;
     ba.sub_first_seg = v.sb.first_seg; ba.tnorm_rest = v.tnorm_rest; ba.znorm_rest = dst->znorm_rest; ba.norm_stride = dst->norm_stride;
@@ -593,7 +597,7 @@ static int run_sub(RunCtx& c, const SubView& v, hipStream_t st) {
     ia.y = (const uint2*)v.y; ia.dst_stats = c.dst->stats; ia.searches = c.searches + sb.a0; ia.n_sub = v.n_sub; ia.first_search = sb.a0;
     ia.sub_first_pair = sb.first_pair; ia.dst_len = c.dst->n; ia.delta = (float)c.delta; ia.cand = v.cand; ia.pair_lb = v.pair_lb; ia.gkeys = c.gkeys;
     ia.pairmap = v.pairmap; ia.tconst = v.tconst; ia.order = v.order; ia.urel = c.dst->urel; ia.nb = c.dst->blocks; ia.ubase = c.dst->base;
-    ia.usrel = c.dst->usrel; ia.sbase = c.dst->base + (c.dst->blocks + 1); ia.flags = c.flags; ia.flag_list = c.flag_list + sb.a0; ia.sub = v.sub;
+    ia.usrel = c.dst->usrel; ia.sbase = c.dst->base1; ia.flags = c.flags; ia.flag_list = c.flag_list + sb.a0; ia.sub = v.sub;
     ia.tiles = v.tiles; ia.candbuf = v.candbuf; ia.cand_cap = (int)cand_capacity(sb.pairs); ia.counters = c.counters; ia.viol = c.viol;
     if (!exclude) {
         // every pair, in the L2-friendly schedule (what round 3 did for every batch)
@@ -758,12 +762,6 @@ static int run_sub_best(RunCtx& c, const SubView& v, hipStream_t st, const BestR
     return launch_best_select(bp, st);
 }
 
-// Nothing crosses the C boundary: an entry point that may allocate runs its body in here.
-template <class F, class R = decltype(std::declval<F>()())>
-static R c_boundary(F&& body, std::common_type_t<R> no_memory = SUSHI_HIP_ENOMEM, std::common_type_t<R> other = SUSHI_HIP_EINTERNAL) {   // (R: the body's alone)
-    try { return body(); } catch (const std::bad_alloc&) { return no_memory; } catch (...) { return other; }
-}
-
 // the plan sushi_hip_batch_bytes made, for the sushi_hip_batch_create behind it (batch_core.hpp PlanCache); SUSHI_HIP_LANES is
 // read once per ABI call: the planner and the cache's key get the same value
 static thread_local PlanCache g_plan_cache;
@@ -810,19 +808,14 @@ int sushi_hip_stream_add_spectra(SushiHipStream* s, void* mem_dev, size_t mem_by
     const size_t need = sushi_hip_stream_spectra_bytes(s->n);
     if (mem_bytes < need) return SUSHI_HIP_ENOSPACE;
     if (s->blocks >= 0x7fffffff) return SUSHI_HIP_EINVAL;
-    const SpectraLayout l = spectra_layout(s->n);
-    uint4* low = (uint4*)((char*)mem_dev + l.low);
-    float* zn = (float*)((char*)mem_dev + l.norms);
+    SushiHipStream with = *s;                                    // (the handle gets its spectra when they are on their way)
+    fill_spectra(with, mem_dev, stream_layout(s->n, 0));
     if (launch_dtype(s->dtype, [&](auto t) {
             using T = std::remove_pointer_t<decltype(t)>;
             hipLaunchKernelGGL(spectra_kernel<T>, dim3((unsigned)s->blocks + 1), dim3(FT), 0, (hipStream_t)hip_stream, (const T*)s->raw, s->n,
-                               (uint32_t*)mem_dev, (const double*)s->stats, low, zn, l.norm_stride); }) != SUSHI_HIP_OK)
+                               (uint32_t*)with.spec, (const double*)s->stats, (uint4*)with.spec_low, with.znorm_rest, with.norm_stride); }) != SUSHI_HIP_OK)
         return SUSHI_HIP_ELAUNCH;
-    s->spec = mem_dev;
-    s->spec_low = low;
-    s->znorm_rest = zn;
-    s->norm_stride = l.norm_stride;
-    s->spec_bytes = l.low;                                       // (the whole rows)
+    *s = with;
     return SUSHI_HIP_OK;
 }
 

@@ -37,6 +37,7 @@ constexpr int FFT_ROW = 32;                        // 64-bit entries per pair in
 static_assert(FFT_CAND + 2 + AUDIT_RUNS * FFT_AUDIT <= FFT_ROW, "candidates, overflow marker, error bound, audit runs");
 constexpr int TILE = 1024;                         // positions per exact-evaluation tile (aligned to the absolute grid)
 constexpr int TILES_PER_PAIR = 2 * FFT_H / TILE;
+constexpr int COARSE_G = 256;                      // granularity of the coarse prefix table (SushiHipStream.coarse)
 
 // Overlap-save layout of one search (DESIGN.md "FFT path"): its block pairs sit on the ABSOLUTE pair grid (pair I
 // starts at block FFT_STEP * I), from the pair holding the window's first position to the one holding its last.
@@ -66,6 +67,17 @@ SUSHI_GEOM_HD inline int mac_class(int n_seg) {
 
 // sizes of device-memory parts are rounded up to 256 bytes
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// What a request must be, for every entry point that takes requests: a pattern and a window of at least one sample / position,
+// both short enough that no count derived from them (tiles, pairs, positions past the window) leaves 32 bits, the pattern inside
+// its source stream of `src_n` samples and the window's last read inside the destination's `dst_n`.  (Written without a sum that
+// could overflow.)  sushi_amd/device.py _checked_requests restates it for its messages.
+constexpr int32_t REQUEST_MAX_TERM = 0x7fffffff - 65536;      // n_pos, tmpl_len
+inline bool request_fits(const SushiHipRequest& r, int64_t dst_n, int64_t src_n) {
+    if (r.tmpl_len < 1 || r.n_pos < 1 || r.win_start < 0 || r.tmpl_off < 0) return false;
+    if (r.n_pos > REQUEST_MAX_TERM || r.tmpl_len > REQUEST_MAX_TERM) return false;
+    return r.tmpl_len <= src_n - r.tmpl_off && (int64_t)r.n_pos + r.tmpl_len - 1 <= dst_n - r.win_start;
+}
 
 // One search on the device: a SushiHipRequest plus the running sums that let a workgroup find its work.
 struct SearchDesc {

@@ -6,38 +6,24 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <new>
+#include <type_traits>
+#include <utility>
+
 #include "../../include/sushi_hip.h"
 #include "sushi_common.hpp"
-
-// The opaque stream handle of the C ABI: where the parts of a prepared stream live (all inside the caller's buffer).
-struct SushiHipStream {
-    const void* raw;          // the samples as they are (uint8 / float32), caller-owned
-    int dtype;
-    int64_t n;
-    float* xc;                // [n]      sample - centre
-    double* s1;               // [n + 1]  prefix sums of the samples
-    double* s2;               // [n + 1]  prefix sums of their squares
-    float* urel;              // [n + 1]  s2 relative to the block base
-    float* usrel;             // [n + 1][2]  (urel[e], s1 relative to the block base): TM_CCOEFF_NORMED on the FFT path, one 8-byte load per window end
-    double* base;             // [nb + 1] block bases of s2, then [nb + 1] block bases of s1, then `stats`
-    double* stats;            // [2] FFT path: largest centred energy of seven consecutive blocks; the centring constant
-    double* coarse;           // [2][nc] s2 and s1 at every COARSE_G-th sample (nc = n / COARSE_G + 2; entries past the end hold the
-                              //         totals): bound_kernel's lower bound of a block pair's window energies
-    int64_t nc;
-    size_t base_bytes;
-    void* spec;               // [(nb + 1) * N] block spectra as packed halves, or null; behind them:
-    void* spec_low;           // [(nb + 1) * N / 4] the low band (|f| < N / 8) of every block spectrum again, in bound_low_kernel's order
-    float* znorm_rest;        // [3][norm_stride] norms over the bins OUTSIDE the band of a block spectrum's stored halves: of Z itself, of
-                              // the spectrum of its real block at j B, of the one at j B + H (sushi_fft.hip real_block_rest_norms)
-    int64_t norm_stride;
-    size_t spec_bytes;
-    int64_t blocks;           // nb
-};
+#include "stream_core.hpp"         // SushiHipStream
 
 namespace sushi {
 
 // what every launcher returns after its last launch
 inline int launch_ok() { return hipGetLastError() == hipSuccess ? SUSHI_HIP_OK : SUSHI_HIP_ELAUNCH; }
+
+// Nothing crosses the C boundary: an entry point that may allocate runs its body in here.
+template <class F, class R = decltype(std::declval<F>()())>
+R c_boundary(F&& body, std::common_type_t<R> no_memory = SUSHI_HIP_ENOMEM, std::common_type_t<R> other = SUSHI_HIP_EINTERNAL) {   // (R: the body's alone)
+    try { return body(); } catch (const std::bad_alloc&) { return no_memory; } catch (...) { return other; }
+}
 
 // FFT path: the pairs of a sub-batch are numbered from its first search's first pair (`sub_first_pair`: that pair's number in the
 // batch); `pr` is a pair of the sub-batch, `sd` its search.

@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <new>
+#include <memory>
 
 #include "../../include/sushi_hip.h"
 #include "sushi_common.hpp"
@@ -19,8 +19,7 @@ using namespace sushi;
 // ------------------------------------------------------------------------------------------
 constexpr int PB_THREADS = 256;
 constexpr int PB_PER_THREAD = 16;
-constexpr int PB = PB_THREADS * PB_PER_THREAD;   // 4096 samples per block
-static_assert(PB == FFT_HOP, "the relative prefix sums are per FFT block");
+static_assert(PB == PB_THREADS * PB_PER_THREAD, "a block of the passes (stream_core.hpp: 4096 samples) is a workgroup's");
 
 template <typename T> __device__ __forceinline__ float centred(T x);
 template <> __device__ __forceinline__ float centred<float>(float x) { return x - 0.5f; }
@@ -229,26 +228,6 @@ void fft_stats_kernel(const double* __restrict__ bs2, const double* __restrict__
     }
 }
 
-// where the parts of a prepared stream go inside the caller's buffer
-struct StreamLayout { size_t xc, s1, s2, urel, srel, base, base_bytes, coarse, spec, total; };
-
-StreamLayout stream_layout(int64_t n, int searchable) {
-    StreamLayout l;
-    const int64_t nb = (n + PB - 1) / PB;
-    size_t o = 0;
-    l.xc = o; o += align_up((size_t)n * sizeof(float), 256);
-    l.s1 = o; o += align_up((size_t)(n + 1) * sizeof(double), 256);
-    l.s2 = o; o += align_up((size_t)(n + 1) * sizeof(double), 256);
-    l.urel = o; o += align_up((size_t)(n + 1) * sizeof(float), 256);
-    l.srel = o; o += align_up((size_t)(n + 1) * 2 * sizeof(float), 256);     // usrel: (urel, srel) interleaved
-    l.base_bytes = (size_t)(2 * (nb + 1) + 2) * sizeof(double);  // block bases of sum x^2, then of sum x, then the FFT path's stats
-    l.base = o; o += align_up(l.base_bytes, 256);
-    l.coarse = o; o += align_up((size_t)2 * (size_t)(n / COARSE_G + 2) * sizeof(double), 256);
-    l.spec = o; o += searchable ? align_up(sushi_hip_stream_spectra_bytes(n), 256) : 0;
-    l.total = o;
-    return l;
-}
-
 }  // namespace
 
 using namespace sushi;
@@ -285,32 +264,22 @@ int sushi_hip_device_ok(void) {
 
 double sushi_hip_centre(int dtype) { return dtype == SUSHI_HIP_U8 ? 128.0 : 0.5; }
 
-size_t sushi_hip_stream_bytes(int64_t n, int dtype, int searchable) {
-    if (n <= 0 || (dtype != SUSHI_HIP_U8 && dtype != SUSHI_HIP_F32)) return 0;
-    return stream_layout(n, searchable).total;
-}
+size_t sushi_hip_stream_bytes(int64_t n, int dtype, int searchable) { return stream_bytes(n, dtype, searchable); }
 
 int sushi_hip_stream_create(const void* raw_dev, int dtype, int64_t n, int searchable, void* mem_dev, size_t mem_bytes,
-                            void* hip_stream, SushiHipStream** out) {
+                            void* hip_stream, SushiHipStream** out) { return c_boundary([&]() -> int {
     if (!raw_dev || !mem_dev || !out || n <= 0) return SUSHI_HIP_EINVAL;
-    if (dtype != SUSHI_HIP_U8 && dtype != SUSHI_HIP_F32) return SUSHI_HIP_EINVAL;
+    if (!stream_dtype_ok(dtype)) return SUSHI_HIP_EINVAL;
     if (((uintptr_t)mem_dev & 255) || (dtype == SUSHI_HIP_F32 && ((uintptr_t)raw_dev & 3))) return SUSHI_HIP_EALIGN;
     const StreamLayout l = stream_layout(n, searchable);
     if (mem_bytes < l.total) return SUSHI_HIP_ENOSPACE;
-    const int64_t nb64 = (n + PB - 1) / PB;
-    if (nb64 > 0x7ffffffe) return SUSHI_HIP_EINVAL;
-    const int nb = (int)nb64;
-    SushiHipStream* s = new (std::nothrow) SushiHipStream();
-    if (!s) return SUSHI_HIP_EINVAL;
-    char* m = (char*)mem_dev;
-    s->raw = raw_dev; s->dtype = dtype; s->n = n;
-    s->xc = (float*)(m + l.xc); s->s1 = (double*)(m + l.s1); s->s2 = (double*)(m + l.s2);
-    s->urel = (float*)(m + l.urel); s->usrel = (float*)(m + l.srel); s->base = (double*)(m + l.base); s->base_bytes = l.base_bytes;
-    s->spec = nullptr; s->spec_low = nullptr; s->znorm_rest = nullptr; s->norm_stride = 0; s->spec_bytes = 0; s->blocks = nb; s->stats = s->base + 2 * (nb + 1);
-    s->coarse = (double*)(m + l.coarse); s->nc = n / COARSE_G + 2;
+    if (l.nb > 0x7ffffffe) return SUSHI_HIP_EINVAL;
+    const int nb = (int)l.nb;
+    std::unique_ptr<SushiHipStream> s(new SushiHipStream());
+    fill_stream(*s, raw_dev, dtype, n, mem_dev, l);
     hipStream_t st = (hipStream_t)hip_stream;
     double* bs2 = s->base;                       // block bases of sum x^2 (what the FFT path's scoring reads)
-    double* bs1 = s->base + (nb + 1);            // block bases of sum x
+    double* bs1 = s->base1;                      // block bases of sum x
     if (dtype == SUSHI_HIP_F32)
         hipLaunchKernelGGL(centre_blocksum_kernel<float>, dim3(nb), dim3(PB_THREADS), 0, st,
                            (const float*)raw_dev, n, s->xc, bs1, bs2);
@@ -341,29 +310,15 @@ int sushi_hip_stream_create(const void* raw_dev, int dtype, int64_t n, int searc
         rc = launch_ok();
     }
     if (rc == SUSHI_HIP_OK && searchable)
-        rc = sushi_hip_stream_add_spectra(s, m + l.spec, mem_bytes - l.spec, hip_stream);
-    if (rc != SUSHI_HIP_OK) { delete s; return rc; }
-    *out = s;
+        rc = sushi_hip_stream_add_spectra(s.get(), s->mem + l.spec, mem_bytes - l.spec, hip_stream);
+    if (rc != SUSHI_HIP_OK) return rc;
+    *out = s.release();
     return SUSHI_HIP_OK;
-}
+}); }
 
 int sushi_hip_stream_view(const SushiHipStream* s, int which, const void** ptr_dev, size_t* bytes) {
     if (!s || !ptr_dev || !bytes) return SUSHI_HIP_EINVAL;
-    switch (which) {
-        case SUSHI_HIP_VIEW_XC: *ptr_dev = s->xc; *bytes = (size_t)s->n * sizeof(float); break;
-        case SUSHI_HIP_VIEW_S1: *ptr_dev = s->s1; *bytes = (size_t)(s->n + 1) * sizeof(double); break;
-        case SUSHI_HIP_VIEW_S2: *ptr_dev = s->s2; *bytes = (size_t)(s->n + 1) * sizeof(double); break;
-        case SUSHI_HIP_VIEW_UREL: *ptr_dev = s->urel; *bytes = (size_t)(s->n + 1) * sizeof(float); break;
-        case SUSHI_HIP_VIEW_BASE: *ptr_dev = s->base; *bytes = (size_t)(s->blocks + 1) * sizeof(double); break;
-        case SUSHI_HIP_VIEW_SPECTRA: *ptr_dev = s->spec; *bytes = s->spec_bytes; break;
-        case SUSHI_HIP_VIEW_SPECTRA_LOW: *ptr_dev = s->spec_low; *bytes = s->spec ? s->spec_bytes / 4 : 0; break;
-        case SUSHI_HIP_VIEW_ZNORM_REST: *ptr_dev = s->znorm_rest; *bytes = s->spec ? (size_t)3 * (size_t)s->norm_stride * sizeof(float) : 0; break;
-        case SUSHI_HIP_VIEW_USREL: *ptr_dev = s->usrel; *bytes = (size_t)(s->n + 1) * 2 * sizeof(float); break;
-        case SUSHI_HIP_VIEW_BASE1: *ptr_dev = s->base + (s->blocks + 1); *bytes = (size_t)(s->blocks + 1) * sizeof(double); break;
-        case SUSHI_HIP_VIEW_COARSE: *ptr_dev = s->coarse; *bytes = (size_t)2 * (size_t)s->nc * sizeof(double); break;
-        default: return SUSHI_HIP_EINVAL;
-    }
-    return SUSHI_HIP_OK;
+    return stream_view(*s, which, ptr_dev, bytes);
 }
 
 void sushi_hip_stream_destroy(SushiHipStream* s) { delete s; }

@@ -210,7 +210,8 @@ def default_path():
 
 
 def _checked_requests(dst, src, tmpl_off, tmpl_len, win_start, n_pos):
-    """The SushiHipRequest array of a batch (include/sushi_hip.h), after the checks the reference leaves to NumPy and cv2."""
+    """The SushiHipRequest array of a batch (include/sushi_hip.h), after the checks the reference leaves to NumPy and cv2.
+    They restate, with a message each, the one rule the library itself refuses by: request_fits (csrc/sushi_geometry.hpp)."""
     tmpl_off = np.asarray(tmpl_off, dtype=np.int64).reshape(-1)
     tmpl_len = np.asarray(tmpl_len, dtype=np.int64).reshape(-1)
     win_start = np.asarray(win_start, dtype=np.int64).reshape(-1)

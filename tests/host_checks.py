@@ -17,10 +17,12 @@ FLAGS = {   # check: (flags, flags of its sanitizer variant or None)
     "host_fft_check": (PLAIN, None),
     "host_mac_check": (PLAIN, None),
     "host_mfma_check": (PLAIN, None),
-    # host-only integer logic (plan_core.hpp, batch_core.hpp, run_policy.hpp), compared with recorded output
+    # host-only integer logic (plan_core.hpp, batch_core.hpp, run_policy.hpp; stream_core.hpp, curve_core.hpp and the host part of
+    # retime_core.hpp), compared with recorded output
     "host_plan_check": (PLAIN, SANITIZED),
     "host_batch_check": (PLAIN, SANITIZED),
     "host_policy_check": (PLAIN, SANITIZED),
+    "host_stream_check": (PLAIN, SANITIZED),
     "host_downmix_check": (KERNEL_ARITHMETIC, None),
     "host_resample_check": (KERNEL_ARITHMETIC, None),
     "host_retime_check": (KERNEL_ARITHMETIC, None),
