@@ -46,7 +46,8 @@ extern "C" {
                                      13 (additive): SUSHI_HIP_BEST_MAX_K, sushi_hip_batch_run_best;
                                      13 (additive): SushiHipRetimeSegment, sushi_hip_retime_bytes, sushi_hip_retime;
                                      13 (additive): SUSHI_HIP_MIX_MAX_CHANNELS / _OUTPUTS, sushi_hip_load_decode_mix;
-                                     13 (additive): sushi_hip_load_resample_fir */
+                                     13 (additive): sushi_hip_load_resample_fir;
+                                     13 (additive): SushiHipJointRow, SushiHipJointGroup, sushi_hip_joint_bytes, sushi_hip_joint_reduce */
 
 #if defined(__GNUC__)
 #define SUSHI_HIP_API __attribute__((visibility("default")))
@@ -435,6 +436,48 @@ SUSHI_HIP_API int sushi_hip_retime(const void* in_dev, int dtype, int64_t n_in,
                                    const SushiHipRetimeSegment* seg_host, int n_seg,
                                    void* out_dev, int64_t n_out,
                                    void* mem_dev, size_t mem_bytes, void* hip_stream);
+
+/* ---- joint search: the one shift a group of score rows shares (13, additive) -----------------
+ * Events of one scene share one shift, and a lone search of a short or repeated pattern may prefer a decoy in its window.  The
+ * rows of a group are therefore put on one shift axis and reduced together.  A group is m >= 1 rows; a row is n_shift consecutive
+ * float32 values of a sushi_hip_match_curves output (all rows of a call by the same method), starting at a curve_off of its own,
+ * with a float64 weight w_i, finite and >= 0.  Joint index j in [0, n_shift) addresses element j of every row R_i.  In row order:
+ *     acc = 0.0
+ *     acc = acc + w_i * (double)R_i[j]     for i = 0 .. m - 1 (the product and the sum round separately, no fused multiply-add)
+ *     joint[j] = (float)acc
+ * so a NumPy float64 restatement equals the result bit for bit.  The group's answer is the FIRST index of the minimum of joint
+ * (SUSHI_HIP_METHOD_SQDIFF_NORMED) or of its maximum (SUSHI_HIP_METHOD_CCOEFF_NORMED; 0.0 and -0.0 tie, as in NumPy), and that
+ * float32 value.  Per row the same pass returns R_i[answer] -- each row's own score at the joint index -- and the row's own first
+ * extremum over [0, n_shift), as index and value: what a lone search over that range returns.  Row values are assumed finite, and
+ * under SQDIFF_NORMED not negative (-0.0 included), as curves are; with a NaN the results are unspecified, but no access leaves
+ * the buffers. */
+typedef struct SushiHipJointRow {
+    int64_t curve_off;  /* first float of the row in curves_dev */
+    double weight;      /* finite, >= 0 */
+} SushiHipJointRow;         /* 16 bytes */
+typedef struct SushiHipJointGroup {
+    int32_t first_row;  /* the groups tile the rows in order: the sum of n_rows of the groups before this one */
+    int32_t n_rows;     /* m >= 1 */
+    int32_t n_shift;    /* >= 1 */
+    int32_t reserved;
+} SushiHipJointGroup;       /* 16 bytes */
+/* workspace a joint call needs (both tables, the extremum keys); 0 for n_groups < 1 or n_rows < n_groups */
+SUSHI_HIP_API size_t sushi_hip_joint_bytes(int n_groups, int n_rows);
+/* out_idx_dev / out_score_dev: [n_groups] the answers; out_row_score_dev: [n_rows] R_i[answer of its group]; out_row_idx_dev /
+ * out_row_best_dev: [n_rows] every row's own first extremum; out_joint_dev: NULL, or the joint rows back to back (group g's starts
+ * at the sum of n_shift of the groups before it).  No device allocation: one upload of the tables into mem_dev (256-byte aligned,
+ * >= sushi_hip_joint_bytes), then two launches (the reduce; the gather of R_i[answer]).  Asynchronous; stateless (any thread, own
+ * workspace).  Checked before any HIP call -- EINVAL: a null pointer (but out_joint_dev), an unknown method, n_groups < 1,
+ * n_rows < n_groups, n_curve < 1, groups that do not tile the rows in order, n_shift < 1, curve_off < 0 or curve_off + n_shift >
+ * n_curve (decided without forming the sum), a weight that is not finite or is negative; EALIGN: mem_dev not 256-byte aligned, a
+ * float / int32 pointer not 4-byte aligned; ENOSPACE: mem_bytes too small. */
+SUSHI_HIP_API int sushi_hip_joint_reduce(const float* curves_dev, int64_t n_curve,
+                                         const SushiHipJointRow* rows_host, int n_rows,
+                                         const SushiHipJointGroup* groups_host, int n_groups, int method,
+                                         void* mem_dev, size_t mem_bytes,
+                                         int32_t* out_idx_dev, float* out_score_dev,
+                                         float* out_row_score_dev, int32_t* out_row_idx_dev, float* out_row_best_dev,
+                                         float* out_joint_dev, void* hip_stream);
 
 /* ---- WavStream.__init__ on the GPU (wav.py:64-91 decode + downmix, wav.py:113-156 value pipeline) ----
  * sushi_hip_load_decode   : interleaved little-endian PCM frames (sample_width 2 or 3 bytes, `channels` per frame)

@@ -49,6 +49,11 @@ assert HIT_DTYPE.itemsize == 8
 # struct SushiHipRetimeSegment, 32 bytes: one segment of a retime call (sushi_hip_retime)
 RETIME_SEGMENT_DTYPE = np.dtype([("in_start", "<i8"), ("out_off", "<i8"), ("out_len", "<i8"), ("num", "<i4"), ("den", "<i4")], align=True)
 assert RETIME_SEGMENT_DTYPE.itemsize == 32
+# struct SushiHipJointRow / SushiHipJointGroup, 16 bytes each: the tables of a joint call (sushi_hip_joint_reduce)
+JOINT_ROW_DTYPE = np.dtype([("curve_off", "<i8"), ("weight", "<f8")], align=True)
+assert JOINT_ROW_DTYPE.itemsize == 16
+JOINT_GROUP_DTYPE = np.dtype([("first_row", "<i4"), ("n_rows", "<i4"), ("n_shift", "<i4"), ("reserved", "<i4")], align=True)
+assert JOINT_GROUP_DTYPE.itemsize == 16
 
 
 class BatchInfo(ctypes.Structure):
@@ -164,6 +169,10 @@ def lib():
     L.sushi_hip_retime_bytes.argtypes = [ci]
     L.sushi_hip_retime.restype = ci
     L.sushi_hip_retime.argtypes = [vp, ci, i64, vp, ci, vp, i64, vp, sz, vp]
+    L.sushi_hip_joint_bytes.restype = sz
+    L.sushi_hip_joint_bytes.argtypes = [ci, ci]
+    L.sushi_hip_joint_reduce.restype = ci
+    L.sushi_hip_joint_reduce.argtypes = [vp, i64, vp, ci, vp, ci, ci, vp, sz, vp, vp, vp, vp, vp, vp, vp]
     L.sushi_hip_load_decode.restype = ci
     L.sushi_hip_load_decode.argtypes = [vp, i64, i32, i32, vp, vp]
     L.sushi_hip_load_decode_mix.restype = ci

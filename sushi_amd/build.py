@@ -38,6 +38,9 @@ UNITS = [
     ("sushi_retime", ["-ffp-contract=off"]),    # NumPy's float64 operation order: product and sum round separately
     # a low-pass in front of the load pipeline's decimator: polyphase FIR at the file's rate (resample_core.hpp)
     ("sushi_resample", ["-ffp-contract=off"]),  # float64 taps: product and sum round separately, as NumPy's
+    # a group of score rows on one shift axis, summed by weight and reduced to its first extremum (joint_core.hpp: the arithmetic,
+    # and the call's host side)
+    ("sushi_joint", ["-ffp-contract=off"]),     # NumPy's float64 operation order: product and sum round separately
     # overlap-save FFT path; its parts, by stage, are csrc/sushi_fft_*.inc (included inside its anonymous namespace); the plan of
     # a batch (plan_core.hpp), what a handle holds about its requests and how it is staged (batch_core.hpp) and what a run decides
     # (run_policy.hpp) are host only

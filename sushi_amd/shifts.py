@@ -366,3 +366,30 @@ def calculate_shifts_at_speed(src_stream, dst_stream, groups_list, speed, normal
             else:
                 e.set_shift(sh.shift + (sh.start - e.start), sh.diff)
     return result
+
+
+def calculate_group_shifts(src_stream, dst_stream, groups, window, centre_shifts=0.0):
+    """One shift per group of events, found jointly (sushi_amd.joint; DESIGN.md 3.15): `groups` is a list of lists of ScriptEvent;
+    every event's pattern is src_stream.get_substream(e.start, e.end) and its centre e.start + centre_shift (centre_shifts: one
+    number for all groups, or one per group).  All groups go through one dst_stream.find_joint_many call with window `window`
+    (seconds).  Every event gets set_shift(centre_shift + delta, its own score at the joint shift).  SushiError for an event whose
+    pattern is empty.  Returns the JointMatch of every group."""
+    groups = [list(g) for g in groups]
+    try:
+        shifts = [float(s) for s in centre_shifts]
+    except TypeError:
+        shifts = [float(centre_shifts)] * len(groups)
+    if not groups or len(shifts) != len(groups) or any(not g for g in groups):
+        raise SushiError("calculate_group_shifts: non-empty groups, one centre shift per group")
+    requests = []
+    for group, shift in zip(groups, shifts):
+        patterns = [src_stream.get_substream(e.start, e.end) for e in group]
+        for e, p in zip(group, patterns):
+            if p.shape[1] < 1:
+                raise SushiError("calculate_group_shifts: event %s has no samples in the source" % e)
+        requests.append((patterns, [e.start + shift for e in group]))
+    matches = dst_stream.find_joint_many(requests, [window] * len(groups))
+    for group, shift, match in zip(groups, shifts, matches):
+        for e, score in zip(group, match.event_scores):
+            e.set_shift(shift + match.delta, score)
+    return matches

@@ -3,7 +3,8 @@
 Same constructor, attributes and methods as reference wav.py:104-188; ``find_substream`` runs on
 the GPU (libsushi_hip.so) instead of ``cv2.matchTemplate`` + ``argmin`` (wav.py:185-186).
 Extensions: ``WavStream.from_samples`` (in-memory PCM), ``find_substreams`` (batched), ``downmix=`` / ``WavStream.load_mixes`` /
-``WavStream.from_channels`` (the channels mixed by weight instead of averaged: sushi_amd/downmix.py).
+``WavStream.from_channels`` (the channels mixed by weight instead of averaged: sushi_amd/downmix.py), ``find_joint`` /
+``find_joint_many`` (the one shift a group of patterns shares: sushi_amd/joint.py).
 
 The load pipeline (wav.py:64-162): the RIFF header walk on the host; PCM decode, channel downmix, decimation,
 padding, the two medians, clip / scale / quantise on the GPU when one is present (the file is uploaded in bounded
@@ -559,6 +560,30 @@ class WavStream(object):
         if not as_tensor:
             curves = curves.cpu().numpy()
         return [curves[int(bounds[k]):int(bounds[k + 1])].reshape(1, -1) for k in range(n)]
+
+    # ------------------------------------------------------------------ one shift for a group
+    def find_joint(self, patterns, window_centers, window_size, weights='equal', method="sqdiff_normed", with_curve=False):
+        """The one shift a group of patterns shares (sushi_amd.joint): pattern i is looked for at
+        window_centers[i] + delta for one delta, |delta| <= window_size, scored by the weighted sum of every pattern's own score row
+        at that displacement.  Returns a JointMatch (find_joint_many)."""
+        return self.find_joint_many([(patterns, window_centers)], [window_size], method=method, with_curve=with_curve,
+                                    weights=weights if isinstance(weights, str) else [weights])[0]
+
+    def find_joint_many(self, groups, window_sizes, weights='equal', method="sqdiff_normed", with_curve=False, max_bytes=None):
+        """[find_joint(p, c, w) for (p, c), w in zip(groups, window_sizes)]: groups is a list of (patterns, window_centers).
+        Patterns are located as find_substreams locates them.  Event i of a group sits at sample bases[i] + k,
+        bases[i] = _get_sample_for_time(window_centers[i]), for the displacements k every event of the group can take within
+        W = int(sample_rate * window_size) samples inside the row (sushi_amd.joint.joint_window; SushiError if there is none).  All
+        groups of a chunk go through one match_curves call and one sushi_hip_joint_reduce call; chunks hold whole groups under
+        max_bytes of curve memory (default 1 GiB; a single group above it raises SushiError).  weights: 'equal' (1 / m), 'length'
+        (M_i / sum M) or one entry per group, each one of those or a sequence of numbers.  method: 'sqdiff_normed' (first minimum of
+        the sum) or 'ccoeff_normed' (first maximum).  Returns a JointMatch per group: delta (seconds; event i is found at
+        window_centers[i] + delta), score, index, event_scores (every event's own score at the joint shift), event_own_delta /
+        event_own_scores (what a lone search of each event over the same range finds), curve (with_curve: the float32 joint row).
+        Needs a GPU."""
+        from . import joint
+        return joint.find_joint_many(self, groups, window_sizes, weights=weights, method=method, with_curve=with_curve,
+                                     max_bytes=joint.MAX_BYTES if max_bytes is None else int(max_bytes))
 
     # ------------------------------------------------------------------ another clock
     def retimed(self, speed):
