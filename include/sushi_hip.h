@@ -47,7 +47,9 @@ extern "C" {
                                      13 (additive): SushiHipRetimeSegment, sushi_hip_retime_bytes, sushi_hip_retime;
                                      13 (additive): SUSHI_HIP_MIX_MAX_CHANNELS / _OUTPUTS, sushi_hip_load_decode_mix;
                                      13 (additive): sushi_hip_load_resample_fir;
-                                     13 (additive): SushiHipJointRow, SushiHipJointGroup, sushi_hip_joint_bytes, sushi_hip_joint_reduce */
+                                     13 (additive): SushiHipJointRow, SushiHipJointGroup, sushi_hip_joint_bytes, sushi_hip_joint_reduce;
+                                     13 (additive): sushi_hip_path_bytes, sushi_hip_path_stay_words, sushi_hip_path_forward,
+                                     sushi_hip_path_backtrack */
 
 #if defined(__GNUC__)
 #define SUSHI_HIP_API __attribute__((visibility("default")))
@@ -478,6 +480,55 @@ SUSHI_HIP_API int sushi_hip_joint_reduce(const float* curves_dev, int64_t n_curv
                                          int32_t* out_idx_dev, float* out_score_dev,
                                          float* out_row_score_dev, int32_t* out_row_idx_dev, float* out_row_best_dev,
                                          float* out_joint_dev, void* hip_stream);
+
+/* ---- segmentation: where the shift a sequence of score rows shares changes (13, additive) -----------------
+ * A joint search needs its groups named.  Here the rows of consecutive events lie on one shift axis in event order, and a shift is
+ * chosen per event that minimises the sum of the events' weighted scores plus a fixed price `penalty` for every change of shift
+ * between consecutive events (a Potts model: a Viterbi pass of O(events x shifts)).  The groups and their borders are what the
+ * backtrack finds.  A sequence is E >= 1 rows R_e; a row is n_shift >= 1 consecutive float32 values of a sushi_hip_match_curves
+ * output (all rows by one method) at a curve_off of its own, with a float64 weight w_e, finite and >= 0 (a SushiHipJointRow);
+ * penalty is a finite float64 >= 0.  Everything is float64; products and sums round separately (no fused multiply-add):
+ *     c_e[j] = (double)R_e[j] (SQDIFF_NORMED) or -(double)R_e[j] (CCOEFF_NORMED: an exact negation);  u_e[j] = w_e * c_e[j]
+ *     D_0[j] = u_0[j]
+ *     m_e = min_j D_e[j], a_e = the FIRST index of it (0.0 and -0.0 tie, as in NumPy)
+ *     for e >= 1:  jump_e = m_{e-1} + penalty;  stay_e[j] = (D_{e-1}[j] <= jump_e)  (a tie stays);
+ *                  D_e[j] = u_e[j] + (stay_e[j] ? D_{e-1}[j] : jump_e)
+ *     backtrack:   s_{E-1} = a_{E-1};  for e = E-1 .. 1:  s_{e-1} = stay_e[s_e] ? s_e : a_{e-1}
+ * The total cost is m_{E-1}.  Because floating-point addition is monotone, it equals the minimum over ALL n_shift^E paths of the
+ * path's cost accumulated in this order: c = u_0[s_0]; per event c = c + penalty if the shift changed, then c = c + u_e[s_e].
+ * Per row the pass also returns the row's own first extremum over the axis (minimum / maximum by method; 0.0 and -0.0 tie), as
+ * index and float32 value with its own bits: what a lone search over that range returns.  Rows are assumed finite; with a NaN the
+ * results are unspecified, but no access leaves the buffers (indices are clamped into [0, n_shift)).
+ * Stay bits: row e's occupy sushi_hip_path_stay_words(n_shift) = ceil(n_shift / 64) 64-bit words from word e * that on; shift j is
+ * bit j % 64 of word j / 64; tail bits and all of row 0's are zero. */
+/* workspace of a forward call (two sets of per-workgroup partial minima, used by turns; a row's curve_off and weight travel with
+ * its launch, nothing is uploaded); 0 for n_rows < 1 or n_shift < 1 */
+SUSHI_HIP_API size_t sushi_hip_path_bytes(int n_rows, int32_t n_shift);
+/* 64-bit words of one row's stay bits; 0 for n_shift < 1 */
+SUSHI_HIP_API int64_t sushi_hip_path_stay_words(int32_t n_shift);
+/* Advances rows row0 .. row0 + n_rows - 1 of a sequence of n_total rows: rows_host[i] is row row0 + i.  The output arrays are the
+ * whole sequence's -- D_dev: [n_shift] float64, updated in place; stay_dev: [n_total][words]; row_min_dev (m_e) float64,
+ * row_arg_dev (a_e) int32, row_own_index_dev int32, row_own_score_dev float32: [n_total] -- and the call writes rows row0 ..
+ * row0 + n_rows - 1 of them.  row0 > 0 continues from D_dev and row_min_dev[row0 - 1] as the call before it on the same stream left
+ * them, so a sequence whose curves do not fit in memory at once is streamed through in chunks of events, with the bits of one
+ * call.  No device allocation, no upload: one launch per row, stream-ordered, and one that closes the last row.  Asynchronous;
+ * stateless (any thread, own workspace and arrays).  Checked before any HIP call -- EINVAL: a null pointer, an unknown method,
+ * n_rows < 1, n_shift < 1, n_curve < 1, n_shift > n_curve, n_total < 1, row0 < 0, row0 + n_rows > n_total, curve_off < 0 or
+ * curve_off + n_shift > n_curve (decided without forming the sum), a weight or a penalty that is not finite or is negative;
+ * EALIGN: mem_dev not 256-byte aligned; ENOSPACE: mem_bytes < sushi_hip_path_bytes; EALIGN: D_dev / stay_dev / row_min_dev not
+ * 8-byte aligned, a float / int32 pointer not 4-byte aligned. */
+SUSHI_HIP_API int sushi_hip_path_forward(const float* curves_dev, int64_t n_curve,
+                                         const SushiHipJointRow* rows_host, int n_rows, int32_t n_shift,
+                                         int method, double penalty, int row0, int n_total,
+                                         double* D_dev, unsigned long long* stay_dev,
+                                         double* row_min_dev, int32_t* row_arg_dev,
+                                         int32_t* row_own_index_dev, float* row_own_score_dev,
+                                         void* mem_dev, size_t mem_bytes, void* hip_stream);
+/* out_shift_dev[e] = s_e for the n_total rows of a sequence whose forward calls lie before it on the stream.  One wave, one lane
+ * walking n_total dependent bit reads.  EINVAL: a null pointer, n_total < 1, n_shift < 1; EALIGN: stay_dev not 8-byte aligned, an
+ * int32 pointer not 4-byte aligned. */
+SUSHI_HIP_API int sushi_hip_path_backtrack(const unsigned long long* stay_dev, const int32_t* row_arg_dev, int n_total,
+                                           int32_t n_shift, int32_t* out_shift_dev, void* hip_stream);
 
 /* ---- WavStream.__init__ on the GPU (wav.py:64-91 decode + downmix, wav.py:113-156 value pipeline) ----
  * sushi_hip_load_decode   : interleaved little-endian PCM frames (sample_width 2 or 3 bytes, `channels` per frame)

@@ -173,6 +173,14 @@ def lib():
     L.sushi_hip_joint_bytes.argtypes = [ci, ci]
     L.sushi_hip_joint_reduce.restype = ci
     L.sushi_hip_joint_reduce.argtypes = [vp, i64, vp, ci, vp, ci, ci, vp, sz, vp, vp, vp, vp, vp, vp, vp]
+    L.sushi_hip_path_bytes.restype = sz
+    L.sushi_hip_path_bytes.argtypes = [ci, i32]
+    L.sushi_hip_path_stay_words.restype = i64
+    L.sushi_hip_path_stay_words.argtypes = [i32]
+    L.sushi_hip_path_forward.restype = ci
+    L.sushi_hip_path_forward.argtypes = [vp, i64, vp, ci, i32, ci, dbl, ci, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.sushi_hip_path_backtrack.restype = ci
+    L.sushi_hip_path_backtrack.argtypes = [vp, vp, ci, i32, vp, vp]
     L.sushi_hip_load_decode.restype = ci
     L.sushi_hip_load_decode.argtypes = [vp, i64, i32, i32, vp, vp]
     L.sushi_hip_load_decode_mix.restype = ci

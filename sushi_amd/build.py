@@ -41,6 +41,9 @@ UNITS = [
     # a group of score rows on one shift axis, summed by weight and reduced to its first extremum (joint_core.hpp: the arithmetic,
     # and the call's host side)
     ("sushi_joint", ["-ffp-contract=off"]),     # NumPy's float64 operation order: product and sum round separately
+    # where the shift a sequence of score rows shares changes: a Viterbi pass with one price per change, one launch per row
+    # (path_core.hpp: the arithmetic, and the call's host side)
+    ("sushi_path", ["-ffp-contract=off"]),      # NumPy's float64 operation order: product and sum round separately
     # overlap-save FFT path; its parts, by stage, are csrc/sushi_fft_*.inc (included inside its anonymous namespace); the plan of
     # a batch (plan_core.hpp), what a handle holds about its requests and how it is staged (batch_core.hpp) and what a run decides
     # (run_policy.hpp) are host only

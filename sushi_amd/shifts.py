@@ -393,3 +393,23 @@ def calculate_group_shifts(src_stream, dst_stream, groups, window, centre_shifts
         for e, score in zip(group, match.event_scores):
             e.set_shift(shift + match.delta, score)
     return matches
+
+
+def calculate_segmented_shifts(src_stream, dst_stream, events, window, penalty, centre_shift=0.0):
+    """A shift per event, changing only where a change pays (sushi_amd.segments): `events` is a list of ScriptEvent
+    in order; every event's pattern is src_stream.get_substream(e.start, e.end) and its centre e.start + centre_shift.  All go
+    through one dst_stream.find_segments call with window `window` (seconds) and `penalty` (its docstring).  Every event gets
+    set_shift(centre_shift + its delta, its own score there).  SushiError for an event whose pattern is empty.  Returns the
+    Segmentation."""
+    events = list(events)
+    shift = float(centre_shift)
+    if not events:
+        raise SushiError("calculate_segmented_shifts: no events")
+    patterns = [src_stream.get_substream(e.start, e.end) for e in events]
+    for e, p in zip(events, patterns):
+        if p.shape[1] < 1:
+            raise SushiError("calculate_segmented_shifts: event %s has no samples in the source" % e)
+    found = dst_stream.find_segments(patterns, [e.start + shift for e in events], window, penalty)
+    for e, delta, score in zip(events, found.deltas, found.event_scores):
+        e.set_shift(shift + delta, score)
+    return found

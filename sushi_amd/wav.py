@@ -585,6 +585,30 @@ class WavStream(object):
         return joint.find_joint_many(self, groups, window_sizes, weights=weights, method=method, with_curve=with_curve,
                                      max_bytes=joint.MAX_BYTES if max_bytes is None else int(max_bytes))
 
+    # ------------------------------------------------------------------ where the shared shift changes
+    def find_segments(self, patterns, window_centers, window_size, penalty, weights='equal', method="sqdiff_normed", max_bytes=None,
+                      max_state_bytes=None):
+        """A shift for every event of a sequence, and the places where it changes (sushi_amd.segments): the events
+        (patterns, window_centers: in order) are put on one shift axis -- the displacements k every event can take within
+        W = int(sample_rate * window_size) samples inside the row (sushi_amd.joint.joint_window over all of them), event i at
+        sample _get_sample_for_time(window_centers[i]) + k -- and a shift is chosen per event that minimises the sum of the
+        events' weighted scores plus `penalty` for every change of shift between consecutive events.  Exact: the minimum over all
+        assignments.  penalty (required; finite, >= 0) is in units of one event's weighted score: a change of shift must buy more
+        than `penalty` of summed score, and a lone outlier between two events that agree must beat 2 x penalty.  0 gives every
+        event its lone answer; a huge value gives one shift for all, the arg-min of the weighted sum.  weights: 'equal' (1.0
+        each -- not 1 / m: the penalty is per event), 'length' (M_i * E / sum M) or a sequence of numbers.  method: 'sqdiff_normed'
+        or 'ccoeff_normed' (the scores are negated: the larger is the better).  Patterns are located as find_substreams locates
+        them.  Events go through in chunks under max_bytes of curve memory (default 1 GiB), one match_curves call and one
+        sushi_hip_path_forward call each, then one backtrack; the stay bits and costs of the whole sequence, E x ceil(n_shift / 64)
+        x 8 + n_shift x 8 bytes, must fit max_state_bytes (default 2 GiB; SushiError names the need).  Returns a Segmentation:
+        k_lo, n_shift, shifts (samples per event), deltas (seconds), segments ([(first_event, n_events, delta)]: maximal runs of
+        equal shift), cost, event_scores (every event's score at its chosen shift), event_own_delta / event_own_scores (what a
+        lone search of each event over the same range finds).  Needs a GPU."""
+        from . import segments
+        return segments.find_segments(self, patterns, window_centers, window_size, penalty, weights=weights, method=method,
+                                      max_bytes=segments.MAX_BYTES if max_bytes is None else int(max_bytes),
+                                      max_state_bytes=segments.MAX_STATE_BYTES if max_state_bytes is None else int(max_state_bytes))
+
     # ------------------------------------------------------------------ another clock
     def retimed(self, speed):
         """This stream on the clock of a destination it plays `speed` times as fast as (sushi_amd.retime: 25/24 for PAL-sped-up

@@ -1,0 +1,249 @@
+// sushi_hip_path_forward / sushi_hip_path_backtrack on the CPU (sushi_amd/csrc/path_core.hpp): the call's host side -- stage_path's
+// refusals, the workspace's layout, the work split -- and its arithmetic: path_cost, path_step, the two first-extremum rules and
+// path_backtrack, over whole sequences.
+// usage: host_path_check validate
+//          prints "<case> <return code>" for good and bad arguments (sizes up to INT64_MAX), then the facts of staged calls.
+//        host_path_check pass <sqdiff|ccoeff> <penalty> <n_shift> <curves file> <rows file> <output file>
+//          penalty: a float64 as text (a hexadecimal literal keeps its bits); curves: raw float32; rows: SushiHipJointRow records,
+//          one sequence in event order.  The pass is divided as the kernels divide it: the axis into the work items of path_split,
+//          the items onto its workgroups, one partial record per workgroup -- but every order the device leaves open is taken
+//          BACKWARDS here (a workgroup's items, an item's indices, the partial records), so the rules that make the result
+//          independent of the order are what is checked.  The output file holds [shift i32 x E][row_arg i32 x E]
+//          [own index i32 x E][own value f32 x E][row_min f64 x E][stay words u64 x E x words].  The test compares it with
+//          sushi_amd.segments.path_host, bit for bit.
+// Built by tests/test_segments_host.py with g++ -O2 -std=c++17 -ffp-contract=off -fsanitize=address,undefined.
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <vector>
+
+#include "../include/sushi_hip.h"
+#include "../sushi_amd/csrc/path_core.hpp"
+
+namespace {
+
+using sushi::PathStage;
+
+std::vector<unsigned char> read_file(const char* path) {
+    std::vector<unsigned char> buf;
+    FILE* f = std::fopen(path, "rb");
+    if (!f) { std::fprintf(stderr, "cannot open %s\n", path); std::exit(2); }
+    unsigned char tmp[65536];
+    size_t got;
+    while ((got = std::fread(tmp, 1, sizeof(tmp), f)) > 0) buf.insert(buf.end(), tmp, tmp + got);
+    std::fclose(f);
+    return buf;
+}
+
+template <class T>
+std::vector<T> records(const std::vector<unsigned char>& bytes) {
+    std::vector<T> v(bytes.size() / sizeof(T));
+    if (!v.empty()) std::memcpy(v.data(), bytes.data(), v.size() * sizeof(T));
+    return v;
+}
+
+constexpr int64_t MAX64 = std::numeric_limits<int64_t>::max();
+constexpr int32_t MAX32 = std::numeric_limits<int32_t>::max();
+void* const MEM = reinterpret_cast<void*>((uintptr_t)1 << 20);      // aligned, never dereferenced
+
+struct Call {
+    std::vector<SushiHipJointRow> rows;
+    int n_rows;
+    int32_t n_shift;
+    int64_t n_curve;
+    int method;
+    double penalty;
+    int row0, n_total;
+    const void* mem;
+    size_t mem_bytes;
+    bool null_rows;
+};
+
+// rows 2 .. 4 of a sequence of 7 over 499 shifts, on a buffer of 1000 floats
+Call good() {
+    Call c;
+    c.rows = {{0, 1.0}, {501, 0.0}, {333, 2.5}};
+    c.n_rows = 3; c.n_shift = 499; c.n_curve = 1000;
+    c.method = SUSHI_HIP_METHOD_SQDIFF_NORMED;
+    c.penalty = 0.5;
+    c.row0 = 2; c.n_total = 7;
+    c.mem = MEM; c.mem_bytes = 1 << 20;
+    c.null_rows = false;
+    return c;
+}
+
+int stage(const Call& c, PathStage& st) {
+    return sushi::stage_path(c.null_rows ? nullptr : c.rows.data(), c.n_rows, c.n_shift, c.n_curve, c.method, c.penalty, c.row0,
+                             c.n_total, c.mem, c.mem_bytes, st);
+}
+
+void report(const char* name, const Call& c) {
+    PathStage st;
+    std::printf("%s %d\n", name, stage(c, st));
+}
+
+void facts(const char* name, int32_t n_shift) {
+    Call c = good();
+    c.rows = {{0, 1.0}};
+    c.n_rows = 1; c.row0 = 0; c.n_total = 1; c.n_shift = n_shift; c.n_curve = MAX64;
+    PathStage st;
+    const int rc = stage(c, st);
+    std::printf("%s rc=%d", name, rc);
+    if (rc == SUSHI_HIP_OK)
+        std::printf(" per=%d items=%lld grid=%u words=%lld set=%zu bytes=%zu offsets=(%zu,%zu,%zu,%zu)", st.split.per,
+                    (long long)st.split.n_items, st.split.grid, (long long)st.words, st.lay.set_bytes, st.lay.bytes, st.lay.d_min,
+                    st.lay.d_arg, st.lay.own_idx, st.lay.own_val);
+    std::printf("\n");
+}
+
+int validate() {
+    Call c = good();
+    report("good", c);
+    c = good(); c.method = SUSHI_HIP_METHOD_CCOEFF_NORMED; report("good_ccoeff", c);
+    c = good(); c.null_rows = true; report("null_rows", c);
+    c = good(); c.mem = nullptr; report("null_mem", c);
+    c = good(); c.method = 2; report("method_2", c);
+    c = good(); c.method = -1; report("method_neg", c);
+    c = good(); c.n_rows = 0; report("no_rows", c);
+    c = good(); c.n_rows = -3; report("negative_rows", c);
+    c = good(); c.n_shift = 0; report("no_shift", c);
+    c = good(); c.n_shift = -3; report("negative_shift", c);
+    c = good(); c.n_curve = 0; report("empty_curves", c);
+    c = good(); c.n_curve = -5; report("negative_curves", c);
+    c = good(); c.n_shift = 1001; report("shift_beyond_curves", c);
+    // the rows inside the sequence
+    c = good(); c.row0 = 0; c.n_total = 3; report("whole_sequence", c);
+    c = good(); c.row0 = 4; report("rows_end_at_sequence_end", c);
+    c = good(); c.row0 = 5; report("rows_past_sequence_end", c);
+    c = good(); c.row0 = -1; report("row0_negative", c);
+    c = good(); c.row0 = 7; report("row0_at_end", c);
+    c = good(); c.n_total = 0; report("no_total", c);
+    c = good(); c.n_total = -7; report("negative_total", c);
+    c = good(); c.row0 = MAX32 - 3; c.n_total = MAX32; report("rows_end_at_int_max", c);
+    c = good(); c.row0 = MAX32 - 2; c.n_total = MAX32; report("rows_sum_overflows_int", c);
+    c = good(); c.row0 = MAX32; c.n_total = MAX32; report("row0_int_max", c);
+    // the rows inside the curve buffer; sums that do not fit 64 bits are never formed
+    c = good(); c.rows[0].curve_off = -1; report("row_before_curves", c);
+    c = good(); c.rows[1].curve_off = 501; report("row_ends_at_curves_end", c);
+    c = good(); c.rows[1].curve_off = 502; report("row_one_past_curves_end", c);
+    c = good(); c.n_shift = 1; c.rows[2].curve_off = 999; report("single_shift_last_float", c);
+    c = good(); c.n_shift = 1; c.rows[2].curve_off = 1000; report("single_shift_past_end", c);
+    c = good(); c.rows[2].curve_off = MAX64; report("row_at_int64_max", c);
+    c = good(); c.rows[2].curve_off = MAX64 - 498; report("row_sum_overflows", c);
+    c = good(); c.n_curve = MAX64; c.rows[2].curve_off = MAX64 - 499; report("huge_curves_row_at_end", c);
+    c = good(); c.n_curve = MAX64; c.rows[2].curve_off = MAX64 - 498; report("huge_curves_row_past_end", c);
+    c = good(); c.n_curve = MAX64; c.n_shift = MAX32; c.rows[2].curve_off = MAX64 / 2; report("huge_curves_int32_max_shifts", c);
+    // weights and the penalty
+    c = good(); c.rows[1].weight = std::nan(""); report("weight_nan", c);
+    c = good(); c.rows[1].weight = INFINITY; report("weight_inf", c);
+    c = good(); c.rows[1].weight = -INFINITY; report("weight_neg_inf", c);
+    c = good(); c.rows[1].weight = -1e-300; report("weight_negative", c);
+    c = good(); c.rows[1].weight = -0.0; report("weight_neg_zero", c);
+    c = good(); c.rows[1].weight = 1e300; report("weight_large", c);
+    c = good(); c.penalty = std::nan(""); report("penalty_nan", c);
+    c = good(); c.penalty = INFINITY; report("penalty_inf", c);
+    c = good(); c.penalty = -1e-300; report("penalty_negative", c);
+    c = good(); c.penalty = 0.0; report("penalty_zero", c);
+    c = good(); c.penalty = -0.0; report("penalty_neg_zero", c);
+    c = good(); c.penalty = 1e300; report("penalty_large", c);
+    // the workspace: one partial record of 20 bytes per set, each set padded to 256
+    c = good(); c.mem_bytes = 512; report("workspace_exact", c);
+    c = good(); c.mem_bytes = 511; report("workspace_short", c);
+    c = good(); c.mem_bytes = 0; report("workspace_none", c);
+    c = good(); c.mem = reinterpret_cast<void*>(((uintptr_t)1 << 20) + 128); report("workspace_misaligned", c);
+    c = good(); c.mem = reinterpret_cast<void*>(((uintptr_t)1 << 20) + 128); c.mem_bytes = 0; report("workspace_misaligned_and_short", c);
+    c = good(); c.n_shift = 0; c.mem_bytes = 0; report("bad_tables_before_workspace", c);
+
+    std::printf("bytes %zu %zu %zu %zu %zu %zu %zu\n", sushi::path_layout_bytes(1, 1), sushi::path_layout_bytes(7, 513),
+                sushi::path_layout_bytes(200, 240001), sushi::path_layout_bytes(1, MAX32), sushi::path_layout_bytes(0, 5),
+                sushi::path_layout_bytes(5, 0), sushi::path_layout_bytes(-1, -1));
+    std::printf("words %lld %lld %lld %lld %lld %lld\n", (long long)sushi::path_stay_words(1), (long long)sushi::path_stay_words(64),
+                (long long)sushi::path_stay_words(65), (long long)sushi::path_stay_words(MAX32), (long long)sushi::path_stay_words(0),
+                (long long)sushi::path_stay_words(-4));
+    facts("facts_one", 1);
+    facts("facts_512", 512);
+    facts("facts_513", 513);
+    facts("facts_240001", 240001);
+    // the size from which on the large items are taken, and one shift below it
+    facts("facts_large_items", 1023 * 2048 + 1);
+    facts("facts_small_items", 1023 * 2048);
+    facts("facts_2880001", 2880001);
+    facts("facts_int32_max", MAX32);
+    return 0;
+}
+
+int pass(const char* method_name, const char* penalty_text, const char* n_shift_text, const char* curves_path, const char* rows_path,
+         const char* out_path) {
+    const int method = !std::strcmp(method_name, "ccoeff") ? SUSHI_HIP_METHOD_CCOEFF_NORMED : SUSHI_HIP_METHOD_SQDIFF_NORMED;
+    const double penalty = std::strtod(penalty_text, nullptr);
+    const int32_t n_shift = (int32_t)std::strtol(n_shift_text, nullptr, 10);
+    const std::vector<float> curves = records<float>(read_file(curves_path));
+    const std::vector<SushiHipJointRow> rows = records<SushiHipJointRow>(read_file(rows_path));
+    const int E = (int)rows.size();
+    PathStage st;
+    const int rc = sushi::stage_path(rows.data(), E, n_shift, (int64_t)curves.size(), method, penalty, 0, E, MEM, (size_t)1 << 30, st);
+    if (rc != SUSHI_HIP_OK) { std::fprintf(stderr, "stage_path refused the call: %d\n", rc); return 3; }
+    const int64_t words = st.words, span = (int64_t)st.split.per * sushi::PATH_THREADS;
+    const int grid = (int)st.split.grid;
+    std::vector<double> D((size_t)n_shift), row_min((size_t)E), p_min((size_t)grid);
+    std::vector<uint64_t> stay((size_t)(E * words), 0);
+    std::vector<int32_t> row_arg((size_t)E), own_idx((size_t)E), shifts((size_t)E), p_arg((size_t)grid), p_own_idx((size_t)grid);
+    std::vector<float> own_val((size_t)E), p_own_val((size_t)grid);
+    const float worst = method == SUSHI_HIP_METHOD_CCOEFF_NORMED ? -INFINITY : INFINITY;
+    for (int e = 0; e < E; ++e) {
+        const float* r = curves.data() + rows[(size_t)e].curve_off;
+        const double jump = e ? row_min[(size_t)e - 1] + penalty : 0.0;
+        for (int b = grid - 1; b >= 0; --b) {                              // one partial record per workgroup
+            double best = INFINITY; int32_t at = sushi::PATH_NO_INDEX;
+            float own = worst; int32_t own_at = sushi::PATH_NO_INDEX;
+            int64_t last_item = b;
+            while (last_item + grid < st.split.n_items) last_item += grid;
+            for (int64_t item = last_item; item >= b; item -= grid) {
+                const int64_t lo = item * span, hi = lo + span < n_shift ? lo + span : n_shift;
+                for (int64_t j = hi - 1; j >= lo; --j) {
+                    const double u = sushi::path_cost(method, rows[(size_t)e].weight, r[j]);
+                    bool s = false;
+                    const double stepped = e ? sushi::path_step(D[(size_t)j], u, jump, &s) : u;
+                    D[(size_t)j] = stepped;
+                    if (e && s) stay[(size_t)(e * words + (j >> 6))] |= (uint64_t)1 << (j & 63);
+                    if (sushi::path_min_replaces(stepped, (int32_t)j, best, at)) { best = stepped; at = (int32_t)j; }
+                    if (sushi::path_own_replaces(method, r[j], (int32_t)j, own, own_at)) { own = r[j]; own_at = (int32_t)j; }
+                }
+            }
+            p_min[(size_t)b] = best; p_arg[(size_t)b] = at; p_own_idx[(size_t)b] = own_at; p_own_val[(size_t)b] = own;
+        }
+        double best = INFINITY; int32_t at = sushi::PATH_NO_INDEX;
+        float own = worst; int32_t own_at = sushi::PATH_NO_INDEX;
+        for (int b = grid - 1; b >= 0; --b) {
+            if (sushi::path_min_replaces(p_min[(size_t)b], p_arg[(size_t)b], best, at)) { best = p_min[(size_t)b]; at = p_arg[(size_t)b]; }
+            if (sushi::path_own_replaces(method, p_own_val[(size_t)b], p_own_idx[(size_t)b], own, own_at)) {
+                own = p_own_val[(size_t)b]; own_at = p_own_idx[(size_t)b];
+            }
+        }
+        row_min[(size_t)e] = best; row_arg[(size_t)e] = sushi::path_clamp(at, n_shift);
+        own_idx[(size_t)e] = sushi::path_clamp(own_at, n_shift); own_val[(size_t)e] = own;
+    }
+    sushi::path_backtrack(stay.data(), row_arg.data(), E, n_shift, shifts.data());
+    FILE* f = std::fopen(out_path, "wb");
+    if (!f) { std::fprintf(stderr, "cannot write %s\n", out_path); return 2; }
+    bool ok = std::fwrite(shifts.data(), 4, shifts.size(), f) == shifts.size();
+    ok = ok && std::fwrite(row_arg.data(), 4, row_arg.size(), f) == row_arg.size();
+    ok = ok && std::fwrite(own_idx.data(), 4, own_idx.size(), f) == own_idx.size();
+    ok = ok && std::fwrite(own_val.data(), 4, own_val.size(), f) == own_val.size();
+    ok = ok && std::fwrite(row_min.data(), 8, row_min.size(), f) == row_min.size();
+    ok = ok && std::fwrite(stay.data(), 8, stay.size(), f) == stay.size();
+    std::fclose(f);
+    return ok ? 0 : 2;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    if (argc == 2 && !std::strcmp(argv[1], "validate")) return validate();
+    if (argc == 8 && !std::strcmp(argv[1], "pass")) return pass(argv[2], argv[3], argv[4], argv[5], argv[6], argv[7]);
+    std::fprintf(stderr, "usage: %s validate | pass <sqdiff|ccoeff> <penalty> <n_shift> <curves> <rows> <output>\n", argv[0]);
+    return 2;
+}
