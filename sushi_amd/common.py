@@ -7,6 +7,13 @@ class SushiError(Exception):
     pass
 
 
+class Record(object):
+    """What a search found, as attributes; a subclass documents them and gives the repr."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
 def clip(value, minimum, maximum):
     """common.py:41-42"""
     return max(min(value, maximum), minimum)

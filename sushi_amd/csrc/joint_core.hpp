@@ -6,7 +6,6 @@
 #ifndef SUSHI_JOINT_CORE_HPP
 #define SUSHI_JOINT_CORE_HPP
 
-#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
@@ -14,41 +13,29 @@
 #include <vector>
 
 #include "../../include/sushi_hip.h"
-#include "sushi_geometry.hpp"      // align_up
-
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define JOINT_HD __host__ __device__
-#else
-#define JOINT_HD
-#endif
+#include "axis_core.hpp"           // the first-extremum rule, the row check, the work split
 
 namespace sushi {
 
 // One row's share of a joint value: acc + w * (double)v, the product rounded before the sum.
-JOINT_HD inline double joint_accumulate(double acc, double w, float v) {
+SUSHI_GEOM_HD inline double joint_accumulate(double acc, double w, float v) {
     const double p = w * (double)v;
     return acc + p;
 }
 
 // joint[j] of a group: rows first_row .. first_row + n_rows - 1 of `rows` (any record with curve_off and weight), in row order.
 template <class Row>
-JOINT_HD inline float joint_value(const float* curves, const Row* rows, int first_row, int n_rows, int64_t j) {
+SUSHI_GEOM_HD inline float joint_value(const float* curves, const Row* rows, int first_row, int n_rows, int64_t j) {
     double acc = 0.0;
     for (int i = 0; i < n_rows; ++i) acc = joint_accumulate(acc, rows[first_row + i].weight, curves[rows[first_row + i].curve_off + j]);
     return (float)acc;
 }
 
-// Whether `v` replaces `best` as the extremum when the values are visited in ascending index order: the FIRST minimum
-// (SQDIFF_NORMED) or maximum (CCOEFF_NORMED) wins; 0.0 and -0.0 tie.
-JOINT_HD inline bool joint_better(int method, float v, float best) {
-    return method == SUSHI_HIP_METHOD_CCOEFF_NORMED ? v > best : v < best;
-}
-
-// the first extremum of n >= 1 values
+// the first extremum of n >= 1 values (axis_better's rule)
 inline int32_t joint_first_extremum(const float* v, int32_t n, int method) {
     int32_t at = 0;
     for (int32_t j = 1; j < n; ++j)
-        if (joint_better(method, v[j], v[at])) at = j;
+        if (axis_better(method, v[j], v[at])) at = j;
     return at;
 }
 
@@ -70,13 +57,8 @@ struct JointRowDev {
 };
 static_assert(sizeof(JointRowDev) == 24, "JointRowDev layout");
 
-// A group's joint indices are cut into work items of PER * JOINT_THREADS consecutive ones, one workgroup each; thread t of an item
-// holds the indices t, t + JOINT_THREADS, ...: a wave's load of one row is 64 consecutive floats.  PER is JOINT_PER_LARGE where
-// there are enough such items to fill the GPU, else JOINT_PER_SMALL (a quarter of the indices each, four times the items).
-constexpr int JOINT_THREADS = 256;
-constexpr int JOINT_PER_LARGE = 8, JOINT_PER_SMALL = 2;
-constexpr int64_t JOINT_FILL = 2048;            // items of JOINT_PER_LARGE from which on they are taken
-constexpr int64_t JOINT_MAX_GRID = 2048;        // a fixed grid striding over the items: 256 CUs, eight workgroups each
+// Every group's joint indices are cut into work items of their own (axis_core.hpp), and one grid strides over the items of all groups.
+constexpr int64_t JOINT_FILL = 2048;            // items of AXIS_PER_LARGE, over all groups, from which on they are taken
 
 // workspace: [JointGroupDev x n_groups][JointRowDev x n_rows][group keys (u64) x n_groups][row keys (u64) x n_rows], each part
 // padded to 256 bytes, uploaded in one copy (the keys as NO_KEY: all bits set)
@@ -99,7 +81,7 @@ inline size_t joint_layout_bytes(int n_groups, int n_rows) {
 struct JointStage {
     std::vector<char> image;    // the workspace as uploaded
     JointLayout lay;
-    int per;                    // JOINT_PER_LARGE or JOINT_PER_SMALL
+    int per;                    // AXIS_PER_LARGE or AXIS_PER_SMALL
     int64_t n_items;
     int64_t n_joint;            // floats of out_joint_dev
     unsigned grid;
@@ -111,28 +93,24 @@ struct JointStage {
 // finite or is negative.  `out` is then unspecified.
 inline int stage_joint(const SushiHipJointRow* rows, int n_rows, const SushiHipJointGroup* groups, int n_groups, int64_t n_curve,
                        int method, JointStage& out) {
-    if (method != SUSHI_HIP_METHOD_SQDIFF_NORMED && method != SUSHI_HIP_METHOD_CCOEFF_NORMED) return SUSHI_HIP_EINVAL;
+    if (!method_known(method)) return SUSHI_HIP_EINVAL;
     if (n_groups < 1 || n_rows < n_groups || n_curve < 1) return SUSHI_HIP_EINVAL;
     int64_t next_row = 0, items_large = 0;
     for (int g = 0; g < n_groups; ++g) {
         const SushiHipJointGroup& G = groups[g];
         if (G.first_row != next_row || G.n_rows < 1 || G.n_rows > n_rows - next_row) return SUSHI_HIP_EINVAL;
         if (G.n_shift < 1 || G.n_shift > n_curve) return SUSHI_HIP_EINVAL;
-        for (int i = 0; i < G.n_rows; ++i) {
-            const SushiHipJointRow& R = rows[G.first_row + i];
-            if (R.curve_off < 0 || R.curve_off > n_curve - G.n_shift) return SUSHI_HIP_EINVAL;
-            if (!isfinite(R.weight) || R.weight < 0.0) return SUSHI_HIP_EINVAL;
-        }
+        for (int i = 0; i < G.n_rows; ++i)
+            if (!axis_row_ok(rows[G.first_row + i], n_curve, G.n_shift)) return SUSHI_HIP_EINVAL;
         next_row += G.n_rows;
-        items_large += ((int64_t)G.n_shift + JOINT_PER_LARGE * JOINT_THREADS - 1) / (JOINT_PER_LARGE * JOINT_THREADS);
+        items_large += axis_items(G.n_shift, AXIS_PER_LARGE);
     }
     if (next_row != n_rows) return SUSHI_HIP_EINVAL;
-    out.per = items_large >= JOINT_FILL ? JOINT_PER_LARGE : JOINT_PER_SMALL;
+    out.per = axis_per(items_large, JOINT_FILL);
     out.lay = joint_layout(n_groups, n_rows);
     out.image.assign(out.lay.bytes, 0);
     JointGroupDev* gd = reinterpret_cast<JointGroupDev*>(out.image.data() + out.lay.groups);
     JointRowDev* rd = reinterpret_cast<JointRowDev*>(out.image.data() + out.lay.rows);
-    const int64_t span = (int64_t)out.per * JOINT_THREADS;
     int64_t items = 0, joint_off = 0;
     for (int g = 0; g < n_groups; ++g) {
         const SushiHipJointGroup& G = groups[g];
@@ -142,13 +120,13 @@ inline int stage_joint(const SushiHipJointRow* rows, int n_rows, const SushiHipJ
             JointRowDev& r = rd[G.first_row + i];
             r.curve_off = rows[G.first_row + i].curve_off; r.weight = rows[G.first_row + i].weight; r.group = g; r.reserved = 0;
         }
-        items += (G.n_shift + span - 1) / span;
+        items += axis_items(G.n_shift, out.per);
         joint_off += G.n_shift;
     }
     memset(out.image.data() + out.lay.group_keys, 0xff, out.lay.bytes - out.lay.group_keys);
     out.n_items = items;
     out.n_joint = joint_off;
-    out.grid = (unsigned)(items < JOINT_MAX_GRID ? items : JOINT_MAX_GRID);
+    out.grid = axis_grid(items);
     return SUSHI_HIP_OK;
 }
 

@@ -10,25 +10,19 @@
 #include <stdint.h>
 
 #include "../../include/sushi_hip.h"
-#include "sushi_geometry.hpp"      // align_up
-
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define PATH_HD __host__ __device__
-#else
-#define PATH_HD
-#endif
+#include "axis_core.hpp"           // the first-extremum rule, the row check, the work split
 
 namespace sushi {
 
 // u_e[j]: the weighted cost of one score.  The cost of a value is the value itself where the smaller score is the better one
 // (SQDIFF_NORMED) and its exact negation where the larger one is (CCOEFF_NORMED); the product rounds once.
-PATH_HD inline double path_cost(int method, double w, float v) {
+SUSHI_GEOM_HD inline double path_cost(int method, double w, float v) {
     const double c = method == SUSHI_HIP_METHOD_CCOEFF_NORMED ? -(double)v : (double)v;
     return w * c;
 }
 
 // D_e[j] from D_{e-1}[j], u_e[j] and jump_e = m_{e-1} + penalty.  *stay: the path into (e, j) comes from (e - 1, j); a tie stays.
-PATH_HD inline double path_step(double d_prev, double u, double jump, bool* stay) {
+SUSHI_GEOM_HD inline double path_step(double d_prev, double u, double jump, bool* stay) {
     *stay = d_prev <= jump;
     return u + (*stay ? d_prev : jump);
 }
@@ -37,33 +31,26 @@ PATH_HD inline double path_step(double d_prev, double u, double jump, bool* stay
 // values (0.0 and -0.0 are equal) the lower index.  No element: at = PATH_NO_INDEX, which every real index beats on a tie.
 constexpr int32_t PATH_NO_INDEX = INT32_MAX;
 // (| and &, not || and &&: the device code takes no branch for it)
-PATH_HD inline bool path_min_replaces(double v, int32_t i, double best, int32_t at) {
+SUSHI_GEOM_HD inline bool path_min_replaces(double v, int32_t i, double best, int32_t at) {
     return ((int)(v < best) | ((int)(v == best) & (int)(i < at))) != 0;
 }
 
-// The same for a row's own first extremum (joint_core.hpp joint_better's rule: strict, so equal values leave the lower index).
-PATH_HD inline bool path_own_better(int method, float v, float best) {
-    return method == SUSHI_HIP_METHOD_CCOEFF_NORMED ? v > best : v < best;
-}
-PATH_HD inline bool path_own_replaces(int method, float v, int32_t i, float best, int32_t at) {
-    return ((int)path_own_better(method, v, best) | ((int)!path_own_better(method, best, v) & (int)(i < at))) != 0;
+// The same for a row's own first extremum (axis_better's rule: strict, so equal values leave the lower index).
+SUSHI_GEOM_HD inline bool path_own_replaces(int method, float v, int32_t i, float best, int32_t at) {
+    return ((int)axis_better(method, v, best) | ((int)!axis_better(method, best, v) & (int)(i < at))) != 0;
 }
 
 // an index a NaN let through (unspecified results) is brought back into the axis: no access leaves the buffers
-PATH_HD inline int32_t path_clamp(int32_t i, int32_t n_shift) { return i < 0 ? 0 : (i >= n_shift ? n_shift - 1 : i); }
+SUSHI_GEOM_HD inline int32_t path_clamp(int32_t i, int32_t n_shift) { return i < 0 ? 0 : (i >= n_shift ? n_shift - 1 : i); }
 
 // ---- the host side of a call ----
-// The shift axis is cut into work items of PER * PATH_THREADS consecutive indices; thread t of an item holds the indices t,
-// t + PATH_THREADS, ...: a wave's 64 lanes hold 64 consecutive indices from a multiple of 64 on -- one contiguous load of the row, and
-// one whole word of stay bits.  PER is PATH_PER_LARGE where there are at least PATH_FILL such items (four workgroups for each of 256
-// CUs: n_shift >= 2,095,105), else PATH_PER_SMALL (a quarter of the indices each, four times the items).  A grid of at most
-// PATH_MAX_GRID workgroups strides over the items; every workgroup leaves one partial record.
-constexpr int PATH_THREADS = 256;
-constexpr int PATH_PER_LARGE = 8, PATH_PER_SMALL = 2;
+// The shift axis is cut into work items (axis_core.hpp: a wave's 64 consecutive indices are also one whole word of stay bits), of
+// AXIS_PER_LARGE where there are at least PATH_FILL such items (four workgroups for each of 256 CUs: n_shift >= 2,095,105).  Every
+// workgroup of the grid leaves one partial record.
 constexpr int64_t PATH_FILL = 1024;
-constexpr int64_t PATH_MAX_GRID = 2048;
+constexpr int PATH_THREADS = AXIS_THREADS;      // a step kernel's workgroup: the threads of one work item
 
-PATH_HD inline int64_t path_stay_words(int64_t n_shift) { return n_shift < 1 || n_shift > INT32_MAX ? 0 : (n_shift + 63) / 64; }
+SUSHI_GEOM_HD inline int64_t path_stay_words(int64_t n_shift) { return n_shift < 1 || n_shift > INT32_MAX ? 0 : (n_shift + 63) / 64; }
 
 struct PathSplit {
     int per;
@@ -72,10 +59,9 @@ struct PathSplit {
 };
 inline PathSplit path_split(int32_t n_shift) {
     PathSplit s;
-    const int64_t large = ((int64_t)n_shift + PATH_PER_LARGE * PATH_THREADS - 1) / (PATH_PER_LARGE * PATH_THREADS);
-    s.per = large >= PATH_FILL ? PATH_PER_LARGE : PATH_PER_SMALL;
-    s.n_items = ((int64_t)n_shift + s.per * PATH_THREADS - 1) / (s.per * PATH_THREADS);
-    s.grid = (unsigned)(s.n_items < PATH_MAX_GRID ? s.n_items : PATH_MAX_GRID);
+    s.per = axis_per(axis_items(n_shift, AXIS_PER_LARGE), PATH_FILL);
+    s.n_items = axis_items(n_shift, s.per);
+    s.grid = axis_grid(s.n_items);
     return s;
 }
 
@@ -114,14 +100,12 @@ struct PathStage {
 inline int stage_path(const SushiHipJointRow* rows, int n_rows, int32_t n_shift, int64_t n_curve, int method, double penalty,
                       int row0, int n_total, const void* mem, size_t mem_bytes, PathStage& out) {
     if (!rows || !mem) return SUSHI_HIP_EINVAL;
-    if (method != SUSHI_HIP_METHOD_SQDIFF_NORMED && method != SUSHI_HIP_METHOD_CCOEFF_NORMED) return SUSHI_HIP_EINVAL;
+    if (!method_known(method)) return SUSHI_HIP_EINVAL;
     if (n_rows < 1 || n_shift < 1 || n_curve < 1 || n_shift > n_curve) return SUSHI_HIP_EINVAL;
     if (n_total < 1 || row0 < 0 || row0 >= n_total || n_rows > n_total - row0) return SUSHI_HIP_EINVAL;
     if (!isfinite(penalty) || penalty < 0.0) return SUSHI_HIP_EINVAL;
-    for (int i = 0; i < n_rows; ++i) {
-        if (rows[i].curve_off < 0 || rows[i].curve_off > n_curve - n_shift) return SUSHI_HIP_EINVAL;
-        if (!isfinite(rows[i].weight) || rows[i].weight < 0.0) return SUSHI_HIP_EINVAL;
-    }
+    for (int i = 0; i < n_rows; ++i)
+        if (!axis_row_ok(rows[i], n_curve, n_shift)) return SUSHI_HIP_EINVAL;
     out.split = path_split(n_shift);
     out.lay = path_layout(n_shift);
     out.words = path_stay_words(n_shift);
@@ -132,7 +116,7 @@ inline int stage_path(const SushiHipJointRow* rows, int n_rows, int32_t n_shift,
 
 // ---- the backtrack: one walker, on the device (one lane) and on the CPU ----
 // s_{E-1} = a_{E-1}; s_{e-1} = stay_e[s_e] ? s_e : a_{e-1}
-PATH_HD inline void path_backtrack(const uint64_t* stay, const int32_t* row_arg, int n_total, int32_t n_shift, int32_t* out_shift) {
+SUSHI_GEOM_HD inline void path_backtrack(const uint64_t* stay, const int32_t* row_arg, int n_total, int32_t n_shift, int32_t* out_shift) {
     const int64_t words = path_stay_words(n_shift);
     int32_t s = path_clamp(row_arg[n_total - 1], n_shift);
     out_shift[n_total - 1] = s;

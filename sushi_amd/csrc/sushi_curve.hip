@@ -424,7 +424,7 @@ size_t sushi_hip_curve_bytes(const SushiHipRequest* req_host, int n) {
 int sushi_hip_match_curves(const SushiHipStream* dst, const SushiHipStream* src, const SushiHipRequest* req_host, int n,
                            int method, void* mem_dev, size_t mem_bytes, float* out_dev, void* hip_stream) { return c_boundary([&]() -> int {
     if (!dst || !src || !req_host || !mem_dev || !out_dev || n < 0) return SUSHI_HIP_EINVAL;
-    if (method != SUSHI_HIP_METHOD_SQDIFF_NORMED && method != SUSHI_HIP_METHOD_CCOEFF_NORMED) return SUSHI_HIP_EINVAL;
+    if (!method_known(method)) return SUSHI_HIP_EINVAL;
     if (n == 0) return SUSHI_HIP_OK;
     if (dst->dtype != src->dtype) return SUSHI_HIP_EINVAL;           // cv2.matchTemplate asserts equal types
     CurveStage staged;

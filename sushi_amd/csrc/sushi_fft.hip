@@ -905,7 +905,7 @@ void sushi_hip_batch_destroy(SushiHipBatch* b) { delete b; }
 
 int sushi_hip_batch_set_method(SushiHipBatch* b, int method) {
     if (!b) return SUSHI_HIP_EINVAL;
-    if (method != SUSHI_HIP_METHOD_SQDIFF_NORMED && method != SUSHI_HIP_METHOD_CCOEFF_NORMED) return SUSHI_HIP_EINVAL;
+    if (!method_known(method)) return SUSHI_HIP_EINVAL;
     b->method = method;                                          // both paths compute both methods
     return SUSHI_HIP_OK;
 }

@@ -65,6 +65,11 @@ SUSHI_GEOM_HD inline int mac_class(int n_seg) {
     return MAC_CLASSES - 1;
 }
 
+// the two matching methods (include/sushi_hip.h): what every entry point that takes a method refuses by
+SUSHI_GEOM_HD inline bool method_known(int method) {
+    return method == SUSHI_HIP_METHOD_SQDIFF_NORMED || method == SUSHI_HIP_METHOD_CCOEFF_NORMED;
+}
+
 // sizes of device-memory parts are rounded up to 256 bytes
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

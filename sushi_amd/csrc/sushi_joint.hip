@@ -57,14 +57,14 @@ __device__ __forceinline__ unsigned long long thread_key(const float (&v)[PER], 
     int64_t at = j0;
 #pragma unroll
     for (int p = 1; p < PER; ++p) {
-        const int64_t j = j0 + p * JOINT_THREADS;
-        if (j < n_shift && joint_better(method, v[p], best)) { best = v[p]; at = j; }
+        const int64_t j = j0 + p * AXIS_THREADS;
+        if (j < n_shift && axis_better(method, v[p], best)) { best = v[p]; at = j; }
     }
     return joint_key<MAX>(best, (unsigned)at);
 }
 
 template <int PER, bool MAX>
-__global__ __launch_bounds__(JOINT_THREADS)
+__global__ __launch_bounds__(AXIS_THREADS)
 void joint_reduce_kernel(JointArgs a) {
     const float* __restrict__ curves = a.curves;
     const JointRowDev* __restrict__ rows = a.rows;
@@ -77,15 +77,13 @@ void joint_reduce_kernel(JointArgs a) {
         const JointGroupDev g = a.groups[lo];
         const int32_t n_shift = g.n_shift;
         // (an item's first index is below n_shift < 2^31; the indices behind it may pass 2^31 only where they are not used: 64 bits)
-        const int64_t j0 = (item - g.first_item) * (PER * JOINT_THREADS) + threadIdx.x;
-        // where the thread's loads go: its indices, those past the group's end moved onto the last one (a load that is always made
-        // needs no branch, and the loads of several rows can be counted in flight; what such a load returns is not used)
+        const int64_t j0 = (item - g.first_item) * (PER * AXIS_THREADS) + threadIdx.x;
+        // where the thread's loads go: its indices, those past the group's end moved onto the last one (axis_at)
         int32_t at[PER];
         double acc[PER];
 #pragma unroll
         for (int p = 0; p < PER; ++p) {
-            const int64_t j = j0 + p * JOINT_THREADS;
-            at[p] = (int32_t)(j < n_shift ? j : n_shift - 1);
+            at[p] = axis_at(j0 + p * AXIS_THREADS, n_shift);
             acc[p] = 0.0;
         }
         int i = 0;
@@ -128,7 +126,7 @@ void joint_reduce_kernel(JointArgs a) {
             float* __restrict__ o = a.out_joint + g.joint_off + j0;
 #pragma unroll
             for (int p = 0; p < PER; ++p)
-                if (j0 + p * JOINT_THREADS < n_shift) o[p * JOINT_THREADS] = joint[p];
+                if (j0 + p * AXIS_THREADS < n_shift) o[p * AXIS_THREADS] = joint[p];
         }
         wave_key_min(thread_key<PER, MAX>(joint, j0, n_shift), a.group_keys + lo);
     }
@@ -137,9 +135,9 @@ void joint_reduce_kernel(JointArgs a) {
 // Keys -> outputs.  Thread t < n_groups: group t's index and the joint value there (formed again: joint_value); thread t < n_rows:
 // row t's own first extremum and its score at its group's joint index.  The values are read where they lie, not taken from the keys
 // (a key holds -0.0 as 0.0).  An index a key could not hold (a NaN row: unspecified results) is taken as 0: no access leaves the rows.
-__global__ __launch_bounds__(JOINT_THREADS)
+__global__ __launch_bounds__(AXIS_THREADS)
 void joint_gather_kernel(JointArgs a) {
-    const int t = blockIdx.x * JOINT_THREADS + threadIdx.x;
+    const int t = blockIdx.x * AXIS_THREADS + threadIdx.x;
     if (t < a.n_groups) {
         const JointGroupDev g = a.groups[t];
         uint32_t idx = key_pos(a.group_keys[t]);
@@ -196,17 +194,12 @@ int sushi_hip_joint_reduce(const float* curves_dev, int64_t n_curve, const Sushi
     a.out_joint = out_joint_dev;
     a.out_idx = out_idx_dev; a.out_score = out_score_dev;
     a.out_row_score = out_row_score_dev; a.out_row_idx = out_row_idx_dev; a.out_row_best = out_row_best_dev;
-    const bool mx = method == SUSHI_HIP_METHOD_CCOEFF_NORMED, large = staged.per == JOINT_PER_LARGE;
-    const dim3 grid(staged.grid), block(JOINT_THREADS);
-    if (large) {
-        if (mx) hipLaunchKernelGGL((joint_reduce_kernel<JOINT_PER_LARGE, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((joint_reduce_kernel<JOINT_PER_LARGE, false>), grid, block, 0, st, a);
-    } else {
-        if (mx) hipLaunchKernelGGL((joint_reduce_kernel<JOINT_PER_SMALL, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((joint_reduce_kernel<JOINT_PER_SMALL, false>), grid, block, 0, st, a);
-    }
+    const dim3 grid(staged.grid), block(AXIS_THREADS);
+    axis_dispatch(staged.per, method == SUSHI_HIP_METHOD_CCOEFF_NORMED, [&](auto per, auto mx) {
+        hipLaunchKernelGGL((joint_reduce_kernel<per.value, mx.value>), grid, block, 0, st, a);
+    });
     if (hipGetLastError() != hipSuccess) return SUSHI_HIP_ELAUNCH;
-    hipLaunchKernelGGL(joint_gather_kernel, dim3((unsigned)((n_rows + JOINT_THREADS - 1) / JOINT_THREADS)), block, 0, st, a);
+    hipLaunchKernelGGL(joint_gather_kernel, dim3((unsigned)((n_rows + AXIS_THREADS - 1) / AXIS_THREADS)), block, 0, st, a);
     return launch_ok();
 }); }
 

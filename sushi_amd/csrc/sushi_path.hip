@@ -105,9 +105,9 @@ __device__ __forceinline__ float own_worst() { return METHOD == SUSHI_HIP_METHOD
 template <int METHOD>
 __device__ __forceinline__ double reduce_partials(const PathPartials& in, int n, bool with_outputs, int row, const PathArgs& a,
                                                   PathLds& s) {
-    // a thread takes the records t, t + 256, ... (PATH_MAX_GRID / PATH_THREADS of them), those past the end moved onto the last one --
+    // a thread takes the records t, t + 256, ... (AXIS_MAX_GRID / PATH_THREADS of them), those past the end moved onto the last one --
     // every load is always made, and all are in flight together; a record met twice changes nothing
-    constexpr int ROUNDS = (int)(PATH_MAX_GRID / PATH_THREADS);
+    constexpr int ROUNDS = (int)(AXIS_MAX_GRID / PATH_THREADS);
     int at[ROUNDS];
     double dv[ROUNDS];
     int32_t di[ROUNDS];
@@ -162,16 +162,13 @@ void path_step_kernel(PathArgs a) {
     for (int64_t item = blockIdx.x; item < a.n_items; item += gridDim.x) {
         // (an item's first index is below n_shift < 2^31; the indices behind it may pass 2^31 only where they are not used: 64 bits)
         const int64_t j0 = item * (PER * PATH_THREADS) + threadIdx.x;
-        // every load is always made, the indices past the end moved onto the last element: a load under a branch would make the
-        // wait counts assume the worst.  What such a load returns is not used.
+        // every load is always made, the indices past the end moved onto the last element (axis_at): a load under a branch would
+        // make the wait counts assume the worst
         int32_t at[PER];
         float r[PER];
         double d[PER];
 #pragma unroll
-        for (int p = 0; p < PER; ++p) {
-            const int64_t j = j0 + p * PATH_THREADS;
-            at[p] = (int32_t)(j < n_shift ? j : n_shift - 1);
-        }
+        for (int p = 0; p < PER; ++p) at[p] = axis_at(j0 + p * PATH_THREADS, n_shift);
 #pragma unroll
         for (int p = 0; p < PER; ++p) r[p] = row[at[p]];
 #pragma unroll
@@ -259,7 +256,7 @@ int sushi_hip_path_forward(const float* curves_dev, int64_t n_curve, const Sushi
     a.n_items = staged.split.n_items;
     a.n_partials = (int)staged.split.grid;
     a.row_min = row_min_dev; a.row_arg = row_arg_dev; a.row_own_index = row_own_index_dev; a.row_own_score = row_own_score_dev;
-    const bool mx = method == SUSHI_HIP_METHOD_CCOEFF_NORMED, large = staged.split.per == PATH_PER_LARGE;
+    const bool mx = method == SUSHI_HIP_METHOD_CCOEFF_NORMED;
     const dim3 grid(staged.split.grid), block(PATH_THREADS);
     for (int i = 0; i < n_rows; ++i) {
         a.e = row0 + i;
@@ -269,13 +266,9 @@ int sushi_hip_path_forward(const float* curves_dev, int64_t n_curve, const Sushi
         a.prev = a.e == 0 ? PREV_NONE : (i == 0 ? PREV_ROW_MIN : PREV_PARTIALS);
         a.in = partial_set((char*)mem_dev, staged.lay, (i + 1) & 1);
         a.out = partial_set((char*)mem_dev, staged.lay, i & 1);
-        if (large) {
-            if (mx) hipLaunchKernelGGL((path_step_kernel<PATH_PER_LARGE, true>), grid, block, 0, st, a);
-            else hipLaunchKernelGGL((path_step_kernel<PATH_PER_LARGE, false>), grid, block, 0, st, a);
-        } else {
-            if (mx) hipLaunchKernelGGL((path_step_kernel<PATH_PER_SMALL, true>), grid, block, 0, st, a);
-            else hipLaunchKernelGGL((path_step_kernel<PATH_PER_SMALL, false>), grid, block, 0, st, a);
-        }
+        axis_dispatch(staged.split.per, mx, [&](auto per, auto is_max) {
+            hipLaunchKernelGGL((path_step_kernel<per.value, is_max.value>), grid, block, 0, st, a);
+        });
         if (hipGetLastError() != hipSuccess) return SUSHI_HIP_ELAUNCH;
     }
     a.e = row0 + n_rows - 1;

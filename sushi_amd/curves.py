@@ -8,8 +8,9 @@ import numpy as np
 import torch
 
 from . import _native
+from .axis import method_code
 from .common import SushiError
-from .device import _buffer, _checked_requests, _raw_stream
+from .device import _checked_requests, _launch
 
 
 def match_curves(dst, src, tmpl_off, tmpl_len, win_start, n_pos, method="sqdiff_normed", out=None, hip_stream=None):
@@ -20,8 +21,7 @@ def match_curves(dst, src, tmpl_off, tmpl_len, win_start, n_pos, method="sqdiff_
     TM_SQDIFF_NORMED value) or 'ccoeff_normed' (the TM_CCOEFF_NORMED value itself, not 1 - value).  ``out``: a contiguous
     float32 CUDA tensor of at least offsets[-1] elements to write into.  Asynchronous on ``hip_stream`` (default: the
     current torch stream of dst's device)."""
-    if method not in _native.METHODS:
-        raise SushiError("method must be one of %s" % sorted(_native.METHODS))
+    code = method_code(method)
     if dst.device != src.device:
         raise SushiError("dst and src streams live on different devices")
     if dst.dtype != src.dtype:
@@ -32,18 +32,13 @@ def match_curves(dst, src, tmpl_off, tmpl_len, win_start, n_pos, method="sqdiff_
     np.cumsum(req["n_pos"].astype(np.int64), out=offsets[1:])
     total = int(offsets[-1])
     L = _native.lib()
-    with torch.cuda.device(dst.device):
-        if out is None:
-            out = torch.empty(total, dtype=torch.float32, device=dst.device)
-        elif out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or out.numel() < total or \
-                out.device != dst.device:
-            raise SushiError("out: a contiguous float32 CUDA tensor of >= %d elements on %s" % (total, dst.device))
-        mem = _buffer(max(256, L.sushi_hip_curve_bytes(req.ctypes.data, n)), dst.device)
-        st = _raw_stream(dst.device) if hip_stream is None else hip_stream
-        rc = L.sushi_hip_match_curves(dst.handle, src.handle, req.ctypes.data, n, _native.METHODS[method], mem.data_ptr(),
-                                      mem.numel(), out.data_ptr(), st)
-        _native.check(rc, "sushi_hip_match_curves")
-        if hip_stream is not None:
-            # (the workspace is the current stream's block: another stream's call returns it to the allocator only once passed)
-            mem.record_stream(torch.cuda.ExternalStream(hip_stream, device=dst.device))
+    if out is None:
+        out = torch.empty(total, dtype=torch.float32, device=dst.device)
+    elif out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or out.numel() < total or \
+            out.device != dst.device:
+        raise SushiError("out: a contiguous float32 CUDA tensor of >= %d elements on %s" % (total, dst.device))
+    _launch("sushi_hip_match_curves", dst.device, L.sushi_hip_curve_bytes(req.ctypes.data, n),
+            lambda mem, mem_bytes, st: L.sushi_hip_match_curves(dst.handle, src.handle, req.ctypes.data, n, code, mem, mem_bytes,
+                                                                out.data_ptr(), st),
+            (out, dst.raw, dst._mem, src.raw, src._mem), hip_stream)
     return out, offsets

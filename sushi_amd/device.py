@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _native
+from .axis import method_code
 from .common import SushiError
 
 _DTYPE_CODE = {np.dtype(np.uint8): _native.U8, np.dtype(np.float32): _native.F32}
@@ -97,6 +98,24 @@ def _buffer(nbytes, device):
     if buf.data_ptr() % 256:
         raise SushiError("device allocation is not 256-byte aligned")
     return buf
+
+
+def _launch(name, device, workspace_bytes, call, tensors, hip_stream=None):
+    """One stateless call of the library, `name`, on `device`: call(workspace pointer, workspace bytes, raw stream) -> its return
+    code, checked.  workspace_bytes: what the call asks for (at least 256 are given; None: it takes no workspace).  Asynchronous on
+    hip_stream (default: the current torch stream of the device); `tensors` -- every tensor the call reads or writes -- and the
+    workspace are blocks of the current stream's, so on a stream of the caller's they are recorded there: the allocator hands none
+    of them out again before that stream has passed the call."""
+    with torch.cuda.device(device):
+        mem = None if workspace_bytes is None else _buffer(max(256, workspace_bytes), device)
+        st = _raw_stream(device) if hip_stream is None else hip_stream
+        rc = call(None, 0, st) if mem is None else call(mem.data_ptr(), mem.numel(), st)
+        _native.check(rc, name)
+        if hip_stream is not None:
+            ext = torch.cuda.ExternalStream(hip_stream, device=device)
+            for t in (mem,) + tuple(tensors):
+                if t is not None:
+                    t.record_stream(ext)
 
 
 class DeviceStream(object):
@@ -282,8 +301,7 @@ class SearchBatch(object):
     def __init__(self, dst, src, tmpl_off, tmpl_len, win_start, n_pos, variant=None, path=None,
                  delta=DEFAULT_DELTA, workspace_bytes=None, method="sqdiff_normed", exclusion=None, headroom=1.0):
         self._handle = None
-        if method not in _native.METHODS:
-            raise SushiError("method must be one of %s" % sorted(_native.METHODS))
+        method_code(method)
         self.method = method
         if dst.device != src.device:
             raise SushiError("dst and src streams live on different devices")
@@ -408,9 +426,7 @@ class SearchBatch(object):
 
     def set_method(self, method):
         """Matching method of the following runs (sushi_hip_batch_set_method): 'sqdiff_normed' or 'ccoeff_normed'."""
-        if method not in _native.METHODS:
-            raise SushiError("method must be one of %s" % sorted(_native.METHODS))
-        _native.check(_native.lib().sushi_hip_batch_set_method(self._handle, _native.METHODS[method]), "sushi_hip_batch_set_method")
+        _native.check(_native.lib().sushi_hip_batch_set_method(self._handle, method_code(method)), "sushi_hip_batch_set_method")
         self.method = method
 
     def set_bound_model(self, model):

@@ -10,15 +10,14 @@ block pairs that no exact score can make pass are excluded by the pair bound, ev
 """
 import numpy as np
 
-from . import _native
+from .axis import method_code
 from .common import SushiError
 from .device import SearchBatch, _checked_requests
 
 
 def _fft_batch(dst, src, tmpl_off, tmpl_len, win_start, n_pos, method, threshold):
     """The argument checks find_occurrences and find_best share, and the FFT-path batch of their requests."""
-    if method not in _native.METHODS:
-        raise SushiError("method must be one of %s" % sorted(_native.METHODS))
+    method_code(method)
     if dst.device != src.device:
         raise SushiError("dst and src streams live on different devices")
     if dst.dtype != src.dtype:
@@ -43,8 +42,7 @@ def peaks(index, score, min_separation, method="ccoeff_normed"):
     'sqdiff_normed'; ties by the lower index), and a hit is kept only if no kept hit lies within ``min_separation`` positions
     (|i - j| < min_separation: a hit exactly min_separation away is kept).  Returns (index int64, score float32) of the kept hits
     in ascending index order.  Deterministic; NumPy on the host."""
-    if method not in _native.METHODS:
-        raise SushiError("method must be one of %s" % sorted(_native.METHODS))
+    method_code(method)
     index = np.asarray(index, np.int64).reshape(-1)
     score = np.asarray(score, np.float32).reshape(-1)
     if index.shape != score.shape:
@@ -85,8 +83,7 @@ def best_peaks(curve, k, min_separation, method="ccoeff_normed", threshold=None)
     ``threshold`` (if given: score >= threshold / score <= threshold) and lie at least ``min_separation`` away from every earlier
     pick.  Returns (index int64, score float32) in pick order, best first; fewer than k where nothing is left.  This is ``peaks``
     over all eligible positions, sorted best first and cut at k.  NumPy on the host; needs no GPU."""
-    if method not in _native.METHODS:
-        raise SushiError("method must be one of %s" % sorted(_native.METHODS))
+    method_code(method)
     c = np.asarray(curve, np.float32).reshape(-1)
     k = int(k)
     sep = int(min_separation)

@@ -15,7 +15,7 @@ from fractions import Fraction
 import numpy as np
 
 from . import _native
-from .common import SushiError
+from .common import Record, SushiError
 
 MAX_TERM = 1 << 20           # numerator and denominator of a step (sushi_hip_retime)
 MAX_RATIO = 8                # a step lies in [1/8, 8]
@@ -129,7 +129,7 @@ def retime_device(tensor, segments, out=None, hip_stream=None):
     dtype and device to write into (samples outside every segment keep their value); None: a new one of the smallest length that
     holds the segments, zero outside them.  Asynchronous on hip_stream (default: the current torch stream of the tensor's device)."""
     import torch
-    from .device import _buffer, _raw_stream
+    from .device import _launch
     codes = {torch.uint8: _native.U8, torch.float32: _native.F32}
     if not isinstance(tensor, torch.Tensor) or tensor.dim() != 1 or not tensor.is_cuda or not tensor.is_contiguous() or \
             tensor.dtype not in codes:
@@ -138,19 +138,15 @@ def retime_device(tensor, segments, out=None, hip_stream=None):
     seg, need = _segments(segments, n, None if out is None else int(out.shape[0]))
     L = _native.lib()
     dev = tensor.device
-    with torch.cuda.device(dev):
-        if out is None:
-            out = torch.zeros(need, dtype=tensor.dtype, device=dev)
-        elif not isinstance(out, torch.Tensor) or out.dim() != 1 or out.dtype != tensor.dtype or out.device != dev or \
-                not out.is_contiguous():
-            raise SushiError("retime: out must be a contiguous 1-D CUDA tensor of the input's dtype and device")
-        mem = _buffer(max(256, L.sushi_hip_retime_bytes(seg.shape[0])), dev)
-        st = _raw_stream(dev) if hip_stream is None else hip_stream
-        rc = L.sushi_hip_retime(tensor.data_ptr(), codes[tensor.dtype], n, seg.ctypes.data, seg.shape[0], out.data_ptr(),
-                                int(out.shape[0]), mem.data_ptr(), mem.numel(), st)
-        _native.check(rc, "sushi_hip_retime")
-        if hip_stream is not None:
-            mem.record_stream(torch.cuda.ExternalStream(hip_stream, device=dev))
+    if out is None:
+        out = torch.zeros(need, dtype=tensor.dtype, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.dim() != 1 or out.dtype != tensor.dtype or out.device != dev or \
+            not out.is_contiguous():
+        raise SushiError("retime: out must be a contiguous 1-D CUDA tensor of the input's dtype and device")
+    _launch("sushi_hip_retime", dev, L.sushi_hip_retime_bytes(seg.shape[0]),
+            lambda mem, mem_bytes, st: L.sushi_hip_retime(tensor.data_ptr(), codes[tensor.dtype], n, seg.ctypes.data, seg.shape[0],
+                                                          out.data_ptr(), int(out.shape[0]), mem, mem_bytes, st),
+            (tensor, out), hip_stream)
     return out
 
 
@@ -185,7 +181,7 @@ def fit_speed(src_index, dst_index):
     return float(np.median((d[b][keep] - d[a][keep]) / (s[b][keep] - s[a][keep])))
 
 
-class SpeedEstimate(object):
+class SpeedEstimate(Record):
     """What estimate_speed found.
     candidates    the speeds tried (Fractions);
     scores        the median probe score per candidate;
@@ -197,9 +193,6 @@ class SpeedEstimate(object):
     probe_scores  [candidate][probe] scores;  probe_src_index / probe_dst_index: where `best`'s probes start in the source body and
                   were found in the destination body (samples);
     seconds       wall time of the call."""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
 
     def __repr__(self):
         return "SpeedEstimate(speed=%s, fitted=%r, offset_seconds=%r, scores=%s)" % (

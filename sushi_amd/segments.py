@@ -16,9 +16,9 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import _native
-from .common import SushiError
-from .joint import MAX_BYTES, _first_extremum, joint_window
+from . import _native, axis
+from .common import Record, SushiError
+from .joint import MAX_BYTES
 
 MAX_STATE_BYTES = 2 << 30     # stay bits and D of one sequence (find_segments)
 
@@ -26,13 +26,8 @@ PathHost = namedtuple("PathHost", "shifts cost row_min row_arg row_own_index row
 
 
 def _checked(weights, n, penalty, method):
-    if method not in _native.METHODS:
-        raise SushiError("method must be one of %s" % sorted(_native.METHODS))
-    w = np.asarray(weights, dtype=np.float64).reshape(-1)
-    if n < 1 or w.shape[0] != n:
-        raise SushiError("path: as many weights as rows (>= 1)")
-    if not np.isfinite(w).all() or (w < 0).any():
-        raise SushiError("path: weights must be finite and >= 0")
+    axis.method_code(method)
+    w = axis.checked_weights(weights, n, "path")
     try:
         lam = float(penalty)
     except (TypeError, ValueError):
@@ -50,11 +45,9 @@ def path_host(rows, weights, penalty, method="sqdiff_normed"):
     s_{E-1} = a_{E-1}, s_{e-1} = s_e if stay_e[s_e] else a_{e-1}.  Returns a PathHost: shifts (int32 index per event), cost
     (float64: m_{E-1}), row_min (float64) / row_arg (int32) per row, row_own_index / row_own_scores (every row's own first
     extremum)."""
-    rows = [np.asarray(r) for r in rows]
+    rows = list(rows)
     w, lam = _checked(weights, len(rows), penalty, method)
-    n = rows[0].shape[0] if rows[0].ndim == 1 else -1
-    if n < 1 or any(r.ndim != 1 or r.dtype != np.float32 or r.shape[0] != n for r in rows):
-        raise SushiError("path: rows are 1-D float32 arrays of one length >= 1")
+    rows = axis.checked_score_rows(rows, "path")
     E = len(rows)
     row_min = np.empty(E, np.float64)
     row_arg = np.empty(E, np.int32)
@@ -80,7 +73,7 @@ def path_host(rows, weights, penalty, method="sqdiff_normed"):
         if not stay[e][s]:
             s = int(row_arg[e - 1])
         shifts[e - 1] = s
-    own = np.array([_first_extremum(r, method) for r in rows], np.int32)
+    own = np.array([axis.first_extremum(r, method) for r in rows], np.int32)
     return PathHost(shifts, float(row_min[E - 1]), row_min, row_arg, own, np.array([r[k] for r, k in zip(rows, own)], np.float32))
 
 
@@ -129,35 +122,21 @@ def path_device(curves, rows, penalty, state, row0=0, method="sqdiff_normed", hi
     in `curves`, a contiguous 1-D float32 CUDA tensor (match_curves' output) on state's device.  row0 > 0 continues what the calls
     before it on the same stream left in `state`: a sequence goes through chunk by chunk, with the bits of one call.  Asynchronous
     on hip_stream (default: the current torch stream of the device)."""
-    import torch
-    from .device import _buffer, _raw_stream
-    if not isinstance(curves, torch.Tensor) or curves.dim() != 1 or not curves.is_cuda or not curves.is_contiguous() or \
-            curves.dtype != torch.float32 or curves.numel() < 1 or curves.device != state.D.device:
-        raise SushiError("path: a contiguous 1-D float32 CUDA tensor of curves on the state's device")
-    if isinstance(rows, np.ndarray) and rows.dtype == _native.JOINT_ROW_DTYPE:
-        rt = np.ascontiguousarray(rows).reshape(-1)
-    else:
-        rt = np.array([(int(o), float(w)) for o, w in rows], dtype=_native.JOINT_ROW_DTYPE).reshape(-1)
+    from .device import _launch
+    axis.check_curves(curves, "path", device=state.D.device)
+    rt = axis.row_table(rows)
     _w, lam = _checked(rt["weight"], rt.shape[0], penalty, method)
     row0 = int(row0)
     if row0 < 0 or row0 + rt.shape[0] > state.n_total:
         raise SushiError("path: rows %d .. %d are not inside a sequence of %d" % (row0, row0 + rt.shape[0] - 1, state.n_total))
-    if (rt["curve_off"] < 0).any() or (rt["curve_off"] > int(curves.numel()) - state.n_shift).any():
-        raise SushiError("path: a row leaves the curve buffer")
+    axis.check_rows_inside(rt, int(curves.numel()), state.n_shift, "path")
     L = _native.lib()
-    dev = state.D.device
-    with torch.cuda.device(dev):
-        mem = _buffer(max(256, L.sushi_hip_path_bytes(rt.shape[0], state.n_shift)), dev)
-        st = _raw_stream(dev) if hip_stream is None else hip_stream
-        rc = L.sushi_hip_path_forward(curves.data_ptr(), int(curves.numel()), rt.ctypes.data, rt.shape[0], state.n_shift,
-                                      _native.METHODS[method], lam, row0, state.n_total, state.D.data_ptr(), state.stay.data_ptr(),
-                                      state.row_min.data_ptr(), state.row_arg.data_ptr(), state.row_own_index.data_ptr(),
-                                      state.row_own_scores.data_ptr(), mem.data_ptr(), mem.numel(), st)
-        _native.check(rc, "sushi_hip_path_forward")
-        if hip_stream is not None:
-            ext = torch.cuda.ExternalStream(hip_stream, device=dev)
-            for t in (mem, curves) + state.tensors():
-                t.record_stream(ext)
+    _launch("sushi_hip_path_forward", state.D.device, L.sushi_hip_path_bytes(rt.shape[0], state.n_shift),
+            lambda mem, mem_bytes, st: L.sushi_hip_path_forward(
+                curves.data_ptr(), int(curves.numel()), rt.ctypes.data, rt.shape[0], state.n_shift, _native.METHODS[method], lam,
+                row0, state.n_total, state.D.data_ptr(), state.stay.data_ptr(), state.row_min.data_ptr(), state.row_arg.data_ptr(),
+                state.row_own_index.data_ptr(), state.row_own_scores.data_ptr(), mem, mem_bytes, st),
+            (curves,) + state.tensors(), hip_stream)
     return state
 
 
@@ -165,21 +144,17 @@ def path_backtrack_device(state, hip_stream=None):
     """sushi_hip_path_backtrack over `state` once every row has gone through path_device on the same stream: the shift index of
     every row, an int32 CUDA tensor."""
     import torch
-    from .device import _raw_stream
+    from .device import _launch
     L = _native.lib()
-    dev = state.D.device
-    with torch.cuda.device(dev):
-        out = torch.empty(state.n_total, dtype=torch.int32, device=dev)
-        st = _raw_stream(dev) if hip_stream is None else hip_stream
-        rc = L.sushi_hip_path_backtrack(state.stay.data_ptr(), state.row_arg.data_ptr(), state.n_total, state.n_shift,
-                                        out.data_ptr(), st)
-        _native.check(rc, "sushi_hip_path_backtrack")
-        if hip_stream is not None:
-            out.record_stream(torch.cuda.ExternalStream(hip_stream, device=dev))
+    out = torch.empty(state.n_total, dtype=torch.int32, device=state.D.device)
+    _launch("sushi_hip_path_backtrack", state.D.device, None,
+            lambda _mem, _mem_bytes, st: L.sushi_hip_path_backtrack(state.stay.data_ptr(), state.row_arg.data_ptr(), state.n_total,
+                                                                    state.n_shift, out.data_ptr(), st),
+            (state.stay, state.row_arg, out), hip_stream)
     return out
 
 
-class Segmentation(object):
+class Segmentation(Record):
     """What find_segments found.
     k_lo, n_shift     the shift axis: displacements k_lo .. k_lo + n_shift - 1 samples (joint_window over all events);
     shifts            every event's displacement in samples (list of int);  deltas: the same in seconds: event i is found at
@@ -189,29 +164,8 @@ class Segmentation(object):
     event_scores      every event's own score at its chosen shift (float32 array);
     event_own_delta   where every event's lone search over the same range lands (seconds, list), event_own_scores its score."""
 
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
-
     def __repr__(self):
         return "Segmentation(segments=%r, cost=%r)" % (self.segments, self.cost)
-
-
-def _weights(weights, lens):
-    n = len(lens)
-    if isinstance(weights, str):
-        if weights == "equal":
-            return [1.0] * n
-        if weights == "length":
-            total = float(sum(lens))
-            return [float(m) * n / total for m in lens]
-        raise SushiError("weights: 'equal', 'length' or a sequence of numbers")
-    try:
-        w = [float(x) for x in weights]
-    except (TypeError, ValueError):
-        raise SushiError("weights: 'equal', 'length' or a sequence of numbers")
-    if len(w) != n:
-        raise SushiError("weights: one per event")
-    return w
 
 
 def find_segments(stream, patterns, window_centers, window_size, penalty, weights="equal", method="sqdiff_normed",
@@ -223,14 +177,11 @@ def find_segments(stream, patterns, window_centers, window_size, penalty, weight
         raise SushiError("find_segments: equally many patterns and centres (>= 1)")
     dst_dev = stream.device_stream()
     src_dev, offs, lens, _ = stream._pattern_source(patterns, dst_dev)
-    lens = [int(m) for m in lens]
-    if min(lens) < 1:
-        raise SushiError("empty pattern")
+    lens = axis.pattern_lengths(lens)
     E = len(patterns)
-    w, lam = _checked(_weights(weights, lens), E, penalty, method)
-    total, rate = int(stream.data.shape[1]), stream.sample_rate
-    bases = [stream._get_sample_for_time(c) for c in centres]
-    k_lo, n_shift = joint_window(bases, lens, total, int(rate * window_size))
+    w, lam = _checked(axis.event_weights(weights, lens, per_event=True), E, penalty, method)
+    ax = axis.event_axis(stream, offs, lens, centres, window_size)
+    k_lo, n_shift, rate = ax.k_lo, ax.n_shift, stream.sample_rate
     need = PathState.nbytes(E, n_shift)
     if need > max_state_bytes:
         raise SushiError("find_segments: %d events x %d shifts need %d bytes of stay bits and costs, max_state_bytes is %d"
@@ -242,13 +193,12 @@ def find_segments(stream, patterns, window_centers, window_size, penalty, weight
     state = PathState(E, n_shift, dst_dev.device)
     for first in range(0, E, per_chunk):
         last = min(E, first + per_chunk)
-        curves, bounds = match_curves(dst_dev, src_dev, [int(o) for o in offs[first:last]], lens[first:last],
-                                      [b + k_lo for b in bases[first:last]], [n_shift] * (last - first), method=method)
-        path_device(curves, list(zip(bounds[:-1].tolist(), w[first:last].tolist())), lam, state, row0=first, method=method)
+        curves, row_off = axis.event_curves(dst_dev, src_dev, [ax.part(first, last)], method)
+        path_device(curves, zip(row_off, w[first:last].tolist()), lam, state, row0=first, method=method)
     index = path_backtrack_device(state).cpu().numpy()
     shifts = [k_lo + int(k) for k in index]
     # every event's score at its chosen shift: curves are exact per position, so these are the bits of its row there
-    at, _ = match_curves(dst_dev, src_dev, [int(o) for o in offs], lens, [b + k for b, k in zip(bases, shifts)], [1] * E, method=method)
+    at, _ = match_curves(dst_dev, src_dev, ax.offs, lens, [b + k for b, k in zip(ax.bases, shifts)], [1] * E, method=method)
     own = state.row_own_index.cpu().numpy()
     return Segmentation(
         k_lo=k_lo, n_shift=n_shift, shifts=shifts, deltas=[k / float(rate) for k in shifts],

@@ -20,6 +20,7 @@ import logging
 import os
 import struct
 import weakref
+from collections import namedtuple
 from time import time
 
 import numpy as np
@@ -29,6 +30,9 @@ from .row import fill_pads, row_layout
 
 WAVE_FORMAT_PCM = 0x0001
 WAVE_FORMAT_EXTENSIBLE = 0xFFFE
+
+# what WavStream._requests returns
+_Requests = namedtuple("_Requests", "dst_dev src_dev offs lens one_owner start_times win_start n_pos")
 
 
 class DownmixedWavFile(object):
@@ -405,35 +409,35 @@ class WavStream(object):
         'ccoeff_normed' = cv2.TM_CCOEFF_NORMED with argmax instead (not used by the reference; the method BASELINE.json names)."""
         from .device import SearchBatch
         n = len(patterns)
-        dst_dev, src_dev, offs, lens, one_owner, start_times, win_start, n_pos = self._requests(
-            'find_substreams', patterns, window_centers, window_sizes)
+        r = self._requests('find_substreams', patterns, window_centers, window_sizes)
+        dst_dev, src_dev = r.dst_dev, r.src_dev
         # A drop-in call is a batch of one (a triple of three): its cost is host work and launches, not arithmetic.  Such batches
         # are kept per (source stream, size, method) and RE-PLANNED in place for the next call (sushi_hip_batch_reset: no
         # allocation, one upload) instead of being built and torn down every time.
         batch = None
-        pooled = n <= 4 and one_owner
+        pooled = n <= 4 and r.one_owner
         if pooled:
             pool = self.__dict__.setdefault("_small_batches", {})
             from .device import default_path
             key = (id(src_dev), n, method, default_path(), os.environ.get("SUSHI_HIP_EXCLUSION"))   # (what a new batch would read from the environment)
             batch = pool.get(key)
-            if batch is not None and (batch.dst is not dst_dev or batch.src is not src_dev or not batch.reset(offs, lens, win_start, n_pos)):
+            if batch is not None and (batch.dst is not dst_dev or batch.src is not src_dev or not batch.reset(r.offs, r.lens, r.win_start, r.n_pos)):
                 batch = None
         if batch is None:
-            batch = SearchBatch(dst_dev, src_dev, offs, lens, win_start, n_pos, method=method, headroom=4.0 if pooled else 1.0)
+            batch = SearchBatch(dst_dev, src_dev, r.offs, r.lens, r.win_start, r.n_pos, method=method, headroom=4.0 if pooled else 1.0)
             if pooled:
                 pool[key] = batch
         batch.run()
         idx, score = batch.results()
-        times = [st + (int(k) / float(self.sample_rate)) for st, k in zip(start_times, idx)]
+        times = [st + (int(k) / float(self.sample_rate)) for st, k in zip(r.start_times, idx)]
         if with_index:
-            return score, times, [int(lo) + int(k) for lo, k in zip(win_start, idx)]
+            return score, times, [int(lo) + int(k) for lo, k in zip(r.win_start, idx)]
         return score, times
 
     def _requests(self, who, patterns, window_centers, window_sizes, widest=False):
         """What the batched methods (`who`: the public one's name, for the error) ask of the device for their patterns and
-        windows: (destination DeviceStream, source DeviceStream, offsets, lengths, whether the patterns are views of ONE live
-        stream; per request: start time, first sample of search_source, result length P).  widest: None for a centre or a size
+        windows, as a _Requests record: destination DeviceStream, source DeviceStream, offsets, lengths, whether the patterns are
+        views of ONE live stream; per request: start time, first sample of search_source, result length P.  widest: None for a centre or a size
         (or for the whole list) is the widest window (_widest)."""
         n = len(patterns)
         if widest:
@@ -451,7 +455,7 @@ class WavStream(object):
             start_times.append(st)
             win_start.append(lo)
             n_pos.append(p)
-        return dst_dev, src_dev, offs, lens, one_owner, start_times, win_start, n_pos
+        return _Requests(dst_dev, src_dev, offs, lens, one_owner, start_times, win_start, n_pos)
 
     def _pattern_source(self, patterns, dst_dev):
         """Where a batch's patterns live: (source DeviceStream, offsets, lengths, whether they are views of ONE live stream).
@@ -499,12 +503,11 @@ class WavStream(object):
         find_substreams does).  window_centers / window_sizes: lists (None entries, or None for the list: the widest window)."""
         from .device import SearchBatch
         from .occurrences import peaks
-        dst_dev, src_dev, offs, lens, _, start_times, win_start, n_pos = self._requests(
-            'find_occurrences_many', patterns, window_centers, window_sizes, widest=True)
-        batch = SearchBatch(dst_dev, src_dev, offs, lens, win_start, n_pos, path="fft", method=method)
+        r = self._requests('find_occurrences_many', patterns, window_centers, window_sizes, widest=True)
+        batch = SearchBatch(r.dst_dev, r.src_dev, r.offs, r.lens, r.win_start, r.n_pos, path="fft", method=method)
         found = batch.occurrences(threshold, capacity)
         out = []
-        for st, (idx, score) in zip(start_times, found):
+        for st, (idx, score) in zip(r.start_times, found):
             if min_separation is not None:
                 idx, score = peaks(idx, score, int(round(float(min_separation) * self.sample_rate)), method)
             out.append((np.asarray(score, np.float32), [st + (int(k) / float(self.sample_rate)) for k in idx]))
@@ -526,13 +529,12 @@ class WavStream(object):
         """[find_best_matches(p, k, c, w) for p, c, w in zip(...)] in one best-k run (patterns located as find_substreams does).
         window_centers / window_sizes: lists (None entries, or None for the list: the widest window)."""
         from .device import SearchBatch
-        dst_dev, src_dev, offs, lens, _, start_times, win_start, n_pos = self._requests(
-            'find_best_matches_many', patterns, window_centers, window_sizes, widest=True)
-        batch = SearchBatch(dst_dev, src_dev, offs, lens, win_start, n_pos, path="fft", method=method)
+        r = self._requests('find_best_matches_many', patterns, window_centers, window_sizes, widest=True)
+        batch = SearchBatch(r.dst_dev, r.src_dev, r.offs, r.lens, r.win_start, r.n_pos, path="fft", method=method)
         sep = None if min_separation is None else max(1, int(round(float(min_separation) * self.sample_rate)))
         found = batch.best(k, sep, threshold)
         return [(np.asarray(score, np.float32), [st + (int(i) / float(self.sample_rate)) for i in idx])
-                for st, (idx, score) in zip(start_times, found)]
+                for st, (idx, score) in zip(r.start_times, found)]
 
     def _widest(self, window_center, window_size):
         """find_occurrences' default window: the widest _window allows -- the whole stream, padding included."""
@@ -555,8 +557,8 @@ class WavStream(object):
         as_tensor=True: a list of (1, P) float32 CUDA tensors -- views of one device buffer, no copy to the host."""
         from .curves import match_curves
         n = len(patterns)
-        dst_dev, src_dev, offs, lens, _, _, win_start, n_pos = self._requests('match_templates', patterns, window_centers, window_sizes)
-        curves, bounds = match_curves(dst_dev, src_dev, offs, lens, win_start, n_pos, method=method)
+        r = self._requests('match_templates', patterns, window_centers, window_sizes)
+        curves, bounds = match_curves(r.dst_dev, r.src_dev, r.offs, r.lens, r.win_start, r.n_pos, method=method)
         if not as_tensor:
             curves = curves.cpu().numpy()
         return [curves[int(bounds[k]):int(bounds[k + 1])].reshape(1, -1) for k in range(n)]

@@ -14,28 +14,17 @@
 
 #include "../include/sushi_hip.h"
 #include "../sushi_amd/csrc/downmix_core.hpp"
+#include "host_check_io.hpp"
 
 namespace {
 
-std::vector<unsigned char> read_file(const char* path) {
-    std::vector<unsigned char> buf;
-    FILE* f = std::fopen(path, "rb");
-    if (!f) { std::fprintf(stderr, "cannot open %s\n", path); std::exit(2); }
-    unsigned char tmp[65536];
-    size_t got;
-    while ((got = std::fread(tmp, 1, sizeof(tmp), f)) > 0) buf.insert(buf.end(), tmp, tmp + got);
-    std::fclose(f);
-    return buf;
-}
-
 template <int WIDTH>
 int run(int channels, int n_out, const char* pcm_path, const char* w_path, const char* out_path) {
-    const std::vector<unsigned char> file = read_file(pcm_path), w_bytes = read_file(w_path);
+    const std::vector<unsigned char> file = host_check::read_file(pcm_path), w_bytes = host_check::read_file(w_path);
     const int fs = channels * WIDTH;
     const int64_t n_frames = (int64_t)(file.size() / (size_t)fs);
     if (w_bytes.size() != (size_t)n_out * channels * sizeof(float)) { std::fprintf(stderr, "weights: wrong size\n"); return 2; }
-    std::vector<float> w_rows((size_t)n_out * channels);
-    std::memcpy(w_rows.data(), w_bytes.data(), w_bytes.size());
+    const std::vector<float> w_rows = host_check::records<float>(w_bytes);
     // as the entry point lays them out for the kernel: w[c * 8 + o], zero elsewhere
     std::vector<float> w((size_t)sushi::DOWNMIX_MAX_CHANNELS * sushi::DOWNMIX_MAX_OUTPUTS, 0.f);
     for (int c = 0; c < channels; ++c)
@@ -67,11 +56,7 @@ int run(int channels, int n_out, const char* pcm_path, const char* w_path, const
     std::free(block);
     std::free(exact);
     if (rc) return rc;
-    FILE* fo = std::fopen(out_path, "wb");
-    if (!fo) { std::fprintf(stderr, "cannot write %s\n", out_path); return 2; }
-    const size_t put = std::fwrite(out.data(), sizeof(float), out.size(), fo);
-    std::fclose(fo);
-    return put == out.size() ? 0 : 2;
+    return host_check::write_file(out_path, {host_check::part(out)});
 }
 
 }  // namespace

@@ -18,28 +18,13 @@
 
 #include "../include/sushi_hip.h"
 #include "../sushi_amd/csrc/joint_core.hpp"
+#include "host_check_io.hpp"
 
 namespace {
 
+using host_check::read_file;
+using host_check::records;
 using sushi::JointStage;
-
-std::vector<unsigned char> read_file(const char* path) {
-    std::vector<unsigned char> buf;
-    FILE* f = std::fopen(path, "rb");
-    if (!f) { std::fprintf(stderr, "cannot open %s\n", path); std::exit(2); }
-    unsigned char tmp[65536];
-    size_t got;
-    while ((got = std::fread(tmp, 1, sizeof(tmp), f)) > 0) buf.insert(buf.end(), tmp, tmp + got);
-    std::fclose(f);
-    return buf;
-}
-
-template <class T>
-std::vector<T> records(const std::vector<unsigned char>& bytes) {
-    std::vector<T> v(bytes.size() / sizeof(T));
-    if (!v.empty()) std::memcpy(v.data(), bytes.data(), v.size() * sizeof(T));
-    return v;
-}
 
 constexpr int64_t MAX64 = std::numeric_limits<int64_t>::max();
 
@@ -178,16 +163,8 @@ int reduce(const char* method_name, const char* curves_path, const char* rows_pa
             row_score[(size_t)i] = r[idx[g]];
         }
     }
-    FILE* f = std::fopen(out_path, "wb");
-    if (!f) { std::fprintf(stderr, "cannot write %s\n", out_path); return 2; }
-    bool ok = std::fwrite(idx.data(), 4, idx.size(), f) == idx.size();
-    ok = ok && std::fwrite(score.data(), 4, score.size(), f) == score.size();
-    ok = ok && std::fwrite(row_score.data(), 4, row_score.size(), f) == row_score.size();
-    ok = ok && std::fwrite(row_idx.data(), 4, row_idx.size(), f) == row_idx.size();
-    ok = ok && std::fwrite(row_best.data(), 4, row_best.size(), f) == row_best.size();
-    ok = ok && std::fwrite(joint.data(), 4, joint.size(), f) == joint.size();
-    std::fclose(f);
-    return ok ? 0 : 2;
+    using host_check::part;
+    return host_check::write_file(out_path, {part(idx), part(score), part(row_score), part(row_idx), part(row_best), part(joint)});
 }
 
 }  // namespace

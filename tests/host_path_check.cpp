@@ -22,28 +22,13 @@
 
 #include "../include/sushi_hip.h"
 #include "../sushi_amd/csrc/path_core.hpp"
+#include "host_check_io.hpp"
 
 namespace {
 
+using host_check::read_file;
+using host_check::records;
 using sushi::PathStage;
-
-std::vector<unsigned char> read_file(const char* path) {
-    std::vector<unsigned char> buf;
-    FILE* f = std::fopen(path, "rb");
-    if (!f) { std::fprintf(stderr, "cannot open %s\n", path); std::exit(2); }
-    unsigned char tmp[65536];
-    size_t got;
-    while ((got = std::fread(tmp, 1, sizeof(tmp), f)) > 0) buf.insert(buf.end(), tmp, tmp + got);
-    std::fclose(f);
-    return buf;
-}
-
-template <class T>
-std::vector<T> records(const std::vector<unsigned char>& bytes) {
-    std::vector<T> v(bytes.size() / sizeof(T));
-    if (!v.empty()) std::memcpy(v.data(), bytes.data(), v.size() * sizeof(T));
-    return v;
-}
 
 constexpr int64_t MAX64 = std::numeric_limits<int64_t>::max();
 constexpr int32_t MAX32 = std::numeric_limits<int32_t>::max();
@@ -227,16 +212,8 @@ int pass(const char* method_name, const char* penalty_text, const char* n_shift_
         own_idx[(size_t)e] = sushi::path_clamp(own_at, n_shift); own_val[(size_t)e] = own;
     }
     sushi::path_backtrack(stay.data(), row_arg.data(), E, n_shift, shifts.data());
-    FILE* f = std::fopen(out_path, "wb");
-    if (!f) { std::fprintf(stderr, "cannot write %s\n", out_path); return 2; }
-    bool ok = std::fwrite(shifts.data(), 4, shifts.size(), f) == shifts.size();
-    ok = ok && std::fwrite(row_arg.data(), 4, row_arg.size(), f) == row_arg.size();
-    ok = ok && std::fwrite(own_idx.data(), 4, own_idx.size(), f) == own_idx.size();
-    ok = ok && std::fwrite(own_val.data(), 4, own_val.size(), f) == own_val.size();
-    ok = ok && std::fwrite(row_min.data(), 8, row_min.size(), f) == row_min.size();
-    ok = ok && std::fwrite(stay.data(), 8, stay.size(), f) == stay.size();
-    std::fclose(f);
-    return ok ? 0 : 2;
+    using host_check::part;
+    return host_check::write_file(out_path, {part(shifts), part(row_arg), part(own_idx), part(own_val), part(row_min), part(stay)});
 }
 
 }  // namespace

@@ -11,22 +11,12 @@
 #include <vector>
 
 #include "../sushi_amd/csrc/resample_core.hpp"
+#include "host_check_io.hpp"
 
 namespace {
 
 constexpr int RUN = 1024;    // outputs of a workgroup's run
 constexpr int HOP = 256;     // outputs between two of one thread
-
-std::vector<unsigned char> read_file(const char* path) {
-    std::vector<unsigned char> buf;
-    FILE* f = std::fopen(path, "rb");
-    if (!f) { std::fprintf(stderr, "cannot open %s\n", path); std::exit(2); }
-    unsigned char tmp[65536];
-    size_t got;
-    while ((got = std::fread(tmp, 1, sizeof(tmp), f)) > 0) buf.insert(buf.end(), tmp, tmp + got);
-    std::fclose(f);
-    return buf;
-}
 
 }  // namespace
 
@@ -37,15 +27,13 @@ int main(int argc, char** argv) {
     if (num < 1 || num > sushi::RESAMPLE_MAX_TERM || den < 1 || den > sushi::RESAMPLE_MAX_TERM || W < 1 ||
         (int64_t)den * 2 * W > sushi::RESAMPLE_MAX_TABLE || n_body < 1 || n_body >= sushi::RESAMPLE_MAX_BODY)
         return 2;
-    const std::vector<unsigned char> in_bytes = read_file(argv[1]), table_bytes = read_file(argv[2]);
-    const int64_t n_raw = (int64_t)(in_bytes.size() / sizeof(float));
+    const std::vector<float> x = host_check::records<float>(host_check::read_file(argv[1]));
+    const std::vector<unsigned char> table_bytes = host_check::read_file(argv[2]);
+    const int64_t n_raw = (int64_t)x.size();
     const int32_t taps = 2 * W;
     if (n_raw < 1 || table_bytes.size() != (size_t)den * taps * sizeof(double)) return 2;
     if ((n_body - 1) * (int64_t)num / den > n_raw - 1) return 2;
-    std::vector<float> x((size_t)n_raw);
-    std::memcpy(x.data(), in_bytes.data(), (size_t)n_raw * sizeof(float));
-    std::vector<double> table((size_t)den * taps);
-    std::memcpy(table.data(), table_bytes.data(), table.size() * sizeof(double));
+    const std::vector<double> table = host_check::records<double>(table_bytes);
     std::vector<float> out((size_t)n_body);
     const int64_t hop = (int64_t)HOP * num;
     const int32_t qhop = (int32_t)(hop / den), rhop = (int32_t)(hop % den);
@@ -62,9 +50,5 @@ int main(int argc, char** argv) {
             }
         }
     }
-    FILE* f = std::fopen(argv[3], "wb");
-    if (!f) { std::fprintf(stderr, "cannot write %s\n", argv[3]); return 2; }
-    const size_t put = std::fwrite(out.data(), sizeof(float), out.size(), f);
-    std::fclose(f);
-    return put == out.size() ? 0 : 2;
+    return host_check::write_file(argv[3], {host_check::part(out)});
 }

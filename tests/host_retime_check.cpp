@@ -12,31 +12,17 @@
 
 #include "../include/sushi_hip.h"
 #include "../sushi_amd/csrc/retime_core.hpp"
+#include "host_check_io.hpp"
 
 namespace {
 
 constexpr int RUN = 16;      // outputs between two divisions (a thread's chunk in the kernel)
 
-std::vector<unsigned char> read_file(const char* path) {
-    std::vector<unsigned char> buf;
-    FILE* f = std::fopen(path, "rb");
-    if (!f) { std::fprintf(stderr, "cannot open %s\n", path); std::exit(2); }
-    unsigned char tmp[65536];
-    size_t got;
-    while ((got = std::fread(tmp, 1, sizeof(tmp), f)) > 0) buf.insert(buf.end(), tmp, tmp + got);
-    std::fclose(f);
-    return buf;
-}
-
 template <class T>
 int run(const char* in_path, const char* seg_path, const char* out_path, int64_t n_out) {
-    const std::vector<unsigned char> in_bytes = read_file(in_path), seg_bytes = read_file(seg_path);
-    const int64_t n_in = (int64_t)(in_bytes.size() / sizeof(T));
-    std::vector<T> x((size_t)n_in);
-    std::memcpy(x.data(), in_bytes.data(), (size_t)n_in * sizeof(T));
-    const size_t n_seg = seg_bytes.size() / sizeof(SushiHipRetimeSegment);
-    std::vector<SushiHipRetimeSegment> seg(n_seg);
-    std::memcpy(seg.data(), seg_bytes.data(), n_seg * sizeof(SushiHipRetimeSegment));
+    const std::vector<T> x = host_check::records<T>(host_check::read_file(in_path));
+    const std::vector<SushiHipRetimeSegment> seg = host_check::records<SushiHipRetimeSegment>(host_check::read_file(seg_path));
+    const int64_t n_in = (int64_t)x.size();
     std::vector<T> out((size_t)n_out, (T)0);
     for (const SushiHipRetimeSegment& s : seg) {
         const int32_t qstep = s.num / s.den, rstep = s.num % s.den;
@@ -49,11 +35,7 @@ int run(const char* in_path, const char* seg_path, const char* out_path, int64_t
             }
         }
     }
-    FILE* f = std::fopen(out_path, "wb");
-    if (!f) { std::fprintf(stderr, "cannot write %s\n", out_path); return 2; }
-    const size_t put = std::fwrite(out.data(), sizeof(T), out.size(), f);
-    std::fclose(f);
-    return put == out.size() ? 0 : 2;
+    return host_check::write_file(out_path, {host_check::part(out)});
 }
 
 }  // namespace

@@ -12,7 +12,7 @@ import pytest
 
 import segment_cases as cases
 from host_checks import HERE, KERNEL_ARITHMETIC
-from sushi_amd import _native, joint, segments
+from sushi_amd import _native, axis, joint, segments
 from sushi_amd.common import SushiError
 
 METHODS = ("sqdiff_normed", "ccoeff_normed")
@@ -391,9 +391,9 @@ def test_find_segments_names_the_state_it_cannot_hold():
 
 
 def test_weights_are_per_event():
-    assert segments._weights("equal", [500, 900, 100]) == [1.0, 1.0, 1.0]                  # not 1 / m: the penalty is per event
-    assert segments._weights("length", [500, 900, 100]) == [1.0, 1.8, 0.2]
-    assert segments._weights([2, 0, 1], [5, 5, 5]) == [2.0, 0.0, 1.0]
+    assert axis.event_weights("equal", [500, 900, 100], per_event=True) == [1.0, 1.0, 1.0]  # not 1 / m: the penalty is per event
+    assert axis.event_weights("length", [500, 900, 100], per_event=True) == [1.0, 1.8, 0.2]
+    assert axis.event_weights([2, 0, 1], [5, 5, 5], per_event=True) == [2.0, 0.0, 1.0]
 
 
 # ---------------------------------------------------------------------------------------------- the two-cut scenario on the oracle
