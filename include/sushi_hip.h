@@ -49,7 +49,8 @@ extern "C" {
                                      13 (additive): sushi_hip_load_resample_fir;
                                      13 (additive): SushiHipJointRow, SushiHipJointGroup, sushi_hip_joint_bytes, sushi_hip_joint_reduce;
                                      13 (additive): sushi_hip_path_bytes, sushi_hip_path_stay_words, sushi_hip_path_forward,
-                                     sushi_hip_path_backtrack */
+                                     sushi_hip_path_backtrack;
+                                     13 (additive): sushi_hip_drift_bytes, sushi_hip_drift_reduce */
 
 #if defined(__GNUC__)
 #define SUSHI_HIP_API __attribute__((visibility("default")))
@@ -529,6 +530,45 @@ SUSHI_HIP_API int sushi_hip_path_forward(const float* curves_dev, int64_t n_curv
  * int32 pointer not 4-byte aligned. */
 SUSHI_HIP_API int sushi_hip_path_backtrack(const unsigned long long* stay_dev, const int32_t* row_arg_dev, int n_total,
                                            int32_t n_shift, int32_t* out_shift_dev, void* hip_stream);
+
+/* ---- drift search: score rows summed along a sloped line of shifts (13, additive) -----------------
+ * A joint search sums a group's rows at one displacement.  Where source and destination run at slightly different rates the shared
+ * shift moves along the programme, and the rows have to be summed along a sloped line instead: row e at k + round(r * (pos_e -
+ * anchor)) for a candidate rate r.  The native side does not know rates: it is given E >= 1 rows R_e (SushiHipJointRow: n_shift >= 1
+ * consecutive float32 values of a sushi_hip_match_curves output at a curve_off of its own, all by one method, with a float64 weight
+ * w_e, finite and >= 0) and a table of int32 offsets o[d][e], [n_drifts][n_rows] row-major, n_drifts in 1 .. 65535: the
+ * displacement of row e under candidate d relative to the axis index.  Candidate d is valid on j in [lo_d, hi_d),
+ *     lo_d = max(0, max_e(-o[d][e])),  hi_d = n_shift - max(0, max_e o[d][e]),
+ * where every row is addressed inside itself.  For a valid j, in row order (joint_accumulate, unchanged):
+ *     acc = 0.0
+ *     acc = acc + w_e * (double)R_e[j + o[d][e]]     for e = 0 .. E - 1 (the product and the sum round separately, no fused multiply-add)
+ *     line[d][j] = (float)acc
+ * so a NumPy float64 restatement equals the result bit for bit.  Per candidate the call returns the FIRST index of the minimum
+ * (SUSHI_HIP_METHOD_SQDIFF_NORMED) or maximum (SUSHI_HIP_METHOD_CCOEFF_NORMED) of line[d] over its valid range and that float32
+ * value.  The answer is the best of those: a tie goes to the first candidate in table order, then to the first j; 0.0 and -0.0 tie,
+ * as in NumPy.  Per row it returns R_e[j* + o[d*][e]], the row's own score on the answer's line, read where it lies (-0.0 keeps its
+ * bits).  Row values are assumed finite, and under SQDIFF_NORMED not negative (-0.0 included), as curves are; with a NaN the results
+ * are unspecified, but no access leaves the buffers. */
+/* workspace a drift call needs (the rows, the offset table in blocks of candidates, their valid ranges, the extremum keys); 0 for
+ * n_rows < 1 or n_drifts outside 1 .. 65535 */
+SUSHI_HIP_API size_t sushi_hip_drift_bytes(int n_rows, int n_drifts);
+/* out_best_dev: int32[2], the answer's candidate d* and index j*; out_score_dev: float32[1], line[d*][j*]; out_row_score_dev:
+ * [n_rows] R_e[j* + o[d*][e]]; out_drift_idx_dev / out_drift_score_dev: [n_drifts] every candidate's own first extremum over its
+ * valid range; out_lines_dev: NULL, or [n_drifts][n_shift] the lines, +inf (SQDIFF_NORMED) / -inf (CCOEFF_NORMED) outside a
+ * candidate's valid range.  No device allocation: one upload of the tables into mem_dev (256-byte aligned, >=
+ * sushi_hip_drift_bytes), then three launches (the reduce; keys to the per-candidate outputs and the answer's key; the gather of
+ * the rows' scores).  Asynchronous; stateless (any thread, own workspace).  Checked before any HIP call -- EINVAL: a null pointer
+ * (but out_lines_dev), an unknown method, n_rows < 1, n_drifts outside 1 .. 65535, n_shift < 1, curve_off < 0 or curve_off +
+ * n_shift > n_curve (decided without forming the sum), a weight that is not finite or is negative, a candidate whose valid range is
+ * empty (hi_d <= lo_d, decided in 64 bits: any |o| >= n_shift is one); EALIGN: mem_dev not 256-byte aligned, a float / int32 device
+ * pointer not 4-byte aligned; ENOSPACE: mem_bytes too small. */
+SUSHI_HIP_API int sushi_hip_drift_reduce(const float* curves_dev, int64_t n_curve,
+                                         const SushiHipJointRow* rows_host, int n_rows, int32_t n_shift,
+                                         const int32_t* offsets_host, int n_drifts, int method,
+                                         void* mem_dev, size_t mem_bytes,
+                                         int32_t* out_best_dev, float* out_score_dev, float* out_row_score_dev,
+                                         int32_t* out_drift_idx_dev, float* out_drift_score_dev,
+                                         float* out_lines_dev, void* hip_stream);
 
 /* ---- WavStream.__init__ on the GPU (wav.py:64-91 decode + downmix, wav.py:113-156 value pipeline) ----
  * sushi_hip_load_decode   : interleaved little-endian PCM frames (sample_width 2 or 3 bytes, `channels` per frame)

@@ -173,6 +173,10 @@ def lib():
     L.sushi_hip_joint_bytes.argtypes = [ci, ci]
     L.sushi_hip_joint_reduce.restype = ci
     L.sushi_hip_joint_reduce.argtypes = [vp, i64, vp, ci, vp, ci, ci, vp, sz, vp, vp, vp, vp, vp, vp, vp]
+    L.sushi_hip_drift_bytes.restype = sz
+    L.sushi_hip_drift_bytes.argtypes = [ci, ci]
+    L.sushi_hip_drift_reduce.restype = ci
+    L.sushi_hip_drift_reduce.argtypes = [vp, i64, vp, ci, i32, vp, ci, ci, vp, sz, vp, vp, vp, vp, vp, vp, vp]
     L.sushi_hip_path_bytes.restype = sz
     L.sushi_hip_path_bytes.argtypes = [ci, i32]
     L.sushi_hip_path_stay_words.restype = i64

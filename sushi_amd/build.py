@@ -41,6 +41,9 @@ UNITS = [
     # a group of score rows on one shift axis, summed by weight and reduced to its first extremum (joint_core.hpp: the arithmetic,
     # and the call's host side)
     ("sushi_joint", ["-ffp-contract=off"]),     # NumPy's float64 operation order: product and sum round separately
+    # score rows summed along sloped lines of shifts, one per candidate offset table row, reduced to the first extremum over all
+    # (candidate, index) pairs (drift_core.hpp: the arithmetic, and the call's host side)
+    ("sushi_drift", ["-ffp-contract=off"]),     # joint_accumulate unchanged: product and sum round separately
     # where the shift a sequence of score rows shares changes: a Viterbi pass with one price per change, one launch per row
     # (path_core.hpp: the arithmetic, and the call's host side)
     ("sushi_path", ["-ffp-contract=off"]),      # NumPy's float64 operation order: product and sum round separately

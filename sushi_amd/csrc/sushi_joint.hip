@@ -17,6 +17,7 @@
 #include "../../include/sushi_hip.h"
 #include "sushi_internal.hpp"
 #include "joint_core.hpp"
+#include "axis_device.hpp"         // how an extremum leaves a wave: joint_key, wave_key_min, thread_key
 
 namespace {
 
@@ -36,32 +37,6 @@ struct JointArgs {
     int32_t* out_idx; float* out_score;
     float* out_row_score; int32_t* out_row_idx; float* out_row_best;
 };
-
-template <bool MAX>
-__device__ __forceinline__ unsigned long long joint_key(float v, unsigned pos) { return MAX ? make_key_max(v, pos) : make_key(v, pos); }
-
-// A wave's smallest key into *slot.  Keys only ever fall, so a wave whose key is not below what the slot already holds has nothing to
-// add: most waves leave after the load.
-__device__ __forceinline__ void wave_key_min(unsigned long long key, unsigned long long* slot) {
-    key = wave_min_u64(key);
-    if ((threadIdx.x & 63) == 0 && key != NO_KEY &&
-        key < __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(slot, key);
-}
-
-// the thread's own first extremum of one row's PER values (ascending index), as a key
-template <int PER, bool MAX>
-__device__ __forceinline__ unsigned long long thread_key(const float (&v)[PER], int64_t j0, int32_t n_shift) {
-    constexpr int method = MAX ? SUSHI_HIP_METHOD_CCOEFF_NORMED : SUSHI_HIP_METHOD_SQDIFF_NORMED;
-    if (j0 >= n_shift) return NO_KEY;
-    float best = v[0];
-    int64_t at = j0;
-#pragma unroll
-    for (int p = 1; p < PER; ++p) {
-        const int64_t j = j0 + p * AXIS_THREADS;
-        if (j < n_shift && axis_better(method, v[p], best)) { best = v[p]; at = j; }
-    }
-    return joint_key<MAX>(best, (unsigned)at);
-}
 
 template <int PER, bool MAX>
 __global__ __launch_bounds__(AXIS_THREADS)

@@ -413,3 +413,23 @@ def calculate_segmented_shifts(src_stream, dst_stream, events, window, penalty, 
     for e, delta, score in zip(events, found.deltas, found.event_scores):
         e.set_shift(shift + delta, score)
     return found
+
+
+def calculate_drifting_shifts(src_stream, dst_stream, events, window, max_rate, centre_shift=0.0, resolution=1.0):
+    """A shift per event along one line of shifts (sushi_amd.drift): `events` is a list of ScriptEvent; every
+    event's pattern is src_stream.get_substream(e.start, e.end) and its centre e.start + centre_shift.  All go through one
+    dst_stream.find_drift call with window `window` (seconds), rates out to +-max_rate and `resolution` (its docstring).  Every
+    event gets set_shift(centre_shift + its event_delta, its own score there).  SushiError for an event whose pattern is empty.
+    Returns the DriftMatch."""
+    events = list(events)
+    shift = float(centre_shift)
+    if not events:
+        raise SushiError("calculate_drifting_shifts: no events")
+    patterns = [src_stream.get_substream(e.start, e.end) for e in events]
+    for e, p in zip(events, patterns):
+        if p.shape[1] < 1:
+            raise SushiError("calculate_drifting_shifts: event %s has no samples in the source" % e)
+    found = dst_stream.find_drift(patterns, [e.start + shift for e in events], window, max_rate, resolution=resolution)
+    for e, delta, score in zip(events, found.event_deltas, found.event_scores):
+        e.set_shift(shift + delta, score)
+    return found

@@ -611,6 +611,29 @@ class WavStream(object):
                                       max_bytes=segments.MAX_BYTES if max_bytes is None else int(max_bytes),
                                       max_state_bytes=segments.MAX_STATE_BYTES if max_state_bytes is None else int(max_state_bytes))
 
+    # ------------------------------------------------------------------ a shift that moves along the programme
+    def find_drift(self, patterns, window_centers, window_size, max_rate, resolution=1.0, weights='equal', method="sqdiff_normed",
+                   with_lines=False, max_bytes=None):
+        """The line of shifts a sequence of events shares when source and destination run at slightly different rates
+        (sushi_amd.drift).  The events (patterns, window_centers) are put on one shift axis -- the displacements k
+        every event can take within W = int(sample_rate * window_size) samples inside the row (sushi_amd.joint.joint_window over
+        all of them), event i at sample pos_i + k, pos_i = _get_sample_for_time(window_centers[i]).  Candidate rates are
+        sushi_amd.drift.rate_grid(max_rate, half_span, resolution) around anchor = (min pos + max pos) // 2: steps that move the
+        farthest event by `resolution` samples, out to +-max_rate (seconds of shift per second of programme).  For every rate r
+        and displacement k the events' exact score rows are summed by weight, event i at k + int(np.rint(r * (pos_i - anchor))),
+        and the answer is the first extremum over all (rate, k), the lowest rate first: no lone decision is made.  All rows are
+        resident at once, E x n_shift x 4 bytes under max_bytes (default 1 GiB; SushiError names the need): one match_curves call,
+        one sushi_hip_drift_reduce call, and one sushi_hip_joint_reduce call for every event's own lone extremum.  SushiError when
+        the window leaves a candidate no displacement every event can take: window_size must cover the uncertainty of the base
+        shift + max_rate x half span.  weights: 'equal' (1 / E), 'length' (M_i / sum M) or a sequence of numbers.  Returns a
+        DriftMatch: rate, anchor (seconds), delta (the shift at the anchor), score, index, k_lo, n_shift, event_deltas /
+        event_scores (every event on the line), event_own_delta / event_own_scores (its lone search), drift_rates / drift_scores /
+        drift_deltas (the profile over rate), rate_ties, lines (with_lines).  A large speed difference goes through estimate_speed
+        and retimed first; this finds the residual.  Needs a GPU."""
+        from . import drift
+        return drift.find_drift(self, patterns, window_centers, window_size, max_rate, resolution=resolution, weights=weights,
+                                method=method, with_lines=with_lines, max_bytes=drift.MAX_BYTES if max_bytes is None else int(max_bytes))
+
     # ------------------------------------------------------------------ another clock
     def retimed(self, speed):
         """This stream on the clock of a destination it plays `speed` times as fast as (sushi_amd.retime: 25/24 for PAL-sped-up
