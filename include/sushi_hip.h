@@ -50,7 +50,9 @@ extern "C" {
                                      13 (additive): SushiHipJointRow, SushiHipJointGroup, sushi_hip_joint_bytes, sushi_hip_joint_reduce;
                                      13 (additive): sushi_hip_path_bytes, sushi_hip_path_stay_words, sushi_hip_path_forward,
                                      sushi_hip_path_backtrack;
-                                     13 (additive): sushi_hip_drift_bytes, sushi_hip_drift_reduce */
+                                     13 (additive): sushi_hip_drift_bytes, sushi_hip_drift_reduce;
+                                     13 (additive): SUSHI_HIP_TRACK_MAX_REACH, SUSHI_HIP_TRACK_JUMP, sushi_hip_track_bytes,
+                                     sushi_hip_track_forward, sushi_hip_track_backtrack */
 
 #if defined(__GNUC__)
 #define SUSHI_HIP_API __attribute__((visibility("default")))
@@ -569,6 +571,62 @@ SUSHI_HIP_API int sushi_hip_drift_reduce(const float* curves_dev, int64_t n_curv
                                          int32_t* out_best_dev, float* out_score_dev, float* out_row_score_dev,
                                          int32_t* out_drift_idx_dev, float* out_drift_score_dev,
                                          float* out_lines_dev, void* hip_stream);
+
+/* ---- tracking: a shift that wanders from event to event, and may jump (13, additive) -----------------
+ * The segmentation pass charges the full `penalty` for every change of shift, however small, and the drift search follows one
+ * straight line.  Here the shift may, between consecutive events, either MOVE by at most reach_e samples at step_cost a sample,
+ * or JUMP anywhere at `penalty` (a Viterbi pass with bounded moves: O(events x shifts x reach)).  A sequence is E >= 1 rows R_e in
+ * event order, as for sushi_hip_path_forward: n_shift >= 1 consecutive float32 values of a sushi_hip_match_curves output (all rows
+ * by one method) at a curve_off of its own, with a float64 weight w_e, finite and >= 0 (a SushiHipJointRow).  In addition an
+ * int32 reach_e per row, in 0 .. SUSHI_HIP_TRACK_MAX_REACH (row 0's is ignored), and penalty and step_cost, finite float64 >= 0.
+ * Everything is float64; products and sums round separately (no fused multiply-add):
+ *     u_e[j] = w_e * c_e[j] as in "segmentation";  D_0[j] = u_0[j]
+ *     m_e = min_j D_e[j], a_e = the FIRST index of it (0.0 and -0.0 tie)
+ *     for e >= 1:  jump_e = m_{e-1} + penalty
+ *         the candidates of j are every d with |d| <= reach_e and 0 <= j + d < n_shift:
+ *             cand(0) = D_{e-1}[j] itself (nothing is added: -0.0 keeps its bits, and reach 0 is the segmentation pass)
+ *             cand(d) = D_{e-1}[j + d] + step_cost * (double)|d|  for d != 0 (the product rounds once, then the sum rounds once)
+ *         near_e[j] = the smallest candidate; of equal candidates the one with the smaller |d| wins, and of those the negative d
+ *                     (a total order on (value, |d|, d > 0): the result does not depend on the order the candidates meet in)
+ *         take_near = (near_e[j] <= jump_e)  (a tie moves);  D_e[j] = u_e[j] + (take_near ? near_e[j] : jump_e)
+ *         move_e[j] = the winning d (int16), or SUSHI_HIP_TRACK_JUMP;  row 0's moves are 0
+ *     backtrack:   s_{E-1} = a_{E-1};  for e = E-1 .. 1:  s_{e-1} = move_e[s_e] == SUSHI_HIP_TRACK_JUMP ? a_{e-1} : s_e + move_e[s_e]
+ * The total cost is m_{E-1}.  Because floating-point addition is monotone, it equals the minimum over ALL n_shift^E paths of the
+ * path's cost accumulated in this order: c = u_0[s_0]; per event c = c + step_cost * |d| (a move within reach, d != 0), or c
+ * unchanged (d = 0), or c + penalty (a jump, allowed for any pair), whichever allowed choice is cheaper; then c = u_e[s_e] + c.
+ * With every reach_e = 0 the pass is sushi_hip_path_forward bit for bit.  Per row the pass also returns the row's own first
+ * extremum, as the segmentation pass does.  Rows are assumed finite; with a NaN the results are unspecified, but no access leaves
+ * the buffers (indices are clamped into [0, n_shift)). */
+#define SUSHI_HIP_TRACK_MAX_REACH 1024
+#define SUSHI_HIP_TRACK_JUMP (-32768)
+/* workspace of a forward call (two sets of per-workgroup partial minima, used by turns; a row's curve_off, weight and reach travel
+ * with its launch, nothing is uploaded); 0 for n_rows < 1 or n_shift < 1 */
+SUSHI_HIP_API size_t sushi_hip_track_bytes(int n_rows, int32_t n_shift);
+/* Advances rows row0 .. row0 + n_rows - 1 of a sequence of n_total rows: rows_host[i] and reach_host[i] are row row0 + i's.  The
+ * output arrays are the whole sequence's -- D_dev: [2][n_shift] float64 in two halves (row e reads half (e - 1) & 1 and writes
+ * half e & 1: a row reads its neighbours' costs, so it cannot be updated in place); move_dev: [n_total][n_shift] int16;
+ * row_min_dev (m_e) float64, row_arg_dev (a_e) int32, row_own_index_dev int32, row_own_score_dev float32: [n_total] -- and the
+ * call writes rows row0 .. row0 + n_rows - 1 of them.  row0 > 0 continues from D_dev and row_min_dev[row0 - 1] as the call before
+ * it on the same stream left them: a sequence in chunks has the bits of one call, whether row0 is odd or even.  No device
+ * allocation, no upload: one launch per row, stream-ordered, and one that closes the last row.  Asynchronous; stateless (any
+ * thread, own workspace and arrays).  Checked before any HIP call -- EINVAL: a null pointer, an unknown method, n_rows < 1,
+ * n_shift < 1, n_curve < 1, n_shift > n_curve, n_total < 1, row0 < 0, row0 + n_rows > n_total, curve_off < 0 or curve_off +
+ * n_shift > n_curve (decided without forming the sum), a weight, a penalty or a step_cost that is not finite or is negative, a
+ * reach outside 0 .. SUSHI_HIP_TRACK_MAX_REACH in any row but the sequence's row 0; EALIGN: mem_dev not 256-byte aligned;
+ * ENOSPACE: mem_bytes < sushi_hip_track_bytes; EALIGN: D_dev / row_min_dev not 8-byte aligned, a float / int32 pointer not 4-byte
+ * aligned, move_dev not 2-byte aligned. */
+SUSHI_HIP_API int sushi_hip_track_forward(const float* curves_dev, int64_t n_curve,
+                                          const SushiHipJointRow* rows_host, const int32_t* reach_host, int n_rows, int32_t n_shift,
+                                          int method, double penalty, double step_cost, int row0, int n_total,
+                                          double* D_dev, int16_t* move_dev,
+                                          double* row_min_dev, int32_t* row_arg_dev,
+                                          int32_t* row_own_index_dev, float* row_own_score_dev,
+                                          void* mem_dev, size_t mem_bytes, void* hip_stream);
+/* out_shift_dev[e] = s_e for the n_total rows of a sequence whose forward calls lie before it on the stream.  One wave, one lane
+ * walking n_total dependent reads.  EINVAL: a null pointer, n_total < 1, n_shift < 1; EALIGN: move_dev not 2-byte aligned, an
+ * int32 pointer not 4-byte aligned. */
+SUSHI_HIP_API int sushi_hip_track_backtrack(const int16_t* move_dev, const int32_t* row_arg_dev, int n_total,
+                                            int32_t n_shift, int32_t* out_shift_dev, void* hip_stream);
 
 /* ---- WavStream.__init__ on the GPU (wav.py:64-91 decode + downmix, wav.py:113-156 value pipeline) ----
  * sushi_hip_load_decode   : interleaved little-endian PCM frames (sample_width 2 or 3 bytes, `channels` per frame)

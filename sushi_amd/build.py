@@ -47,6 +47,9 @@ UNITS = [
     # where the shift a sequence of score rows shares changes: a Viterbi pass with one price per change, one launch per row
     # (path_core.hpp: the arithmetic, and the call's host side)
     ("sushi_path", ["-ffp-contract=off"]),      # NumPy's float64 operation order: product and sum round separately
+    # a shift that wanders: the same pass with moves of bounded reach between rows, a window minimum over an LDS-staged tile of the
+    # row before (track_core.hpp: the arithmetic, and the call's host side; path_device.hpp: what it shares with sushi_path)
+    ("sushi_track", ["-ffp-contract=off"]),     # the price of a move and the candidate it is added to round separately
     # overlap-save FFT path; its parts, by stage, are csrc/sushi_fft_*.inc (included inside its anonymous namespace); the plan of
     # a batch (plan_core.hpp), what a handle holds about its requests and how it is staged (batch_core.hpp) and what a run decides
     # (run_policy.hpp) are host only

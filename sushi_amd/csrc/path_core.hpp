@@ -71,8 +71,7 @@ inline PathSplit path_split(int32_t n_shift) {
 struct PathLayout {
     size_t set_bytes, d_min, d_arg, own_idx, own_val, bytes;    // offsets inside a set; set s starts at s * set_bytes
 };
-inline PathLayout path_layout(int32_t n_shift) {
-    const size_t g = path_split(n_shift).grid;
+inline PathLayout path_layout_of(size_t g) {        // g: the workgroups of the grid
     PathLayout l;
     l.d_min = 0;
     l.d_arg = l.d_min + 8 * g;
@@ -82,6 +81,7 @@ inline PathLayout path_layout(int32_t n_shift) {
     l.bytes = 2 * l.set_bytes;
     return l;
 }
+inline PathLayout path_layout(int32_t n_shift) { return path_layout_of(path_split(n_shift).grid); }
 inline size_t path_layout_bytes(int n_rows, int64_t n_shift) {
     return n_rows < 1 || n_shift < 1 || n_shift > INT32_MAX ? 0 : path_layout((int32_t)n_shift).bytes;
 }

@@ -611,6 +611,29 @@ class WavStream(object):
                                       max_bytes=segments.MAX_BYTES if max_bytes is None else int(max_bytes),
                                       max_state_bytes=segments.MAX_STATE_BYTES if max_state_bytes is None else int(max_state_bytes))
 
+    # ------------------------------------------------------------------ a shift that wanders, and may jump
+    def find_track(self, patterns, window_centers, window_size, penalty, max_rate=None, reach=None, step_cost=0.0, slack=1,
+                   weights='equal', method="sqdiff_normed", max_bytes=None, max_state_bytes=None):
+        """A shift for every event of a sequence that may move a little from event to event and jump at a cut
+        (sushi_amd.track): the events (patterns, window_centers: in order) are put on one shift axis as
+        find_segments puts them, and a shift is chosen per event that minimises the sum of the events' weighted scores plus, between
+        consecutive events, either step_cost per sample moved (at most reach_e samples) or `penalty` for a jump to anywhere.  Exact:
+        the minimum over all assignments.  Exactly one of max_rate and reach is given: max_rate, the largest drift as a ratio (1e-4
+        is 100 ppm), gives reach_e = ceil(max_rate * |base_e - base_{e-1}|) + slack samples from the events' places; reach is an
+        int or one int per event (event 0's is ignored).  A reach above 1024 is a SushiError that names the event and the value.
+        penalty (required; finite, >= 0) is in units of one event's weighted score, as in find_segments; step_cost (default 0: any
+        move within reach is free) is in the same units per sample.  With every reach 0 the result is find_segments'.  weights,
+        method, the location of patterns and max_bytes are find_segments'.  The moves and costs of the whole sequence, E x n_shift
+        x 2 + 2 x n_shift x 8 bytes, must fit max_state_bytes (default 2 GiB; SushiError names the need).  Returns a Track: k_lo,
+        n_shift, shifts (samples per event), deltas (seconds), reach, moves (shifts[e] - shifts[e - 1]), jumps (the events entered
+        by a jump), segments ([(first_event, n_events, first_delta, last_delta)]: maximal runs without a jump), cost, event_scores,
+        event_own_delta / event_own_scores (what a lone search of each event over the same range finds).  Needs a GPU."""
+        from . import track
+        return track.find_track(self, patterns, window_centers, window_size, penalty, max_rate=max_rate, reach=reach,
+                                step_cost=step_cost, slack=slack, weights=weights, method=method,
+                                max_bytes=track.MAX_BYTES if max_bytes is None else int(max_bytes),
+                                max_state_bytes=track.MAX_STATE_BYTES if max_state_bytes is None else int(max_state_bytes))
+
     # ------------------------------------------------------------------ a shift that moves along the programme
     def find_drift(self, patterns, window_centers, window_size, max_rate, resolution=1.0, weights='equal', method="sqdiff_normed",
                    with_lines=False, max_bytes=None):
