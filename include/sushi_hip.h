@@ -52,7 +52,8 @@ extern "C" {
                                      sushi_hip_path_backtrack;
                                      13 (additive): sushi_hip_drift_bytes, sushi_hip_drift_reduce;
                                      13 (additive): SUSHI_HIP_TRACK_MAX_REACH, SUSHI_HIP_TRACK_JUMP, sushi_hip_track_bytes,
-                                     sushi_hip_track_forward, sushi_hip_track_backtrack */
+                                     sushi_hip_track_forward, sushi_hip_track_backtrack;
+                                     13 (additive): sushi_hip_track_forward_keep, sushi_hip_track_margins_bytes, sushi_hip_track_margins */
 
 #if defined(__GNUC__)
 #define SUSHI_HIP_API __attribute__((visibility("default")))
@@ -627,6 +628,71 @@ SUSHI_HIP_API int sushi_hip_track_forward(const float* curves_dev, int64_t n_cur
  * int32 pointer not 4-byte aligned. */
 SUSHI_HIP_API int sushi_hip_track_backtrack(const int16_t* move_dev, const int32_t* row_arg_dev, int n_total,
                                             int32_t n_shift, int32_t* out_shift_dev, void* hip_stream);
+
+/* ---- margins: how firmly the tracking pass places each event -- its min-marginals (13, additive) --------------
+ * For event e and shift j the MIN-MARGINAL M_e[j] is the cost of the best whole path that puts event e at shift j.  The best
+ * value of M_e more than guard_e samples away from the chosen shift s_e is the cost of the best alternative explanation that moves
+ * this event; its excess over M_e[s_e] is the event's margin, its index where the event would go instead.  The forward half, D_e, is
+ * what the tracking pass computes (sushi_hip_track_forward_keep keeps every row of it); the backward half is the same recurrence
+ * run from the last event down.  Inputs: those of "tracking" (u_e, reach_e, penalty, step_cost), D_e, the backtrack's s_e, and an
+ * int32 guard_e >= 0 per row.  Everything is float64; products and sums round separately:
+ *     C_{E-1}[j] = u_{E-1}[j];   M_{E-1}[j] = D_{E-1}[j]            (nothing is added: the bits of D)
+ *     for e = E-2 .. 0, with r = reach_{e+1}:
+ *         n_{e+1}  = min_j C_{e+1}[j];   jumpB = n_{e+1} + penalty
+ *         nearB[j] = the smallest of cand(0) = C_{e+1}[j] itself and cand(d) = C_{e+1}[j + d] + step_cost * (double)|d|,
+ *                    0 < |d| <= r, 0 <= j + d < n_shift  (the candidates and the tie rule of "tracking"; only the value is kept)
+ *         B_e[j]   = nearB[j] <= jumpB ? nearB[j] : jumpB
+ *         M_e[j]   = D_e[j] + B_e[j]   (one rounding);   C_e[j] = u_e[j] + B_e[j]   (one rounding)
+ *     per row e:
+ *         through_e          = M_e[s_e]
+ *         best_e, best_arg_e = the minimum of M_e and its FIRST index (0.0 and -0.0 tie)
+ *         alt_e,  alt_arg_e  = the minimum of M_e over { j : |j - s_e| > guard_e } and its first index; (+inf, -1) where that set is
+ *                              empty
+ *         c_min_e            = n_e  (kept per row so that a later call can continue)
+ * Three facts.  EXACT PATH MINIMUM: floating-point addition is monotone, so M_e[j] is bitwise the minimum, over all paths with
+ * s_e = j, of (the prefix cost, accumulated forwards as "tracking" states it) + (the suffix cost, accumulated backwards in the
+ * mirrored order -- c = u_{E-1}[s_{E-1}]; per event from E-2 down to e + 1 the cheaper allowed choice of a move's price, nothing,
+ * or the penalty is added, then c = u_i[s_i] + c -- ending, at event e, before u_e is added).  REVERSAL: n_0 is bitwise the
+ * tracking pass's total cost of the reversed sequence, with reach_rev[i] = reach[E - i] for i >= 1.  CONSISTENCY WITH THE TOTAL:
+ * best_e <= through_e exactly; through_e equals the total m_{E-1} only up to summation order: |through_e - m_{E-1}| <=
+ * 6 E 2^-53 S, S the sum of the absolute values of the optimal path's terms (w_e |R_e[s_e]|, its prices and its penalties) --
+ * Higham's bound for two recursive sums of at most 3 E terms each.
+ * With every reach 0 this is the same statement about the segmentation model. */
+/* sushi_hip_track_forward with D kept: D_all_dev is [n_total][n_shift] float64, row e reads row e - 1 and writes row e.  Everything
+ * else -- the kernels, the other outputs, their bits, the refusals, the workspace (sushi_hip_track_bytes) and the continuation of
+ * a sequence in chunks -- is sushi_hip_track_forward's. */
+SUSHI_HIP_API int sushi_hip_track_forward_keep(const float* curves_dev, int64_t n_curve,
+                                               const SushiHipJointRow* rows_host, const int32_t* reach_host, int n_rows, int32_t n_shift,
+                                               int method, double penalty, double step_cost, int row0, int n_total,
+                                               double* D_all_dev, int16_t* move_dev,
+                                               double* row_min_dev, int32_t* row_arg_dev,
+                                               int32_t* row_own_index_dev, float* row_own_score_dev,
+                                               void* mem_dev, size_t mem_bytes, void* hip_stream);
+/* workspace of a margins call (two sets of per-workgroup partial minima, used by turns); 0 for n_rows < 1 or n_shift < 1 */
+SUSHI_HIP_API size_t sushi_hip_track_margins_bytes(int n_rows, int32_t n_shift);
+/* Walks rows row0 + n_rows - 1 down to row0 of a sequence of n_total rows whose forward_keep calls and backtrack lie before it on
+ * the stream.  rows_host[i] and guard_host[i] are row row0 + i's; reach_host[i] is row row0 + i's for i = 0 .. n_rows, the last
+ * only where row0 + n_rows < n_total (reach_host[0] is not used and is ignored: the step into row row0 is priced by the call that
+ * walks row row0 - 1).  D_all_dev: [n_total][n_shift] as sushi_hip_track_forward_keep left it; shift_dev: [n_total], the
+ * backtrack's output; C_dev: [2][n_shift] float64 in two halves (row e reads half (e + 1) & 1 and writes half e & 1).  The outputs
+ * are the whole sequence's -- c_min_dev, through_dev, best_dev, alt_dev float64 and best_arg_dev, alt_arg_dev int32: [n_total];
+ * M_dev: [n_total][n_shift] float64 or NULL -- and the call writes rows row0 .. row0 + n_rows - 1 of them.  The first call of a
+ * sequence has row0 + n_rows == n_total; a later one continues from C_dev and c_min_dev[row0 + n_rows] as the call before it on the
+ * same stream left them: a sequence in chunks has the bits of one call, whatever the parity of the boundary.  No device
+ * allocation, no upload: one launch per row, stream-ordered, and one that closes row row0.  Asynchronous; stateless.  Checked
+ * before any HIP call -- EINVAL: a null pointer (M_dev may be null), an unknown method, n_rows < 1, n_shift < 1, n_curve < 1,
+ * n_shift > n_curve, n_total < 1, row0 < 0, row0 + n_rows > n_total (no sum is formed), a row outside the curve buffer, a weight, a
+ * penalty or a step_cost that is not finite or is negative, a used reach outside 0 .. SUSHI_HIP_TRACK_MAX_REACH, a guard < 0;
+ * EALIGN: mem_dev not 256-byte aligned; ENOSPACE: mem_bytes < sushi_hip_track_margins_bytes; EALIGN: a float64 pointer not 8-byte
+ * aligned, a float / int32 pointer not 4-byte aligned. */
+SUSHI_HIP_API int sushi_hip_track_margins(const float* curves_dev, int64_t n_curve,
+                                          const SushiHipJointRow* rows_host, const int32_t* reach_host, const int32_t* guard_host,
+                                          int n_rows, int32_t n_shift, int method, double penalty, double step_cost,
+                                          int row0, int n_total,
+                                          const double* D_all_dev, const int32_t* shift_dev, double* C_dev, double* c_min_dev,
+                                          double* through_dev, double* best_dev, int32_t* best_arg_dev,
+                                          double* alt_dev, int32_t* alt_arg_dev, double* M_dev,
+                                          void* mem_dev, size_t mem_bytes, void* hip_stream);
 
 /* ---- WavStream.__init__ on the GPU (wav.py:64-91 decode + downmix, wav.py:113-156 value pipeline) ----
  * sushi_hip_load_decode   : interleaved little-endian PCM frames (sample_width 2 or 3 bytes, `channels` per frame)

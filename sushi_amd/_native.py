@@ -192,6 +192,13 @@ def lib():
     L.sushi_hip_track_forward.argtypes = [vp, i64, vp, vp, ci, i32, ci, dbl, dbl, ci, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     L.sushi_hip_track_backtrack.restype = ci
     L.sushi_hip_track_backtrack.argtypes = [vp, vp, ci, i32, vp, vp]
+    L.sushi_hip_track_forward_keep.restype = ci
+    L.sushi_hip_track_forward_keep.argtypes = L.sushi_hip_track_forward.argtypes
+    L.sushi_hip_track_margins_bytes.restype = sz
+    L.sushi_hip_track_margins_bytes.argtypes = [ci, i32]
+    L.sushi_hip_track_margins.restype = ci
+    L.sushi_hip_track_margins.argtypes = [vp, i64, vp, vp, vp, ci, i32, ci, dbl, dbl, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                          sz, vp]
     L.sushi_hip_load_decode.restype = ci
     L.sushi_hip_load_decode.argtypes = [vp, i64, i32, i32, vp, vp]
     L.sushi_hip_load_decode_mix.restype = ci

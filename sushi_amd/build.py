@@ -50,6 +50,9 @@ UNITS = [
     # a shift that wanders: the same pass with moves of bounded reach between rows, a window minimum over an LDS-staged tile of the
     # row before (track_core.hpp: the arithmetic, and the call's host side; path_device.hpp: what it shares with sushi_path)
     ("sushi_track", ["-ffp-contract=off"]),     # the price of a move and the candidate it is added to round separately
+    # how firmly the tracking pass places each event: the same recurrence from the last row down over the kept forward rows, and
+    # three first minima per row (track_margin_core.hpp: the arithmetic, and the call's host side)
+    ("sushi_track_margins", ["-ffp-contract=off"]),     # track_core.hpp's candidates unchanged; M and C round once each
     # overlap-save FFT path; its parts, by stage, are csrc/sushi_fft_*.inc (included inside its anonymous namespace); the plan of
     # a batch (plan_core.hpp), what a handle holds about its requests and how it is staged (batch_core.hpp) and what a run decides
     # (run_policy.hpp) are host only

@@ -1,5 +1,5 @@
 // sushi_amd/csrc/sushi_track.hip -- sushi_hip_track_forward / sushi_hip_track_backtrack: a shift that wanders from event to event
-// (gfx950).
+// (gfx950); and sushi_hip_track_forward_keep, the same launches with every row of D kept (for sushi_track_margins.hip).
 //
 // The rows of a sequence (sushi_hip_match_curves output, each from a curve_off of its own) lie on one shift axis in event order.
 // Between consecutive rows the shift may move by at most reach_e samples at step_cost a sample, or jump anywhere at `penalty`:
@@ -186,11 +186,12 @@ extern "C" {
 
 size_t sushi_hip_track_bytes(int n_rows, int32_t n_shift) { return track_layout_bytes(n_rows, n_shift); }
 
-int sushi_hip_track_forward(const float* curves_dev, int64_t n_curve, const SushiHipJointRow* rows_host, const int32_t* reach_host,
-                            int n_rows, int32_t n_shift, int method, double penalty, double step_cost, int row0, int n_total,
-                            double* D_dev, int16_t* move_dev, double* row_min_dev, int32_t* row_arg_dev, int32_t* row_own_index_dev,
-                            float* row_own_score_dev, void* mem_dev, size_t mem_bytes, void* hip_stream) {
-    return c_boundary([&]() -> int {
+// sushi_hip_track_forward and sushi_hip_track_forward_keep: one body.  keep: D_dev holds every row ([n_total][n_shift]: row e reads
+// row e - 1 and writes row e) instead of two halves used by turns; the launches, and so the bits, are the same.
+static int track_forward(bool keep, const float* curves_dev, int64_t n_curve, const SushiHipJointRow* rows_host,
+                         const int32_t* reach_host, int n_rows, int32_t n_shift, int method, double penalty, double step_cost, int row0,
+                         int n_total, double* D_dev, int16_t* move_dev, double* row_min_dev, int32_t* row_arg_dev,
+                         int32_t* row_own_index_dev, float* row_own_score_dev, void* mem_dev, size_t mem_bytes, void* hip_stream) {
     if (!curves_dev || !rows_host || !reach_host || !D_dev || !move_dev || !row_min_dev || !row_arg_dev || !row_own_index_dev ||
         !row_own_score_dev || !mem_dev) return SUSHI_HIP_EINVAL;
     TrackStage staged;
@@ -217,8 +218,9 @@ int sushi_hip_track_forward(const float* curves_dev, int64_t n_curve, const Sush
         a.row = curves_dev + rows_host[i].curve_off;
         a.weight = rows_host[i].weight;
         a.reach = a.e == 0 ? 0 : reach_host[i];
-        a.D_in = D_dev + (int64_t)((a.e + 1) & 1) * n_shift;
-        a.D_out = D_dev + (int64_t)(a.e & 1) * n_shift;
+        // (row 0 has no row before it: its launch's loads of D_in, which are always made and never used, go to its own row)
+        a.D_in = D_dev + (keep ? (int64_t)(a.e == 0 ? 0 : a.e - 1) : (int64_t)((a.e + 1) & 1)) * n_shift;
+        a.D_out = D_dev + (keep ? (int64_t)a.e : (int64_t)(a.e & 1)) * n_shift;
         a.move = move_dev + (int64_t)a.e * n_shift;
         a.prev = a.e == 0 ? PREV_NONE : (i == 0 ? PREV_ROW_MIN : PREV_PARTIALS);
         a.in = partial_set((char*)mem_dev, staged.lay, (i + 1) & 1);
@@ -235,6 +237,24 @@ int sushi_hip_track_forward(const float* curves_dev, int64_t n_curve, const Sush
     if (mx) hipLaunchKernelGGL(track_close_kernel<true>, dim3(1), block, 0, st, a);
     else hipLaunchKernelGGL(track_close_kernel<false>, dim3(1), block, 0, st, a);
     return launch_ok();
+}
+
+int sushi_hip_track_forward(const float* curves_dev, int64_t n_curve, const SushiHipJointRow* rows_host, const int32_t* reach_host,
+                            int n_rows, int32_t n_shift, int method, double penalty, double step_cost, int row0, int n_total,
+                            double* D_dev, int16_t* move_dev, double* row_min_dev, int32_t* row_arg_dev, int32_t* row_own_index_dev,
+                            float* row_own_score_dev, void* mem_dev, size_t mem_bytes, void* hip_stream) {
+    return c_boundary([&]() -> int {
+        return track_forward(false, curves_dev, n_curve, rows_host, reach_host, n_rows, n_shift, method, penalty, step_cost, row0, n_total,
+                             D_dev, move_dev, row_min_dev, row_arg_dev, row_own_index_dev, row_own_score_dev, mem_dev, mem_bytes, hip_stream);
+}); }
+
+int sushi_hip_track_forward_keep(const float* curves_dev, int64_t n_curve, const SushiHipJointRow* rows_host, const int32_t* reach_host,
+                                 int n_rows, int32_t n_shift, int method, double penalty, double step_cost, int row0, int n_total,
+                                 double* D_all_dev, int16_t* move_dev, double* row_min_dev, int32_t* row_arg_dev,
+                                 int32_t* row_own_index_dev, float* row_own_score_dev, void* mem_dev, size_t mem_bytes, void* hip_stream) {
+    return c_boundary([&]() -> int {
+        return track_forward(true, curves_dev, n_curve, rows_host, reach_host, n_rows, n_shift, method, penalty, step_cost, row0, n_total,
+                             D_all_dev, move_dev, row_min_dev, row_arg_dev, row_own_index_dev, row_own_score_dev, mem_dev, mem_bytes, hip_stream);
 }); }
 
 int sushi_hip_track_backtrack(const int16_t* move_dev, const int32_t* row_arg_dev, int n_total, int32_t n_shift,

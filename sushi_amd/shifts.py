@@ -416,12 +416,13 @@ def calculate_segmented_shifts(src_stream, dst_stream, events, window, penalty, 
 
 
 def calculate_tracked_shifts(src_stream, dst_stream, events, window, penalty, max_rate=None, reach=None, step_cost=0.0,
-                             centre_shift=0.0):
+                             centre_shift=0.0, margins=False, guard=None, marginals=False):
     """A shift per event that may move a little between events and jump where a jump pays (sushi_amd.track):
     `events` is a list of ScriptEvent in order; every event's pattern is src_stream.get_substream(e.start, e.end) and its centre
     e.start + centre_shift.  All go through one dst_stream.find_track call with window `window` (seconds), `penalty`, and max_rate
     or reach and step_cost (its docstring).  Every event gets set_shift(centre_shift + its delta, its own score there).  SushiError
-    for an event whose pattern is empty.  Returns the Track."""
+    for an event whose pattern is empty.  margins, guard and marginals are find_track's: with margins=True the Track also says how
+    firmly every event is placed (event_margin, event_alt_delta, ...).  Returns the Track."""
     events = list(events)
     shift = float(centre_shift)
     if not events:
@@ -431,7 +432,7 @@ def calculate_tracked_shifts(src_stream, dst_stream, events, window, penalty, ma
         if p.shape[1] < 1:
             raise SushiError("calculate_tracked_shifts: event %s has no samples in the source" % e)
     found = dst_stream.find_track(patterns, [e.start + shift for e in events], window, penalty, max_rate=max_rate, reach=reach,
-                                  step_cost=step_cost)
+                                  step_cost=step_cost, margins=margins, guard=guard, marginals=marginals)
     for e, delta, score in zip(events, found.deltas, found.event_scores):
         e.set_shift(shift + delta, score)
     return found

@@ -11,6 +11,8 @@ minimum over all assignments (include/sushi_hip.h "tracking").  
   ``sushi_hip_track_forward`` on a chunk of its rows, and the backtrack.
 * ``find_track`` -- what ``WavStream.find_track`` runs: per chunk of events one ``match_curves`` call and one forward call, then
   one backtrack.
+* ``track_margins_host`` / ``track_forward_keep_device`` / ``track_margins_device`` -- how firmly each event is placed: the pass's
+  min-marginals (include/sushi_hip.h "margins"), in NumPy and on the device; ``find_track(margins=True)`` runs them.
 """
 import math
 from collections import namedtuple
@@ -26,6 +28,9 @@ MAX_STATE_BYTES = 2 << 30     # moves and D of one sequence (find_track)
 MAX_REACH, JUMP = _native.TRACK_MAX_REACH, _native.TRACK_JUMP
 
 TrackHost = namedtuple("TrackHost", "shifts cost row_min row_arg moves row_own_index row_own_scores")
+TrackMarginsHost = namedtuple("TrackMarginsHost", TrackHost._fields + ("D", "marginals", "through", "best", "best_arg", "alt", "alt_arg",
+                                                                       "c_min"))
+NO_ALT = -1                   # alt_arg where no shift lies outside the guard window
 
 
 def _checked(weights, n, penalty, step_cost, method):
@@ -56,7 +61,43 @@ def checked_reach(reach, n, first_row=0):
     return np.array(r, np.int32)
 
 
-def track_host(rows, weights, penalty, step_cost, reach, method="sqdiff_normed"):
+def checked_guard(guard, n, first_row=0):
+    """`guard` -- one int for every row, or a sequence of n -- as an int32 array of n values >= 0.  SushiError names the row and the
+    value otherwise."""
+    try:
+        g = [int(guard)] * n if np.ndim(guard) == 0 else [int(x) for x in guard]
+    except (TypeError, ValueError):
+        raise SushiError("track: guard is an int, or one int per row")
+    if len(g) != n:
+        raise SushiError("track: as many guards as rows (%d guards, %d rows)" % (len(g), n))
+    for i, x in enumerate(g):
+        if x < 0 or x > 2 ** 31 - 1:
+            raise SushiError("track: the guard of event %d is %d, outside 0 .. 2^31 - 1" % (first_row + i, x))
+    return np.array(g, np.int32)
+
+
+def _near(D, reach, mu, moves=False):
+    """near[j]: the smallest of D[j] itself and D[j + d] + mu * |d| over 0 < |d| <= reach inside the axis, visited in the order 0, -1,
+    +1, -2, +2, ... with strict replacement; with `moves` also the winning d (int16)."""
+    n = D.shape[0]
+    near = D.copy()                              # cand(0): the value itself, nothing added
+    nd = np.zeros(n, np.int16) if moves else None
+    for a in range(1, min(int(reach), n - 1) + 1):
+        price = mu * float(a)                    # rounds once; the sums below round once
+        lo = D[:n - a] + price                   # cand(-a) of j = a .. n - 1
+        take = lo < near[a:]
+        near[a:][take] = lo[take]
+        if moves:
+            nd[a:][take] = -a
+        hi = D[a:] + price                       # cand(+a) of j = 0 .. n - 1 - a
+        take = hi < near[:n - a]
+        near[:n - a][take] = hi[take]
+        if moves:
+            nd[:n - a][take] = a
+    return near, nd
+
+
+def track_host(rows, weights, penalty, step_cost, reach, method="sqdiff_normed", _keep=None):
     """sushi_hip_track_forward + sushi_hip_track_backtrack for one sequence in NumPy (include/sushi_hip.h states the arithmetic):
     rows, a list of E >= 1 float32 arrays of one length n_shift >= 1 in event order; weights, E finite float64 values >= 0; penalty
     and step_cost, finite numbers >= 0; reach, an int or E ints in 0 .. 1024 (row 0's is ignored).  u_e = w_e * float64(R_e) (negated
@@ -84,23 +125,14 @@ def track_host(rows, weights, penalty, step_cost, reach, method="sqdiff_normed")
             D = u
         else:
             jump = row_min[e - 1] + lam
-            near = D.copy()                          # cand(0): the value itself, nothing added
-            nd = np.zeros(n, np.int16)
-            for a in range(1, min(int(reach[e]), n - 1) + 1):
-                price = mu * float(a)                # rounds once; the sums below round once
-                lo = D[:n - a] + price               # cand(-a) of j = a .. n - 1
-                take = lo < near[a:]
-                near[a:][take] = lo[take]
-                nd[a:][take] = -a
-                hi = D[a:] + price                   # cand(+a) of j = 0 .. n - 1 - a
-                take = hi < near[:n - a]
-                near[:n - a][take] = hi[take]
-                nd[:n - a][take] = a
+            near, nd = _near(D, reach[e], mu, moves=True)
             take_near = near <= jump
             D = u + np.where(take_near, near, jump)
             moves[e] = np.where(take_near, nd, np.int16(JUMP))
         row_arg[e] = int(np.argmin(D))              # the first index of the minimum; 0.0 and -0.0 compare equal
         row_min[e] = D[row_arg[e]]
+        if _keep is not None:
+            _keep.append(D)
     shifts = backtrack_host(moves, row_arg)
     own = np.array([axis.first_extremum(r, method) for r in rows], np.int32)
     return TrackHost(shifts, float(row_min[E - 1]), row_min, row_arg, moves, own,
@@ -121,37 +153,98 @@ def backtrack_host(moves, row_arg):
     return shifts
 
 
+def track_margins_host(rows, weights, penalty, step_cost, reach, guard, method="sqdiff_normed"):
+    """sushi_hip_track_forward_keep + sushi_hip_track_backtrack + sushi_hip_track_margins for one sequence in NumPy (include/sushi_hip.h
+    "margins" states the arithmetic); the arguments of track_host, and guard, an int or E ints >= 0.  C_{E-1} = u_{E-1}, M_{E-1} =
+    D_{E-1}; for e = E-2 .. 0: n_{e+1} = the minimum of C_{e+1}, nearB = track_host's window minimum over C_{e+1} with reach_{e+1},
+    B_e = where(nearB <= n_{e+1} + penalty, nearB, n_{e+1} + penalty), M_e = D_e + B_e, C_e = u_e + B_e.  Returns a TrackMarginsHost:
+    track_host's fields, then D ([E, n] float64: every row of the forward pass), marginals ([E, n] float64: M), through (M_e[s_e]),
+    best / best_arg (the minimum of M_e and its first index), alt / alt_arg (the same over the shifts more than guard_e from s_e;
+    inf and -1 where there are none), c_min (n_e) -- float64 and int32 arrays of E."""
+    rows = list(rows)
+    kept = []
+    fwd = track_host(rows, weights, penalty, step_cost, reach, method, _keep=kept)
+    w, lam, mu = _checked(weights, len(rows), penalty, step_cost, method)
+    rows = axis.checked_score_rows(rows, "track")
+    E, n = len(rows), rows[0].shape[0]
+    reach = checked_reach(reach, E)
+    guard = checked_guard(guard, E)
+    D = np.stack(kept)
+    M = np.empty((E, n), np.float64)
+    c_min = np.empty(E, np.float64)
+    C = None
+    for e in range(E - 1, -1, -1):
+        c = rows[e].astype(np.float64)
+        if method == "ccoeff_normed":
+            c = -c
+        u = w[e] * c
+        if e == E - 1:
+            C, M[e] = u, D[e]
+        else:
+            jump = c_min[e + 1] + lam
+            near, _nd = _near(C, reach[e + 1], mu)
+            B = np.where(near <= jump, near, jump)
+            M[e] = D[e] + B
+            C = u + B
+        c_min[e] = C[int(np.argmin(C))]
+    through = np.array([M[e, fwd.shifts[e]] for e in range(E)], np.float64)
+    best_arg = np.array([int(np.argmin(M[e])) for e in range(E)], np.int32)
+    best = np.array([M[e, best_arg[e]] for e in range(E)], np.float64)
+    alt, alt_arg = np.full(E, np.inf, np.float64), np.full(E, NO_ALT, np.int32)
+    j = np.arange(n, dtype=np.int64)
+    for e in range(E):
+        outside = np.abs(j - int(fwd.shifts[e])) > int(guard[e])
+        if outside.any():
+            at = int(np.argmin(np.where(outside, M[e], np.inf)))       # the first index of the minimum outside the window
+            alt[e], alt_arg[e] = M[e, at], at
+    return TrackMarginsHost(*(tuple(fwd) + (D, M, through, best, best_arg, alt, alt_arg, c_min)))
+
+
 class TrackState(object):
     """The device arrays of one sequence of n_total rows over n_shift shifts: D (float64[2 * n_shift]: two halves, used by turns),
     moves (int16[n_total * n_shift]), row_min (float64[n_total]), row_arg / row_own_index (int32[n_total]), row_own_scores
-    (float32[n_total]).  track_device fills them chunk by chunk; track_backtrack_device reads them."""
+    (float32[n_total]).  track_device fills them chunk by chunk; track_backtrack_device reads them.
+    keep=True: D is float64[n_total * n_shift], every row of the pass (track_forward_keep_device fills it), and the state also holds
+    what track_margins_device needs and fills: C (float64[2 * n_shift]: two halves), c_min, through, best, alt (float64[n_total]),
+    best_arg, alt_arg (int32[n_total])."""
 
-    def __init__(self, n_total, n_shift, device):
+    def __init__(self, n_total, n_shift, device, keep=False):
         import torch
         n_total, n_shift = int(n_total), int(n_shift)
         if n_total < 1 or n_shift < 1 or n_shift > 2 ** 31 - 1:
             raise SushiError("track: a sequence has >= 1 rows and 1 .. 2^31 - 1 shifts")
-        self.n_total, self.n_shift, self.device = n_total, n_shift, device
+        self.n_total, self.n_shift, self.device, self.keep = n_total, n_shift, device, bool(keep)
         with torch.cuda.device(device):
-            self.D = torch.empty(2 * n_shift, dtype=torch.float64, device=device)
+            self.D = torch.empty((n_total if keep else 2) * n_shift, dtype=torch.float64, device=device)
             self.moves = torch.empty(n_total * n_shift, dtype=torch.int16, device=device)
             self.row_min = torch.empty(n_total, dtype=torch.float64, device=device)
             self.row_arg = torch.empty(n_total, dtype=torch.int32, device=device)
             self.row_own_index = torch.empty(n_total, dtype=torch.int32, device=device)
             self.row_own_scores = torch.empty(n_total, dtype=torch.float32, device=device)
+            if keep:
+                self.C = torch.empty(2 * n_shift, dtype=torch.float64, device=device)
+                self.c_min, self.through, self.best, self.alt = (torch.empty(n_total, dtype=torch.float64, device=device)
+                                                                 for _ in range(4))
+                self.best_arg, self.alt_arg = (torch.empty(n_total, dtype=torch.int32, device=device) for _ in range(2))
 
     def tensors(self):
         return (self.D, self.moves, self.row_min, self.row_arg, self.row_own_index, self.row_own_scores)
 
+    def margin_tensors(self):
+        return (self.C, self.c_min, self.through, self.best, self.best_arg, self.alt, self.alt_arg)
+
     def last_D(self):
-        """D of the sequence's last row: the half it was written to."""
-        half = (self.n_total - 1) & 1
+        """D of the sequence's last row: the half (keep: the row) it was written to."""
+        half = (self.n_total - 1) if self.keep else (self.n_total - 1) & 1
         return self.D[half * self.n_shift:(half + 1) * self.n_shift]
 
     @staticmethod
-    def nbytes(n_total, n_shift):
-        """Bytes of moves and D: what grows with the sequence."""
-        return int(n_total) * int(n_shift) * 2 + 2 * int(n_shift) * 8
+    def nbytes(n_total, n_shift, keep=False, marginals=False):
+        """Bytes of moves and D: what grows with the sequence.  keep: every row of D and the two halves of C; marginals: M too."""
+        n_total, n_shift = int(n_total), int(n_shift)
+        if not keep:
+            return n_total * n_shift * 2 + 2 * n_shift * 8
+        return n_total * n_shift * 2 + n_total * n_shift * 8 + 2 * n_shift * 8 + (n_total * n_shift * 8 if marginals else 0)
 
 
 def track_device(curves, rows, reach, penalty, step_cost, state, row0=0, method="sqdiff_normed", hip_stream=None):
@@ -159,6 +252,20 @@ def track_device(curves, rows, reach, penalty, step_cost, state, row0=0, method=
     in `curves`, a contiguous 1-D float32 CUDA tensor (match_curves' output) on state's device, reach an int or one int per row
     of the call.  row0 > 0 continues what the calls before it on the same stream left in `state`: a sequence goes through chunk by
     chunk, with the bits of one call.  Asynchronous on hip_stream (default: the current torch stream of the device)."""
+    if getattr(state, "keep", False):
+        raise SushiError("track: a state that keeps its rows goes through track_forward_keep_device")
+    return _forward_device("sushi_hip_track_forward", curves, rows, reach, penalty, step_cost, state, row0, method, hip_stream)
+
+
+def track_forward_keep_device(curves, rows, reach, penalty, step_cost, state, row0=0, method="sqdiff_normed", hip_stream=None):
+    """track_device through sushi_hip_track_forward_keep: `state` is a TrackState(keep=True), and row e of its D is D_e afterwards.
+    Everything else -- arguments, the other outputs and their bits, chunks -- is track_device's."""
+    if not getattr(state, "keep", False):
+        raise SushiError("track: track_forward_keep_device needs a TrackState(keep=True)")
+    return _forward_device("sushi_hip_track_forward_keep", curves, rows, reach, penalty, step_cost, state, row0, method, hip_stream)
+
+
+def _forward_device(name, curves, rows, reach, penalty, step_cost, state, row0, method, hip_stream):
     from .device import _launch
     axis.check_curves(curves, "track", device=state.D.device)
     rt = axis.row_table(rows)
@@ -169,13 +276,63 @@ def track_device(curves, rows, reach, penalty, step_cost, state, row0=0, method=
     rc = np.ascontiguousarray(checked_reach(reach, rt.shape[0], first_row=row0))
     axis.check_rows_inside(rt, int(curves.numel()), state.n_shift, "track")
     L = _native.lib()
-    _launch("sushi_hip_track_forward", state.D.device, L.sushi_hip_track_bytes(rt.shape[0], state.n_shift),
-            lambda mem, mem_bytes, st: L.sushi_hip_track_forward(
+    fn = getattr(L, name)
+    _launch(name, state.D.device, L.sushi_hip_track_bytes(rt.shape[0], state.n_shift),
+            lambda mem, mem_bytes, st: fn(
                 curves.data_ptr(), int(curves.numel()), rt.ctypes.data, rc.ctypes.data, rt.shape[0], state.n_shift,
                 _native.METHODS[method], lam, mu, row0, state.n_total, state.D.data_ptr(), state.moves.data_ptr(),
                 state.row_min.data_ptr(), state.row_arg.data_ptr(), state.row_own_index.data_ptr(), state.row_own_scores.data_ptr(),
                 mem, mem_bytes, st),
             (curves,) + state.tensors(), hip_stream)
+    return state
+
+
+def track_margins_device(curves, rows, reach, guard, penalty, step_cost, state, shifts, row0=0, method="sqdiff_normed", marginals=None,
+                         hip_stream=None):
+    """One call of sushi_hip_track_margins: rows row0 + len(rows) - 1 down to row0 of `state`'s sequence (a TrackState(keep=True) whose
+    every row has gone through track_forward_keep_device), `shifts` the int32 CUDA tensor track_backtrack_device returned.  rows[i] =
+    (curve_off, weight) and guard[i] are row row0 + i's (guard: an int, or one per row of the call); reach: an int, or one int per
+    row of the call and then the reach of row row0 + len(rows) where that row exists (the step out of the call's last row).  The
+    first call of a sequence ends at its last row; a later one continues downwards from what the call before it on the same stream
+    left in `state`, with the bits of one call.  marginals: a float64 CUDA tensor of n_total * n_shift values that receives M, or
+    None.  Fills rows row0 .. of state.c_min, through, best, best_arg, alt, alt_arg.  Asynchronous on hip_stream."""
+    from .device import _launch
+    import torch
+    if not getattr(state, "keep", False):
+        raise SushiError("track: track_margins_device needs a TrackState(keep=True)")
+    axis.check_curves(curves, "track", device=state.D.device)
+    rt = axis.row_table(rows)
+    n_rows = rt.shape[0]
+    _w, lam, mu = _checked(rt["weight"], n_rows, penalty, step_cost, method)
+    row0 = int(row0)
+    if row0 < 0 or row0 + n_rows > state.n_total:
+        raise SushiError("track: rows %d .. %d are not inside a sequence of %d" % (row0, row0 + n_rows - 1, state.n_total))
+    n_reach = n_rows + (1 if row0 + n_rows < state.n_total else 0)
+    if np.ndim(reach) == 0:
+        reach = [reach] * n_reach
+    reach = list(reach)
+    if len(reach) != n_reach:
+        raise SushiError("track: %d reaches for a margins call of %d rows that %s the sequence's last row (%d are needed)"
+                         % (len(reach), n_rows, "ends below" if n_reach > n_rows else "ends at", n_reach))
+    rc = np.ascontiguousarray(checked_reach([0] + reach[1:], n_reach, first_row=row0))          # entry 0 is not used
+    gd = np.ascontiguousarray(checked_guard(guard, n_rows, first_row=row0))
+    axis.check_rows_inside(rt, int(curves.numel()), state.n_shift, "track")
+    if not (isinstance(shifts, torch.Tensor) and shifts.is_cuda and shifts.dtype == torch.int32 and shifts.is_contiguous()
+            and shifts.numel() == state.n_total and shifts.device == state.D.device):
+        raise SushiError("track: shifts is the backtrack's output, an int32 CUDA tensor of %d values" % state.n_total)
+    if marginals is not None and not (isinstance(marginals, torch.Tensor) and marginals.is_cuda and marginals.dtype == torch.float64
+                                      and marginals.is_contiguous() and marginals.numel() == state.n_total * state.n_shift
+                                      and marginals.device == state.D.device):
+        raise SushiError("track: marginals is a contiguous float64 CUDA tensor of %d x %d values" % (state.n_total, state.n_shift))
+    L = _native.lib()
+    _launch("sushi_hip_track_margins", state.D.device, L.sushi_hip_track_margins_bytes(n_rows, state.n_shift),
+            lambda mem, mem_bytes, st: L.sushi_hip_track_margins(
+                curves.data_ptr(), int(curves.numel()), rt.ctypes.data, rc.ctypes.data, gd.ctypes.data, n_rows, state.n_shift,
+                _native.METHODS[method], lam, mu, row0, state.n_total, state.D.data_ptr(), shifts.data_ptr(), state.C.data_ptr(),
+                state.c_min.data_ptr(), state.through.data_ptr(), state.best.data_ptr(), state.best_arg.data_ptr(),
+                state.alt.data_ptr(), state.alt_arg.data_ptr(), None if marginals is None else marginals.data_ptr(),
+                mem, mem_bytes, st),
+            (curves, shifts, state.D) + state.margin_tensors() + (() if marginals is None else (marginals,)), hip_stream)
     return state
 
 
@@ -223,21 +380,39 @@ class Track(Record):
     cost              the pass's total (float64): the weighted scores (negated under 'ccoeff_normed') plus step_cost per sample
                       moved plus penalty per jump;
     event_scores      every event's own score at its chosen shift (float32 array);
-    event_own_delta   where every event's lone search over the same range lands (seconds, list), event_own_scores its score."""
+    event_own_delta   where every event's lone search over the same range lands (seconds, list), event_own_scores its score.
+    With margins=True (else None), how firmly every event is placed:
+    guard             every event's guard in samples (list of int);
+    event_through     the cost of the best whole path through every event's chosen shift (float64 array: the total, up to
+                      summation order);
+    event_margin      by how much the pass's total rises if the event must lie more than `guard` samples from its place (float64
+                      array: the best alternative's cost minus event_through; inf where the axis holds no such shift).  It counts
+                      what the neighbours pay as well -- an alternative may move a whole run of events -- and is at most 2 *
+                      penalty plus the event's own weighted score difference.  A margin far below the penalty says that the run the
+                      event lies in has a second explanation nearly as good; it is not a probability and not an error in samples;
+    event_alt_shift   where the event goes in that best alternative (samples; None where there is none), event_alt_delta the same
+                      in seconds;
+    marginals         with marginals=True, the whole min-marginals: a float64 CUDA tensor [events, n_shift], entry [e, j] the cost
+                      of the best path that puts event e at displacement k_lo + j."""
 
     def __repr__(self):
         return "Track(segments=%r, cost=%r)" % (self.segments, self.cost)
 
 
 def find_track(stream, patterns, window_centers, window_size, penalty, max_rate=None, reach=None, step_cost=0.0, slack=1,
-               weights="equal", method="sqdiff_normed", max_bytes=MAX_BYTES, max_state_bytes=MAX_STATE_BYTES):
+               weights="equal", method="sqdiff_normed", max_bytes=MAX_BYTES, max_state_bytes=MAX_STATE_BYTES, margins=False,
+               guard=None, marginals=False):
     """WavStream.find_track (its docstring)."""
+    import torch
     from .curves import match_curves
     patterns, centres = list(patterns), list(window_centers)
     if not patterns or len(patterns) != len(centres):
         raise SushiError("find_track: equally many patterns and centres (>= 1)")
     if (max_rate is None) == (reach is None):
         raise SushiError("find_track: exactly one of max_rate and reach")
+    margins, marginals = bool(margins), bool(marginals)
+    if not margins and (marginals or guard is not None):
+        raise SushiError("find_track: guard and marginals belong to margins=True")
     dst_dev = stream.device_stream()
     src_dev, offs, lens, _ = stream._pattern_source(patterns, dst_dev)
     lens = axis.pattern_lengths(lens)
@@ -246,20 +421,42 @@ def find_track(stream, patterns, window_centers, window_size, penalty, max_rate=
     ax = axis.event_axis(stream, offs, lens, centres, window_size)
     k_lo, n_shift, rate = ax.k_lo, ax.n_shift, stream.sample_rate
     reach = checked_reach(rate_reach(ax.bases, max_rate, slack) if reach is None else reach, E)
-    need = TrackState.nbytes(E, n_shift)
+    if margins:
+        guard = checked_guard(int(0.01 * rate) if guard is None else guard, E)
+    need = TrackState.nbytes(E, n_shift, keep=margins, marginals=marginals)
     if need > max_state_bytes:
+        if margins:
+            raise SushiError("find_track: %d events x %d shifts need %d bytes of moves, kept costs%s, max_state_bytes is %d (%d "
+                             "without margins)" % (E, n_shift, need, " and marginals" if marginals else "", max_state_bytes,
+                                                   TrackState.nbytes(E, n_shift)))
         raise SushiError("find_track: %d events x %d shifts need %d bytes of moves and costs, max_state_bytes is %d"
                          % (E, n_shift, need, max_state_bytes))
     per_chunk = int(max_bytes) // (4 * n_shift)
     if per_chunk < 1:
         raise SushiError("find_track: one event of %d shifts needs %d bytes of curves, max_bytes is %d"
                          % (n_shift, 4 * n_shift, max_bytes))
-    state = TrackState(E, n_shift, dst_dev.device)
-    for first in range(0, E, per_chunk):
-        last = min(E, first + per_chunk)
+    state = TrackState(E, n_shift, dst_dev.device, keep=margins)
+    forward = track_forward_keep_device if margins else track_device
+    chunks = [(first, min(E, first + per_chunk)) for first in range(0, E, per_chunk)]
+    for first, last in chunks:
         curves, row_off = axis.event_curves(dst_dev, src_dev, [ax.part(first, last)], method)
-        track_device(curves, zip(row_off, w[first:last].tolist()), reach[first:last], lam, mu, state, row0=first, method=method)
+        forward(curves, zip(row_off, w[first:last].tolist()), reach[first:last], lam, mu, state, row0=first, method=method)
     index_dev = track_backtrack_device(state)
+    extra = dict(guard=None, event_through=None, event_margin=None, event_alt_shift=None, event_alt_delta=None, marginals=None)
+    if margins:
+        # the chunks again, from the last one down: a lone chunk's curves are still there, several chunks' are formed a second time
+        M = torch.empty(E * n_shift, dtype=torch.float64, device=state.D.device) if marginals else None
+        for first, last in reversed(chunks):
+            if len(chunks) > 1:
+                curves, row_off = axis.event_curves(dst_dev, src_dev, [ax.part(first, last)], method)
+            track_margins_device(curves, zip(row_off, w[first:last].tolist()), reach[first:last + 1 if last < E else last],
+                                 guard[first:last], lam, mu, state, index_dev, row0=first, method=method, marginals=M)
+        through, alt, alt_arg = state.through.cpu().numpy(), state.alt.cpu().numpy(), state.alt_arg.cpu().numpy()
+        alt_shift = [None if int(k) == NO_ALT else k_lo + int(k) for k in alt_arg]
+        extra = dict(guard=guard.tolist(), event_through=through,
+                     event_margin=np.where(alt_arg == NO_ALT, np.inf, alt - through), event_alt_shift=alt_shift,
+                     event_alt_delta=[None if k is None else k / float(rate) for k in alt_shift],
+                     marginals=None if M is None else M.view(E, n_shift))
     index = index_dev.cpu().numpy()
     # the move word every event was entered by: row e's, at its chosen shift (E reads of the device array, gathered there)
     words = state.moves[index_dev.long() + n_shift * _arange_like(index_dev)].cpu().numpy()
@@ -273,7 +470,7 @@ def find_track(stream, patterns, window_centers, window_size, penalty, max_rate=
         moves=[0] + [b - a for a, b in zip(shifts[:-1], shifts[1:])], jumps=jumps,
         segments=[(f, n, shifts[f] / float(rate), shifts[f + n - 1] / float(rate)) for f, n in jump_runs(E, jumps)],
         cost=float(state.row_min[E - 1].item()), event_scores=at.cpu().numpy(),
-        event_own_delta=[(k_lo + int(k)) / float(rate) for k in own], event_own_scores=state.row_own_scores.cpu().numpy())
+        event_own_delta=[(k_lo + int(k)) / float(rate) for k in own], event_own_scores=state.row_own_scores.cpu().numpy(), **extra)
 
 
 def _arange_like(index_dev):

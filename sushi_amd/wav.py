@@ -613,7 +613,8 @@ class WavStream(object):
 
     # ------------------------------------------------------------------ a shift that wanders, and may jump
     def find_track(self, patterns, window_centers, window_size, penalty, max_rate=None, reach=None, step_cost=0.0, slack=1,
-                   weights='equal', method="sqdiff_normed", max_bytes=None, max_state_bytes=None):
+                   weights='equal', method="sqdiff_normed", max_bytes=None, max_state_bytes=None, margins=False, guard=None,
+                   marginals=False):
         """A shift for every event of a sequence that may move a little from event to event and jump at a cut
         (sushi_amd.track): the events (patterns, window_centers: in order) are put on one shift axis as
         find_segments puts them, and a shift is chosen per event that minimises the sum of the events' weighted scores plus, between
@@ -627,12 +628,24 @@ class WavStream(object):
         x 2 + 2 x n_shift x 8 bytes, must fit max_state_bytes (default 2 GiB; SushiError names the need).  Returns a Track: k_lo,
         n_shift, shifts (samples per event), deltas (seconds), reach, moves (shifts[e] - shifts[e - 1]), jumps (the events entered
         by a jump), segments ([(first_event, n_events, first_delta, last_delta)]: maximal runs without a jump), cost, event_scores,
-        event_own_delta / event_own_scores (what a lone search of each event over the same range finds).  Needs a GPU."""
+        event_own_delta / event_own_scores (what a lone search of each event over the same range finds).
+        margins=True also says how firmly every event is placed: the pass keeps every row of its costs, runs the
+        same recurrence from the last event down, and the Track gains guard, event_through, event_margin -- by how much the total
+        rises if the event must lie more than `guard` samples from its place: this counts what its neighbours pay too, is at most 2
+        x penalty plus the event's own weighted score difference, and is inf where the axis has no such shift --, event_alt_shift /
+        event_alt_delta (where it would go instead; None where there is none) and, with marginals=True, marginals (a float64 CUDA
+        tensor [events, n_shift]: the cost of the best whole path through every (event, shift)).  guard is an int or one int per
+        event, in samples (default int(0.01 * sample_rate), the reference's ALLOWED_ERROR).  The kept costs, another E x n_shift x 8
+        + 2 x n_shift x 8 bytes (and E x n_shift x 8 for marginals), count under max_state_bytes.  A sequence that goes through in
+        one chunk of max_bytes keeps its curves; one in several chunks forms every chunk's curves a second time, which doubles the
+        curve work.  With margins=False (the default) nothing changes and the new fields are None.  find_segments' margins are
+        find_track(reach=0, margins=True).  Needs a GPU."""
         from . import track
         return track.find_track(self, patterns, window_centers, window_size, penalty, max_rate=max_rate, reach=reach,
                                 step_cost=step_cost, slack=slack, weights=weights, method=method,
                                 max_bytes=track.MAX_BYTES if max_bytes is None else int(max_bytes),
-                                max_state_bytes=track.MAX_STATE_BYTES if max_state_bytes is None else int(max_state_bytes))
+                                max_state_bytes=track.MAX_STATE_BYTES if max_state_bytes is None else int(max_state_bytes),
+                                margins=margins, guard=guard, marginals=marginals)
 
     # ------------------------------------------------------------------ a shift that moves along the programme
     def find_drift(self, patterns, window_centers, window_size, max_rate, resolution=1.0, weights='equal', method="sqdiff_normed",
