@@ -9,11 +9,13 @@
 //   sub_excludes, listed_run_excludes                     does a sub-batch go through the exclusion
 //   vote_due, decide_form, exclusion_form                 band-split or whole rows
 //   direct_slots                  slots of a listed transform that get a workgroup each
+//   pilot_rows_route, pilot_rows_by_search                how the band-split form's pilots get their whole rows
 //   begin_run, report_last_run    what a handle remembers of a run, what each run kind reports
 #ifndef SUSHI_RUN_POLICY_HPP
 #define SUSHI_RUN_POLICY_HPP
 
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
 
@@ -126,6 +128,18 @@ inline int64_t direct_slots(unsigned long long last_transformed, int64_t pairs, 
     else if (last_transformed == 0) direct64 = std::min<int64_t>(pairs, std::max<int64_t>(DIRECT_SLOTS_MIN, pairs / DIRECT_FIRST_RUN_PART));
     return direct64;
 }
+
+// How the band-split form's pilots get their whole rows in an argmin run.  BY_SEARCH (the default): a pass over the searches, each
+// pattern's spectra read once for the pilot and for the search's audit pair -- known before anything is scored: a hash of the
+// search and the run --, and the survivors' pass later reads only the searches the bound left something of.  LIST: every pilot
+// pair by pair and the survivors' pass over every search, as before that pass existed; kept for A/B measurements on one build.
+// `setting` is SUSHI_HIP_PILOT_ROWS as the environment holds it (NULL or empty: the default); -1: neither route's name.
+enum { PILOT_ROWS_BY_SEARCH = 0, PILOT_ROWS_LIST = 1 };
+inline int pilot_rows_route(const char* setting) {
+    if (!setting || !*setting || !strcmp(setting, "search")) return PILOT_ROWS_BY_SEARCH;
+    return !strcmp(setting, "list") ? PILOT_ROWS_LIST : -1;
+}
+inline bool pilot_rows_by_search(int route) { return route != PILOT_ROWS_LIST; }
 
 // What a handle notes when a run of `kind` starts: run_form fills in the cut and the suspension of an argmin run, the sub-batches
 // that go through the exclusion its form and those that do not their pairs.

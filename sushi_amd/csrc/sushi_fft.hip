@@ -17,8 +17,9 @@
 //                    block FFT_STEP * I, FFT_STEP = 2H / B):
 //                    Y_I(f) = sum_s Tt_s(f) * Z_{FFT_STEP*I+s}(f)       (a 1-D Toeplitz product along j)
 //                    -- over every pair on the LOW rows (a quarter of the bins: the band-split form of the exclusion), or on whole
-//                    rows (the whole-row form, no exclusion, the dense fall-back); mac_list_kernel / mac_rows_kernel form the
-//                    whole rows of LISTED pairs only
+//                    rows (the whole-row form, no exclusion, the dense fall-back); mac_rows_kernel / mac_list_kernel form the
+//                    whole rows of LISTED pairs only (search by search: each pilot with its search's audit pair, then what the
+//                    bounds left)
 //   bound_low_kernel / bound_kernel + slb_kernel, pilot_kernel, survivor_kernel
 //                    a LOWER bound of every pair's scores without scoring it; the pair with the smallest bound of every search
 //                    is transformed first, then only the pairs whose bound is not above what the search has found
@@ -167,6 +168,7 @@ struct SushiHipBatch {
     LastRun last;                       // what its last run was
     unsigned run_seq = 0;               // runs so far: rotates which excluded pairs are audited
     int audit_every = 2;                // one search in this many has one excluded pair transformed as a check, per run
+    int pilot_rows = PILOT_ROWS_BY_SEARCH;  // how the pilots' whole rows are formed (run_policy.hpp; SUSHI_HIP_PILOT_ROWS=list: pair by pair, for A/B)
     int bound_model = SUSHI_HIP_BOUND_WORST_CASE;   // (default) / SUSHI_HIP_BOUND_STATISTICAL: how the excluded side's roundings enter slb
     BoundFault fault;                   // the tests' seam (SUSHI_HIP_TEST_BOUND_FAULT; period 0, the default: none)
     // AUTO learns from its own runs (Learnt): the last run's counts come back through 16 bytes of pinned host memory behind an
@@ -441,6 +443,26 @@ static int launch_mac_list(const RunCtx& c, const SubView& v, hipStream_t st, co
     return launch_ok();
 }
 
+// ... search by search, for the patterns of up to MAC_SMAX_LONG segments (header of MacRowsArgs; `mode`: which pairs of a search)
+static int launch_mac_rows(const RunCtx& c, const SubView& v, hipStream_t st, const BoundArgs& ba, const int mode) {
+    const SubBatch& sb = v.sb;
+    MacRowsArgs ra;
+    ra.spec = (const uint4*)c.dst->spec; ra.spec_blocks = c.dst->blocks; ra.tspec = (const uint4*)v.tspec; ra.y = v.y;
+    ra.searches = c.searches + sb.a0; ra.tconst = v.tconst; ra.mark = ba.audit_mark; ra.n_sub = v.n_sub;
+    ra.sub_first_seg = sb.first_seg; ra.sub_first_pair = sb.first_pair; ra.dense_search = v.dense_search;
+    ra.plist = ba.plist; ra.first_search = ba.first_search; ra.audit_seq = ba.audit_seq; ra.audit_every = ba.audit_every;
+    const int64_t rows_want = (int64_t)v.n_sub * MACL_PARTS;
+    const dim3 grid0((unsigned)std::min<int64_t>(rows_want, 256 * 32)), grid1((unsigned)std::min<int64_t>(rows_want, 256 * 16));
+    auto go = [&](auto m) {
+        if (sb.item_count[0] > 0) hipLaunchKernelGGL((mac_rows_kernel<0, decltype(m)::value>), grid0, dim3(MACL_THREADS), 0, st, ra);
+        if (sb.item_count[1] > 0) hipLaunchKernelGGL((mac_rows_kernel<1, decltype(m)::value>), grid1, dim3(MACL_THREADS), 0, st, ra);
+    };
+    if (mode == ROWS_FIRST) go(std::integral_constant<int, ROWS_FIRST>());
+    else if (mode == ROWS_REST) go(std::integral_constant<int, ROWS_REST>());
+    else go(std::integral_constant<int, ROWS_MARKED>());
+    return launch_ok();
+}
+
 static int launch_ifft(const RunCtx& c, const IfftArgs& x, unsigned grid, hipStream_t st) {
     const bool strided = x.count && !x.list_direct;                   // a list whose length only the device knows: a fixed grid strides over its tail
     return launch_method(c.method, [&](auto m) {
@@ -505,7 +527,14 @@ static int exclude_pairs(const RunCtx& c, const SubView& v, hipStream_t st, cons
     if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     ip.slb = ba.slb; ip.audit_mark = nullptr;              // (the pairs transformed first are nobody's excluded pairs)
     ip.order = ba.plist; ip.count = nullptr;
-    if (band && launch_mac_list(c, v, st, ba.plist, nullptr, v.n_sub, nullptr, 0) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    // the pilots' whole rows (band-split form): search by search, each audited search's audit row in the same read of its pattern's
+    // spectra (run_policy.hpp pilot_rows_by_search), and pair by pair for the patterns beyond MAC_SMAX_LONG segments -- or every pilot
+    // pair by pair.  (The pair-by-pair launch is made whether or not the sub-batch holds such a pattern: without one its workgroups
+    // read a descriptor each and leave, a few microseconds, and the stage's kernels -- what the recorded traffic of every bench
+    // workload lists, tests/test_bench_contract.py -- are the same for every batch.)
+    const bool by_search = pilot_rows_by_search(c.b->pilot_rows);
+    if (band && by_search && launch_mac_rows(c, v, st, ba, ROWS_FIRST) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    if (band && launch_mac_list(c, v, st, ba.plist, nullptr, v.n_sub, nullptr, by_search ? 1 : 0) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     if (launch_ifft(c, ip, (unsigned)v.n_sub, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     hipLaunchKernelGGL(survivor_kernel, dim3((unsigned)((sb.pairs + 255) / 256)), dim3(256), 0, st, ba);
     if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
@@ -523,14 +552,8 @@ static int exclude_pairs(const RunCtx& c, const SubView& v, hipStream_t st, cons
                        sb.item_count[1], v.dense_search, v.n_sub, v.ditems, v.ditems + second, v.n_dense_listed, (int)(sb.pairs / 8),
                        v.any_dense);                             // (zero since the run's first launch)
     if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-    MacRowsArgs ra;
-    ra.spec = (const uint4*)c.dst->spec; ra.spec_blocks = c.dst->blocks; ra.tspec = (const uint4*)v.tspec; ra.y = v.y;
-    ra.searches = c.searches + sb.a0; ra.tconst = v.tconst; ra.mark = ba.audit_mark; ra.n_sub = v.n_sub;
-    ra.sub_first_seg = sb.first_seg; ra.sub_first_pair = sb.first_pair; ra.dense_search = v.dense_search;
-    const int64_t rows_want = (int64_t)v.n_sub * MACL_PARTS;
-    if (sb.item_count[0] > 0) hipLaunchKernelGGL(mac_rows_kernel<0>, dim3((unsigned)std::min<int64_t>(rows_want, 256 * 32)), dim3(MACL_THREADS), 0, st, ra);
-    if (sb.item_count[1] > 0) hipLaunchKernelGGL(mac_rows_kernel<1>, dim3((unsigned)std::min<int64_t>(rows_want, 256 * 16)), dim3(MACL_THREADS), 0, st, ra);
-    if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    // (what the pilots' pass formed beside the pilot is not formed again, and a search with nothing left is not read at all)
+    if (launch_mac_rows(c, v, st, ba, by_search ? ROWS_REST : ROWS_MARKED) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     if (sb.long_patterns && launch_mac_list(c, v, st, ba.list2, ba.list2_count, (int)sb.pairs, v.dense_search, 1) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     return launch_mac(c, v, st, false, v.any_dense, v.ditems);
 }
@@ -870,6 +893,8 @@ int sushi_hip_batch_create(const SushiHipStream* dst, const SushiHipStream* src,
     // (measurements only, read once per batch: 0 = no excluded pair is audited; "statistical" = round 5's error model)
     const char* e = getenv("SUSHI_HIP_AUDIT_EVERY");
     if (e && *e) { const int v = atoi(e); b->audit_every = v < 0 ? 0 : v; }
+    // (a value that is neither route is refused: a typo must not turn an A/B measurement into an A/A one)
+    if ((b->pilot_rows = pilot_rows_route(getenv("SUSHI_HIP_PILOT_ROWS"))) < 0) return SUSHI_HIP_EINVAL;
     const char* m = getenv("SUSHI_HIP_BOUND_MODEL");
     if (m && !strcmp(m, "statistical")) b->bound_model = SUSHI_HIP_BOUND_STATISTICAL;
     // (the tests' seam, DESIGN.md 3.2: a value that does not parse is refused -- a typo must not turn a fault test into a no-fault test)

@@ -524,6 +524,19 @@ void survivor_kernel(BoundArgs a) {
 // configs[2], what that kernel's time is --; here they are read once per search (1.8 GB), and the block spectra of neighbouring
 // searches' pairs, walked at about the same time, meet in the L2.  Patterns of more than MAC_SMAX_LONG segments stay with
 // mac_list_kernel (`long_only` there).  Same sums in the same order as mac_kernel (a segment past the pattern's end is a zero entry).
+//
+// An argmin run calls it TWICE (ROWS_FIRST, ROWS_REST), so that a pattern's spectra are read once for the rows known before
+// anything is scored and once more only where the bound left something:
+//   ROWS_FIRST, behind pilot_kernel: the search's pilot (plist[k]) and, if the search is audited in this run, its hashed audit
+//     pair -- survivor_kernel lists that pair whether the bound excludes it or not, so its row can be formed while the spectra are
+//     in registers.  No marks exist yet: the pairs come from the list and the hash.
+//   ROWS_REST, behind the second look: the pairs marked MARK_LISTED, without the audit pair ROWS_FIRST formed (survivor_kernel has
+//     rewritten the marks since: the pair is found again from the same hash arguments).  The marks are scanned BEFORE the spectra are
+//     loaded, and a search with nothing left to form -- a third of the searches at BASELINE configs[2] list nothing, nearly half only
+//     their audit pair -- is left at once.
+//   ROWS_MARKED: every pair marked MARK_LISTED, the spectra loaded first (the route of SUSHI_HIP_PILOT_ROWS=list, where
+//     mac_list_kernel forms every pilot).
+enum { ROWS_MARKED = 0, ROWS_FIRST = 1, ROWS_REST = 2 };
 struct MacRowsArgs {
     const uint4* spec;
     int64_t spec_blocks;
@@ -531,28 +544,76 @@ struct MacRowsArgs {
     uint4* y;
     const SearchDesc* searches;
     const TemplConsts* tconst;
-    const unsigned char* mark;        // [pairs of the sub-batch] MARK_LISTED: the pair's row is formed
+    const unsigned char* mark;        // [pairs of the sub-batch] MARK_LISTED: the pair's row is formed (ROWS_FIRST: not read)
     int n_sub;
     int sub_first_seg;
     int sub_first_pair;
-    const int* dense_search;          // [searches of the sub-batch]: 1 = the dense multiply-accumulate forms this search's rows instead
+    const int* dense_search;          // [searches of the sub-batch]: 1 = the dense multiply-accumulate forms this search's rows instead (ROWS_FIRST: not read)
+    const int* plist;                 // [searches of the sub-batch] ROWS_FIRST: the pair transformed first
+    int first_search;                 // ROWS_FIRST / ROWS_REST: what audited_search and audit_pair_of hash (BoundArgs' own)
+    unsigned audit_seq;
+    int audit_every;
 };
+// one row: the pattern's spectra `tt` against the block spectra of pair `ip` of the search
 template <int SMAX>
-__device__ __forceinline__ void mac_rows_of_search(const MacRowsArgs& a, const SearchDesc& sd, const FftLayout& lay, const float sy,
-                                                   const int e, unsigned long long (*masks)[4], const int z_zero) {
+__device__ __forceinline__ void mac_row_of_pair(const MacRowsArgs& a, const FftLayout& lay, const sushi_mac::h8 (&tt)[SMAX],
+                                                const uint4* __restrict__ zsp, const int p0, const int ip, const float sy, const int e,
+                                                const int z_zero) {
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    const long long I = lay.pair0 + ip;
+    sushi_mac::acc4 acc = sushi_mac::zero_acc();
+#pragma unroll
+    for (int s6 = 0; s6 < SMAX; s6 += 6) {
+        sushi_mac::h8 z[6];
+#pragma unroll
+        for (int t = 0; t < 6; ++t) {
+            const long long jj = s6 + t < lay.n_seg ? FFT_STEP * I + s6 + t : (long long)z_zero;     // (past the pattern: the zero block)
+            z[t] = as_h8(zsp[(size_t)(jj < z_zero ? jj : z_zero) * ROWE]);
+        }
+#pragma unroll
+        for (int t = 0; t < 6; ++t) {
+            const sushi_mac::zrow zr = {z[t], sushi_mac::rot_mi(z[t])};
+            sushi_mac::mac4(acc, tt[s6 + t], zr);
+        }
+    }
+    unsigned o[sushi_mac::BINS];
+#pragma unroll
+    for (int q = 0; q < sushi_mac::BINS; ++q) {
+        const h2 h = {(_Float16)(acc.re[q] * sy), (_Float16)(acc.im[q] * sy)};
+        o[q] = __builtin_bit_cast(unsigned, h);
+    }
+    a.y[(size_t)(p0 + ip) * ROWE + e] = uint4{o[0], o[1], o[2], o[3]};
+}
+template <int SMAX, int MODE>
+__device__ __forceinline__ void mac_rows_of_search(const MacRowsArgs& a, const SearchDesc& sd, const FftLayout& lay, const int k,
+                                                   const float sy, const int e, unsigned long long (*masks)[4], const int z_zero) {
     const uint4* __restrict__ tsp = a.tspec + (size_t)(sd.first_seg - a.sub_first_seg) * ROWE + e;
     const uint4* __restrict__ zsp = a.spec + e;
     const int p0 = first_pair_in_sub(a.sub_first_pair, sd);
+    const int tid = threadIdx.x;
+    // the audit pair of the search (its index inside the search; -1: the search is not audited in this run): what ROWS_FIRST forms
+    // beside the pilot and ROWS_REST leaves out
+    int audit = -1;
+    if (MODE != ROWS_MARKED && audited_search(a, k)) audit = audit_pair_of(a, sd, k);
+    if (MODE == ROWS_REST) {
+        bool any = false;
+        for (int i = tid; i < lay.n_pairs; i += MACL_THREADS) any = any || (i != audit && (a.mark[p0 + i] & MARK_LISTED));
+        if (!__syncthreads_or(any)) return;                    // (uniform: nothing of this search is left to form)
+    }
     sushi_mac::h8 tt[SMAX];
 #pragma unroll
     for (int s = 0; s < SMAX; ++s) tt[s] = s < lay.n_seg ? as_h8(tsp[(size_t)s * ROWE]) : sushi_mac::zero_h8();
-    const int tid = threadIdx.x;
+    if (MODE == ROWS_FIRST) {
+        const int pilot = a.plist[k] - p0;
+        mac_row_of_pair<SMAX>(a, lay, tt, zsp, p0, pilot, sy, e, z_zero);
+        if (audit >= 0 && audit < lay.n_pairs && audit != pilot) mac_row_of_pair<SMAX>(a, lay, tt, zsp, p0, audit, sy, e, z_zero);
+        return;
+    }
     for (int base = 0; base < lay.n_pairs; base += MACL_THREADS) {
         // which of these 256 pairs are listed: one flag per thread, a ballot per wave
         __syncthreads();
         const int i = base + tid;
-        const bool on = i < lay.n_pairs && (a.mark[p0 + i] & MARK_LISTED);
+        const bool on = i < lay.n_pairs && (MODE == ROWS_MARKED || i != audit) && (a.mark[p0 + i] & MARK_LISTED);
         const unsigned long long bm = __ballot(on);
         if ((tid & 63) == 0) (*masks)[tid >> 6] = bm;
         __syncthreads();
@@ -561,52 +622,30 @@ __device__ __forceinline__ void mac_rows_of_search(const MacRowsArgs& a, const S
             while (m) {
                 const int bit = __builtin_ctzll(m);
                 m &= m - 1;
-                const int ip = base + 64 * w + bit;
-                const long long I = lay.pair0 + ip;
-                sushi_mac::acc4 acc = sushi_mac::zero_acc();
-#pragma unroll
-                for (int s6 = 0; s6 < SMAX; s6 += 6) {
-                    sushi_mac::h8 z[6];
-#pragma unroll
-                    for (int t = 0; t < 6; ++t) {
-                        const long long jj = s6 + t < lay.n_seg ? FFT_STEP * I + s6 + t : (long long)z_zero;     // (past the pattern: the zero block)
-                        z[t] = as_h8(zsp[(size_t)(jj < z_zero ? jj : z_zero) * ROWE]);
-                    }
-#pragma unroll
-                    for (int t = 0; t < 6; ++t) {
-                        const sushi_mac::zrow zr = {z[t], sushi_mac::rot_mi(z[t])};
-                        sushi_mac::mac4(acc, tt[s6 + t], zr);
-                    }
-                }
-                unsigned o[sushi_mac::BINS];
-#pragma unroll
-                for (int q = 0; q < sushi_mac::BINS; ++q) {
-                    const h2 h = {(_Float16)(acc.re[q] * sy), (_Float16)(acc.im[q] * sy)};
-                    o[q] = __builtin_bit_cast(unsigned, h);
-                }
-                a.y[(size_t)(p0 + ip) * ROWE + e] = uint4{o[0], o[1], o[2], o[3]};
+                mac_row_of_pair<SMAX>(a, lay, tt, zsp, p0, base + 64 * w + bit, sy, e, z_zero);
             }
         }
     }
 }
-template <int LONG>            // 0: patterns of up to MAC_SMAX_SHORT segments; 1: longer ones up to MAC_SMAX_LONG (their registers halve the occupancy)
+// LONG 0: patterns of up to MAC_SMAX_SHORT segments; 1: longer ones up to MAC_SMAX_LONG (their registers halve the occupancy)
+template <int LONG, int MODE>
 __global__ __launch_bounds__(MACL_THREADS)
 void mac_rows_kernel(MacRowsArgs a) {
     __shared__ unsigned long long masks[4];
     const int z_zero = (int)(a.spec_blocks < 0x7fffffff ? a.spec_blocks : 0x7fffffff);
     for (long long it = blockIdx.x; it < (long long)a.n_sub * MACL_PARTS; it += gridDim.x) {
         const int k = (int)(it / MACL_PARTS);
-        if (a.dense_search[k]) continue;                       // (uniform: a workgroup is one search's)
+        if (MODE != ROWS_FIRST && a.dense_search[k]) continue;  // (uniform: a workgroup is one search's)
         const int e = (int)(it % MACL_PARTS) * MACL_THREADS + threadIdx.x;
         const SearchDesc sd = a.searches[k];
         const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
         const float sy = a.tconst[k].mac_scale;
         if (LONG) {
-            if (lay.n_seg > MAC_SMAX_SHORT && lay.n_seg <= MAC_SMAX_LONG) mac_rows_of_search<MAC_SMAX_LONG>(a, sd, lay, sy, e, &masks, z_zero);
+            if (lay.n_seg > MAC_SMAX_SHORT && lay.n_seg <= MAC_SMAX_LONG) mac_rows_of_search<MAC_SMAX_LONG, MODE>(a, sd, lay, k, sy, e, &masks, z_zero);
         } else {
-            if (lay.n_seg <= 6) mac_rows_of_search<6>(a, sd, lay, sy, e, &masks, z_zero);
-            else if (lay.n_seg <= 12) mac_rows_of_search<12>(a, sd, lay, sy, e, &masks, z_zero);
-            else if (lay.n_seg <= MAC_SMAX_SHORT) mac_rows_of_search<MAC_SMAX_SHORT>(a, sd, lay, sy, e, &masks, z_zero);
+            if (lay.n_seg <= 6) mac_rows_of_search<6, MODE>(a, sd, lay, k, sy, e, &masks, z_zero);
+            else if (lay.n_seg <= 12) mac_rows_of_search<12, MODE>(a, sd, lay, k, sy, e, &masks, z_zero);
+            else if (lay.n_seg <= MAC_SMAX_SHORT) mac_rows_of_search<MAC_SMAX_SHORT, MODE>(a, sd, lay, k, sy, e, &masks, z_zero);
         }
         // (longer patterns still: mac_list_kernel, several passes)
     }
