@@ -314,7 +314,8 @@ static_assert(sizeof(SubCounters) <= SUBC_SCOUNT * sizeof(int), "the scount word
 enum ScountSlot {
     SC_SLIST = 0,           // survivors: entries of slist
     SC_CITEMS = 1,          // collect items: entries of citems (refine_kernel's list for collect_kernel)
-    // 2, 3: free
+    SC_REST_ITEMS = 2,      // work items of the survivors' pass (dense_search_kernel): entries of slist, which is dead by then
+    // 3: free
     SC_ANY_DENSE = 4,       // dense whole rows: 1 where some search takes the dense form (dense_repack_kernel; enables that launch)
     SC_SLIST2 = 5,          // pairs left after the second look: entries of slist2
     SC_DENSE_LISTED = 6,    // listed pairs of the searches that would take the dense form

@@ -10,6 +10,9 @@
 //   vote_due, decide_form, exclusion_form                 band-split or whole rows
 //   direct_slots                  slots of a listed transform that get a workgroup each
 //   pilot_rows_route, pilot_rows_by_search                how the band-split form's pilots get their whole rows
+//   rest_rows_route, rest_rows_by_item                    the unit of work of the survivors' pass behind them
+//   rest_pair_to_form, rest_item_starts, rest_item_take   how a search's surviving pairs are cut into that pass's work items
+//                                                         (the three the device calls as well: SUSHI_HHD)
 //   begin_run, report_last_run    what a handle remembers of a run, what each run kind reports
 #ifndef SUSHI_RUN_POLICY_HPP
 #define SUSHI_RUN_POLICY_HPP
@@ -20,6 +23,14 @@
 #include <algorithm>
 
 #include "sushi_geometry.hpp"
+
+#ifndef SUSHI_HHD
+#ifdef __HIPCC__
+#define SUSHI_HHD __host__ __device__ inline
+#else
+#define SUSHI_HHD inline
+#endif
+#endif
 
 namespace sushi {
 
@@ -140,6 +151,48 @@ inline int pilot_rows_route(const char* setting) {
     return !strcmp(setting, "list") ? PILOT_ROWS_LIST : -1;
 }
 inline bool pilot_rows_by_search(int route) { return route != PILOT_ROWS_LIST; }
+
+// The unit of work of the survivors' pass behind a BY_SEARCH first pass (mac_rows_kernel).  BY_ITEM (the default): a few listed
+// pairs of one search -- dense_search_kernel cuts every search's pairs to form into runs of at most REST_ITEM_PAIRS and lists the
+// runs, a workgroup takes (run, 256 entries).  BY_SEARCH: (search, 256 entries), every listed pair of the search one after the
+// other, as before the items existed; kept for A/B measurements on one build.  `setting` is SUSHI_HIP_REST_ROWS as the
+// environment holds it (NULL or empty: the default); -1: neither route's name.
+enum { REST_ROWS_BY_ITEM = 0, REST_ROWS_BY_SEARCH = 1 };
+inline int rest_rows_route(const char* setting) {
+    if (!setting || !*setting || !strcmp(setting, "items")) return REST_ROWS_BY_ITEM;
+    return !strcmp(setting, "search") ? REST_ROWS_BY_SEARCH : -1;
+}
+inline bool rest_rows_by_item(int route) { return route != REST_ROWS_BY_SEARCH; }
+
+// THE CUT of a search's pairs into the survivors' pass's work items.  An item is a run of the search's pairs that holds at most
+// REST_ITEM_PAIRS pairs TO FORM -- listed, and not the audit pair the first pass formed already --, named by its first such
+// pair; a search with nothing to form has no item.  Every item re-reads its pattern's spectra (a few 64 KB rows of the short
+// patterns where the cutting happens, L2-hot behind the item in front), so the constant trades an even launch against those
+// reads: 2, 4 and 8 were measured (tools/experiments/README.md).
+// (-DSUSHI_REST_ITEM_PAIRS=<n>: a library with another value, for those measurements)
+#ifndef SUSHI_REST_ITEM_PAIRS
+#define SUSHI_REST_ITEM_PAIRS 4
+#endif
+constexpr int REST_ITEM_PAIRS = SUSHI_REST_ITEM_PAIRS;
+static_assert(REST_ITEM_PAIRS >= 1, "an item holds a pair");
+// is pair `i` of its search (`listed`: its mark's MARK_LISTED bit; `audit`: the search's audit pair, -1: none) one to form
+SUSHI_HHD bool rest_pair_to_form(int listed, int i, int audit) { return listed != 0 && i != audit; }
+// The builder's half.  `form`: which of 64 consecutive pairs of a search are to form (bit j: the j-th of them), `before`: how many
+// pairs to form the search holds in front of them -> the bits that START an item: every `per_item`-th pair to form, from the first.
+SUSHI_HHD unsigned long long rest_item_starts(unsigned long long form, int before, int per_item) {
+    unsigned long long starts = 0;
+    int rank = before;
+    for (unsigned long long m = form; m; m &= m - 1, ++rank)
+        if (rank % per_item == 0) starts |= m & (~m + 1);
+    return starts;
+}
+// The consumer's half, walking on from an item's first pair 64 pairs at a time: of the pairs to form `form` among the next 64,
+// the ones that are still the item's, which has room for `room` more -> the first `room` of them.
+SUSHI_HHD unsigned long long rest_item_take(unsigned long long form, int room) {
+    unsigned long long take = 0;
+    for (unsigned long long m = form; m && room > 0; m &= m - 1, --room) take |= m & (~m + 1);
+    return take;
+}
 
 // What a handle notes when a run of `kind` starts: run_form fills in the cut and the suspension of an argmin run, the sub-batches
 // that go through the exclusion its form and those that do not their pairs.

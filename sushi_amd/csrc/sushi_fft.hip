@@ -169,6 +169,7 @@ struct SushiHipBatch {
     unsigned run_seq = 0;               // runs so far: rotates which excluded pairs are audited
     int audit_every = 2;                // one search in this many has one excluded pair transformed as a check, per run
     int pilot_rows = PILOT_ROWS_BY_SEARCH;  // how the pilots' whole rows are formed (run_policy.hpp; SUSHI_HIP_PILOT_ROWS=list: pair by pair, for A/B)
+    int rest_rows = REST_ROWS_BY_ITEM;      // the survivors' pass's unit of work (run_policy.hpp; SUSHI_HIP_REST_ROWS=search: a whole search, for A/B)
     int bound_model = SUSHI_HIP_BOUND_WORST_CASE;   // (default) / SUSHI_HIP_BOUND_STATISTICAL: how the excluded side's roundings enter slb
     BoundFault fault;                   // the tests' seam (SUSHI_HIP_TEST_BOUND_FAULT; period 0, the default: none)
     // AUTO learns from its own runs (Learnt): the last run's counts come back through 16 bytes of pinned host memory behind an
@@ -451,7 +452,9 @@ static int launch_mac_rows(const RunCtx& c, const SubView& v, hipStream_t st, co
     ra.searches = c.searches + sb.a0; ra.tconst = v.tconst; ra.mark = ba.audit_mark; ra.n_sub = v.n_sub;
     ra.sub_first_seg = sb.first_seg; ra.sub_first_pair = sb.first_pair; ra.dense_search = v.dense_search;
     ra.plist = ba.plist; ra.first_search = ba.first_search; ra.audit_seq = ba.audit_seq; ra.audit_every = ba.audit_every;
-    const int64_t rows_want = (int64_t)v.n_sub * MACL_PARTS;
+    ra.items = v.slist; ra.item_count = v.n_rest_items; ra.pairmap = v.pairmap; ra.n_pairs = (int)sb.pairs;
+    // (ROWS_ITEMS: how many items there are only the device knows -- at most one per pair; a fixed grid strides over them)
+    const int64_t rows_want = (int64_t)(mode == ROWS_ITEMS ? sb.pairs : v.n_sub) * MACL_PARTS;
     const dim3 grid0((unsigned)std::min<int64_t>(rows_want, 256 * 32)), grid1((unsigned)std::min<int64_t>(rows_want, 256 * 16));
     auto go = [&](auto m) {
         if (sb.item_count[0] > 0) hipLaunchKernelGGL((mac_rows_kernel<0, decltype(m)::value>), grid0, dim3(MACL_THREADS), 0, st, ra);
@@ -459,6 +462,7 @@ static int launch_mac_rows(const RunCtx& c, const SubView& v, hipStream_t st, co
     };
     if (mode == ROWS_FIRST) go(std::integral_constant<int, ROWS_FIRST>());
     else if (mode == ROWS_REST) go(std::integral_constant<int, ROWS_REST>());
+    else if (mode == ROWS_ITEMS) go(std::integral_constant<int, ROWS_ITEMS>());
     else go(std::integral_constant<int, ROWS_MARKED>());
     return launch_ok();
 }
@@ -546,14 +550,18 @@ static int exclude_pairs(const RunCtx& c, const SubView& v, hipStream_t st, cons
     // whole rows of what is left: pair by pair for the searches that left few (the usual case), by the dense
     // multiply-accumulate for the searches the bound could exclude little of (no match anywhere) -- decided per search and
     // regrouped into items of their own, on the device (dense_search_kernel, dense_repack_kernel)
-    hipLaunchKernelGGL(dense_search_kernel, dim3((unsigned)v.n_sub), dim3(64), 0, st, ba, v.dense_search, v.n_dense_listed);
+    // (... and, for the survivors' pass by items, each search's pairs to form cut into that pass's work items: slist is dead behind
+    // the second look, the count word zero since the run's first launch)
+    const bool by_item = by_search && rest_rows_by_item(c.b->rest_rows);
+    hipLaunchKernelGGL(dense_search_kernel, dim3((unsigned)v.n_sub), dim3(64), 0, st, ba, v.dense_search, v.n_dense_listed,
+                       by_item ? v.slist : nullptr, v.n_rest_items);
     const size_t second = (size_t)(sb.item_first[1] - sb.item_first[0]) * (1 + MAC_SPW);
     hipLaunchKernelGGL(dense_repack_kernel, dim3(2), dim3(REPACK_THREADS), 0, st, v.items, sb.item_count[0], v.items + second,
                        sb.item_count[1], v.dense_search, v.n_sub, v.ditems, v.ditems + second, v.n_dense_listed, (int)(sb.pairs / 8),
                        v.any_dense);                             // (zero since the run's first launch)
     if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     // (what the pilots' pass formed beside the pilot is not formed again, and a search with nothing left is not read at all)
-    if (launch_mac_rows(c, v, st, ba, by_search ? ROWS_REST : ROWS_MARKED) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    if (launch_mac_rows(c, v, st, ba, by_item ? ROWS_ITEMS : by_search ? ROWS_REST : ROWS_MARKED) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     if (sb.long_patterns && launch_mac_list(c, v, st, ba.list2, ba.list2_count, (int)sb.pairs, v.dense_search, 1) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     return launch_mac(c, v, st, false, v.any_dense, v.ditems);
 }
@@ -895,6 +903,7 @@ int sushi_hip_batch_create(const SushiHipStream* dst, const SushiHipStream* src,
     if (e && *e) { const int v = atoi(e); b->audit_every = v < 0 ? 0 : v; }
     // (a value that is neither route is refused: a typo must not turn an A/B measurement into an A/A one)
     if ((b->pilot_rows = pilot_rows_route(getenv("SUSHI_HIP_PILOT_ROWS"))) < 0) return SUSHI_HIP_EINVAL;
+    if ((b->rest_rows = rest_rows_route(getenv("SUSHI_HIP_REST_ROWS"))) < 0) return SUSHI_HIP_EINVAL;
     const char* m = getenv("SUSHI_HIP_BOUND_MODEL");
     if (m && !strcmp(m, "statistical")) b->bound_model = SUSHI_HIP_BOUND_STATISTICAL;
     // (the tests' seam, DESIGN.md 3.2: a value that does not parse is refused -- a typo must not turn a fault test into a no-fault test)

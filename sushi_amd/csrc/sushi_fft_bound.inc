@@ -536,7 +536,18 @@ void survivor_kernel(BoundArgs a) {
 //     their audit pair -- is left at once.
 //   ROWS_MARKED: every pair marked MARK_LISTED, the spectra loaded first (the route of SUSHI_HIP_PILOT_ROWS=list, where
 //     mac_list_kernel forms every pilot).
-enum { ROWS_MARKED = 0, ROWS_FIRST = 1, ROWS_REST = 2 };
+//   ROWS_ITEMS: ROWS_REST's rows with another unit of work (the default; SUSHI_HIP_REST_ROWS=search: ROWS_REST).  A workgroup of
+//     ROWS_REST is (search, 256 entries): more than half of them scan the marks and leave, and the real survivors sit mostly in the
+//     few searches of up to four segments, whose workgroups form their rows one after the other, each a dependent round trip of six
+//     loads, the multiply-accumulates and a store -- the launch ends with a few long chains on an idle chip (0.47 ms for 1.5 GB
+//     at BASELINE configs[2], 3.3 TB/s where the first pass reads at 4.8).  Here a workgroup is (ITEM, 256 entries): an item is a run
+//     of one search's pairs that holds at most REST_ITEM_PAIRS pairs to form (run_policy.hpp: the cut rule, and why that many),
+//     listed by dense_search_kernel, which walks every search's marks anyway -- no launch more; the list is one int per item, the
+//     run's first pair, in `slist` (dead once survivor2_kernel has run) and its length a word of the zeroed counters.  A fixed grid
+//     strides over (item, part), the count read from device memory; the workgroup finds the search through `pairmap`, loads the
+//     pattern's spectra once for the item and walks the marks on from its first pair to REST_ITEM_PAIRS pairs to form or the
+//     search's end.  mac_row_of_pair is the same: every row keeps its bits.  No workgroup waits for another.
+enum { ROWS_MARKED = 0, ROWS_FIRST = 1, ROWS_REST = 2, ROWS_ITEMS = 3 };
 struct MacRowsArgs {
     const uint4* spec;
     int64_t spec_blocks;
@@ -550,9 +561,14 @@ struct MacRowsArgs {
     int sub_first_pair;
     const int* dense_search;          // [searches of the sub-batch]: 1 = the dense multiply-accumulate forms this search's rows instead (ROWS_FIRST: not read)
     const int* plist;                 // [searches of the sub-batch] ROWS_FIRST: the pair transformed first
-    int first_search;                 // ROWS_FIRST / ROWS_REST: what audited_search and audit_pair_of hash (BoundArgs' own)
+    int first_search;                 // ROWS_FIRST / ROWS_REST / ROWS_ITEMS: what audited_search and audit_pair_of hash (BoundArgs' own)
     unsigned audit_seq;
     int audit_every;
+    // ROWS_ITEMS
+    const int* items;                 // [up to n_pairs] an item's first pair to form (a pair of the sub-batch)
+    const int* item_count;            // [1] how many
+    const int* pairmap;               // [pairs of the sub-batch] -> search of the sub-batch
+    int n_pairs;                      // pairs of the sub-batch: the list's capacity
 };
 // one row: the pattern's spectra `tt` against the block spectra of pair `ip` of the search
 template <int SMAX>
@@ -627,12 +643,61 @@ __device__ __forceinline__ void mac_rows_of_search(const MacRowsArgs& a, const S
         }
     }
 }
+// ROWS_ITEMS: the rows of one item, the run of the search's pairs that starts at its pair `first` (a pair to form).  Every wave
+// reads the same marks and takes the same pairs: no exchange, no barrier.
+template <int SMAX>
+__device__ __forceinline__ void mac_rows_of_item(const MacRowsArgs& a, const SearchDesc& sd, const FftLayout& lay, const int k,
+                                                 const float sy, const int e, const int z_zero, const int first) {
+    const uint4* __restrict__ tsp = a.tspec + (size_t)(sd.first_seg - a.sub_first_seg) * ROWE + e;
+    const uint4* __restrict__ zsp = a.spec + e;
+    const int p0 = first_pair_in_sub(a.sub_first_pair, sd);
+    const int audit = audited_search(a, k) ? audit_pair_of(a, sd, k) : -1;
+    sushi_mac::h8 tt[SMAX];
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) tt[s] = s < lay.n_seg ? as_h8(tsp[(size_t)s * ROWE]) : sushi_mac::zero_h8();
+    int room = REST_ITEM_PAIRS;
+    for (int base = first; base < lay.n_pairs && room > 0; base += 64) {
+        const int i = base + (threadIdx.x & 63);
+        const bool on = i < lay.n_pairs && rest_pair_to_form(a.mark[p0 + i] & MARK_LISTED, i, audit);
+        unsigned long long m = rest_item_take(__ballot(on), room);
+        room -= __popcll(m);
+        while (m) {
+            const int bit = __builtin_ctzll(m);
+            m &= m - 1;
+            mac_row_of_pair<SMAX>(a, lay, tt, zsp, p0, base + bit, sy, e, z_zero);
+        }
+    }
+}
 // LONG 0: patterns of up to MAC_SMAX_SHORT segments; 1: longer ones up to MAC_SMAX_LONG (their registers halve the occupancy)
 template <int LONG, int MODE>
 __global__ __launch_bounds__(MACL_THREADS)
 void mac_rows_kernel(MacRowsArgs a) {
     __shared__ unsigned long long masks[4];
     const int z_zero = (int)(a.spec_blocks < 0x7fffffff ? a.spec_blocks : 0x7fffffff);
+    if (MODE == ROWS_ITEMS) {
+        const int listed = *a.item_count;
+        const int n_items = listed < a.n_pairs ? listed : a.n_pairs;           // (the list's capacity)
+        for (long long it = blockIdx.x; it < (long long)n_items * MACL_PARTS; it += gridDim.x) {
+            const int first = __builtin_amdgcn_readfirstlane(a.items[it / MACL_PARTS]);
+            if ((unsigned)first >= (unsigned)a.n_pairs) continue;
+            const int k = __builtin_amdgcn_readfirstlane(a.pairmap[first]);
+            if ((unsigned)k >= (unsigned)a.n_sub || a.dense_search[k]) continue;   // (the dense multiply-accumulate forms this search's rows)
+            const int e = (int)(it % MACL_PARTS) * MACL_THREADS + threadIdx.x;
+            const SearchDesc sd = a.searches[k];
+            const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
+            const float sy = a.tconst[k].mac_scale;
+            const int i0 = first - first_pair_in_sub(a.sub_first_pair, sd);
+            if ((unsigned)i0 >= (unsigned)lay.n_pairs) continue;
+            if (LONG) {
+                if (lay.n_seg > MAC_SMAX_SHORT && lay.n_seg <= MAC_SMAX_LONG) mac_rows_of_item<MAC_SMAX_LONG>(a, sd, lay, k, sy, e, z_zero, i0);
+            } else {
+                if (lay.n_seg <= 6) mac_rows_of_item<6>(a, sd, lay, k, sy, e, z_zero, i0);
+                else if (lay.n_seg <= 12) mac_rows_of_item<12>(a, sd, lay, k, sy, e, z_zero, i0);
+                else if (lay.n_seg <= MAC_SMAX_SHORT) mac_rows_of_item<MAC_SMAX_SHORT>(a, sd, lay, k, sy, e, z_zero, i0);
+            }
+        }
+        return;
+    }
     for (long long it = blockIdx.x; it < (long long)a.n_sub * MACL_PARTS; it += gridDim.x) {
         const int k = (int)(it / MACL_PARTS);
         if (MODE != ROWS_FIRST && a.dense_search[k]) continue;  // (uniform: a workgroup is one search's)
@@ -763,14 +828,34 @@ void survivor2_kernel(BoundArgs a) {
 // short patterns of BASELINE configs[2] whose survivors exceed two fifths of their pairs (1 - 2 % of all pairs) cost 1.4 ms a step
 // in the dense form, the ones at 6 dB of noise (2 - 9 %) 1.4 ms more than pair by pair.
 __global__ __launch_bounds__(64)
-void dense_search_kernel(BoundArgs a, int* __restrict__ dense_search, int* __restrict__ any) {
+void dense_search_kernel(BoundArgs a, int* __restrict__ dense_search, int* __restrict__ any, int* __restrict__ items,
+                         int* __restrict__ item_count) {
     const int lane = threadIdx.x;
     const int k = blockIdx.x;
     const SearchDesc sd = a.searches[k];
     const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
     const int p0 = first_pair_in_sub(a.sub_first_pair, sd);
-    int listed = 0;
-    for (int i = lane; i < lay.n_pairs; i += 64) listed += (a.audit_mark[p0 + i] & MARK_LISTED) ? 1 : 0;
+    // `items` (or NULL): the work items of mac_rows_kernel's ROWS_ITEMS pass (its header) -- the search's pairs to form, cut by
+    // run_policy.hpp's rule, each item the sub-batch index of its first pair; whatever becomes of the dense flags later, the
+    // consumer skips the searches that keep theirs.  One atomicAdd per 64 pairs that start an item; the list holds a slot per pair.
+    const int audit = items && audited_search(a, k) ? audit_pair_of(a, sd, k) : -1;
+    int listed = 0, formed = 0;
+    for (int base = 0; base < lay.n_pairs; base += 64) {
+        const int i = base + lane;
+        const int on = i < lay.n_pairs ? (a.audit_mark[p0 + i] & MARK_LISTED) : 0;
+        listed += on ? 1 : 0;
+        if (items) {
+            const unsigned long long form = __ballot(rest_pair_to_form(on, i, audit));
+            const unsigned long long starts = rest_item_starts(form, formed, REST_ITEM_PAIRS);
+            formed += __popcll(form);
+            if (starts) {
+                int slot = 0;
+                if (lane == 0) slot = atomicAdd(item_count, __popcll(starts));
+                slot = __shfl(slot, 0, 64) + __popcll(starts & ((1ull << lane) - 1ull));
+                if (((starts >> lane) & 1ull) && slot < a.n_pairs) items[slot] = p0 + i;
+            }
+        }
+    }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) listed += __shfl_xor(listed, d, 64);
     if (lane == 0) {

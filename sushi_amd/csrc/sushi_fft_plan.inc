@@ -44,7 +44,7 @@ struct SubView {
     uint32_t* tspec; uint4 *y, *tspec_low, *ylow, *dummy; unsigned long long* cand; TemplConsts* tconst; TileDesc* tiles; int32_t* candbuf;
     float *pair_lb, *slb, *acc, *tnorm_rest; unsigned char* audit_mark; SubCounters* sub; const int32_t *order, *items;
     int *pairmap, *plist, *slist, *slist2, *votes, *dense_search, *ditems, *citems;
-    int *n_slist, *n_citems, *any_dense, *n_slist2, *n_dense_listed, *n_list3;     // the scount words (ScountSlot)
+    int *n_slist, *n_citems, *any_dense, *n_slist2, *n_dense_listed, *n_list3, *n_rest_items;     // the scount words (ScountSlot)
     SubView(char* mem, const BatchLayout& lay, size_t ws_lane, const SubBatch& s, size_t si) : sb(s), n_sub(s.b0 - s.a0) {
         const WsLayout w = ws_layout(s.pairs, s.segs, n_sub);
         char* p = mem + lay.ws + (size_t)s.lane * ws_lane;
@@ -54,7 +54,7 @@ struct SubView {
         audit_mark = (unsigned char*)(p + w.audit_mark); sub = (SubCounters*)(mem + lay.subc + si * SUBC_BYTES);
         int* const scount = (int*)sub + SUBC_SCOUNT;
         n_slist = scount + SC_SLIST; n_citems = scount + SC_CITEMS; any_dense = scount + SC_ANY_DENSE; n_slist2 = scount + SC_SLIST2;
-        n_dense_listed = scount + SC_DENSE_LISTED; n_list3 = scount + SC_LIST3;
+        n_dense_listed = scount + SC_DENSE_LISTED; n_list3 = scount + SC_LIST3; n_rest_items = scount + SC_REST_ITEMS;
         order = (const int32_t*)(mem + lay.order) + s.order_first;
         items = (const int32_t*)(mem + lay.items) + (size_t)s.item_first[0] * (1 + MAC_SPW);   // (its two item lists lie next to each other)
         pairmap = (int*)(p + w.pairmap); plist = (int*)(p + w.plist); slist = (int*)(p + w.slist); slist2 = (int*)(p + w.slist2);
