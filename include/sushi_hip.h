@@ -320,6 +320,7 @@ SUSHI_HIP_API int sushi_hip_batch_pair_bounds(SushiHipBatch* batch, float* slb_h
 #define SUSHI_HIP_WS_Y 1
 #define SUSHI_HIP_WS_TSPEC_LOW 2
 #define SUSHI_HIP_WS_Y_LOW 3
+#define SUSHI_HIP_WS_TNORM_REST 4   /* float32 per pattern segment: the SQUARED norm of its stored halves outside the band */
 SUSHI_HIP_API int sushi_hip_batch_workspace_view(SushiHipBatch* batch, int which, void** ptr_dev, size_t* bytes);
 SUSHI_HIP_API void sushi_hip_batch_destroy(SushiHipBatch* batch);
 

@@ -29,13 +29,13 @@ ABI_VERSION = 13
 ENOSPACE = -4              # SUSHI_HIP_ENOSPACE: buffer or workspace too small
 NSTAGES = 6
 STAGE_NAMES = ("tspec", "mac", "ifft", "refine", "finish", "bound")
-STAGE_KERNELS = {"tspec": "tspec_kernel", "mac": "mac_kernel", "ifft": "mac_list_kernel+mac_rows_kernel+ifft_kernel", "refine": "refine_kernel",
+STAGE_KERNELS = {"tspec": "tspec_real_kernel|tspec_kernel", "mac": "mac_kernel", "ifft": "mac_list_kernel+mac_rows_kernel+ifft_kernel", "refine": "refine_kernel",
                  "finish": "collect_kernel+exact_tiles_kernel+unpack_keys_kernel", "bound": "bound_low_kernel|bound_kernel"}
 EXCLUSION = {"auto": 0, "always": 1, "never": 2, "band": 3, "whole": 4}        # SUSHI_HIP_EXCLUDE_*
-WS_TSPEC, WS_Y, WS_TSPEC_LOW, WS_Y_LOW = range(4)                               # SUSHI_HIP_WS_*
+WS_TSPEC, WS_Y, WS_TSPEC_LOW, WS_Y_LOW, WS_TNORM_REST = range(5)                            # SUSHI_HIP_WS_*
 BOUND_MODEL = {"worst_case": 0, "statistical": 1}                              # SUSHI_HIP_BOUND_*
 # every kernel a stage's HIP-event span covers (profiles/pmc_traffic.json is keyed by kernel)
-STAGE_KERNEL_SETS = {"tspec": ("tspec_kernel",), "mac": ("mac_kernel", "mac_long_kernel"),
+STAGE_KERNEL_SETS = {"tspec": ("tspec_real_kernel", "tspec_kernel"), "mac": ("mac_kernel", "mac_long_kernel"),
                      "ifft": ("ifft_kernel", "ifft_list_kernel", "pilot_kernel", "survivor_kernel", "mac_list_kernel", "mac_rows_kernel",
                               "bound_low_exact_kernel", "slb_list_kernel", "survivor2_kernel"),
                      "refine": ("refine_kernel",),

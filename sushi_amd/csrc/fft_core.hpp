@@ -391,6 +391,130 @@ SUSHI_HD void w_wg_load(cpx* v, int tid, const float* lds) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// Forward transform of a REAL, zero-padded pattern segment (tspec_real_kernel): half the transform of the complex route.
+//
+// The segment x[0 .. RN) (RN = 16384, samples from FFT_SEG = 4096 on zero) is packed as z[m] = x[2m] + i x[2m+1], m < RN/2, and
+// goes through ONE 8192-point complex transform Z = DFT(z): Plan<13> above, RNT = 512 threads x 16 points, of whose inputs only
+// m < 2048 are not zero.  With w = exp(-2 pi i / RN) the spectrum is unfolded from pairs of Z (indices mod RN/2):
+//     X[k]      = 1/2 (Z[k] + conj Z[RN/2-k]) - (i/2) w^k (Z[k] - conj Z[RN/2-k]),      X[RN-k] = conj X[k].
+// With E = Z[k] + conj Z[RN/2-k], O = Z[k] - conj Z[RN/2-k], T = (-i w^k) O:  2 X[k] = E + T and 2 X[RN/2-k] = conj(E - T) --
+// ONE butterfly gives four bins (the two and their mirrors), and the factor 1/2 goes into the scale the halves are stored with.
+//
+// Ownership.  A 16-byte entry of a stored spectrum holds four bins 1024 apart (mslot_of_bin): entry u of "row" f0 = bin mod 1024
+// holds the bins f0 + 1024 (4u + j), j < 4.  Rows a and b = 1024 - a unfold from each other -- k = a + 1024 d and RN/2 - k = b + 1024 (7 - d), d < 8 -- and
+// their bins 8 .. 15 are each other's mirrors.  So thread t owns TWO rows, a = real_row(t, 0) in [0, 512) and b = 1024 - a: it
+// takes Z[a + 1024 d] and Z[b + 1024 d], d < 8 (sixteen points), out of the LDS, makes eight butterflies (za[d], zb[7 - d]) ->
+// X[a + 1024 d], X[b + 1024 (7 - d)], and stores the eight 16-byte entries of the two rows: four as computed, four conjugated.
+//   * Thread 0 (a = 0, "b = 1024") is the same arithmetic: row 0 unfolds from itself, Z[1024 d] with Z[1024 (8 - d) mod 8192],
+//     which are the bins of a row 1024 taken mod RN/2 (its last, b + 7168 = RN/2, is Z[0] and gives X[RN/2]).  What it computes
+//     as "row b" are row 0's bins 1 .. 8 a second time; it stores row 0 alone, mirrored in ITSELF (bin 16 - d of bin d, bin 8 real),
+//     so that the row is conjugate-symmetric word for word.
+//   * Row 512 unfolds from itself too, Z[512 + 1024 d] with Z[512 + 1024 (7 - d)], and is nobody's partner: the TAIL, four
+//     butterflies made by lanes 0 .. 3 of the workgroup, one each (bins d, 7 - d and their mirrors 15 - d, 8 + d), stored word by word.
+// The twiddle w^k = w^a w16^d, w16 = exp(-2 pi i / 16): the table's entry of the thread's row (half an ulp a component), times an
+// exact 16th root whose product is folded into the butterfly's own multiply-adds (bfly_root32) -- one rounded complex product
+// (2 u with fused multiply-adds: Jeannerod, Kornerup, Louvet, Muller 2017) in front of the butterfly: w^a + 0.71 u, the root's
+// constants + 0.71 u, the product + 2 u: good to 3.5 u, inside the 4 u the tables are held to.  The tail takes w^k from the table
+// itself.  No sine or cosine is evaluated.
+//
+// The hand-over (the transform ends with thread t holding Z[t + 512 r]) goes through the transform's own buffer, real parts and
+// then imaginary parts: Z[e] at e + 2 (e >> 6), so that the 64 rows a wave reads (a = n1 + 16 d3 + 64 d2, d2 = 4 g + d2lo: lane =
+// 32 (n1 & 1) + 16 g + 4 d3 + d2lo, bank n1 + 16 d3 + 2 d2 mod 64) are 64 different banks.  It REPLACES the complex route's hand-over to the load order: the same barriers, half its floats.
+// ------------------------------------------------------------------------------------------------------------
+constexpr int RN = 16384, RLOGN = 13, RNT = Plan<RLOGN>::NT;
+static_assert(Plan<RLOGN>::N * 2 == RN && RNT * PER == Plan<RLOGN>::N, "the half-size plan");
+constexpr int REAL_TAIL_ROW = 512, REAL_TAIL_LANES = 4;
+// the two rows of thread t: side 0 in [0, 512), side 1 its partner (thread 0: 1024, no row).  A row a = n1 + 16 (4 d2 + d3) sits,
+// in every entry it has, at position m = 4 d3 + (d2 & 3) of a run of sixteen entries (mslot_of_bin): the lane's low four bits
+// are m, so that sixteen lanes store 256 consecutive bytes, whole 128-byte lines.
+SUSHI_HHD int real_row(int t, int side) {
+    const int m = t & 15, g = (t >> 4) & 1, n1 = t >> 5;
+    const int a = n1 + 64 * (4 * g + (m & 3)) + 16 * (m >> 2);
+    return side == 0 ? a : 1024 - a;
+}
+// index of entry u (bins row + 1024 (4u + j), j < 4) of a row, inside a stored spectrum: mslot_of_bin(row + 4096 u) / 4 -- spectra
+// are stored in the order the inverse transform's matrix-pipe first pass loads them
+SUSHI_HHD int real_entry(int row, int u) {
+    const int n1 = row & 15, d3 = (row >> 4) & 3, d2 = row >> 6;
+    return (((n1 * 4 + (d2 >> 2)) << 6) + 16 * ((u >> 1) | ((u & 1) << 1)) + ((d3 << 2) | (d2 & 3)));
+}
+// where Z[e] waits in the buffer
+SUSHI_HHD int real_zpos(int e) { return e + 2 * (e >> 6); }
+constexpr int REAL_ZSTEP = 1024 + 2 * (1024 >> 6);             // real_zpos(e + 1024) - real_zpos(e)
+static_assert(Plan<RLOGN>::N + 2 * (Plan<RLOGN>::N >> 6) <= Plan<RLOGN>::N + Plan<RLOGN>::N / 8, "the hand-over fits the transform's buffer");
+// the sample that is the real part of the thread's input register r (the imaginary part: the next one); below 4096 for r = 0, 1, 8, 9 only
+SUSHI_HHD int real_in_sample(int t, int r) { return 2 * (2 * t + (r / R1) + (Plan<RLOGN>::N / R1) * (r % R1)); }
+// the tail: lane l < REAL_TAIL_LANES takes Z[real_tail_z(l, 0)] and its partner Z[real_tail_z(l, 1)], twiddle table entry
+// real_tail_z(l, 0), and leaves bins l ("lo") and 7 - l ("hi") of row 512 and their mirrors, bins 15 - l and 8 + l
+SUSHI_HHD int real_tail_z(int l, int partner) { return REAL_TAIL_ROW + 1024 * (partner ? 7 - l : l); }
+// word index, inside a stored spectrum, of bin d of row 512
+SUSHI_HHD int real_tail_word(int d) { return 4 * real_entry(REAL_TAIL_ROW, d >> 2) + (d & 3); }
+
+template <int IM>
+SUSHI_HD void real_z_store(const cpx* v, int t, float* lds) {
+    float* out = lds + real_zpos(t);
+#pragma unroll
+    for (int r = 0; r < PER; ++r) out[(RNT + 2 * (RNT >> 6)) * r] = part_of<IM>(v[r]);      // real_zpos(t + 512 r)
+}
+template <int IM>
+SUSHI_HD void real_z_load(cpx* za, cpx* zb, int t, const float* lds) {
+    const float* ia = lds + real_zpos(real_row(t, 0));
+    const float* ib = lds + real_zpos(real_row(t, 1));
+    const float* ib7 = t == 0 ? lds : ib + REAL_ZSTEP * 7;                                    // (thread 0: Z[RN/2 mod RN/2])
+#pragma unroll
+    for (int d = 0; d < 8; ++d) {                                                             // real_zpos(row + 1024 d)
+        set_part<IM>(za[d], ia[REAL_ZSTEP * d]);
+        set_part<IM>(zb[d], d == 7 ? *ib7 : ib[REAL_ZSTEP * d]);
+    }
+}
+template <int IM>
+SUSHI_HD void real_tail_load(cpx& z, cpx& p, int l, const float* lds) {
+    set_part<IM>(z, lds[real_zpos(real_tail_z(l, 0))]);
+    set_part<IM>(p, lds[real_zpos(real_tail_z(l, 1))]);
+}
+// one butterfly: z = Z[k], p = Z[RN/2 - k], k = row + 1024 D, wmi = -i w^row  ->  lo = 2 X[k], hi = 2 X[RN/2 - k]
+template <int D>
+SUSHI_HD void real_bfly(const cpx z, const cpx p, const cpx wmi, cpx& lo, cpx& hi) {
+    const cpx e = cpx{z.x + p.x, z.y - p.y}, o = cpx{z.x - p.x, z.y + p.y};
+    cpx h;
+    bfly_root32<-1>(e, cmul(o, wmi), 2 * D, lo, h);
+    hi = cconj(h);
+}
+// The thread's sixteen bins, TWICE their values: xa[d] = 2 X[a + 1024 d], xb[d] = 2 X[b + 1024 d], d < 8 (thread 0:
+// xb[d] = 2 X[1024 (d + 1)], xb[7] = 2 X[RN/2]).  wa = the table's entry a = real_row(t, 0).
+SUSHI_HD void real_unfold(const cpx* za, const cpx* zb, int t, const cpx wa, cpx* xa, cpx* xb) {
+    const cpx wmi = cpx{wa.y, -wa.x};
+    real_bfly<0>(za[0], zb[7], wmi, xa[0], xb[7]);
+    real_bfly<1>(za[1], zb[6], wmi, xa[1], xb[6]);
+    real_bfly<2>(za[2], zb[5], wmi, xa[2], xb[5]);
+    real_bfly<3>(za[3], zb[4], wmi, xa[3], xb[4]);
+    real_bfly<4>(za[4], zb[3], wmi, xa[4], xb[3]);
+    real_bfly<5>(za[5], zb[2], wmi, xa[5], xb[2]);
+    real_bfly<6>(za[6], zb[1], wmi, xa[6], xb[1]);
+    real_bfly<7>(za[7], zb[0], wmi, xa[7], xb[0]);
+    if (t == 0) { xa[0].y = 0.f; xb[7].y = 0.f; }        // (bins 0 and RN/2 are real: Z[0] with itself; no signed zero is left to the mirror's rule)
+}
+// the tail's butterfly: the twiddle w = w^k as the table holds it  ->  lo = 2 X[k], hi = 2 X[RN/2 - k]
+SUSHI_HD void real_tail_bfly(const cpx z, const cpx p, const cpx w, cpx& lo, cpx& hi) {
+    const cpx e = cpx{z.x + p.x, z.y - p.y}, o = cpx{z.x - p.x, z.y + p.y};
+    const cpx tt = cmul(o, cpx{w.y, -w.x});
+    lo = cadd(e, tt);
+    hi = cconj(csub(e, tt));
+}
+// The stored words of bins 8 .. 15 of the thread's two rows from the words of its bins 0 .. 7 (wa[d], wb[d]: rows a / b):
+// mirrors -- X[RN - k] = conj X[k]: the word with the sign of its imaginary half flipped; a ZERO imaginary half is kept as it is,
+// so that a row of zeros is zero words throughout -- of the OTHER row's bins 7 .. 0.
+// Thread 0: row 0's bin 8 is wb[7] as it is and its bins 9 .. 15 mirror its OWN bins 7 .. 1; its mb is no row's.
+SUSHI_HHD unsigned real_conj_word(unsigned w) { return w ^ (((w & 0x7fff0000u) + 0x7fff0000u) & 0x80000000u); }
+SUSHI_HD void real_mirror_words(const unsigned* wa, const unsigned* wb, int t, unsigned* ma, unsigned* mb) {
+#pragma unroll
+    for (int d = 0; d < 8; ++d) {
+        ma[d] = t != 0 ? real_conj_word(wb[7 - d]) : (d == 0 ? wb[7] : real_conj_word(wa[8 - d]));
+        mb[d] = real_conj_word(wa[7 - d]);
+    }
+}
+
 #ifdef __HIPCC__
 struct NoHook { __device__ __forceinline__ void operator()() const {} };
 

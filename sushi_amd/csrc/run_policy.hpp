@@ -12,6 +12,7 @@
 //   pilot_rows_route, pilot_rows_by_search                how the band-split form's pilots get their whole rows
 //   rest_rows_route, rest_rows_by_item                    the unit of work of the survivors' pass behind them
 //   rest_pair_to_form, rest_item_starts, rest_item_take   how a search's surviving pairs are cut into that pass's work items
+//   tspec_route, tspec_real                               which transform the pattern segments' spectra come from
 //                                                         (the three the device calls as well: SUSHI_HHD)
 //   begin_run, report_last_run    what a handle remembers of a run, what each run kind reports
 #ifndef SUSHI_RUN_POLICY_HPP
@@ -193,6 +194,18 @@ SUSHI_HHD unsigned long long rest_item_take(unsigned long long form, int room) {
     for (unsigned long long m = form; m && room > 0; m &= m - 1, --room) take |= m & (~m + 1);
     return take;
 }
+
+// Which transform tspec_kernel's rows come from.  REAL (the default): a segment is real input -- packed into half as many complex
+// points, one half-size transform, unfolded (fft_core.hpp; tspec_real_kernel).  COMPLEX: the full-size complex transform with zero
+// imaginary parts, as before the real route existed; kept for A/B measurements on one build.  Both leave every buffer in the same
+// place and format; stored halves may differ in their last bit.  `setting` is SUSHI_HIP_TSPEC as the environment holds it (NULL
+// or empty: the default); -1: neither route's name.
+enum { TSPEC_REAL = 0, TSPEC_COMPLEX = 1 };
+inline int tspec_route(const char* setting) {
+    if (!setting || !*setting || !strcmp(setting, "real")) return TSPEC_REAL;
+    return !strcmp(setting, "complex") ? TSPEC_COMPLEX : -1;
+}
+inline bool tspec_real(int route) { return route != TSPEC_COMPLEX; }
 
 // What a handle notes when a run of `kind` starts: run_form fills in the cut and the suspension of an argmin run, the sub-batches
 // that go through the exclusion its form and those that do not their pairs.

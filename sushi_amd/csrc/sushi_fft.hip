@@ -11,8 +11,10 @@
 //   spectra_kernel   once per destination stream, for every block j (hop B):
 //                    Z_j = DFT_N( x[jB .. jB+N) + i * x[jB+H .. jB+H+N) )
 //                    (+ the low band of Z_j once more and its norms outside the band: the band-split exclusion below)
-//   tspec_kernel     per search, per pattern segment s (B samples, zero padded to N):
+//   tspec_real_kernel  per search, per pattern segment s (B samples, zero padded to N):
 //                    Tt_s = conj(DFT_N(t_s)) / N                                  (+ its low band and its norm outside the band)
+//                    -- t_s is real: packed into N/2 complex points, one N/2-point transform, unfolded (fft_core.hpp);
+//                    tspec_kernel (SUSHI_HIP_TSPEC=complex) is the N-point complex transform it replaced, kept for A/B
 //   mac_kernel       per search, per frequency bin f, per pair I of the absolute pair grid (pair I starts at
 //                    block FFT_STEP * I, FFT_STEP = 2H / B):
 //                    Y_I(f) = sum_s Tt_s(f) * Z_{FFT_STEP*I+s}(f)       (a 1-D Toeplitz product along j)
@@ -52,7 +54,7 @@
 //   run_policy.hpp         (a header: host only, checked on the CPU by tests/host_policy_check.cpp) what a run decides from the
 //                          exclusion mode and from what earlier runs left: Learnt, LastRun, one function per rule
 //   sushi_fft_store.inc    packed-half storage: scales, stored bin order, the low band of a row and the norms outside it
-//   sushi_fft_spectra.inc  spectra_kernel, tspec_kernel
+//   sushi_fft_spectra.inc  spectra_kernel, tspec_real_kernel / tspec_kernel
 //   sushi_fft_mac.inc      mac_kernel / mac_long_kernel / mac_list_kernel
 //   sushi_fft_ifft.inc     ifft_kernel / ifft_list_kernel: transform, scoring epilogue, error model, candidates
 //   sushi_fft_bound.inc    the pair exclusion: bound_kernel / bound_low_kernel / slb_kernel / pilot / survivor / second look / mac_rows_kernel;
@@ -170,6 +172,7 @@ struct SushiHipBatch {
     int audit_every = 2;                // one search in this many has one excluded pair transformed as a check, per run
     int pilot_rows = PILOT_ROWS_BY_SEARCH;  // how the pilots' whole rows are formed (run_policy.hpp; SUSHI_HIP_PILOT_ROWS=list: pair by pair, for A/B)
     int rest_rows = REST_ROWS_BY_ITEM;      // the survivors' pass's unit of work (run_policy.hpp; SUSHI_HIP_REST_ROWS=search: a whole search, for A/B)
+    int tspec = TSPEC_REAL;                 // the pattern segments' transform (run_policy.hpp; SUSHI_HIP_TSPEC=complex: the full-size complex one, for A/B)
     int bound_model = SUSHI_HIP_BOUND_WORST_CASE;   // (default) / SUSHI_HIP_BOUND_STATISTICAL: how the excluded side's roundings enter slb
     BoundFault fault;                   // the tests' seam (SUSHI_HIP_TEST_BOUND_FAULT; period 0, the default: none)
     // AUTO learns from its own runs (Learnt): the last run's counts come back through 16 bytes of pinned host memory behind an
@@ -337,8 +340,11 @@ static int stage_tspec(const RunCtx& c, const SubView& v, hipStream_t st) {
     ta.tspec = v.tspec; ta.sub_first_pair = v.sb.first_pair; ta.pairmap = v.pairmap; ta.tconst = v.tconst;
     ta.src_s1 = c.src->s1; ta.src_s2 = c.src->s2; ta.centre = c.r.centre; ta.dst_stats = c.dst->stats; ta.method = c.method;
     ta.tspec_low = v.tspec_low; ta.tnorm_rest = v.tnorm_rest;
+    const bool real = tspec_real(c.b->tspec);
     if (launch_dtype(c.src->dtype, [&](auto t) {
-            hipLaunchKernelGGL(tspec_kernel<std::remove_pointer_t<decltype(t)>>, dim3((unsigned)v.sb.segs), dim3(FT), 0, st, ta); }) != SUSHI_HIP_OK)
+            typedef std::remove_pointer_t<decltype(t)> S;
+            if (real) hipLaunchKernelGGL(tspec_real_kernel<S>, dim3((unsigned)v.sb.segs), dim3(RT), 0, st, ta);
+            else hipLaunchKernelGGL(tspec_kernel<S>, dim3((unsigned)v.sb.segs), dim3(FT), 0, st, ta); }) != SUSHI_HIP_OK)
         return SUSHI_HIP_ELAUNCH;
     prof_end(c.pc, t0, SUSHI_HIP_STAGE_TSPEC, st);
     return SUSHI_HIP_OK;
@@ -904,6 +910,7 @@ int sushi_hip_batch_create(const SushiHipStream* dst, const SushiHipStream* src,
     // (a value that is neither route is refused: a typo must not turn an A/B measurement into an A/A one)
     if ((b->pilot_rows = pilot_rows_route(getenv("SUSHI_HIP_PILOT_ROWS"))) < 0) return SUSHI_HIP_EINVAL;
     if ((b->rest_rows = rest_rows_route(getenv("SUSHI_HIP_REST_ROWS"))) < 0) return SUSHI_HIP_EINVAL;
+    if ((b->tspec = tspec_route(getenv("SUSHI_HIP_TSPEC"))) < 0) return SUSHI_HIP_EINVAL;
     const char* m = getenv("SUSHI_HIP_BOUND_MODEL");
     if (m && !strcmp(m, "statistical")) b->bound_model = SUSHI_HIP_BOUND_STATISTICAL;
     // (the tests' seam, DESIGN.md 3.2: a value that does not parse is refused -- a typo must not turn a fault test into a no-fault test)
@@ -1103,6 +1110,7 @@ int sushi_hip_batch_workspace_view(SushiHipBatch* b, int which, void** ptr_dev, 
         case SUSHI_HIP_WS_Y: *ptr_dev = v.y; *bytes = (size_t)v.sb.pairs * ROW_BYTES; break;
         case SUSHI_HIP_WS_TSPEC_LOW: *ptr_dev = v.tspec_low; *bytes = (size_t)v.sb.segs * LROW_BYTES; break;
         case SUSHI_HIP_WS_Y_LOW: *ptr_dev = v.ylow; *bytes = (size_t)v.sb.pairs * LROW_BYTES; break;
+        case SUSHI_HIP_WS_TNORM_REST: *ptr_dev = v.tnorm_rest; *bytes = (size_t)v.sb.segs * sizeof(float); break;
         default: return SUSHI_HIP_EINVAL;
     }
     return SUSHI_HIP_OK;

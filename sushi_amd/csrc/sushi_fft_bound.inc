@@ -345,7 +345,9 @@ __device__ __forceinline__ void slb_one(const BoundArgs& a, const int pr, const 
             //      <= c |T| sqrt(sum_s |z_s|^2) <= c |T| sqrt(8) zn_c
             // (every sample of the pair's span of n_seg + 6 blocks enters at most four block spectra as a first and four as a second
             // half).  e_F = 1e-5 >= 14 (mu + g_4 (sqrt 2 + mu)): the float32 forward transforms' relative error in the 2-norm (Higham,
-            // Accuracy and Stability of Numerical Algorithms, Thm 24.2, log2 N = 14 radix-2 levels, twiddles good to 4 u);
+            // Accuracy and Stability of Numerical Algorithms, Thm 24.2, log2 N = 14 radix-2 levels, twiddles good to 4 u: 8.06e-6;
+            // the pattern rows' real-input route is 13 such levels, one rounded addition and one more such level -- its unfold --:
+            // 14 (...) + u = 8.12e-6, DESIGN.md 3.3);
             // g <= 2e-5: mac_kernel's float32 sums.  The same terms cover what the NORMS of the stored rows outside the band differ
             // from the exact rows' by, and what the stored pattern rows lack of conjugate symmetry.  The halves' subnormal floor
             // (2^-25 absolute per stored value, N bins a row): of the pattern rows < 1.3e-9 sqrt(n_seg) |T| zn_c (inside c), of the block

@@ -72,12 +72,16 @@ struct TspecArgs {
     float* tnorm_rest;                // [segments of the sub-batch] SQUARED norm of the stored halves outside the band (accumulated: zero it first)
 };
 
-template <typename T>
-__global__ __launch_bounds__(FT, 8)        // (64 VGPRs: two workgroups of sixteen waves per CU -- at 69 only one fits, 1.15 -> 1.6 ms)
-void tspec_kernel(TspecArgs a) {
-    __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
-    const int tid = threadIdx.x;
-    const sushi_fft::Twiddles tw = sushi_fft::load_twiddles<FFT_LOGN, -1>(tid, twiddles());
+// What both routes of the kernel do first: find the segment's search, take the pattern's statistics and scales, and -- the
+// workgroup of a search's first segment -- write the search's constants and its pairs' map.  NT: the workgroup's threads.
+struct TspecSeg {
+    int64_t off;                      // the segment's first sample in the source stream
+    int len;                          // its samples (1 .. FFT_SEG)
+    float t_sub;                      // what is subtracted from every sample (TM_CCOEFF_NORMED: the pattern's mean)
+    float sc;                         // t_scale / N
+};
+template <int NT>
+__device__ __forceinline__ TspecSeg tspec_segment(const TspecArgs& a, const int tid) {
     const int seg = a.sub_first_seg + blockIdx.x;
     const int k = find_search_by_seg(a.searches, a.n_sub, seg);
     const SearchDesc sd = a.searches[k];
@@ -89,13 +93,12 @@ void tspec_kernel(TspecArgs a) {
     // scales are sized by -- is the centred pattern's norm.  (A pattern without variance is answered without its spectra.)
     const bool cc = a.method == SUSHI_HIP_METHOD_CCOEFF_NORMED;
     const double tn_spec = cc && !ts_all.flat ? ts_all.tnorm_c : ts_all.tnorm;
-    const float t_sub = cc ? (float)ts_all.tmean : 0.f;
     const float y_scale = y_scale_for(tn_spec, (M + FFT_SEG - 1) / FFT_SEG, a.dst_stats[0]);
     const float t_scale = t_scale_for(tn_spec);
     if (s == 0) {
         const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, M);
         int* __restrict__ pm = a.pairmap + first_pair_in_sub(a.sub_first_pair, sd);
-        for (int i = tid; i < lay.n_pairs; i += FT) pm[i] = k;
+        for (int i = tid; i < lay.n_pairs; i += NT) pm[i] = k;
         if (tid == 0) {
             const TemplStats ts = templ_stats(a.src_s1, a.src_s2, sd.tmpl_off, M, a.centre);
             TemplConsts tc;
@@ -108,8 +111,26 @@ void tspec_kernel(TspecArgs a) {
             a.tconst[k] = tc;
         }
     }
-    const T* __restrict__ t = (const T*)a.src_raw + sd.tmpl_off + (int64_t)s * FFT_SEG;
-    const int len = min(FFT_SEG, M - s * FFT_SEG);
+    TspecSeg g;
+    g.off = sd.tmpl_off + (int64_t)s * FFT_SEG;
+    g.len = min(FFT_SEG, M - s * FFT_SEG);
+    g.t_sub = cc ? (float)ts_all.tmean : 0.f;
+    g.sc = t_scale / (float)FN;
+    return g;
+}
+
+// The complex route (SUSHI_HIP_TSPEC=complex; the route of every run before the real one existed, kept for A/B measurements on
+// one build): the zero-padded segment through a full 16384-point complex transform whose imaginary inputs are all zero.
+template <typename T>
+__global__ __launch_bounds__(FT, 8)        // (64 VGPRs: two workgroups of sixteen waves per CU -- at 69 only one fits, 1.15 -> 1.6 ms)
+void tspec_kernel(TspecArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
+    const int tid = threadIdx.x;
+    const sushi_fft::Twiddles tw = sushi_fft::load_twiddles<FFT_LOGN, -1>(tid, twiddles());
+    const TspecSeg g = tspec_segment<FT>(a, tid);
+    const T* __restrict__ t = (const T*)a.src_raw + g.off;
+    const int len = g.len;
+    const float t_sub = g.t_sub;
     cpx v[sushi_fft::PER];
 #pragma unroll
     for (int r = 0; r < sushi_fft::PER; ++r) {
@@ -119,7 +140,7 @@ void tspec_kernel(TspecArgs a) {
         v[r].y = 0.f;
     }
     sushi_fft::fft_split<FFT_LOGN, -1>(v, tid, lds, tw);
-    const float sc = t_scale / (float)FN;
+    const float sc = g.sc;
     // The low entry straight to its place (sixteen half-written lines per wave, all completed by this workgroup within
     // microseconds) and the wave's share of the norm's SQUARE to the segment's accumulator (zeroed before the launch; slb_kernel
     // takes the root): staging both through the LDS, as spectra_kernel does once per stream, cost this kernel -- which runs every
@@ -137,4 +158,115 @@ void tspec_kernel(TspecArgs a) {
     for (int u = 0; u < sushi_fft::PER / 4; ++u)
         out[sushi_fft::wslot_uint4(tid, u)] = uint4{pack_h2(v[4 * u].x * sc, v[4 * u].y * sc), pack_h2(v[4 * u + 1].x * sc, v[4 * u + 1].y * sc),
                                                     pack_h2(v[4 * u + 2].x * sc, v[4 * u + 2].y * sc), pack_h2(v[4 * u + 3].x * sc, v[4 * u + 3].y * sc)};
+}
+
+// The real route (the default): the segment is real, so it is packed into HALF as many complex points, transformed by the
+// 8192-point plan and unfolded (fft_core.hpp "Forward transform of a REAL, zero-padded pattern segment").  512 threads a segment,
+// half the buffer: four workgroups of eight waves per CU, the complex route's residency.  Everything the kernel leaves has the
+// complex route's place and meaning; a row's bins N - k are now the conjugates of its bins k word for word.
+constexpr int RT = sushi_fft::RNT;
+constexpr int RLDS_FLOATS = sushi_fft::lds_floats<sushi_fft::RLOGN>();
+static_assert(2 * RT == FT && 2 * RLDS_FLOATS == LDS_FLOATS && sushi_fft::RN == FN && FFT_SEG * 4 == FN, "the real route's halves");
+template <typename T>
+__global__ __launch_bounds__(RT, 8)        // (64 VGPRs, as the complex route)
+void tspec_real_kernel(TspecArgs a) {
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    __shared__ __attribute__((aligned(16))) float lds[RLDS_FLOATS];
+    const int tid = threadIdx.x;
+    const sushi_fft::Twiddles tw = sushi_fft::load_twiddles<sushi_fft::RLOGN, -1>(tid, twiddles());
+    const cpx wrow = twiddles()[sushi_fft::real_row(tid, 0)];
+    const TspecSeg g = tspec_segment<RT>(a, tid);
+    const T* __restrict__ t = (const T*)a.src_raw + g.off;
+    const int len = g.len;
+    const float t_sub = g.t_sub;
+    cpx v[sushi_fft::PER];
+#pragma unroll
+    for (int r = 0; r < sushi_fft::PER; ++r) {
+        // z[m] = x[2m] + i x[2m+1]; the registers whose samples lie past FFT_SEG (all but r = 0, 1, 8, 9: real_in_sample) are
+        // zero as they stand
+        const int e = sushi_fft::real_in_sample(tid, r);
+        if ((r % sushi_fft::R1) < 2) {
+            const float xa = (float)t[e < len ? e : len - 1] - t_sub;
+            const float xb = (float)t[e + 1 < len ? e + 1 : len - 1] - t_sub;
+            v[r].x = e < len ? xa : 0.f;
+            v[r].y = e + 1 < len ? xb : 0.f;
+        } else {
+            v[r] = cpx{0.f, 0.f};
+        }
+    }
+    sushi_fft::fft_split<sushi_fft::RLOGN, -1>(v, tid, lds, tw);
+    // the hand-over: thread tid holds Z[tid + 512 r]; it takes the sixteen Z of its two rows, the tail's lanes their two of row 512 besides
+    const bool tail = tid < sushi_fft::REAL_TAIL_LANES;
+    cpx za[8], zb[8], tz = cpx{0.f, 0.f}, tp = cpx{0.f, 0.f}, tw_tail = cpx{0.f, 0.f};
+    __syncthreads();                                             // the transform's own use of the buffer is over
+    sushi_fft::real_z_store<0>(v, tid, lds);
+    __syncthreads();
+    sushi_fft::real_z_load<0>(za, zb, tid, lds);
+    if (tail) {
+        sushi_fft::real_tail_load<0>(tz, tp, tid, lds);
+        tw_tail = twiddles()[sushi_fft::real_tail_z(tid, 0)];
+    }
+    __syncthreads();
+    sushi_fft::real_z_store<1>(v, tid, lds);
+    __syncthreads();
+    sushi_fft::real_z_load<1>(za, zb, tid, lds);
+    const float sc = 0.5f * g.sc;                                // (the unfold leaves twice the bins)
+    uint32_t* __restrict__ row_words = a.tspec + (size_t)blockIdx.x * FN;
+    uint4* __restrict__ low = a.tspec_low + (size_t)blockIdx.x * LROWE;
+    auto abs2 = [](const unsigned w, const float acc) {
+        const h2 h = __builtin_bit_cast(h2, w);
+        return __builtin_amdgcn_fdot2(h, h, acc, false);
+    };
+    // The norm's square outside the band (bins 2 .. 13 of a row; row 0's bin 14, 7N/8, is counted with them and zero in its low
+    // entry: low_entry_and_rest): a mirror has its bin's modulus exactly, so a thread's share is twice its own bins 2 .. 7 of
+    // both rows -- thread 0: of row 0, and bin N/2 once.
+    float e = 0.f;
+    if (tail) {                                                  // row 512: bins tid, 7 - tid and their mirrors 15 - tid, 8 + tid, word by word
+        sushi_fft::real_tail_load<1>(tz, tp, tid, lds);
+        cpx lo, hi;
+        sushi_fft::real_tail_bfly(tz, tp, tw_tail, lo, hi);
+        const unsigned wlo = pack_h2(__builtin_fmaf(lo.x, sc, 0.f), __builtin_fmaf(lo.y, sc, 0.f));
+        const unsigned whi = pack_h2(__builtin_fmaf(hi.x, sc, 0.f), __builtin_fmaf(hi.y, sc, 0.f));
+        row_words[sushi_fft::real_tail_word(tid)] = wlo;
+        row_words[sushi_fft::real_tail_word(7 - tid)] = whi;
+        row_words[sushi_fft::real_tail_word(8 + tid)] = sushi_fft::real_conj_word(whi);
+        row_words[sushi_fft::real_tail_word(15 - tid)] = sushi_fft::real_conj_word(wlo);
+        uint32_t* __restrict__ lw = reinterpret_cast<uint32_t*>(low + sushi_fft::lslot_of_thread(sushi_fft::REAL_TAIL_ROW));
+        if (tid < 2) { lw[tid] = wlo; lw[3 - tid] = sushi_fft::real_conj_word(wlo); }       // bins 0, 1, 14, 15: the band
+        e = abs2(whi, tid < 2 ? 0.f : abs2(wlo, 0.f));
+    }
+    cpx xa[8], xb[8];
+    sushi_fft::real_unfold(za, zb, tid, wrow, xa, xb);
+    unsigned wa[8], wb[8], ma[8], mb[8];
+#pragma unroll
+    for (int d = 0; d < 8; ++d) {                                // (+ 0: a zero is stored as +0 whatever sign the arithmetic left it)
+        wa[d] = pack_h2(__builtin_fmaf(xa[d].x, sc, 0.f), __builtin_fmaf(xa[d].y, sc, 0.f));
+        wb[d] = pack_h2(__builtin_fmaf(xb[d].x, sc, 0.f), __builtin_fmaf(xb[d].y, sc, 0.f));
+    }
+    sushi_fft::real_mirror_words(wa, wb, tid, ma, mb);
+    const int ra = sushi_fft::real_row(tid, 0), rb = sushi_fft::real_row(tid, 1);
+    {
+        float eb = 0.f;
+#pragma unroll
+        for (int d = 2; d < 8; ++d) { e = abs2(wa[d], e); eb = abs2(wb[d], eb); }
+        e = 2.f * (e + (tid == 0 ? 0.f : eb));
+        if (tid == 0) e = abs2(wb[7], e);
+        // the low entries (bins 0, 1, 14, 15 of a row) straight to their places and the wave's share of the norm's square to the
+        // segment's accumulator (zeroed before the launch), as the complex route does
+        low[sushi_fft::lslot_of_thread(ra)] = uint4{wa[0], wa[1], tid == 0 ? 0u : ma[6], ma[7]};
+        if (tid != 0) low[sushi_fft::lslot_of_thread(rb)] = uint4{wb[0], wb[1], mb[6], mb[7]};
+        const float w = wave_sum_shfl(e);
+        if ((tid & 63) == 0) atomicAdd(a.tnorm_rest + blockIdx.x, w);
+    }
+    uint4* __restrict__ out = reinterpret_cast<uint4*>(row_words);
+    out[sushi_fft::real_entry(ra, 0)] = uint4{wa[0], wa[1], wa[2], wa[3]};
+    out[sushi_fft::real_entry(ra, 1)] = uint4{wa[4], wa[5], wa[6], wa[7]};
+    out[sushi_fft::real_entry(ra, 2)] = uint4{ma[0], ma[1], ma[2], ma[3]};
+    out[sushi_fft::real_entry(ra, 3)] = uint4{ma[4], ma[5], ma[6], ma[7]};
+    if (tid != 0) {
+        out[sushi_fft::real_entry(rb, 0)] = uint4{wb[0], wb[1], wb[2], wb[3]};
+        out[sushi_fft::real_entry(rb, 1)] = uint4{wb[4], wb[5], wb[6], wb[7]};
+        out[sushi_fft::real_entry(rb, 2)] = uint4{mb[0], mb[1], mb[2], mb[3]};
+        out[sushi_fft::real_entry(rb, 3)] = uint4{mb[4], mb[5], mb[6], mb[7]};
+    }
 }
