@@ -315,12 +315,18 @@ SUSHI_HIP_API int sushi_hip_batch_pair_bounds(SushiHipBatch* batch, float* slb_h
  * (packed halves, 4 bytes per bin, bin f of a whole row at sushi_hip_fft_slot_of_bin(f), of a low row at
  * sushi_hip_fft_low_slot_of_bin(f)): TSPEC [segments][N], Y [block pairs][N] -- whole rows exist only for the pairs that were
  * transformed --, TSPEC_LOW [segments][N/4], Y_LOW [block pairs][N/4] (band-split form only).  Synchronises; the memory is the
- * caller's own batch buffer, valid until the next run. */
+ * caller's own batch buffer, valid until the next run.
+ * The real route of the pattern transform (the default; SUSHI_HIP_TSPEC) STORES half rows: TSPEC is then a whole-row copy made on
+ * request, in a buffer the batch allocates at the first request and frees with itself (ENOMEM: it could not), valid until the next
+ * request or run; TSPEC_HALF is what is stored, [segments][N/2 + 64] words -- the entries whose index has bit 4 clear, in order, then
+ * a run of sixteen entries whose first two are the conj-reversals of row 0's entries 3 and 2.  EINVAL under SUSHI_HIP_TSPEC=complex,
+ * whose rows are stored whole. */
 #define SUSHI_HIP_WS_TSPEC 0
 #define SUSHI_HIP_WS_Y 1
 #define SUSHI_HIP_WS_TSPEC_LOW 2
 #define SUSHI_HIP_WS_Y_LOW 3
 #define SUSHI_HIP_WS_TNORM_REST 4   /* float32 per pattern segment: the SQUARED norm of its stored halves outside the band */
+#define SUSHI_HIP_WS_TSPEC_HALF 5
 SUSHI_HIP_API int sushi_hip_batch_workspace_view(SushiHipBatch* batch, int which, void** ptr_dev, size_t* bytes);
 SUSHI_HIP_API void sushi_hip_batch_destroy(SushiHipBatch* batch);
 

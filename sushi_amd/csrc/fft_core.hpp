@@ -515,6 +515,65 @@ SUSHI_HD void real_mirror_words(const unsigned* wa, const unsigned* wb, int t, u
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// HALF ROWS: what the real route stores of a pattern segment's spectrum.  The stored word of bin RN - k is real_conj_word of the
+// stored word of bin k, so the entries u >= 2 of a row (bins 8 .. 15 of it: exactly the entries whose index has bit 4 set, every
+// other run of sixteen) need not exist: for f0 != 0
+//     entry (f0, u >= 2)  =  conj-reversal of entry (1024 - f0, 3 - u)       (its four words reversed, each through real_conj_word)
+// -- bin f0 + 1024 (4u + j) mirrors bin (1024 - f0) + 1024 (4 (3 - u) + 3 - j); row 512 is its own partner.  Row 0 mirrors in
+// itself shifted by one bin -- entry (0, 2) = {X[RN/2], conj X[7168], conj X[6144], conj X[5120]}, (0, 3) = {conj X[4096] ..
+// conj X[1024]} -- which is no single stored entry's reversal, and X[RN/2] is in no stored entry at all: their conj-reversals,
+// {X[1024] .. X[4096]} and {X[5120], X[6144], X[7168], X[RN/2]}, are kept as entries 0 and 1 of a ROW 1024 that only exists
+// here (real_conj_word is an involution, its zero-imaginary rule included, so reversing them again gives the words back).  With
+// that row the one rule above holds for every f0.
+// A half row: the 2048 entries u < 2 in the whole row's order with the upper runs taken out (index bit 4 dropped), then one run
+// of sixteen entries whose first two are row 1024's -- HALF_ROWE entries, runs of sixteen still 256-byte aligned.
+// ------------------------------------------------------------------------------------------------------------
+constexpr int HALF_STORED = RN / 8;                // the stored entries u < 2 of a half row
+constexpr int HALF_ROWE = HALF_STORED + 16;        // ... and the run that holds row 1024's two
+// full-row index (u < 2: bit 4 clear) <-> its place in a half row
+SUSHI_HHD int half_index(int e) { return ((e >> 5) << 4) | (e & 15); }
+SUSHI_HHD int half_to_full(int h) { return ((h >> 4) << 5) | (h & 15); }
+// place of entry u < 2 of row 0 .. 1024 in a half row
+SUSHI_HHD int half_entry(int row, int u) { return row == 1024 ? HALF_STORED + u : half_index(real_entry(row, u)); }
+// word index, inside a half row, of bin d < 8 of row 512
+SUSHI_HHD int half_tail_word(int d) { return 4 * half_entry(REAL_TAIL_ROW, d >> 2) + (d & 3); }
+// the row and u of a full-row index (real_entry's inverse)
+SUSHI_HHD void real_entry_row(int e, int* row, int* u) {
+    const int n1 = e >> 8, g = (e >> 6) & 3, q = (e >> 4) & 3, m = e & 15;
+    *u = (q >> 1) | ((q & 1) << 1);
+    *row = n1 + 16 * (m >> 2) + 64 * (4 * g + (m & 3));
+}
+// where the words of full-row entry e come from: a place in the half row, and whether they are its conj-reversal
+struct HalfSource { int index; bool conjrev; };
+SUSHI_HHD HalfSource half_source(int e) {
+    if ((e & 16) == 0) return HalfSource{half_index(e), false};
+    int row, u;
+    real_entry_row(e, &row, &u);
+    return HalfSource{half_entry(1024 - row, 3 - u), true};
+}
+// the full-row entry that is the conj-reversal of stored entry h < HALF_STORED of a half row -- (row, u) -> (1024 - row mod 1024, 3 - u);
+// row 0's two take their pattern words for it from row 1024's entries (half_entry(1024, u)), everyone else from themselves
+SUSHI_HHD int half_mirror_of(int h) {
+    int row, u;
+    real_entry_row(half_to_full(h), &row, &u);
+    return real_entry((1024 - row) & 1023, 3 - u);
+}
+// the conj-reversal of an entry (E: four 32-bit words x, y, z, w)
+template <class E>
+SUSHI_HHD E real_conjrev(const E v) {
+    E r = v;
+    r.x = real_conj_word(v.w); r.y = real_conj_word(v.z); r.z = real_conj_word(v.y); r.w = real_conj_word(v.x);
+    return r;
+}
+// the words of full-row entry e, from a half row
+template <class E>
+SUSHI_HHD E half_fetch(const E* half_row, int e) {
+    const HalfSource s = half_source(e);
+    const E v = half_row[s.index];
+    return s.conjrev ? real_conjrev(v) : v;
+}
+
 #ifdef __HIPCC__
 struct NoHook { __device__ __forceinline__ void operator()() const {} };
 

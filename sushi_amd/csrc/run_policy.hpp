@@ -197,8 +197,8 @@ SUSHI_HHD unsigned long long rest_item_take(unsigned long long form, int room) {
 
 // Which transform tspec_kernel's rows come from.  REAL (the default): a segment is real input -- packed into half as many complex
 // points, one half-size transform, unfolded (fft_core.hpp; tspec_real_kernel).  COMPLEX: the full-size complex transform with zero
-// imaginary parts, as before the real route existed; kept for A/B measurements on one build.  Both leave every buffer in the same
-// place and format; stored halves may differ in their last bit.  `setting` is SUSHI_HIP_TSPEC as the environment holds it (NULL
+// imaginary parts, as before the real route existed; kept for A/B measurements on one build.  Both leave the low rows and norms in
+// the same place and format (the whole rows: tspec_half_rows below); stored halves may differ in their last bit.  `setting` is SUSHI_HIP_TSPEC as the environment holds it (NULL
 // or empty: the default); -1: neither route's name.
 enum { TSPEC_REAL = 0, TSPEC_COMPLEX = 1 };
 inline int tspec_route(const char* setting) {
@@ -206,6 +206,10 @@ inline int tspec_route(const char* setting) {
     return !strcmp(setting, "complex") ? TSPEC_COMPLEX : -1;
 }
 inline bool tspec_real(int route) { return route != TSPEC_COMPLEX; }
+// The stored format of the whole pattern rows belongs to the route.  The real route's rows are conjugate-symmetric word for word,
+// so it stores HALF rows (fft_core.hpp "HALF ROWS") and every reader derives the other half; the complex route's are symmetric
+// only up to their last bit and stay whole rows, read as they always were.
+inline bool tspec_half_rows(int route) { return tspec_real(route); }
 
 // What a handle notes when a run of `kind` starts: run_form fills in the cut and the suspension of an argmin run, the sub-batches
 // that go through the exclusion its form and those that do not their pairs.

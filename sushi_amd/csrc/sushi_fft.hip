@@ -13,7 +13,8 @@
 //                    (+ the low band of Z_j once more and its norms outside the band: the band-split exclusion below)
 //   tspec_real_kernel  per search, per pattern segment s (B samples, zero padded to N):
 //                    Tt_s = conj(DFT_N(t_s)) / N                                  (+ its low band and its norm outside the band)
-//                    -- t_s is real: packed into N/2 complex points, one N/2-point transform, unfolded (fft_core.hpp);
+//                    -- t_s is real: packed into N/2 complex points, one N/2-point transform, unfolded (fft_core.hpp); its
+//                    whole rows are conjugate-symmetric word for word and stored as HALF rows, which every reader expands;
 //                    tspec_kernel (SUSHI_HIP_TSPEC=complex) is the N-point complex transform it replaced, kept for A/B
 //   mac_kernel       per search, per frequency bin f, per pair I of the absolute pair grid (pair I starts at
 //                    block FFT_STEP * I, FFT_STEP = 2H / B):
@@ -54,7 +55,7 @@
 //   run_policy.hpp         (a header: host only, checked on the CPU by tests/host_policy_check.cpp) what a run decides from the
 //                          exclusion mode and from what earlier runs left: Learnt, LastRun, one function per rule
 //   sushi_fft_store.inc    packed-half storage: scales, stored bin order, the low band of a row and the norms outside it
-//   sushi_fft_spectra.inc  spectra_kernel, tspec_real_kernel / tspec_kernel
+//   sushi_fft_spectra.inc  spectra_kernel, tspec_real_kernel / tspec_kernel, tspec_expand_kernel (half rows -> whole rows, for the workspace view)
 //   sushi_fft_mac.inc      mac_kernel / mac_long_kernel / mac_list_kernel
 //   sushi_fft_ifft.inc     ifft_kernel / ifft_list_kernel: transform, scoring epilogue, error model, candidates
 //   sushi_fft_bound.inc    the pair exclusion: bound_kernel / bound_low_kernel / slb_kernel / pilot / survivor / second look / mac_rows_kernel;
@@ -196,6 +197,9 @@ struct SushiHipBatch {
     hipStream_t lane_stream[MAX_LANES] = {};
     hipEvent_t lane_done[MAX_LANES] = {};
     hipEvent_t fork = nullptr;
+    // sushi_hip_batch_workspace_view(WS_TSPEC) over half rows: the whole-row copy it hands out, made at the first request
+    void* tspec_whole = nullptr;
+    size_t tspec_whole_bytes = 0;
     void forget_learnt() { learnt.forget(); last = LastRun(); }
     ~SushiHipBatch() {
         for (int l = 1; l < MAX_LANES; ++l) {
@@ -207,6 +211,7 @@ struct SushiHipBatch {
         if (stats_pending && stats_ready) (void)hipEventSynchronize(stats_ready);       // the last run's counts may still be on their way
         if (stats_ready) (void)hipEventDestroy(stats_ready);
         g_host_slots.give(host_stats);
+        if (tspec_whole) (void)hipFree(tspec_whole);
     }
 };
 
@@ -420,6 +425,7 @@ static int launch_mac(const RunCtx& c, const SubView& v, hipStream_t st, const b
     ma.sub_first_pair = sb.first_pair; ma.dummy = v.dummy; ma.enable = enable;
     if (low) { ma.spec = (const uint4*)c.dst->spec_low; ma.tspec = v.tspec_low; ma.y = v.ylow; }
     else { ma.spec = (const uint4*)c.dst->spec; ma.tspec = (const uint4*)v.tspec; ma.y = v.y; }
+    ma.tspec_half = !low && tspec_half_rows(c.b->tspec) ? 1 : 0;
     for (int kern = 0; kern < 2; ++kern) {
         if (sb.item_count[kern] == 0) continue;
         ma.items = items_of_the_launch + (size_t)(sb.item_first[kern] - sb.item_first[0]) * (1 + MAC_SPW);
@@ -442,7 +448,7 @@ static int launch_mac_list(const RunCtx& c, const SubView& v, hipStream_t st, co
                            const int* dense_search, int long_only) {
     MacListArgs la;
     la.dense_search = dense_search; la.long_only = long_only;
-    la.spec = (const uint4*)c.dst->spec; la.spec_blocks = c.dst->blocks; la.tspec = (const uint4*)v.tspec; la.y = v.y;
+    la.spec = (const uint4*)c.dst->spec; la.spec_blocks = c.dst->blocks; la.tspec = (const uint4*)v.tspec; la.tspec_half = tspec_half_rows(c.b->tspec) ? 1 : 0; la.y = v.y;
     la.searches = c.searches + v.sb.a0; la.tconst = v.tconst; la.pairmap = v.pairmap; la.list = list; la.count = count;
     la.n_list = n_list; la.sub_first_seg = v.sb.first_seg; la.sub_first_pair = v.sb.first_pair;
     const int64_t want = (int64_t)n_list * MACL_PARTS;
@@ -454,13 +460,14 @@ static int launch_mac_list(const RunCtx& c, const SubView& v, hipStream_t st, co
 static int launch_mac_rows(const RunCtx& c, const SubView& v, hipStream_t st, const BoundArgs& ba, const int mode) {
     const SubBatch& sb = v.sb;
     MacRowsArgs ra;
-    ra.spec = (const uint4*)c.dst->spec; ra.spec_blocks = c.dst->blocks; ra.tspec = (const uint4*)v.tspec; ra.y = v.y;
+    ra.spec = (const uint4*)c.dst->spec; ra.spec_blocks = c.dst->blocks; ra.tspec = (const uint4*)v.tspec; ra.tspec_half = tspec_half_rows(c.b->tspec) ? 1 : 0; ra.y = v.y;
     ra.searches = c.searches + sb.a0; ra.tconst = v.tconst; ra.mark = ba.audit_mark; ra.n_sub = v.n_sub;
     ra.sub_first_seg = sb.first_seg; ra.sub_first_pair = sb.first_pair; ra.dense_search = v.dense_search;
     ra.plist = ba.plist; ra.first_search = ba.first_search; ra.audit_seq = ba.audit_seq; ra.audit_every = ba.audit_every;
     ra.items = v.slist; ra.item_count = v.n_rest_items; ra.pairmap = v.pairmap; ra.n_pairs = (int)sb.pairs;
     // (ROWS_ITEMS: how many items there are only the device knows -- at most one per pair; a fixed grid strides over them)
-    const int64_t rows_want = (int64_t)(mode == ROWS_ITEMS ? sb.pairs : v.n_sub) * MACL_PARTS;
+    // (ROWS_FIRST over half rows: half as many workgroups a search, each forming two entries a thread)
+    const int64_t rows_want = (int64_t)(mode == ROWS_ITEMS ? sb.pairs : v.n_sub) * (mode == ROWS_FIRST && ra.tspec_half ? MACL_PARTS / 2 : MACL_PARTS);
     const dim3 grid0((unsigned)std::min<int64_t>(rows_want, 256 * 32)), grid1((unsigned)std::min<int64_t>(rows_want, 256 * 16));
     auto go = [&](auto m) {
         if (sb.item_count[0] > 0) hipLaunchKernelGGL((mac_rows_kernel<0, decltype(m)::value>), grid0, dim3(MACL_THREADS), 0, st, ra);
@@ -1106,7 +1113,27 @@ int sushi_hip_batch_workspace_view(SushiHipBatch* b, int which, void** ptr_dev, 
     if (hipStreamSynchronize(b->last_stream) != hipSuccess) return SUSHI_HIP_ELAUNCH;
     const SubView v = last_sub(b);
     switch (which) {
-        case SUSHI_HIP_WS_TSPEC: *ptr_dev = v.tspec; *bytes = (size_t)v.sb.segs * ROW_BYTES; break;
+        case SUSHI_HIP_WS_TSPEC: {
+            const size_t need = (size_t)v.sb.segs * ROW_BYTES;
+            if (!tspec_half_rows(b->tspec)) { *ptr_dev = v.tspec; *bytes = need; break; }
+            // the view means whole rows: expanded from the half rows into a buffer of the batch's own
+            if (b->tspec_whole_bytes < need) {
+                if (b->tspec_whole) (void)hipFree(b->tspec_whole);
+                b->tspec_whole = nullptr; b->tspec_whole_bytes = 0;
+                if (hipMalloc(&b->tspec_whole, need) != hipSuccess) { b->tspec_whole = nullptr; return SUSHI_HIP_ENOMEM; }
+                b->tspec_whole_bytes = need;
+            }
+            const long long n_entries = (long long)v.sb.segs * ROWE;
+            hipLaunchKernelGGL(tspec_expand_kernel, dim3((unsigned)std::min<long long>((n_entries + 255) / 256, 256 * 32)), dim3(256), 0, b->last_stream,
+                               (const uint4*)v.tspec, (uint4*)b->tspec_whole, n_entries);
+            if (launch_ok() != SUSHI_HIP_OK || hipStreamSynchronize(b->last_stream) != hipSuccess) return SUSHI_HIP_ELAUNCH;
+            *ptr_dev = b->tspec_whole; *bytes = need;
+            break;
+        }
+        case SUSHI_HIP_WS_TSPEC_HALF:
+            if (!tspec_half_rows(b->tspec)) return SUSHI_HIP_EINVAL;
+            *ptr_dev = v.tspec; *bytes = (size_t)v.sb.segs * HROW_BYTES;
+            break;
         case SUSHI_HIP_WS_Y: *ptr_dev = v.y; *bytes = (size_t)v.sb.pairs * ROW_BYTES; break;
         case SUSHI_HIP_WS_TSPEC_LOW: *ptr_dev = v.tspec_low; *bytes = (size_t)v.sb.segs * LROW_BYTES; break;
         case SUSHI_HIP_WS_Y_LOW: *ptr_dev = v.ylow; *bytes = (size_t)v.sb.pairs * LROW_BYTES; break;

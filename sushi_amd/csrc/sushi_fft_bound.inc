@@ -554,6 +554,7 @@ struct MacRowsArgs {
     const uint4* spec;
     int64_t spec_blocks;
     const uint4* tspec;
+    int tspec_half;                   // `tspec` holds half rows (TspecLane; ROWS_FIRST then forms a row and its mirror together)
     uint4* y;
     const SearchDesc* searches;
     const TemplConsts* tconst;
@@ -602,10 +603,43 @@ __device__ __forceinline__ void mac_row_of_pair(const MacRowsArgs& a, const FftL
     }
     a.y[(size_t)(p0 + ip) * ROWE + e] = uint4{o[0], o[1], o[2], o[3]};
 }
+// ROWS_FIRST over HALF rows: a thread owns stored entry `h` of the search's half rows AND the whole-row entry that is its
+// conj-reversal (fft_core.hpp half_mirror_of) -- a workgroup is 256 stored entries, eight parts a search.  The pattern's stored
+// words are loaded once; they form the thread's own entry of the pilot's and the audit pair's rows as they are, and then, reversed
+// and conjugated in registers, the mirrored entry of the same rows: the same sums in the same order as every other route, against
+// the block spectra's entry at the mirror's index.  One after the other, so that no more loads are in flight than before.  Sixteen
+// lanes' mirrors are 256 consecutive bytes in reversed lane order (the eight runs of row 0's neighbours: in two pieces): whole
+// lines, read and written.  Row 0's two lanes mirror row 0 in itself: their words for it are row 1024's (reloaded in between).
+template <int SMAX>
+__device__ __forceinline__ void mac_rows_first_paired(const MacRowsArgs& a, const SearchDesc& sd, const FftLayout& lay, const int k,
+                                                      const float sy, const int h, const int z_zero) {
+    const uint4* __restrict__ hrow = a.tspec + (size_t)(sd.first_seg - a.sub_first_seg) * HROWE;
+    const int e_own = sushi_fft::half_to_full(h), e_mir = sushi_fft::half_mirror_of(h);
+    const int p0 = first_pair_in_sub(a.sub_first_pair, sd);
+    const int audit = audited_search(a, k) ? audit_pair_of(a, sd, k) : -1;
+    const int pilot = a.plist[k] - p0;
+    const bool two = audit >= 0 && audit < lay.n_pairs && audit != pilot;
+    sushi_mac::h8 tt[SMAX];
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) tt[s] = s < lay.n_seg ? as_h8(hrow[(size_t)s * HROWE + h]) : sushi_mac::zero_h8();
+    mac_row_of_pair<SMAX>(a, lay, tt, a.spec + e_own, p0, pilot, sy, e_own, z_zero);
+    if (two) mac_row_of_pair<SMAX>(a, lay, tt, a.spec + e_own, p0, audit, sy, e_own, z_zero);
+    if ((h & ~16) == 0) {                                        // entries 0 and 1 of row 0: h = 0, 16
+        const int hx = sushi_fft::half_entry(1024, h >> 4);
+#pragma unroll
+        for (int s = 0; s < SMAX; ++s) tt[s] = s < lay.n_seg ? as_h8(hrow[(size_t)s * HROWE + hx]) : sushi_mac::zero_h8();
+    }
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) tt[s] = as_h8(sushi_fft::real_conjrev(as_uint4(tt[s])));
+    mac_row_of_pair<SMAX>(a, lay, tt, a.spec + e_mir, p0, pilot, sy, e_mir, z_zero);
+    if (two) mac_row_of_pair<SMAX>(a, lay, tt, a.spec + e_mir, p0, audit, sy, e_mir, z_zero);
+}
+// (`e`: the thread's entry of the whole row -- ROWS_FIRST over half rows: its stored entry of the half row)
 template <int SMAX, int MODE>
 __device__ __forceinline__ void mac_rows_of_search(const MacRowsArgs& a, const SearchDesc& sd, const FftLayout& lay, const int k,
                                                    const float sy, const int e, unsigned long long (*masks)[4], const int z_zero) {
-    const uint4* __restrict__ tsp = a.tspec + (size_t)(sd.first_seg - a.sub_first_seg) * ROWE + e;
+    if (MODE == ROWS_FIRST && a.tspec_half) { mac_rows_first_paired<SMAX>(a, sd, lay, k, sy, e, z_zero); return; }
+    const TspecLane tsp = tspec_lane(a.tspec, a.tspec_half, (size_t)(sd.first_seg - a.sub_first_seg), e);
     const uint4* __restrict__ zsp = a.spec + e;
     const int p0 = first_pair_in_sub(a.sub_first_pair, sd);
     const int tid = threadIdx.x;
@@ -620,7 +654,7 @@ __device__ __forceinline__ void mac_rows_of_search(const MacRowsArgs& a, const S
     }
     sushi_mac::h8 tt[SMAX];
 #pragma unroll
-    for (int s = 0; s < SMAX; ++s) tt[s] = s < lay.n_seg ? as_h8(tsp[(size_t)s * ROWE]) : sushi_mac::zero_h8();
+    for (int s = 0; s < SMAX; ++s) tt[s] = s < lay.n_seg ? as_h8(tspec_entry(tsp, (size_t)s)) : sushi_mac::zero_h8();
     if (MODE == ROWS_FIRST) {
         const int pilot = a.plist[k] - p0;
         mac_row_of_pair<SMAX>(a, lay, tt, zsp, p0, pilot, sy, e, z_zero);
@@ -650,13 +684,13 @@ __device__ __forceinline__ void mac_rows_of_search(const MacRowsArgs& a, const S
 template <int SMAX>
 __device__ __forceinline__ void mac_rows_of_item(const MacRowsArgs& a, const SearchDesc& sd, const FftLayout& lay, const int k,
                                                  const float sy, const int e, const int z_zero, const int first) {
-    const uint4* __restrict__ tsp = a.tspec + (size_t)(sd.first_seg - a.sub_first_seg) * ROWE + e;
+    const TspecLane tsp = tspec_lane(a.tspec, a.tspec_half, (size_t)(sd.first_seg - a.sub_first_seg), e);
     const uint4* __restrict__ zsp = a.spec + e;
     const int p0 = first_pair_in_sub(a.sub_first_pair, sd);
     const int audit = audited_search(a, k) ? audit_pair_of(a, sd, k) : -1;
     sushi_mac::h8 tt[SMAX];
 #pragma unroll
-    for (int s = 0; s < SMAX; ++s) tt[s] = s < lay.n_seg ? as_h8(tsp[(size_t)s * ROWE]) : sushi_mac::zero_h8();
+    for (int s = 0; s < SMAX; ++s) tt[s] = s < lay.n_seg ? as_h8(tspec_entry(tsp, (size_t)s)) : sushi_mac::zero_h8();
     int room = REST_ITEM_PAIRS;
     for (int base = first; base < lay.n_pairs && room > 0; base += 64) {
         const int i = base + (threadIdx.x & 63);
@@ -700,10 +734,12 @@ void mac_rows_kernel(MacRowsArgs a) {
         }
         return;
     }
-    for (long long it = blockIdx.x; it < (long long)a.n_sub * MACL_PARTS; it += gridDim.x) {
-        const int k = (int)(it / MACL_PARTS);
+    // (ROWS_FIRST over half rows: a workgroup is 256 STORED entries, half as many parts a search -- mac_rows_first_paired)
+    const int parts = MODE == ROWS_FIRST && a.tspec_half ? MACL_PARTS / 2 : MACL_PARTS;
+    for (long long it = blockIdx.x; it < (long long)a.n_sub * parts; it += gridDim.x) {
+        const int k = (int)(it / parts);
         if (MODE != ROWS_FIRST && a.dense_search[k]) continue;  // (uniform: a workgroup is one search's)
-        const int e = (int)(it % MACL_PARTS) * MACL_THREADS + threadIdx.x;
+        const int e = (int)(it % parts) * MACL_THREADS + threadIdx.x;
         const SearchDesc sd = a.searches[k];
         const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
         const float sy = a.tconst[k].mac_scale;

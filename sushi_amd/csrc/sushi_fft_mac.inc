@@ -16,6 +16,7 @@ struct MacArgs {
     const uint4* spec;                // destination spectra, as 4-bin entries of packed halves
     int64_t spec_blocks;              // blocks of the stream; block `spec_blocks` is all zero
     const uint4* tspec;
+    int tspec_half;                   // whole rows only: `tspec` holds half rows (TspecLane)
     uint4* y;                         // [pairs of the sub-batch][ROWE]
     const SearchDesc* searches;       // the sub-batch's searches
     const TemplConsts* tconst;        // [searches of the sub-batch]: mac_scale
@@ -27,6 +28,20 @@ struct MacArgs {
     uint4* dummy;                     // [MAC_DUMMY_LINES][MAC_THREADS] where the stores of lanes without a valid output go
     const int* enable;                // NULL, or a device flag: 0 = this launch is not needed (every workgroup leaves at once)
 };
+
+// Where a lane finds entry `e` of a pattern's whole rows, segment after segment.  Whole rows as they are; of HALF rows (the real
+// route's format, fft_core.hpp "HALF ROWS") the one function every reader goes through: the place in the half row and whether
+// the words there are the entry's conj-reversal.  Every entry comes back with the words a whole row holds.
+struct TspecLane { const uint4* __restrict__ p; size_t stride; bool conjrev; };
+__device__ __forceinline__ TspecLane tspec_lane(const uint4* __restrict__ tspec, const int half_rows, const size_t first_seg, const int e) {
+    if (!half_rows) return TspecLane{tspec + first_seg * ROWE + e, (size_t)ROWE, false};
+    const sushi_fft::HalfSource s = sushi_fft::half_source(e);
+    return TspecLane{tspec + first_seg * HROWE + s.index, (size_t)HROWE, s.conjrev};
+}
+__device__ __forceinline__ uint4 tspec_entry(const TspecLane& t, const size_t s) {
+    const uint4 v = t.p[s * t.stride];
+    return t.conjrev ? sushi_fft::real_conjrev(v) : v;
+}
 
 constexpr int MAC_ZR = 6;                        // rows per load instruction: divides every SMAX
 
@@ -178,7 +193,8 @@ __device__ __forceinline__ void mac_item(const MacArgs& a, const int* __restrict
     const int wv_first = __builtin_amdgcn_readfirstlane(wave_min_i32(jb0));
     const int wv_last = __builtin_amdgcn_readfirstlane(wave_max_i32(jb1));
     const int wv_seg = __builtin_amdgcn_readfirstlane(wave_max_i32(n_seg));
-    const uint4* __restrict__ tsp = a.tspec + (size_t)first_seg * RE + e0;
+    // (the low form's rows are whole low rows on every route)
+    const TspecLane tsp = RE == ROWE ? tspec_lane(a.tspec, a.tspec_half, (size_t)first_seg, e0) : TspecLane{a.tspec + (size_t)first_seg * RE + e0, (size_t)RE, false};
     uint4* __restrict__ yout = a.y + (size_t)first_pair * RE + e0;
     const uint4* __restrict__ zsp = a.spec + e0;
     // one 16-byte slot per wave: the invalid lanes of a store instruction then add one request to it instead of a line per
@@ -188,7 +204,7 @@ __device__ __forceinline__ void mac_item(const MacArgs& a, const int* __restrict
     for (int c0 = 0; c0 < wv_seg; c0 += SMAX) {                 // patterns longer than SMAX segments: SMAX at a time
         h8 tt[SMAX];
 #pragma unroll
-        for (int s = 0; s < SMAX; ++s) tt[s] = (c0 + s) < n_seg ? as_h8(tsp[(size_t)(c0 + s) * RE]) : sushi_mac::zero_h8();
+        for (int s = 0; s < SMAX; ++s) tt[s] = (c0 + s) < n_seg ? as_h8(tspec_entry(tsp, (size_t)(c0 + s))) : sushi_mac::zero_h8();
         const bool lane_chunk = c0 < n_seg;
         if (c0 == 0) mac_chunk<SMAX, false, ZROWS, RE>(a, c0, wv_first, wv_last, pair_lo, pair_hi, lane_chunk, tt, zsp, z_zero, yout, dummy, sy, slot, fb, zw);
         else if (SMAX == MAC_SMAX_LONG) mac_chunk<SMAX, true, ZROWS, RE>(a, c0, wv_first, wv_last, pair_lo, pair_hi, lane_chunk, tt, zsp, z_zero, yout, dummy, sy, slot, fb, zw);
@@ -262,6 +278,7 @@ struct MacListArgs {
     const uint4* spec;
     int64_t spec_blocks;
     const uint4* tspec;
+    int tspec_half;                   // `tspec` holds half rows (TspecLane)
     uint4* y;                         // [pairs of the sub-batch][ROWE]
     const SearchDesc* searches;
     const TemplConsts* tconst;
@@ -291,7 +308,7 @@ void mac_list_kernel(MacListArgs a) {
         if (a.long_only && lay.n_seg <= MAC_SMAX_LONG) continue;
         const long long I = absolute_pair(lay, a.sub_first_pair, pr, sd);
         const float sy = a.tconst[k].mac_scale;
-        const uint4* __restrict__ tsp = a.tspec + (size_t)(sd.first_seg - a.sub_first_seg) * ROWE + e;
+        const TspecLane tsp = tspec_lane(a.tspec, a.tspec_half, (size_t)(sd.first_seg - a.sub_first_seg), e);
         const uint4* __restrict__ zsp = a.spec + e;
         float re[sushi_mac::BINS], im[sushi_mac::BINS];
         for (int c0 = 0; c0 < lay.n_seg; c0 += MAC_SMAX_LONG) {
@@ -306,7 +323,7 @@ void mac_list_kernel(MacListArgs a) {
                     const int sx = s6 + t < s_end ? s6 + t : s_end - 1;
                     const long long jj = FFT_STEP * I + sx;
                     z[t] = as_h8(zsp[(size_t)(jj < z_zero ? jj : z_zero) * ROWE]);
-                    u[t] = as_h8(tsp[(size_t)sx * ROWE]);
+                    u[t] = as_h8(tspec_entry(tsp, (size_t)sx));
                 }
 #pragma unroll
                 for (int t = 0; t < 6; ++t) {

@@ -60,7 +60,7 @@ struct TspecArgs {
     int n_sub;
     int sub_first_seg;
     int sub_first_pair;
-    uint32_t* tspec;                  // [segments of the sub-batch][FN] packed halves
+    uint32_t* tspec;                  // [segments of the sub-batch] packed halves: whole rows of FN words (tspec_kernel) or half rows of 4 HROWE (tspec_real_kernel)
     int* pairmap;                     // [pairs of the sub-batch] -> search index inside the sub-batch
     TemplConsts* tconst;      // [searches of the sub-batch]
     const double* src_s1;
@@ -162,11 +162,14 @@ void tspec_kernel(TspecArgs a) {
 
 // The real route (the default): the segment is real, so it is packed into HALF as many complex points, transformed by the
 // 8192-point plan and unfolded (fft_core.hpp "Forward transform of a REAL, zero-padded pattern segment").  512 threads a segment,
-// half the buffer: four workgroups of eight waves per CU, the complex route's residency.  Everything the kernel leaves has the
-// complex route's place and meaning; a row's bins N - k are now the conjugates of its bins k word for word.
+// half the buffer: four workgroups of eight waves per CU, the complex route's residency.  The low rows and norms it leaves have the
+// complex route's place and meaning.  A whole row's bins N - k are the conjugates of its bins k word for word, so it is stored as a
+// HALF row (fft_core.hpp "HALF ROWS"): a thread's entries u = 0, 1 of its two rows -- thread 0: of row 0 and, as "row 1024", the
+// conj-reversals of row 0's own mirrored entries.  The mirrors are still made in registers, for the low entries.
 constexpr int RT = sushi_fft::RNT;
 constexpr int RLDS_FLOATS = sushi_fft::lds_floats<sushi_fft::RLOGN>();
 static_assert(2 * RT == FT && 2 * RLDS_FLOATS == LDS_FLOATS && sushi_fft::RN == FN && FFT_SEG * 4 == FN, "the real route's halves");
+static_assert(HROWE == sushi_fft::HALF_ROWE && ROWE == 2 * sushi_fft::HALF_STORED, "sushi_geometry.hpp's half row is fft_core's");
 template <typename T>
 __global__ __launch_bounds__(RT, 8)        // (64 VGPRs, as the complex route)
 void tspec_real_kernel(TspecArgs a) {
@@ -211,7 +214,7 @@ void tspec_real_kernel(TspecArgs a) {
     __syncthreads();
     sushi_fft::real_z_load<1>(za, zb, tid, lds);
     const float sc = 0.5f * g.sc;                                // (the unfold leaves twice the bins)
-    uint32_t* __restrict__ row_words = a.tspec + (size_t)blockIdx.x * FN;
+    uint32_t* __restrict__ row_words = a.tspec + (size_t)blockIdx.x * (4 * HROWE);
     uint4* __restrict__ low = a.tspec_low + (size_t)blockIdx.x * LROWE;
     auto abs2 = [](const unsigned w, const float acc) {
         const h2 h = __builtin_bit_cast(h2, w);
@@ -221,16 +224,14 @@ void tspec_real_kernel(TspecArgs a) {
     // entry: low_entry_and_rest): a mirror has its bin's modulus exactly, so a thread's share is twice its own bins 2 .. 7 of
     // both rows -- thread 0: of row 0, and bin N/2 once.
     float e = 0.f;
-    if (tail) {                                                  // row 512: bins tid, 7 - tid and their mirrors 15 - tid, 8 + tid, word by word
+    if (tail) {                                                  // row 512: bins tid and 7 - tid, word by word (their mirrors 15 - tid, 8 + tid: the low entry's only)
         sushi_fft::real_tail_load<1>(tz, tp, tid, lds);
         cpx lo, hi;
         sushi_fft::real_tail_bfly(tz, tp, tw_tail, lo, hi);
         const unsigned wlo = pack_h2(__builtin_fmaf(lo.x, sc, 0.f), __builtin_fmaf(lo.y, sc, 0.f));
         const unsigned whi = pack_h2(__builtin_fmaf(hi.x, sc, 0.f), __builtin_fmaf(hi.y, sc, 0.f));
-        row_words[sushi_fft::real_tail_word(tid)] = wlo;
-        row_words[sushi_fft::real_tail_word(7 - tid)] = whi;
-        row_words[sushi_fft::real_tail_word(8 + tid)] = sushi_fft::real_conj_word(whi);
-        row_words[sushi_fft::real_tail_word(15 - tid)] = sushi_fft::real_conj_word(wlo);
+        row_words[sushi_fft::half_tail_word(tid)] = wlo;
+        row_words[sushi_fft::half_tail_word(7 - tid)] = whi;
         uint32_t* __restrict__ lw = reinterpret_cast<uint32_t*>(low + sushi_fft::lslot_of_thread(sushi_fft::REAL_TAIL_ROW));
         if (tid < 2) { lw[tid] = wlo; lw[3 - tid] = sushi_fft::real_conj_word(wlo); }       // bins 0, 1, 14, 15: the band
         e = abs2(whi, tid < 2 ? 0.f : abs2(wlo, 0.f));
@@ -259,14 +260,18 @@ void tspec_real_kernel(TspecArgs a) {
         if ((tid & 63) == 0) atomicAdd(a.tnorm_rest + blockIdx.x, w);
     }
     uint4* __restrict__ out = reinterpret_cast<uint4*>(row_words);
-    out[sushi_fft::real_entry(ra, 0)] = uint4{wa[0], wa[1], wa[2], wa[3]};
-    out[sushi_fft::real_entry(ra, 1)] = uint4{wa[4], wa[5], wa[6], wa[7]};
-    out[sushi_fft::real_entry(ra, 2)] = uint4{ma[0], ma[1], ma[2], ma[3]};
-    out[sushi_fft::real_entry(ra, 3)] = uint4{ma[4], ma[5], ma[6], ma[7]};
-    if (tid != 0) {
-        out[sushi_fft::real_entry(rb, 0)] = uint4{wb[0], wb[1], wb[2], wb[3]};
-        out[sushi_fft::real_entry(rb, 1)] = uint4{wb[4], wb[5], wb[6], wb[7]};
-        out[sushi_fft::real_entry(rb, 2)] = uint4{mb[0], mb[1], mb[2], mb[3]};
-        out[sushi_fft::real_entry(rb, 3)] = uint4{mb[4], mb[5], mb[6], mb[7]};
-    }
+    out[sushi_fft::half_entry(ra, 0)] = uint4{wa[0], wa[1], wa[2], wa[3]};
+    out[sushi_fft::half_entry(ra, 1)] = uint4{wa[4], wa[5], wa[6], wa[7]};
+    // (thread 0, rb = 1024: the conj-reversals of row 0's entries 3 and 2 as they were stored whole -- its OWN bins 1 .. 7 and bin N/2,
+    // not the second computation of them that its wb holds)
+    out[sushi_fft::half_entry(rb, 0)] = tid != 0 ? uint4{wb[0], wb[1], wb[2], wb[3]} : uint4{wa[1], wa[2], wa[3], wa[4]};
+    out[sushi_fft::half_entry(rb, 1)] = tid != 0 ? uint4{wb[4], wb[5], wb[6], wb[7]} : uint4{wa[5], wa[6], wa[7], wb[7]};
+}
+
+// Half rows -> the whole rows they stand for, entry by entry through the readers' own function (for
+// sushi_hip_batch_workspace_view: tests and tools read whole rows).
+__global__ __launch_bounds__(256)
+void tspec_expand_kernel(const uint4* __restrict__ half_rows, uint4* __restrict__ whole_rows, const long long n_entries) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_entries; i += (long long)gridDim.x * 256)
+        whole_rows[i] = sushi_fft::half_fetch(half_rows + (size_t)(i / ROWE) * HROWE, (int)(i % ROWE));
 }

@@ -154,6 +154,10 @@ constexpr int ROWE = FFT_N / 4;                // ... as 16-byte entries (four b
 // loads them (fft_core.hpp "LOW BAND"): the band-split exclusion multiplies, stores and transforms only these.
 constexpr int LROWE = FFT_N / 16;              // 16-byte entries of a low row (sushi_fft::LB_ENTRIES)
 constexpr int LROW_BYTES = LROWE * 16;
+// A pattern segment's whole row is stored as a HALF row where its transform leaves it conjugate-symmetric word for word (the real
+// route: run_policy.hpp tspec_half_rows): half the entries and one run of sixteen more (fft_core.hpp "HALF ROWS").
+constexpr int HROWE = ROWE / 2 + 16;           // 16-byte entries of a half row (sushi_fft::HALF_ROWE)
+constexpr int HROW_BYTES = HROWE * 16;         // (a workspace keeps a whole row's room per segment on either route: plan_core.hpp ws_layout)
 // The spectra of a searchable stream of n samples (sushi_hip_stream_add_spectra), as they lie in the memory it is given: a whole
 // row per block and one more (its samples are all past the end, so its spectrum is zero), from `low` on their low rows, from
 // `norms` on three arrays of `norm_stride` floats -- the rows' norms outside the band: of Z, of its two real blocks.

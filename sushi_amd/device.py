@@ -576,14 +576,22 @@ class SearchBatch(object):
 
     def workspace_view(self, which):
         """FFT path, after run(): the last sub-batch's pattern spectra / products as a float16 CUDA tensor of (re, im) pairs
-        (sushi_hip_batch_workspace_view; which = _native.WS_*).  A view of this batch's own buffer: valid until the next run()."""
+        (sushi_hip_batch_workspace_view; which = _native.WS_*).  A view of this batch's own buffer: valid until the next run() --
+        WS_TSPEC of the real route, whose stored rows are half rows (WS_TSPEC_HALF), is a whole-row copy that owns its bytes."""
         ptr, nbytes = ctypes.c_void_p(), ctypes.c_size_t(0)
         _native.check(_native.lib().sushi_hip_batch_workspace_view(self._handle, int(which), ctypes.byref(ptr), ctypes.byref(nbytes)),
                       "sushi_hip_batch_workspace_view")
         if not ptr.value:
             return None
         off = ptr.value - self._mem.data_ptr()
-        return self._mem[off:off + nbytes.value].view(torch.float16)
+        if 0 <= off and off + nbytes.value <= self._mem.numel():
+            return self._mem[off:off + nbytes.value].view(torch.float16)
+        # (WS_TSPEC over stored half rows: the whole-row copy lives in a buffer of the native batch's own -- taken over as a tensor
+        # that owns its bytes, so that it outlives the next request)
+        class _Foreign:
+            __cuda_array_interface__ = {"shape": (nbytes.value,), "typestr": "|u1", "data": (ptr.value, False), "version": 2}
+        with torch.cuda.device(self._mem.device):
+            return torch.as_tensor(_Foreign(), device=self._mem.device).clone().view(torch.float16)
 
     def ranking_errors(self):
         """FFT path: |f32 FFT score - exact score| at every search's result position in the last run()
