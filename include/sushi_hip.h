@@ -701,6 +701,50 @@ SUSHI_HIP_API int sushi_hip_track_margins(const float* curves_dev, int64_t n_cur
                                           double* alt_dev, int32_t* alt_arg_dev, double* M_dev,
                                           void* mem_dev, size_t mem_bytes, void* hip_stream);
 
+/* ---- rows: score rows clamped at a threshold, formed from a threshold run's hits (13, additive) ---------------
+ * A pass over a shift axis needs to know where a row is good and how good; how bad the rest is only feeds decoys.  The CLAMPED row
+ * of a score row R at a float32 value f keeps every value that passes f and holds f everywhere else:
+ *     SUSHI_HIP_METHOD_SQDIFF_NORMED   C[p] = R[p] <= f ? R[p] : f      (min(R, f), the bits of a passing value kept, -0.0 included)
+ *     SUSHI_HIP_METHOD_CCOEFF_NORMED   C[p] = R[p] >= f ? R[p] : f      (max(R, f))
+ * (a NaN does not pass).  A float32 score passes a threshold run's double comparison with (double)f exactly when it passes f, so
+ * "the hits of sushi_hip_batch_run_threshold(batch, (double)f, ...), and f everywhere else" is C bit for bit: that is
+ * sushi_hip_rows_from_hits, a fill and a scatter, no score formed.  sushi_hip_rows_clamp applies the rule to rows that exist.
+ * A row record names where a row lies in each buffer of a call; rows of one call that overlap are the caller's business. */
+typedef struct SushiHipRowsRow {
+    int64_t out_off;    /* first float of the row in out_dev */
+    int64_t in_off;     /* sushi_hip_rows_clamp: first float of the row in in_dev; sushi_hip_rows_from_hits: not read */
+    int32_t n_pos;      /* floats of the row, >= 1 */
+    int32_t reserved;
+} SushiHipRowsRow;          /* 24 bytes */
+#define SUSHI_HIP_ROWS_OVERFLOW 1   /* flag bit 0: the request has more hits than `capacity`; its row is all f */
+#define SUSHI_HIP_ROWS_BAD_HITS 2   /* flag bit 1: a hit index outside [0, n_pos), hits not in ascending index order, a count < 0 */
+/* floats of a tile: one workgroup fills a tile of consecutive floats of one row, then writes the hits that fall into it */
+SUSHI_HIP_API int sushi_hip_rows_tile(void);
+/* workspace of either call (the row table); 0 for n < 1 */
+SUSHI_HIP_API size_t sushi_hip_rows_bytes(int n);
+/* hits_dev: [n][capacity] records and counts_dev: [n], as sushi_hip_batch_run_threshold leaves them (request k's hits in ascending
+ * index order in the first min(counts[k], capacity) records).  Row k, rows_host[k].n_pos floats from out_dev + rows_host[k].out_off
+ * on, becomes f over [0, n_pos) and then hits[k][j].score at hits[k][j].index for every j < counts[k]; flags_dev[k] (int32) becomes
+ * 0, or SUSHI_HIP_ROWS_OVERFLOW where counts[k] > capacity -- that row is all f: it has to be formed densely --, or
+ * SUSHI_HIP_ROWS_BAD_HITS where the list is not what a threshold run leaves: such a row holds f and an unspecified subset of its
+ * hits, and no access leaves the row or the list.  Floats of out_dev outside every row are not written.  A tile of a row is
+ * written by one workgroup only, which finds its hits by bisection of the list: no atomics on the rows, and the result does not
+ * depend on the launch geometry.  No device allocation: one upload of the table into mem_dev, one memset of the flags, one launch.
+ * Asynchronous; stateless (any thread, own workspace).  Checked before any HIP call -- EINVAL: a null pointer, n < 1, capacity < 0,
+ * n_out < 1, an f that is not finite, n_pos < 1, out_off < 0 or out_off + n_pos > n_out (decided without forming the sum); EALIGN:
+ * mem_dev not 256-byte aligned, counts_dev not 8-byte aligned, another pointer not 4-byte aligned; ENOSPACE: mem_bytes too small. */
+SUSHI_HIP_API int sushi_hip_rows_from_hits(const SushiHipHit* hits_dev, const int64_t* counts_dev, int n, int32_t capacity,
+                                           const SushiHipRowsRow* rows_host, float f, float* out_dev, int64_t n_out,
+                                           int32_t* flags_dev, void* mem_dev, size_t mem_bytes, void* hip_stream);
+/* out_dev[out_off + p] = C[p] of R = in_dev[in_off ..], for every row of the table and p in [0, n_pos).  in_dev == out_dev with
+ * in_off == out_off in every row clamps in place; buffers that overlap in any other way are refused.  One upload of the table, one
+ * launch.  Asynchronous; stateless.  Checked before any HIP call -- EINVAL: a null pointer, n < 1, n_in < 1, n_out < 1, an unknown
+ * method, an f that is not finite, n_pos < 1, a row that leaves either buffer, buffers that overlap other than in place; EALIGN:
+ * mem_dev not 256-byte aligned, a float pointer not 4-byte aligned; ENOSPACE: mem_bytes too small. */
+SUSHI_HIP_API int sushi_hip_rows_clamp(const float* in_dev, int64_t n_in, float* out_dev, int64_t n_out,
+                                       const SushiHipRowsRow* rows_host, int n, int method, float f,
+                                       void* mem_dev, size_t mem_bytes, void* hip_stream);
+
 /* ---- WavStream.__init__ on the GPU (wav.py:64-91 decode + downmix, wav.py:113-156 value pipeline) ----
  * sushi_hip_load_decode   : interleaved little-endian PCM frames (sample_width 2 or 3 bytes, `channels` per frame)
  *     -> float32 mono: the int16 (for 24-bit: the top two bytes, wav.py:70-74) of every channel converted to

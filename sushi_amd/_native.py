@@ -55,6 +55,10 @@ JOINT_ROW_DTYPE = np.dtype([("curve_off", "<i8"), ("weight", "<f8")], align=True
 assert JOINT_ROW_DTYPE.itemsize == 16
 JOINT_GROUP_DTYPE = np.dtype([("first_row", "<i4"), ("n_rows", "<i4"), ("n_shift", "<i4"), ("reserved", "<i4")], align=True)
 assert JOINT_GROUP_DTYPE.itemsize == 16
+# struct SushiHipRowsRow, 24 bytes: where a row lies in the buffers of a rows call (sushi_hip_rows_from_hits / sushi_hip_rows_clamp)
+ROWS_ROW_DTYPE = np.dtype([("out_off", "<i8"), ("in_off", "<i8"), ("n_pos", "<i4"), ("reserved", "<i4")], align=True)
+assert ROWS_ROW_DTYPE.itemsize == 24
+ROWS_OVERFLOW, ROWS_BAD_HITS = 1, 2          # SUSHI_HIP_ROWS_*: the flag bits of sushi_hip_rows_from_hits
 
 
 class BatchInfo(ctypes.Structure):
@@ -199,6 +203,13 @@ def lib():
     L.sushi_hip_track_margins.restype = ci
     L.sushi_hip_track_margins.argtypes = [vp, i64, vp, vp, vp, ci, i32, ci, dbl, dbl, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                           sz, vp]
+    L.sushi_hip_rows_tile.restype = ci
+    L.sushi_hip_rows_bytes.restype = sz
+    L.sushi_hip_rows_bytes.argtypes = [ci]
+    L.sushi_hip_rows_from_hits.restype = ci
+    L.sushi_hip_rows_from_hits.argtypes = [vp, vp, ci, i32, vp, cf, vp, i64, vp, vp, sz, vp]
+    L.sushi_hip_rows_clamp.restype = ci
+    L.sushi_hip_rows_clamp.argtypes = [vp, i64, vp, i64, vp, ci, ci, cf, vp, sz, vp]
     L.sushi_hip_load_decode.restype = ci
     L.sushi_hip_load_decode.argtypes = [vp, i64, i32, i32, vp, vp]
     L.sushi_hip_load_decode_mix.restype = ci

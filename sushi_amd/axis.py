@@ -132,3 +132,124 @@ def event_curves(dst_dev, src_dev, axes, method):
                                   [b + a.k_lo for a in axes for b in a.bases], [a.n_shift for a in axes for _ in a.bases],
                                   method=method)
     return curves, bounds[:-1].tolist()
+
+
+# ---------------------------------------------------------------------------------------------- rows clamped at a threshold
+HIT_BYTES = 256 << 20        # hit records of one threshold run (event_rows' default capacity stays under it)
+
+
+def clamp_value(clamp, method):
+    """The float32 value f a clamp stands for: the smallest float32 >= clamp for 'sqdiff_normed', the largest float32 <= clamp for
+    'ccoeff_normed' -- rounded towards the side that fails, so that a float32 score passes f exactly when it passes `clamp`, and a
+    threshold run at float(f) finds exactly the positions a clamped row keeps.  SushiError unless clamp (and f) is finite."""
+    code = method_code(method)
+    try:
+        c = float(clamp)
+    except (TypeError, ValueError):
+        raise SushiError("clamp must be a number")
+    if not np.isfinite(c):
+        raise SushiError("clamp must be finite")
+    with np.errstate(over="ignore"):
+        f = np.float32(c)
+    if code == _native.METHOD_CCOEFF_NORMED:
+        if float(f) > c:
+            f = np.nextafter(f, np.float32(-np.inf))
+    elif float(f) < c:
+        f = np.nextafter(f, np.float32(np.inf))
+    if not np.isfinite(f):
+        raise SushiError("clamp must be finite as a float32")
+    return np.float32(f)
+
+
+def clamp_rows_host(rows, clamp, method):
+    """The clamped row in NumPy, the statement every other form is compared with: min(R, f) for 'sqdiff_normed' as np.where(R <= f,
+    R, f), max(R, f) for 'ccoeff_normed' as np.where(R >= f, R, f), f = clamp_value(clamp, method), the comparison in float64.
+    float32, the shape of `rows`; the bits of every passing value are kept, -0.0 included; a NaN becomes f."""
+    f = clamp_value(clamp, method)
+    R = np.asarray(rows)
+    if R.dtype != np.float32:
+        raise SushiError("clamp_rows_host: float32 rows")
+    wide = R.astype(np.float64)
+    keep = wide >= float(f) if method == "ccoeff_normed" else wide <= float(f)
+    return np.where(keep, R, f).astype(np.float32)
+
+
+def checked_clamp(clamp, capacity, method):
+    """(f or None, capacity or None) of a search's clamp= / capacity= arguments; SushiError for a capacity without a clamp, or one
+    that is not an int >= 0."""
+    if clamp is None:
+        if capacity is not None:
+            raise SushiError("capacity belongs to clamp=")
+        return None, None
+    f = clamp_value(clamp, method)
+    if capacity is not None:
+        if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < 0:
+            raise SushiError("capacity must be an int >= 0")
+        capacity = int(capacity)
+    return f, capacity
+
+
+def default_capacity(n_requests, n_shift):
+    """Hits kept per request when the caller names none: min(n_shift, max(1024, n_shift // 16)), and no more than HIT_BYTES of
+    8-byte records over all requests of the run (at least 1)."""
+    return max(1, min(int(n_shift), max(1024, int(n_shift) // 16), HIT_BYTES // (8 * max(1, int(n_requests)))))
+
+
+def merge_rows_info(total, info):
+    """A search's rows_info: event_rows' counts summed over its formings (capacity: the largest)."""
+    if total is None:
+        return dict(info, formings=1)
+    out = {k: total[k] + info[k] for k in ("n_sparse", "n_dense", "hits", "pairs_evaluated", "pairs")}
+    out["capacity"] = max(total["capacity"], info["capacity"])
+    out["formings"] = total["formings"] + 1
+    return out
+
+
+def event_rows(dst_dev, src_dev, axes, method, clamp=None, capacity=None, info=None):
+    """event_curves with every row clamped at `clamp`: (curves, the first float of every row), the same layout.  clamp=None is
+    event_curves itself.  Otherwise, with f = clamp_value(clamp, method): one FFT-path SearchBatch over the chunk's requests, one
+    threshold run at float(f) keeping `capacity` hits per request, and one sushi_hip_rows_from_hits call that writes f and the hits
+    into a fresh buffer -- no whole row is formed.  The flags are then read (one host synchronisation, as SearchBatch.occurrences
+    accepts): every request with more hits than `capacity` is formed densely, by match_curves into a buffer of its own and
+    sushi_hip_rows_clamp from there into its place (that buffer is as large as those requests' rows).  The result is bit for bit
+    clamp_rows_host(event_curves' rows, clamp, method).  capacity (None: default_capacity -- min(n_shift, max(1024, n_shift // 16)),
+    and at most HIT_BYTES = 256 MiB of records per run): an int >= 0; 0 sends every request with a hit the dense way.  info: a dict
+    that receives n_sparse / n_dense (requests formed from their hits / densely), hits (all requests' counts), capacity, pairs_evaluated
+    / pairs (block pairs the threshold run evaluated exactly, of how many).  SushiError if a hit list is not what a threshold run
+    leaves (a bug, never a property of the input).
+    What it costs is the threshold run: where its pair bound excludes most block pairs at f the forming takes a fraction of
+    event_curves' time, where it excludes none (a clamp near chance level) it takes a little more, and a request that overflows pays
+    for both routes (DESIGN.md 3.20 has the figures)."""
+    f, capacity = checked_clamp(clamp, capacity, method)
+    if f is None:
+        return event_curves(dst_dev, src_dev, axes, method)
+    import torch
+    from .curves import match_curves
+    from .device import SearchBatch
+    from .rows import BAD_HITS, OVERFLOW, rows_clamp_device, rows_from_hits_device, rows_table
+    offs, lens = [o for a in axes for o in a.offs], [m for a in axes for m in a.lens]
+    starts, n_pos = [b + a.k_lo for a in axes for b in a.bases], [a.n_shift for a in axes for _ in a.bases]
+    n = len(offs)
+    if capacity is None:
+        capacity = default_capacity(n, max(n_pos))
+    capacity = min(capacity, max(n_pos))
+    batch = SearchBatch(dst_dev, src_dev, offs, lens, starts, n_pos, path="fft", method=method)
+    hits, counts = batch.run_threshold(float(f), capacity)
+    bounds = np.zeros(n + 1, np.int64)
+    np.cumsum(np.asarray(n_pos, np.int64), out=bounds[1:])
+    with torch.cuda.device(dst_dev.device):
+        curves = torch.empty(int(bounds[-1]), dtype=torch.float32, device=dst_dev.device)
+    flags = rows_from_hits_device(hits, counts, rows_table(bounds[:-1], n_pos), f, curves).cpu().numpy()
+    if (flags & BAD_HITS).any():
+        raise SushiError("event_rows: the threshold run left a hit list that is not in ascending order inside its row (request %d)"
+                         % int(np.flatnonzero(flags & BAD_HITS)[0]))
+    dense = np.flatnonzero(flags & OVERFLOW)
+    if dense.size:
+        whole, at = match_curves(dst_dev, src_dev, [offs[k] for k in dense], [lens[k] for k in dense], [starts[k] for k in dense],
+                                 [n_pos[k] for k in dense], method=method)
+        rows_clamp_device(whole, rows_table(bounds[dense], [n_pos[k] for k in dense], in_off=at[:-1]), method, f, out=curves)
+    if info is not None:
+        d = batch.diagnostics()
+        info.update(n_sparse=n - int(dense.size), n_dense=int(dense.size), hits=int(counts.cpu().numpy().sum()), capacity=capacity,
+                    pairs_evaluated=int(d["pairs_transformed"]), pairs=int(batch.fft_pairs))
+    return curves, bounds[:-1].tolist()

@@ -53,6 +53,9 @@ UNITS = [
     # how firmly the tracking pass places each event: the same recurrence from the last row down over the kept forward rows, and
     # three first minima per row (track_margin_core.hpp: the arithmetic, and the call's host side)
     ("sushi_track_margins", ["-ffp-contract=off"]),     # track_core.hpp's candidates unchanged; M and C round once each
+    # score rows clamped at a threshold: a fill and a scatter of a threshold run's hits, and the rule applied to rows that exist
+    # (rows_core.hpp: the rule, the tiles, the search of a hit list, and the call's host side)
+    ("sushi_rows", []),                         # comparisons and copies: no arithmetic to contract
     # overlap-save FFT path; its parts, by stage, are csrc/sushi_fft_*.inc (included inside its anonymous namespace); the plan of
     # a batch (plan_core.hpp), what a handle holds about its requests and how it is staged (batch_core.hpp) and what a run decides
     # (run_policy.hpp) are host only

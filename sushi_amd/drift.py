@@ -169,16 +169,21 @@ class DriftMatch(Record):
                      there; its sharpness is the caller's confidence;
     rate_ties        every candidate rate whose best score equals the answer's bit for bit (events clustered near the anchor give
                      candidates the same offsets: the answer is then the lowest such rate);
-    lines            float32 [candidates][n_shift] (with_lines=True), or None."""
+    lines            float32 [candidates][n_shift] (with_lines=True), or None;
+    clamp, rows_info None, or with clamp= the float32 value f the rows were clamped at (as a float) and what forming them took
+                     (axis.event_rows' info).  score, the profile over rate, lines and the own extrema are then those of the clamped
+                     rows: an event_own_scores entry equal to f with its event_own_delta at index 0 (k_lo) means nothing in that
+                     event's window passed.  event_scores stay the true scores on the line, formed one position each."""
 
     def __repr__(self):
         return "DriftMatch(rate=%r, delta=%r, score=%r, events=%d)" % (self.rate, self.delta, float(self.score), len(self.event_scores))
 
 
 def find_drift(stream, patterns, window_centers, window_size, max_rate, resolution=1.0, weights="equal", method="sqdiff_normed",
-               with_lines=False, max_bytes=MAX_BYTES):
+               with_lines=False, max_bytes=MAX_BYTES, clamp=None, capacity=None):
     """WavStream.find_drift (its docstring)."""
     axis.method_code(method)
+    f, capacity = axis.checked_clamp(clamp, capacity, method)
     patterns, centres = list(patterns), list(window_centers)
     if not patterns or len(patterns) != len(centres):
         raise SushiError("find_drift: equally many patterns and centres (>= 1)")
@@ -202,11 +207,17 @@ def find_drift(stream, patterns, window_centers, window_size, max_rate, resoluti
     if need > max_bytes:
         raise SushiError("find_drift: %d events x %d shifts need %d bytes of curves at once, max_bytes is %d"
                          % (E, n_shift, need, max_bytes))
-    curves, row_off = axis.event_curves(dst_dev, src_dev, [ax], method)
+    info = None if f is None else {}
+    curves, row_off = axis.event_rows(dst_dev, src_dev, [ax], method, clamp=f, capacity=capacity, info=info)
     res = drift_reduce_device(curves, zip(row_off, w), n_shift, offsets, method=method, with_lines=with_lines)
     own = joint_reduce_device(curves, zip(row_off, w), [(0, E, n_shift)], method=method)
     best, score, row_score, drift_idx, drift_score = (t.cpu().numpy() for t in res[:5])
     d, j = int(best[0]), int(best[1])
+    if f is not None:
+        # every event's true score on the line: the rows hold f where nothing passes, so one position each is formed
+        from .curves import match_curves
+        row_score = match_curves(dst_dev, src_dev, ax.offs, lens, [b + k_lo + j + int(o) for b, o in zip(ax.bases, offsets[d])],
+                                 [1] * E, method=method)[0].cpu().numpy()
     ties = np.flatnonzero(drift_score.view(np.uint32) == drift_score.view(np.uint32)[d])
     return DriftMatch(
         rate=float(rates[d]), anchor=(anchor - stream.padding_size) / float(hz), delta=(k_lo + j) / float(hz), score=score[0],
@@ -215,4 +226,5 @@ def find_drift(stream, patterns, window_centers, window_size, max_rate, resoluti
         event_own_delta=[(k_lo + int(k)) / float(hz) for k in own.row_own_index.cpu().numpy()],
         event_own_scores=own.row_own_scores.cpu().numpy(),
         drift_rates=rates, drift_scores=drift_score, drift_deltas=(k_lo + drift_idx.astype(np.int64)) / float(hz),
-        rate_ties=[float(rates[t]) for t in ties], lines=res.lines.cpu().numpy() if with_lines else None)
+        rate_ties=[float(rates[t]) for t in ties], lines=res.lines.cpu().numpy() if with_lines else None,
+        clamp=None if f is None else float(f), rows_info=None if info is None else axis.merge_rows_info(None, info))

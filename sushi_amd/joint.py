@@ -104,7 +104,11 @@ class JointMatch(Record):
     k_lo, n_shift    the joint axis: displacements k_lo .. k_lo + n_shift - 1 samples (joint_window);
     event_scores     every event's own score at the joint shift (float32 array);
     event_own_delta  where every event's lone search over the same range lands (seconds, list), event_own_scores its score;
-    curve            the float32 joint row (with_curve=True), or None."""
+    curve            the float32 joint row (with_curve=True), or None;
+    clamp, rows_info None, or with clamp= the float32 value f the rows were clamped at (as a float) and what forming the group's chunk
+                     of rows took (axis.event_rows' info).  score, curve and the own extrema are then those of the clamped rows: an
+                     event_own_scores entry equal to f with its event_own_delta at index 0 (k_lo) means nothing in that event's window
+                     passed.  event_scores stay the true scores at the joint shift, formed one position each."""
 
     def __repr__(self):
         return "JointMatch(delta=%r, score=%r, events=%d)" % (self.delta, float(self.score), len(self.event_scores))
@@ -114,9 +118,11 @@ class JointMatch(Record):
 _Group = namedtuple("_Group", "first axis weights")
 
 
-def find_joint_many(stream, groups, window_sizes, weights="equal", method="sqdiff_normed", with_curve=False, max_bytes=MAX_BYTES):
+def find_joint_many(stream, groups, window_sizes, weights="equal", method="sqdiff_normed", with_curve=False, max_bytes=MAX_BYTES,
+                    clamp=None, capacity=None):
     """WavStream.find_joint_many (its docstring)."""
     axis.method_code(method)
+    f, capacity = axis.checked_clamp(clamp, capacity, method)
     groups = [(list(p), list(c)) for p, c in groups]
     window_sizes = list(window_sizes)
     if not groups or len(window_sizes) != len(groups) or any(not p or len(p) != len(c) for p, c in groups):
@@ -145,19 +151,27 @@ def find_joint_many(stream, groups, window_sizes, weights="equal", method="sqdif
             raise SushiError("find_joint_many: one group of %d events x %d shifts needs %d bytes of curves, max_bytes is %d"
                              % (len(plans[first].weights), plans[first].axis.n_shift, need, max_bytes))
         chunk = plans[first:last]
-        curves, row_off = axis.event_curves(dst_dev, src_dev, [g.axis for g in chunk], method)
+        info = None if f is None else {}
+        curves, row_off = axis.event_rows(dst_dev, src_dev, [g.axis for g in chunk], method, clamp=f, capacity=capacity, info=info)
         res = joint_reduce_device(curves, zip(row_off, [w for g in chunk for w in g.weights]),
                                   [(g.first - chunk[0].first, len(g.weights), g.axis.n_shift) for g in chunk],
                                   method=method, with_curve=with_curve)
         idx, score, row_score, row_idx, row_best = (t.cpu().numpy() for t in res[:5])
         joint = res.joint.cpu().numpy() if with_curve else None
+        if f is not None:
+            # every event's true score at its group's shift: the rows hold f where nothing passes, so one position each is formed
+            from .curves import match_curves
+            at = [b + g.axis.k_lo + int(idx[i]) for i, g in enumerate(chunk) for b in g.axis.bases]
+            row_score = match_curves(dst_dev, src_dev, [o for g in chunk for o in g.axis.offs], [m for g in chunk for m in g.axis.lens],
+                                     at, [1] * len(at), method=method)[0].cpu().numpy()
         for g, grp in enumerate(chunk):
             r0, m, k_lo = grp.first - chunk[0].first, len(grp.weights), grp.axis.k_lo
             out.append(JointMatch(
                 delta=(k_lo + int(idx[g])) / float(rate), score=score[g], index=int(idx[g]), k_lo=k_lo, n_shift=grp.axis.n_shift,
                 event_scores=row_score[r0:r0 + m].copy(),
                 event_own_delta=[(k_lo + int(k)) / float(rate) for k in row_idx[r0:r0 + m]],
-                event_own_scores=row_best[r0:r0 + m].copy(),
+                event_own_scores=row_best[r0:r0 + m].copy(), clamp=None if f is None else float(f),
+                rows_info=None if info is None else axis.merge_rows_info(None, info),
                 curve=None if joint is None else joint[int(res.joint_offsets[g]):int(res.joint_offsets[g + 1])].copy()))
         first = last
     return out

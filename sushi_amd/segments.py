@@ -162,19 +162,25 @@ class Segmentation(Record):
     segments          maximal runs of equal shift: [(first_event, n_events, delta)];
     cost              the pass's total (float64): the weighted scores (negated under 'ccoeff_normed') plus penalty per change;
     event_scores      every event's own score at its chosen shift (float32 array);
-    event_own_delta   where every event's lone search over the same range lands (seconds, list), event_own_scores its score."""
+    event_own_delta   where every event's lone search over the same range lands (seconds, list), event_own_scores its score;
+    clamp, rows_info  None, or with clamp= the float32 value f the rows were clamped at (as a float) and what forming them took
+                      (axis.event_rows' info, summed over the chunks).  The pass is then the exact minimum of the clamped problem;
+                      cost and the own extrema are those of the clamped rows: an event_own_scores entry equal to f with its
+                      event_own_delta at index 0 (k_lo) means nothing in that event's window passed.  event_scores stay the true
+                      scores at the chosen shifts, formed one position each."""
 
     def __repr__(self):
         return "Segmentation(segments=%r, cost=%r)" % (self.segments, self.cost)
 
 
 def find_segments(stream, patterns, window_centers, window_size, penalty, weights="equal", method="sqdiff_normed",
-                  max_bytes=MAX_BYTES, max_state_bytes=MAX_STATE_BYTES):
+                  max_bytes=MAX_BYTES, max_state_bytes=MAX_STATE_BYTES, clamp=None, capacity=None):
     """WavStream.find_segments (its docstring)."""
     from .curves import match_curves
     patterns, centres = list(patterns), list(window_centers)
     if not patterns or len(patterns) != len(centres):
         raise SushiError("find_segments: equally many patterns and centres (>= 1)")
+    f, capacity = axis.checked_clamp(clamp, capacity, method)
     dst_dev = stream.device_stream()
     src_dev, offs, lens, _ = stream._pattern_source(patterns, dst_dev)
     lens = axis.pattern_lengths(lens)
@@ -191,9 +197,13 @@ def find_segments(stream, patterns, window_centers, window_size, penalty, weight
         raise SushiError("find_segments: one event of %d shifts needs %d bytes of curves, max_bytes is %d"
                          % (n_shift, 4 * n_shift, max_bytes))
     state = PathState(E, n_shift, dst_dev.device)
+    rows_info = None
     for first in range(0, E, per_chunk):
         last = min(E, first + per_chunk)
-        curves, row_off = axis.event_curves(dst_dev, src_dev, [ax.part(first, last)], method)
+        info = {}
+        curves, row_off = axis.event_rows(dst_dev, src_dev, [ax.part(first, last)], method, clamp=f, capacity=capacity, info=info)
+        if f is not None:
+            rows_info = axis.merge_rows_info(rows_info, info)
         path_device(curves, zip(row_off, w[first:last].tolist()), lam, state, row0=first, method=method)
     index = path_backtrack_device(state).cpu().numpy()
     shifts = [k_lo + int(k) for k in index]
@@ -204,4 +214,4 @@ def find_segments(stream, patterns, window_centers, window_size, penalty, weight
         k_lo=k_lo, n_shift=n_shift, shifts=shifts, deltas=[k / float(rate) for k in shifts],
         segments=[(f, n, k / float(rate)) for f, n, k in runs(shifts)], cost=float(state.row_min[E - 1].item()),
         event_scores=at.cpu().numpy(), event_own_delta=[(k_lo + int(k)) / float(rate) for k in own],
-        event_own_scores=state.row_own_scores.cpu().numpy())
+        event_own_scores=state.row_own_scores.cpu().numpy(), clamp=None if f is None else float(f), rows_info=rows_info)

@@ -368,12 +368,13 @@ def calculate_shifts_at_speed(src_stream, dst_stream, groups_list, speed, normal
     return result
 
 
-def calculate_group_shifts(src_stream, dst_stream, groups, window, centre_shifts=0.0):
+def calculate_group_shifts(src_stream, dst_stream, groups, window, centre_shifts=0.0, clamp=None, capacity=None):
     """One shift per group of events, found jointly (sushi_amd.joint; DESIGN.md 3.15): `groups` is a list of lists of ScriptEvent;
     every event's pattern is src_stream.get_substream(e.start, e.end) and its centre e.start + centre_shift (centre_shifts: one
     number for all groups, or one per group).  All groups go through one dst_stream.find_joint_many call with window `window`
     (seconds).  Every event gets set_shift(centre_shift + delta, its own score at the joint shift).  SushiError for an event whose
-    pattern is empty.  Returns the JointMatch of every group."""
+    pattern is empty.  clamp, capacity: find_joint_many's (rows clamped at a threshold; the scores the events get stay the true ones).
+    Returns the JointMatch of every group."""
     groups = [list(g) for g in groups]
     try:
         shifts = [float(s) for s in centre_shifts]
@@ -388,19 +389,20 @@ def calculate_group_shifts(src_stream, dst_stream, groups, window, centre_shifts
             if p.shape[1] < 1:
                 raise SushiError("calculate_group_shifts: event %s has no samples in the source" % e)
         requests.append((patterns, [e.start + shift for e in group]))
-    matches = dst_stream.find_joint_many(requests, [window] * len(groups))
+    kw = {} if clamp is None and capacity is None else dict(clamp=clamp, capacity=capacity)
+    matches = dst_stream.find_joint_many(requests, [window] * len(groups), **kw)
     for group, shift, match in zip(groups, shifts, matches):
         for e, score in zip(group, match.event_scores):
             e.set_shift(shift + match.delta, score)
     return matches
 
 
-def calculate_segmented_shifts(src_stream, dst_stream, events, window, penalty, centre_shift=0.0):
+def calculate_segmented_shifts(src_stream, dst_stream, events, window, penalty, centre_shift=0.0, clamp=None, capacity=None):
     """A shift per event, changing only where a change pays (sushi_amd.segments): `events` is a list of ScriptEvent
     in order; every event's pattern is src_stream.get_substream(e.start, e.end) and its centre e.start + centre_shift.  All go
     through one dst_stream.find_segments call with window `window` (seconds) and `penalty` (its docstring).  Every event gets
-    set_shift(centre_shift + its delta, its own score there).  SushiError for an event whose pattern is empty.  Returns the
-    Segmentation."""
+    set_shift(centre_shift + its delta, its own score there).  SushiError for an event whose pattern is empty.  clamp, capacity:
+    find_segments' (rows clamped at a threshold; the scores the events get stay the true ones).  Returns the Segmentation."""
     events = list(events)
     shift = float(centre_shift)
     if not events:
@@ -409,20 +411,22 @@ def calculate_segmented_shifts(src_stream, dst_stream, events, window, penalty, 
     for e, p in zip(events, patterns):
         if p.shape[1] < 1:
             raise SushiError("calculate_segmented_shifts: event %s has no samples in the source" % e)
-    found = dst_stream.find_segments(patterns, [e.start + shift for e in events], window, penalty)
+    kw = {} if clamp is None and capacity is None else dict(clamp=clamp, capacity=capacity)
+    found = dst_stream.find_segments(patterns, [e.start + shift for e in events], window, penalty, **kw)
     for e, delta, score in zip(events, found.deltas, found.event_scores):
         e.set_shift(shift + delta, score)
     return found
 
 
 def calculate_tracked_shifts(src_stream, dst_stream, events, window, penalty, max_rate=None, reach=None, step_cost=0.0,
-                             centre_shift=0.0, margins=False, guard=None, marginals=False):
+                             centre_shift=0.0, margins=False, guard=None, marginals=False, clamp=None, capacity=None):
     """A shift per event that may move a little between events and jump where a jump pays (sushi_amd.track):
     `events` is a list of ScriptEvent in order; every event's pattern is src_stream.get_substream(e.start, e.end) and its centre
     e.start + centre_shift.  All go through one dst_stream.find_track call with window `window` (seconds), `penalty`, and max_rate
     or reach and step_cost (its docstring).  Every event gets set_shift(centre_shift + its delta, its own score there).  SushiError
     for an event whose pattern is empty.  margins, guard and marginals are find_track's: with margins=True the Track also says how
-    firmly every event is placed (event_margin, event_alt_delta, ...).  Returns the Track."""
+    firmly every event is placed (event_margin, event_alt_delta, ...).  clamp, capacity: find_track's (rows clamped at a threshold;
+    the scores the events get stay the true ones).  Returns the Track."""
     events = list(events)
     shift = float(centre_shift)
     if not events:
@@ -432,18 +436,21 @@ def calculate_tracked_shifts(src_stream, dst_stream, events, window, penalty, ma
         if p.shape[1] < 1:
             raise SushiError("calculate_tracked_shifts: event %s has no samples in the source" % e)
     found = dst_stream.find_track(patterns, [e.start + shift for e in events], window, penalty, max_rate=max_rate, reach=reach,
-                                  step_cost=step_cost, margins=margins, guard=guard, marginals=marginals)
+                                  step_cost=step_cost, margins=margins, guard=guard, marginals=marginals,
+                                  **({} if clamp is None and capacity is None else dict(clamp=clamp, capacity=capacity)))
     for e, delta, score in zip(events, found.deltas, found.event_scores):
         e.set_shift(shift + delta, score)
     return found
 
 
-def calculate_drifting_shifts(src_stream, dst_stream, events, window, max_rate, centre_shift=0.0, resolution=1.0):
+def calculate_drifting_shifts(src_stream, dst_stream, events, window, max_rate, centre_shift=0.0, resolution=1.0, clamp=None,
+                              capacity=None):
     """A shift per event along one line of shifts (sushi_amd.drift): `events` is a list of ScriptEvent; every
     event's pattern is src_stream.get_substream(e.start, e.end) and its centre e.start + centre_shift.  All go through one
     dst_stream.find_drift call with window `window` (seconds), rates out to +-max_rate and `resolution` (its docstring).  Every
     event gets set_shift(centre_shift + its event_delta, its own score there).  SushiError for an event whose pattern is empty.
-    Returns the DriftMatch."""
+    clamp, capacity: find_drift's (rows clamped at a threshold; the scores the events get stay the true ones).  Returns the
+    DriftMatch."""
     events = list(events)
     shift = float(centre_shift)
     if not events:
@@ -452,7 +459,8 @@ def calculate_drifting_shifts(src_stream, dst_stream, events, window, max_rate, 
     for e, p in zip(events, patterns):
         if p.shape[1] < 1:
             raise SushiError("calculate_drifting_shifts: event %s has no samples in the source" % e)
-    found = dst_stream.find_drift(patterns, [e.start + shift for e in events], window, max_rate, resolution=resolution)
+    kw = {} if clamp is None and capacity is None else dict(clamp=clamp, capacity=capacity)
+    found = dst_stream.find_drift(patterns, [e.start + shift for e in events], window, max_rate, resolution=resolution, **kw)
     for e, delta, score in zip(events, found.event_deltas, found.event_scores):
         e.set_shift(shift + delta, score)
     return found

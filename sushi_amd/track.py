@@ -380,7 +380,13 @@ class Track(Record):
     cost              the pass's total (float64): the weighted scores (negated under 'ccoeff_normed') plus step_cost per sample
                       moved plus penalty per jump;
     event_scores      every event's own score at its chosen shift (float32 array);
-    event_own_delta   where every event's lone search over the same range lands (seconds, list), event_own_scores its score.
+    event_own_delta   where every event's lone search over the same range lands (seconds, list), event_own_scores its score;
+    clamp, rows_info  None, or with clamp= the float32 value f the rows were clamped at (as a float) and what forming them took
+                      (axis.event_rows' info, summed over every forming of a chunk, the second one for margins included).  The pass
+                      -- and its margins -- is then the exact minimum of the clamped problem; cost and the own extrema are those of
+                      the clamped rows: an event_own_scores entry equal to f with its event_own_delta at index 0 (k_lo) means
+                      nothing in that event's window passed.  event_scores stay the true scores at the chosen shifts, formed one
+                      position each.
     With margins=True (else None), how firmly every event is placed:
     guard             every event's guard in samples (list of int);
     event_through     the cost of the best whole path through every event's chosen shift (float64 array: the total, up to
@@ -401,7 +407,7 @@ class Track(Record):
 
 def find_track(stream, patterns, window_centers, window_size, penalty, max_rate=None, reach=None, step_cost=0.0, slack=1,
                weights="equal", method="sqdiff_normed", max_bytes=MAX_BYTES, max_state_bytes=MAX_STATE_BYTES, margins=False,
-               guard=None, marginals=False):
+               guard=None, marginals=False, clamp=None, capacity=None):
     """WavStream.find_track (its docstring)."""
     import torch
     from .curves import match_curves
@@ -413,6 +419,7 @@ def find_track(stream, patterns, window_centers, window_size, penalty, max_rate=
     margins, marginals = bool(margins), bool(marginals)
     if not margins and (marginals or guard is not None):
         raise SushiError("find_track: guard and marginals belong to margins=True")
+    f, capacity = axis.checked_clamp(clamp, capacity, method)
     dst_dev = stream.device_stream()
     src_dev, offs, lens, _ = stream._pattern_source(patterns, dst_dev)
     lens = axis.pattern_lengths(lens)
@@ -438,8 +445,17 @@ def find_track(stream, patterns, window_centers, window_size, penalty, max_rate=
     state = TrackState(E, n_shift, dst_dev.device, keep=margins)
     forward = track_forward_keep_device if margins else track_device
     chunks = [(first, min(E, first + per_chunk)) for first in range(0, E, per_chunk)]
+    rows_info = [None]
+
+    def form(first, last):
+        info = {}
+        formed = axis.event_rows(dst_dev, src_dev, [ax.part(first, last)], method, clamp=f, capacity=capacity, info=info)
+        if f is not None:
+            rows_info[0] = axis.merge_rows_info(rows_info[0], info)
+        return formed
+
     for first, last in chunks:
-        curves, row_off = axis.event_curves(dst_dev, src_dev, [ax.part(first, last)], method)
+        curves, row_off = form(first, last)
         forward(curves, zip(row_off, w[first:last].tolist()), reach[first:last], lam, mu, state, row0=first, method=method)
     index_dev = track_backtrack_device(state)
     extra = dict(guard=None, event_through=None, event_margin=None, event_alt_shift=None, event_alt_delta=None, marginals=None)
@@ -448,7 +464,7 @@ def find_track(stream, patterns, window_centers, window_size, penalty, max_rate=
         M = torch.empty(E * n_shift, dtype=torch.float64, device=state.D.device) if marginals else None
         for first, last in reversed(chunks):
             if len(chunks) > 1:
-                curves, row_off = axis.event_curves(dst_dev, src_dev, [ax.part(first, last)], method)
+                curves, row_off = form(first, last)
             track_margins_device(curves, zip(row_off, w[first:last].tolist()), reach[first:last + 1 if last < E else last],
                                  guard[first:last], lam, mu, state, index_dev, row0=first, method=method, marginals=M)
         through, alt, alt_arg = state.through.cpu().numpy(), state.alt.cpu().numpy(), state.alt_arg.cpu().numpy()
@@ -470,7 +486,8 @@ def find_track(stream, patterns, window_centers, window_size, penalty, max_rate=
         moves=[0] + [b - a for a, b in zip(shifts[:-1], shifts[1:])], jumps=jumps,
         segments=[(f, n, shifts[f] / float(rate), shifts[f + n - 1] / float(rate)) for f, n in jump_runs(E, jumps)],
         cost=float(state.row_min[E - 1].item()), event_scores=at.cpu().numpy(),
-        event_own_delta=[(k_lo + int(k)) / float(rate) for k in own], event_own_scores=state.row_own_scores.cpu().numpy(), **extra)
+        event_own_delta=[(k_lo + int(k)) / float(rate) for k in own], event_own_scores=state.row_own_scores.cpu().numpy(),
+        clamp=None if f is None else float(f), rows_info=rows_info[0], **extra)
 
 
 def _arange_like(index_dev):

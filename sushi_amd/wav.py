@@ -564,14 +564,16 @@ class WavStream(object):
         return [curves[int(bounds[k]):int(bounds[k + 1])].reshape(1, -1) for k in range(n)]
 
     # ------------------------------------------------------------------ one shift for a group
-    def find_joint(self, patterns, window_centers, window_size, weights='equal', method="sqdiff_normed", with_curve=False):
+    def find_joint(self, patterns, window_centers, window_size, weights='equal', method="sqdiff_normed", with_curve=False, clamp=None,
+                   capacity=None):
         """The one shift a group of patterns shares (sushi_amd.joint): pattern i is looked for at
         window_centers[i] + delta for one delta, |delta| <= window_size, scored by the weighted sum of every pattern's own score row
-        at that displacement.  Returns a JointMatch (find_joint_many)."""
+        at that displacement.  clamp, capacity: find_joint_many's.  Returns a JointMatch (find_joint_many)."""
         return self.find_joint_many([(patterns, window_centers)], [window_size], method=method, with_curve=with_curve,
-                                    weights=weights if isinstance(weights, str) else [weights])[0]
+                                    weights=weights if isinstance(weights, str) else [weights], clamp=clamp, capacity=capacity)[0]
 
-    def find_joint_many(self, groups, window_sizes, weights='equal', method="sqdiff_normed", with_curve=False, max_bytes=None):
+    def find_joint_many(self, groups, window_sizes, weights='equal', method="sqdiff_normed", with_curve=False, max_bytes=None,
+                        clamp=None, capacity=None):
         """[find_joint(p, c, w) for (p, c), w in zip(groups, window_sizes)]: groups is a list of (patterns, window_centers).
         Patterns are located as find_substreams locates them.  Event i of a group sits at sample bases[i] + k,
         bases[i] = _get_sample_for_time(window_centers[i]), for the displacements k every event of the group can take within
@@ -582,14 +584,27 @@ class WavStream(object):
         the sum) or 'ccoeff_normed' (first maximum).  Returns a JointMatch per group: delta (seconds; event i is found at
         window_centers[i] + delta), score, index, event_scores (every event's own score at the joint shift), event_own_delta /
         event_own_scores (what a lone search of each event over the same range finds), curve (with_curve: the float32 joint row).
+        clamp (default None: nothing changes): a finite number; every event's row is then CLAMPED at f = the float32 on the failing
+        side of it (sushi_amd.axis.clamp_value) -- min(R, f) under 'sqdiff_normed', max(R, f) under 'ccoeff_normed' -- and formed
+        from the hits of one threshold run per chunk instead of as a whole exact row (sushi_amd.axis.event_rows): a
+        position that does not pass the clamp counts as f, however badly it matches.  The answer is the exact answer of the clamped
+        problem.  capacity: hits kept per event before its row is formed densely instead (None: min(n_shift, max(1024, n_shift //
+        16))).  The result's event_scores stay the true scores at the chosen shift, formed one position each; an event's own
+        extremum (event_own_scores) equal to f at index 0 of the axis means nothing in its window passed; clamp and rows_info say
+        what was done.  Clamping pays where the threshold run's pair bound can exclude most of the window at f, and costs where
+        it cannot (64 events of 3 s, +-120 s windows at 12 kHz, one MI355X): at coefficient 0.5 the run evaluates
+        110 of 7564 block pairs and the whole search takes a tenth (uint8) to a thirtieth (float32) of clamp=None's time; at
+        coefficient 0.3 the bound excludes nothing, every pair is evaluated and the search is 0.83 - 0.90 x as fast as clamp=None;
+        a clamp that most positions pass overflows every event, which is then formed densely on top of the run: 0.45 x.  Exact
+        rows of short uint8 windows are cheap: there clamp=None is the faster call.
         Needs a GPU."""
         from . import joint
         return joint.find_joint_many(self, groups, window_sizes, weights=weights, method=method, with_curve=with_curve,
-                                     max_bytes=joint.MAX_BYTES if max_bytes is None else int(max_bytes))
+                                     max_bytes=joint.MAX_BYTES if max_bytes is None else int(max_bytes), clamp=clamp, capacity=capacity)
 
     # ------------------------------------------------------------------ where the shared shift changes
     def find_segments(self, patterns, window_centers, window_size, penalty, weights='equal', method="sqdiff_normed", max_bytes=None,
-                      max_state_bytes=None):
+                      max_state_bytes=None, clamp=None, capacity=None):
         """A shift for every event of a sequence, and the places where it changes (sushi_amd.segments): the events
         (patterns, window_centers: in order) are put on one shift axis -- the displacements k every event can take within
         W = int(sample_rate * window_size) samples inside the row (sushi_amd.joint.joint_window over all of them), event i at
@@ -605,16 +620,18 @@ class WavStream(object):
         x 8 + n_shift x 8 bytes, must fit max_state_bytes (default 2 GiB; SushiError names the need).  Returns a Segmentation:
         k_lo, n_shift, shifts (samples per event), deltas (seconds), segments ([(first_event, n_events, delta)]: maximal runs of
         equal shift), cost, event_scores (every event's score at its chosen shift), event_own_delta / event_own_scores (what a
-        lone search of each event over the same range finds).  Needs a GPU."""
+        lone search of each event over the same range finds).  clamp, capacity: find_joint_many's -- the pass then runs on rows
+        clamped at f and is the exact minimum of that clamped problem (the truncated cost of labelling passes).  Needs a GPU."""
         from . import segments
         return segments.find_segments(self, patterns, window_centers, window_size, penalty, weights=weights, method=method,
                                       max_bytes=segments.MAX_BYTES if max_bytes is None else int(max_bytes),
-                                      max_state_bytes=segments.MAX_STATE_BYTES if max_state_bytes is None else int(max_state_bytes))
+                                      max_state_bytes=segments.MAX_STATE_BYTES if max_state_bytes is None else int(max_state_bytes),
+                                      clamp=clamp, capacity=capacity)
 
     # ------------------------------------------------------------------ a shift that wanders, and may jump
     def find_track(self, patterns, window_centers, window_size, penalty, max_rate=None, reach=None, step_cost=0.0, slack=1,
                    weights='equal', method="sqdiff_normed", max_bytes=None, max_state_bytes=None, margins=False, guard=None,
-                   marginals=False):
+                   marginals=False, clamp=None, capacity=None):
         """A shift for every event of a sequence that may move a little from event to event and jump at a cut
         (sushi_amd.track): the events (patterns, window_centers: in order) are put on one shift axis as
         find_segments puts them, and a shift is chosen per event that minimises the sum of the events' weighted scores plus, between
@@ -639,17 +656,18 @@ class WavStream(object):
         + 2 x n_shift x 8 bytes (and E x n_shift x 8 for marginals), count under max_state_bytes.  A sequence that goes through in
         one chunk of max_bytes keeps its curves; one in several chunks forms every chunk's curves a second time, which doubles the
         curve work.  With margins=False (the default) nothing changes and the new fields are None.  find_segments' margins are
-        find_track(reach=0, margins=True).  Needs a GPU."""
+        find_track(reach=0, margins=True).  clamp, capacity: find_joint_many's -- the pass and its margins then run on rows clamped
+        at f (every forming of a chunk, the second one for margins included) and are exact for that clamped problem.  Needs a GPU."""
         from . import track
         return track.find_track(self, patterns, window_centers, window_size, penalty, max_rate=max_rate, reach=reach,
                                 step_cost=step_cost, slack=slack, weights=weights, method=method,
                                 max_bytes=track.MAX_BYTES if max_bytes is None else int(max_bytes),
                                 max_state_bytes=track.MAX_STATE_BYTES if max_state_bytes is None else int(max_state_bytes),
-                                margins=margins, guard=guard, marginals=marginals)
+                                margins=margins, guard=guard, marginals=marginals, clamp=clamp, capacity=capacity)
 
     # ------------------------------------------------------------------ a shift that moves along the programme
     def find_drift(self, patterns, window_centers, window_size, max_rate, resolution=1.0, weights='equal', method="sqdiff_normed",
-                   with_lines=False, max_bytes=None):
+                   with_lines=False, max_bytes=None, clamp=None, capacity=None):
         """The line of shifts a sequence of events shares when source and destination run at slightly different rates
         (sushi_amd.drift).  The events (patterns, window_centers) are put on one shift axis -- the displacements k
         every event can take within W = int(sample_rate * window_size) samples inside the row (sushi_amd.joint.joint_window over
@@ -665,10 +683,12 @@ class WavStream(object):
         DriftMatch: rate, anchor (seconds), delta (the shift at the anchor), score, index, k_lo, n_shift, event_deltas /
         event_scores (every event on the line), event_own_delta / event_own_scores (its lone search), drift_rates / drift_scores /
         drift_deltas (the profile over rate), rate_ties, lines (with_lines).  A large speed difference goes through estimate_speed
-        and retimed first; this finds the residual.  Needs a GPU."""
+        and retimed first; this finds the residual.  clamp, capacity: find_joint_many's -- the lines are then summed over rows
+        clamped at f.  Needs a GPU."""
         from . import drift
         return drift.find_drift(self, patterns, window_centers, window_size, max_rate, resolution=resolution, weights=weights,
-                                method=method, with_lines=with_lines, max_bytes=drift.MAX_BYTES if max_bytes is None else int(max_bytes))
+                                method=method, with_lines=with_lines, max_bytes=drift.MAX_BYTES if max_bytes is None else int(max_bytes),
+                                clamp=clamp, capacity=capacity)
 
     # ------------------------------------------------------------------ another clock
     def retimed(self, speed):
