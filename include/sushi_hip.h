@@ -53,7 +53,9 @@ extern "C" {
                                      13 (additive): sushi_hip_drift_bytes, sushi_hip_drift_reduce;
                                      13 (additive): SUSHI_HIP_TRACK_MAX_REACH, SUSHI_HIP_TRACK_JUMP, sushi_hip_track_bytes,
                                      sushi_hip_track_forward, sushi_hip_track_backtrack;
-                                     13 (additive): sushi_hip_track_forward_keep, sushi_hip_track_margins_bytes, sushi_hip_track_margins */
+                                     13 (additive): sushi_hip_track_forward_keep, sushi_hip_track_margins_bytes, sushi_hip_track_margins;
+                                     13 (additive): SUSHI_HIP_TRACK_BACK_ANY, sushi_hip_track_order_bytes,
+                                     sushi_hip_track_forward_ordered, sushi_hip_track_backtrack_ordered */
 
 #if defined(__GNUC__)
 #define SUSHI_HIP_API __attribute__((visibility("default")))
@@ -700,6 +702,56 @@ SUSHI_HIP_API int sushi_hip_track_margins(const float* curves_dev, int64_t n_cur
                                           double* through_dev, double* best_dev, int32_t* best_arg_dev,
                                           double* alt_dev, int32_t* alt_arg_dev, double* M_dev,
                                           void* mem_dev, size_t mem_bytes, void* hip_stream);
+
+/* ---- ordered tracking: tracked events kept in order -- one-sided jumps, a penalty per event (13, additive) -------
+ * "tracking" lets a jump go anywhere at one fixed penalty.  But no cut puts an event in the destination before the end of the event
+ * in front of it: inserted material raises the shift by any amount, removed material lowers it by at most what lay between the two
+ * events.  And a caller may know where a cut is cheap (a chapter mark, a long silence) and where it is dear.  So here a jump into
+ * row e may lower the shift index by at most back_e (int32 >= 0, or SUSHI_HIP_TRACK_BACK_ANY: no limit), and costs penalty_e, row
+ * e's own (float64, finite and >= 0); row 0's back and penalty are ignored.  Moves are not restricted by the backs: a reach says how
+ * far the clock may wander either way.  Everything else -- u_e, D_0, m_e, a_e, reach_e, step_cost, the candidates cand(d) and
+ * near_e[j] with its tie rule, the move words -- is "tracking"'s; float64, products and sums round separately.  For e >= 1:
+ *     P_{e-1}[t] = min D_{e-1}[0 .. t];  A_{e-1}[t] = the FIRST index that attains it (scanning upwards with a strict <: 0.0 and
+ *                  -0.0 tie);  P_{e-1}[t] is D_{e-1}[A_{e-1}[t]] itself, so a zero keeps its sign
+ *     t_e(j)     = min(j + back_e, n_shift - 1), formed in 64 bits;  n_shift - 1 where back_e is SUSHI_HIP_TRACK_BACK_ANY
+ *     jump_e[j]  = P_{e-1}[t_e(j)] + penalty_e
+ *     take_near  = (near_e[j] <= jump_e[j])  (a tie moves);  D_e[j] = u_e[j] + (take_near ? near_e[j] : jump_e[j])
+ *     move_e[j]  = the winning d (int16), or SUSHI_HIP_TRACK_JUMP
+ *     backtrack:   s_{E-1} = a_{E-1};  for e = E-1 .. 1:
+ *                  s_{e-1} = move_e[s_e] == SUSHI_HIP_TRACK_JUMP ? A_{e-1}[t_e(s_e)] : s_e + move_e[s_e]
+ * The total cost is m_{E-1}: the minimum over all paths whose jumps obey s_e >= s_{e-1} - back_e, accumulated in "tracking"'s order
+ * with penalty_e for a jump into event e.  With every back SUSHI_HIP_TRACK_BACK_ANY (or >= n_shift - 1) and one penalty the pass is
+ * sushi_hip_track_forward + sushi_hip_track_backtrack bit for bit.  Rows are assumed finite; with a NaN the results are
+ * unspecified, but no access leaves the buffers. */
+#define SUSHI_HIP_TRACK_BACK_ANY (-1)
+/* workspace of an ordered forward call (one set of per-workgroup partial records, and per work item of the axis one (minimum, first
+ * index) record and the same of everything before the item); 0 for n_rows < 1 or n_shift < 1 */
+SUSHI_HIP_API size_t sushi_hip_track_order_bytes(int n_rows, int32_t n_shift);
+/* sushi_hip_track_forward for the ordered pass.  penalty_host[i] and back_host[i] are row row0 + i's, as rows_host[i] and
+ * reach_host[i] are.  The state it adds to sushi_hip_track_forward's: P_dev, [n_shift] float64 (P of the last row advanced);
+ * from_dev, [n_total][n_shift] int32 (row e holds A_e); back_dev, [n_total] int32 (every advanced row's back, left there for the
+ * backtrack).  row0 > 0 continues from D_dev and P_dev as the call before it on the same stream left them: a sequence in chunks has
+ * the bits of one call.  No device allocation, no upload: three launches per row, stream-ordered -- the step, a scan of one record
+ * per work item, and the prefix minimum of the row just written -- and the launch boundary is their only synchronisation.
+ * Asynchronous; stateless.  Checked before any HIP call -- EINVAL: everything sushi_hip_track_forward refuses (the penalty: per
+ * row, in any row but the sequence's row 0), a null back or penalty table, a null P_dev / from_dev / back_dev, a back below
+ * SUSHI_HIP_TRACK_BACK_ANY; EALIGN: mem_dev not 256-byte aligned; ENOSPACE: mem_bytes < sushi_hip_track_order_bytes; EALIGN: D_dev
+ * / P_dev / row_min_dev not 8-byte aligned, a float / int32 pointer not 4-byte aligned, move_dev not 2-byte aligned. */
+SUSHI_HIP_API int sushi_hip_track_forward_ordered(const float* curves_dev, int64_t n_curve,
+                                                  const SushiHipJointRow* rows_host, const int32_t* reach_host,
+                                                  const int32_t* back_host, int n_rows, int32_t n_shift,
+                                                  int method, const double* penalty_host, double step_cost, int row0, int n_total,
+                                                  double* D_dev, int16_t* move_dev,
+                                                  double* P_dev, int32_t* from_dev, int32_t* back_dev,
+                                                  double* row_min_dev, int32_t* row_arg_dev,
+                                                  int32_t* row_own_index_dev, float* row_own_score_dev,
+                                                  void* mem_dev, size_t mem_bytes, void* hip_stream);
+/* out_shift_dev[e] = s_e for the n_total rows of a sequence whose ordered forward calls lie before it on the stream.  One wave,
+ * one lane walking n_total dependent reads.  EINVAL: a null pointer, n_total < 1, n_shift < 1; EALIGN: move_dev not 2-byte aligned,
+ * an int32 pointer not 4-byte aligned. */
+SUSHI_HIP_API int sushi_hip_track_backtrack_ordered(const int16_t* move_dev, const int32_t* from_dev, const int32_t* back_dev,
+                                                    const int32_t* row_arg_dev, int n_total, int32_t n_shift,
+                                                    int32_t* out_shift_dev, void* hip_stream);
 
 /* ---- rows: score rows clamped at a threshold, formed from a threshold run's hits (13, additive) ---------------
  * A pass over a shift axis needs to know where a row is good and how good; how bad the rest is only feeds decoys.  The CLAMPED row

@@ -53,6 +53,9 @@ UNITS = [
     # how firmly the tracking pass places each event: the same recurrence from the last row down over the kept forward rows, and
     # three first minima per row (track_margin_core.hpp: the arithmetic, and the call's host side)
     ("sushi_track_margins", ["-ffp-contract=off"]),     # track_core.hpp's candidates unchanged; M and C round once each
+    # tracked events kept in order: the tracking step with a jump read per index from the prefix minimum of the row before, and
+    # per row a scan of (minimum, first index) that writes it (track_order_core.hpp: the combine rule, the call's host side, the walker)
+    ("sushi_track_order", ["-ffp-contract=off"]),       # track_core.hpp's candidates unchanged; the jump's sum rounds once
     # score rows clamped at a threshold: a fill and a scatter of a threshold run's hits, and the rule applied to rows that exist
     # (rows_core.hpp: the rule, the tiles, the search of a hit list, and the call's host side)
     ("sushi_rows", []),                         # comparisons and copies: no arithmetic to contract

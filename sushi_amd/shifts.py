@@ -418,15 +418,35 @@ def calculate_segmented_shifts(src_stream, dst_stream, events, window, penalty, 
     return found
 
 
+def chapter_penalties(events, chapter_times, penalty, chapter_penalty):
+    """One penalty per event for find_track / calculate_tracked_shifts: `chapter_penalty` for an event whose chapter differs from
+    that of the event before it, `penalty` for every other one (event 0 gets `penalty`; its value is ignored by the pass).  Cuts
+    happen at chapter marks, which is why the reference groups events by chapter: a change of shift is cheap there and dear inside a
+    chapter.  chapter_times are the chapters' start points in seconds (the first one opens the first chapter and decides nothing);
+    an event belongs to the chapter its END falls in -- the number of later start points below its end --, as in
+    grouping.groups_from_chapters.  SushiError for a penalty that is not a finite number >= 0."""
+    try:
+        inside, across = float(penalty), float(chapter_penalty)
+        limits = sorted(float(t) for t in list(chapter_times)[1:])
+    except (TypeError, ValueError):
+        raise SushiError("chapter_penalties: penalties and chapter times are numbers")
+    if not (np.isfinite(inside) and inside >= 0 and np.isfinite(across) and across >= 0):
+        raise SushiError("chapter_penalties: penalties must be finite and >= 0")
+    chapters = [sum(1 for t in limits if e.end > t) for e in events]
+    return [inside] + [across if b != a else inside for a, b in zip(chapters[:-1], chapters[1:])] if chapters else []
+
+
 def calculate_tracked_shifts(src_stream, dst_stream, events, window, penalty, max_rate=None, reach=None, step_cost=0.0,
-                             centre_shift=0.0, margins=False, guard=None, marginals=False, clamp=None, capacity=None):
+                             centre_shift=0.0, margins=False, guard=None, marginals=False, clamp=None, capacity=None, order=None):
     """A shift per event that may move a little between events and jump where a jump pays (sushi_amd.track):
     `events` is a list of ScriptEvent in order; every event's pattern is src_stream.get_substream(e.start, e.end) and its centre
     e.start + centre_shift.  All go through one dst_stream.find_track call with window `window` (seconds), `penalty`, and max_rate
     or reach and step_cost (its docstring).  Every event gets set_shift(centre_shift + its delta, its own score there).  SushiError
     for an event whose pattern is empty.  margins, guard and marginals are find_track's: with margins=True the Track also says how
     firmly every event is placed (event_margin, event_alt_delta, ...).  clamp, capacity: find_track's (rows clamped at a threshold;
-    the scores the events get stay the true ones).  Returns the Track."""
+    the scores the events get stay the true ones).  order: find_track's (None; True: the events are kept in order in the
+    destination; or one back per event), and `penalty` may be one number per event (chapter_penalties gives them from chapter marks):
+    either takes the ordered pass, which has no margins.  Returns the Track."""
     events = list(events)
     shift = float(centre_shift)
     if not events:
@@ -437,7 +457,8 @@ def calculate_tracked_shifts(src_stream, dst_stream, events, window, penalty, ma
             raise SushiError("calculate_tracked_shifts: event %s has no samples in the source" % e)
     found = dst_stream.find_track(patterns, [e.start + shift for e in events], window, penalty, max_rate=max_rate, reach=reach,
                                   step_cost=step_cost, margins=margins, guard=guard, marginals=marginals,
-                                  **({} if clamp is None and capacity is None else dict(clamp=clamp, capacity=capacity)))
+                                  **dict({} if clamp is None and capacity is None else dict(clamp=clamp, capacity=capacity),
+                                         **({} if order is None else dict(order=order))))
     for e, delta, score in zip(events, found.deltas, found.event_scores):
         e.set_shift(shift + delta, score)
     return found

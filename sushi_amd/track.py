@@ -11,6 +11,10 @@ minimum over all assignments (include/sushi_hip.h "tracking").  
   ``sushi_hip_track_forward`` on a chunk of its rows, and the backtrack.
 * ``find_track`` -- what ``WavStream.find_track`` runs: per chunk of events one ``match_curves`` call and one forward call, then
   one backtrack.
+* ``track_ordered_host`` / ``TrackState(ordered=True)`` / ``track_ordered_device`` / ``track_ordered_backtrack_device`` -- the pass
+  with events kept in order (include/sushi_hip.h "ordered tracking"): a jump into event e may lower the shift by at
+  most ``back_e`` samples and costs ``penalty_e``; ``order_back`` gives the backs of a list of events; ``find_track(order=...)`` and a
+  ``penalty`` per event run it.
 * ``track_margins_host`` / ``track_forward_keep_device`` / ``track_margins_device`` -- how firmly each event is placed: the pass's
   min-marginals (include/sushi_hip.h "margins"), in NumPy and on the device; ``find_track(margins=True)`` runs them.
 """
@@ -31,6 +35,8 @@ TrackHost = namedtuple("TrackHost", "shifts cost row_min row_arg moves row_own_i
 TrackMarginsHost = namedtuple("TrackMarginsHost", TrackHost._fields + ("D", "marginals", "through", "best", "best_arg", "alt", "alt_arg",
                                                                        "c_min"))
 NO_ALT = -1                   # alt_arg where no shift lies outside the guard window
+BACK_ANY = _native.TRACK_BACK_ANY        # a back that leaves a jump free to come from anywhere
+TrackOrderedHost = namedtuple("TrackOrderedHost", TrackHost._fields + ("prefix_arg",))
 
 
 def _checked(weights, n, penalty, step_cost, method):
@@ -153,6 +159,137 @@ def backtrack_host(moves, row_arg):
     return shifts
 
 
+def checked_penalties(penalty, n, first_row=0):
+    """`penalty` -- one number for every row, or a sequence of n -- as a float64 array of n finite values >= 0; the value of the
+    sequence's row 0 (first_row == 0: entry 0) is ignored and returned as 0.  SushiError names the row and the value otherwise."""
+    try:
+        p = [float(penalty)] * n if np.ndim(penalty) == 0 else [float(x) for x in penalty]
+    except (TypeError, ValueError):
+        raise SushiError("track: penalty is a number, or one number per row")
+    if len(p) != n:
+        raise SushiError("track: as many penalties as rows (%d penalties, %d rows)" % (len(p), n))
+    if first_row == 0 and p:
+        p[0] = 0.0
+    for i, x in enumerate(p):
+        if not np.isfinite(x) or x < 0:
+            raise SushiError("track: the penalty of event %d is %r, not finite and >= 0" % (first_row + i, x))
+    return np.array(p, np.float64)
+
+
+def checked_back(back, n, first_row=0):
+    """`back` -- one value for every row, or a sequence of n; an int >= 0, or -1 or None for no limit -- as an int32 array of n
+    values in -1 .. 2^31 - 1.  SushiError names the row and the value otherwise."""
+    try:
+        b = [back] * n if back is None or np.ndim(back) == 0 else list(back)
+        b = [BACK_ANY if x is None else int(x) for x in b]
+    except (TypeError, ValueError):
+        raise SushiError("track: a back is an int or None, one for every row or one per row")
+    if len(b) != n:
+        raise SushiError("track: as many backs as rows (%d backs, %d rows)" % (len(b), n))
+    for i, x in enumerate(b):
+        if x < BACK_ANY or x > 2 ** 31 - 1:
+            raise SushiError("track: the back of event %d is %d, outside -1 .. 2^31 - 1" % (first_row + i, x))
+    return np.array(b, np.int32)
+
+
+def order_back(bases, lens, slack=0):
+    """back_e = max(base_e - base_{e-1} - len_{e-1}, 0) + slack for e >= 1, no limit (-1) for event 0: by how much the shift may drop
+    in a jump into event e if the event is to lie, in the destination, behind the end of the event in front of it -- base_e the
+    destination sample of event e at shift 0, len_e its pattern's length; `slack` samples for the events' own rounding.  SushiError
+    if the bases decrease."""
+    try:
+        bases, lens, slack = [int(b) for b in bases], [int(m) for m in lens], int(slack)
+    except (TypeError, ValueError):
+        raise SushiError("order_back: bases, lens and slack are ints")
+    if not bases or len(bases) != len(lens) or slack < 0 or min(lens) < 0:
+        raise SushiError("order_back: as many lengths (>= 0) as bases (>= 1), slack >= 0")
+    for e in range(1, len(bases)):
+        if bases[e] < bases[e - 1]:
+            raise SushiError("order_back: event %d lies at %d, before event %d at %d: the events are not in order"
+                             % (e, bases[e], e - 1, bases[e - 1]))
+    return [BACK_ANY] + [max(bases[e] - bases[e - 1] - lens[e - 1], 0) + slack for e in range(1, len(bases))]
+
+
+def _prefix(D):
+    """(P, A): P[t] = the minimum of D[0 .. t], A[t] = the first index that attains it (a record is strictly below everything in
+    front of it: 0.0 and -0.0 tie); P is D[A], so a zero keeps its sign."""
+    run = np.minimum.accumulate(D)
+    record = np.ones(D.shape[0], bool)
+    record[1:] = D[1:] < run[:-1]
+    A = np.maximum.accumulate(np.where(record, np.arange(D.shape[0], dtype=np.int64), 0)).astype(np.int32)
+    return D[A], A
+
+
+def _reach_back(n, back):
+    """t_e(j) for every j of an axis of n: min(j + back, n - 1); n - 1 where back is BACK_ANY."""
+    j = np.arange(n, dtype=np.int64)
+    return np.full(n, n - 1, np.int64) if back < 0 else np.minimum(j + int(back), n - 1)
+
+
+def track_ordered_host(rows, weights, penalties, step_cost, reach, back, method="sqdiff_normed", _keep=None):
+    """sushi_hip_track_forward_ordered + sushi_hip_track_backtrack_ordered for one sequence in NumPy (include/sushi_hip.h "ordered
+    tracking" states the arithmetic): track_host's arguments, but penalties, a number or E finite numbers >= 0 (row 0's is ignored),
+    and back, an int >= 0, -1 or None (no limit), or E of them (row 0's is not used).  u_e, D_0, m_e, a_e, near_e and the moves are
+    track_host's; P_{e-1}[t] = min D_{e-1}[0 .. t], A_{e-1}[t] = its first index; t_e(j) = min(j + back_e, n_shift - 1) (n_shift - 1
+    without a limit); jump_e[j] = P_{e-1}[t_e(j)] + penalty_e; D_e = u_e + where(near_e <= jump_e, near_e, jump_e); s_{E-1} = a_{E-1},
+    s_{e-1} = A_{e-1}[t_e(s_e)] after a jump, else s_e + move_e[s_e].  With every back without a limit (or >= n_shift - 1) and one
+    penalty this is track_host bit for bit.  Returns a TrackOrderedHost: TrackHost's fields, then prefix_arg (int32 [E, n_shift]:
+    row e is A_e)."""
+    rows = list(rows)
+    E = len(rows)
+    w, _lam, mu = _checked(weights, E, 0.0, step_cost, method)
+    rows = axis.checked_score_rows(rows, "track")
+    n = rows[0].shape[0]
+    reach = checked_reach(reach, E)
+    lam = checked_penalties(penalties, E)
+    back = checked_back(back, E)
+    row_min = np.empty(E, np.float64)
+    row_arg = np.empty(E, np.int32)
+    moves = np.zeros((E, n), np.int16)
+    prefix_arg = np.empty((E, n), np.int32)
+    D = P = None
+    for e, (r, we) in enumerate(zip(rows, w)):
+        c = r.astype(np.float64)
+        if method == "ccoeff_normed":
+            c = -c
+        u = we * c
+        if e == 0:
+            D = u
+        else:
+            jump = P[_reach_back(n, back[e])] + lam[e]
+            near, nd = _near(D, reach[e], mu, moves=True)
+            take_near = near <= jump
+            D = u + np.where(take_near, near, jump)
+            moves[e] = np.where(take_near, nd, np.int16(JUMP))
+        P, prefix_arg[e] = _prefix(D)
+        row_arg[e] = prefix_arg[e, n - 1]           # the first index of the minimum
+        row_min[e] = D[row_arg[e]]
+        if _keep is not None:
+            _keep.append(D)
+    shifts = backtrack_ordered_host(moves, prefix_arg, back, row_arg)
+    own = np.array([axis.first_extremum(r, method) for r in rows], np.int32)
+    return TrackOrderedHost(shifts, float(row_min[E - 1]), row_min, row_arg, moves, own,
+                            np.array([r[k] for r, k in zip(rows, own)], np.float32), prefix_arg)
+
+
+def backtrack_ordered_host(moves, prefix_arg, back, row_arg):
+    """s_{E-1} = a_{E-1}; s_{e-1} = A_{e-1}[t_e(s_e)] where move_e[s_e] is a jump, else s_e + move_e[s_e] (clamped into the axis)."""
+    E, n = moves.shape
+    shifts = np.empty(E, np.int32)
+    s = min(max(int(row_arg[E - 1]), 0), n - 1)
+    shifts[E - 1] = s
+    for e in range(E - 1, 0, -1):
+        m = int(moves[e, s])
+        if m == JUMP:
+            b = int(back[e])
+            s = int(prefix_arg[e - 1, n - 1 if b < 0 else min(s + b, n - 1)])
+        else:
+            s = s + m
+        s = min(max(s, 0), n - 1)
+        shifts[e - 1] = s
+    return shifts
+
+
 def track_margins_host(rows, weights, penalty, step_cost, reach, guard, method="sqdiff_normed"):
     """sushi_hip_track_forward_keep + sushi_hip_track_backtrack + sushi_hip_track_margins for one sequence in NumPy (include/sushi_hip.h
     "margins" states the arithmetic); the arguments of track_host, and guard, an int or E ints >= 0.  C_{E-1} = u_{E-1}, M_{E-1} =
@@ -206,15 +343,24 @@ class TrackState(object):
     (float32[n_total]).  track_device fills them chunk by chunk; track_backtrack_device reads them.
     keep=True: D is float64[n_total * n_shift], every row of the pass (track_forward_keep_device fills it), and the state also holds
     what track_margins_device needs and fills: C (float64[2 * n_shift]: two halves), c_min, through, best, alt (float64[n_total]),
-    best_arg, alt_arg (int32[n_total])."""
+    best_arg, alt_arg (int32[n_total]).
+    ordered=True (not together with keep): the state of the ordered pass (track_ordered_device fills it, chunk by chunk;
+    track_ordered_backtrack_device reads it) -- also P (float64[n_shift]: the prefix minimum of the last row advanced), prefix_arg
+    (int32[n_total * n_shift]: row e holds A_e) and back (int32[n_total]: every advanced row's back)."""
 
-    def __init__(self, n_total, n_shift, device, keep=False):
+    def __init__(self, n_total, n_shift, device, keep=False, ordered=False):
         import torch
         n_total, n_shift = int(n_total), int(n_shift)
         if n_total < 1 or n_shift < 1 or n_shift > 2 ** 31 - 1:
             raise SushiError("track: a sequence has >= 1 rows and 1 .. 2^31 - 1 shifts")
-        self.n_total, self.n_shift, self.device, self.keep = n_total, n_shift, device, bool(keep)
+        if keep and ordered:
+            raise SushiError("track: the ordered pass keeps no rows (its margins are not built)")
+        self.n_total, self.n_shift, self.device, self.keep, self.ordered = n_total, n_shift, device, bool(keep), bool(ordered)
         with torch.cuda.device(device):
+            if ordered:
+                self.P = torch.empty(n_shift, dtype=torch.float64, device=device)
+                self.prefix_arg = torch.empty(n_total * n_shift, dtype=torch.int32, device=device)
+                self.back = torch.empty(n_total, dtype=torch.int32, device=device)
             self.D = torch.empty((n_total if keep else 2) * n_shift, dtype=torch.float64, device=device)
             self.moves = torch.empty(n_total * n_shift, dtype=torch.int16, device=device)
             self.row_min = torch.empty(n_total, dtype=torch.float64, device=device)
@@ -233,15 +379,21 @@ class TrackState(object):
     def margin_tensors(self):
         return (self.C, self.c_min, self.through, self.best, self.best_arg, self.alt, self.alt_arg)
 
+    def order_tensors(self):
+        return (self.P, self.prefix_arg, self.back)
+
     def last_D(self):
         """D of the sequence's last row: the half (keep: the row) it was written to."""
         half = (self.n_total - 1) if self.keep else (self.n_total - 1) & 1
         return self.D[half * self.n_shift:(half + 1) * self.n_shift]
 
     @staticmethod
-    def nbytes(n_total, n_shift, keep=False, marginals=False):
-        """Bytes of moves and D: what grows with the sequence.  keep: every row of D and the two halves of C; marginals: M too."""
+    def nbytes(n_total, n_shift, keep=False, marginals=False, ordered=False):
+        """Bytes of moves and D: what grows with the sequence.  keep: every row of D and the two halves of C; marginals: M too;
+        ordered: moves and A, 6 bytes per (event, shift), the two halves of D and P."""
         n_total, n_shift = int(n_total), int(n_shift)
+        if ordered:
+            return n_total * n_shift * 6 + 2 * n_shift * 8 + n_shift * 8
         if not keep:
             return n_total * n_shift * 2 + 2 * n_shift * 8
         return n_total * n_shift * 2 + n_total * n_shift * 8 + 2 * n_shift * 8 + (n_total * n_shift * 8 if marginals else 0)
@@ -267,6 +419,8 @@ def track_forward_keep_device(curves, rows, reach, penalty, step_cost, state, ro
 
 def _forward_device(name, curves, rows, reach, penalty, step_cost, state, row0, method, hip_stream):
     from .device import _launch
+    if getattr(state, "ordered", False):
+        raise SushiError("track: a TrackState(ordered=True) goes through track_ordered_device")
     axis.check_curves(curves, "track", device=state.D.device)
     rt = axis.row_table(rows)
     _w, lam, mu = _checked(rt["weight"], rt.shape[0], penalty, step_cost, method)
@@ -336,6 +490,54 @@ def track_margins_device(curves, rows, reach, guard, penalty, step_cost, state, 
     return state
 
 
+def track_ordered_device(curves, rows, reach, penalties, step_cost, back, state, row0=0, method="sqdiff_normed", hip_stream=None):
+    """One call of sushi_hip_track_forward_ordered: track_device's arguments, but penalties (a number, or one per row of the call)
+    and back (an int >= 0, -1 or None for no limit, or one per row of the call), and `state` a TrackState(ordered=True).  row0 > 0
+    continues what the calls before it on the same stream left in `state` -- D, and P of the last row advanced: a sequence goes
+    through chunk by chunk, with the bits of one call.  Three launches per row; measured at 64 rows x 2.88 M shifts, 12.3 x
+    track_device's time at reach 0 and 2.8 x at reach 88 (profiles/track_order/).  Asynchronous on hip_stream."""
+    from .device import _launch
+    if not getattr(state, "ordered", False):
+        raise SushiError("track: track_ordered_device needs a TrackState(ordered=True)")
+    axis.check_curves(curves, "track", device=state.D.device)
+    rt = axis.row_table(rows)
+    n_rows = rt.shape[0]
+    _w, _lam, mu = _checked(rt["weight"], n_rows, 0.0, step_cost, method)
+    row0 = int(row0)
+    if row0 < 0 or row0 + n_rows > state.n_total:
+        raise SushiError("track: rows %d .. %d are not inside a sequence of %d" % (row0, row0 + n_rows - 1, state.n_total))
+    rc = np.ascontiguousarray(checked_reach(reach, n_rows, first_row=row0))
+    pc = np.ascontiguousarray(checked_penalties(penalties, n_rows, first_row=row0))
+    bc = np.ascontiguousarray(checked_back(back, n_rows, first_row=row0))
+    axis.check_rows_inside(rt, int(curves.numel()), state.n_shift, "track")
+    L = _native.lib()
+    _launch("sushi_hip_track_forward_ordered", state.D.device, L.sushi_hip_track_order_bytes(n_rows, state.n_shift),
+            lambda mem, mem_bytes, st: L.sushi_hip_track_forward_ordered(
+                curves.data_ptr(), int(curves.numel()), rt.ctypes.data, rc.ctypes.data, bc.ctypes.data, n_rows, state.n_shift,
+                _native.METHODS[method], pc.ctypes.data, mu, row0, state.n_total, state.D.data_ptr(), state.moves.data_ptr(),
+                state.P.data_ptr(), state.prefix_arg.data_ptr(), state.back.data_ptr(), state.row_min.data_ptr(),
+                state.row_arg.data_ptr(), state.row_own_index.data_ptr(), state.row_own_scores.data_ptr(), mem, mem_bytes, st),
+            (curves,) + state.tensors() + state.order_tensors(), hip_stream)
+    return state
+
+
+def track_ordered_backtrack_device(state, hip_stream=None):
+    """sushi_hip_track_backtrack_ordered over `state` once every row has gone through track_ordered_device on the same stream: the
+    shift index of every row, an int32 CUDA tensor."""
+    import torch
+    from .device import _launch
+    if not getattr(state, "ordered", False):
+        raise SushiError("track: track_ordered_backtrack_device needs a TrackState(ordered=True)")
+    L = _native.lib()
+    out = torch.empty(state.n_total, dtype=torch.int32, device=state.D.device)
+    _launch("sushi_hip_track_backtrack_ordered", state.D.device, None,
+            lambda _mem, _mem_bytes, st: L.sushi_hip_track_backtrack_ordered(
+                state.moves.data_ptr(), state.prefix_arg.data_ptr(), state.back.data_ptr(), state.row_arg.data_ptr(), state.n_total,
+                state.n_shift, out.data_ptr(), st),
+            (state.moves, state.prefix_arg, state.back, state.row_arg, out), hip_stream)
+    return out
+
+
 def track_backtrack_device(state, hip_stream=None):
     """sushi_hip_track_backtrack over `state` once every row has gone through track_device on the same stream: the shift index of
     every row, an int32 CUDA tensor."""
@@ -387,6 +589,9 @@ class Track(Record):
                       the clamped rows: an event_own_scores entry equal to f with its event_own_delta at index 0 (k_lo) means
                       nothing in that event's window passed.  event_scores stay the true scores at the chosen shifts, formed one
                       position each.
+    back, penalties   None, or through the ordered pass (order=, a penalty per event) every event's back in samples (None: no
+                      limit; event 0's is None) and every event's penalty (event 0's is 0): a jump into event e lowers the shift by
+                      at most back[e] and costs penalties[e].
     With margins=True (else None), how firmly every event is placed:
     guard             every event's guard in samples (list of int);
     event_through     the cost of the best whole path through every event's chosen shift (float64 array: the total, up to
@@ -407,7 +612,7 @@ class Track(Record):
 
 def find_track(stream, patterns, window_centers, window_size, penalty, max_rate=None, reach=None, step_cost=0.0, slack=1,
                weights="equal", method="sqdiff_normed", max_bytes=MAX_BYTES, max_state_bytes=MAX_STATE_BYTES, margins=False,
-               guard=None, marginals=False, clamp=None, capacity=None):
+               guard=None, marginals=False, clamp=None, capacity=None, order=None):
     """WavStream.find_track (its docstring)."""
     import torch
     from .curves import match_curves
@@ -419,6 +624,15 @@ def find_track(stream, patterns, window_centers, window_size, penalty, max_rate=
     margins, marginals = bool(margins), bool(marginals)
     if not margins and (marginals or guard is not None):
         raise SushiError("find_track: guard and marginals belong to margins=True")
+    # the ordered pass is taken only when it is asked for; otherwise the code path, the launches and the bits are those of before
+    order = None if order is False else order
+    ordered = order is not None or (penalty is not None and np.ndim(penalty) != 0)
+    if ordered:
+        if margins:
+            raise SushiError("find_track: margins of the ordered pass (order=, a penalty per event) are not built: its backward "
+                             "recurrence needs the mirrored suffix minimum")
+        return _find_track_ordered(stream, patterns, centres, window_size, penalty, max_rate, reach, step_cost, slack, weights, method,
+                                   max_bytes, max_state_bytes, clamp, capacity, order)
     f, capacity = axis.checked_clamp(clamp, capacity, method)
     dst_dev = stream.device_stream()
     src_dev, offs, lens, _ = stream._pattern_source(patterns, dst_dev)
@@ -487,7 +701,60 @@ def find_track(stream, patterns, window_centers, window_size, penalty, max_rate=
         segments=[(f, n, shifts[f] / float(rate), shifts[f + n - 1] / float(rate)) for f, n in jump_runs(E, jumps)],
         cost=float(state.row_min[E - 1].item()), event_scores=at.cpu().numpy(),
         event_own_delta=[(k_lo + int(k)) / float(rate) for k in own], event_own_scores=state.row_own_scores.cpu().numpy(),
-        clamp=None if f is None else float(f), rows_info=rows_info[0], **extra)
+        clamp=None if f is None else float(f), rows_info=rows_info[0], back=None, penalties=None, **extra)
+
+
+def _find_track_ordered(stream, patterns, centres, window_size, penalty, max_rate, reach, step_cost, slack, weights, method, max_bytes,
+                        max_state_bytes, clamp, capacity, order):
+    """find_track through the ordered pass: order None (every back without a limit: a penalty per event alone), True (order_back of
+    the events) or one back per event; penalty a number or one per event."""
+    from .curves import match_curves
+    f, capacity = axis.checked_clamp(clamp, capacity, method)
+    dst_dev = stream.device_stream()
+    src_dev, offs, lens, _ = stream._pattern_source(patterns, dst_dev)
+    lens = axis.pattern_lengths(lens)
+    E = len(patterns)
+    w, _lam, mu = _checked(axis.event_weights(weights, lens, per_event=True), E, 0.0, step_cost, method)
+    lam = checked_penalties(penalty, E)
+    ax = axis.event_axis(stream, offs, lens, centres, window_size)
+    k_lo, n_shift, rate = ax.k_lo, ax.n_shift, stream.sample_rate
+    reach = checked_reach(rate_reach(ax.bases, max_rate, slack) if reach is None else reach, E)
+    back = checked_back(None if order is None else (order_back(ax.bases, lens) if order is True else order), E)
+    back[0] = BACK_ANY
+    need = TrackState.nbytes(E, n_shift, ordered=True)
+    if need > max_state_bytes:
+        raise SushiError("find_track: %d events x %d shifts need %d bytes of moves, jump sources and costs, max_state_bytes is %d"
+                         % (E, n_shift, need, max_state_bytes))
+    per_chunk = int(max_bytes) // (4 * n_shift)
+    if per_chunk < 1:
+        raise SushiError("find_track: one event of %d shifts needs %d bytes of curves, max_bytes is %d"
+                         % (n_shift, 4 * n_shift, max_bytes))
+    state = TrackState(E, n_shift, dst_dev.device, ordered=True)
+    rows_info = None
+    for first in range(0, E, per_chunk):
+        last = min(E, first + per_chunk)
+        info = {}
+        curves, row_off = axis.event_rows(dst_dev, src_dev, [ax.part(first, last)], method, clamp=f, capacity=capacity, info=info)
+        if f is not None:
+            rows_info = axis.merge_rows_info(rows_info, info)
+        track_ordered_device(curves, zip(row_off, w[first:last].tolist()), reach[first:last], lam[first:last], mu, back[first:last],
+                             state, row0=first, method=method)
+    index_dev = track_ordered_backtrack_device(state)
+    index = index_dev.cpu().numpy()
+    words = state.moves[index_dev.long() + n_shift * _arange_like(index_dev)].cpu().numpy()
+    shifts = [k_lo + int(k) for k in index]
+    jumps = [e for e in range(1, E) if int(words[e]) == JUMP]
+    at, _ = match_curves(dst_dev, src_dev, ax.offs, lens, [b + k for b, k in zip(ax.bases, shifts)], [1] * E, method=method)
+    own = state.row_own_index.cpu().numpy()
+    return Track(
+        k_lo=k_lo, n_shift=n_shift, shifts=shifts, deltas=[k / float(rate) for k in shifts], reach=reach.tolist(),
+        moves=[0] + [b - a for a, b in zip(shifts[:-1], shifts[1:])], jumps=jumps,
+        segments=[(s, n, shifts[s] / float(rate), shifts[s + n - 1] / float(rate)) for s, n in jump_runs(E, jumps)],
+        cost=float(state.row_min[E - 1].item()), event_scores=at.cpu().numpy(),
+        event_own_delta=[(k_lo + int(k)) / float(rate) for k in own], event_own_scores=state.row_own_scores.cpu().numpy(),
+        clamp=None if f is None else float(f), rows_info=rows_info, guard=None, event_through=None, event_margin=None,
+        event_alt_shift=None, event_alt_delta=None, marginals=None,
+        back=[None if int(b) == BACK_ANY else int(b) for b in back], penalties=lam.tolist())
 
 
 def _arange_like(index_dev):

@@ -621,7 +621,9 @@ class WavStream(object):
         k_lo, n_shift, shifts (samples per event), deltas (seconds), segments ([(first_event, n_events, delta)]: maximal runs of
         equal shift), cost, event_scores (every event's score at its chosen shift), event_own_delta / event_own_scores (what a
         lone search of each event over the same range finds).  clamp, capacity: find_joint_many's -- the pass then runs on rows
-        clamped at f and is the exact minimum of that clamped problem (the truncated cost of labelling passes).  Needs a GPU."""
+        clamped at f and is the exact minimum of that clamped problem (the truncated cost of labelling passes).  A change of shift
+        may go either way here; the same model with the events kept in order in the destination, or with a penalty per event, is
+        find_track(reach=0, order=...).  Needs a GPU."""
         from . import segments
         return segments.find_segments(self, patterns, window_centers, window_size, penalty, weights=weights, method=method,
                                       max_bytes=segments.MAX_BYTES if max_bytes is None else int(max_bytes),
@@ -631,7 +633,7 @@ class WavStream(object):
     # ------------------------------------------------------------------ a shift that wanders, and may jump
     def find_track(self, patterns, window_centers, window_size, penalty, max_rate=None, reach=None, step_cost=0.0, slack=1,
                    weights='equal', method="sqdiff_normed", max_bytes=None, max_state_bytes=None, margins=False, guard=None,
-                   marginals=False, clamp=None, capacity=None):
+                   marginals=False, clamp=None, capacity=None, order=None):
         """A shift for every event of a sequence that may move a little from event to event and jump at a cut
         (sushi_amd.track): the events (patterns, window_centers: in order) are put on one shift axis as
         find_segments puts them, and a shift is chosen per event that minimises the sum of the events' weighted scores plus, between
@@ -657,13 +659,27 @@ class WavStream(object):
         one chunk of max_bytes keeps its curves; one in several chunks forms every chunk's curves a second time, which doubles the
         curve work.  With margins=False (the default) nothing changes and the new fields are None.  find_segments' margins are
         find_track(reach=0, margins=True).  clamp, capacity: find_joint_many's -- the pass and its margins then run on rows clamped
-        at f (every forming of a chunk, the second one for margins included) and are exact for that clamped problem.  Needs a GPU."""
+        at f (every forming of a chunk, the second one for margins included) and are exact for that clamped problem.
+        order keeps the events in order: no cut puts an event in the destination before the end of the event in
+        front of it, so a jump into event e may lower the shift by at most back_e samples (and raise it by any amount).  None (the
+        default): no limit, as before; True: back_e = max(base_e - base_{e-1} - len_{e-1}, 0) from the events' places and lengths
+        (sushi_amd.track.order_back; SushiError if the events are not in order); or one int per event, -1 or None for no limit
+        (event 0's is ignored).  A decoy -- a repeated jingle, a better chance match elsewhere in the window -- costs a path two
+        jumps, one of which goes back further than any cut can: with order= small penalties stay safe.  penalty may also be one
+        number per event (event 0's is ignored): a cut is cheap at a chapter mark and dear inside a dialogue
+        (sushi_amd.shifts.chapter_penalties).  Either takes the ordered pass: its state is E x n_shift x 6 + 3 x n_shift x 8 bytes
+        under max_state_bytes, the Track gains back and penalties, and margins=True with it is a SushiError (not built: the
+        backward recurrence needs the mirrored suffix minimum).  Moves are not restricted by order.  Without order= and with one
+        penalty the code path, the launches and the bits are those of before.  Measured on one MI355X (profiles/track_order/): the
+        ordered forward pass takes 12.3 x the plain one at reach 0 and 2.8 x at reach 88 (64 rows x 2.88 M shifts: 14.1 ms
+        against 1.1 ms, 20.2 ms against 7.2 ms -- its prefix-minimum kernel, not tuned); a whole call on 64 uint8 events at +-120 s
+        1.27 x (59.9 ms against 47.1 ms), with clamp=0.5 3.7 x (17.7 ms against 4.8 ms).  Needs a GPU."""
         from . import track
         return track.find_track(self, patterns, window_centers, window_size, penalty, max_rate=max_rate, reach=reach,
                                 step_cost=step_cost, slack=slack, weights=weights, method=method,
                                 max_bytes=track.MAX_BYTES if max_bytes is None else int(max_bytes),
                                 max_state_bytes=track.MAX_STATE_BYTES if max_state_bytes is None else int(max_state_bytes),
-                                margins=margins, guard=guard, marginals=marginals, clamp=clamp, capacity=capacity)
+                                margins=margins, guard=guard, marginals=marginals, clamp=clamp, capacity=capacity, order=order)
 
     # ------------------------------------------------------------------ a shift that moves along the programme
     def find_drift(self, patterns, window_centers, window_size, max_rate, resolution=1.0, weights='equal', method="sqdiff_normed",
