@@ -55,7 +55,9 @@ extern "C" {
                                      sushi_hip_track_forward, sushi_hip_track_backtrack;
                                      13 (additive): sushi_hip_track_forward_keep, sushi_hip_track_margins_bytes, sushi_hip_track_margins;
                                      13 (additive): SUSHI_HIP_TRACK_BACK_ANY, sushi_hip_track_order_bytes,
-                                     sushi_hip_track_forward_ordered, sushi_hip_track_backtrack_ordered */
+                                     sushi_hip_track_forward_ordered, sushi_hip_track_backtrack_ordered;
+                                     13 (additive): sushi_hip_track_forward_ordered_keep, sushi_hip_track_order_margins_bytes,
+                                     sushi_hip_track_order_margins */
 
 #if defined(__GNUC__)
 #define SUSHI_HIP_API __attribute__((visibility("default")))
@@ -752,6 +754,69 @@ SUSHI_HIP_API int sushi_hip_track_forward_ordered(const float* curves_dev, int64
 SUSHI_HIP_API int sushi_hip_track_backtrack_ordered(const int16_t* move_dev, const int32_t* from_dev, const int32_t* back_dev,
                                                     const int32_t* row_arg_dev, int n_total, int32_t n_shift,
                                                     int32_t* out_shift_dev, void* hip_stream);
+
+/* ---- ordered margins: how firmly ordered tracking places each event -- its min-marginals (13, additive) --------
+ * "margins" for the pass of "ordered tracking": M_e[j] is the cost of the best whole path that puts event e at shift j among the
+ * paths whose jumps obey the backs, with penalty_{i+1} for a jump out of event i.  Everything not named here is theirs, unchanged:
+ * u_e, near / cand and their tie rule, the price of a move, B, M and C from nearB and jumpB (a tie moves), the guard window, the
+ * stored index of an alternative, the (min, first index) combine rule; float64, products and sums round separately, one rounding
+ * per sum.  A jump from (e, i) into (e + 1, j) exists iff j >= i - back_{e+1}.  So, backwards, with D_e the ordered forward pass's
+ * row (sushi_hip_track_forward_ordered_keep keeps every one):
+ *     C_{E-1} = u_{E-1};   M_{E-1} = D_{E-1}                          (nothing is added: the bits of D)
+ *     S_e[t]     = min C_e[t .. n_shift - 1], the value at the FIRST (lowest) index that attains it (0.0 and -0.0 tie; a zero keeps
+ *                  its sign): the (min, first index) combine over the span, in any grouping
+ *     for e = E-2 .. 0, with r = reach_{e+1}, b = back_{e+1}, penalty_{e+1}:
+ *         t'_e(j)  = max(j - b, 0), formed in 64 bits;  0 where b is SUSHI_HIP_TRACK_BACK_ANY
+ *         jumpB[j] = S_{e+1}[t'_e(j)] + penalty_{e+1}                 (one rounding)
+ *         nearB[j] = "margins"' window minimum over C_{e+1} with reach r (the value only)
+ *         B_e[j]   = nearB[j] <= jumpB[j] ? nearB[j] : jumpB[j]       (a tie moves)
+ *         M_e[j]   = D_e[j] + B_e[j];   C_e[j] = u_e[j] + B_e[j]
+ *     per row e:   through_e, best_e / best_arg_e, alt_e / alt_arg_e as in "margins";  c_min_e = S_e[0]
+ * Four facts.  EXACT PATH MINIMUM: M_e[j] is bitwise the minimum, over all paths with s_e = j whose jumps obey the backs, of (the
+ * prefix cost, accumulated forwards as "ordered tracking" states it) + (the suffix cost, accumulated backwards in the mirrored
+ * order as "margins" states it, with penalty_{i+1} per jump out of event i).  REVERSAL: c_min_0 == the ordered forward pass's total
+ * on the reversed sequence -- the rows in reverse order and every row flipped end to end, reach_rev[i] = reach[E - i], back_rev[i] =
+ * back[E - i], penalty_rev[i] = penalty[E - i]; a zero may differ in sign, since the window's tie order is mirrored.  CONSISTENCY
+ * WITH THE TOTAL: best_e <= through_e exactly; |through_e - m_{E-1}| <= 6 E 2^-53 S as in "margins".  NO LIMIT: with every used back
+ * SUSHI_HIP_TRACK_BACK_ANY or >= n_shift - 1 and one penalty, every output -- M, C, c_min, through, best, alt and their indices --
+ * is sushi_hip_track_margins' bit for bit (S[0] with the first-index rule is n_{e+1} of "margins"). */
+/* sushi_hip_track_forward_ordered with D kept: D_all_dev is [n_total][n_shift] float64, row e reads row e - 1 and writes row e.
+ * Everything else -- the kernels, the other outputs, their bits, the refusals, the workspace (sushi_hip_track_order_bytes) and the
+ * continuation of a sequence in chunks -- is sushi_hip_track_forward_ordered's. */
+SUSHI_HIP_API int sushi_hip_track_forward_ordered_keep(const float* curves_dev, int64_t n_curve,
+                                                       const SushiHipJointRow* rows_host, const int32_t* reach_host,
+                                                       const int32_t* back_host, int n_rows, int32_t n_shift,
+                                                       int method, const double* penalty_host, double step_cost, int row0, int n_total,
+                                                       double* D_all_dev, int16_t* move_dev,
+                                                       double* P_dev, int32_t* from_dev, int32_t* back_dev,
+                                                       double* row_min_dev, int32_t* row_arg_dev,
+                                                       int32_t* row_own_index_dev, float* row_own_score_dev,
+                                                       void* mem_dev, size_t mem_bytes, void* hip_stream);
+/* workspace of an ordered margins call (one set of per-workgroup partial minima, and per work item of the axis one (minimum, first
+ * index) record and the minimum of everything after the item); 0 for n_rows < 1 or n_shift < 1 */
+SUSHI_HIP_API size_t sushi_hip_track_order_margins_bytes(int n_rows, int32_t n_shift);
+/* sushi_hip_track_margins for the ordered pass: walks rows row0 + n_rows - 1 down to row0 of a sequence whose
+ * forward_ordered_keep calls and ordered backtrack lie before it on the stream.  rows_host[i] and guard_host[i] are row row0 + i's;
+ * reach_host[i], back_host[i] and penalty_host[i] are row row0 + i's for i = 0 .. n_rows, the last only where row0 + n_rows <
+ * n_total; entry 0 is not used and is ignored.  S_dev: [n_shift] float64, S of the last row walked; the other buffers are
+ * sushi_hip_track_margins'.  The first call of a sequence has row0 + n_rows == n_total; a later one continues from C_dev and S_dev
+ * as the call before it on the same stream left them: a sequence in chunks has the bits of one call, whatever the parity of the
+ * boundary.  No device allocation, no upload: three launches per row, stream-ordered -- the step, a scan of one record per work
+ * item (which also writes the row's outputs), and the suffix minimum of the row just written -- and the launch boundary is their
+ * only synchronisation.  Asynchronous; stateless.  Checked before any HIP call -- EINVAL: everything sushi_hip_track_margins
+ * refuses (it has no penalty of its own), a null back or penalty table, a null S_dev, a used back below
+ * SUSHI_HIP_TRACK_BACK_ANY, a used penalty that is not finite or is negative; EALIGN: mem_dev not 256-byte aligned; ENOSPACE:
+ * mem_bytes < sushi_hip_track_order_margins_bytes; EALIGN: a float64 pointer not 8-byte aligned, a float / int32 pointer not 4-byte
+ * aligned. */
+SUSHI_HIP_API int sushi_hip_track_order_margins(const float* curves_dev, int64_t n_curve,
+                                                const SushiHipJointRow* rows_host, const int32_t* reach_host,
+                                                const int32_t* back_host, const int32_t* guard_host,
+                                                int n_rows, int32_t n_shift, int method, const double* penalty_host, double step_cost,
+                                                int row0, int n_total,
+                                                const double* D_all_dev, const int32_t* shift_dev, double* C_dev, double* S_dev,
+                                                double* c_min_dev, double* through_dev, double* best_dev, int32_t* best_arg_dev,
+                                                double* alt_dev, int32_t* alt_arg_dev, double* M_dev,
+                                                void* mem_dev, size_t mem_bytes, void* hip_stream);
 
 /* ---- rows: score rows clamped at a threshold, formed from a threshold run's hits (13, additive) ---------------
  * A pass over a shift axis needs to know where a row is good and how good; how bad the rest is only feeds decoys.  The CLAMPED row

@@ -211,6 +211,13 @@ def lib():
                                                   vp, sz, vp]
     L.sushi_hip_track_backtrack_ordered.restype = ci
     L.sushi_hip_track_backtrack_ordered.argtypes = [vp, vp, vp, vp, ci, i32, vp, vp]
+    L.sushi_hip_track_forward_ordered_keep.restype = ci
+    L.sushi_hip_track_forward_ordered_keep.argtypes = L.sushi_hip_track_forward_ordered.argtypes
+    L.sushi_hip_track_order_margins_bytes.restype = sz
+    L.sushi_hip_track_order_margins_bytes.argtypes = [ci, i32]
+    L.sushi_hip_track_order_margins.restype = ci
+    L.sushi_hip_track_order_margins.argtypes = [vp, i64, vp, vp, vp, vp, ci, i32, ci, vp, dbl, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                vp, vp, vp, sz, vp]
     L.sushi_hip_rows_tile.restype = ci
     L.sushi_hip_rows_bytes.restype = sz
     L.sushi_hip_rows_bytes.argtypes = [ci]

@@ -56,6 +56,9 @@ UNITS = [
     # tracked events kept in order: the tracking step with a jump read per index from the prefix minimum of the row before, and
     # per row a scan of (minimum, first index) that writes it (track_order_core.hpp: the combine rule, the call's host side, the walker)
     ("sushi_track_order", ["-ffp-contract=off"]),       # track_core.hpp's candidates unchanged; the jump's sum rounds once
+    # how firmly the ordered pass places each event: the margins step with a jump read per index from the suffix minimum of the row
+    # after, and per row a scan downwards that writes it (track_order_margin_core.hpp: t', the jump sum, the call's host side)
+    ("sushi_track_order_margins", ["-ffp-contract=off"]),       # the candidates unchanged; the jump's sum, M and C round once each
     # score rows clamped at a threshold: a fill and a scatter of a threshold run's hits, and the rule applied to rows that exist
     # (rows_core.hpp: the rule, the tiles, the search of a hit list, and the call's host side)
     ("sushi_rows", []),                         # comparisons and copies: no arithmetic to contract

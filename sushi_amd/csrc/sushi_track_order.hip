@@ -278,12 +278,14 @@ extern "C" {
 
 size_t sushi_hip_track_order_bytes(int n_rows, int32_t n_shift) { return order_layout_bytes(n_rows, n_shift); }
 
-int sushi_hip_track_forward_ordered(const float* curves_dev, int64_t n_curve, const SushiHipJointRow* rows_host, const int32_t* reach_host,
-                                    const int32_t* back_host, int n_rows, int32_t n_shift, int method, const double* penalty_host,
-                                    double step_cost, int row0, int n_total, double* D_dev, int16_t* move_dev, double* P_dev,
-                                    int32_t* from_dev, int32_t* back_dev, double* row_min_dev, int32_t* row_arg_dev,
-                                    int32_t* row_own_index_dev, float* row_own_score_dev, void* mem_dev, size_t mem_bytes,
-                                    void* hip_stream) { return c_boundary([&]() -> int {
+// sushi_hip_track_forward_ordered and sushi_hip_track_forward_ordered_keep: one body.  keep: D_dev holds every row ([n_total][n_shift]:
+// row e reads row e - 1 and writes row e) instead of two halves used by turns; the launches, and so the bits, are the same.
+static int track_forward_ordered(bool keep, const float* curves_dev, int64_t n_curve, const SushiHipJointRow* rows_host,
+                                 const int32_t* reach_host, const int32_t* back_host, int n_rows, int32_t n_shift, int method,
+                                 const double* penalty_host, double step_cost, int row0, int n_total, double* D_dev, int16_t* move_dev,
+                                 double* P_dev, int32_t* from_dev, int32_t* back_dev, double* row_min_dev, int32_t* row_arg_dev,
+                                 int32_t* row_own_index_dev, float* row_own_score_dev, void* mem_dev, size_t mem_bytes,
+                                 void* hip_stream) {
     if (!curves_dev || !rows_host || !reach_host || !back_host || !penalty_host || !D_dev || !move_dev || !P_dev || !from_dev ||
         !back_dev || !row_min_dev || !row_arg_dev || !row_own_index_dev || !row_own_score_dev || !mem_dev) return SUSHI_HIP_EINVAL;
     OrderStage staged;
@@ -319,9 +321,9 @@ int sushi_hip_track_forward_ordered(const float* curves_dev, int64_t n_curve, co
         a.reach = a.e == 0 ? 0 : reach_host[i];
         a.back = back_host[i];
         // (row 0 has no row before it: its launch's loads of D_in and P, which are always made and never used, go to its own
-        // half and to P as it stands)
-        a.D_in = D_dev + (int64_t)((a.e + 1) & 1) * n_shift;
-        a.D_out = D_dev + (int64_t)(a.e & 1) * n_shift;
+        // half -- keep: its own row -- and to P as it stands)
+        a.D_in = D_dev + (keep ? (int64_t)(a.e == 0 ? 0 : a.e - 1) : (int64_t)((a.e + 1) & 1)) * n_shift;
+        a.D_out = D_dev + (keep ? (int64_t)a.e : (int64_t)(a.e & 1)) * n_shift;
         a.move = move_dev + (int64_t)a.e * n_shift;
         a.from = from_dev + (int64_t)a.e * n_shift;
         const int halo = track_halo_rounds(a.reach);
@@ -334,6 +336,28 @@ int sushi_hip_track_forward_ordered(const float* curves_dev, int64_t n_curve, co
         if (hipGetLastError() != hipSuccess) return SUSHI_HIP_ELAUNCH;
     }
     return launch_ok();
+}
+
+int sushi_hip_track_forward_ordered(const float* curves_dev, int64_t n_curve, const SushiHipJointRow* rows_host, const int32_t* reach_host,
+                                    const int32_t* back_host, int n_rows, int32_t n_shift, int method, const double* penalty_host,
+                                    double step_cost, int row0, int n_total, double* D_dev, int16_t* move_dev, double* P_dev,
+                                    int32_t* from_dev, int32_t* back_dev, double* row_min_dev, int32_t* row_arg_dev,
+                                    int32_t* row_own_index_dev, float* row_own_score_dev, void* mem_dev, size_t mem_bytes,
+                                    void* hip_stream) { return c_boundary([&]() -> int {
+    return track_forward_ordered(false, curves_dev, n_curve, rows_host, reach_host, back_host, n_rows, n_shift, method, penalty_host,
+                                 step_cost, row0, n_total, D_dev, move_dev, P_dev, from_dev, back_dev, row_min_dev, row_arg_dev,
+                                 row_own_index_dev, row_own_score_dev, mem_dev, mem_bytes, hip_stream);
+}); }
+
+int sushi_hip_track_forward_ordered_keep(const float* curves_dev, int64_t n_curve, const SushiHipJointRow* rows_host,
+                                         const int32_t* reach_host, const int32_t* back_host, int n_rows, int32_t n_shift, int method,
+                                         const double* penalty_host, double step_cost, int row0, int n_total, double* D_all_dev,
+                                         int16_t* move_dev, double* P_dev, int32_t* from_dev, int32_t* back_dev, double* row_min_dev,
+                                         int32_t* row_arg_dev, int32_t* row_own_index_dev, float* row_own_score_dev, void* mem_dev,
+                                         size_t mem_bytes, void* hip_stream) { return c_boundary([&]() -> int {
+    return track_forward_ordered(true, curves_dev, n_curve, rows_host, reach_host, back_host, n_rows, n_shift, method, penalty_host,
+                                 step_cost, row0, n_total, D_all_dev, move_dev, P_dev, from_dev, back_dev, row_min_dev, row_arg_dev,
+                                 row_own_index_dev, row_own_score_dev, mem_dev, mem_bytes, hip_stream);
 }); }
 
 int sushi_hip_track_backtrack_ordered(const int16_t* move_dev, const int32_t* from_dev, const int32_t* back_dev, const int32_t* row_arg_dev,

@@ -446,7 +446,7 @@ def calculate_tracked_shifts(src_stream, dst_stream, events, window, penalty, ma
     firmly every event is placed (event_margin, event_alt_delta, ...).  clamp, capacity: find_track's (rows clamped at a threshold;
     the scores the events get stay the true ones).  order: find_track's (None; True: the events are kept in order in the
     destination; or one back per event), and `penalty` may be one number per event (chapter_penalties gives them from chapter marks):
-    either takes the ordered pass, which has no margins.  Returns the Track."""
+    either takes the ordered pass, whose margins are calculate_ordered_shifts'.  Returns the Track."""
     events = list(events)
     shift = float(centre_shift)
     if not events:
@@ -459,6 +459,28 @@ def calculate_tracked_shifts(src_stream, dst_stream, events, window, penalty, ma
                                   step_cost=step_cost, margins=margins, guard=guard, marginals=marginals,
                                   **dict({} if clamp is None and capacity is None else dict(clamp=clamp, capacity=capacity),
                                          **({} if order is None else dict(order=order))))
+    for e, delta, score in zip(events, found.deltas, found.event_scores):
+        e.set_shift(shift + delta, score)
+    return found
+
+
+def calculate_ordered_shifts(src_stream, dst_stream, events, window, penalty, order=True, max_rate=None, reach=None, step_cost=0.0,
+                             centre_shift=0.0, margins=False, guard=None, marginals=False, clamp=None, capacity=None):
+    """calculate_tracked_shifts through dst_stream.find_ordered_track (its docstring): the events are kept
+    in order in the destination (order: True, the default here; None; or one back per event), `penalty` may be one number per event,
+    and with margins=True the Track says how firmly the ordered pass places every event (guard, marginals: find_ordered_track's).
+    Every event gets set_shift(centre_shift + its delta, its own score there).  Returns the Track."""
+    events = list(events)
+    shift = float(centre_shift)
+    if not events:
+        raise SushiError("calculate_ordered_shifts: no events")
+    patterns = [src_stream.get_substream(e.start, e.end) for e in events]
+    for e, p in zip(events, patterns):
+        if p.shape[1] < 1:
+            raise SushiError("calculate_ordered_shifts: event %s has no samples in the source" % e)
+    found = dst_stream.find_ordered_track(patterns, [e.start + shift for e in events], window, penalty, order=order, max_rate=max_rate,
+                                          reach=reach, step_cost=step_cost, margins=margins, guard=guard, marginals=marginals,
+                                          **({} if clamp is None and capacity is None else dict(clamp=clamp, capacity=capacity)))
     for e, delta, score in zip(events, found.deltas, found.event_scores):
         e.set_shift(shift + delta, score)
     return found

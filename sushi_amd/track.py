@@ -17,6 +17,9 @@ minimum over all assignments (include/sushi_hip.h "tracking").  
   ``penalty`` per event run it.
 * ``track_margins_host`` / ``track_forward_keep_device`` / ``track_margins_device`` -- how firmly each event is placed: the pass's
   min-marginals (include/sushi_hip.h "margins"), in NumPy and on the device; ``find_track(margins=True)`` runs them.
+* ``track_ordered_margins_host`` / ``TrackState(ordered=True, margins=True)`` / ``track_ordered_keep_device`` /
+  ``track_ordered_margins_device`` -- the same for the ordered pass (include/sushi_hip.h "ordered margins"; DESIGN.md 3.22);
+  ``find_ordered_track(margins=True)`` runs them.
 """
 import math
 from collections import namedtuple
@@ -37,6 +40,7 @@ TrackMarginsHost = namedtuple("TrackMarginsHost", TrackHost._fields + ("D", "mar
 NO_ALT = -1                   # alt_arg where no shift lies outside the guard window
 BACK_ANY = _native.TRACK_BACK_ANY        # a back that leaves a jump free to come from anywhere
 TrackOrderedHost = namedtuple("TrackOrderedHost", TrackHost._fields + ("prefix_arg",))
+TrackOrderedMarginsHost = namedtuple("TrackOrderedMarginsHost", TrackOrderedHost._fields + TrackMarginsHost._fields[len(TrackHost._fields):])
 
 
 def _checked(weights, n, penalty, step_cost, method):
@@ -337,6 +341,77 @@ def track_margins_host(rows, weights, penalty, step_cost, reach, guard, method="
     return TrackMarginsHost(*(tuple(fwd) + (D, M, through, best, best_arg, alt, alt_arg, c_min)))
 
 
+def _suffix(C):
+    """S[t] = the minimum of C[t ..], the value at the first (lowest) index that attains it (walking down, a record is at or below
+    everything behind it: 0.0 and -0.0 tie, and the lower index's zero is kept)."""
+    rev = C[::-1]
+    run = np.minimum.accumulate(rev)
+    record = np.ones(rev.shape[0], bool)
+    record[1:] = rev[1:] <= run[:-1]
+    at = np.maximum.accumulate(np.where(record, np.arange(rev.shape[0], dtype=np.int64), 0))
+    return np.ascontiguousarray(rev[at][::-1])
+
+
+def _reach_from(n, back):
+    """t'_e(j) for every j of an axis of n: max(j - back, 0); 0 where back is BACK_ANY."""
+    j = np.arange(n, dtype=np.int64)
+    return np.zeros(n, np.int64) if back < 0 else np.maximum(j - int(back), 0)
+
+
+def track_ordered_margins_host(rows, weights, penalties, step_cost, reach, back, guard, method="sqdiff_normed", _trace=None):
+    """sushi_hip_track_forward_ordered_keep + sushi_hip_track_backtrack_ordered + sushi_hip_track_order_margins for one sequence in
+    NumPy (include/sushi_hip.h "ordered margins" states the arithmetic); the arguments of track_ordered_host, and guard, an int or E
+    ints >= 0.  C_{E-1} = u_{E-1}, M_{E-1} = D_{E-1}; S_e = _suffix(C_e); for e = E-2 .. 0: jumpB[j] = S_{e+1}[max(j - back_{e+1}, 0)] +
+    penalty_{e+1} (S_{e+1}[0] without a limit), nearB = track_host's window minimum over C_{e+1} with reach_{e+1}, B_e = where(nearB <=
+    jumpB, nearB, jumpB), M_e = D_e + B_e, C_e = u_e + B_e.  With every back without a limit (or >= n_shift - 1) and one penalty this
+    is track_margins_host bit for bit.  Returns a TrackOrderedMarginsHost: track_ordered_host's fields, then D ([E, n] float64: every
+    row of the ordered forward pass), marginals ([E, n] float64: M), through (M_e[s_e]), best / best_arg, alt / alt_arg (inf and -1
+    where no shift lies outside the guard window), c_min (S_e[0]) -- as track_margins_host's."""
+    rows = list(rows)
+    kept = []
+    fwd = track_ordered_host(rows, weights, penalties, step_cost, reach, back, method, _keep=kept)
+    E = len(rows)
+    w, _lam, mu = _checked(weights, E, 0.0, step_cost, method)
+    rows = axis.checked_score_rows(rows, "track")
+    n = rows[0].shape[0]
+    reach = checked_reach(reach, E)
+    lam = checked_penalties(penalties, E)
+    back = checked_back(back, E)
+    guard = checked_guard(guard, E)
+    D = np.stack(kept)
+    M = np.empty((E, n), np.float64)
+    c_min = np.empty(E, np.float64)
+    C = S = None
+    for e in range(E - 1, -1, -1):
+        c = rows[e].astype(np.float64)
+        if method == "ccoeff_normed":
+            c = -c
+        u = w[e] * c
+        if e == E - 1:
+            C, M[e] = u, D[e]
+        else:
+            jump = S[_reach_from(n, back[e + 1])] + lam[e + 1]
+            near, _nd = _near(C, reach[e + 1], mu)
+            B = np.where(near <= jump, near, jump)
+            M[e] = D[e] + B
+            C = u + B
+        S = _suffix(C)
+        c_min[e] = S[0]
+        if _trace is not None:
+            _trace.append((e, C, S))
+    through = np.array([M[e, fwd.shifts[e]] for e in range(E)], np.float64)
+    best_arg = np.array([int(np.argmin(M[e])) for e in range(E)], np.int32)
+    best = np.array([M[e, best_arg[e]] for e in range(E)], np.float64)
+    alt, alt_arg = np.full(E, np.inf, np.float64), np.full(E, NO_ALT, np.int32)
+    j = np.arange(n, dtype=np.int64)
+    for e in range(E):
+        outside = np.abs(j - int(fwd.shifts[e])) > int(guard[e])
+        if outside.any():
+            at = int(np.argmin(np.where(outside, M[e], np.inf)))       # the first index of the minimum outside the window
+            alt[e], alt_arg[e] = M[e, at], at
+    return TrackOrderedMarginsHost(*(tuple(fwd) + (D, M, through, best, best_arg, alt, alt_arg, c_min)))
+
+
 class TrackState(object):
     """The device arrays of one sequence of n_total rows over n_shift shifts: D (float64[2 * n_shift]: two halves, used by turns),
     moves (int16[n_total * n_shift]), row_min (float64[n_total]), row_arg / row_own_index (int32[n_total]), row_own_scores
@@ -346,16 +421,24 @@ class TrackState(object):
     best_arg, alt_arg (int32[n_total]).
     ordered=True (not together with keep): the state of the ordered pass (track_ordered_device fills it, chunk by chunk;
     track_ordered_backtrack_device reads it) -- also P (float64[n_shift]: the prefix minimum of the last row advanced), prefix_arg
-    (int32[n_total * n_shift]: row e holds A_e) and back (int32[n_total]: every advanced row's back)."""
+    (int32[n_total * n_shift]: row e holds A_e) and back (int32[n_total]: every advanced row's back).
+    ordered=True, margins=True: the ordered pass with its rows kept (track_ordered_keep_device fills it) -- D is float64[n_total *
+    n_shift] -- and what track_ordered_margins_device needs and fills: keep=True's C and per-row outputs, and S (float64[n_shift]:
+    the suffix minimum of the last row walked)."""
 
-    def __init__(self, n_total, n_shift, device, keep=False, ordered=False):
+    def __init__(self, n_total, n_shift, device, keep=False, ordered=False, margins=False):
         import torch
         n_total, n_shift = int(n_total), int(n_shift)
         if n_total < 1 or n_shift < 1 or n_shift > 2 ** 31 - 1:
             raise SushiError("track: a sequence has >= 1 rows and 1 .. 2^31 - 1 shifts")
         if keep and ordered:
             raise SushiError("track: the ordered pass keeps no rows (its margins are not built)")
-        self.n_total, self.n_shift, self.device, self.keep, self.ordered = n_total, n_shift, device, bool(keep), bool(ordered)
+        if margins and not ordered:
+            raise SushiError("track: margins= belongs to a TrackState(ordered=True); the plain pass keeps its rows with keep=True")
+        margins = bool(margins)
+        keep = bool(keep) or margins                # D holds every row
+        self.n_total, self.n_shift, self.device, self.keep, self.ordered = n_total, n_shift, device, keep, bool(ordered)
+        self.margins = margins
         with torch.cuda.device(device):
             if ordered:
                 self.P = torch.empty(n_shift, dtype=torch.float64, device=device)
@@ -372,6 +455,8 @@ class TrackState(object):
                 self.c_min, self.through, self.best, self.alt = (torch.empty(n_total, dtype=torch.float64, device=device)
                                                                  for _ in range(4))
                 self.best_arg, self.alt_arg = (torch.empty(n_total, dtype=torch.int32, device=device) for _ in range(2))
+            if margins:
+                self.S = torch.empty(n_shift, dtype=torch.float64, device=device)
 
     def tensors(self):
         return (self.D, self.moves, self.row_min, self.row_arg, self.row_own_index, self.row_own_scores)
@@ -388,10 +473,13 @@ class TrackState(object):
         return self.D[half * self.n_shift:(half + 1) * self.n_shift]
 
     @staticmethod
-    def nbytes(n_total, n_shift, keep=False, marginals=False, ordered=False):
+    def nbytes(n_total, n_shift, keep=False, marginals=False, ordered=False, margins=False):
         """Bytes of moves and D: what grows with the sequence.  keep: every row of D and the two halves of C; marginals: M too;
-        ordered: moves and A, 6 bytes per (event, shift), the two halves of D and P."""
+        ordered: moves and A, 6 bytes per (event, shift), the two halves of D and P; ordered with margins: moves, A and every row of
+        D, 14 bytes per (event, shift), the two halves of C, P and S, and M with marginals."""
         n_total, n_shift = int(n_total), int(n_shift)
+        if ordered and margins:
+            return n_total * n_shift * 14 + 2 * n_shift * 8 + 2 * n_shift * 8 + (n_total * n_shift * 8 if marginals else 0)
         if ordered:
             return n_total * n_shift * 6 + 2 * n_shift * 8 + n_shift * 8
         if not keep:
@@ -496,9 +584,25 @@ def track_ordered_device(curves, rows, reach, penalties, step_cost, back, state,
     continues what the calls before it on the same stream left in `state` -- D, and P of the last row advanced: a sequence goes
     through chunk by chunk, with the bits of one call.  Three launches per row; measured at 64 rows x 2.88 M shifts, 12.3 x
     track_device's time at reach 0 and 2.8 x at reach 88 (profiles/track_order/).  Asynchronous on hip_stream."""
-    from .device import _launch
     if not getattr(state, "ordered", False):
         raise SushiError("track: track_ordered_device needs a TrackState(ordered=True)")
+    if getattr(state, "margins", False):
+        raise SushiError("track: a state that keeps its rows goes through track_ordered_keep_device")
+    return _forward_ordered_device("sushi_hip_track_forward_ordered", curves, rows, reach, penalties, step_cost, back, state, row0, method,
+                                   hip_stream)
+
+
+def track_ordered_keep_device(curves, rows, reach, penalties, step_cost, back, state, row0=0, method="sqdiff_normed", hip_stream=None):
+    """track_ordered_device through sushi_hip_track_forward_ordered_keep: `state` is a TrackState(ordered=True, margins=True), and row
+    e of its D is D_e afterwards.  Everything else -- arguments, the other outputs and their bits, chunks -- is track_ordered_device's."""
+    if not (getattr(state, "ordered", False) and getattr(state, "margins", False)):
+        raise SushiError("track: track_ordered_keep_device needs a TrackState(ordered=True, margins=True)")
+    return _forward_ordered_device("sushi_hip_track_forward_ordered_keep", curves, rows, reach, penalties, step_cost, back, state, row0,
+                                   method, hip_stream)
+
+
+def _forward_ordered_device(name, curves, rows, reach, penalties, step_cost, back, state, row0, method, hip_stream):
+    from .device import _launch
     axis.check_curves(curves, "track", device=state.D.device)
     rt = axis.row_table(rows)
     n_rows = rt.shape[0]
@@ -511,13 +615,67 @@ def track_ordered_device(curves, rows, reach, penalties, step_cost, back, state,
     bc = np.ascontiguousarray(checked_back(back, n_rows, first_row=row0))
     axis.check_rows_inside(rt, int(curves.numel()), state.n_shift, "track")
     L = _native.lib()
-    _launch("sushi_hip_track_forward_ordered", state.D.device, L.sushi_hip_track_order_bytes(n_rows, state.n_shift),
-            lambda mem, mem_bytes, st: L.sushi_hip_track_forward_ordered(
+    fn = getattr(L, name)
+    _launch(name, state.D.device, L.sushi_hip_track_order_bytes(n_rows, state.n_shift),
+            lambda mem, mem_bytes, st: fn(
                 curves.data_ptr(), int(curves.numel()), rt.ctypes.data, rc.ctypes.data, bc.ctypes.data, n_rows, state.n_shift,
                 _native.METHODS[method], pc.ctypes.data, mu, row0, state.n_total, state.D.data_ptr(), state.moves.data_ptr(),
                 state.P.data_ptr(), state.prefix_arg.data_ptr(), state.back.data_ptr(), state.row_min.data_ptr(),
                 state.row_arg.data_ptr(), state.row_own_index.data_ptr(), state.row_own_scores.data_ptr(), mem, mem_bytes, st),
             (curves,) + state.tensors() + state.order_tensors(), hip_stream)
+    return state
+
+
+def track_ordered_margins_device(curves, rows, reach, guard, penalties, step_cost, back, state, shifts, row0=0, method="sqdiff_normed",
+                                 marginals=None, hip_stream=None):
+    """One call of sushi_hip_track_order_margins: rows row0 + len(rows) - 1 down to row0 of `state`'s sequence (a TrackState(ordered=True,
+    margins=True) whose every row has gone through track_ordered_keep_device), `shifts` the int32 CUDA tensor
+    track_ordered_backtrack_device returned.  track_margins_device's arguments, but reach, penalties and back are each a single value,
+    or one per row of the call and then that of row row0 + len(rows) where that row exists (the step out of the call's last row); entry
+    0 is not used.  The first call of a sequence ends at its last row; a later one continues downwards from what the call before it on
+    the same stream left in `state` (C and S), with the bits of one call.  Fills rows row0 .. of state.c_min, through, best, best_arg,
+    alt, alt_arg, and of marginals where given.  Three launches per row.  Asynchronous on hip_stream."""
+    from .device import _launch
+    import torch
+    if not (getattr(state, "ordered", False) and getattr(state, "margins", False)):
+        raise SushiError("track: track_ordered_margins_device needs a TrackState(ordered=True, margins=True)")
+    axis.check_curves(curves, "track", device=state.D.device)
+    rt = axis.row_table(rows)
+    n_rows = rt.shape[0]
+    _w, _lam, mu = _checked(rt["weight"], n_rows, 0.0, step_cost, method)
+    row0 = int(row0)
+    if row0 < 0 or row0 + n_rows > state.n_total:
+        raise SushiError("track: rows %d .. %d are not inside a sequence of %d" % (row0, row0 + n_rows - 1, state.n_total))
+    n_after = n_rows + (1 if row0 + n_rows < state.n_total else 0)
+
+    def per_row(values, what, fill):
+        values = [values] * n_after if values is None or np.ndim(values) == 0 else list(values)
+        if len(values) != n_after:
+            raise SushiError("track: %d %s for a margins call of %d rows that %s the sequence's last row (%d are needed)"
+                             % (len(values), what, n_rows, "ends below" if n_after > n_rows else "ends at", n_after))
+        return [fill] + values[1:]                                                              # entry 0 is not used
+
+    rc = np.ascontiguousarray(checked_reach(per_row(reach, "reaches", 0), n_after, first_row=row0))
+    pc = np.ascontiguousarray(checked_penalties(per_row(penalties, "penalties", 0.0), n_after, first_row=row0))
+    bc = np.ascontiguousarray(checked_back(per_row(back, "backs", BACK_ANY), n_after, first_row=row0))
+    gd = np.ascontiguousarray(checked_guard(guard, n_rows, first_row=row0))
+    axis.check_rows_inside(rt, int(curves.numel()), state.n_shift, "track")
+    if not (isinstance(shifts, torch.Tensor) and shifts.is_cuda and shifts.dtype == torch.int32 and shifts.is_contiguous()
+            and shifts.numel() == state.n_total and shifts.device == state.D.device):
+        raise SushiError("track: shifts is the backtrack's output, an int32 CUDA tensor of %d values" % state.n_total)
+    if marginals is not None and not (isinstance(marginals, torch.Tensor) and marginals.is_cuda and marginals.dtype == torch.float64
+                                      and marginals.is_contiguous() and marginals.numel() == state.n_total * state.n_shift
+                                      and marginals.device == state.D.device):
+        raise SushiError("track: marginals is a contiguous float64 CUDA tensor of %d x %d values" % (state.n_total, state.n_shift))
+    L = _native.lib()
+    _launch("sushi_hip_track_order_margins", state.D.device, L.sushi_hip_track_order_margins_bytes(n_rows, state.n_shift),
+            lambda mem, mem_bytes, st: L.sushi_hip_track_order_margins(
+                curves.data_ptr(), int(curves.numel()), rt.ctypes.data, rc.ctypes.data, bc.ctypes.data, gd.ctypes.data, n_rows,
+                state.n_shift, _native.METHODS[method], pc.ctypes.data, mu, row0, state.n_total, state.D.data_ptr(), shifts.data_ptr(),
+                state.C.data_ptr(), state.S.data_ptr(), state.c_min.data_ptr(), state.through.data_ptr(), state.best.data_ptr(),
+                state.best_arg.data_ptr(), state.alt.data_ptr(), state.alt_arg.data_ptr(),
+                None if marginals is None else marginals.data_ptr(), mem, mem_bytes, st),
+            (curves, shifts, state.D, state.S) + state.margin_tensors() + (() if marginals is None else (marginals,)), hip_stream)
     return state
 
 
@@ -704,10 +862,30 @@ def find_track(stream, patterns, window_centers, window_size, penalty, max_rate=
         clamp=None if f is None else float(f), rows_info=rows_info[0], back=None, penalties=None, **extra)
 
 
+def find_ordered_track(stream, patterns, window_centers, window_size, penalty, order=None, max_rate=None, reach=None, step_cost=0.0,
+                       slack=1, weights="equal", method="sqdiff_normed", max_bytes=MAX_BYTES, max_state_bytes=MAX_STATE_BYTES,
+                       margins=False, guard=None, marginals=False, clamp=None, capacity=None):
+    """WavStream.find_ordered_track (its docstring)."""
+    patterns, centres = list(patterns), list(window_centers)
+    if not patterns or len(patterns) != len(centres):
+        raise SushiError("find_ordered_track: equally many patterns and centres (>= 1)")
+    if (max_rate is None) == (reach is None):
+        raise SushiError("find_ordered_track: exactly one of max_rate and reach")
+    margins, marginals = bool(margins), bool(marginals)
+    if not margins and (marginals or guard is not None):
+        raise SushiError("find_ordered_track: guard and marginals belong to margins=True")
+    return _find_track_ordered(stream, patterns, centres, window_size, penalty, max_rate, reach, step_cost, slack, weights, method,
+                               max_bytes, max_state_bytes, clamp, capacity, None if order is False else order, margins=margins,
+                               guard=guard, marginals=marginals, name="find_ordered_track")
+
+
 def _find_track_ordered(stream, patterns, centres, window_size, penalty, max_rate, reach, step_cost, slack, weights, method, max_bytes,
-                        max_state_bytes, clamp, capacity, order):
+                        max_state_bytes, clamp, capacity, order, margins=False, guard=None, marginals=False, name="find_track"):
     """find_track through the ordered pass: order None (every back without a limit: a penalty per event alone), True (order_back of
-    the events) or one back per event; penalty a number or one per event."""
+    the events) or one back per event; penalty a number or one per event.  margins (find_ordered_track alone): the rows of the
+    forward pass are kept, and after the backtrack the chunks are walked again from the last one down (find_track(margins=True)'s
+    shape)."""
+    import torch
     from .curves import match_curves
     f, capacity = axis.checked_clamp(clamp, capacity, method)
     dst_dev = stream.device_stream()
@@ -721,25 +899,53 @@ def _find_track_ordered(stream, patterns, centres, window_size, penalty, max_rat
     reach = checked_reach(rate_reach(ax.bases, max_rate, slack) if reach is None else reach, E)
     back = checked_back(None if order is None else (order_back(ax.bases, lens) if order is True else order), E)
     back[0] = BACK_ANY
-    need = TrackState.nbytes(E, n_shift, ordered=True)
+    if margins:
+        guard = checked_guard(int(0.01 * rate) if guard is None else guard, E)
+    need = TrackState.nbytes(E, n_shift, ordered=True, margins=margins, marginals=marginals)
     if need > max_state_bytes:
-        raise SushiError("find_track: %d events x %d shifts need %d bytes of moves, jump sources and costs, max_state_bytes is %d"
-                         % (E, n_shift, need, max_state_bytes))
+        if margins:
+            raise SushiError("%s: %d events x %d shifts need %d bytes of moves, jump sources, kept costs%s, max_state_bytes is %d (%d "
+                             "without margins)" % (name, E, n_shift, need, " and marginals" if marginals else "", max_state_bytes,
+                                                   TrackState.nbytes(E, n_shift, ordered=True)))
+        raise SushiError("%s: %d events x %d shifts need %d bytes of moves, jump sources and costs, max_state_bytes is %d"
+                         % (name, E, n_shift, need, max_state_bytes))
     per_chunk = int(max_bytes) // (4 * n_shift)
     if per_chunk < 1:
-        raise SushiError("find_track: one event of %d shifts needs %d bytes of curves, max_bytes is %d"
-                         % (n_shift, 4 * n_shift, max_bytes))
-    state = TrackState(E, n_shift, dst_dev.device, ordered=True)
+        raise SushiError("%s: one event of %d shifts needs %d bytes of curves, max_bytes is %d"
+                         % (name, n_shift, 4 * n_shift, max_bytes))
+    state = TrackState(E, n_shift, dst_dev.device, ordered=True, margins=margins)
+    forward = track_ordered_keep_device if margins else track_ordered_device
+    chunks = [(first, min(E, first + per_chunk)) for first in range(0, E, per_chunk)]
     rows_info = None
-    for first in range(0, E, per_chunk):
-        last = min(E, first + per_chunk)
+    for first, last in chunks:
         info = {}
         curves, row_off = axis.event_rows(dst_dev, src_dev, [ax.part(first, last)], method, clamp=f, capacity=capacity, info=info)
         if f is not None:
             rows_info = axis.merge_rows_info(rows_info, info)
-        track_ordered_device(curves, zip(row_off, w[first:last].tolist()), reach[first:last], lam[first:last], mu, back[first:last],
-                             state, row0=first, method=method)
+        forward(curves, zip(row_off, w[first:last].tolist()), reach[first:last], lam[first:last], mu, back[first:last],
+                state, row0=first, method=method)
     index_dev = track_ordered_backtrack_device(state)
+    extra = dict(guard=None, event_through=None, event_margin=None, event_alt_shift=None, event_alt_delta=None, marginals=None)
+    if margins:
+        # the chunks again, from the last one down: a lone chunk's curves are still there, several chunks' are formed a second time
+        M = torch.empty(E * n_shift, dtype=torch.float64, device=state.D.device) if marginals else None
+        for first, last in reversed(chunks):
+            if len(chunks) > 1:
+                info = {}
+                curves, row_off = axis.event_rows(dst_dev, src_dev, [ax.part(first, last)], method, clamp=f, capacity=capacity,
+                                                  info=info)
+                if f is not None:
+                    rows_info = axis.merge_rows_info(rows_info, info)
+            upto = last + 1 if last < E else last
+            track_ordered_margins_device(curves, zip(row_off, w[first:last].tolist()), reach[first:upto], guard[first:last],
+                                         lam[first:upto], mu, back[first:upto], state, index_dev, row0=first, method=method,
+                                         marginals=M)
+        through, alt, alt_arg = state.through.cpu().numpy(), state.alt.cpu().numpy(), state.alt_arg.cpu().numpy()
+        alt_shift = [None if int(k) == NO_ALT else k_lo + int(k) for k in alt_arg]
+        extra = dict(guard=guard.tolist(), event_through=through,
+                     event_margin=np.where(alt_arg == NO_ALT, np.inf, alt - through), event_alt_shift=alt_shift,
+                     event_alt_delta=[None if k is None else k / float(rate) for k in alt_shift],
+                     marginals=None if M is None else M.view(E, n_shift))
     index = index_dev.cpu().numpy()
     words = state.moves[index_dev.long() + n_shift * _arange_like(index_dev)].cpu().numpy()
     shifts = [k_lo + int(k) for k in index]
@@ -752,9 +958,8 @@ def _find_track_ordered(stream, patterns, centres, window_size, penalty, max_rat
         segments=[(s, n, shifts[s] / float(rate), shifts[s + n - 1] / float(rate)) for s, n in jump_runs(E, jumps)],
         cost=float(state.row_min[E - 1].item()), event_scores=at.cpu().numpy(),
         event_own_delta=[(k_lo + int(k)) / float(rate) for k in own], event_own_scores=state.row_own_scores.cpu().numpy(),
-        clamp=None if f is None else float(f), rows_info=rows_info, guard=None, event_through=None, event_margin=None,
-        event_alt_shift=None, event_alt_delta=None, marginals=None,
-        back=[None if int(b) == BACK_ANY else int(b) for b in back], penalties=lam.tolist())
+        clamp=None if f is None else float(f), rows_info=rows_info,
+        back=[None if int(b) == BACK_ANY else int(b) for b in back], penalties=lam.tolist(), **extra)
 
 
 def _arange_like(index_dev):

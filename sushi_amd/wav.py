@@ -668,8 +668,8 @@ class WavStream(object):
         jumps, one of which goes back further than any cut can: with order= small penalties stay safe.  penalty may also be one
         number per event (event 0's is ignored): a cut is cheap at a chapter mark and dear inside a dialogue
         (sushi_amd.shifts.chapter_penalties).  Either takes the ordered pass: its state is E x n_shift x 6 + 3 x n_shift x 8 bytes
-        under max_state_bytes, the Track gains back and penalties, and margins=True with it is a SushiError (not built: the
-        backward recurrence needs the mirrored suffix minimum).  Moves are not restricted by order.  Without order= and with one
+        under max_state_bytes, the Track gains back and penalties, and margins=True with it is a SushiError (not built here:
+        the ordered pass's margins are find_ordered_track's).  Moves are not restricted by order.  Without order= and with one
         penalty the code path, the launches and the bits are those of before.  Measured on one MI355X (profiles/track_order/): the
         ordered forward pass takes 12.3 x the plain one at reach 0 and 2.8 x at reach 88 (64 rows x 2.88 M shifts: 14.1 ms
         against 1.1 ms, 20.2 ms against 7.2 ms -- its prefix-minimum kernel, not tuned); a whole call on 64 uint8 events at +-120 s
@@ -680,6 +680,28 @@ class WavStream(object):
                                 max_bytes=track.MAX_BYTES if max_bytes is None else int(max_bytes),
                                 max_state_bytes=track.MAX_STATE_BYTES if max_state_bytes is None else int(max_state_bytes),
                                 margins=margins, guard=guard, marginals=marginals, clamp=clamp, capacity=capacity, order=order)
+
+    def find_ordered_track(self, patterns, window_centers, window_size, penalty, order=None, max_rate=None, reach=None, step_cost=0.0,
+                           slack=1, weights='equal', method="sqdiff_normed", max_bytes=None, max_state_bytes=None, margins=False,
+                           guard=None, marginals=False, clamp=None, capacity=None):
+        """find_track through the ordered pass, and how firmly it places every event.  order and
+        penalty (a number, or one per event) are find_track's; with margins=False this is find_track(order=order) -- the same
+        launches, the same bits, the same Track (and with order=None and one penalty the ordered pass without a limit, whose bits
+        are the plain pass's).  margins=True keeps every row of the ordered forward pass, backtracks, and walks the chunks again from
+        the last one down with the backward recurrence of the ordered model -- a jump out of event e reaches shift j of event e + 1
+        only from shifts up to j + back_{e+1}, which the suffix minimum read at max(j - back_{e+1}, 0) states -- so the Track's
+        guard, event_through, event_margin, event_alt_shift / event_alt_delta and (marginals=True) marginals are find_track's
+         for the model the caller asked for: an event that can reach its alternative only by a jump no cut can make
+        is as firm as its whole run.  guard: an int or one per event, in samples (default int(0.01 * sample_rate)).  The state is E
+        x n_shift x 14 + 4 x n_shift x 8 bytes (and E x n_shift x 8 for marginals) under max_state_bytes; SushiError names the
+        need.  One chunk of max_bytes keeps its curves; several chunks form every chunk's rows a second time (clamp= / capacity=
+        work as in find_track).  Needs a GPU."""
+        from . import track
+        return track.find_ordered_track(self, patterns, window_centers, window_size, penalty, order=order, max_rate=max_rate, reach=reach,
+                                        step_cost=step_cost, slack=slack, weights=weights, method=method,
+                                        max_bytes=track.MAX_BYTES if max_bytes is None else int(max_bytes),
+                                        max_state_bytes=track.MAX_STATE_BYTES if max_state_bytes is None else int(max_state_bytes),
+                                        margins=margins, guard=guard, marginals=marginals, clamp=clamp, capacity=capacity)
 
     # ------------------------------------------------------------------ a shift that moves along the programme
     def find_drift(self, patterns, window_centers, window_size, max_rate, resolution=1.0, weights='equal', method="sqdiff_normed",
