@@ -57,7 +57,10 @@ extern "C" {
                                      13 (additive): SUSHI_HIP_TRACK_BACK_ANY, sushi_hip_track_order_bytes,
                                      sushi_hip_track_forward_ordered, sushi_hip_track_backtrack_ordered;
                                      13 (additive): sushi_hip_track_forward_ordered_keep, sushi_hip_track_order_margins_bytes,
-                                     sushi_hip_track_order_margins */
+                                     sushi_hip_track_order_margins;
+                                     13 (additive): SUSHI_HIP_TRACK_WIDE_MAX_REACH, sushi_hip_track_wide_bytes,
+                                     sushi_hip_track_margins_wide_bytes, sushi_hip_track_forward_wide,
+                                     sushi_hip_track_forward_wide_keep, sushi_hip_track_margins_wide */
 
 #if defined(__GNUC__)
 #define SUSHI_HIP_API __attribute__((visibility("default")))
@@ -817,6 +820,58 @@ SUSHI_HIP_API int sushi_hip_track_order_margins(const float* curves_dev, int64_t
                                                 double* c_min_dev, double* through_dev, double* best_dev, int32_t* best_arg_dev,
                                                 double* alt_dev, int32_t* alt_arg_dev, double* M_dev,
                                                 void* mem_dev, size_t mem_bytes, void* hip_stream);
+
+/* ---- wide tracking: a reach up to 32767 where moves are free (13, additive) -----------------------------------
+ * "tracking" and "margins" word for word, with one bound raised: a row's reach may be 0 .. SUSHI_HIP_TRACK_WIDE_MAX_REACH, and every
+ * used reach above SUSHI_HIP_TRACK_MAX_REACH requires a step_cost of +0.0 or -0.0 (with a price per sample a move of more than
+ * penalty / step_cost samples never beats a jump: clip the reach instead).  A move word is an int16 and SUSHI_HIP_TRACK_JUMP is
+ * -32768, so +-32767 fits; sushi_hip_track_backtrack is used as it is.  For a row X (D_{e-1} forwards, C_{e+1} backwards), a reach
+ * r above SUSHI_HIP_TRACK_MAX_REACH and mu = step_cost, near[j] is what the candidate-by-candidate definition gives, bit for bit:
+ *     cand(0) = X[j] itself;  cand(d) = X[j + d] + mu * (double)|d| for 0 < |d| <= r, 0 <= j + d < n_shift
+ *     (mu = +0.0: a winning -0.0 at d != 0 becomes +0.0;  mu = -0.0: it keeps its bits)
+ *     near[j] = the smallest candidate under the order (value, |d|, d > 0).  Adding +-0.0 changes no order, so this is:
+ *         left  = the minimum of X[j - r .. j - 1], of equal values the LARGEST index
+ *         right = the minimum of X[j + 1 .. j + r], of equal values the SMALLEST index        (0.0 and -0.0 are equal)
+ *         own, left and right combined under the same order; the price is added once, to the winner
+ * computed in a time that does not grow with r.  A row whose reach is at most SUSHI_HIP_TRACK_MAX_REACH goes through the kernels of
+ * sushi_hip_track_forward / sushi_hip_track_margins themselves: with every reach <= SUSHI_HIP_TRACK_MAX_REACH each wide call gives
+ * the plain call's outputs bit for bit. */
+#define SUSHI_HIP_TRACK_WIDE_MAX_REACH 32767
+/* workspace of a wide forward / a wide margins call: the plain call's, then one row's window records (24 bytes per shift: per
+ * element the minimum of its 1024-value tile up to it and from it on, each a float64 and two 16-bit indices); 0 wherever
+ * sushi_hip_track_bytes / sushi_hip_track_margins_bytes is 0 */
+SUSHI_HIP_API size_t sushi_hip_track_wide_bytes(int n_rows, int32_t n_shift);
+SUSHI_HIP_API size_t sushi_hip_track_margins_wide_bytes(int n_rows, int32_t n_shift);
+/* sushi_hip_track_forward / sushi_hip_track_forward_keep with a reach up to SUSHI_HIP_TRACK_WIDE_MAX_REACH: the arguments, the
+ * outputs, chunks (a sequence may mix plain and wide calls: the state is the same) and the refusals in their order, but -- EINVAL: a
+ * reach outside 0 .. SUSHI_HIP_TRACK_WIDE_MAX_REACH in any row but the sequence's row 0, or such a reach above
+ * SUSHI_HIP_TRACK_MAX_REACH beside a step_cost that is not +-0.0; ENOSPACE: mem_bytes < sushi_hip_track_wide_bytes.  A wide row
+ * takes two launches, stream-ordered; no grid waits on itself and there are no atomics. */
+SUSHI_HIP_API int sushi_hip_track_forward_wide(const float* curves_dev, int64_t n_curve,
+                                               const SushiHipJointRow* rows_host, const int32_t* reach_host, int n_rows, int32_t n_shift,
+                                               int method, double penalty, double step_cost, int row0, int n_total,
+                                               double* D_dev, int16_t* move_dev,
+                                               double* row_min_dev, int32_t* row_arg_dev,
+                                               int32_t* row_own_index_dev, float* row_own_score_dev,
+                                               void* mem_dev, size_t mem_bytes, void* hip_stream);
+SUSHI_HIP_API int sushi_hip_track_forward_wide_keep(const float* curves_dev, int64_t n_curve,
+                                                    const SushiHipJointRow* rows_host, const int32_t* reach_host, int n_rows,
+                                                    int32_t n_shift, int method, double penalty, double step_cost, int row0, int n_total,
+                                                    double* D_all_dev, int16_t* move_dev,
+                                                    double* row_min_dev, int32_t* row_arg_dev,
+                                                    int32_t* row_own_index_dev, float* row_own_score_dev,
+                                                    void* mem_dev, size_t mem_bytes, void* hip_stream);
+/* sushi_hip_track_margins in the same way: a used reach outside 0 .. SUSHI_HIP_TRACK_WIDE_MAX_REACH, or one above
+ * SUSHI_HIP_TRACK_MAX_REACH beside a step_cost that is not +-0.0, is EINVAL; ENOSPACE: mem_bytes <
+ * sushi_hip_track_margins_wide_bytes. */
+SUSHI_HIP_API int sushi_hip_track_margins_wide(const float* curves_dev, int64_t n_curve,
+                                               const SushiHipJointRow* rows_host, const int32_t* reach_host, const int32_t* guard_host,
+                                               int n_rows, int32_t n_shift, int method, double penalty, double step_cost,
+                                               int row0, int n_total,
+                                               const double* D_all_dev, const int32_t* shift_dev, double* C_dev, double* c_min_dev,
+                                               double* through_dev, double* best_dev, int32_t* best_arg_dev,
+                                               double* alt_dev, int32_t* alt_arg_dev, double* M_dev,
+                                               void* mem_dev, size_t mem_bytes, void* hip_stream);
 
 /* ---- rows: score rows clamped at a threshold, formed from a threshold run's hits (13, additive) ---------------
  * A pass over a shift axis needs to know where a row is good and how good; how bad the rest is only feeds decoys.  The CLAMPED row

@@ -21,6 +21,7 @@ METHOD_SQDIFF_NORMED, METHOD_CCOEFF_NORMED = 0, 1       # cv2.TM_SQDIFF_NORMED +
 MIX_MAX_CHANNELS, MIX_MAX_OUTPUTS = 32, 8    # SUSHI_HIP_MIX_MAX_*: channels and output rows of sushi_hip_load_decode_mix
 BEST_MAX_K = 32            # SUSHI_HIP_BEST_MAX_K: picks per request of a best-K run (sushi_hip_batch_run_best)
 TRACK_MAX_REACH, TRACK_JUMP = 1024, -32768   # SUSHI_HIP_TRACK_*: the widest move between two events, and the move word of a jump
+TRACK_WIDE_MAX_REACH = 32767     # SUSHI_HIP_TRACK_WIDE_MAX_REACH: the widest move of the wide pass (a free move: step_cost 0)
 TRACK_BACK_ANY = -1        # SUSHI_HIP_TRACK_BACK_ANY: a back that leaves a jump free to come from anywhere
 METHODS = {"sqdiff_normed": METHOD_SQDIFF_NORMED, "ccoeff_normed": METHOD_CCOEFF_NORMED}
 VIEW_XC, VIEW_S1, VIEW_S2, VIEW_UREL, VIEW_BASE, VIEW_SPECTRA, VIEW_USREL, VIEW_BASE1, VIEW_COARSE, VIEW_SPECTRA_LOW, \
@@ -204,6 +205,16 @@ def lib():
     L.sushi_hip_track_margins.restype = ci
     L.sushi_hip_track_margins.argtypes = [vp, i64, vp, vp, vp, ci, i32, ci, dbl, dbl, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                           sz, vp]
+    L.sushi_hip_track_wide_bytes.restype = sz
+    L.sushi_hip_track_wide_bytes.argtypes = [ci, i32]
+    L.sushi_hip_track_margins_wide_bytes.restype = sz
+    L.sushi_hip_track_margins_wide_bytes.argtypes = [ci, i32]
+    L.sushi_hip_track_forward_wide.restype = ci
+    L.sushi_hip_track_forward_wide.argtypes = L.sushi_hip_track_forward.argtypes
+    L.sushi_hip_track_forward_wide_keep.restype = ci
+    L.sushi_hip_track_forward_wide_keep.argtypes = L.sushi_hip_track_forward.argtypes
+    L.sushi_hip_track_margins_wide.restype = ci
+    L.sushi_hip_track_margins_wide.argtypes = L.sushi_hip_track_margins.argtypes
     L.sushi_hip_track_order_bytes.restype = sz
     L.sushi_hip_track_order_bytes.argtypes = [ci, i32]
     L.sushi_hip_track_forward_ordered.restype = ci

@@ -59,6 +59,10 @@ UNITS = [
     # how firmly the ordered pass places each event: the margins step with a jump read per index from the suffix minimum of the row
     # after, and per row a scan downwards that writes it (track_order_margin_core.hpp: t', the jump sum, the call's host side)
     ("sushi_track_order_margins", ["-ffp-contract=off"]),       # the candidates unchanged; the jump's sum, M and C round once each
+    # the tracking pass and its margins with a reach up to 32767 where moves are free: per wide row a tile pass of prefix / suffix
+    # minima and a step that combines a few of its records; narrower rows go through sushi_track's and sushi_track_margins' own
+    # step kernels (the two .inc parts) (track_wide_core.hpp: the decomposition, the records, the call's host side)
+    ("sushi_track_wide", ["-ffp-contract=off"]),        # track_core.hpp's candidates unchanged: the price is added once, to the winner
     # score rows clamped at a threshold: a fill and a scatter of a threshold run's hits, and the rule applied to rows that exist
     # (rows_core.hpp: the rule, the tiles, the search of a hit list, and the call's host side)
     ("sushi_rows", []),                         # comparisons and copies: no arithmetic to contract

@@ -437,7 +437,8 @@ def chapter_penalties(events, chapter_times, penalty, chapter_penalty):
 
 
 def calculate_tracked_shifts(src_stream, dst_stream, events, window, penalty, max_rate=None, reach=None, step_cost=0.0,
-                             centre_shift=0.0, margins=False, guard=None, marginals=False, clamp=None, capacity=None, order=None):
+                             centre_shift=0.0, margins=False, guard=None, marginals=False, clamp=None, capacity=None, order=None,
+                             wide=False):
     """A shift per event that may move a little between events and jump where a jump pays (sushi_amd.track):
     `events` is a list of ScriptEvent in order; every event's pattern is src_stream.get_substream(e.start, e.end) and its centre
     e.start + centre_shift.  All go through one dst_stream.find_track call with window `window` (seconds), `penalty`, and max_rate
@@ -446,7 +447,9 @@ def calculate_tracked_shifts(src_stream, dst_stream, events, window, penalty, ma
     firmly every event is placed (event_margin, event_alt_delta, ...).  clamp, capacity: find_track's (rows clamped at a threshold;
     the scores the events get stay the true ones).  order: find_track's (None; True: the events are kept in order in the
     destination; or one back per event), and `penalty` may be one number per event (chapter_penalties gives them from chapter marks):
-    either takes the ordered pass, whose margins are calculate_ordered_shifts'.  Returns the Track."""
+    either takes the ordered pass, whose margins are calculate_ordered_shifts'.  wide: find_track's (a reach up to
+    32767 samples where step_cost is 0: a long stretch without an event no longer ends the call).  Returns the
+    Track."""
     events = list(events)
     shift = float(centre_shift)
     if not events:
@@ -455,10 +458,14 @@ def calculate_tracked_shifts(src_stream, dst_stream, events, window, penalty, ma
     for e, p in zip(events, patterns):
         if p.shape[1] < 1:
             raise SushiError("calculate_tracked_shifts: event %s has no samples in the source" % e)
+    # (the keywords a caller did not use are not passed on: a stream without them still serves)
+    more = {} if clamp is None and capacity is None else dict(clamp=clamp, capacity=capacity)
+    if order is not None:
+        more["order"] = order
+    if wide:
+        more["wide"] = True
     found = dst_stream.find_track(patterns, [e.start + shift for e in events], window, penalty, max_rate=max_rate, reach=reach,
-                                  step_cost=step_cost, margins=margins, guard=guard, marginals=marginals,
-                                  **dict({} if clamp is None and capacity is None else dict(clamp=clamp, capacity=capacity),
-                                         **({} if order is None else dict(order=order))))
+                                  step_cost=step_cost, margins=margins, guard=guard, marginals=marginals, **more)
     for e, delta, score in zip(events, found.deltas, found.event_scores):
         e.set_shift(shift + delta, score)
     return found

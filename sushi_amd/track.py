@@ -17,6 +17,10 @@ minimum over all assignments (include/sushi_hip.h "tracking").  
   ``penalty`` per event run it.
 * ``track_margins_host`` / ``track_forward_keep_device`` / ``track_margins_device`` -- how firmly each event is placed: the pass's
   min-marginals (include/sushi_hip.h "margins"), in NumPy and on the device; ``find_track(margins=True)`` runs them.
+* ``wide=True`` on ``track_host``, ``track_margins_host``, ``TrackState`` and ``find_track``, and ``track_wide_device`` /
+  ``track_wide_keep_device`` / ``track_wide_margins_device`` -- a reach up to 32767 where moves are free (include/sushi_hip.h "wide
+  tracking"): a wide row's window minimum comes from prefix and suffix minima (``_near_wide``), bit for bit the
+  candidate loop's.
 * ``track_ordered_margins_host`` / ``TrackState(ordered=True, margins=True)`` / ``track_ordered_keep_device`` /
   ``track_ordered_margins_device`` -- the same for the ordered pass (include/sushi_hip.h "ordered margins"; DESIGN.md 3.22);
   ``find_ordered_track(margins=True)`` runs them.
@@ -33,6 +37,7 @@ from .segments import _checked as _checked_path
 
 MAX_STATE_BYTES = 2 << 30     # moves and D of one sequence (find_track)
 MAX_REACH, JUMP = _native.TRACK_MAX_REACH, _native.TRACK_JUMP
+WIDE_MAX_REACH = _native.TRACK_WIDE_MAX_REACH      # wide=True: the widest move, allowed where step_cost is 0
 
 TrackHost = namedtuple("TrackHost", "shifts cost row_min row_arg moves row_own_index row_own_scores")
 TrackMarginsHost = namedtuple("TrackMarginsHost", TrackHost._fields + ("D", "marginals", "through", "best", "best_arg", "alt", "alt_arg",
@@ -54,9 +59,11 @@ def _checked(weights, n, penalty, step_cost, method):
     return w, lam, mu
 
 
-def checked_reach(reach, n, first_row=0):
-    """`reach` -- one int for every row, or a sequence of n -- as an int32 array of n values in 0 .. MAX_REACH; the value of the
-    sequence's row 0 (first_row == 0: entry 0) is ignored and returned as 0.  SushiError names the row and the value otherwise."""
+def checked_reach(reach, n, first_row=0, wide=False):
+    """`reach` -- one int for every row, or a sequence of n -- as an int32 array of n values in 0 .. MAX_REACH (wide: 0 ..
+    WIDE_MAX_REACH); the value of the sequence's row 0 (first_row == 0: entry 0) is ignored and returned as 0.  SushiError names the
+    row and the value otherwise."""
+    most = WIDE_MAX_REACH if wide else MAX_REACH
     try:
         r = [int(reach)] * n if np.ndim(reach) == 0 else [int(x) for x in reach]
     except (TypeError, ValueError):
@@ -66,9 +73,20 @@ def checked_reach(reach, n, first_row=0):
     if first_row == 0 and r:
         r[0] = 0
     for i, x in enumerate(r):
-        if x < 0 or x > MAX_REACH:
-            raise SushiError("track: the reach of event %d is %d, outside 0 .. %d" % (first_row + i, x, MAX_REACH))
+        if x < 0 or x > most:
+            raise SushiError("track: the reach of event %d is %d, outside 0 .. %d" % (first_row + i, x, most))
     return np.array(r, np.int32)
+
+
+def checked_wide_step_cost(reach, mu, first_row=0):
+    """The wide pass's one condition: a reach above MAX_REACH (`reach`: checked_reach's array) needs a step_cost of 0.  SushiError
+    names the event, the reach and the step cost otherwise."""
+    if mu != 0.0:
+        for i, x in enumerate(reach):
+            if x > MAX_REACH:
+                raise SushiError("track: the reach of event %d is %d, above %d, and step_cost is %r: a wide move is a free move.  Such a "
+                                 "move costs more than a jump once step_cost * reach > penalty, so clip the reach to %d or to penalty / "
+                                 "step_cost" % (first_row + i, x, MAX_REACH, mu, MAX_REACH))
 
 
 def checked_guard(guard, n, first_row=0):
@@ -107,7 +125,85 @@ def _near(D, reach, mu, moves=False):
     return near, nd
 
 
-def track_host(rows, weights, penalty, step_cost, reach, method="sqdiff_normed", _keep=None):
+def _block_arg_minima(D, r):
+    """The axis in blocks of r values: (pF, pL, sF, sL), int64 arrays of n -- the index of the minimum of D[block's first index .. i]
+    (p) and of D[i .. block's last index] (s), of equal values (0.0 and -0.0 are equal) the first (F) or the last (L)."""
+    n = D.shape[0]
+    nb = -(-n // r)
+    B = np.full(nb * r, np.inf, np.float64)
+    B[:n] = D
+    B = B.reshape(nb, r)
+    idx = np.arange(nb * r, dtype=np.int64).reshape(nb, r)
+    pos = np.arange(r, dtype=np.int64)
+
+    def last_record(record, index):
+        at = np.maximum.accumulate(np.where(record, pos, -1), axis=1)       # the scan position of the latest record
+        return np.take_along_axis(index, np.maximum(at, 0), axis=1)
+
+    run = np.minimum.accumulate(B, axis=1)
+    new_f, new_l = np.ones((nb, r), bool), np.ones((nb, r), bool)
+    new_f[:, 1:] = B[:, 1:] < run[:, :-1]            # upwards: an equal value is not the first ...
+    new_l[:, 1:] = B[:, 1:] <= run[:, :-1]           # ... but it is the last
+    pF, pL = last_record(new_f, idx), last_record(new_l, idx)
+    # downwards: the columns reversed.  The padding behind the axis's end comes first there: it is no record, and the first real
+    # value is one whatever it is
+    Br, idx_r = B[:, ::-1], idx[:, ::-1]
+    real = idx_r < n
+    first_real = real.copy()
+    first_real[:, 1:] &= ~real[:, :-1]
+    run = np.minimum.accumulate(Br, axis=1)
+    new_f, new_l = np.ones((nb, r), bool), np.ones((nb, r), bool)
+    new_f[:, 1:] = Br[:, 1:] <= run[:, :-1]          # downwards: an equal value lies lower, so it is the first ...
+    new_l[:, 1:] = Br[:, 1:] < run[:, :-1]           # ... and not the last
+    sF = last_record((new_f & real) | first_real, idx_r)[:, ::-1]
+    sL = last_record((new_l & real) | first_real, idx_r)[:, ::-1]
+    return tuple(a.reshape(-1)[:n] for a in (pF, pL, sF, sL))
+
+
+def _near_wide(D, reach, mu, moves=False):
+    """_near for a free move (mu is +0.0 or -0.0) in O(n) whatever the reach: adding +-0.0 changes no order, so the smallest
+    candidate under (value, |d|, d > 0) is the minimum of D[j - r .. j - 1] with ties to the largest index, the minimum of D[j + 1
+    .. j + r] with ties to the smallest, and D[j] itself, combined under that order; the price is added once, to the winner.  A
+    window of r values is a block's suffix and the next block's prefix (blocks of r values: van Herk's form), each with its first
+    and its last arg-min.  Bit for bit _near's (near, nd)."""
+    if mu != 0.0:
+        raise SushiError("track: the wide window minimum is for a step_cost of 0")
+    n = D.shape[0]
+    r = min(int(reach), n - 1)
+    if r < 1:
+        return D.copy(), (np.zeros(n, np.int16) if moves else None)
+    pF, pL, sF, sL = _block_arg_minima(D, r)
+    a = np.arange(n, dtype=np.int64)                 # a window's first index; its last is b
+    b = np.minimum(a + r - 1, n - 1)
+    cross = (a // r) != (b // r)                     # the window ends in the next block: its prefix there belongs to it
+    # (in one block the suffix from a is the window: it starts the block, or the axis's end cut it)
+    first = np.where(cross & (D[pF[b]] < D[sF[a]]), pF[b], sF[a])           # arg-min of D[a .. b], ties to the first
+    last = np.where(cross & (D[pL[b]] <= D[sL[a]]), pL[b], sL[a])           # ... ties to the last
+    j = np.arange(n, dtype=np.int64)
+    best, bd = D.copy(), np.zeros(n, np.int64)
+    # the left side of j >= 1: the window from j - r, or, where the axis's start cuts it, block 0's prefix up to j - 1
+    left = np.where(j[1:] >= r, last[np.maximum(j[1:] - r, 0)], pL[j[1:] - 1])
+    take = D[left] < best[1:]                        # an equal value does not beat d = 0
+    best[1:][take] = D[left][take]
+    bd[1:][take] = (left - j[1:])[take]
+    # the right side of j <= n - 2: the window from j + 1; of equal values the smaller |d|, then the negative d, wins
+    right = first[j[:-1] + 1]
+    dr = right - j[:-1]
+    take = (D[right] < best[:-1]) | ((D[right] == best[:-1]) & (bd[:-1] != 0) & (dr < -bd[:-1]))
+    best[:-1][take] = D[right][take]
+    bd[:-1][take] = dr[take]
+    moved = bd != 0
+    near = D.copy()                                  # cand(0): the value itself, nothing added
+    near[moved] = D[(j + bd)[moved]] + np.float64(mu) * np.abs(bd[moved]).astype(np.float64)
+    return near, (bd.astype(np.int16) if moves else None)
+
+
+def _near_of(reach):
+    """The window minimum of one row: the candidate loop up to MAX_REACH, the wide form above it."""
+    return _near_wide if int(reach) > MAX_REACH else _near
+
+
+def track_host(rows, weights, penalty, step_cost, reach, method="sqdiff_normed", _keep=None, wide=False):
     """sushi_hip_track_forward + sushi_hip_track_backtrack for one sequence in NumPy (include/sushi_hip.h states the arithmetic):
     rows, a list of E >= 1 float32 arrays of one length n_shift >= 1 in event order; weights, E finite float64 values >= 0; penalty
     and step_cost, finite numbers >= 0; reach, an int or E ints in 0 .. 1024 (row 0's is ignored).  u_e = w_e * float64(R_e) (negated
@@ -116,12 +212,16 @@ def track_host(rows, weights, penalty, step_cost, reach, method="sqdiff_normed",
     0, -1, +1, -2, +2, ... with strict replacement (so the smaller |d|, then the negative d, wins a tie); D_e = u_e + where(near_e <=
     jump_e, near_e, jump_e); move_e = the winning d, or -32768 for a jump; s_{E-1} = a_{E-1}, s_{e-1} = a_{e-1} after a jump, else
     s_e + move_e[s_e].  Returns a TrackHost: shifts (int32 index per event), cost (float64: m_{E-1}), row_min (float64) / row_arg
-    (int32) per row, moves (int16 [E, n_shift]; row 0's are 0), row_own_index / row_own_scores (every row's own first extremum)."""
+    (int32) per row, moves (int16 [E, n_shift]; row 0's are 0), row_own_index / row_own_scores (every row's own first extremum).
+    wide=True (include/sushi_hip.h "wide tracking"): a reach may be up to 32767, and one above 1024 needs a step_cost of 0; such a
+    row's near_e is _near_wide's, the same candidates and the same bits in O(n_shift); every other row's is untouched."""
     rows = list(rows)
     w, lam, mu = _checked(weights, len(rows), penalty, step_cost, method)
     rows = axis.checked_score_rows(rows, "track")
     E, n = len(rows), rows[0].shape[0]
-    reach = checked_reach(reach, E)
+    reach = checked_reach(reach, E, wide=wide)
+    if wide:
+        checked_wide_step_cost(reach, mu)
     row_min = np.empty(E, np.float64)
     row_arg = np.empty(E, np.int32)
     moves = np.zeros((E, n), np.int16)
@@ -135,7 +235,7 @@ def track_host(rows, weights, penalty, step_cost, reach, method="sqdiff_normed",
             D = u
         else:
             jump = row_min[e - 1] + lam
-            near, nd = _near(D, reach[e], mu, moves=True)
+            near, nd = _near_of(reach[e])(D, reach[e], mu, moves=True)
             take_near = near <= jump
             D = u + np.where(take_near, near, jump)
             moves[e] = np.where(take_near, nd, np.int16(JUMP))
@@ -294,21 +394,22 @@ def backtrack_ordered_host(moves, prefix_arg, back, row_arg):
     return shifts
 
 
-def track_margins_host(rows, weights, penalty, step_cost, reach, guard, method="sqdiff_normed"):
+def track_margins_host(rows, weights, penalty, step_cost, reach, guard, method="sqdiff_normed", wide=False):
     """sushi_hip_track_forward_keep + sushi_hip_track_backtrack + sushi_hip_track_margins for one sequence in NumPy (include/sushi_hip.h
     "margins" states the arithmetic); the arguments of track_host, and guard, an int or E ints >= 0.  C_{E-1} = u_{E-1}, M_{E-1} =
     D_{E-1}; for e = E-2 .. 0: n_{e+1} = the minimum of C_{e+1}, nearB = track_host's window minimum over C_{e+1} with reach_{e+1},
     B_e = where(nearB <= n_{e+1} + penalty, nearB, n_{e+1} + penalty), M_e = D_e + B_e, C_e = u_e + B_e.  Returns a TrackMarginsHost:
     track_host's fields, then D ([E, n] float64: every row of the forward pass), marginals ([E, n] float64: M), through (M_e[s_e]),
     best / best_arg (the minimum of M_e and its first index), alt / alt_arg (the same over the shifts more than guard_e from s_e;
-    inf and -1 where there are none), c_min (n_e) -- float64 and int32 arrays of E."""
+    inf and -1 where there are none), c_min (n_e) -- float64 and int32 arrays of E.  wide=True: track_host's (a reach up to 32767
+    where step_cost is 0; the backward window minimum of such a row is _near_wide's)."""
     rows = list(rows)
     kept = []
-    fwd = track_host(rows, weights, penalty, step_cost, reach, method, _keep=kept)
+    fwd = track_host(rows, weights, penalty, step_cost, reach, method, _keep=kept, wide=wide)
     w, lam, mu = _checked(weights, len(rows), penalty, step_cost, method)
     rows = axis.checked_score_rows(rows, "track")
     E, n = len(rows), rows[0].shape[0]
-    reach = checked_reach(reach, E)
+    reach = checked_reach(reach, E, wide=wide)
     guard = checked_guard(guard, E)
     D = np.stack(kept)
     M = np.empty((E, n), np.float64)
@@ -323,7 +424,7 @@ def track_margins_host(rows, weights, penalty, step_cost, reach, guard, method="
             C, M[e] = u, D[e]
         else:
             jump = c_min[e + 1] + lam
-            near, _nd = _near(C, reach[e + 1], mu)
+            near, _nd = _near_of(reach[e + 1])(C, reach[e + 1], mu)
             B = np.where(near <= jump, near, jump)
             M[e] = D[e] + B
             C = u + B
@@ -412,6 +513,14 @@ def track_ordered_margins_host(rows, weights, penalties, step_cost, reach, back,
     return TrackOrderedMarginsHost(*(tuple(fwd) + (D, M, through, best, best_arg, alt, alt_arg, c_min)))
 
 
+def wide_workspace_bytes(n_shift):
+    """What a wide call's workspace holds beyond a plain call's: one row's window records -- per shift two float64 values and two
+    32-bit index words, each array padded to 256 bytes (sushi_hip_track_wide_bytes - sushi_hip_track_bytes, up to the padding in
+    front of them)."""
+    pad = lambda b: (b + 255) // 256 * 256
+    return 2 * pad(8 * int(n_shift)) + 2 * pad(4 * int(n_shift))
+
+
 class TrackState(object):
     """The device arrays of one sequence of n_total rows over n_shift shifts: D (float64[2 * n_shift]: two halves, used by turns),
     moves (int16[n_total * n_shift]), row_min (float64[n_total]), row_arg / row_own_index (int32[n_total]), row_own_scores
@@ -424,13 +533,19 @@ class TrackState(object):
     (int32[n_total * n_shift]: row e holds A_e) and back (int32[n_total]: every advanced row's back).
     ordered=True, margins=True: the ordered pass with its rows kept (track_ordered_keep_device fills it) -- D is float64[n_total *
     n_shift] -- and what track_ordered_margins_device needs and fills: keep=True's C and per-row outputs, and S (float64[n_shift]:
-    the suffix minimum of the last row walked)."""
+    the suffix minimum of the last row walked).
+    wide=True (not together with ordered): the same arrays -- the wide pass changes no state, a move word holds +-32767 -- for
+    track_wide_device, track_wide_keep_device and track_wide_margins_device; what a wide call needs beyond a plain one is its
+    workspace, one row's window records (wide_workspace_bytes), which the call takes for its own duration."""
 
-    def __init__(self, n_total, n_shift, device, keep=False, ordered=False, margins=False):
+    def __init__(self, n_total, n_shift, device, keep=False, ordered=False, margins=False, wide=False):
         import torch
         n_total, n_shift = int(n_total), int(n_shift)
         if n_total < 1 or n_shift < 1 or n_shift > 2 ** 31 - 1:
             raise SushiError("track: a sequence has >= 1 rows and 1 .. 2^31 - 1 shifts")
+        if wide and ordered:
+            raise SushiError("track: the ordered pass keeps its reach of %d (no wide form of it is built)" % MAX_REACH)
+        self.wide = bool(wide)
         if keep and ordered:
             raise SushiError("track: the ordered pass keeps no rows (its margins are not built)")
         if margins and not ordered:
@@ -473,11 +588,16 @@ class TrackState(object):
         return self.D[half * self.n_shift:(half + 1) * self.n_shift]
 
     @staticmethod
-    def nbytes(n_total, n_shift, keep=False, marginals=False, ordered=False, margins=False):
+    def nbytes(n_total, n_shift, keep=False, marginals=False, ordered=False, margins=False, wide=False):
         """Bytes of moves and D: what grows with the sequence.  keep: every row of D and the two halves of C; marginals: M too;
         ordered: moves and A, 6 bytes per (event, shift), the two halves of D and P; ordered with margins: moves, A and every row of
-        D, 14 bytes per (event, shift), the two halves of C, P and S, and M with marginals."""
+        D, 14 bytes per (event, shift), the two halves of C, P and S, and M with marginals.  wide (the plain pass alone): a wide
+        call's window records as well (wide_workspace_bytes: 24 bytes per shift)."""
         n_total, n_shift = int(n_total), int(n_shift)
+        if wide:
+            if ordered:
+                raise SushiError("track: the ordered pass keeps its reach of %d (no wide form of it is built)" % MAX_REACH)
+            return TrackState.nbytes(n_total, n_shift, keep=keep, marginals=marginals) + wide_workspace_bytes(n_shift)
         if ordered and margins:
             return n_total * n_shift * 14 + 2 * n_shift * 8 + 2 * n_shift * 8 + (n_total * n_shift * 8 if marginals else 0)
         if ordered:
@@ -505,7 +625,32 @@ def track_forward_keep_device(curves, rows, reach, penalty, step_cost, state, ro
     return _forward_device("sushi_hip_track_forward_keep", curves, rows, reach, penalty, step_cost, state, row0, method, hip_stream)
 
 
-def _forward_device(name, curves, rows, reach, penalty, step_cost, state, row0, method, hip_stream):
+def track_wide_device(curves, rows, reach, penalty, step_cost, state, row0=0, method="sqdiff_normed", hip_stream=None):
+    """track_device through sushi_hip_track_forward_wide: a reach may be up to WIDE_MAX_REACH, and one above MAX_REACH needs a
+    step_cost of 0 (SushiError otherwise).  Rows of a reach up to MAX_REACH go through track_device's own kernels: with no wider
+    reach the outputs are track_device's bit for bit.  `state`: any TrackState that does not keep its rows."""
+    if getattr(state, "keep", False):
+        raise SushiError("track: a state that keeps its rows goes through track_wide_keep_device")
+    return _forward_device("sushi_hip_track_forward_wide", curves, rows, reach, penalty, step_cost, state, row0, method, hip_stream,
+                           wide=True)
+
+
+def track_wide_keep_device(curves, rows, reach, penalty, step_cost, state, row0=0, method="sqdiff_normed", hip_stream=None):
+    """track_forward_keep_device through sushi_hip_track_forward_wide_keep (track_wide_device's reaches)."""
+    if not getattr(state, "keep", False):
+        raise SushiError("track: track_wide_keep_device needs a TrackState(keep=True)")
+    return _forward_device("sushi_hip_track_forward_wide_keep", curves, rows, reach, penalty, step_cost, state, row0, method, hip_stream,
+                           wide=True)
+
+
+def track_wide_margins_device(curves, rows, reach, guard, penalty, step_cost, state, shifts, row0=0, method="sqdiff_normed",
+                              marginals=None, hip_stream=None):
+    """track_margins_device through sushi_hip_track_margins_wide (track_wide_device's reaches)."""
+    return track_margins_device(curves, rows, reach, guard, penalty, step_cost, state, shifts, row0=row0, method=method,
+                                marginals=marginals, hip_stream=hip_stream, _wide=True)
+
+
+def _forward_device(name, curves, rows, reach, penalty, step_cost, state, row0, method, hip_stream, wide=False):
     from .device import _launch
     if getattr(state, "ordered", False):
         raise SushiError("track: a TrackState(ordered=True) goes through track_ordered_device")
@@ -515,11 +660,13 @@ def _forward_device(name, curves, rows, reach, penalty, step_cost, state, row0, 
     row0 = int(row0)
     if row0 < 0 or row0 + rt.shape[0] > state.n_total:
         raise SushiError("track: rows %d .. %d are not inside a sequence of %d" % (row0, row0 + rt.shape[0] - 1, state.n_total))
-    rc = np.ascontiguousarray(checked_reach(reach, rt.shape[0], first_row=row0))
+    rc = np.ascontiguousarray(checked_reach(reach, rt.shape[0], first_row=row0, wide=wide))
+    if wide:
+        checked_wide_step_cost(rc, mu, first_row=row0)
     axis.check_rows_inside(rt, int(curves.numel()), state.n_shift, "track")
     L = _native.lib()
     fn = getattr(L, name)
-    _launch(name, state.D.device, L.sushi_hip_track_bytes(rt.shape[0], state.n_shift),
+    _launch(name, state.D.device, (L.sushi_hip_track_wide_bytes if wide else L.sushi_hip_track_bytes)(rt.shape[0], state.n_shift),
             lambda mem, mem_bytes, st: fn(
                 curves.data_ptr(), int(curves.numel()), rt.ctypes.data, rc.ctypes.data, rt.shape[0], state.n_shift,
                 _native.METHODS[method], lam, mu, row0, state.n_total, state.D.data_ptr(), state.moves.data_ptr(),
@@ -530,7 +677,7 @@ def _forward_device(name, curves, rows, reach, penalty, step_cost, state, row0, 
 
 
 def track_margins_device(curves, rows, reach, guard, penalty, step_cost, state, shifts, row0=0, method="sqdiff_normed", marginals=None,
-                         hip_stream=None):
+                         hip_stream=None, _wide=False):
     """One call of sushi_hip_track_margins: rows row0 + len(rows) - 1 down to row0 of `state`'s sequence (a TrackState(keep=True) whose
     every row has gone through track_forward_keep_device), `shifts` the int32 CUDA tensor track_backtrack_device returned.  rows[i] =
     (curve_off, weight) and guard[i] are row row0 + i's (guard: an int, or one per row of the call); reach: an int, or one int per
@@ -556,7 +703,9 @@ def track_margins_device(curves, rows, reach, guard, penalty, step_cost, state, 
     if len(reach) != n_reach:
         raise SushiError("track: %d reaches for a margins call of %d rows that %s the sequence's last row (%d are needed)"
                          % (len(reach), n_rows, "ends below" if n_reach > n_rows else "ends at", n_reach))
-    rc = np.ascontiguousarray(checked_reach([0] + reach[1:], n_reach, first_row=row0))          # entry 0 is not used
+    rc = np.ascontiguousarray(checked_reach([0] + reach[1:], n_reach, first_row=row0, wide=_wide))          # entry 0 is not used
+    if _wide:
+        checked_wide_step_cost(rc, mu, first_row=row0)
     gd = np.ascontiguousarray(checked_guard(guard, n_rows, first_row=row0))
     axis.check_rows_inside(rt, int(curves.numel()), state.n_shift, "track")
     if not (isinstance(shifts, torch.Tensor) and shifts.is_cuda and shifts.dtype == torch.int32 and shifts.is_contiguous()
@@ -567,8 +716,10 @@ def track_margins_device(curves, rows, reach, guard, penalty, step_cost, state, 
                                       and marginals.device == state.D.device):
         raise SushiError("track: marginals is a contiguous float64 CUDA tensor of %d x %d values" % (state.n_total, state.n_shift))
     L = _native.lib()
-    _launch("sushi_hip_track_margins", state.D.device, L.sushi_hip_track_margins_bytes(n_rows, state.n_shift),
-            lambda mem, mem_bytes, st: L.sushi_hip_track_margins(
+    name = "sushi_hip_track_margins_wide" if _wide else "sushi_hip_track_margins"
+    fn = getattr(L, name)
+    _launch(name, state.D.device, (L.sushi_hip_track_margins_wide_bytes if _wide else L.sushi_hip_track_margins_bytes)(n_rows, state.n_shift),
+            lambda mem, mem_bytes, st: fn(
                 curves.data_ptr(), int(curves.numel()), rt.ctypes.data, rc.ctypes.data, gd.ctypes.data, n_rows, state.n_shift,
                 _native.METHODS[method], lam, mu, row0, state.n_total, state.D.data_ptr(), shifts.data_ptr(), state.C.data_ptr(),
                 state.c_min.data_ptr(), state.through.data_ptr(), state.best.data_ptr(), state.best_arg.data_ptr(),
@@ -770,8 +921,9 @@ class Track(Record):
 
 def find_track(stream, patterns, window_centers, window_size, penalty, max_rate=None, reach=None, step_cost=0.0, slack=1,
                weights="equal", method="sqdiff_normed", max_bytes=MAX_BYTES, max_state_bytes=MAX_STATE_BYTES, margins=False,
-               guard=None, marginals=False, clamp=None, capacity=None, order=None):
+               guard=None, marginals=False, clamp=None, capacity=None, order=None, wide=False):
     """WavStream.find_track (its docstring)."""
+    wide = bool(wide)
     import torch
     from .curves import match_curves
     patterns, centres = list(patterns), list(window_centers)
@@ -786,6 +938,9 @@ def find_track(stream, patterns, window_centers, window_size, penalty, max_rate=
     order = None if order is False else order
     ordered = order is not None or (penalty is not None and np.ndim(penalty) != 0)
     if ordered:
+        if wide:
+            raise SushiError("find_track: wide=True belongs to the plain pass; the ordered pass (order=, a penalty per event) keeps "
+                             "its reach of %d" % MAX_REACH)
         if margins:
             raise SushiError("find_track: margins of the ordered pass (order=, a penalty per event) are not built: its backward "
                              "recurrence needs the mirrored suffix minimum")
@@ -799,23 +954,29 @@ def find_track(stream, patterns, window_centers, window_size, penalty, max_rate=
     w, lam, mu = _checked(axis.event_weights(weights, lens, per_event=True), E, penalty, step_cost, method)
     ax = axis.event_axis(stream, offs, lens, centres, window_size)
     k_lo, n_shift, rate = ax.k_lo, ax.n_shift, stream.sample_rate
-    reach = checked_reach(rate_reach(ax.bases, max_rate, slack) if reach is None else reach, E)
+    reach = checked_reach(rate_reach(ax.bases, max_rate, slack) if reach is None else reach, E, wide=wide)
+    if wide:
+        checked_wide_step_cost(reach, mu)
     if margins:
         guard = checked_guard(int(0.01 * rate) if guard is None else guard, E)
-    need = TrackState.nbytes(E, n_shift, keep=margins, marginals=marginals)
+    need = TrackState.nbytes(E, n_shift, keep=margins, marginals=marginals, wide=wide)
     if need > max_state_bytes:
+        records = ", a wide call's window records" if wide else ""
         if margins:
-            raise SushiError("find_track: %d events x %d shifts need %d bytes of moves, kept costs%s, max_state_bytes is %d (%d "
-                             "without margins)" % (E, n_shift, need, " and marginals" if marginals else "", max_state_bytes,
-                                                   TrackState.nbytes(E, n_shift)))
-        raise SushiError("find_track: %d events x %d shifts need %d bytes of moves and costs, max_state_bytes is %d"
-                         % (E, n_shift, need, max_state_bytes))
+            raise SushiError("find_track: %d events x %d shifts need %d bytes of moves, kept costs%s%s, max_state_bytes is %d (%d "
+                             "without margins)" % (E, n_shift, need, " and marginals" if marginals else "", records, max_state_bytes,
+                                                   TrackState.nbytes(E, n_shift, wide=wide)))
+        raise SushiError("find_track: %d events x %d shifts need %d bytes of moves and costs%s, max_state_bytes is %d"
+                         % (E, n_shift, need, records, max_state_bytes))
     per_chunk = int(max_bytes) // (4 * n_shift)
     if per_chunk < 1:
         raise SushiError("find_track: one event of %d shifts needs %d bytes of curves, max_bytes is %d"
                          % (n_shift, 4 * n_shift, max_bytes))
-    state = TrackState(E, n_shift, dst_dev.device, keep=margins)
-    forward = track_forward_keep_device if margins else track_device
+    state = TrackState(E, n_shift, dst_dev.device, keep=margins, wide=wide)
+    if wide:
+        forward, margins_device = (track_wide_keep_device if margins else track_wide_device), track_wide_margins_device
+    else:
+        forward, margins_device = (track_forward_keep_device if margins else track_device), track_margins_device
     chunks = [(first, min(E, first + per_chunk)) for first in range(0, E, per_chunk)]
     rows_info = [None]
 
@@ -837,8 +998,8 @@ def find_track(stream, patterns, window_centers, window_size, penalty, max_rate=
         for first, last in reversed(chunks):
             if len(chunks) > 1:
                 curves, row_off = form(first, last)
-            track_margins_device(curves, zip(row_off, w[first:last].tolist()), reach[first:last + 1 if last < E else last],
-                                 guard[first:last], lam, mu, state, index_dev, row0=first, method=method, marginals=M)
+            margins_device(curves, zip(row_off, w[first:last].tolist()), reach[first:last + 1 if last < E else last],
+                           guard[first:last], lam, mu, state, index_dev, row0=first, method=method, marginals=M)
         through, alt, alt_arg = state.through.cpu().numpy(), state.alt.cpu().numpy(), state.alt_arg.cpu().numpy()
         alt_shift = [None if int(k) == NO_ALT else k_lo + int(k) for k in alt_arg]
         extra = dict(guard=guard.tolist(), event_through=through,
@@ -864,8 +1025,11 @@ def find_track(stream, patterns, window_centers, window_size, penalty, max_rate=
 
 def find_ordered_track(stream, patterns, window_centers, window_size, penalty, order=None, max_rate=None, reach=None, step_cost=0.0,
                        slack=1, weights="equal", method="sqdiff_normed", max_bytes=MAX_BYTES, max_state_bytes=MAX_STATE_BYTES,
-                       margins=False, guard=None, marginals=False, clamp=None, capacity=None):
+                       margins=False, guard=None, marginals=False, clamp=None, capacity=None, wide=False):
     """WavStream.find_ordered_track (its docstring)."""
+    if wide:
+        raise SushiError("find_ordered_track: wide=True belongs to find_track's plain pass; the ordered pass keeps its reach of %d"
+                         % MAX_REACH)
     patterns, centres = list(patterns), list(window_centers)
     if not patterns or len(patterns) != len(centres):
         raise SushiError("find_ordered_track: equally many patterns and centres (>= 1)")

@@ -633,7 +633,7 @@ class WavStream(object):
     # ------------------------------------------------------------------ a shift that wanders, and may jump
     def find_track(self, patterns, window_centers, window_size, penalty, max_rate=None, reach=None, step_cost=0.0, slack=1,
                    weights='equal', method="sqdiff_normed", max_bytes=None, max_state_bytes=None, margins=False, guard=None,
-                   marginals=False, clamp=None, capacity=None, order=None):
+                   marginals=False, clamp=None, capacity=None, order=None, wide=False):
         """A shift for every event of a sequence that may move a little from event to event and jump at a cut
         (sushi_amd.track): the events (patterns, window_centers: in order) are put on one shift axis as
         find_segments puts them, and a shift is chosen per event that minimises the sum of the events' weighted scores plus, between
@@ -673,17 +673,26 @@ class WavStream(object):
         penalty the code path, the launches and the bits are those of before.  Measured on one MI355X (profiles/track_order/): the
         ordered forward pass takes 12.3 x the plain one at reach 0 and 2.8 x at reach 88 (64 rows x 2.88 M shifts: 14.1 ms
         against 1.1 ms, 20.2 ms against 7.2 ms -- its prefix-minimum kernel, not tuned); a whole call on 64 uint8 events at +-120 s
-        1.27 x (59.9 ms against 47.1 ms), with clamp=0.5 3.7 x (17.7 ms against 4.8 ms).  Needs a GPU."""
+        1.27 x (59.9 ms against 47.1 ms), with clamp=0.5 3.7 x (17.7 ms against 4.8 ms).
+        wide=True lifts the reach's bound to 32767 samples wherever step_cost is 0 (the default): one long stretch
+        without an event -- at max_rate 1e-3 a gap of more than 85 s -- no longer ends the call, and the pass walks it instead of
+        paying a jump.  The model, the tie rules and the bits are the same (a wide row's window minimum is formed from prefix and
+        suffix minima of 1024-value tiles, in a time that does not grow with the reach); margins=, marginals=, clamp= and chunks work
+        as before; a wide call's window records, 24 bytes per shift, count under max_state_bytes.  A reach above 1024 with step_cost
+        > 0 is a SushiError (such a move costs more than a jump once step_cost x reach > penalty: clip the reach), and so is wide=True
+        with order= or a penalty per event: the ordered pass keeps its 1024.  With wide=False (the default) nothing changes.  Needs a
+        GPU."""
         from . import track
         return track.find_track(self, patterns, window_centers, window_size, penalty, max_rate=max_rate, reach=reach,
                                 step_cost=step_cost, slack=slack, weights=weights, method=method,
                                 max_bytes=track.MAX_BYTES if max_bytes is None else int(max_bytes),
                                 max_state_bytes=track.MAX_STATE_BYTES if max_state_bytes is None else int(max_state_bytes),
-                                margins=margins, guard=guard, marginals=marginals, clamp=clamp, capacity=capacity, order=order)
+                                margins=margins, guard=guard, marginals=marginals, clamp=clamp, capacity=capacity, order=order,
+                                wide=wide)
 
     def find_ordered_track(self, patterns, window_centers, window_size, penalty, order=None, max_rate=None, reach=None, step_cost=0.0,
                            slack=1, weights='equal', method="sqdiff_normed", max_bytes=None, max_state_bytes=None, margins=False,
-                           guard=None, marginals=False, clamp=None, capacity=None):
+                           guard=None, marginals=False, clamp=None, capacity=None, wide=False):
         """find_track through the ordered pass, and how firmly it places every event.  order and
         penalty (a number, or one per event) are find_track's; with margins=False this is find_track(order=order) -- the same
         launches, the same bits, the same Track (and with order=None and one penalty the ordered pass without a limit, whose bits
@@ -695,13 +704,14 @@ class WavStream(object):
         is as firm as its whole run.  guard: an int or one per event, in samples (default int(0.01 * sample_rate)).  The state is E
         x n_shift x 14 + 4 x n_shift x 8 bytes (and E x n_shift x 8 for marginals) under max_state_bytes; SushiError names the
         need.  One chunk of max_bytes keeps its curves; several chunks form every chunk's rows a second time (clamp= / capacity=
-        work as in find_track).  Needs a GPU."""
+        work as in find_track).  wide=True is a SushiError: the ordered pass keeps its reach of 1024 (find_track's wide form is the
+        plain pass's).  Needs a GPU."""
         from . import track
         return track.find_ordered_track(self, patterns, window_centers, window_size, penalty, order=order, max_rate=max_rate, reach=reach,
                                         step_cost=step_cost, slack=slack, weights=weights, method=method,
                                         max_bytes=track.MAX_BYTES if max_bytes is None else int(max_bytes),
                                         max_state_bytes=track.MAX_STATE_BYTES if max_state_bytes is None else int(max_state_bytes),
-                                        margins=margins, guard=guard, marginals=marginals, clamp=clamp, capacity=capacity)
+                                        margins=margins, guard=guard, marginals=marginals, clamp=clamp, capacity=capacity, wide=wide)
 
     # ------------------------------------------------------------------ a shift that moves along the programme
     def find_drift(self, patterns, window_centers, window_size, max_rate, resolution=1.0, weights='equal', method="sqdiff_normed",
