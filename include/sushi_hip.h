@@ -60,7 +60,10 @@ extern "C" {
                                      sushi_hip_track_order_margins;
                                      13 (additive): SUSHI_HIP_TRACK_WIDE_MAX_REACH, sushi_hip_track_wide_bytes,
                                      sushi_hip_track_margins_wide_bytes, sushi_hip_track_forward_wide,
-                                     sushi_hip_track_forward_wide_keep, sushi_hip_track_margins_wide */
+                                     sushi_hip_track_forward_wide_keep, sushi_hip_track_margins_wide;
+                                     13 (additive): sushi_hip_track_order_wide_bytes, sushi_hip_track_order_margins_wide_bytes,
+                                     sushi_hip_track_forward_ordered_wide, sushi_hip_track_forward_ordered_wide_keep,
+                                     sushi_hip_track_order_margins_wide */
 
 #if defined(__GNUC__)
 #define SUSHI_HIP_API __attribute__((visibility("default")))
@@ -872,6 +875,53 @@ SUSHI_HIP_API int sushi_hip_track_margins_wide(const float* curves_dev, int64_t 
                                                double* through_dev, double* best_dev, int32_t* best_arg_dev,
                                                double* alt_dev, int32_t* alt_arg_dev, double* M_dev,
                                                void* mem_dev, size_t mem_bytes, void* hip_stream);
+
+/* ---- wide ordered tracking: the ordered pass and its margins with a reach up to 32767 where moves are free (13,
+ * additive) ---------------------------------------------------------------------------------------------------------------------
+ * "ordered tracking" and "ordered margins" word for word, with "wide tracking"'s one bound raised: a row's reach may be 0 ..
+ * SUSHI_HIP_TRACK_WIDE_MAX_REACH, and every used reach above SUSHI_HIP_TRACK_MAX_REACH requires a step_cost of +0.0 or -0.0.  The
+ * recurrences, the tie rules, the move words, P / A / S, chunks and every output are unchanged; near[j] of a row of a reach above
+ * SUSHI_HIP_TRACK_MAX_REACH is "wide tracking"'s, bit for bit the candidate-by-candidate definition's, and its jump term is the
+ * ordered pass's own: P_{e-1}[t_e(j)] + penalty_e forwards, S_{e+1}[t'_e(j)] + penalty_{e+1} backwards.  A row whose reach is at
+ * most SUSHI_HIP_TRACK_MAX_REACH goes through the ordered calls' own kernels: with no reach above it each call gives the ordered
+ * call's outputs bit for bit; with every back without a limit and one penalty each gives the wide call's.
+ * sushi_hip_track_backtrack_ordered is used as it is.  The state is the ordered calls': a sequence may mix them. */
+/* workspace: the ordered call's, then one row's window records (24 bytes per shift); 0 wherever sushi_hip_track_order_bytes /
+ * sushi_hip_track_order_margins_bytes is 0 */
+SUSHI_HIP_API size_t sushi_hip_track_order_wide_bytes(int n_rows, int32_t n_shift);
+SUSHI_HIP_API size_t sushi_hip_track_order_margins_wide_bytes(int n_rows, int32_t n_shift);
+/* sushi_hip_track_forward_ordered / _ordered_keep: the arguments, the outputs and the refusals in their order, but -- EINVAL: a reach
+ * outside 0 .. SUSHI_HIP_TRACK_WIDE_MAX_REACH in any row but the sequence's row 0, or such a reach above SUSHI_HIP_TRACK_MAX_REACH
+ * beside a step_cost that is not +-0.0 (both where the ordered call checks a row's reach); ENOSPACE: mem_bytes <
+ * sushi_hip_track_order_wide_bytes.  A wide row takes four launches (tile pass, step, scan, apply), stream-ordered; no grid waits
+ * on itself and there are no atomics. */
+SUSHI_HIP_API int sushi_hip_track_forward_ordered_wide(const float* curves_dev, int64_t n_curve,
+                                                       const SushiHipJointRow* rows_host, const int32_t* reach_host,
+                                                       const int32_t* back_host, int n_rows, int32_t n_shift, int method,
+                                                       const double* penalty_host, double step_cost, int row0, int n_total,
+                                                       double* D_dev, int16_t* move_dev, double* P_dev, int32_t* from_dev,
+                                                       int32_t* back_dev, double* row_min_dev, int32_t* row_arg_dev,
+                                                       int32_t* row_own_index_dev, float* row_own_score_dev,
+                                                       void* mem_dev, size_t mem_bytes, void* hip_stream);
+SUSHI_HIP_API int sushi_hip_track_forward_ordered_wide_keep(const float* curves_dev, int64_t n_curve,
+                                                            const SushiHipJointRow* rows_host, const int32_t* reach_host,
+                                                            const int32_t* back_host, int n_rows, int32_t n_shift, int method,
+                                                            const double* penalty_host, double step_cost, int row0, int n_total,
+                                                            double* D_all_dev, int16_t* move_dev, double* P_dev, int32_t* from_dev,
+                                                            int32_t* back_dev, double* row_min_dev, int32_t* row_arg_dev,
+                                                            int32_t* row_own_index_dev, float* row_own_score_dev,
+                                                            void* mem_dev, size_t mem_bytes, void* hip_stream);
+/* sushi_hip_track_order_margins in the same way: a used reach outside 0 .. SUSHI_HIP_TRACK_WIDE_MAX_REACH, or one above
+ * SUSHI_HIP_TRACK_MAX_REACH beside a step_cost that is not +-0.0, is EINVAL; ENOSPACE: mem_bytes <
+ * sushi_hip_track_order_margins_wide_bytes. */
+SUSHI_HIP_API int sushi_hip_track_order_margins_wide(const float* curves_dev, int64_t n_curve,
+                                                     const SushiHipJointRow* rows_host, const int32_t* reach_host,
+                                                     const int32_t* back_host, const int32_t* guard_host, int n_rows, int32_t n_shift,
+                                                     int method, const double* penalty_host, double step_cost, int row0, int n_total,
+                                                     const double* D_all_dev, const int32_t* shift_dev, double* C_dev, double* S_dev,
+                                                     double* c_min_dev, double* through_dev, double* best_dev, int32_t* best_arg_dev,
+                                                     double* alt_dev, int32_t* alt_arg_dev, double* M_dev,
+                                                     void* mem_dev, size_t mem_bytes, void* hip_stream);
 
 /* ---- rows: score rows clamped at a threshold, formed from a threshold run's hits (13, additive) ---------------
  * A pass over a shift axis needs to know where a row is good and how good; how bad the rest is only feeds decoys.  The CLAMPED row

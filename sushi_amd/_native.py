@@ -229,6 +229,16 @@ def lib():
     L.sushi_hip_track_order_margins.restype = ci
     L.sushi_hip_track_order_margins.argtypes = [vp, i64, vp, vp, vp, vp, ci, i32, ci, vp, dbl, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                                 vp, vp, vp, sz, vp]
+    L.sushi_hip_track_order_wide_bytes.restype = sz
+    L.sushi_hip_track_order_wide_bytes.argtypes = [ci, i32]
+    L.sushi_hip_track_order_margins_wide_bytes.restype = sz
+    L.sushi_hip_track_order_margins_wide_bytes.argtypes = [ci, i32]
+    L.sushi_hip_track_forward_ordered_wide.restype = ci
+    L.sushi_hip_track_forward_ordered_wide.argtypes = L.sushi_hip_track_forward_ordered.argtypes
+    L.sushi_hip_track_forward_ordered_wide_keep.restype = ci
+    L.sushi_hip_track_forward_ordered_wide_keep.argtypes = L.sushi_hip_track_forward_ordered.argtypes
+    L.sushi_hip_track_order_margins_wide.restype = ci
+    L.sushi_hip_track_order_margins_wide.argtypes = L.sushi_hip_track_order_margins.argtypes
     L.sushi_hip_rows_tile.restype = ci
     L.sushi_hip_rows_bytes.restype = sz
     L.sushi_hip_rows_bytes.argtypes = [ci]

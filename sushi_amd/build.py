@@ -63,6 +63,10 @@ UNITS = [
     # minima and a step that combines a few of its records; narrower rows go through sushi_track's and sushi_track_margins' own
     # step kernels (the two .inc parts) (track_wide_core.hpp: the decomposition, the records, the call's host side)
     ("sushi_track_wide", ["-ffp-contract=off"]),        # track_core.hpp's candidates unchanged: the price is added once, to the winner
+    # the ordered pass and its margins with the same wide reach: a wide row's tile pass (sushi_track_wide_tile.inc), a step with
+    # wide_near and the jump read per index from P / S, then the ordered pass's own scan and apply; narrower rows go through
+    # sushi_track_order's and sushi_track_order_margins' own kernels (their .inc parts) (track_order_wide_core.hpp: the call's host side)
+    ("sushi_track_order_wide", ["-ffp-contract=off"]),  # the candidates and the jump's sum unchanged: each rounds once
     # score rows clamped at a threshold: a fill and a scatter of a threshold run's hits, and the rule applied to rows that exist
     # (rows_core.hpp: the rule, the tiles, the search of a hit list, and the call's host side)
     ("sushi_rows", []),                         # comparisons and copies: no arithmetic to contract

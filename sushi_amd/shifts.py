@@ -477,17 +477,32 @@ def calculate_ordered_shifts(src_stream, dst_stream, events, window, penalty, or
     in order in the destination (order: True, the default here; None; or one back per event), `penalty` may be one number per event,
     and with margins=True the Track says how firmly the ordered pass places every event (guard, marginals: find_ordered_track's).
     Every event gets set_shift(centre_shift + its delta, its own score there).  Returns the Track."""
+    return _ordered_shifts("calculate_ordered_shifts", dst_stream.find_ordered_track, src_stream, events, window, penalty, order, max_rate,
+                           reach, step_cost, centre_shift, margins, guard, marginals, clamp, capacity)
+
+
+def calculate_ordered_wide_shifts(src_stream, dst_stream, events, window, penalty, order=True, max_rate=None, reach=None, step_cost=0.0,
+                                  centre_shift=0.0, margins=False, guard=None, marginals=False, clamp=None, capacity=None):
+    """calculate_ordered_shifts through dst_stream.find_ordered_wide_track (its docstring): a reach may be up to 32767
+    samples where step_cost is 0, so one long stretch without an event does not end the call.  Everything else is
+    calculate_ordered_shifts'.  Returns the Track."""
+    return _ordered_shifts("calculate_ordered_wide_shifts", dst_stream.find_ordered_wide_track, src_stream, events, window, penalty, order,
+                           max_rate, reach, step_cost, centre_shift, margins, guard, marginals, clamp, capacity)
+
+
+def _ordered_shifts(name, find, src_stream, events, window, penalty, order, max_rate, reach, step_cost, centre_shift, margins, guard,
+                    marginals, clamp, capacity):
     events = list(events)
     shift = float(centre_shift)
     if not events:
-        raise SushiError("calculate_ordered_shifts: no events")
+        raise SushiError("%s: no events" % name)
     patterns = [src_stream.get_substream(e.start, e.end) for e in events]
     for e, p in zip(events, patterns):
         if p.shape[1] < 1:
-            raise SushiError("calculate_ordered_shifts: event %s has no samples in the source" % e)
-    found = dst_stream.find_ordered_track(patterns, [e.start + shift for e in events], window, penalty, order=order, max_rate=max_rate,
-                                          reach=reach, step_cost=step_cost, margins=margins, guard=guard, marginals=marginals,
-                                          **({} if clamp is None and capacity is None else dict(clamp=clamp, capacity=capacity)))
+            raise SushiError("%s: event %s has no samples in the source" % (name, e))
+    found = find(patterns, [e.start + shift for e in events], window, penalty, order=order, max_rate=max_rate, reach=reach,
+                 step_cost=step_cost, margins=margins, guard=guard, marginals=marginals,
+                 **({} if clamp is None and capacity is None else dict(clamp=clamp, capacity=capacity)))
     for e, delta, score in zip(events, found.deltas, found.event_scores):
         e.set_shift(shift + delta, score)
     return found

@@ -24,6 +24,10 @@ minimum over all assignments (include/sushi_hip.h "tracking").  
 * ``track_ordered_margins_host`` / ``TrackState(ordered=True, margins=True)`` / ``track_ordered_keep_device`` /
   ``track_ordered_margins_device`` -- the same for the ordered pass (include/sushi_hip.h "ordered margins"; DESIGN.md 3.22);
   ``find_ordered_track(margins=True)`` runs them.
+* ``wide=True`` on ``track_ordered_host`` and ``track_ordered_margins_host``, and ``track_ordered_wide_device`` /
+  ``track_ordered_wide_keep_device`` / ``track_ordered_wide_margins_device`` -- the two together (include/sushi_hip.h "wide ordered
+  tracking"; DESIGN.md 3.24): the ordered pass and its margins with a reach up to 32767 where moves are free;
+  ``find_ordered_wide_track`` runs them.
 """
 import math
 from collections import namedtuple
@@ -330,7 +334,7 @@ def _reach_back(n, back):
     return np.full(n, n - 1, np.int64) if back < 0 else np.minimum(j + int(back), n - 1)
 
 
-def track_ordered_host(rows, weights, penalties, step_cost, reach, back, method="sqdiff_normed", _keep=None):
+def track_ordered_host(rows, weights, penalties, step_cost, reach, back, method="sqdiff_normed", _keep=None, wide=False):
     """sushi_hip_track_forward_ordered + sushi_hip_track_backtrack_ordered for one sequence in NumPy (include/sushi_hip.h "ordered
     tracking" states the arithmetic): track_host's arguments, but penalties, a number or E finite numbers >= 0 (row 0's is ignored),
     and back, an int >= 0, -1 or None (no limit), or E of them (row 0's is not used).  u_e, D_0, m_e, a_e, near_e and the moves are
@@ -338,13 +342,16 @@ def track_ordered_host(rows, weights, penalties, step_cost, reach, back, method=
     without a limit); jump_e[j] = P_{e-1}[t_e(j)] + penalty_e; D_e = u_e + where(near_e <= jump_e, near_e, jump_e); s_{E-1} = a_{E-1},
     s_{e-1} = A_{e-1}[t_e(s_e)] after a jump, else s_e + move_e[s_e].  With every back without a limit (or >= n_shift - 1) and one
     penalty this is track_host bit for bit.  Returns a TrackOrderedHost: TrackHost's fields, then prefix_arg (int32 [E, n_shift]:
-    row e is A_e)."""
+    row e is A_e).  wide=True (include/sushi_hip.h "wide ordered tracking"): track_host's -- a reach may be up to 32767, and one above
+    1024 needs a step_cost of 0; such a row's near_e is _near_wide's, the same bits; the jump term and every other row are untouched."""
     rows = list(rows)
     E = len(rows)
     w, _lam, mu = _checked(weights, E, 0.0, step_cost, method)
     rows = axis.checked_score_rows(rows, "track")
     n = rows[0].shape[0]
-    reach = checked_reach(reach, E)
+    reach = checked_reach(reach, E, wide=wide)
+    if wide:
+        checked_wide_step_cost(reach, mu)
     lam = checked_penalties(penalties, E)
     back = checked_back(back, E)
     row_min = np.empty(E, np.float64)
@@ -361,7 +368,7 @@ def track_ordered_host(rows, weights, penalties, step_cost, reach, back, method=
             D = u
         else:
             jump = P[_reach_back(n, back[e])] + lam[e]
-            near, nd = _near(D, reach[e], mu, moves=True)
+            near, nd = (_near_of(reach[e]) if wide else _near)(D, reach[e], mu, moves=True)
             take_near = near <= jump
             D = u + np.where(take_near, near, jump)
             moves[e] = np.where(take_near, nd, np.int16(JUMP))
@@ -459,7 +466,8 @@ def _reach_from(n, back):
     return np.zeros(n, np.int64) if back < 0 else np.maximum(j - int(back), 0)
 
 
-def track_ordered_margins_host(rows, weights, penalties, step_cost, reach, back, guard, method="sqdiff_normed", _trace=None):
+def track_ordered_margins_host(rows, weights, penalties, step_cost, reach, back, guard, method="sqdiff_normed", _trace=None,
+                               wide=False):
     """sushi_hip_track_forward_ordered_keep + sushi_hip_track_backtrack_ordered + sushi_hip_track_order_margins for one sequence in
     NumPy (include/sushi_hip.h "ordered margins" states the arithmetic); the arguments of track_ordered_host, and guard, an int or E
     ints >= 0.  C_{E-1} = u_{E-1}, M_{E-1} = D_{E-1}; S_e = _suffix(C_e); for e = E-2 .. 0: jumpB[j] = S_{e+1}[max(j - back_{e+1}, 0)] +
@@ -467,15 +475,16 @@ def track_ordered_margins_host(rows, weights, penalties, step_cost, reach, back,
     jumpB, nearB, jumpB), M_e = D_e + B_e, C_e = u_e + B_e.  With every back without a limit (or >= n_shift - 1) and one penalty this
     is track_margins_host bit for bit.  Returns a TrackOrderedMarginsHost: track_ordered_host's fields, then D ([E, n] float64: every
     row of the ordered forward pass), marginals ([E, n] float64: M), through (M_e[s_e]), best / best_arg, alt / alt_arg (inf and -1
-    where no shift lies outside the guard window), c_min (S_e[0]) -- as track_margins_host's."""
+    where no shift lies outside the guard window), c_min (S_e[0]) -- as track_margins_host's.  wide=True: track_ordered_host's (a
+    reach up to 32767 where step_cost is 0; the backward window minimum of such a row is _near_wide's)."""
     rows = list(rows)
     kept = []
-    fwd = track_ordered_host(rows, weights, penalties, step_cost, reach, back, method, _keep=kept)
+    fwd = track_ordered_host(rows, weights, penalties, step_cost, reach, back, method, _keep=kept, wide=wide)
     E = len(rows)
     w, _lam, mu = _checked(weights, E, 0.0, step_cost, method)
     rows = axis.checked_score_rows(rows, "track")
     n = rows[0].shape[0]
-    reach = checked_reach(reach, E)
+    reach = checked_reach(reach, E, wide=wide)
     lam = checked_penalties(penalties, E)
     back = checked_back(back, E)
     guard = checked_guard(guard, E)
@@ -492,7 +501,7 @@ def track_ordered_margins_host(rows, weights, penalties, step_cost, reach, back,
             C, M[e] = u, D[e]
         else:
             jump = S[_reach_from(n, back[e + 1])] + lam[e + 1]
-            near, _nd = _near(C, reach[e + 1], mu)
+            near, _nd = (_near_of(reach[e + 1]) if wide else _near)(C, reach[e + 1], mu)
             B = np.where(near <= jump, near, jump)
             M[e] = D[e] + B
             C = u + B
@@ -519,6 +528,12 @@ def wide_workspace_bytes(n_shift):
     front of them)."""
     pad = lambda b: (b + 255) // 256 * 256
     return 2 * pad(8 * int(n_shift)) + 2 * pad(4 * int(n_shift))
+
+
+def ordered_wide_state_bytes(n_total, n_shift, margins=False, marginals=False):
+    """What find_ordered_wide_track's max_state_bytes counts: the ordered pass's state (TrackState.nbytes(ordered=True, ...)) and a
+    wide call's window records (wide_workspace_bytes: 24 bytes per shift)."""
+    return TrackState.nbytes(n_total, n_shift, ordered=True, margins=margins, marginals=marginals) + wide_workspace_bytes(n_shift)
 
 
 class TrackState(object):
@@ -752,7 +767,36 @@ def track_ordered_keep_device(curves, rows, reach, penalties, step_cost, back, s
                                    method, hip_stream)
 
 
-def _forward_ordered_device(name, curves, rows, reach, penalties, step_cost, back, state, row0, method, hip_stream):
+def track_ordered_wide_device(curves, rows, reach, penalties, step_cost, back, state, row0=0, method="sqdiff_normed", hip_stream=None):
+    """track_ordered_device through sushi_hip_track_forward_ordered_wide: a reach may be up to WIDE_MAX_REACH, and one above MAX_REACH
+    needs a step_cost of 0 (SushiError otherwise).  Rows of a reach up to MAX_REACH go through track_ordered_device's own kernels:
+    with no wider reach the outputs are track_ordered_device's bit for bit.  `state`: an ordinary TrackState(ordered=True) -- a wide
+    call changes no state, and a sequence may mix the two calls; what it needs beyond it is its workspace."""
+    if not getattr(state, "ordered", False):
+        raise SushiError("track: track_ordered_wide_device needs a TrackState(ordered=True)")
+    if getattr(state, "margins", False):
+        raise SushiError("track: a state that keeps its rows goes through track_ordered_wide_keep_device")
+    return _forward_ordered_device("sushi_hip_track_forward_ordered_wide", curves, rows, reach, penalties, step_cost, back, state, row0,
+                                   method, hip_stream, wide=True)
+
+
+def track_ordered_wide_keep_device(curves, rows, reach, penalties, step_cost, back, state, row0=0, method="sqdiff_normed",
+                                   hip_stream=None):
+    """track_ordered_keep_device through sushi_hip_track_forward_ordered_wide_keep (track_ordered_wide_device's reaches)."""
+    if not (getattr(state, "ordered", False) and getattr(state, "margins", False)):
+        raise SushiError("track: track_ordered_wide_keep_device needs a TrackState(ordered=True, margins=True)")
+    return _forward_ordered_device("sushi_hip_track_forward_ordered_wide_keep", curves, rows, reach, penalties, step_cost, back, state,
+                                   row0, method, hip_stream, wide=True)
+
+
+def track_ordered_wide_margins_device(curves, rows, reach, guard, penalties, step_cost, back, state, shifts, row0=0,
+                                      method="sqdiff_normed", marginals=None, hip_stream=None):
+    """track_ordered_margins_device through sushi_hip_track_order_margins_wide (track_ordered_wide_device's reaches)."""
+    return track_ordered_margins_device(curves, rows, reach, guard, penalties, step_cost, back, state, shifts, row0=row0, method=method,
+                                        marginals=marginals, hip_stream=hip_stream, _wide=True)
+
+
+def _forward_ordered_device(name, curves, rows, reach, penalties, step_cost, back, state, row0, method, hip_stream, wide=False):
     from .device import _launch
     axis.check_curves(curves, "track", device=state.D.device)
     rt = axis.row_table(rows)
@@ -761,13 +805,15 @@ def _forward_ordered_device(name, curves, rows, reach, penalties, step_cost, bac
     row0 = int(row0)
     if row0 < 0 or row0 + n_rows > state.n_total:
         raise SushiError("track: rows %d .. %d are not inside a sequence of %d" % (row0, row0 + n_rows - 1, state.n_total))
-    rc = np.ascontiguousarray(checked_reach(reach, n_rows, first_row=row0))
+    rc = np.ascontiguousarray(checked_reach(reach, n_rows, first_row=row0, wide=wide))
+    if wide:
+        checked_wide_step_cost(rc, mu, first_row=row0)
     pc = np.ascontiguousarray(checked_penalties(penalties, n_rows, first_row=row0))
     bc = np.ascontiguousarray(checked_back(back, n_rows, first_row=row0))
     axis.check_rows_inside(rt, int(curves.numel()), state.n_shift, "track")
     L = _native.lib()
     fn = getattr(L, name)
-    _launch(name, state.D.device, L.sushi_hip_track_order_bytes(n_rows, state.n_shift),
+    _launch(name, state.D.device, (L.sushi_hip_track_order_wide_bytes if wide else L.sushi_hip_track_order_bytes)(n_rows, state.n_shift),
             lambda mem, mem_bytes, st: fn(
                 curves.data_ptr(), int(curves.numel()), rt.ctypes.data, rc.ctypes.data, bc.ctypes.data, n_rows, state.n_shift,
                 _native.METHODS[method], pc.ctypes.data, mu, row0, state.n_total, state.D.data_ptr(), state.moves.data_ptr(),
@@ -778,7 +824,7 @@ def _forward_ordered_device(name, curves, rows, reach, penalties, step_cost, bac
 
 
 def track_ordered_margins_device(curves, rows, reach, guard, penalties, step_cost, back, state, shifts, row0=0, method="sqdiff_normed",
-                                 marginals=None, hip_stream=None):
+                                 marginals=None, hip_stream=None, _wide=False):
     """One call of sushi_hip_track_order_margins: rows row0 + len(rows) - 1 down to row0 of `state`'s sequence (a TrackState(ordered=True,
     margins=True) whose every row has gone through track_ordered_keep_device), `shifts` the int32 CUDA tensor
     track_ordered_backtrack_device returned.  track_margins_device's arguments, but reach, penalties and back are each a single value,
@@ -806,7 +852,9 @@ def track_ordered_margins_device(curves, rows, reach, guard, penalties, step_cos
                              % (len(values), what, n_rows, "ends below" if n_after > n_rows else "ends at", n_after))
         return [fill] + values[1:]                                                              # entry 0 is not used
 
-    rc = np.ascontiguousarray(checked_reach(per_row(reach, "reaches", 0), n_after, first_row=row0))
+    rc = np.ascontiguousarray(checked_reach(per_row(reach, "reaches", 0), n_after, first_row=row0, wide=_wide))
+    if _wide:
+        checked_wide_step_cost(rc, mu, first_row=row0)
     pc = np.ascontiguousarray(checked_penalties(per_row(penalties, "penalties", 0.0), n_after, first_row=row0))
     bc = np.ascontiguousarray(checked_back(per_row(back, "backs", BACK_ANY), n_after, first_row=row0))
     gd = np.ascontiguousarray(checked_guard(guard, n_rows, first_row=row0))
@@ -819,8 +867,11 @@ def track_ordered_margins_device(curves, rows, reach, guard, penalties, step_cos
                                       and marginals.device == state.D.device):
         raise SushiError("track: marginals is a contiguous float64 CUDA tensor of %d x %d values" % (state.n_total, state.n_shift))
     L = _native.lib()
-    _launch("sushi_hip_track_order_margins", state.D.device, L.sushi_hip_track_order_margins_bytes(n_rows, state.n_shift),
-            lambda mem, mem_bytes, st: L.sushi_hip_track_order_margins(
+    name = "sushi_hip_track_order_margins_wide" if _wide else "sushi_hip_track_order_margins"
+    fn = getattr(L, name)
+    _launch(name, state.D.device,
+            (L.sushi_hip_track_order_margins_wide_bytes if _wide else L.sushi_hip_track_order_margins_bytes)(n_rows, state.n_shift),
+            lambda mem, mem_bytes, st: fn(
                 curves.data_ptr(), int(curves.numel()), rt.ctypes.data, rc.ctypes.data, bc.ctypes.data, gd.ctypes.data, n_rows,
                 state.n_shift, _native.METHODS[method], pc.ctypes.data, mu, row0, state.n_total, state.D.data_ptr(), shifts.data_ptr(),
                 state.C.data_ptr(), state.S.data_ptr(), state.c_min.data_ptr(), state.through.data_ptr(), state.best.data_ptr(),
@@ -1030,25 +1081,42 @@ def find_ordered_track(stream, patterns, window_centers, window_size, penalty, o
     if wide:
         raise SushiError("find_ordered_track: wide=True belongs to find_track's plain pass; the ordered pass keeps its reach of %d"
                          % MAX_REACH)
+    return _find_ordered("find_ordered_track", False, stream, patterns, window_centers, window_size, penalty, order, max_rate, reach,
+                         step_cost, slack, weights, method, max_bytes, max_state_bytes, margins, guard, marginals, clamp, capacity)
+
+
+def find_ordered_wide_track(stream, patterns, window_centers, window_size, penalty, order=None, max_rate=None, reach=None, step_cost=0.0,
+                            slack=1, weights="equal", method="sqdiff_normed", max_bytes=MAX_BYTES, max_state_bytes=MAX_STATE_BYTES,
+                            margins=False, guard=None, marginals=False, clamp=None, capacity=None):
+    """WavStream.find_ordered_wide_track (its docstring)."""
+    return _find_ordered("find_ordered_wide_track", True, stream, patterns, window_centers, window_size, penalty, order, max_rate, reach,
+                         step_cost, slack, weights, method, max_bytes, max_state_bytes, margins, guard, marginals, clamp, capacity)
+
+
+def _find_ordered(name, wide, stream, patterns, window_centers, window_size, penalty, order, max_rate, reach, step_cost, slack, weights,
+                  method, max_bytes, max_state_bytes, margins, guard, marginals, clamp, capacity):
+    """What find_ordered_track and find_ordered_wide_track share in front of the search: the checks of their own arguments."""
     patterns, centres = list(patterns), list(window_centers)
     if not patterns or len(patterns) != len(centres):
-        raise SushiError("find_ordered_track: equally many patterns and centres (>= 1)")
+        raise SushiError("%s: equally many patterns and centres (>= 1)" % name)
     if (max_rate is None) == (reach is None):
-        raise SushiError("find_ordered_track: exactly one of max_rate and reach")
+        raise SushiError("%s: exactly one of max_rate and reach" % name)
     margins, marginals = bool(margins), bool(marginals)
     if not margins and (marginals or guard is not None):
-        raise SushiError("find_ordered_track: guard and marginals belong to margins=True")
+        raise SushiError("%s: guard and marginals belong to margins=True" % name)
     return _find_track_ordered(stream, patterns, centres, window_size, penalty, max_rate, reach, step_cost, slack, weights, method,
                                max_bytes, max_state_bytes, clamp, capacity, None if order is False else order, margins=margins,
-                               guard=guard, marginals=marginals, name="find_ordered_track")
+                               guard=guard, marginals=marginals, name=name, **({"wide": True} if wide else {}))
 
 
 def _find_track_ordered(stream, patterns, centres, window_size, penalty, max_rate, reach, step_cost, slack, weights, method, max_bytes,
-                        max_state_bytes, clamp, capacity, order, margins=False, guard=None, marginals=False, name="find_track"):
+                        max_state_bytes, clamp, capacity, order, margins=False, guard=None, marginals=False, name="find_track",
+                        wide=False):
     """find_track through the ordered pass: order None (every back without a limit: a penalty per event alone), True (order_back of
     the events) or one back per event; penalty a number or one per event.  margins (find_ordered_track alone): the rows of the
     forward pass are kept, and after the backtrack the chunks are walked again from the last one down (find_track(margins=True)'s
-    shape)."""
+    shape).  wide (find_ordered_wide_track alone): the reach's bound is WIDE_MAX_REACH, the calls are the wide ordered ones, and the
+    state's count holds a wide call's window records."""
     import torch
     from .curves import match_curves
     f, capacity = axis.checked_clamp(clamp, capacity, method)
@@ -1060,25 +1128,32 @@ def _find_track_ordered(stream, patterns, centres, window_size, penalty, max_rat
     lam = checked_penalties(penalty, E)
     ax = axis.event_axis(stream, offs, lens, centres, window_size)
     k_lo, n_shift, rate = ax.k_lo, ax.n_shift, stream.sample_rate
-    reach = checked_reach(rate_reach(ax.bases, max_rate, slack) if reach is None else reach, E)
+    reach = checked_reach(rate_reach(ax.bases, max_rate, slack) if reach is None else reach, E, wide=wide)
+    if wide:
+        checked_wide_step_cost(reach, mu)
     back = checked_back(None if order is None else (order_back(ax.bases, lens) if order is True else order), E)
     back[0] = BACK_ANY
     if margins:
         guard = checked_guard(int(0.01 * rate) if guard is None else guard, E)
-    need = TrackState.nbytes(E, n_shift, ordered=True, margins=margins, marginals=marginals)
+    state_bytes = ordered_wide_state_bytes if wide else (lambda *a, **k: TrackState.nbytes(*a, ordered=True, **k))
+    records = ", a wide call's window records" if wide else ""
+    need = state_bytes(E, n_shift, margins=margins, marginals=marginals)
     if need > max_state_bytes:
         if margins:
-            raise SushiError("%s: %d events x %d shifts need %d bytes of moves, jump sources, kept costs%s, max_state_bytes is %d (%d "
-                             "without margins)" % (name, E, n_shift, need, " and marginals" if marginals else "", max_state_bytes,
-                                                   TrackState.nbytes(E, n_shift, ordered=True)))
-        raise SushiError("%s: %d events x %d shifts need %d bytes of moves, jump sources and costs, max_state_bytes is %d"
-                         % (name, E, n_shift, need, max_state_bytes))
+            raise SushiError("%s: %d events x %d shifts need %d bytes of moves, jump sources, kept costs%s%s, max_state_bytes is %d (%d "
+                             "without margins)" % (name, E, n_shift, need, " and marginals" if marginals else "", records,
+                                                   max_state_bytes, state_bytes(E, n_shift)))
+        raise SushiError("%s: %d events x %d shifts need %d bytes of moves, jump sources and costs%s, max_state_bytes is %d"
+                         % (name, E, n_shift, need, records, max_state_bytes))
     per_chunk = int(max_bytes) // (4 * n_shift)
     if per_chunk < 1:
         raise SushiError("%s: one event of %d shifts needs %d bytes of curves, max_bytes is %d"
                          % (name, n_shift, 4 * n_shift, max_bytes))
     state = TrackState(E, n_shift, dst_dev.device, ordered=True, margins=margins)
-    forward = track_ordered_keep_device if margins else track_ordered_device
+    if wide:
+        forward, margins_device = (track_ordered_wide_keep_device if margins else track_ordered_wide_device), track_ordered_wide_margins_device
+    else:
+        forward, margins_device = (track_ordered_keep_device if margins else track_ordered_device), track_ordered_margins_device
     chunks = [(first, min(E, first + per_chunk)) for first in range(0, E, per_chunk)]
     rows_info = None
     for first, last in chunks:
@@ -1101,9 +1176,8 @@ def _find_track_ordered(stream, patterns, centres, window_size, penalty, max_rat
                 if f is not None:
                     rows_info = axis.merge_rows_info(rows_info, info)
             upto = last + 1 if last < E else last
-            track_ordered_margins_device(curves, zip(row_off, w[first:last].tolist()), reach[first:upto], guard[first:last],
-                                         lam[first:upto], mu, back[first:upto], state, index_dev, row0=first, method=method,
-                                         marginals=M)
+            margins_device(curves, zip(row_off, w[first:last].tolist()), reach[first:upto], guard[first:last], lam[first:upto], mu,
+                           back[first:upto], state, index_dev, row0=first, method=method, marginals=M)
         through, alt, alt_arg = state.through.cpu().numpy(), state.alt.cpu().numpy(), state.alt_arg.cpu().numpy()
         alt_shift = [None if int(k) == NO_ALT else k_lo + int(k) for k in alt_arg]
         extra = dict(guard=guard.tolist(), event_through=through,

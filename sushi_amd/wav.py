@@ -713,6 +713,24 @@ class WavStream(object):
                                         max_state_bytes=track.MAX_STATE_BYTES if max_state_bytes is None else int(max_state_bytes),
                                         margins=margins, guard=guard, marginals=marginals, clamp=clamp, capacity=capacity, wide=wide)
 
+    def find_ordered_wide_track(self, patterns, window_centers, window_size, penalty, order=None, max_rate=None, reach=None,
+                                step_cost=0.0, slack=1, weights='equal', method="sqdiff_normed", max_bytes=None, max_state_bytes=None,
+                                margins=False, guard=None, marginals=False, clamp=None, capacity=None):
+        """find_ordered_track across long gaps: every argument, the Track and its margins are find_ordered_track's,
+        but a reach -- given, or from max_rate -- may be up to 32767 samples, and one above 1024 needs step_cost 0 (SushiError names
+        the event otherwise), as find_track(wide=True)'s does.  A programme with long stretches without an event (an opening, a
+        song) and with repeated jingles or chapter marks needs both: order= and a penalty per event keep a path off the decoys, and
+        the wide reach lets the shift walk across the stretch instead of paying a jump.  A row of a reach up to 1024 goes through
+        find_ordered_track's own kernels: with no wider reach the Track is find_ordered_track's bit for bit; with order=None and one
+        penalty it is find_track(wide=True)'s.  The state is find_ordered_track's and 24 bytes per shift of window records
+        (track.ordered_wide_state_bytes) under max_state_bytes.  Needs a GPU."""
+        from . import track
+        return track.find_ordered_wide_track(self, patterns, window_centers, window_size, penalty, order=order, max_rate=max_rate,
+                                             reach=reach, step_cost=step_cost, slack=slack, weights=weights, method=method,
+                                             max_bytes=track.MAX_BYTES if max_bytes is None else int(max_bytes),
+                                             max_state_bytes=track.MAX_STATE_BYTES if max_state_bytes is None else int(max_state_bytes),
+                                             margins=margins, guard=guard, marginals=marginals, clamp=clamp, capacity=capacity)
+
     # ------------------------------------------------------------------ a shift that moves along the programme
     def find_drift(self, patterns, window_centers, window_size, max_rate, resolution=1.0, weights='equal', method="sqdiff_normed",
                    with_lines=False, max_bytes=None, clamp=None, capacity=None):
