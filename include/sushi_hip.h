@@ -63,7 +63,8 @@ extern "C" {
                                      sushi_hip_track_forward_wide_keep, sushi_hip_track_margins_wide;
                                      13 (additive): sushi_hip_track_order_wide_bytes, sushi_hip_track_order_margins_wide_bytes,
                                      sushi_hip_track_forward_ordered_wide, sushi_hip_track_forward_ordered_wide_keep,
-                                     sushi_hip_track_order_margins_wide */
+                                     sushi_hip_track_order_margins_wide;
+                                     13 (additive): SUSHI_HIP_PCM_*, sushi_hip_load_decode_format, sushi_hip_load_decode_mix_format */
 
 #if defined(__GNUC__)
 #define SUSHI_HIP_API __attribute__((visibility("default")))
@@ -1004,6 +1005,39 @@ SUSHI_HIP_API int sushi_hip_load_decode(const void* pcm_dev, int64_t n_frames, i
 SUSHI_HIP_API int sushi_hip_load_decode_mix(const void* pcm_dev, int64_t n_frames, int32_t channels, int32_t sample_width,
                               const float* weights_host, int32_t n_out, float* out_dev, int64_t out_stride,
                               void* hip_stream);
+/* ---- sample formats: the decode for 8-bit, 32-bit, float and double files (13, additive) ----
+ * sushi_hip_load_decode and sushi_hip_load_decode_mix with a format code in place of the sample width.  A sample's value is a
+ * float32 on the int16 scale of the rest of the pipeline, read little-endian, byte by byte, from its container:
+ *     SUSHI_HIP_PCM_U8   1 byte    (float)(((int)b - 128) * 256)
+ *     SUSHI_HIP_PCM_S16  2 bytes   the top two bytes as int16, as float32 (sushi_hip_load_decode's value; valid bits are
+ *     SUSHI_HIP_PCM_S24  3 bytes   left-justified in their container, so 20-in-24 and 24-in-32 come out right)
+ *     SUSHI_HIP_PCM_S32  4 bytes
+ *     SUSHI_HIP_PCM_F32  4 bytes   s = v * 32768.0f: one float32 multiply.  A NaN or +-inf s becomes +0.0f.  A denormal v and
+ *                                  -0.0f are values like any other: nothing is flushed and the sign is kept.
+ *     SUSHI_HIP_PCM_F64  8 bytes   s = (float)(v * 32768.0): a float64 multiply, then one rounding to float32 (nearest-even).  A
+ *                                  NaN or +-inf s becomes +0.0f, also where the cast overflows.
+ * Nothing is clamped.  sushi_hip_load_decode_format: the mean of a frame's values -- the float32 sum left to right, divided by
+ * float(channels), no division for one channel -- to mono_dev[0 .. n_frames).  sushi_hip_load_decode_mix_format: the weighted
+ * rows of sushi_hip_load_decode_mix on those values, in its order (every product and every sum rounded to float32), to
+ * out_dev + o * out_stride.  A NumPy restatement (sushi_amd.downmix.samples_from_bytes, then mean_host / mix_host) equals either
+ * result bit for bit; S16 and S24 give the bits of sushi_hip_load_decode / sushi_hip_load_decode_mix at sample_width 2 and 3.
+ * pcm_dev may have any byte alignment; only its n_frames * channels * container bytes are read.  weights_host is HOST memory and
+ * travels in the kernel's arguments.  Asynchronous; stateless; nothing is allocated.
+ * Checked before any HIP call, in this order -- sushi_hip_load_decode_format: EINVAL: a null pointer, n_frames < 0, channels < 1,
+ * an unknown format; EALIGN: mono_dev not 4-byte aligned.  sushi_hip_load_decode_mix_format: EINVAL: a null pointer, n_frames < 0,
+ * channels outside [1, SUSHI_HIP_MIX_MAX_CHANNELS], n_out outside [1, SUSHI_HIP_MIX_MAX_OUTPUTS], an unknown format, out_stride <
+ * n_frames, a weight that is not finite; EALIGN: out_dev not 4-byte aligned.  n_frames == 0 returns SUSHI_HIP_OK without a launch. */
+#define SUSHI_HIP_PCM_U8 1
+#define SUSHI_HIP_PCM_S16 2
+#define SUSHI_HIP_PCM_S24 3
+#define SUSHI_HIP_PCM_S32 4
+#define SUSHI_HIP_PCM_F32 5
+#define SUSHI_HIP_PCM_F64 6
+SUSHI_HIP_API int sushi_hip_load_decode_format(const void* pcm_dev, int64_t n_frames, int32_t channels, int32_t format,
+                                 float* mono_dev, void* hip_stream);
+SUSHI_HIP_API int sushi_hip_load_decode_mix_format(const void* pcm_dev, int64_t n_frames, int32_t channels, int32_t format,
+                                     const float* weights_host, int32_t n_out, float* out_dev, int64_t out_stride,
+                                     void* hip_stream);
 SUSHI_HIP_API int sushi_hip_load_resample(const float* raw_dev, int64_t n_raw, int32_t chunk, int32_t nl_full, double scale_full,
                             int64_t n_full, int32_t rest, int32_t nl_rest, double scale_rest,
                             int64_t pad, int64_t total, float* data_dev, void* hip_stream);

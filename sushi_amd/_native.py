@@ -19,6 +19,9 @@ U8, F32 = 0, 1
 PATH_FFT, PATH_DIRECT = 0, 1
 METHOD_SQDIFF_NORMED, METHOD_CCOEFF_NORMED = 0, 1       # cv2.TM_SQDIFF_NORMED + argmin (wav.py:185-186) | cv2.TM_CCOEFF_NORMED + argmax
 MIX_MAX_CHANNELS, MIX_MAX_OUTPUTS = 32, 8    # SUSHI_HIP_MIX_MAX_*: channels and output rows of sushi_hip_load_decode_mix
+# SUSHI_HIP_PCM_*: the sample formats of sushi_hip_load_decode_format / _decode_mix_format, and their container bytes
+PCM_FORMATS = {"u8": 1, "s16": 2, "s24": 3, "s32": 4, "f32": 5, "f64": 6}
+PCM_WIDTHS = {"u8": 1, "s16": 2, "s24": 3, "s32": 4, "f32": 4, "f64": 8}
 BEST_MAX_K = 32            # SUSHI_HIP_BEST_MAX_K: picks per request of a best-K run (sushi_hip_batch_run_best)
 TRACK_MAX_REACH, TRACK_JUMP = 1024, -32768   # SUSHI_HIP_TRACK_*: the widest move between two events, and the move word of a jump
 TRACK_WIDE_MAX_REACH = 32767     # SUSHI_HIP_TRACK_WIDE_MAX_REACH: the widest move of the wide pass (a free move: step_cost 0)
@@ -250,6 +253,10 @@ def lib():
     L.sushi_hip_load_decode.argtypes = [vp, i64, i32, i32, vp, vp]
     L.sushi_hip_load_decode_mix.restype = ci
     L.sushi_hip_load_decode_mix.argtypes = [vp, i64, i32, i32, vp, i32, vp, i64, vp]
+    L.sushi_hip_load_decode_format.restype = ci
+    L.sushi_hip_load_decode_format.argtypes = [vp, i64, i32, i32, vp, vp]
+    L.sushi_hip_load_decode_mix_format.restype = ci
+    L.sushi_hip_load_decode_mix_format.argtypes = [vp, i64, i32, i32, vp, i32, vp, i64, vp]
     L.sushi_hip_load_resample.restype = ci
     L.sushi_hip_load_resample.argtypes = [vp, i64, i32, i32, dbl, i64, i32, i32, dbl, i64, i64, vp, vp]
     L.sushi_hip_load_resample_fir.restype = ci

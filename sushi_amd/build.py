@@ -30,6 +30,9 @@ UNITS = [
     ("sushi_stream", ["-ffp-contract=off"]),    # stream preparation (prefix sums) and the stream C ABI (its parts: stream_core.hpp)
     # WavStream load pipeline (decode / downmix, weighted: downmix_core.hpp / decimate / pad / median clip / scale / quantise)
     ("sushi_load", ["-ffp-contract=off"]),      # NumPy's float32 operation order, no fused multiply-add
+    # the decode for every sample format a WAV carries: 8-bit, 16- / 24- / 32-bit integer, float, double (pcm_core.hpp: the sample
+    # rule, the mean and the mix on its values; a unit of its own: sushi_load's code does not change)
+    ("sushi_pcm", ["-ffp-contract=off"]),       # the scale's product, and the mix's products and sums, round separately
     # whole score curves: i8 MFMA Toeplitz GEMM (uint8), canonical float64 chain (float32); the same tiles (curve_tiles.hpp)
     # evaluate the listed pairs of a threshold run and of a best-K run; what a curve call uploads and launches is host only
     # (curve_core.hpp)

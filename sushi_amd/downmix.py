@@ -117,9 +117,47 @@ def frames_from_bytes(data, channels, sample_width):
     return out.reshape(n, channels)
 
 
+def scale_float_samples(values):
+    """The F32 / F64 rule of csrc/pcm_core.hpp on an array of full-scale samples (+-1.0): float32 values v become s = v * 32768.0f
+    (one float32 multiply), float64 values s = float32(v * 32768.0) (a float64 multiply, one rounding, nearest-even); a NaN or
+    +-inf s becomes +0.0f; denormals and -0.0 are values like any other.  Returns float32 of the same shape."""
+    values = np.asarray(values)
+    if values.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise SushiError('scale_float_samples: float32 or float64 samples')
+    with np.errstate(over='ignore', invalid='ignore', under='ignore'):
+        if values.dtype == np.float32:
+            s = values * np.float32(32768.0)
+        else:
+            s = (values * np.float64(32768.0)).astype(np.float32)
+    s[~np.isfinite(s)] = np.float32(0.0)
+    return s
+
+
+def samples_from_bytes(data, channels, sample_format):
+    """float32[n, channels] of raw little-endian frame bytes: every sample's value on the int16 scale, as csrc/pcm_core.hpp states it
+    (include/sushi_hip.h "sample formats") -- the NumPy restatement of sushi_hip_load_decode_format's samples, and the CPU path.
+    'u8': (b - 128) * 256;  's16' / 's24' / 's32': the top two bytes as int16 (for 's16' and 's24' frames_from_bytes as float32);
+    'f32' / 'f64': scale_float_samples.  Bytes behind the last whole frame are dropped."""
+    if sample_format not in _native.PCM_WIDTHS:
+        raise SushiError('Unsupported sample format: {0!r}'.format(sample_format))
+    width = _native.PCM_WIDTHS[sample_format]
+    raw = np.frombuffer(data, dtype=np.uint8)
+    n = raw.shape[0] // (channels * width)
+    raw = raw[:n * channels * width]
+    if sample_format == 'u8':
+        return ((raw.astype(np.int32) - 128) * 256).astype(np.float32).reshape(n, channels)
+    if sample_format in ('f32', 'f64'):
+        values = np.frombuffer(raw.tobytes(), dtype=np.float32 if sample_format == 'f32' else np.float64)
+        return scale_float_samples(values.reshape(n, channels))
+    top = np.empty(n * channels, np.int16)
+    top.view(np.uint8)[0::2] = raw[width - 2::width]
+    top.view(np.uint8)[1::2] = raw[width - 1::width]
+    return top.astype(np.float32).reshape(n, channels)
+
+
 def mean_host(frames):
-    """The reference's channel mean (wav.py:78-91) of int16 frames [n, C]: the channels as float32 summed left to right, the sum
-    divided by float(C) -- one channel: no division.  Returns float32[n]."""
+    """The reference's channel mean (wav.py:78-91) of int16 frames [n, C] -- or of float32 samples [n, C] (samples_from_bytes) --:
+    the channels as float32 summed left to right, the sum divided by float(C) -- one channel: no division.  Returns float32[n]."""
     s = frames.astype(np.float32)
     acc = s[:, 0].copy()
     for c in range(1, s.shape[1]):
@@ -130,13 +168,15 @@ def mean_host(frames):
 
 
 def mix_host(frames, weights):
-    """sushi_hip_load_decode_mix in NumPy, and the CPU path.  frames: int16[n, C]; weights: float32[n_out, C].  Row o is
+    """sushi_hip_load_decode_mix in NumPy, and the CPU path.  frames: int16[n, C] -- or float32 samples [n, C] (samples_from_bytes:
+    sushi_hip_load_decode_mix_format) --; weights: float32[n_out, C].  Row o is
     acc = w[o][0] * s_0, then acc = acc + w[o][c] * s_c for c = 1 .. C - 1 with s_c the samples as float32: every product and
     every sum rounded to float32, every channel in file order, zero weights included.  Returns float32[n_out, n]."""
     frames = np.asarray(frames)
     w = np.asarray(weights, dtype=np.float32)
-    if frames.ndim != 2 or frames.dtype != np.int16 or w.ndim != 2 or w.shape[1] != frames.shape[1] or w.shape[0] < 1:
-        raise SushiError("mix_host: int16 frames [n, C] and float32 weights [n_out, C]")
+    if frames.ndim != 2 or frames.dtype not in (np.dtype(np.int16), np.dtype(np.float32)) or w.ndim != 2 or \
+            w.shape[1] != frames.shape[1] or w.shape[0] < 1:
+        raise SushiError("mix_host: int16 or float32 frames [n, C] and float32 weights [n_out, C]")
     s = frames.astype(np.float32)
     out = np.empty((w.shape[0], frames.shape[0]), np.float32)
     for o in range(w.shape[0]):

@@ -58,25 +58,42 @@ def _median(L, data, n, side, hist, stream):
 UPLOAD_CHUNK_BYTES = 32 << 20      # PCM bytes uploaded and decoded per step: bounds the host memory of a load
 
 
-def decode_mix_on_device(L, staged, n_frames, channels, sample_width, weights, rows, first, st):
+def decode_mix_on_device(L, staged, n_frames, channels, sample_width, weights, rows, first, st, sample_format=None):
     """One sushi_hip_load_decode_mix launch: frames [0, n_frames) of the uploaded PCM bytes `staged` under the float32 weights
-    [n_out, channels] (a C-contiguous host array) go to rows[o, first : first + n_frames] of the float32 CUDA tensor `rows`."""
+    [n_out, channels] (a C-contiguous host array) go to rows[o, first : first + n_frames] of the float32 CUDA tensor `rows`.
+    sample_format (one of the formats _uses_format_entry names): the launch is sushi_hip_load_decode_mix_format's instead."""
+    if _uses_format_entry(sample_format):
+        _native.check(L.sushi_hip_load_decode_mix_format(staged.data_ptr(), n_frames, channels, _native.PCM_FORMATS[sample_format],
+                                                         weights.ctypes.data, weights.shape[0], rows.data_ptr() + 4 * first,
+                                                         rows.stride(0), st), "sushi_hip_load_decode_mix_format")
+        return
     _native.check(L.sushi_hip_load_decode_mix(staged.data_ptr(), n_frames, channels, sample_width, weights.ctypes.data,
                                               weights.shape[0], rows.data_ptr() + 4 * first, rows.stride(0), st),
                   "sushi_hip_load_decode_mix")
 
 
+def _uses_format_entry(sample_format):
+    """16- and 24-bit files (and a file read without a format: 'reference') keep the existing decode entry points, launch for launch;
+    'u8', 's32', 'f32' and 'f64' go through sushi_hip_load_decode_format / _decode_mix_format (csrc/sushi_pcm.hip)."""
+    return sample_format not in (None, 's16', 's24')
+
+
 def decode_file_on_device(wavfile, dev, weights=None, with_mean=False):
     """wav.py:64-91 on the GPU: the data chunk of `wavfile` (a DownmixedWavFile positioned at its first frame) is
     read UPLOAD_CHUNK_BYTES at a time, uploaded, decoded and downmixed by sushi_hip_load_decode into one float32
-    mono tensor.  Host memory: one chunk of file bytes.
+    mono tensor.  Host memory: one chunk of file bytes.  A file whose sample_format is 'u8', 's32', 'f32' or 'f64' (read with
+    formats='all') takes sushi_hip_load_decode_format / _decode_mix_format instead, chunk by chunk in the same way.
     weights (float32 [n_out, channels], sushi_amd.downmix.weight_matrix): every chunk is still read and uploaded once, and one
     sushi_hip_load_decode_mix launch on it writes all n_out weighted rows; the channel mean is then decoded only with with_mean=True,
     by the existing entry on the same uploaded chunk.  Returns (mean tensor [frames] or None, rows tensor [n_out, frames] or None,
     frames).  Device memory: one float32 row at the file's frame rate per mix."""
     L = _native.lib()
     frame_size = wavfile.frame_size
-    if wavfile.sample_width not in (2, 3):
+    sample_format = getattr(wavfile, 'sample_format', None)
+    if _uses_format_entry(sample_format):
+        if sample_format not in _native.PCM_FORMATS or wavfile.sample_width != _native.PCM_WIDTHS[sample_format]:
+            raise SushiError('Unsupported sample format: {0!r}'.format(sample_format))
+    elif wavfile.sample_width not in (2, 3):
         raise SushiError('Unsupported sample width: {0}'.format(wavfile.sample_width))
     if weights is not None:
         weights = np.ascontiguousarray(weights, dtype=np.float32)
@@ -101,11 +118,16 @@ def decode_file_on_device(wavfile, dev, weights=None, with_mean=False):
                 logging.error("Length of audio channels didn't match. This might result in broken output")
             # (a pageable-memory upload returns when the bytes have left `stage`: it can be refilled right away)
             staged = torch.frombuffer(stage, dtype=torch.uint8, count=got * frame_size).to(dev)
-            if want_mean:
+            if want_mean and _uses_format_entry(sample_format):
+                _native.check(L.sushi_hip_load_decode_format(staged.data_ptr(), got, wavfile.channels_count,
+                                                             _native.PCM_FORMATS[sample_format], mono.data_ptr() + 4 * done, st),
+                              "sushi_hip_load_decode_format")
+            elif want_mean:
                 _native.check(L.sushi_hip_load_decode(staged.data_ptr(), got, wavfile.channels_count, wavfile.sample_width,
                                                       mono.data_ptr() + 4 * done, st), "sushi_hip_load_decode")
             if rows is not None:
-                decode_mix_on_device(L, staged, got, wavfile.channels_count, wavfile.sample_width, weights, rows, done, st)
+                decode_mix_on_device(L, staged, got, wavfile.channels_count, wavfile.sample_width, weights, rows, done, st,
+                                     sample_format)
             done += got
             del staged                                           # stream-ordered free: the kernels above are queued first
     keep = max(done, 1)                                       # the frames that were there (n_raw of the pipeline)
@@ -114,12 +136,15 @@ def decode_file_on_device(wavfile, dev, weights=None, with_mean=False):
 
 def mix_frames_on_device(frames, weights, dev):
     """mix_host on the GPU for frames already in memory: int16 frames [n, channels] (C-contiguous) under the float32 weights
-    [n_out, channels] -> a float32 CUDA tensor [n_out, n] on `dev`.  One upload, one sushi_hip_load_decode_mix launch."""
+    [n_out, channels] -> a float32 CUDA tensor [n_out, n] on `dev`.  One upload, one sushi_hip_load_decode_mix launch.
+    float32 / float64 frames: full-scale samples, mixed as an 'f32' / 'f64' file's (one sushi_hip_load_decode_mix_format launch)."""
     n, channels = frames.shape
+    sample_format = {np.dtype(np.int16): None, np.dtype(np.float32): 'f32', np.dtype(np.float64): 'f64'}[frames.dtype]
     with torch.cuda.device(dev):
         staged = torch.from_numpy(frames.reshape(-1).view(np.uint8)).to(dev)
         rows = torch.empty((weights.shape[0], n), dtype=torch.float32, device=dev)
-        decode_mix_on_device(_native.lib(), staged, n, channels, 2, weights, rows, 0, torch.cuda.current_stream(dev).cuda_stream)
+        decode_mix_on_device(_native.lib(), staged, n, channels, 2, weights, rows, 0, torch.cuda.current_stream(dev).cuda_stream,
+                             sample_format)
     return rows
 
 

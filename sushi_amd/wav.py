@@ -4,7 +4,8 @@ Same constructor, attributes and methods as reference wav.py:104-188; ``find_sub
 the GPU (libsushi_hip.so) instead of ``cv2.matchTemplate`` + ``argmin`` (wav.py:185-186).
 Extensions: ``WavStream.from_samples`` (in-memory PCM), ``find_substreams`` (batched), ``downmix=`` / ``WavStream.load_mixes`` /
 ``WavStream.from_channels`` (the channels mixed by weight instead of averaged: sushi_amd/downmix.py), ``find_joint`` /
-``find_joint_many`` (the one shift a group of patterns shares: sushi_amd/joint.py).
+``find_joint_many`` (the one shift a group of patterns shares: sushi_amd/joint.py), ``formats='all'`` (float, 32-bit, 8-bit and
+RF64 / BW64 files: the header walk below, the sample rule in sushi_amd/downmix.py ``samples_from_bytes`` / csrc/pcm_core.hpp).
 
 The load pipeline (wav.py:64-162): the RIFF header walk on the host; PCM decode, channel downmix, decimation,
 padding, the two medians, clip / scale / quantise on the GPU when one is present (the file is uploaded in bounded
@@ -29,7 +30,17 @@ from .common import SushiError, clip
 from .row import fill_pads, row_layout
 
 WAVE_FORMAT_PCM = 0x0001
+WAVE_FORMAT_IEEE_FLOAT = 0x0003
 WAVE_FORMAT_EXTENSIBLE = 0xFFFE
+# what follows the two format bytes in every SubFormat GUID that stands for a format tag (KSDATAFORMAT_SUBTYPE_*)
+_SUBFORMAT_TAIL = bytes.fromhex("000000001000800000aa00389b71")
+FORMATS = ('reference', 'all')
+
+
+def check_formats(formats):
+    if not isinstance(formats, str) or formats not in FORMATS:
+        raise SushiError("Unknown formats setting of WAV stream, must be 'reference' or 'all'")
+
 
 # what WavStream._requests returns
 _Requests = namedtuple("_Requests", "dst_dev src_dev offs lens one_owner start_times win_start n_pos")
@@ -40,33 +51,54 @@ class DownmixedWavFile(object):
     channel_mask: the dwChannelMask of an EXTENSIBLE fmt chunk that is long enough to hold one (an int), else None."""
     _file = None
     channel_mask = None
+    sample_format = None    # 'u8', 's16', 's24', 's32', 'f32', 'f64'; None: a width only formats='all' decodes, read as 'reference'
+    formats = 'reference'
 
-    def __init__(self, path):
+    def __init__(self, path, formats='reference'):
+        """formats: 'reference' (the default) -- the reference's parser and its refusals: RIFF, format tag 1 or 0xFFFE, 16 or 24
+        bits --, or 'all': also 8-bit and 32-bit integer, 32- and 64-bit float (format tag 3, and EXTENSIBLE headers by their
+        SubFormat), inside RIFF, RF64 or BW64."""
         super(DownmixedWavFile, self).__init__()
+        check_formats(formats)
+        self.formats = formats
         self._file = open(path, 'rb')
         try:
             head = self._file.read(12)
-            if head[0:4] != b'RIFF':
+            rf64 = formats == 'all' and head[0:4] in (b'RF64', b'BW64')
+            if head[0:4] != b'RIFF' and not rf64:
                 raise SushiError('File does not start with RIFF id')
             if head[8:12] != b'WAVE':
                 raise SushiError('Not a WAVE file')
             fmt_chunk_read = False
             data_chunk_read = False
+            ds64_data_size = None
             file_size = os.path.getsize(path)
             while True:
                 hdr = self._file.read(8)
                 if len(hdr) < 8:
                     break
                 name, size = hdr[0:4], struct.unpack('<L', hdr[4:8])[0]
-                if name == b'fmt ':
+                if formats == 'all' and name != b'data' and size == 0xFFFFFFFF:
+                    raise SushiError('Invalid WAV file')              # only the data chunk's size may stand in ds64
+                if rf64 and name == b'ds64':
+                    # riffSize, dataSize, sampleCount (u64 each), then a table of other chunks' sizes, which is ignored
+                    body = self._file.read(size + (size & 1))
+                    if size < 24 or len(body) < 24:
+                        raise SushiError('Invalid WAV file')
+                    ds64_data_size = struct.unpack('<Q', body[8:16])[0]
+                elif name == b'fmt ':
                     body = self._file.read(size + (size & 1))
                     self._read_fmt_chunk(body)
                     fmt_chunk_read = True
                 elif name == b'data':
                     if not fmt_chunk_read:
                         raise SushiError('Invalid WAV file')
+                    if rf64 and ds64_data_size is None:
+                        raise SushiError('Invalid WAV file')          # RF64 / BW64: ds64 comes before data
                     self._data_start = self._file.tell()
-                    if file_size > 0xFFFFFFFF:
+                    if rf64:
+                        self.frames_count = (ds64_data_size if size == 0xFFFFFFFF else size) // self.frame_size
+                    elif file_size > 0xFFFFFFFF:
                         # large broken wav
                         self.frames_count = (file_size - self._file.tell()) // self.frame_size
                     else:
@@ -95,14 +127,45 @@ class DownmixedWavFile(object):
 
     def _read_fmt_chunk(self, body):
         wFormatTag, self.channels_count, self.framerate, _avg, _align = struct.unpack('<HHLLH', body[:14])
-        if wFormatTag == WAVE_FORMAT_PCM or wFormatTag == WAVE_FORMAT_EXTENSIBLE:  # ignore the rest
+        if self.formats == 'all':
+            bits_per_sample = struct.unpack('<H', body[14:16])[0]
+            self.sample_format = self._classify(wFormatTag, bits_per_sample, body)
+            self.sample_width = (bits_per_sample + 7) // 8
+        elif wFormatTag == WAVE_FORMAT_PCM or wFormatTag == WAVE_FORMAT_EXTENSIBLE:  # ignore the rest
             bits_per_sample = struct.unpack('<H', body[14:16])[0]
             self.sample_width = (bits_per_sample + 7) // 8
+            self.sample_format = {2: 's16', 3: 's24'}.get(self.sample_width)      # (any other width is refused where it is decoded)
         else:
             raise SushiError('unknown format: {0}'.format(wFormatTag))
         self.frame_size = self.channels_count * self.sample_width
         if wFormatTag == WAVE_FORMAT_EXTENSIBLE and len(body) >= 24:      # cbSize, wValidBitsPerSample, then the mask
             self.channel_mask = struct.unpack('<L', body[20:24])[0]
+
+    @staticmethod
+    def _classify(tag, bits, body):
+        """formats='all': the sample format of a fmt chunk.  Tag 1 by its bits (8: 'u8', 9-16: 's16', 17-24: 's24', 25-32: 's32'),
+        tag 3 'f32' / 'f64'; tag 0xFFFE with a body that holds a SubFormat by the GUID's first two bytes (its fixed tail must match),
+        a shorter one as PCM.  Anything else is refused by tag and bits."""
+        kind = tag
+        if tag == WAVE_FORMAT_EXTENSIBLE:
+            kind = WAVE_FORMAT_PCM
+            if len(body) >= 40:
+                kind = struct.unpack('<H', body[24:26])[0] if body[26:40] == _SUBFORMAT_TAIL else None
+        if kind == WAVE_FORMAT_PCM and 8 <= bits <= 32:
+            return ('u8', 's16', 's24', 's32')[(bits + 7) // 8 - 1]
+        if kind == WAVE_FORMAT_IEEE_FLOAT and bits in (32, 64):
+            return 'f32' if bits == 32 else 'f64'
+        if tag == WAVE_FORMAT_EXTENSIBLE and len(body) >= 40:
+            raise SushiError('Unsupported sample format: tag 0x{0:04X}, SubFormat {1}, {2} bits'.format(tag, body[24:40].hex(), bits))
+        raise SushiError('Unsupported sample format: tag 0x{0:04X}, {1} bits'.format(tag, bits))
+
+    def frames(self, data):
+        """Raw frame bytes as what the mean and the mixes work on: int16 [n, channels] for 16- and 24-bit files (frames_int16),
+        float32 samples [n, channels] for the formats only formats='all' reads (sushi_amd.downmix.samples_from_bytes)."""
+        if self.sample_format in (None, 's16', 's24'):
+            return self.frames_int16(data)
+        from .downmix import samples_from_bytes
+        return samples_from_bytes(data, self.channels_count, self.sample_format)
 
     def frames_int16(self, data):
         """Raw frame bytes as int16 [n, channels]: what _decode averages, before it does (24-bit samples: their top two bytes)."""
@@ -115,7 +178,7 @@ class DownmixedWavFile(object):
 
     def _decode(self, data):
         from .downmix import mean_host
-        frames = self.frames_int16(data)
+        frames = self.frames(data)
         if (len(data) // self.sample_width) % self.channels_count:
             logging.error("Length of audio channels didn't match. This might result in broken output")
         return mean_host(frames)
@@ -139,12 +202,13 @@ def torch_device(device):
     return torch.device("cuda", torch.cuda.current_device()) if d.type == "cuda" and d.index is None else d
 
 
-def _check_args(sample_type, resample):
+def _check_args(sample_type, resample, formats='reference'):
     """What every way of building a stream checks before anything else."""
     if sample_type not in ('float32', 'uint8'):
         raise SushiError('Unknown sample type of WAV stream, must be uint8 or float32')
     from .resample import check_mode
     check_mode(resample)
+    check_formats(formats)
 
 
 def _is_mean(downmix):
@@ -171,15 +235,20 @@ class WavStream(object):
     READ_CHUNK_SIZE = 1  # one second, seems to be the fastest
     PADDING_SECONDS = 10
 
-    def __init__(self, path, sample_rate=12000, sample_type='uint8', device=None, downmix='mean', resample='nearest'):
+    def __init__(self, path, sample_rate=12000, sample_type='uint8', device=None, downmix='mean', resample='nearest',
+                 formats='reference'):
         """resample: 'nearest' (the reference's decimation, wav.py:125-137: the nearest frame, no filter) or 'fir': a zero-phase
         windowed-sinc low-pass at the file's rate in front of the decimator (sushi_amd.resample) -- on the GPU when there is one
         (sushi_hip_load_resample_fir), in NumPy otherwise, bit for bit the same; shape, time axis and everything after it unchanged.
         downmix: 'mean' (the reference's channel average, wav.py:80-91), a named mix or one weight per channel
         (sushi_amd.downmix.weights_for): the channels are then mixed by weight in the decode -- on the GPU when there is one
-        (sushi_hip_load_decode_mix), in NumPy otherwise, bit for bit the same -- and everything after it is unchanged."""
-        _check_args(sample_type, resample)
-        self._load_mixes(path, [downmix], sample_rate, sample_type, device, resample, first=self)
+        (sushi_hip_load_decode_mix), in NumPy otherwise, bit for bit the same -- and everything after it is unchanged.
+        formats: 'reference' (the reference's front door: RIFF, 16- or 24-bit PCM, its refusals and their text) or 'all': 8-bit and
+        32-bit integer, 32- and 64-bit float files too, inside RIFF, RF64 or BW64 (DownmixedWavFile).  A sample
+        becomes a float32 on the int16 scale (sushi_amd.downmix.samples_from_bytes; on the GPU sushi_hip_load_decode_format /
+        _decode_mix_format, bit for bit the same), and everything after the decode -- downmix=, resample=, the clip -- is unchanged."""
+        _check_args(sample_type, resample, formats)
+        self._load_mixes(path, [downmix], sample_rate, sample_type, device, resample, first=self, formats=formats)
 
     @classmethod
     def from_samples(cls, samples, framerate, sample_rate=12000, sample_type='uint8', device=None, resample='nearest'):
@@ -192,24 +261,24 @@ class WavStream(object):
         return self
 
     @classmethod
-    def load_mixes(cls, path, mixes, sample_rate=12000, sample_type='uint8', device=None, resample='nearest'):
+    def load_mixes(cls, path, mixes, sample_rate=12000, sample_type='uint8', device=None, resample='nearest', formats='reference'):
         """[WavStream(path, downmix=m, resample=resample) for m in mixes] -- live streams, bit for bit those -- with the file read once: each chunk is
         uploaded once and one decode launch per chunk serves every weighted mix ('mean' in the list: the existing decode on the same
         uploaded chunk).  At most 8 weighted mixes.  Memory: one float32 row at the FILE's frame rate per mix (in HBM on the GPU path)
-        until the last of them has been decimated."""
-        _check_args(sample_type, resample)
+        until the last of them has been decimated.  formats: the constructor's."""
+        _check_args(sample_type, resample, formats)
         mixes = list(mixes)
         if not mixes:
             raise SushiError('load_mixes: at least one mix')
-        return cls._load_mixes(path, mixes, sample_rate, sample_type, device, resample)
+        return cls._load_mixes(path, mixes, sample_rate, sample_type, device, resample, formats=formats)
 
     @classmethod
-    def _load_mixes(cls, path, mixes, sample_rate, sample_type, device, resample, first=None):
+    def _load_mixes(cls, path, mixes, sample_rate, sample_type, device, resample, first=None, formats='reference'):
         """One stream per mix from one pass over the file -- the one place a file is read; `first`: the instance to fill for
         mixes[0] (the constructor's).  resample: every mix row is decimated on its own, so 'fir' filters each separately."""
         from .downmix import mix_host, weight_matrix
         before_read = time()
-        stream = DownmixedWavFile(path)
+        stream = DownmixedWavFile(path, formats)
         streams = [first if (k == 0 and first is not None) else cls.__new__(cls) for k in range(len(mixes))]
         try:
             weighted = [k for k, m in enumerate(mixes) if not _is_mean(m)]
@@ -235,7 +304,7 @@ class WavStream(object):
                     if with_mean:
                         mono[got:got + m] = stream._decode(data)
                     if weighted:
-                        rows[:, got:got + m] = mix_host(stream.frames_int16(data), W)
+                        rows[:, got:got + m] = mix_host(stream.frames(data), W)
                     got += m
             if got == 0:
                 raise SushiError('no audio frames in the data chunk')
@@ -259,21 +328,23 @@ class WavStream(object):
                       resample='nearest'):
         """Build a stream from PCM frames already in memory -- int16 [n, channels], as DownmixedWavFile.frames_int16 returns them --
         mixed by `downmix` ('mean', a named mix or weights; channel_mask: the speaker layout a named mix reads, None: the WAV default
-        order), running the same pipeline as the constructor."""
-        from .downmix import mean_host, mix_host, weight_matrix
+        order), running the same pipeline as the constructor.  float32 or float64 frames [n, channels] are samples in full-scale
+        units (+-1.0), taken as a float file's are under formats='all' (sushi_amd.downmix.scale_float_samples)."""
+        from .downmix import mean_host, mix_host, scale_float_samples, weight_matrix
         _check_args(sample_type, resample)
         frames = np.ascontiguousarray(frames)
-        if frames.ndim != 2 or frames.dtype != np.int16 or frames.shape[0] < 1 or frames.shape[1] < 1:
+        if frames.ndim != 2 or frames.dtype not in (np.dtype(np.int16), np.dtype(np.float32), np.dtype(np.float64)) or \
+                frames.shape[0] < 1 or frames.shape[1] < 1:
             raise SushiError('from_channels: int16 frames [n, channels]')
         if _is_mean(downmix):
-            samples = mean_host(frames)
+            samples = mean_host(frames if frames.dtype == np.int16 else scale_float_samples(frames))
         else:
             W = weight_matrix([downmix], frames.shape[1], channel_mask)
             if cls._use_gpu():
                 from .load import mix_frames_on_device
                 samples = mix_frames_on_device(frames, W, torch_device("cuda" if device is None else device))[0]
             else:
-                samples = mix_host(frames, W)[0]
+                samples = mix_host(frames if frames.dtype == np.int16 else scale_float_samples(frames), W)[0]
         self = cls.__new__(cls)
         self._build(samples, int(framerate), frames.shape[0], sample_rate, sample_type, resample, device)
         return self
