@@ -64,7 +64,8 @@ extern "C" {
                                      13 (additive): sushi_hip_track_order_wide_bytes, sushi_hip_track_order_margins_wide_bytes,
                                      sushi_hip_track_forward_ordered_wide, sushi_hip_track_forward_ordered_wide_keep,
                                      sushi_hip_track_order_margins_wide;
-                                     13 (additive): SUSHI_HIP_PCM_*, sushi_hip_load_decode_format, sushi_hip_load_decode_mix_format */
+                                     13 (additive): SUSHI_HIP_PCM_*, sushi_hip_load_decode_format, sushi_hip_load_decode_mix_format;
+                                     13 (additive): sushi_hip_envelope */
 
 #if defined(__GNUC__)
 #define SUSHI_HIP_API __attribute__((visibility("default")))
@@ -460,6 +461,26 @@ SUSHI_HIP_API int sushi_hip_retime(const void* in_dev, int dtype, int64_t n_in,
                                    const SushiHipRetimeSegment* seg_host, int n_seg,
                                    void* out_dev, int64_t n_out,
                                    void* mem_dev, size_t mem_bytes, void* hip_stream);
+
+/* ---- loudness contour: a row's mean absolute deviation, decimated (13, additive) --------------
+ * Two releases of one programme whose waveforms differ -- inverted polarity, a speed change with the pitch kept, another carrier
+ * under the same contour -- still share their loudness contour.  This call turns a row into that contour at 1 / hop of its rate,
+ * in an arithmetic stated to the bit.  hop h in [1, 256], span m in [1, 64], W = h * m <= 4096, a = (m - 1) / 2 (integer
+ * division), c = sushi_hip_centre(dtype).  For a block index b, which may be negative,
+ *     B_b = sum over t = 0 .. h - 1, in that order, of |x[clamp(in_start + b * h + t, 0, n_in - 1)] - c|
+ * and output i, 0 <= i < out_len, is
+ *     E_i = B_{i-a} + B_{i-a+1} + ... + B_{i-a+m-1}, summed in that order
+ *     SUSHI_HIP_U8:  everything in integers (E <= 524288);  out = min(255, (4 * E + W) / (2 * W))    (2 E / W rounded half up)
+ *     SUSHI_HIP_F32: d = fabs((double)x - 0.5); B and E are float64 running sums from 0.0, every addition rounded once (no fused
+ *                    multiply-add, no pairwise sum);  out = (float)((E + E) / (double)W)
+ * so a NumPy restatement equals the result bit for bit; there is no square root and no logarithm.  Output i covers the input
+ * samples in_start + (i - a) * h .. in_start + (i - a + m) * h - 1; reads outside the row see its edge samples.
+ * in_dev / out_dev: n_in / out_len samples of `dtype`, naturally aligned, not overlapping.  One launch, no workspace, no device
+ * allocation.  Asynchronous; stateless (any thread).  Checked before any HIP call -- EINVAL: a null pointer, an unknown dtype,
+ * n_in < 1 (or >= 2^62), out_len < 1 or >= 2^40, in_start outside [0, n_in - 1], hop outside [1, 256], span outside [1, 64],
+ * hop * span > 4096; EALIGN: in_dev / out_dev not aligned to their sample type. */
+SUSHI_HIP_API int sushi_hip_envelope(const void* in_dev, int dtype, int64_t n_in, int64_t in_start,
+                                     int32_t hop, int32_t span, void* out_dev, int64_t out_len, void* hip_stream);
 
 /* ---- joint search: the one shift a group of score rows shares (13, additive) -----------------
  * Events of one scene share one shift, and a lone search of a short or repeated pattern may prefer a decoy in its window.  The

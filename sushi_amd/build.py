@@ -73,6 +73,9 @@ UNITS = [
     # score rows clamped at a threshold: a fill and a scatter of a threshold run's hits, and the rule applied to rows that exist
     # (rows_core.hpp: the rule, the tiles, the search of a hit list, and the call's host side)
     ("sushi_rows", []),                         # comparisons and copies: no arithmetic to contract
+    # a row's loudness contour: the mean absolute deviation about the sample type's centre over span blocks of hop samples, a tile
+    # of blocks staged through LDS (envelope_core.hpp: the arithmetic, the tile, and the call's host side)
+    ("sushi_envelope", ["-ffp-contract=off"]),  # float64 sums in a stated order, each addition rounded once, as NumPy's
     # overlap-save FFT path; its parts, by stage, are csrc/sushi_fft_*.inc (included inside its anonymous namespace); the plan of
     # a batch (plan_core.hpp), what a handle holds about its requests and how it is staged (batch_core.hpp) and what a run decides
     # (run_policy.hpp) are host only

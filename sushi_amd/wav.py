@@ -5,7 +5,8 @@ the GPU (libsushi_hip.so) instead of ``cv2.matchTemplate`` + ``argmin`` (wav.py:
 Extensions: ``WavStream.from_samples`` (in-memory PCM), ``find_substreams`` (batched), ``downmix=`` / ``WavStream.load_mixes`` /
 ``WavStream.from_channels`` (the channels mixed by weight instead of averaged: sushi_amd/downmix.py), ``find_joint`` /
 ``find_joint_many`` (the one shift a group of patterns shares: sushi_amd/joint.py), ``formats='all'`` (float, 32-bit, 8-bit and
-RF64 / BW64 files: the header walk below, the sample rule in sushi_amd/downmix.py ``samples_from_bytes`` / csrc/pcm_core.hpp).
+RF64 / BW64 files: the header walk below, the sample rule in sushi_amd/downmix.py ``samples_from_bytes`` / csrc/pcm_core.hpp),
+``retimed`` (the stream on another clock: sushi_amd/retime.py), ``envelope`` (its loudness contour: sushi_amd/envelope.py).
 
 The load pipeline (wav.py:64-162): the RIFF header walk on the host; PCM decode, channel downmix, decimation,
 padding, the two medians, clip / scale / quantise on the GPU when one is present (the file is uploaded in bounded
@@ -862,4 +863,45 @@ class WavStream(object):
             fill_pads(data[0], pad)
         new = self.__class__.__new__(self.__class__)
         new._adopt(data, dev_row, self.sample_rate, new_count, self.padding_size, self._device)
+        return new
+
+    # ------------------------------------------------------------------ the loudness contour
+    def envelope(self, hop=8, span=4):
+        """This stream's loudness contour (sushi_amd.envelope; DESIGN.md 3.26): a new live WavStream at sample_rate // hop
+        (SushiError unless hop divides the rate) whose sample k is the mean absolute deviation, about the sample type's nominal
+        centre, of span blocks of hop samples -- twice that mean, so that a full-scale square wave gives full scale.  With
+        a = (span - 1) // 2, sample k of the body covers the source instants [(k - a) * hop, (k - a + span) * hop) / sample_rate
+        of this stream's body; reads outside the row see its edge samples.  Source and destination of a search are enveloped with
+        the same hop and span and so get the same offset: shifts are unaffected.  padding_size // hop samples of padding, filled as
+        the loader fills them, ceil(sample_count / hop) samples of body, the same sample type.  What survives is what two releases
+        share when their waveforms do not: inverted polarity, a speed change with the pitch kept (envelope().retimed(speed) puts
+        the contour on the destination's clock), another carrier under the same contour.  On the GPU when there is one
+        (sushi_hip_envelope; the row stays in HBM for the matching), else in NumPy -- bit for bit the same.  The result is an
+        ordinary stream: every search method, SpeculativeStream, retimed and estimate_speed take it as it is."""
+        from .envelope import envelope_device, envelope_host, envelope_layout
+        pad, count, total = int(self.padding_size), int(self.sample_count), int(self.data.shape[1])
+        if count < 1 or pad < 0 or pad + count > total:
+            raise SushiError('envelope: the stream has no body inside its row')
+        new_rate, new_pad, new_count = envelope_layout(self.sample_rate, pad, count, hop)
+        if self._use_gpu():
+            import torch
+            dev = torch_device("cuda" if self._device is None else self._device)
+            if self._dev is not None and self._dev.device == dev:
+                row = self._dev.raw
+            elif self._dev_row is not None and self._dev_row.device == dev:
+                row = self._dev_row
+            else:
+                row = torch.from_numpy(self.data[0]).to(dev)
+            with torch.cuda.device(dev):
+                dev_row = torch.empty(2 * new_pad + new_count, dtype=row.dtype, device=dev)
+                envelope_device(row, pad, hop, span, new_count, out=dev_row[new_pad:new_pad + new_count])
+                fill_pads(dev_row, new_pad)
+                data = dev_row.cpu().numpy().reshape(1, -1)
+        else:
+            dev_row = None
+            data = np.empty((1, 2 * new_pad + new_count), self.data.dtype)
+            data[0, new_pad:new_pad + new_count] = envelope_host(self.data[0], pad, hop, span, new_count)
+            fill_pads(data[0], new_pad)
+        new = self.__class__.__new__(self.__class__)
+        new._adopt(data, dev_row, new_rate, new_count, new_pad, self._device)
         return new
