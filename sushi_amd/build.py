@@ -51,25 +51,16 @@ UNITS = [
     # (path_core.hpp: the arithmetic, and the call's host side)
     ("sushi_path", ["-ffp-contract=off"]),      # NumPy's float64 operation order: product and sum round separately
     # a shift that wanders: the same pass with moves of bounded reach between rows, a window minimum over an LDS-staged tile of the
-    # row before (track_core.hpp: the arithmetic, and the call's host side; path_device.hpp: what it shares with sushi_path)
-    ("sushi_track", ["-ffp-contract=off"]),     # the price of a move and the candidate it is added to round separately
-    # how firmly the tracking pass places each event: the same recurrence from the last row down over the kept forward rows, and
-    # three first minima per row (track_margin_core.hpp: the arithmetic, and the call's host side)
-    ("sushi_track_margins", ["-ffp-contract=off"]),     # track_core.hpp's candidates unchanged; M and C round once each
-    # tracked events kept in order: the tracking step with a jump read per index from the prefix minimum of the row before, and
-    # per row a scan of (minimum, first index) that writes it (track_order_core.hpp: the combine rule, the call's host side, the walker)
+    # row before; its margins, the same recurrence from the last row down over the kept forward rows and three first minima per
+    # row; and the wide form of both, a reach up to 32767 where moves are free: per wide row a tile pass of prefix / suffix minima
+    # (sushi_track_wide_tile.inc) and a step that combines a few of its records.  One unit, its step parts (the .inc files)
+    # included once (track_core.hpp, track_margin_core.hpp, track_wide_core.hpp: the arithmetic, and the calls' host side;
+    # path_device.hpp: what it shares with sushi_path)
+    ("sushi_track", ["-ffp-contract=off"]),     # a move's price and its candidate round separately; M and C round once each
+    # tracked events kept in order: the same four walks with a jump read per index from the prefix (margins: suffix) minimum of the
+    # row before (after), and per row a scan of (minimum, first index) that writes it; the wide rows share sushi_track's tile pass
+    # (track_order_core.hpp, track_order_margin_core.hpp: the combine rule, t and t', the jump sums, the calls' host side)
     ("sushi_track_order", ["-ffp-contract=off"]),       # track_core.hpp's candidates unchanged; the jump's sum rounds once
-    # how firmly the ordered pass places each event: the margins step with a jump read per index from the suffix minimum of the row
-    # after, and per row a scan downwards that writes it (track_order_margin_core.hpp: t', the jump sum, the call's host side)
-    ("sushi_track_order_margins", ["-ffp-contract=off"]),       # the candidates unchanged; the jump's sum, M and C round once each
-    # the tracking pass and its margins with a reach up to 32767 where moves are free: per wide row a tile pass of prefix / suffix
-    # minima and a step that combines a few of its records; narrower rows go through sushi_track's and sushi_track_margins' own
-    # step kernels (the two .inc parts) (track_wide_core.hpp: the decomposition, the records, the call's host side)
-    ("sushi_track_wide", ["-ffp-contract=off"]),        # track_core.hpp's candidates unchanged: the price is added once, to the winner
-    # the ordered pass and its margins with the same wide reach: a wide row's tile pass (sushi_track_wide_tile.inc), a step with
-    # wide_near and the jump read per index from P / S, then the ordered pass's own scan and apply; narrower rows go through
-    # sushi_track_order's and sushi_track_order_margins' own kernels (their .inc parts) (track_order_wide_core.hpp: the call's host side)
-    ("sushi_track_order_wide", ["-ffp-contract=off"]),  # the candidates and the jump's sum unchanged: each rounds once
     # score rows clamped at a threshold: a fill and a scatter of a threshold run's hits, and the rule applied to rows that exist
     # (rows_core.hpp: the rule, the tiles, the search of a hit list, and the call's host side)
     ("sushi_rows", []),                         # comparisons and copies: no arithmetic to contract

@@ -1,6 +1,6 @@
 // sushi_amd/csrc/sushi_track_margins_step.inc -- the margins pass's step and close kernels and their launcher: a part of
-// sushi_track_margins.hip, which describes them, and of sushi_track_wide.hip, which sends its rows of a reach up to TRACK_MAX_REACH
-// through the same code.  Included inside the unit's anonymous namespace, after sushi_internal.hpp, track_margin_core.hpp,
+// sushi_track.hip, which describes them; a wide call sends its rows of a reach up to TRACK_MAX_REACH through the same code.
+// Included once, inside the unit's anonymous namespace, after sushi_internal.hpp, track_margin_core.hpp,
 // path_device.hpp and track_margin_device.hpp and a `using namespace sushi`.
 struct MarginArgs {
     const float* row;                       // R_e: curves + curve_off

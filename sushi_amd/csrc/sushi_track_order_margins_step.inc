@@ -1,6 +1,6 @@
 // sushi_amd/csrc/sushi_track_order_margins_step.inc -- the ordered margins' step, scan and apply kernels and the step's launcher,
-// included inside the anonymous namespace of sushi_track_order_margins.hip and of sushi_track_order_wide.hip (which sends its rows
-// of a reach up to TRACK_MAX_REACH through them, and every row through the scan and the apply): one text, the same code in both.
+// included once, inside the anonymous namespace of sushi_track_order.hip, which describes them; a wide call sends its rows of a
+// reach up to TRACK_MAX_REACH through them, and every row through the scan and the apply.
 struct OrderMarginArgs {
     const float* row;                       // R_e: curves + curve_off
     double weight, penalty, step_cost;      // penalty: row e + 1's

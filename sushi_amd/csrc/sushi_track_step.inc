@@ -1,6 +1,6 @@
 // sushi_amd/csrc/sushi_track_step.inc -- the tracking pass's step and close kernels and their launcher: a part of sushi_track.hip,
-// which describes them, and of sushi_track_wide.hip, which sends its rows of a reach up to TRACK_MAX_REACH through the same code.
-// Included inside the unit's anonymous namespace, after sushi_internal.hpp, track_core.hpp and path_device.hpp and a `using
+// which describes them; a wide call sends its rows of a reach up to TRACK_MAX_REACH through the same code.  Included once, inside
+// the unit's anonymous namespace, after sushi_internal.hpp, track_core.hpp and path_device.hpp and a `using
 // namespace sushi`.
 struct TrackArgs {
     const float* row;                       // R_e: curves + curve_off

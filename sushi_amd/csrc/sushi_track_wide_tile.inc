@@ -1,6 +1,6 @@
 // sushi_amd/csrc/sushi_track_wide_tile.inc -- the wide pass's tile kernel and its launcher, and how a work item of a wide step
-// stages its whole tiles' records in LDS; included inside the anonymous namespace of sushi_track_wide.hip and of
-// sushi_track_order_wide.hip: one text, the same code in both units.
+// stages its whole tiles' records in LDS; included inside the anonymous namespace of sushi_track.hip and of sushi_track_order.hip:
+// one text, the same code in both units.
 
 // ---- the tile pass ----
 __device__ __forceinline__ WideRec wide_shfl_up(const WideRec& r, int off) {

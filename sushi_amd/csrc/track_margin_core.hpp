@@ -1,8 +1,8 @@
 // sushi_amd/csrc/track_margin_core.hpp -- the arithmetic of sushi_hip_track_margins (include/sushi_hip.h "margins"),
-// one shift index at a time, on top of track_core.hpp's candidates.  Plain C++: sushi_track_margins.hip runs it on the device,
+// one shift index at a time, on top of track_core.hpp's candidates.  Plain C++: sushi_track.hip runs it on the device,
 // tests/host_track_margins_check.cpp on the CPU (g++).  Both are compiled with -ffp-contract=off.  Behind it, host only: the
 // workspace's layout (three first minima per workgroup) and stage_margins -- a call's arguments -> a refusal, or the facts of its
-// launches.
+// launches, plain or wide.
 #ifndef SUSHI_TRACK_MARGIN_CORE_HPP
 #define SUSHI_TRACK_MARGIN_CORE_HPP
 
@@ -54,8 +54,12 @@ inline size_t margin_layout_bytes(int n_rows, int64_t n_shift) {
     return n_rows < 1 || n_shift < 1 || n_shift > INT32_MAX ? 0 : margin_layout((int32_t)n_shift).bytes;
 }
 
-struct MarginStage {
-    PathSplit split;
+inline size_t margin_wide_layout_bytes(int n_rows, int64_t n_shift) {
+    const size_t plain = margin_layout_bytes(n_rows, n_shift);
+    return plain == 0 ? 0 : wide_layout_of(plain, (int32_t)n_shift).bytes;
+}
+
+struct MarginStage : TrackCall {
     MarginLayout lay;
     bool first_call;            // row0 + n_rows == n_total: the call begins at the sequence's last row
 };
@@ -63,31 +67,34 @@ struct MarginStage {
 // The call walks rows row0 + n_rows - 1 down to row0 of a sequence of n_total rows.  rows[i] and guard[i] are row row0 + i's;
 // reach[i] is row row0 + i's for i = 0 .. n_rows, the last only where that row exists (row0 + n_rows < n_total); reach[0] is not
 // used (the step into row row0 is priced when the row before it is walked) and is ignored.
-// stage_track's refusals in its order -- EINVAL: a null table; an unknown method; n_rows < 1, n_shift < 1, n_curve < 1, n_shift >
-// n_curve; row0 < 0, n_total < 1 or the rows not inside [0, n_total) (no sum that could pass int is formed); a penalty or a
-// step_cost that is not finite or is negative; a row that leaves the curve buffer or a weight that is not finite or is negative; a
-// used reach outside 0 .. TRACK_MAX_REACH; a guard < 0.  Then EALIGN: a workspace that is not 256-byte aligned; ENOSPACE:
-// mem_bytes below the layout's.  `out` is unspecified after a refusal.
+// The margins walks' EINVALs: a null guard table and track_args_check's; a row that leaves the curve buffer or a weight that is
+// not finite or is negative; a used reach that is not track_reach_ok; a guard < 0.
+inline int margin_rows_check(const SushiHipJointRow* rows, const int32_t* reach, const int32_t* guard, const void* mem, int n_rows,
+                             int32_t n_shift, int64_t n_curve, int method, double penalty, double step_cost, int row0, int n_total,
+                             bool wide, bool& first_call, int& n_wide) {
+    if (!guard) return SUSHI_HIP_EINVAL;
+    const int rc = track_args_check(rows, reach, mem, n_rows, n_shift, n_curve, method, penalty, step_cost, row0, n_total);
+    if (rc != SUSHI_HIP_OK) return rc;
+    first_call = n_rows == n_total - row0;
+    n_wide = 0;
+    const int used_to = first_call ? n_rows - 1 : n_rows;                  // reach[1 .. used_to] are used
+    for (int i = 0; i <= used_to; ++i) {
+        if (i < n_rows && !axis_row_ok(rows[i], n_curve, n_shift)) return SUSHI_HIP_EINVAL;
+        if (i > 0 && !track_reach_ok(reach[i], step_cost, wide, n_wide)) return SUSHI_HIP_EINVAL;
+        if (i < n_rows && guard[i] < 0) return SUSHI_HIP_EINVAL;
+    }
+    return SUSHI_HIP_OK;
+}
+
+// margin_rows_check's refusals, then track_workspace_check's.  `out` is unspecified after a refusal.
 inline int stage_margins(const SushiHipJointRow* rows, const int32_t* reach, const int32_t* guard, int n_rows, int32_t n_shift,
                          int64_t n_curve, int method, double penalty, double step_cost, int row0, int n_total, const void* mem,
-                         size_t mem_bytes, MarginStage& out) {
-    if (!rows || !reach || !guard || !mem) return SUSHI_HIP_EINVAL;
-    if (!method_known(method)) return SUSHI_HIP_EINVAL;
-    if (n_rows < 1 || n_shift < 1 || n_curve < 1 || n_shift > n_curve) return SUSHI_HIP_EINVAL;
-    if (n_total < 1 || row0 < 0 || row0 >= n_total || n_rows > n_total - row0) return SUSHI_HIP_EINVAL;
-    if (!isfinite(penalty) || penalty < 0.0 || !isfinite(step_cost) || step_cost < 0.0) return SUSHI_HIP_EINVAL;
-    out.first_call = n_rows == n_total - row0;
-    for (int i = 0; i < n_rows; ++i) {
-        if (!axis_row_ok(rows[i], n_curve, n_shift)) return SUSHI_HIP_EINVAL;
-        if (i > 0 && (reach[i] < 0 || reach[i] > TRACK_MAX_REACH)) return SUSHI_HIP_EINVAL;
-        if (guard[i] < 0) return SUSHI_HIP_EINVAL;
-    }
-    if (!out.first_call && (reach[n_rows] < 0 || reach[n_rows] > TRACK_MAX_REACH)) return SUSHI_HIP_EINVAL;
-    out.split = track_split(n_shift);
+                         size_t mem_bytes, MarginStage& out, bool wide = false) {
+    const int rc = margin_rows_check(rows, reach, guard, mem, n_rows, n_shift, n_curve, method, penalty, step_cost, row0, n_total, wide,
+                                     out.first_call, out.n_wide);
+    if (rc != SUSHI_HIP_OK) return rc;
     out.lay = margin_layout(n_shift);
-    if ((uintptr_t)mem & 255) return SUSHI_HIP_EALIGN;
-    if (mem_bytes < out.lay.bytes) return SUSHI_HIP_ENOSPACE;
-    return SUSHI_HIP_OK;
+    return track_workspace_check(mem, mem_bytes, out.lay.bytes, n_shift, wide, out);
 }
 
 // reach_{e+1} for the launch of row row0 + i: 0 for the sequence's last row, which has no row after it

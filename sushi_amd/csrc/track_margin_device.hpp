@@ -1,5 +1,5 @@
-// sushi_amd/csrc/track_margin_device.hpp -- the device side the two margins passes share (sushi_track_margins.hip and
-// sushi_track_order_margins.hip): the partial records of three first minima a step's workgroups leave, and how one workgroup turns
+// sushi_amd/csrc/track_margin_device.hpp -- the device side the two margins passes share (sushi_track.hip's and
+// sushi_track_order.hip's): the partial records of three first minima a step's workgroups leave, and how one workgroup turns
 // them into a row's outputs.  Device code only; included after sushi_internal.hpp, track_margin_core.hpp and path_device.hpp.
 #ifndef SUSHI_TRACK_MARGIN_DEVICE_HPP
 #define SUSHI_TRACK_MARGIN_DEVICE_HPP

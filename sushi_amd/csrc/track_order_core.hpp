@@ -3,7 +3,7 @@
 // row's own.  Plain C++: sushi_track_order.hip runs it on the device, tests/host_track_order_check.cpp on the CPU (g++), both
 // compiled with -ffp-contract=off.  The candidates of a move, track_step and the move word are track_core.hpp's, unchanged.  Here:
 // the (value, index) combine rule of the prefix minimum and t_e(j); host only, stage_track_ordered -- a call's arguments -> a
-// refusal, or the facts of its launches -- and the workspace's layout; host and device, the backtrack's one walker.
+// refusal, or the facts of its launches, plain or wide -- and the workspace's layout; host and device, the backtrack's one walker.
 #ifndef SUSHI_TRACK_ORDER_CORE_HPP
 #define SUSHI_TRACK_ORDER_CORE_HPP
 
@@ -64,32 +64,30 @@ inline size_t order_layout_bytes(int n_rows, int64_t n_shift) {
     return n_rows < 1 || n_shift < 1 || n_shift > INT32_MAX ? 0 : order_layout((int32_t)n_shift).bytes;
 }
 
-struct OrderStage {
-    PathSplit split;
+inline size_t order_wide_layout_bytes(int n_rows, int64_t n_shift) {
+    const size_t plain = order_layout_bytes(n_rows, n_shift);
+    return plain == 0 ? 0 : wide_layout_of(plain, (int32_t)n_shift).bytes;
+}
+
+struct OrderStage : TrackCall {
     OrderLayout lay;
 };
 
-// Everything stage_track refuses about the arguments the two calls share (its penalty check is made per row here, and its
-// workspace is not this call's: an aligned address without a limit stands in for it), and -- EINVAL: a null back or penalty table; a
-// back below TRACK_BACK_ANY; a penalty that is not finite or is negative in any row but the sequence's row 0 (whose penalty is
-// ignored, as its back is: no jump enters it).  Then EALIGN: a workspace that is not 256-byte aligned; ENOSPACE: mem_bytes below the layout's.
+// EINVAL: a null back or penalty table; track_rows_check's (there is no one penalty to check: it is made per row here); a back
+// below TRACK_BACK_ANY; a penalty that is not finite or is negative in any row but the sequence's row 0 (whose penalty is ignored,
+// as its back is: no jump enters it).  Then track_workspace_check's refusals.  `out` is unspecified after a refusal.
 inline int stage_track_ordered(const SushiHipJointRow* rows, const int32_t* reach, const int32_t* back, const double* penalty, int n_rows,
                                int32_t n_shift, int64_t n_curve, int method, double step_cost, int row0, int n_total, const void* mem,
-                               size_t mem_bytes, OrderStage& out) {
+                               size_t mem_bytes, OrderStage& out, bool wide = false) {
     if (!back || !penalty) return SUSHI_HIP_EINVAL;
-    TrackStage shared;
-    const int rc = stage_track(rows, reach, n_rows, n_shift, n_curve, method, 0.0, step_cost, row0, n_total,
-                               mem ? (const void*)(uintptr_t)256 : nullptr, SIZE_MAX, shared);
+    const int rc = track_rows_check(rows, reach, mem, n_rows, n_shift, n_curve, method, 0.0, step_cost, row0, n_total, wide, out.n_wide);
     if (rc != SUSHI_HIP_OK) return rc;
     for (int i = 0; i < n_rows; ++i) {
         if (back[i] < TRACK_BACK_ANY) return SUSHI_HIP_EINVAL;
         if ((row0 > 0 || i > 0) && (!isfinite(penalty[i]) || penalty[i] < 0.0)) return SUSHI_HIP_EINVAL;
     }
-    out.split = shared.split;
     out.lay = order_layout(n_shift);
-    if ((uintptr_t)mem & 255) return SUSHI_HIP_EALIGN;
-    if (mem_bytes < out.lay.bytes) return SUSHI_HIP_ENOSPACE;
-    return SUSHI_HIP_OK;
+    return track_workspace_check(mem, mem_bytes, out.lay.bytes, n_shift, wide, out);
 }
 
 // ---- the backtrack: one walker, on the device (one lane) and on the CPU ----

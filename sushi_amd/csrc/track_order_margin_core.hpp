@@ -1,10 +1,10 @@
 // sushi_amd/csrc/track_order_margin_core.hpp -- the arithmetic of sushi_hip_track_order_margins (include/sushi_hip.h "ordered
 // margins") that track_margin_core.hpp and track_order_core.hpp do not already hold: the backward recurrence's jump
-// term, a suffix minimum read with the bound on the other side.  Plain C++: sushi_track_order_margins.hip runs it on the device,
+// term, a suffix minimum read with the bound on the other side.  Plain C++: sushi_track_order.hip runs it on the device,
 // tests/host_track_order_margins_check.cpp on the CPU (g++), both compiled with -ffp-contract=off.  The window minimum, margin_back
 // / margin_through / margin_suffix / margin_outside / margin_alt_index and order_combine are theirs, unchanged.  Here: t'_e(j), the
 // jump sum and the suffix minimum's combine rule on values alone; host only, the workspace's layout and stage_order_margins -- a
-// call's arguments -> a refusal, or the facts of its launches.
+// call's arguments -> a refusal, or the facts of its launches, plain or wide.
 #ifndef SUSHI_TRACK_ORDER_MARGIN_CORE_HPP
 #define SUSHI_TRACK_ORDER_MARGIN_CORE_HPP
 
@@ -57,37 +57,34 @@ inline size_t order_margin_layout_bytes(int n_rows, int64_t n_shift) {
     return n_rows < 1 || n_shift < 1 || n_shift > INT32_MAX ? 0 : order_margin_layout((int32_t)n_shift).bytes;
 }
 
-struct OrderMarginStage {
-    PathSplit split;
+inline size_t order_margin_wide_layout_bytes(int n_rows, int64_t n_shift) {
+    const size_t plain = order_margin_layout_bytes(n_rows, n_shift);
+    return plain == 0 ? 0 : wide_layout_of(plain, (int32_t)n_shift).bytes;
+}
+
+struct OrderMarginStage : TrackCall {
     OrderMarginLayout lay;
     bool first_call;            // row0 + n_rows == n_total: the call begins at the sequence's last row
 };
 
 // The tables are stage_margins': rows[i] and guard[i] are row row0 + i's; reach[i], back[i] and penalty[i] are row row0 + i's for
-// i = 0 .. n_rows, the last only where that row exists; entry 0 is not used and is ignored.  Everything stage_margins refuses, in
-// its order (it has no penalty of its own to check here, and its workspace is not this call's: an aligned address without a limit
-// stands in for it), and -- EINVAL: a null back or penalty table; a used back below TRACK_BACK_ANY; a used penalty that is not finite
-// or is negative.  Then EALIGN: a workspace that is not 256-byte aligned; ENOSPACE: mem_bytes below the layout's.  `out` is
-// unspecified after a refusal.
+// i = 0 .. n_rows, the last only where that row exists; entry 0 is not used and is ignored.  EINVAL: a null back or penalty table;
+// margin_rows_check's (there is no one penalty to check); a used back below TRACK_BACK_ANY; a used penalty that is not finite or is
+// negative.  Then track_workspace_check's refusals.  `out` is unspecified after a refusal.
 inline int stage_order_margins(const SushiHipJointRow* rows, const int32_t* reach, const int32_t* back, const double* penalty,
                                const int32_t* guard, int n_rows, int32_t n_shift, int64_t n_curve, int method, double step_cost, int row0,
-                               int n_total, const void* mem, size_t mem_bytes, OrderMarginStage& out) {
+                               int n_total, const void* mem, size_t mem_bytes, OrderMarginStage& out, bool wide = false) {
     if (!back || !penalty) return SUSHI_HIP_EINVAL;
-    MarginStage shared;
-    const int rc = stage_margins(rows, reach, guard, n_rows, n_shift, n_curve, method, 0.0, step_cost, row0, n_total,
-                                 mem ? (const void*)(uintptr_t)256 : nullptr, SIZE_MAX, shared);
+    const int rc = margin_rows_check(rows, reach, guard, mem, n_rows, n_shift, n_curve, method, 0.0, step_cost, row0, n_total, wide,
+                                     out.first_call, out.n_wide);
     if (rc != SUSHI_HIP_OK) return rc;
-    const int used = shared.first_call ? n_rows - 1 : n_rows;       // entries 1 .. used
+    const int used = out.first_call ? n_rows - 1 : n_rows;          // entries 1 .. used
     for (int i = 1; i <= used; ++i) {
         if (back[i] < TRACK_BACK_ANY) return SUSHI_HIP_EINVAL;
         if (!isfinite(penalty[i]) || penalty[i] < 0.0) return SUSHI_HIP_EINVAL;
     }
-    out.split = shared.split;
-    out.first_call = shared.first_call;
     out.lay = order_margin_layout(n_shift);
-    if ((uintptr_t)mem & 255) return SUSHI_HIP_EALIGN;
-    if (mem_bytes < out.lay.bytes) return SUSHI_HIP_ENOSPACE;
-    return SUSHI_HIP_OK;
+    return track_workspace_check(mem, mem_bytes, out.lay.bytes, n_shift, wide, out);
 }
 
 // back_{e+1} and penalty_{e+1} for the launch of row row0 + i: no limit and 0 for the sequence's last row, which has no row after

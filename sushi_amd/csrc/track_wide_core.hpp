@@ -1,8 +1,9 @@
 // sushi_amd/csrc/track_wide_core.hpp -- the arithmetic of the wide tracking pass (include/sushi_hip.h "wide tracking"; DESIGN.md
 // 3.23): near_e[j] for a reach above TRACK_MAX_REACH and a step_cost of +-0.0, in a time that does not grow with the reach.  Plain
-// C++: sushi_track_wide.hip runs it on the device, tests/host_track_wide_check.cpp on the CPU (g++).  Both are compiled with
-// -ffp-contract=off, as every track unit is.  Behind it, host only: the workspace's layout and stage_track_wide /
-// stage_margins_wide -- a call's arguments -> a refusal, or the facts of its launches.
+// C++: sushi_track.hip and sushi_track_order.hip run it on the device, tests/host_track_wide_check.cpp on the CPU (g++).  Both are
+// compiled with -ffp-contract=off, as every track unit is.  The tile's size, the workspace's layout and a wide call's staging are
+// track_core.hpp's (stage_track(..., wide) and the stages built on it); stage_track_wide and stage_margins_wide, at the end, are
+// one-line forwards to them.
 //
 // With a free move the order of track_replaces -- (value, |d|, d > 0) -- decomposes: the minimum of X[j - r .. j - 1] with ties to
 // the LARGEST index, the minimum of X[j + 1 .. j + r] with ties to the SMALLEST index, and X[j] itself, combined by track_replaces.
@@ -24,18 +25,7 @@
 
 namespace sushi {
 
-constexpr int32_t TRACK_WIDE_MAX_REACH = SUSHI_HIP_TRACK_WIDE_MAX_REACH;
-static_assert(TRACK_WIDE_MAX_REACH == INT16_MAX, "a move word holds every wide move, and TRACK_JUMP stays free");
-
-// a window tile: WIDE_TILE consecutive indices from a multiple of WIDE_TILE on; an index inside it fits 16 bits
-constexpr int WIDE_TILE_BITS = 10;
-constexpr int32_t WIDE_TILE = 1 << WIDE_TILE_BITS;
-static_assert(TRACK_MAX_REACH + 1 >= WIDE_TILE, "every wide reach is at least a tile: a window that the axis does not cut spans a boundary");
 constexpr int WIDE_PER = WIDE_TILE / TRACK_THREADS;         // consecutive values a thread of the tile pass holds
-
-SUSHI_GEOM_HD inline int64_t wide_tiles(int64_t n_shift) { return (n_shift + WIDE_TILE - 1) >> WIDE_TILE_BITS; }
-SUSHI_GEOM_HD inline bool wide_row(int32_t reach) { return reach > TRACK_MAX_REACH; }
-SUSHI_GEOM_HD inline bool wide_step_cost_ok(double step_cost) { return step_cost == 0.0; }          // +0.0 or -0.0
 
 // ---- the records ----
 // The minimum of a run of consecutive values: its value (of equal values any one's: 0.0 and -0.0 are equal, so the sign of a zero
@@ -67,7 +57,7 @@ struct WideRecords {
     uint32_t* pi; uint32_t* si;
 };
 
-// One window tile on the CPU, one element after the other (the device scans it in a workgroup: sushi_track_wide.hip).
+// One window tile on the CPU, one element after the other (the device scans it in a workgroup: sushi_track_wide_tile.inc).
 inline void wide_tile_scan(const double* X, int32_t n_shift, int64_t tile, const WideRecords& w) {
     const int64_t lo = tile << WIDE_TILE_BITS, hi = lo + WIDE_TILE < n_shift ? lo + WIDE_TILE : n_shift;
     WideRec run = wide_empty();
@@ -151,111 +141,36 @@ SUSHI_GEOM_HD inline double wide_near(const double* X, const double* pv, const d
     return track_cand(best, track_price(mu, bd < 0 ? -bd : bd));
 }
 
-// ---- the host side of a call ----
-// workspace: the plain call's layout, then the records of one row -- [pv: f64 x n_shift][sv: f64 x n_shift][pi: u32 x n_shift]
-// [si: u32 x n_shift], each array padded to 256 bytes.  One row's records live at a time: a wide row's tile pass writes them and its
-// step reads them, in stream order.
-struct WideLayout {
-    size_t pv, sv, pi, si, bytes;           // offsets from the workspace's start
-};
-inline WideLayout wide_layout_of(size_t plain_bytes, int32_t n_shift) {
-    WideLayout l;
-    l.pv = align_up(plain_bytes, 256);
-    l.sv = l.pv + align_up(8 * (size_t)n_shift, 256);
-    l.pi = l.sv + align_up(8 * (size_t)n_shift, 256);
-    l.si = l.pi + align_up(4 * (size_t)n_shift, 256);
-    l.bytes = l.si + align_up(4 * (size_t)n_shift, 256);
-    return l;
-}
+// a wide call's record arrays in its workspace (the layout: track_core.hpp)
 inline WideRecords wide_records(char* mem, const WideLayout& l) {
     return WideRecords{(double*)(mem + l.pv), (double*)(mem + l.sv), (uint32_t*)(mem + l.pi), (uint32_t*)(mem + l.si)};
 }
-inline size_t track_wide_layout_bytes(int n_rows, int64_t n_shift) {
-    const size_t plain = track_layout_bytes(n_rows, n_shift);
-    return plain == 0 ? 0 : wide_layout_of(plain, (int32_t)n_shift).bytes;
-}
-inline size_t margin_wide_layout_bytes(int n_rows, int64_t n_shift) {
-    const size_t plain = margin_layout_bytes(n_rows, n_shift);
-    return plain == 0 ? 0 : wide_layout_of(plain, (int32_t)n_shift).bytes;
-}
-// the tile pass's grid: one workgroup per window tile, at most AXIS_MAX_GRID of them striding over the tiles
-inline unsigned wide_tile_grid(int32_t n_shift) { return axis_grid(wide_tiles(n_shift)); }
 
-struct TrackWideStage {
-    TrackStage plain;
-    WideLayout wide;
-    unsigned tile_grid;
-    int n_wide;                 // rows of the call that go through the wide kernels
+// ---- a wide call's stage by a name of its own ----
+// The stage functions with `wide` set, in the shape the CPU checks of the wide calls read (tests/host_track_wide_check.cpp,
+// tests/host_track_order_wide_check.cpp): the walk's own stage as `plain`, the wide facts beside it.  One-line forwards: the
+// checking body is the walk's.
+template <typename Stage>
+struct WideStageOf : TrackCall {
+    Stage plain;
 };
+using TrackWideStage = WideStageOf<TrackStage>;
+using MarginWideStage = WideStageOf<MarginStage>;
 
-// stage_track's refusals in its order, the reach's bound TRACK_WIDE_MAX_REACH -- and, where stage_track looks at a row's reach:
-// EINVAL for a used reach above TRACK_MAX_REACH beside a step_cost that is not +-0.0.  Then EALIGN and ENOSPACE (the wide layout's
-// bytes), as there.
 inline int stage_track_wide(const SushiHipJointRow* rows, const int32_t* reach, int n_rows, int32_t n_shift, int64_t n_curve, int method,
                             double penalty, double step_cost, int row0, int n_total, const void* mem, size_t mem_bytes,
                             TrackWideStage& out) {
-    if (!rows || !reach || !mem) return SUSHI_HIP_EINVAL;
-    if (!method_known(method)) return SUSHI_HIP_EINVAL;
-    if (n_rows < 1 || n_shift < 1 || n_curve < 1 || n_shift > n_curve) return SUSHI_HIP_EINVAL;
-    if (n_total < 1 || row0 < 0 || row0 >= n_total || n_rows > n_total - row0) return SUSHI_HIP_EINVAL;
-    if (!isfinite(penalty) || penalty < 0.0 || !isfinite(step_cost) || step_cost < 0.0) return SUSHI_HIP_EINVAL;
-    out.n_wide = 0;
-    for (int i = 0; i < n_rows; ++i) {
-        if (!axis_row_ok(rows[i], n_curve, n_shift)) return SUSHI_HIP_EINVAL;
-        if (row0 > 0 || i > 0) {
-            if (reach[i] < 0 || reach[i] > TRACK_WIDE_MAX_REACH) return SUSHI_HIP_EINVAL;
-            if (wide_row(reach[i])) {
-                if (!wide_step_cost_ok(step_cost)) return SUSHI_HIP_EINVAL;
-                ++out.n_wide;
-            }
-        }
-    }
-    out.plain.split = track_split(n_shift);
-    out.plain.lay = track_layout(n_shift);
-    out.wide = wide_layout_of(out.plain.lay.bytes, n_shift);
-    out.tile_grid = wide_tile_grid(n_shift);
-    if ((uintptr_t)mem & 255) return SUSHI_HIP_EALIGN;
-    if (mem_bytes < out.wide.bytes) return SUSHI_HIP_ENOSPACE;
-    return SUSHI_HIP_OK;
+    const int rc = stage_track(rows, reach, n_rows, n_shift, n_curve, method, penalty, step_cost, row0, n_total, mem, mem_bytes, out.plain, true);
+    static_cast<TrackCall&>(out) = out.plain;
+    return rc;
 }
-
-struct MarginWideStage {
-    MarginStage plain;
-    WideLayout wide;
-    unsigned tile_grid;
-    int n_wide;
-};
-
-// stage_margins' refusals in its order, with the same two changes.
 inline int stage_margins_wide(const SushiHipJointRow* rows, const int32_t* reach, const int32_t* guard, int n_rows, int32_t n_shift,
                               int64_t n_curve, int method, double penalty, double step_cost, int row0, int n_total, const void* mem,
                               size_t mem_bytes, MarginWideStage& out) {
-    if (!rows || !reach || !guard || !mem) return SUSHI_HIP_EINVAL;
-    if (!method_known(method)) return SUSHI_HIP_EINVAL;
-    if (n_rows < 1 || n_shift < 1 || n_curve < 1 || n_shift > n_curve) return SUSHI_HIP_EINVAL;
-    if (n_total < 1 || row0 < 0 || row0 >= n_total || n_rows > n_total - row0) return SUSHI_HIP_EINVAL;
-    if (!isfinite(penalty) || penalty < 0.0 || !isfinite(step_cost) || step_cost < 0.0) return SUSHI_HIP_EINVAL;
-    out.plain.first_call = n_rows == n_total - row0;
-    out.n_wide = 0;
-    const int used_to = out.plain.first_call ? n_rows - 1 : n_rows;        // reach[1 .. used_to] are used
-    for (int i = 0; i <= used_to; ++i) {
-        if (i < n_rows && !axis_row_ok(rows[i], n_curve, n_shift)) return SUSHI_HIP_EINVAL;
-        if (i > 0) {
-            if (reach[i] < 0 || reach[i] > TRACK_WIDE_MAX_REACH) return SUSHI_HIP_EINVAL;
-            if (wide_row(reach[i])) {
-                if (!wide_step_cost_ok(step_cost)) return SUSHI_HIP_EINVAL;
-                ++out.n_wide;
-            }
-        }
-        if (i < n_rows && guard[i] < 0) return SUSHI_HIP_EINVAL;
-    }
-    out.plain.split = track_split(n_shift);
-    out.plain.lay = margin_layout(n_shift);
-    out.wide = wide_layout_of(out.plain.lay.bytes, n_shift);
-    out.tile_grid = wide_tile_grid(n_shift);
-    if ((uintptr_t)mem & 255) return SUSHI_HIP_EALIGN;
-    if (mem_bytes < out.wide.bytes) return SUSHI_HIP_ENOSPACE;
-    return SUSHI_HIP_OK;
+    const int rc = stage_margins(rows, reach, guard, n_rows, n_shift, n_curve, method, penalty, step_cost, row0, n_total, mem, mem_bytes,
+                                 out.plain, true);
+    static_cast<TrackCall&>(out) = out.plain;
+    return rc;
 }
 
 }  // namespace sushi

@@ -207,6 +207,32 @@ def _near_of(reach):
     return _near_wide if int(reach) > MAX_REACH else _near
 
 
+def _unit_cost(row, weight, method):
+    """u_e = w_e * float64(R_e), R_e negated first for 'ccoeff_normed'."""
+    c = row.astype(np.float64)
+    if method == "ccoeff_normed":
+        c = -c
+    return weight * c
+
+
+def _margins_tail(shifts, D, M, guard, c_min):
+    """What a margins pass reads off M once it is whole, behind the forward pass's fields: (D, M, through, best, best_arg, alt,
+    alt_arg, c_min) -- through M_e[s_e]; best / best_arg the minimum of M_e and its first index; alt / alt_arg the same over the
+    shifts more than guard_e from s_e (inf and NO_ALT where there are none)."""
+    E, n = M.shape
+    through = np.array([M[e, shifts[e]] for e in range(E)], np.float64)
+    best_arg = np.array([int(np.argmin(M[e])) for e in range(E)], np.int32)
+    best = np.array([M[e, best_arg[e]] for e in range(E)], np.float64)
+    alt, alt_arg = np.full(E, np.inf, np.float64), np.full(E, NO_ALT, np.int32)
+    j = np.arange(n, dtype=np.int64)
+    for e in range(E):
+        outside = np.abs(j - int(shifts[e])) > int(guard[e])
+        if outside.any():
+            at = int(np.argmin(np.where(outside, M[e], np.inf)))       # the first index of the minimum outside the window
+            alt[e], alt_arg[e] = M[e, at], at
+    return D, M, through, best, best_arg, alt, alt_arg, c_min
+
+
 def track_host(rows, weights, penalty, step_cost, reach, method="sqdiff_normed", _keep=None, wide=False):
     """sushi_hip_track_forward + sushi_hip_track_backtrack for one sequence in NumPy (include/sushi_hip.h states the arithmetic):
     rows, a list of E >= 1 float32 arrays of one length n_shift >= 1 in event order; weights, E finite float64 values >= 0; penalty
@@ -231,10 +257,7 @@ def track_host(rows, weights, penalty, step_cost, reach, method="sqdiff_normed",
     moves = np.zeros((E, n), np.int16)
     D = None
     for e, (r, we) in enumerate(zip(rows, w)):
-        c = r.astype(np.float64)
-        if method == "ccoeff_normed":
-            c = -c
-        u = we * c
+        u = _unit_cost(r, we, method)
         if e == 0:
             D = u
         else:
@@ -360,10 +383,7 @@ def track_ordered_host(rows, weights, penalties, step_cost, reach, back, method=
     prefix_arg = np.empty((E, n), np.int32)
     D = P = None
     for e, (r, we) in enumerate(zip(rows, w)):
-        c = r.astype(np.float64)
-        if method == "ccoeff_normed":
-            c = -c
-        u = we * c
+        u = _unit_cost(r, we, method)
         if e == 0:
             D = u
         else:
@@ -423,10 +443,7 @@ def track_margins_host(rows, weights, penalty, step_cost, reach, guard, method="
     c_min = np.empty(E, np.float64)
     C = None
     for e in range(E - 1, -1, -1):
-        c = rows[e].astype(np.float64)
-        if method == "ccoeff_normed":
-            c = -c
-        u = w[e] * c
+        u = _unit_cost(rows[e], w[e], method)
         if e == E - 1:
             C, M[e] = u, D[e]
         else:
@@ -436,17 +453,7 @@ def track_margins_host(rows, weights, penalty, step_cost, reach, guard, method="
             M[e] = D[e] + B
             C = u + B
         c_min[e] = C[int(np.argmin(C))]
-    through = np.array([M[e, fwd.shifts[e]] for e in range(E)], np.float64)
-    best_arg = np.array([int(np.argmin(M[e])) for e in range(E)], np.int32)
-    best = np.array([M[e, best_arg[e]] for e in range(E)], np.float64)
-    alt, alt_arg = np.full(E, np.inf, np.float64), np.full(E, NO_ALT, np.int32)
-    j = np.arange(n, dtype=np.int64)
-    for e in range(E):
-        outside = np.abs(j - int(fwd.shifts[e])) > int(guard[e])
-        if outside.any():
-            at = int(np.argmin(np.where(outside, M[e], np.inf)))       # the first index of the minimum outside the window
-            alt[e], alt_arg[e] = M[e, at], at
-    return TrackMarginsHost(*(tuple(fwd) + (D, M, through, best, best_arg, alt, alt_arg, c_min)))
+    return TrackMarginsHost(*(tuple(fwd) + _margins_tail(fwd.shifts, D, M, guard, c_min)))
 
 
 def _suffix(C):
@@ -493,10 +500,7 @@ def track_ordered_margins_host(rows, weights, penalties, step_cost, reach, back,
     c_min = np.empty(E, np.float64)
     C = S = None
     for e in range(E - 1, -1, -1):
-        c = rows[e].astype(np.float64)
-        if method == "ccoeff_normed":
-            c = -c
-        u = w[e] * c
+        u = _unit_cost(rows[e], w[e], method)
         if e == E - 1:
             C, M[e] = u, D[e]
         else:
@@ -509,17 +513,7 @@ def track_ordered_margins_host(rows, weights, penalties, step_cost, reach, back,
         c_min[e] = S[0]
         if _trace is not None:
             _trace.append((e, C, S))
-    through = np.array([M[e, fwd.shifts[e]] for e in range(E)], np.float64)
-    best_arg = np.array([int(np.argmin(M[e])) for e in range(E)], np.int32)
-    best = np.array([M[e, best_arg[e]] for e in range(E)], np.float64)
-    alt, alt_arg = np.full(E, np.inf, np.float64), np.full(E, NO_ALT, np.int32)
-    j = np.arange(n, dtype=np.int64)
-    for e in range(E):
-        outside = np.abs(j - int(fwd.shifts[e])) > int(guard[e])
-        if outside.any():
-            at = int(np.argmin(np.where(outside, M[e], np.inf)))       # the first index of the minimum outside the window
-            alt[e], alt_arg[e] = M[e, at], at
-    return TrackOrderedMarginsHost(*(tuple(fwd) + (D, M, through, best, best_arg, alt, alt_arg, c_min)))
+    return TrackOrderedMarginsHost(*(tuple(fwd) + _margins_tail(fwd.shifts, D, M, guard, c_min)))
 
 
 def wide_workspace_bytes(n_shift):
@@ -629,7 +623,7 @@ def track_device(curves, rows, reach, penalty, step_cost, state, row0=0, method=
     chunk, with the bits of one call.  Asynchronous on hip_stream (default: the current torch stream of the device)."""
     if getattr(state, "keep", False):
         raise SushiError("track: a state that keeps its rows goes through track_forward_keep_device")
-    return _forward_device("sushi_hip_track_forward", curves, rows, reach, penalty, step_cost, state, row0, method, hip_stream)
+    return _forward_device(False, False, False, curves, rows, reach, penalty, step_cost, None, state, row0, method, hip_stream)
 
 
 def track_forward_keep_device(curves, rows, reach, penalty, step_cost, state, row0=0, method="sqdiff_normed", hip_stream=None):
@@ -637,7 +631,7 @@ def track_forward_keep_device(curves, rows, reach, penalty, step_cost, state, ro
     Everything else -- arguments, the other outputs and their bits, chunks -- is track_device's."""
     if not getattr(state, "keep", False):
         raise SushiError("track: track_forward_keep_device needs a TrackState(keep=True)")
-    return _forward_device("sushi_hip_track_forward_keep", curves, rows, reach, penalty, step_cost, state, row0, method, hip_stream)
+    return _forward_device(False, True, False, curves, rows, reach, penalty, step_cost, None, state, row0, method, hip_stream)
 
 
 def track_wide_device(curves, rows, reach, penalty, step_cost, state, row0=0, method="sqdiff_normed", hip_stream=None):
@@ -646,102 +640,14 @@ def track_wide_device(curves, rows, reach, penalty, step_cost, state, row0=0, me
     reach the outputs are track_device's bit for bit.  `state`: any TrackState that does not keep its rows."""
     if getattr(state, "keep", False):
         raise SushiError("track: a state that keeps its rows goes through track_wide_keep_device")
-    return _forward_device("sushi_hip_track_forward_wide", curves, rows, reach, penalty, step_cost, state, row0, method, hip_stream,
-                           wide=True)
+    return _forward_device(False, False, True, curves, rows, reach, penalty, step_cost, None, state, row0, method, hip_stream)
 
 
 def track_wide_keep_device(curves, rows, reach, penalty, step_cost, state, row0=0, method="sqdiff_normed", hip_stream=None):
     """track_forward_keep_device through sushi_hip_track_forward_wide_keep (track_wide_device's reaches)."""
     if not getattr(state, "keep", False):
         raise SushiError("track: track_wide_keep_device needs a TrackState(keep=True)")
-    return _forward_device("sushi_hip_track_forward_wide_keep", curves, rows, reach, penalty, step_cost, state, row0, method, hip_stream,
-                           wide=True)
-
-
-def track_wide_margins_device(curves, rows, reach, guard, penalty, step_cost, state, shifts, row0=0, method="sqdiff_normed",
-                              marginals=None, hip_stream=None):
-    """track_margins_device through sushi_hip_track_margins_wide (track_wide_device's reaches)."""
-    return track_margins_device(curves, rows, reach, guard, penalty, step_cost, state, shifts, row0=row0, method=method,
-                                marginals=marginals, hip_stream=hip_stream, _wide=True)
-
-
-def _forward_device(name, curves, rows, reach, penalty, step_cost, state, row0, method, hip_stream, wide=False):
-    from .device import _launch
-    if getattr(state, "ordered", False):
-        raise SushiError("track: a TrackState(ordered=True) goes through track_ordered_device")
-    axis.check_curves(curves, "track", device=state.D.device)
-    rt = axis.row_table(rows)
-    _w, lam, mu = _checked(rt["weight"], rt.shape[0], penalty, step_cost, method)
-    row0 = int(row0)
-    if row0 < 0 or row0 + rt.shape[0] > state.n_total:
-        raise SushiError("track: rows %d .. %d are not inside a sequence of %d" % (row0, row0 + rt.shape[0] - 1, state.n_total))
-    rc = np.ascontiguousarray(checked_reach(reach, rt.shape[0], first_row=row0, wide=wide))
-    if wide:
-        checked_wide_step_cost(rc, mu, first_row=row0)
-    axis.check_rows_inside(rt, int(curves.numel()), state.n_shift, "track")
-    L = _native.lib()
-    fn = getattr(L, name)
-    _launch(name, state.D.device, (L.sushi_hip_track_wide_bytes if wide else L.sushi_hip_track_bytes)(rt.shape[0], state.n_shift),
-            lambda mem, mem_bytes, st: fn(
-                curves.data_ptr(), int(curves.numel()), rt.ctypes.data, rc.ctypes.data, rt.shape[0], state.n_shift,
-                _native.METHODS[method], lam, mu, row0, state.n_total, state.D.data_ptr(), state.moves.data_ptr(),
-                state.row_min.data_ptr(), state.row_arg.data_ptr(), state.row_own_index.data_ptr(), state.row_own_scores.data_ptr(),
-                mem, mem_bytes, st),
-            (curves,) + state.tensors(), hip_stream)
-    return state
-
-
-def track_margins_device(curves, rows, reach, guard, penalty, step_cost, state, shifts, row0=0, method="sqdiff_normed", marginals=None,
-                         hip_stream=None, _wide=False):
-    """One call of sushi_hip_track_margins: rows row0 + len(rows) - 1 down to row0 of `state`'s sequence (a TrackState(keep=True) whose
-    every row has gone through track_forward_keep_device), `shifts` the int32 CUDA tensor track_backtrack_device returned.  rows[i] =
-    (curve_off, weight) and guard[i] are row row0 + i's (guard: an int, or one per row of the call); reach: an int, or one int per
-    row of the call and then the reach of row row0 + len(rows) where that row exists (the step out of the call's last row).  The
-    first call of a sequence ends at its last row; a later one continues downwards from what the call before it on the same stream
-    left in `state`, with the bits of one call.  marginals: a float64 CUDA tensor of n_total * n_shift values that receives M, or
-    None.  Fills rows row0 .. of state.c_min, through, best, best_arg, alt, alt_arg.  Asynchronous on hip_stream."""
-    from .device import _launch
-    import torch
-    if not getattr(state, "keep", False):
-        raise SushiError("track: track_margins_device needs a TrackState(keep=True)")
-    axis.check_curves(curves, "track", device=state.D.device)
-    rt = axis.row_table(rows)
-    n_rows = rt.shape[0]
-    _w, lam, mu = _checked(rt["weight"], n_rows, penalty, step_cost, method)
-    row0 = int(row0)
-    if row0 < 0 or row0 + n_rows > state.n_total:
-        raise SushiError("track: rows %d .. %d are not inside a sequence of %d" % (row0, row0 + n_rows - 1, state.n_total))
-    n_reach = n_rows + (1 if row0 + n_rows < state.n_total else 0)
-    if np.ndim(reach) == 0:
-        reach = [reach] * n_reach
-    reach = list(reach)
-    if len(reach) != n_reach:
-        raise SushiError("track: %d reaches for a margins call of %d rows that %s the sequence's last row (%d are needed)"
-                         % (len(reach), n_rows, "ends below" if n_reach > n_rows else "ends at", n_reach))
-    rc = np.ascontiguousarray(checked_reach([0] + reach[1:], n_reach, first_row=row0, wide=_wide))          # entry 0 is not used
-    if _wide:
-        checked_wide_step_cost(rc, mu, first_row=row0)
-    gd = np.ascontiguousarray(checked_guard(guard, n_rows, first_row=row0))
-    axis.check_rows_inside(rt, int(curves.numel()), state.n_shift, "track")
-    if not (isinstance(shifts, torch.Tensor) and shifts.is_cuda and shifts.dtype == torch.int32 and shifts.is_contiguous()
-            and shifts.numel() == state.n_total and shifts.device == state.D.device):
-        raise SushiError("track: shifts is the backtrack's output, an int32 CUDA tensor of %d values" % state.n_total)
-    if marginals is not None and not (isinstance(marginals, torch.Tensor) and marginals.is_cuda and marginals.dtype == torch.float64
-                                      and marginals.is_contiguous() and marginals.numel() == state.n_total * state.n_shift
-                                      and marginals.device == state.D.device):
-        raise SushiError("track: marginals is a contiguous float64 CUDA tensor of %d x %d values" % (state.n_total, state.n_shift))
-    L = _native.lib()
-    name = "sushi_hip_track_margins_wide" if _wide else "sushi_hip_track_margins"
-    fn = getattr(L, name)
-    _launch(name, state.D.device, (L.sushi_hip_track_margins_wide_bytes if _wide else L.sushi_hip_track_margins_bytes)(n_rows, state.n_shift),
-            lambda mem, mem_bytes, st: fn(
-                curves.data_ptr(), int(curves.numel()), rt.ctypes.data, rc.ctypes.data, gd.ctypes.data, n_rows, state.n_shift,
-                _native.METHODS[method], lam, mu, row0, state.n_total, state.D.data_ptr(), shifts.data_ptr(), state.C.data_ptr(),
-                state.c_min.data_ptr(), state.through.data_ptr(), state.best.data_ptr(), state.best_arg.data_ptr(),
-                state.alt.data_ptr(), state.alt_arg.data_ptr(), None if marginals is None else marginals.data_ptr(),
-                mem, mem_bytes, st),
-            (curves, shifts, state.D) + state.margin_tensors() + (() if marginals is None else (marginals,)), hip_stream)
-    return state
+    return _forward_device(False, True, True, curves, rows, reach, penalty, step_cost, None, state, row0, method, hip_stream)
 
 
 def track_ordered_device(curves, rows, reach, penalties, step_cost, back, state, row0=0, method="sqdiff_normed", hip_stream=None):
@@ -754,8 +660,7 @@ def track_ordered_device(curves, rows, reach, penalties, step_cost, back, state,
         raise SushiError("track: track_ordered_device needs a TrackState(ordered=True)")
     if getattr(state, "margins", False):
         raise SushiError("track: a state that keeps its rows goes through track_ordered_keep_device")
-    return _forward_ordered_device("sushi_hip_track_forward_ordered", curves, rows, reach, penalties, step_cost, back, state, row0, method,
-                                   hip_stream)
+    return _forward_device(True, False, False, curves, rows, reach, penalties, step_cost, back, state, row0, method, hip_stream)
 
 
 def track_ordered_keep_device(curves, rows, reach, penalties, step_cost, back, state, row0=0, method="sqdiff_normed", hip_stream=None):
@@ -763,8 +668,7 @@ def track_ordered_keep_device(curves, rows, reach, penalties, step_cost, back, s
     e of its D is D_e afterwards.  Everything else -- arguments, the other outputs and their bits, chunks -- is track_ordered_device's."""
     if not (getattr(state, "ordered", False) and getattr(state, "margins", False)):
         raise SushiError("track: track_ordered_keep_device needs a TrackState(ordered=True, margins=True)")
-    return _forward_ordered_device("sushi_hip_track_forward_ordered_keep", curves, rows, reach, penalties, step_cost, back, state, row0,
-                                   method, hip_stream)
+    return _forward_device(True, True, False, curves, rows, reach, penalties, step_cost, back, state, row0, method, hip_stream)
 
 
 def track_ordered_wide_device(curves, rows, reach, penalties, step_cost, back, state, row0=0, method="sqdiff_normed", hip_stream=None):
@@ -776,8 +680,7 @@ def track_ordered_wide_device(curves, rows, reach, penalties, step_cost, back, s
         raise SushiError("track: track_ordered_wide_device needs a TrackState(ordered=True)")
     if getattr(state, "margins", False):
         raise SushiError("track: a state that keeps its rows goes through track_ordered_wide_keep_device")
-    return _forward_ordered_device("sushi_hip_track_forward_ordered_wide", curves, rows, reach, penalties, step_cost, back, state, row0,
-                                   method, hip_stream, wide=True)
+    return _forward_device(True, False, True, curves, rows, reach, penalties, step_cost, back, state, row0, method, hip_stream)
 
 
 def track_ordered_wide_keep_device(curves, rows, reach, penalties, step_cost, back, state, row0=0, method="sqdiff_normed",
@@ -785,42 +688,65 @@ def track_ordered_wide_keep_device(curves, rows, reach, penalties, step_cost, ba
     """track_ordered_keep_device through sushi_hip_track_forward_ordered_wide_keep (track_ordered_wide_device's reaches)."""
     if not (getattr(state, "ordered", False) and getattr(state, "margins", False)):
         raise SushiError("track: track_ordered_wide_keep_device needs a TrackState(ordered=True, margins=True)")
-    return _forward_ordered_device("sushi_hip_track_forward_ordered_wide_keep", curves, rows, reach, penalties, step_cost, back, state,
-                                   row0, method, hip_stream, wide=True)
+    return _forward_device(True, True, True, curves, rows, reach, penalties, step_cost, back, state, row0, method, hip_stream)
 
 
-def track_ordered_wide_margins_device(curves, rows, reach, guard, penalties, step_cost, back, state, shifts, row0=0,
-                                      method="sqdiff_normed", marginals=None, hip_stream=None):
-    """track_ordered_margins_device through sushi_hip_track_order_margins_wide (track_ordered_wide_device's reaches)."""
-    return track_ordered_margins_device(curves, rows, reach, guard, penalties, step_cost, back, state, shifts, row0=row0, method=method,
-                                        marginals=marginals, hip_stream=hip_stream, _wide=True)
-
-
-def _forward_ordered_device(name, curves, rows, reach, penalties, step_cost, back, state, row0, method, hip_stream, wide=False):
+def _forward_device(ordered, keep, wide, curves, rows, reach, penalty, step_cost, back, state, row0, method, hip_stream):
+    """The forward launcher: one call of sushi_hip_track_forward[_ordered][_wide][_keep].  ordered: penalty is the call's penalties
+    and back its backs (plain: one penalty, no back); wide: the reach's bound, the free-move condition and the workspace are the
+    wide call's."""
     from .device import _launch
+    if not ordered and getattr(state, "ordered", False):
+        raise SushiError("track: a TrackState(ordered=True) goes through track_ordered_device")
     axis.check_curves(curves, "track", device=state.D.device)
     rt = axis.row_table(rows)
     n_rows = rt.shape[0]
-    _w, _lam, mu = _checked(rt["weight"], n_rows, 0.0, step_cost, method)
+    _w, lam, mu = _checked(rt["weight"], n_rows, 0.0 if ordered else penalty, step_cost, method)
     row0 = int(row0)
     if row0 < 0 or row0 + n_rows > state.n_total:
         raise SushiError("track: rows %d .. %d are not inside a sequence of %d" % (row0, row0 + n_rows - 1, state.n_total))
     rc = np.ascontiguousarray(checked_reach(reach, n_rows, first_row=row0, wide=wide))
     if wide:
         checked_wide_step_cost(rc, mu, first_row=row0)
-    pc = np.ascontiguousarray(checked_penalties(penalties, n_rows, first_row=row0))
-    bc = np.ascontiguousarray(checked_back(back, n_rows, first_row=row0))
+    tables, outputs = (rc,), state.tensors()
+    if ordered:
+        pc = np.ascontiguousarray(checked_penalties(penalty, n_rows, first_row=row0))
+        tables += (np.ascontiguousarray(checked_back(back, n_rows, first_row=row0)),)
+        outputs = outputs[:2] + state.order_tensors() + outputs[2:]        # D, moves; P, A, back; the per-row outputs
+        lam = pc.ctypes.data                                               # the penalty argument: a table, not one number
     axis.check_rows_inside(rt, int(curves.numel()), state.n_shift, "track")
     L = _native.lib()
+    name = "sushi_hip_track_forward%s%s%s" % ("_ordered" if ordered else "", "_wide" if wide else "", "_keep" if keep else "")
     fn = getattr(L, name)
-    _launch(name, state.D.device, (L.sushi_hip_track_order_wide_bytes if wide else L.sushi_hip_track_order_bytes)(n_rows, state.n_shift),
+    bytes_fn = getattr(L, "sushi_hip_track%s%s_bytes" % ("_order" if ordered else "", "_wide" if wide else ""))
+    _launch(name, state.D.device, bytes_fn(n_rows, state.n_shift),
             lambda mem, mem_bytes, st: fn(
-                curves.data_ptr(), int(curves.numel()), rt.ctypes.data, rc.ctypes.data, bc.ctypes.data, n_rows, state.n_shift,
-                _native.METHODS[method], pc.ctypes.data, mu, row0, state.n_total, state.D.data_ptr(), state.moves.data_ptr(),
-                state.P.data_ptr(), state.prefix_arg.data_ptr(), state.back.data_ptr(), state.row_min.data_ptr(),
-                state.row_arg.data_ptr(), state.row_own_index.data_ptr(), state.row_own_scores.data_ptr(), mem, mem_bytes, st),
-            (curves,) + state.tensors() + state.order_tensors(), hip_stream)
+                curves.data_ptr(), int(curves.numel()), rt.ctypes.data, *[t.ctypes.data for t in tables], n_rows, state.n_shift,
+                _native.METHODS[method], lam, mu, row0, state.n_total, *[t.data_ptr() for t in outputs], mem, mem_bytes, st),
+            (curves,) + state.tensors() + (state.order_tensors() if ordered else ()), hip_stream)
     return state
+
+
+def track_margins_device(curves, rows, reach, guard, penalty, step_cost, state, shifts, row0=0, method="sqdiff_normed", marginals=None,
+                         hip_stream=None, _wide=False):
+    """One call of sushi_hip_track_margins: rows row0 + len(rows) - 1 down to row0 of `state`'s sequence (a TrackState(keep=True) whose
+    every row has gone through track_forward_keep_device), `shifts` the int32 CUDA tensor track_backtrack_device returned.  rows[i] =
+    (curve_off, weight) and guard[i] are row row0 + i's (guard: an int, or one per row of the call); reach: an int, or one int per
+    row of the call and then the reach of row row0 + len(rows) where that row exists (the step out of the call's last row).  The
+    first call of a sequence ends at its last row; a later one continues downwards from what the call before it on the same stream
+    left in `state`, with the bits of one call.  marginals: a float64 CUDA tensor of n_total * n_shift values that receives M, or
+    None.  Fills rows row0 .. of state.c_min, through, best, best_arg, alt, alt_arg.  Asynchronous on hip_stream."""
+    if not getattr(state, "keep", False):
+        raise SushiError("track: track_margins_device needs a TrackState(keep=True)")
+    return _margins_device(False, _wide, curves, rows, reach, guard, penalty, step_cost, None, state, shifts, row0, method, marginals,
+                           hip_stream)
+
+
+def track_wide_margins_device(curves, rows, reach, guard, penalty, step_cost, state, shifts, row0=0, method="sqdiff_normed",
+                              marginals=None, hip_stream=None):
+    """track_margins_device through sushi_hip_track_margins_wide (track_wide_device's reaches)."""
+    return track_margins_device(curves, rows, reach, guard, penalty, step_cost, state, shifts, row0=row0, method=method,
+                                marginals=marginals, hip_stream=hip_stream, _wide=True)
 
 
 def track_ordered_margins_device(curves, rows, reach, guard, penalties, step_cost, back, state, shifts, row0=0, method="sqdiff_normed",
@@ -832,14 +758,30 @@ def track_ordered_margins_device(curves, rows, reach, guard, penalties, step_cos
     0 is not used.  The first call of a sequence ends at its last row; a later one continues downwards from what the call before it on
     the same stream left in `state` (C and S), with the bits of one call.  Fills rows row0 .. of state.c_min, through, best, best_arg,
     alt, alt_arg, and of marginals where given.  Three launches per row.  Asynchronous on hip_stream."""
-    from .device import _launch
-    import torch
     if not (getattr(state, "ordered", False) and getattr(state, "margins", False)):
         raise SushiError("track: track_ordered_margins_device needs a TrackState(ordered=True, margins=True)")
+    return _margins_device(True, _wide, curves, rows, reach, guard, penalties, step_cost, back, state, shifts, row0, method, marginals,
+                           hip_stream)
+
+
+def track_ordered_wide_margins_device(curves, rows, reach, guard, penalties, step_cost, back, state, shifts, row0=0,
+                                      method="sqdiff_normed", marginals=None, hip_stream=None):
+    """track_ordered_margins_device through sushi_hip_track_order_margins_wide (track_ordered_wide_device's reaches)."""
+    return track_ordered_margins_device(curves, rows, reach, guard, penalties, step_cost, back, state, shifts, row0=row0, method=method,
+                                        marginals=marginals, hip_stream=hip_stream, _wide=True)
+
+
+def _margins_device(ordered, wide, curves, rows, reach, guard, penalty, step_cost, back, state, shifts, row0, method, marginals,
+                    hip_stream):
+    """The margins launcher: one call of sushi_hip_track[_order]_margins[_wide].  What is given per row -- reach, and with `ordered`
+    penalty and back -- is a single value, or one per row of the call and then that of row row0 + len(rows) where that row exists:
+    entries 1 .. n_after are used, entry 0 is not."""
+    from .device import _launch
+    import torch
     axis.check_curves(curves, "track", device=state.D.device)
     rt = axis.row_table(rows)
     n_rows = rt.shape[0]
-    _w, _lam, mu = _checked(rt["weight"], n_rows, 0.0, step_cost, method)
+    _w, lam, mu = _checked(rt["weight"], n_rows, 0.0 if ordered else penalty, step_cost, method)
     row0 = int(row0)
     if row0 < 0 or row0 + n_rows > state.n_total:
         raise SushiError("track: rows %d .. %d are not inside a sequence of %d" % (row0, row0 + n_rows - 1, state.n_total))
@@ -852,12 +794,16 @@ def track_ordered_margins_device(curves, rows, reach, guard, penalties, step_cos
                              % (len(values), what, n_rows, "ends below" if n_after > n_rows else "ends at", n_after))
         return [fill] + values[1:]                                                              # entry 0 is not used
 
-    rc = np.ascontiguousarray(checked_reach(per_row(reach, "reaches", 0), n_after, first_row=row0, wide=_wide))
-    if _wide:
+    rc = np.ascontiguousarray(checked_reach(per_row(reach, "reaches", 0), n_after, first_row=row0, wide=wide))
+    if wide:
         checked_wide_step_cost(rc, mu, first_row=row0)
-    pc = np.ascontiguousarray(checked_penalties(per_row(penalties, "penalties", 0.0), n_after, first_row=row0))
-    bc = np.ascontiguousarray(checked_back(per_row(back, "backs", BACK_ANY), n_after, first_row=row0))
-    gd = np.ascontiguousarray(checked_guard(guard, n_rows, first_row=row0))
+    tables, held = (rc,), (state.C,)
+    if ordered:
+        pc = np.ascontiguousarray(checked_penalties(per_row(penalty, "penalties", 0.0), n_after, first_row=row0))
+        tables += (np.ascontiguousarray(checked_back(per_row(back, "backs", BACK_ANY), n_after, first_row=row0)),)
+        held += (state.S,)
+        lam = pc.ctypes.data                                               # the penalty argument: a table, not one number
+    tables += (np.ascontiguousarray(checked_guard(guard, n_rows, first_row=row0)),)
     axis.check_rows_inside(rt, int(curves.numel()), state.n_shift, "track")
     if not (isinstance(shifts, torch.Tensor) and shifts.is_cuda and shifts.dtype == torch.int32 and shifts.is_contiguous()
             and shifts.numel() == state.n_total and shifts.device == state.D.device):
@@ -867,48 +813,43 @@ def track_ordered_margins_device(curves, rows, reach, guard, penalties, step_cos
                                       and marginals.device == state.D.device):
         raise SushiError("track: marginals is a contiguous float64 CUDA tensor of %d x %d values" % (state.n_total, state.n_shift))
     L = _native.lib()
-    name = "sushi_hip_track_order_margins_wide" if _wide else "sushi_hip_track_order_margins"
+    name = "sushi_hip_track%s_margins%s" % ("_order" if ordered else "", "_wide" if wide else "")
     fn = getattr(L, name)
-    _launch(name, state.D.device,
-            (L.sushi_hip_track_order_margins_wide_bytes if _wide else L.sushi_hip_track_order_margins_bytes)(n_rows, state.n_shift),
+    outputs = held + state.margin_tensors()[1:]                                                  # C (, S); c_min .. alt_arg
+    _launch(name, state.D.device, getattr(L, name + "_bytes")(n_rows, state.n_shift),
             lambda mem, mem_bytes, st: fn(
-                curves.data_ptr(), int(curves.numel()), rt.ctypes.data, rc.ctypes.data, bc.ctypes.data, gd.ctypes.data, n_rows,
-                state.n_shift, _native.METHODS[method], pc.ctypes.data, mu, row0, state.n_total, state.D.data_ptr(), shifts.data_ptr(),
-                state.C.data_ptr(), state.S.data_ptr(), state.c_min.data_ptr(), state.through.data_ptr(), state.best.data_ptr(),
-                state.best_arg.data_ptr(), state.alt.data_ptr(), state.alt_arg.data_ptr(),
-                None if marginals is None else marginals.data_ptr(), mem, mem_bytes, st),
-            (curves, shifts, state.D, state.S) + state.margin_tensors() + (() if marginals is None else (marginals,)), hip_stream)
+                curves.data_ptr(), int(curves.numel()), rt.ctypes.data, *[t.ctypes.data for t in tables], n_rows, state.n_shift,
+                _native.METHODS[method], lam, mu, row0, state.n_total, state.D.data_ptr(), shifts.data_ptr(),
+                *[t.data_ptr() for t in outputs], None if marginals is None else marginals.data_ptr(), mem, mem_bytes, st),
+            (curves, shifts, state.D) + held[1:] + state.margin_tensors() + (() if marginals is None else (marginals,)), hip_stream)
     return state
-
-
-def track_ordered_backtrack_device(state, hip_stream=None):
-    """sushi_hip_track_backtrack_ordered over `state` once every row has gone through track_ordered_device on the same stream: the
-    shift index of every row, an int32 CUDA tensor."""
-    import torch
-    from .device import _launch
-    if not getattr(state, "ordered", False):
-        raise SushiError("track: track_ordered_backtrack_device needs a TrackState(ordered=True)")
-    L = _native.lib()
-    out = torch.empty(state.n_total, dtype=torch.int32, device=state.D.device)
-    _launch("sushi_hip_track_backtrack_ordered", state.D.device, None,
-            lambda _mem, _mem_bytes, st: L.sushi_hip_track_backtrack_ordered(
-                state.moves.data_ptr(), state.prefix_arg.data_ptr(), state.back.data_ptr(), state.row_arg.data_ptr(), state.n_total,
-                state.n_shift, out.data_ptr(), st),
-            (state.moves, state.prefix_arg, state.back, state.row_arg, out), hip_stream)
-    return out
 
 
 def track_backtrack_device(state, hip_stream=None):
     """sushi_hip_track_backtrack over `state` once every row has gone through track_device on the same stream: the shift index of
     every row, an int32 CUDA tensor."""
+    return _backtrack_device(False, state, hip_stream)
+
+
+def track_ordered_backtrack_device(state, hip_stream=None):
+    """sushi_hip_track_backtrack_ordered over `state` once every row has gone through track_ordered_device on the same stream: the
+    shift index of every row, an int32 CUDA tensor."""
+    if not getattr(state, "ordered", False):
+        raise SushiError("track: track_ordered_backtrack_device needs a TrackState(ordered=True)")
+    return _backtrack_device(True, state, hip_stream)
+
+
+def _backtrack_device(ordered, state, hip_stream):
+    """The backtrack launcher: one call of sushi_hip_track_backtrack[_ordered] (ordered: A and the backs are read as well)."""
     import torch
     from .device import _launch
-    L = _native.lib()
+    name = "sushi_hip_track_backtrack" + ("_ordered" if ordered else "")
+    fn = getattr(_native.lib(), name)
     out = torch.empty(state.n_total, dtype=torch.int32, device=state.D.device)
-    _launch("sushi_hip_track_backtrack", state.D.device, None,
-            lambda _mem, _mem_bytes, st: L.sushi_hip_track_backtrack(state.moves.data_ptr(), state.row_arg.data_ptr(), state.n_total,
-                                                                     state.n_shift, out.data_ptr(), st),
-            (state.moves, state.row_arg, out), hip_stream)
+    read = (state.moves,) + ((state.prefix_arg, state.back) if ordered else ()) + (state.row_arg,)
+    _launch(name, state.D.device, None,
+            lambda _mem, _mem_bytes, st: fn(*[t.data_ptr() for t in read], state.n_total, state.n_shift, out.data_ptr(), st),
+            read + (out,), hip_stream)
     return out
 
 
@@ -975,16 +916,8 @@ def find_track(stream, patterns, window_centers, window_size, penalty, max_rate=
                guard=None, marginals=False, clamp=None, capacity=None, order=None, wide=False):
     """WavStream.find_track (its docstring)."""
     wide = bool(wide)
-    import torch
-    from .curves import match_curves
-    patterns, centres = list(patterns), list(window_centers)
-    if not patterns or len(patterns) != len(centres):
-        raise SushiError("find_track: equally many patterns and centres (>= 1)")
-    if (max_rate is None) == (reach is None):
-        raise SushiError("find_track: exactly one of max_rate and reach")
-    margins, marginals = bool(margins), bool(marginals)
-    if not margins and (marginals or guard is not None):
-        raise SushiError("find_track: guard and marginals belong to margins=True")
+    patterns, centres, margins, marginals = _checked_search("find_track", patterns, window_centers, max_rate, reach, margins, guard,
+                                                            marginals)
     # the ordered pass is taken only when it is asked for; otherwise the code path, the launches and the bits are those of before
     order = None if order is False else order
     ordered = order is not None or (penalty is not None and np.ndim(penalty) != 0)
@@ -995,83 +928,8 @@ def find_track(stream, patterns, window_centers, window_size, penalty, max_rate=
         if margins:
             raise SushiError("find_track: margins of the ordered pass (order=, a penalty per event) are not built: its backward "
                              "recurrence needs the mirrored suffix minimum")
-        return _find_track_ordered(stream, patterns, centres, window_size, penalty, max_rate, reach, step_cost, slack, weights, method,
-                                   max_bytes, max_state_bytes, clamp, capacity, order)
-    f, capacity = axis.checked_clamp(clamp, capacity, method)
-    dst_dev = stream.device_stream()
-    src_dev, offs, lens, _ = stream._pattern_source(patterns, dst_dev)
-    lens = axis.pattern_lengths(lens)
-    E = len(patterns)
-    w, lam, mu = _checked(axis.event_weights(weights, lens, per_event=True), E, penalty, step_cost, method)
-    ax = axis.event_axis(stream, offs, lens, centres, window_size)
-    k_lo, n_shift, rate = ax.k_lo, ax.n_shift, stream.sample_rate
-    reach = checked_reach(rate_reach(ax.bases, max_rate, slack) if reach is None else reach, E, wide=wide)
-    if wide:
-        checked_wide_step_cost(reach, mu)
-    if margins:
-        guard = checked_guard(int(0.01 * rate) if guard is None else guard, E)
-    need = TrackState.nbytes(E, n_shift, keep=margins, marginals=marginals, wide=wide)
-    if need > max_state_bytes:
-        records = ", a wide call's window records" if wide else ""
-        if margins:
-            raise SushiError("find_track: %d events x %d shifts need %d bytes of moves, kept costs%s%s, max_state_bytes is %d (%d "
-                             "without margins)" % (E, n_shift, need, " and marginals" if marginals else "", records, max_state_bytes,
-                                                   TrackState.nbytes(E, n_shift, wide=wide)))
-        raise SushiError("find_track: %d events x %d shifts need %d bytes of moves and costs%s, max_state_bytes is %d"
-                         % (E, n_shift, need, records, max_state_bytes))
-    per_chunk = int(max_bytes) // (4 * n_shift)
-    if per_chunk < 1:
-        raise SushiError("find_track: one event of %d shifts needs %d bytes of curves, max_bytes is %d"
-                         % (n_shift, 4 * n_shift, max_bytes))
-    state = TrackState(E, n_shift, dst_dev.device, keep=margins, wide=wide)
-    if wide:
-        forward, margins_device = (track_wide_keep_device if margins else track_wide_device), track_wide_margins_device
-    else:
-        forward, margins_device = (track_forward_keep_device if margins else track_device), track_margins_device
-    chunks = [(first, min(E, first + per_chunk)) for first in range(0, E, per_chunk)]
-    rows_info = [None]
-
-    def form(first, last):
-        info = {}
-        formed = axis.event_rows(dst_dev, src_dev, [ax.part(first, last)], method, clamp=f, capacity=capacity, info=info)
-        if f is not None:
-            rows_info[0] = axis.merge_rows_info(rows_info[0], info)
-        return formed
-
-    for first, last in chunks:
-        curves, row_off = form(first, last)
-        forward(curves, zip(row_off, w[first:last].tolist()), reach[first:last], lam, mu, state, row0=first, method=method)
-    index_dev = track_backtrack_device(state)
-    extra = dict(guard=None, event_through=None, event_margin=None, event_alt_shift=None, event_alt_delta=None, marginals=None)
-    if margins:
-        # the chunks again, from the last one down: a lone chunk's curves are still there, several chunks' are formed a second time
-        M = torch.empty(E * n_shift, dtype=torch.float64, device=state.D.device) if marginals else None
-        for first, last in reversed(chunks):
-            if len(chunks) > 1:
-                curves, row_off = form(first, last)
-            margins_device(curves, zip(row_off, w[first:last].tolist()), reach[first:last + 1 if last < E else last],
-                           guard[first:last], lam, mu, state, index_dev, row0=first, method=method, marginals=M)
-        through, alt, alt_arg = state.through.cpu().numpy(), state.alt.cpu().numpy(), state.alt_arg.cpu().numpy()
-        alt_shift = [None if int(k) == NO_ALT else k_lo + int(k) for k in alt_arg]
-        extra = dict(guard=guard.tolist(), event_through=through,
-                     event_margin=np.where(alt_arg == NO_ALT, np.inf, alt - through), event_alt_shift=alt_shift,
-                     event_alt_delta=[None if k is None else k / float(rate) for k in alt_shift],
-                     marginals=None if M is None else M.view(E, n_shift))
-    index = index_dev.cpu().numpy()
-    # the move word every event was entered by: row e's, at its chosen shift (E reads of the device array, gathered there)
-    words = state.moves[index_dev.long() + n_shift * _arange_like(index_dev)].cpu().numpy()
-    shifts = [k_lo + int(k) for k in index]
-    jumps = [e for e in range(1, E) if int(words[e]) == JUMP]
-    # every event's score at its chosen shift: curves are exact per position, so these are the bits of its row there
-    at, _ = match_curves(dst_dev, src_dev, ax.offs, lens, [b + k for b, k in zip(ax.bases, shifts)], [1] * E, method=method)
-    own = state.row_own_index.cpu().numpy()
-    return Track(
-        k_lo=k_lo, n_shift=n_shift, shifts=shifts, deltas=[k / float(rate) for k in shifts], reach=reach.tolist(),
-        moves=[0] + [b - a for a, b in zip(shifts[:-1], shifts[1:])], jumps=jumps,
-        segments=[(f, n, shifts[f] / float(rate), shifts[f + n - 1] / float(rate)) for f, n in jump_runs(E, jumps)],
-        cost=float(state.row_min[E - 1].item()), event_scores=at.cpu().numpy(),
-        event_own_delta=[(k_lo + int(k)) / float(rate) for k in own], event_own_scores=state.row_own_scores.cpu().numpy(),
-        clamp=None if f is None else float(f), rows_info=rows_info[0], back=None, penalties=None, **extra)
+    return _search("find_track", ordered, wide, stream, patterns, centres, window_size, penalty, order, max_rate, reach, step_cost, slack,
+                   weights, method, max_bytes, max_state_bytes, margins, guard, marginals, clamp, capacity)
 
 
 def find_ordered_track(stream, patterns, window_centers, window_size, penalty, order=None, max_rate=None, reach=None, step_cost=0.0,
@@ -1095,7 +953,13 @@ def find_ordered_wide_track(stream, patterns, window_centers, window_size, penal
 
 def _find_ordered(name, wide, stream, patterns, window_centers, window_size, penalty, order, max_rate, reach, step_cost, slack, weights,
                   method, max_bytes, max_state_bytes, margins, guard, marginals, clamp, capacity):
-    """What find_ordered_track and find_ordered_wide_track share in front of the search: the checks of their own arguments."""
+    patterns, centres, margins, marginals = _checked_search(name, patterns, window_centers, max_rate, reach, margins, guard, marginals)
+    return _search(name, True, wide, stream, patterns, centres, window_size, penalty, None if order is False else order, max_rate, reach,
+                   step_cost, slack, weights, method, max_bytes, max_state_bytes, margins, guard, marginals, clamp, capacity)
+
+
+def _checked_search(name, patterns, window_centers, max_rate, reach, margins, guard, marginals):
+    """What every find_* checks first about its own arguments: (patterns, centres, margins, marginals)."""
     patterns, centres = list(patterns), list(window_centers)
     if not patterns or len(patterns) != len(centres):
         raise SushiError("%s: equally many patterns and centres (>= 1)" % name)
@@ -1104,19 +968,17 @@ def _find_ordered(name, wide, stream, patterns, window_centers, window_size, pen
     margins, marginals = bool(margins), bool(marginals)
     if not margins and (marginals or guard is not None):
         raise SushiError("%s: guard and marginals belong to margins=True" % name)
-    return _find_track_ordered(stream, patterns, centres, window_size, penalty, max_rate, reach, step_cost, slack, weights, method,
-                               max_bytes, max_state_bytes, clamp, capacity, None if order is False else order, margins=margins,
-                               guard=guard, marginals=marginals, name=name, **({"wide": True} if wide else {}))
+    return patterns, centres, margins, marginals
 
 
-def _find_track_ordered(stream, patterns, centres, window_size, penalty, max_rate, reach, step_cost, slack, weights, method, max_bytes,
-                        max_state_bytes, clamp, capacity, order, margins=False, guard=None, marginals=False, name="find_track",
-                        wide=False):
-    """find_track through the ordered pass: order None (every back without a limit: a penalty per event alone), True (order_back of
-    the events) or one back per event; penalty a number or one per event.  margins (find_ordered_track alone): the rows of the
-    forward pass are kept, and after the backtrack the chunks are walked again from the last one down (find_track(margins=True)'s
-    shape).  wide (find_ordered_wide_track alone): the reach's bound is WIDE_MAX_REACH, the calls are the wide ordered ones, and the
-    state's count holds a wide call's window records."""
+def _search(name, ordered, wide, stream, patterns, centres, window_size, penalty, order, max_rate, reach, step_cost, slack, weights,
+            method, max_bytes, max_state_bytes, margins, guard, marginals, clamp, capacity):
+    """The search behind find_track, find_ordered_track and find_ordered_wide_track: per chunk of events one match_curves call and
+    one forward call, then one backtrack; with margins the rows of the forward pass are kept, and the chunks are walked again from
+    the last one down.  ordered: penalty is a number or one per event, and order None (every back without a limit: a penalty per
+    event alone), True (order_back of the events) or one back per event; the state holds the jump sources, and the record the backs
+    and the penalties.  wide: the reach's bound is WIDE_MAX_REACH, the calls are the wide ones, and the state's count holds a wide
+    call's window records."""
     import torch
     from .curves import match_curves
     f, capacity = axis.checked_clamp(clamp, capacity, method)
@@ -1124,60 +986,75 @@ def _find_track_ordered(stream, patterns, centres, window_size, penalty, max_rat
     src_dev, offs, lens, _ = stream._pattern_source(patterns, dst_dev)
     lens = axis.pattern_lengths(lens)
     E = len(patterns)
-    w, _lam, mu = _checked(axis.event_weights(weights, lens, per_event=True), E, 0.0, step_cost, method)
-    lam = checked_penalties(penalty, E)
+    w, lam, mu = _checked(axis.event_weights(weights, lens, per_event=True), E, 0.0 if ordered else penalty, step_cost, method)
+    if ordered:
+        lam = checked_penalties(penalty, E)
     ax = axis.event_axis(stream, offs, lens, centres, window_size)
     k_lo, n_shift, rate = ax.k_lo, ax.n_shift, stream.sample_rate
     reach = checked_reach(rate_reach(ax.bases, max_rate, slack) if reach is None else reach, E, wide=wide)
     if wide:
         checked_wide_step_cost(reach, mu)
-    back = checked_back(None if order is None else (order_back(ax.bases, lens) if order is True else order), E)
-    back[0] = BACK_ANY
+    back = None
+    if ordered:
+        back = checked_back(None if order is None else (order_back(ax.bases, lens) if order is True else order), E)
+        back[0] = BACK_ANY
     if margins:
         guard = checked_guard(int(0.01 * rate) if guard is None else guard, E)
-    state_bytes = ordered_wide_state_bytes if wide else (lambda *a, **k: TrackState.nbytes(*a, ordered=True, **k))
-    records = ", a wide call's window records" if wide else ""
-    need = state_bytes(E, n_shift, margins=margins, marginals=marginals)
+
+    def state_bytes(margins=False, marginals=False):
+        if not ordered:
+            return TrackState.nbytes(E, n_shift, keep=margins, marginals=marginals, wide=wide)
+        return (ordered_wide_state_bytes(E, n_shift, margins=margins, marginals=marginals) if wide else
+                TrackState.nbytes(E, n_shift, ordered=True, margins=margins, marginals=marginals))
+
+    need = state_bytes(margins, marginals)
     if need > max_state_bytes:
+        held = "moves, jump sources" if ordered else "moves"
+        records = ", a wide call's window records" if wide else ""
         if margins:
-            raise SushiError("%s: %d events x %d shifts need %d bytes of moves, jump sources, kept costs%s%s, max_state_bytes is %d (%d "
-                             "without margins)" % (name, E, n_shift, need, " and marginals" if marginals else "", records,
-                                                   max_state_bytes, state_bytes(E, n_shift)))
-        raise SushiError("%s: %d events x %d shifts need %d bytes of moves, jump sources and costs%s, max_state_bytes is %d"
-                         % (name, E, n_shift, need, records, max_state_bytes))
+            raise SushiError("%s: %d events x %d shifts need %d bytes of %s, kept costs%s%s, max_state_bytes is %d (%d "
+                             "without margins)" % (name, E, n_shift, need, held, " and marginals" if marginals else "", records,
+                                                   max_state_bytes, state_bytes()))
+        raise SushiError("%s: %d events x %d shifts need %d bytes of %s and costs%s, max_state_bytes is %d"
+                         % (name, E, n_shift, need, held, records, max_state_bytes))
     per_chunk = int(max_bytes) // (4 * n_shift)
     if per_chunk < 1:
         raise SushiError("%s: one event of %d shifts needs %d bytes of curves, max_bytes is %d"
                          % (name, n_shift, 4 * n_shift, max_bytes))
-    state = TrackState(E, n_shift, dst_dev.device, ordered=True, margins=margins)
-    if wide:
-        forward, margins_device = (track_ordered_wide_keep_device if margins else track_ordered_wide_device), track_ordered_wide_margins_device
+    if ordered:
+        state = TrackState(E, n_shift, dst_dev.device, ordered=True, margins=margins)
     else:
-        forward, margins_device = (track_ordered_keep_device if margins else track_ordered_device), track_ordered_margins_device
+        state = TrackState(E, n_shift, dst_dev.device, keep=margins, wide=wide)
     chunks = [(first, min(E, first + per_chunk)) for first in range(0, E, per_chunk)]
-    rows_info = None
-    for first, last in chunks:
+    rows_info = [None]
+
+    def form(first, last):
         info = {}
-        curves, row_off = axis.event_rows(dst_dev, src_dev, [ax.part(first, last)], method, clamp=f, capacity=capacity, info=info)
+        formed = axis.event_rows(dst_dev, src_dev, [ax.part(first, last)], method, clamp=f, capacity=capacity, info=info)
         if f is not None:
-            rows_info = axis.merge_rows_info(rows_info, info)
-        forward(curves, zip(row_off, w[first:last].tolist()), reach[first:last], lam[first:last], mu, back[first:last],
-                state, row0=first, method=method)
-    index_dev = track_ordered_backtrack_device(state)
+            rows_info[0] = axis.merge_rows_info(rows_info[0], info)
+        return formed
+
+    def per_row(first, upto):                   # (penalty, back) of rows first .. upto - 1: the ordered pass's per-row arrays
+        return (lam[first:upto], back[first:upto]) if ordered else (lam, None)
+
+    for first, last in chunks:
+        curves, row_off = form(first, last)
+        price, backs = per_row(first, last)
+        _forward_device(ordered, margins, wide, curves, zip(row_off, w[first:last].tolist()), reach[first:last], price, mu, backs, state,
+                        first, method, None)
+    index_dev = _backtrack_device(ordered, state, None)
     extra = dict(guard=None, event_through=None, event_margin=None, event_alt_shift=None, event_alt_delta=None, marginals=None)
     if margins:
         # the chunks again, from the last one down: a lone chunk's curves are still there, several chunks' are formed a second time
         M = torch.empty(E * n_shift, dtype=torch.float64, device=state.D.device) if marginals else None
         for first, last in reversed(chunks):
             if len(chunks) > 1:
-                info = {}
-                curves, row_off = axis.event_rows(dst_dev, src_dev, [ax.part(first, last)], method, clamp=f, capacity=capacity,
-                                                  info=info)
-                if f is not None:
-                    rows_info = axis.merge_rows_info(rows_info, info)
+                curves, row_off = form(first, last)
             upto = last + 1 if last < E else last
-            margins_device(curves, zip(row_off, w[first:last].tolist()), reach[first:upto], guard[first:last], lam[first:upto], mu,
-                           back[first:upto], state, index_dev, row0=first, method=method, marginals=M)
+            price, backs = per_row(first, upto)
+            _margins_device(ordered, wide, curves, zip(row_off, w[first:last].tolist()), reach[first:upto], guard[first:last], price, mu,
+                            backs, state, index_dev, first, method, M, None)
         through, alt, alt_arg = state.through.cpu().numpy(), state.alt.cpu().numpy(), state.alt_arg.cpu().numpy()
         alt_shift = [None if int(k) == NO_ALT else k_lo + int(k) for k in alt_arg]
         extra = dict(guard=guard.tolist(), event_through=through,
@@ -1185,9 +1062,11 @@ def _find_track_ordered(stream, patterns, centres, window_size, penalty, max_rat
                      event_alt_delta=[None if k is None else k / float(rate) for k in alt_shift],
                      marginals=None if M is None else M.view(E, n_shift))
     index = index_dev.cpu().numpy()
+    # the move word every event was entered by: row e's, at its chosen shift (E reads of the device array, gathered there)
     words = state.moves[index_dev.long() + n_shift * _arange_like(index_dev)].cpu().numpy()
     shifts = [k_lo + int(k) for k in index]
     jumps = [e for e in range(1, E) if int(words[e]) == JUMP]
+    # every event's score at its chosen shift: curves are exact per position, so these are the bits of its row there
     at, _ = match_curves(dst_dev, src_dev, ax.offs, lens, [b + k for b, k in zip(ax.bases, shifts)], [1] * E, method=method)
     own = state.row_own_index.cpu().numpy()
     return Track(
@@ -1196,8 +1075,9 @@ def _find_track_ordered(stream, patterns, centres, window_size, penalty, max_rat
         segments=[(s, n, shifts[s] / float(rate), shifts[s + n - 1] / float(rate)) for s, n in jump_runs(E, jumps)],
         cost=float(state.row_min[E - 1].item()), event_scores=at.cpu().numpy(),
         event_own_delta=[(k_lo + int(k)) / float(rate) for k in own], event_own_scores=state.row_own_scores.cpu().numpy(),
-        clamp=None if f is None else float(f), rows_info=rows_info,
-        back=[None if int(b) == BACK_ANY else int(b) for b in back], penalties=lam.tolist(), **extra)
+        clamp=None if f is None else float(f), rows_info=rows_info[0],
+        back=None if back is None else [None if int(b) == BACK_ANY else int(b) for b in back],
+        penalties=lam.tolist() if ordered else None, **extra)
 
 
 def _arange_like(index_dev):

@@ -578,7 +578,7 @@ def test_find_ordered_track_refuses_on_the_host():
 def test_find_ordered_track_without_margins_is_find_track_with_order(monkeypatch):
     """Both entries hand the ordered search the same arguments: with margins=False find_ordered_track is find_track(order=...)."""
     seen = []
-    monkeypatch.setattr(track, "_find_track_ordered", lambda *a, **kw: seen.append((a, kw)) or "found")
+    monkeypatch.setattr(track, "_search", lambda *a, **kw: seen.append((a, kw)) or "found")
     stream, patterns, centres = object(), [np.zeros((1, 10), np.uint8)] * 3, [1.0, 2.0, 3.0]
     for order, penalty in ((True, 0.5), ([None, 3, 4], 0.5), (None, [0.0, 0.5, 0.25]), (True, [0.0, 0.5, 0.25])):
         del seen[:]
@@ -587,7 +587,9 @@ def test_find_ordered_track_without_margins_is_find_track_with_order(monkeypatch
         assert track.find_track(stream, patterns, centres, 1.0, penalty, order=order, **kw) == "found"
         assert track.find_ordered_track(stream, patterns, centres, 1.0, penalty, order=order, **kw) == "found"
         (a, akw), (b, bkw) = seen
-        assert a == b and akw == {} and bkw == dict(margins=False, guard=None, marginals=False, name="find_ordered_track")
+        # _search(name, ordered, wide, stream, ..., margins, guard, marginals, clamp, capacity): all but the name
+        assert a[1:] == b[1:] and akw == bkw == {} and (a[0], b[0]) == ("find_track", "find_ordered_track")
+        assert a[1:4] == (True, False, stream) and a[17:20] == (False, None, False) and len(a) == 22
 
 
 # ---------------------------------------------------------------------------------------------- the scenario on the oracle

@@ -5,7 +5,8 @@ build.UNITS (`--cuda-device-only -S`; works without a GPU), cut into its functio
 function's label to its .Lfunc_end, with the function number of local labels (.LBB12_3) normalised, since a new helper renumbers
 them; data symbols, kernel descriptors and the metadata notes are left out.  The functions of all units given are POOLED per tree
 and compared by name, so a kernel that moved to another unit is still compared with itself; of the units given, a tree compiles
-those its own build.UNITS has.  A name that occurs in two units of one tree is keyed `name [unit]`.
+those its own build.UNITS has.  A name that occurs in two units of one tree is keyed `name [unit]`; where B's unit of such a name
+is not one of A's (units folded or renamed), B's function is compared with one of A's that is still free, an equal one first.
 
 usage: kernel_asm_diff.py A B UNIT [UNIT ...] [--show NAME]
   A, B    a directory that holds sushi_amd/ and include/ (a checkout, an export), or a commit (exported to a scratch copy);
@@ -77,8 +78,22 @@ def pooled(tree, units, scratch, tag):
             for name, body in functions(assembly(tree, unit, os.path.join(scratch, "%s_%s.s" % (unit, tag)))).items()]
 
 
-def keyed(pool, by_unit):
-    return {("%s [%s]" % (name, unit) if name in by_unit else name): body for unit, name, body in pool}
+def keyed(pool, by_unit, partner=None):
+    """{key: body}: a name that occurs in two units of a tree is keyed `name [unit]`.  With `partner` (the other tree's keyed
+    functions) such a function whose own unit the other tree does not have under that name is keyed by the unit of a function
+    there that is still free, one with the same body first: units that were folded or renamed are still compared."""
+    out, moved = {}, []
+    for unit, name, body in pool:
+        key = "%s [%s]" % (name, unit) if name in by_unit else name
+        if partner is not None and name in by_unit and key not in partner:
+            moved.append((name, key, body))
+        else:
+            out[key] = body
+    for name, key, body in moved:
+        free = [k for k in partner if k.startswith(name + " [") and k not in out]
+        free.sort(key=lambda k: partner[k] != body)
+        out[free[0] if free else key] = body
+    return out
 
 
 def demangle(names):
@@ -124,7 +139,8 @@ def main():
         pa, pb = pooled(ta, args.units, scratch, "a"), pooled(tb, args.units, scratch, "b")
         # (a name in two units of one tree: keyed by its unit, in both trees)
         by_unit = {name for pool in (pa, pb) for name, n in collections.Counter(name for _, name, _ in pool).items() if n > 1}
-        fa, fb = keyed(pa, by_unit), keyed(pb, by_unit)
+        fa = keyed(pa, by_unit)
+        fb = keyed(pb, by_unit, fa)
         for tag, pool in (("A", pa), ("B", pb)):
             print("%s: %d functions in %s" % (tag, len(pool), ", ".join(sorted({unit for unit, _, _ in pool}))))
         for name in sorted(set(fa) | set(fb)):
