@@ -65,7 +65,8 @@ extern "C" {
                                      sushi_hip_track_forward_ordered_wide, sushi_hip_track_forward_ordered_wide_keep,
                                      sushi_hip_track_order_margins_wide;
                                      13 (additive): SUSHI_HIP_PCM_*, sushi_hip_load_decode_format, sushi_hip_load_decode_mix_format;
-                                     13 (additive): sushi_hip_envelope */
+                                     13 (additive): sushi_hip_envelope;
+                                     13 (additive): sushi_hip_filter */
 
 #if defined(__GNUC__)
 #define SUSHI_HIP_API __attribute__((visibility("default")))
@@ -481,6 +482,25 @@ SUSHI_HIP_API int sushi_hip_retime(const void* in_dev, int dtype, int64_t n_in,
  * hop * span > 4096; EALIGN: in_dev / out_dev not aligned to their sample type. */
 SUSHI_HIP_API int sushi_hip_envelope(const void* in_dev, int dtype, int64_t n_in, int64_t in_start,
                                      int32_t hop, int32_t span, void* out_dev, int64_t out_len, void* hip_stream);
+
+/* ---- FIR filter: a row with a band removed, at its own rate (13, additive) --------------------
+ * Mains hum, DC wander, rumble or a dub's own speech correlate with themselves and hide what two streams share.  This call
+ * correlates a row with T float64 taps in an arithmetic stated to the bit.  T odd in [1, 2047], a = (T - 1) / 2,
+ * c = sushi_hip_centre(dtype), d(g) = (double)x[clamp(g, 0, n_in - 1)] - c (SUSHI_HIP_F32: one float64 subtraction;
+ * SUSHI_HIP_U8: exact).  Output i, 0 <= i < out_len:
+ *     acc = 0.0
+ *     p = taps[k] * d(in_start + i + k - a);  acc = acc + p      for k = 0 .. T - 1, in that order (the product and the sum round
+ *                                                                separately: no fused multiply-add, no pairwise sum)
+ *     SUSHI_HIP_F32: out = (float)(acc + 0.5)
+ *     SUSHI_HIP_U8:  v = floor(acc + 128.5);  out = v >= 255 ? 255 : (v >= 0 ? v : 0)      (a NaN gives 0)
+ * so a NumPy float64 restatement equals the result bit for bit.  Correlation orientation: taps[0] meets the sample a places in
+ * front of the output; reads outside the row see its edge samples.  Taps are not checked for being finite.
+ * in_dev / out_dev: n_in / out_len samples of `dtype`, naturally aligned, not overlapping; taps_dev: T doubles in device memory.
+ * One launch, no workspace, no device allocation.  Asynchronous; stateless (any thread).  Checked before any HIP call -- EINVAL: a
+ * null pointer, an unknown dtype, n_in < 1 (or >= 2^62), in_start outside [0, n_in - 1], out_len < 1 or >= 2^40, n_taps even or
+ * outside [1, 2047]; EALIGN: in_dev / out_dev not aligned to their sample type, taps_dev not to 8 bytes. */
+SUSHI_HIP_API int sushi_hip_filter(const void* in_dev, int dtype, int64_t n_in, int64_t in_start,
+                                   const double* taps_dev, int32_t n_taps, void* out_dev, int64_t out_len, void* hip_stream);
 
 /* ---- joint search: the one shift a group of score rows shares (13, additive) -----------------
  * Events of one scene share one shift, and a lone search of a short or repeated pattern may prefer a decoy in its window.  The

@@ -67,6 +67,9 @@ UNITS = [
     # a row's loudness contour: the mean absolute deviation about the sample type's centre over span blocks of hop samples, a tile
     # of blocks staged through LDS (envelope_core.hpp: the arithmetic, the tile, and the call's host side)
     ("sushi_envelope", ["-ffp-contract=off"]),  # float64 sums in a stated order, each addition rounded once, as NumPy's
+    # a row through a FIR filter of float64 taps about the sample type's centre: a tile's samples and the taps staged in LDS, a few
+    # consecutive outputs a thread (filter_core.hpp: the arithmetic, the tile, and the call's host side)
+    ("sushi_filter", ["-ffp-contract=off"]),    # float64: product and sum round separately, in ascending tap order, as NumPy's
     # overlap-save FFT path; its parts, by stage, are csrc/sushi_fft_*.inc (included inside its anonymous namespace); the plan of
     # a batch (plan_core.hpp), what a handle holds about its requests and how it is staged (batch_core.hpp) and what a run decides
     # (run_policy.hpp) are host only

@@ -6,7 +6,8 @@ Extensions: ``WavStream.from_samples`` (in-memory PCM), ``find_substreams`` (bat
 ``WavStream.from_channels`` (the channels mixed by weight instead of averaged: sushi_amd/downmix.py), ``find_joint`` /
 ``find_joint_many`` (the one shift a group of patterns shares: sushi_amd/joint.py), ``formats='all'`` (float, 32-bit, 8-bit and
 RF64 / BW64 files: the header walk below, the sample rule in sushi_amd/downmix.py ``samples_from_bytes`` / csrc/pcm_core.hpp),
-``retimed`` (the stream on another clock: sushi_amd/retime.py), ``envelope`` (its loudness contour: sushi_amd/envelope.py).
+``retimed`` (the stream on another clock: sushi_amd/retime.py), ``envelope`` (its loudness contour: sushi_amd/envelope.py),
+``filtered`` (a band taken out of it: sushi_amd/filter.py).
 
 The load pipeline (wav.py:64-162): the RIFF header walk on the host; PCM decode, channel downmix, decimation,
 padding, the two medians, clip / scale / quantise on the GPU when one is present (the file is uploaded in bounded
@@ -904,4 +905,44 @@ class WavStream(object):
             fill_pads(data[0], new_pad)
         new = self.__class__.__new__(self.__class__)
         new._adopt(data, dev_row, new_rate, new_count, new_pad, self._device)
+        return new
+
+    # ------------------------------------------------------------------ a band removed
+    def filtered(self, low=None, high=None, stop=False, n_taps=255, taps=None):
+        """This stream through a FIR filter (sushi_amd.filter): a new live WavStream with the same sample rate,
+        padding_size, sample_count and sample type.  The taps are filter.band_taps(sample_rate, low, high, n_taps, stop) -- only
+        low: a high-pass (filtered(low=150) takes mains hum, DC wander and rumble out), only high: a low-pass, both: a band-pass,
+        stop=True: what those leave -- or `taps` as given (an odd number of finite values, up to 2047; taps[k] meets the sample
+        (len - 1) // 2 - k places in front of the output: filter.preemphasis_taps()).  The body is filtered about the sample type's
+        nominal centre; reads past the body see the pads, reads past the row its edge samples; both pads are then filled as the
+        loader fills them.  Source and destination of a search are filtered alike and so get the same delay: shifts are
+        unaffected, also for taps that are not symmetric.  On the GPU when there is one (sushi_hip_filter; the row stays in HBM for
+        the matching), else in NumPy -- bit for bit the same.  The result is an ordinary stream: every search method,
+        SpeculativeStream, retimed and envelope take it as it is."""
+        from .filter import band_taps, filter_device, filter_host
+        pad, count, total = int(self.padding_size), int(self.sample_count), int(self.data.shape[1])
+        if count < 1 or pad < 0 or pad + count > total:
+            raise SushiError('filtered: the stream has no body inside its row')
+        h = band_taps(self.sample_rate, low, high, n_taps, stop) if taps is None else np.asarray(taps, np.float64)
+        if self._use_gpu():
+            import torch
+            dev = torch_device("cuda" if self._device is None else self._device)
+            if self._dev is not None and self._dev.device == dev:
+                row = self._dev.raw
+            elif self._dev_row is not None and self._dev_row.device == dev:
+                row = self._dev_row
+            else:
+                row = torch.from_numpy(self.data[0]).to(dev)
+            with torch.cuda.device(dev):
+                dev_row = torch.empty(2 * pad + count, dtype=row.dtype, device=dev)
+                filter_device(row, pad, h, count, out=dev_row[pad:pad + count])
+                fill_pads(dev_row, pad)
+                data = dev_row.cpu().numpy().reshape(1, -1)
+        else:
+            dev_row = None
+            data = np.empty((1, 2 * pad + count), self.data.dtype)
+            data[0, pad:pad + count] = filter_host(self.data[0], pad, h, count)
+            fill_pads(data[0], pad)
+        new = self.__class__.__new__(self.__class__)
+        new._adopt(data, dev_row, self.sample_rate, count, self.padding_size, self._device)
         return new
