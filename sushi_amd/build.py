@@ -37,7 +37,8 @@ UNITS = [
     # evaluate the listed pairs of a threshold run and of a best-K run; what a curve call uploads and launches is host only
     # (curve_core.hpp)
     ("sushi_curve", ["-ffp-contract=off"]),     # the epilogue restates cv2's operation order (as sushi_direct.hip's)
-    # a stream read at another speed: linear interpolation at a rational step (retime_core.hpp: the arithmetic, and the call's host side)
+    # a stream read at another speed: linear interpolation at a rational step (retime_core.hpp: the arithmetic, and the call's host
+    # side; row_core.hpp: the step's cursor, and what every call on a row of samples checks and dispatches on)
     ("sushi_retime", ["-ffp-contract=off"]),    # NumPy's float64 operation order: product and sum round separately
     # a low-pass in front of the load pipeline's decimator: polyphase FIR at the file's rate (resample_core.hpp)
     ("sushi_resample", ["-ffp-contract=off"]),  # float64 taps: product and sum round separately, as NumPy's
@@ -65,10 +66,11 @@ UNITS = [
     # (rows_core.hpp: the rule, the tiles, the search of a hit list, and the call's host side)
     ("sushi_rows", []),                         # comparisons and copies: no arithmetic to contract
     # a row's loudness contour: the mean absolute deviation about the sample type's centre over span blocks of hop samples, a tile
-    # of blocks staged through LDS (envelope_core.hpp: the arithmetic, the tile, and the call's host side)
+    # of blocks staged through LDS (envelope_core.hpp: the arithmetic, the tile, and the call's host side; row_core.hpp: a row's
+    # sample with both clamps, its deviation, a row call's opening refusals)
     ("sushi_envelope", ["-ffp-contract=off"]),  # float64 sums in a stated order, each addition rounded once, as NumPy's
     # a row through a FIR filter of float64 taps about the sample type's centre: a tile's samples and the taps staged in LDS, a few
-    # consecutive outputs a thread (filter_core.hpp: the arithmetic, the tile, and the call's host side)
+    # consecutive outputs a thread (filter_core.hpp: the arithmetic, the tile, and the call's host side; row_core.hpp as above)
     ("sushi_filter", ["-ffp-contract=off"]),    # float64: product and sum round separately, in ascending tap order, as NumPy's
     # overlap-save FFT path; its parts, by stage, are csrc/sushi_fft_*.inc (included inside its anonymous namespace); the plan of
     # a batch (plan_core.hpp), what a handle holds about its requests and how it is staged (batch_core.hpp) and what a run decides

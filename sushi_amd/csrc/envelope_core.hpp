@@ -11,37 +11,31 @@
 #include <stdint.h>
 
 #include "../../include/sushi_hip.h"
-
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define ENVELOPE_HD __host__ __device__
-#else
-#define ENVELOPE_HD
-#endif
+#include "row_core.hpp"            // row_at, row_deviation, row_call_ok
 
 namespace sushi {
 
 constexpr int32_t ENVELOPE_MAX_HOP = 256;
 constexpr int32_t ENVELOPE_MAX_SPAN = 64;
 constexpr int32_t ENVELOPE_MAX_WINDOW = 4096;                  // hop * span
-constexpr int64_t ENVELOPE_MAX_LEN = (int64_t)1 << 40;         // out_len
-constexpr int64_t ENVELOPE_MAX_IN = (int64_t)1 << 62;          // n_in (in_start + block * hop stays inside int64)
 
 // What a sum of deviations is kept in: float64 for float32 samples, an integer for uint8 (at most 4096 * 128 = 524288).
 template <class T> struct EnvelopeSum;
 template <> struct EnvelopeSum<float> { typedef double type; };
 template <> struct EnvelopeSum<uint8_t> { typedef uint32_t type; };
 
-// |x - c|, c = sushi_hip_centre: 0.5 (the difference rounds once, in float64) or 128.
-ENVELOPE_HD inline double envelope_deviation(float x) { return fabs((double)x - 0.5); }
-ENVELOPE_HD inline uint32_t envelope_deviation(uint8_t x) { return x >= 128 ? (uint32_t)x - 128u : 128u - (uint32_t)x; }
+// |x - c|, c = sushi_hip_centre: 0.5 (the difference rounds once, in float64) or 128 (stated in unsigned integers here: through
+// row_deviation's signed difference the uint8 kernel compiles to other code).
+SUSHI_GEOM_HD inline double envelope_deviation(float x) { return fabs(row_deviation(x)); }
+SUSHI_GEOM_HD inline uint32_t envelope_deviation(uint8_t x) { return x >= 128 ? (uint32_t)x - 128u : 128u - (uint32_t)x; }
 
 // Blocks in front of output i: a = (span - 1) / 2; output i sums blocks i - a .. i - a + span - 1.
-ENVELOPE_HD inline int32_t envelope_lead(int32_t span) { return (span - 1) / 2; }
+SUSHI_GEOM_HD inline int32_t envelope_lead(int32_t span) { return (span - 1) / 2; }
 
 // A block sum B: sample(t), t = 0 .. hop - 1, in that order (sample: where the block's samples are -- the row with both clamps
 // on the CPU, the staged tile on the device).
 template <class T, class Sample>
-ENVELOPE_HD inline typename EnvelopeSum<T>::type envelope_block(Sample sample, int32_t hop) {
+SUSHI_GEOM_HD inline typename EnvelopeSum<T>::type envelope_block(Sample sample, int32_t hop) {
     typename EnvelopeSum<T>::type acc = 0;
     int32_t t = 0;
     for (; t + 8 <= hop; t += 8) {                          // eight reads in flight, the additions in order all the same
@@ -55,7 +49,7 @@ ENVELOPE_HD inline typename EnvelopeSum<T>::type envelope_block(Sample sample, i
 
 // E of an output: block(j), j = 0 .. span - 1, in that order.
 template <class T, class Block>
-ENVELOPE_HD inline typename EnvelopeSum<T>::type envelope_window(Block block, int32_t span) {
+SUSHI_GEOM_HD inline typename EnvelopeSum<T>::type envelope_window(Block block, int32_t span) {
     typename EnvelopeSum<T>::type acc = 0;
     for (int32_t j = 0; j < span; ++j) acc = acc + block(j);
     return acc;
@@ -63,15 +57,11 @@ ENVELOPE_HD inline typename EnvelopeSum<T>::type envelope_window(Block block, in
 
 // E -> the output sample: 2 E / W, W = hop * span.  float32: (float)((E + E) / (double)W); uint8: rounded half up in integers
 // (4 E + W <= 2^21 + 2^12), capped at 255 (a row of 0 gives 256).
-ENVELOPE_HD inline float envelope_finish(double e, int32_t w, const float*) { return (float)((e + e) / (double)w); }
-ENVELOPE_HD inline uint8_t envelope_finish(uint32_t e, int32_t w, const uint8_t*) {
+SUSHI_GEOM_HD inline float envelope_finish(double e, int32_t w, const float*) { return (float)((e + e) / (double)w); }
+SUSHI_GEOM_HD inline uint8_t envelope_finish(uint32_t e, int32_t w, const uint8_t*) {
     const uint32_t y = (4u * e + (uint32_t)w) / (2u * (uint32_t)w);
     return (uint8_t)(y < 255u ? y : 255u);
 }
-
-// The row's sample at index g with both clamps.
-template <class T>
-ENVELOPE_HD inline T envelope_at(const T* x, int64_t n_in, int64_t g) { return x[g < 0 ? 0 : (g < n_in ? g : n_in - 1)]; }
 
 // One output straight from the row (the CPU check; the kernel forms the same sums, in the same order, from its staged tile).
 template <class T>
@@ -80,7 +70,7 @@ inline T envelope_sample(const T* x, int64_t n_in, int64_t in_start, int32_t hop
     const int64_t b0 = i - envelope_lead(span);
     const S e = envelope_window<T>([&](int32_t j) {
         const int64_t g0 = in_start + (b0 + j) * hop;
-        return envelope_block<T>([&](int32_t t) { return envelope_at(x, n_in, g0 + t); }, hop);
+        return envelope_block<T>([&](int32_t t) { return row_at(x, n_in, g0 + t); }, hop);
     }, span);
     return envelope_finish(e, hop * span, (const T*)0);
 }
@@ -95,11 +85,11 @@ constexpr int32_t ENVELOPE_TILE_SAMPLES = 4096;
 constexpr int32_t ENVELOPE_MAX_TILE = 512;
 constexpr int64_t ENVELOPE_MAX_GRID = 1024;                    // a fixed grid striding over the tiles: 256 CUs, four workgroups each (what LDS lets a CU hold)
 
-ENVELOPE_HD constexpr int32_t envelope_tile(int32_t hop) {
+SUSHI_GEOM_HD constexpr int32_t envelope_tile(int32_t hop) {
     return ENVELOPE_TILE_SAMPLES / hop < ENVELOPE_MAX_TILE ? ENVELOPE_TILE_SAMPLES / hop : ENVELOPE_MAX_TILE;
 }
-ENVELOPE_HD constexpr int32_t envelope_stride(int32_t hop) { return hop | 1; }
-ENVELOPE_HD constexpr int32_t envelope_max_span(int32_t hop) {
+SUSHI_GEOM_HD constexpr int32_t envelope_stride(int32_t hop) { return hop | 1; }
+SUSHI_GEOM_HD constexpr int32_t envelope_max_span(int32_t hop) {
     return ENVELOPE_MAX_WINDOW / hop < ENVELOPE_MAX_SPAN ? ENVELOPE_MAX_WINDOW / hop : ENVELOPE_MAX_SPAN;
 }
 // the most words / block sums a tile stages, over every hop and the widest span it allows
@@ -133,10 +123,7 @@ struct EnvelopeStage {
 // EINVAL: an unknown dtype, n_in < 1 (or >= 2^62), out_len outside 1 .. 2^40 - 1, in_start outside [0, n_in - 1], hop outside
 // 1 .. 256, span outside 1 .. 64, hop * span > 4096 (`out` is then unspecified).
 inline int stage_envelope(int dtype, int64_t n_in, int64_t in_start, int32_t hop, int32_t span, int64_t out_len, EnvelopeStage& out) {
-    if (dtype != SUSHI_HIP_U8 && dtype != SUSHI_HIP_F32) return SUSHI_HIP_EINVAL;
-    if (n_in < 1 || n_in >= ENVELOPE_MAX_IN) return SUSHI_HIP_EINVAL;
-    if (out_len < 1 || out_len >= ENVELOPE_MAX_LEN) return SUSHI_HIP_EINVAL;
-    if (in_start < 0 || in_start > n_in - 1) return SUSHI_HIP_EINVAL;
+    if (row_call_ok(dtype, n_in, in_start, out_len) != SUSHI_HIP_OK) return SUSHI_HIP_EINVAL;
     if (hop < 1 || hop > ENVELOPE_MAX_HOP || span < 1 || span > ENVELOPE_MAX_SPAN || hop * span > ENVELOPE_MAX_WINDOW) return SUSHI_HIP_EINVAL;
     out.tile = envelope_tile(hop);
     out.n_tiles = (out_len + out.tile - 1) / out.tile;

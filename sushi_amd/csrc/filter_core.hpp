@@ -11,50 +11,39 @@
 #include <stdint.h>
 
 #include "../../include/sushi_hip.h"
-
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define FILTER_HD __host__ __device__
-#else
-#define FILTER_HD
-#endif
+#include "row_core.hpp"            // row_at, row_deviation, row_call_ok
 
 namespace sushi {
 
 constexpr int32_t FILTER_MAX_TAPS = 2047;                    // T: odd, 1 .. 2047
-constexpr int64_t FILTER_MAX_LEN = (int64_t)1 << 40;         // out_len
-constexpr int64_t FILTER_MAX_IN = (int64_t)1 << 62;          // n_in (in_start + i + k - a stays inside int64)
 
-// x - c, c = sushi_hip_centre: 0.5 (one float64 subtraction) or 128 (exact).
-FILTER_HD inline double filter_deviation(float x) { return (double)x - 0.5; }
-FILTER_HD inline double filter_deviation(uint8_t x) { return (double)((int32_t)x - 128); }
+// x - c, c = sushi_hip_centre, as a float64 (row_deviation: one float64 subtraction, or exact).
+template <class T>
+SUSHI_GEOM_HD inline double filter_deviation(T x) { return (double)row_deviation(x); }
 
 // Samples in front of output i that h[0] meets: a = (T - 1) / 2.
-FILTER_HD inline int32_t filter_lead(int32_t n_taps) { return (n_taps - 1) / 2; }
+SUSHI_GEOM_HD inline int32_t filter_lead(int32_t n_taps) { return (n_taps - 1) / 2; }
 
 // One step of an output's sum: the product rounds, then the sum.
-FILTER_HD inline double filter_step(double acc, double h, double d) {
+SUSHI_GEOM_HD inline double filter_step(double acc, double h, double d) {
     const double p = h * d;
     return acc + p;
 }
 
 // acc -> the output sample.  float32: (float)(acc + 0.5).  uint8: floor(acc + 128.5) held to 0 .. 255; both comparisons fail for a
 // NaN, which so gives 0.
-FILTER_HD inline float filter_finish(double acc, const float*) { return (float)(acc + 0.5); }
-FILTER_HD inline uint8_t filter_finish(double acc, const uint8_t*) {
+SUSHI_GEOM_HD inline float filter_finish(double acc, const float*) { return (float)(acc + 0.5); }
+SUSHI_GEOM_HD inline uint8_t filter_finish(double acc, const uint8_t*) {
     const double v = floor(acc + 128.5);
     return v >= 255.0 ? (uint8_t)255 : (v >= 0.0 ? (uint8_t)v : (uint8_t)0);
 }
-
-// The row's sample at index g with both clamps.
-template <class T>
-FILTER_HD inline T filter_at(const T* x, int64_t n_in, int64_t g) { return x[g < 0 ? 0 : (g < n_in ? g : n_in - 1)]; }
 
 // One output straight from the row (the CPU check; the kernel forms the same sum, in the same order, from its staged tile).
 template <class T>
 inline T filter_sample(const T* x, int64_t n_in, int64_t in_start, const double* taps, int32_t n_taps, int64_t i) {
     const int64_t g0 = in_start + i - filter_lead(n_taps);
     double acc = 0.0;
-    for (int32_t k = 0; k < n_taps; ++k) acc = filter_step(acc, taps[k], filter_deviation(filter_at(x, n_in, g0 + k)));
+    for (int32_t k = 0; k < n_taps; ++k) acc = filter_step(acc, taps[k], filter_deviation(row_at(x, n_in, g0 + k)));
     return filter_finish(acc, (const T*)0);
 }
 
@@ -69,20 +58,20 @@ constexpr int32_t FILTER_WIDE_MAX_TAPS = 1025;
 constexpr int32_t FILTER_CUS = 256, FILTER_CU_LDS = 160 * 1024;
 constexpr int32_t FILTER_MAX_RESIDENT = 5;                     // workgroups a CU holds by registers (a wave of each on every SIMD)
 
-FILTER_HD constexpr int32_t filter_per_thread(int32_t n_taps) { return n_taps <= FILTER_WIDE_MAX_TAPS ? FILTER_WIDE : FILTER_NARROW; }
-FILTER_HD constexpr int32_t filter_tile(int32_t n_taps) { return FILTER_THREADS * filter_per_thread(n_taps); }
-FILTER_HD constexpr int32_t filter_slot(int32_t e, int32_t per) { return e + e / per; }
+SUSHI_GEOM_HD constexpr int32_t filter_per_thread(int32_t n_taps) { return n_taps <= FILTER_WIDE_MAX_TAPS ? FILTER_WIDE : FILTER_NARROW; }
+SUSHI_GEOM_HD constexpr int32_t filter_tile(int32_t n_taps) { return FILTER_THREADS * filter_per_thread(n_taps); }
+SUSHI_GEOM_HD constexpr int32_t filter_slot(int32_t e, int32_t per) { return e + e / per; }
 // slots a tile's staged samples take at T taps
-FILTER_HD constexpr int32_t filter_slots(int32_t n_taps) {
+SUSHI_GEOM_HD constexpr int32_t filter_slots(int32_t n_taps) {
     return filter_slot(filter_tile(n_taps) + n_taps - 2, filter_per_thread(n_taps)) + 1;
 }
 // The LDS of a workgroup, sized by the call: the taps first (T + 1 doubles: what follows stays 16-byte aligned), then the slots.
-FILTER_HD constexpr int32_t filter_lds_bytes(int32_t n_taps) { return (n_taps + 1 + filter_slots(n_taps)) * 8; }
+SUSHI_GEOM_HD constexpr int32_t filter_lds_bytes(int32_t n_taps) { return (n_taps + 1 + filter_slots(n_taps)) * 8; }
 // (within either kind of tile the need grows with T)
 static_assert(filter_lds_bytes(FILTER_WIDE_MAX_TAPS) <= 48 * 1024 && filter_lds_bytes(FILTER_MAX_TAPS) <= 48 * 1024,
               "a tile's samples and the taps fit 48 KB of LDS: at least three workgroups to a CU");
 // A fixed grid striding over the tiles: as many workgroups as the CUs hold at once, by LDS and by registers.
-FILTER_HD constexpr int32_t filter_resident(int32_t n_taps) {
+SUSHI_GEOM_HD constexpr int32_t filter_resident(int32_t n_taps) {
     return FILTER_CU_LDS / filter_lds_bytes(n_taps) < FILTER_MAX_RESIDENT ? FILTER_CU_LDS / filter_lds_bytes(n_taps) : FILTER_MAX_RESIDENT;
 }
 
@@ -99,10 +88,7 @@ struct FilterStage {
 inline int stage_filter(const void* x, int dtype, int64_t n_in, int64_t in_start, const void* taps, int32_t n_taps,
                         const void* y, int64_t out_len, FilterStage& out) {
     if (!x || !taps || !y) return SUSHI_HIP_EINVAL;
-    if (dtype != SUSHI_HIP_U8 && dtype != SUSHI_HIP_F32) return SUSHI_HIP_EINVAL;
-    if (n_in < 1 || n_in >= FILTER_MAX_IN) return SUSHI_HIP_EINVAL;
-    if (in_start < 0 || in_start > n_in - 1) return SUSHI_HIP_EINVAL;
-    if (out_len < 1 || out_len >= FILTER_MAX_LEN) return SUSHI_HIP_EINVAL;
+    if (row_call_ok(dtype, n_in, in_start, out_len) != SUSHI_HIP_OK) return SUSHI_HIP_EINVAL;
     if (n_taps < 1 || n_taps > FILTER_MAX_TAPS || !(n_taps & 1)) return SUSHI_HIP_EINVAL;
     out.tile = filter_tile(n_taps);
     out.n_tiles = (out_len + out.tile - 1) / out.tile;

@@ -6,44 +6,22 @@
 
 #include <stdint.h>
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define RESAMPLE_HD __host__ __device__
-#else
-#define RESAMPLE_HD
-#endif
+#include "row_core.hpp"            // the cursor of a rational step, ROW_MAX_LEN
 
 namespace sushi {
 
 constexpr int32_t RESAMPLE_MAX_TERM = 1 << 20;              // num, den
 constexpr int64_t RESAMPLE_MAX_TABLE = 65536;               // den * 2W table entries
-constexpr int64_t RESAMPLE_MAX_BODY = (int64_t)1 << 40;     // n_body (i * num stays below 2^60)
+constexpr int64_t RESAMPLE_MAX_BODY = ROW_MAX_LEN;          // n_body (i * num stays below 2^60)
 
 // Where body sample i reads its input: the filter is centred on i * num / den = sample j and the fraction r / den behind it;
-// r picks the table's row.
-struct ResampleCursor {
-    int64_t j;
-    int32_t r;            // 0 <= r < den
-};
-
-// The one 64-bit division of a run of outputs: t = i * num, j = t / den, r = t % den  (i < 2^40, num <= 2^20: no overflow).
-RESAMPLE_HD inline ResampleCursor resample_seek(int64_t i, int32_t num, int32_t den) {
-    const uint64_t t = (uint64_t)i * (uint64_t)num;
-    const uint64_t q = t / (uint32_t)den;
-    ResampleCursor c;
-    c.j = (int64_t)q;
-    c.r = (int32_t)(t - q * (uint32_t)den);
-    return c;
-}
-
-// ... and on by a fixed number of outputs without another: (qstep, rstep) = divmod(outputs * num, den); the carry goes into j.
-RESAMPLE_HD inline void resample_advance(ResampleCursor& c, int32_t qstep, int32_t rstep, int32_t den) {
-    c.r += rstep;
-    c.j += qstep;
-    if (c.r >= den) { c.r -= den; c.j += 1; }
-}
+// r picks the table's row.  One division per run of outputs, then advances by a fixed number of outputs (row_core.hpp).
+typedef RowCursor ResampleCursor;
+SUSHI_GEOM_HD inline ResampleCursor resample_seek(int64_t i, int32_t num, int32_t den) { return row_seek(0, i, num, den); }
+SUSHI_GEOM_HD inline void resample_advance(ResampleCursor& c, int32_t qstep, int32_t rstep, int32_t den) { row_advance(c, qstep, rstep, den); }
 
 // The sample tap c of an output centred on j reads: x[clamp(j - W + 1 + c, 0, n_raw - 1)].
-RESAMPLE_HD inline int64_t resample_tap_index(int64_t j, int32_t half_width, int32_t c, int64_t n_raw) {
+SUSHI_GEOM_HD inline int64_t resample_tap_index(int64_t j, int32_t half_width, int32_t c, int64_t n_raw) {
     const int64_t k = j - half_width + 1 + c;
     return k < 0 ? 0 : (k > n_raw - 1 ? n_raw - 1 : k);
 }
@@ -52,7 +30,7 @@ RESAMPLE_HD inline int64_t resample_tap_index(int64_t j, int32_t half_width, int
 // separately; y = (float)acc.  x(c): tap c's input sample as a double (the float32 sample, widened); h(c): H[r][c].  Both are
 // called once per tap, in ascending c.
 template <class X, class H>
-RESAMPLE_HD inline float resample_output(int32_t taps, X x, H h) {
+SUSHI_GEOM_HD inline float resample_output(int32_t taps, X x, H h) {
     double acc = 0.0;
 #if defined(__clang__)
 #pragma unroll 8

@@ -13,45 +13,24 @@
 
 #include "../../include/sushi_hip.h"
 #include "sushi_geometry.hpp"      // align_up
-
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define RETIME_HD __host__ __device__
-#else
-#define RETIME_HD
-#endif
+#include "row_core.hpp"            // the sample type of a call, the cursor of a rational step
 
 namespace sushi {
 
 // Where output i of a segment reads its input: position in_start + i * num / den = sample j and the fraction r / den behind it.
-struct RetimeCursor {
-    int64_t j;
-    int32_t r;            // 0 <= r < den
-};
+// One division per run of outputs (row_core.hpp), then from output i to output i + 1 without another: r += num % den, the carry
+// and num / den go into j.
+typedef RowCursor RetimeCursor;
+SUSHI_GEOM_HD inline RetimeCursor retime_seek(int64_t in_start, int64_t i, int32_t num, int32_t den) { return row_seek(in_start, i, num, den); }
+SUSHI_GEOM_HD inline void retime_advance(RetimeCursor& c, int32_t qstep, int32_t rstep, int32_t den) { row_advance(c, qstep, rstep, den); }
 
-// The one 64-bit division of a run of outputs: t = i * num, j = in_start + t / den, r = t % den  (i < 2^40, num <= 2^20: no overflow).
-RETIME_HD inline RetimeCursor retime_seek(int64_t in_start, int64_t i, int32_t num, int32_t den) {
-    const uint64_t t = (uint64_t)i * (uint64_t)num;
-    const uint64_t q = t / (uint32_t)den;
-    RetimeCursor c;
-    c.j = in_start + (int64_t)q;
-    c.r = (int32_t)(t - q * (uint32_t)den);
-    return c;
-}
-
-// ... and from output i to output i + 1 without another: r += num % den, the carry and num / den go into j.
-RETIME_HD inline void retime_advance(RetimeCursor& c, int32_t qstep, int32_t rstep, int32_t den) {
-    c.r += rstep;
-    c.j += qstep;
-    if (c.r >= den) { c.r -= den; c.j += 1; }
-}
-
-RETIME_HD inline float retime_round(double y, const float*) { return (float)y; }
-RETIME_HD inline uint8_t retime_round(double y, const uint8_t*) { return (uint8_t)(y + 0.5); }       // half up (y >= 0)
+SUSHI_GEOM_HD inline float retime_round(double y, const float*) { return (float)y; }
+SUSHI_GEOM_HD inline uint8_t retime_round(double y, const uint8_t*) { return (uint8_t)(y + 0.5); }       // half up (y >= 0)
 
 // One output sample (T: float or uint8_t): y = x[j] + w * (x[j1] - x[j]) in float64, w = r / den, j1 = min(j + 1, n_in - 1);
 // float32: (float)y; uint8: (uint8_t)(y + 0.5).
 template <class T>
-RETIME_HD inline T retime_sample(const T* x, int64_t n_in, int64_t j, int32_t r, int32_t den) {
+SUSHI_GEOM_HD inline T retime_sample(const T* x, int64_t n_in, int64_t j, int32_t r, int32_t den) {
     const int64_t j1 = j + 1 < n_in - 1 ? j + 1 : n_in - 1;
     const double a = (double)x[j];
     const double b = (double)x[j1];
@@ -84,12 +63,11 @@ constexpr int64_t RETIME_MAX_GRID = 2048;                // a fixed grid stridin
 inline size_t retime_layout_bytes(int n_seg) { return n_seg < 1 ? 0 : align_up((size_t)n_seg * sizeof(RetimeSeg), 256); }
 
 constexpr int32_t RETIME_MAX_TERM = 1 << 20;             // num, den
-constexpr int64_t RETIME_MAX_LEN = (int64_t)1 << 40;     // out_len (i * num stays below 2^60)
 
 inline bool segment_ok(const SushiHipRetimeSegment& s, int64_t n_in, int64_t n_out) {
     if (s.num < 1 || s.num > RETIME_MAX_TERM || s.den < 1 || s.den > RETIME_MAX_TERM) return false;
     if ((int64_t)s.num > 8 * (int64_t)s.den || (int64_t)s.den > 8 * (int64_t)s.num) return false;
-    if (s.out_len < 1 || s.out_len >= RETIME_MAX_LEN) return false;
+    if (s.out_len < 1 || s.out_len >= ROW_MAX_LEN) return false;
     if (s.in_start < 0 || s.in_start > n_in - 1) return false;
     if ((s.out_len - 1) * (int64_t)s.num / s.den > n_in - 1 - s.in_start) return false;           // the last read
     if (s.out_off < 0 || s.out_off > n_out || s.out_len > n_out - s.out_off) return false;
@@ -105,12 +83,11 @@ struct RetimeStage {
 // `out_addr`: the device address of output sample 0 (the chunks lie on the grid of 16-byte-aligned ADDRESSES).  EINVAL: an unknown
 // dtype, no segment, an empty input or output, a segment that segment_ok refuses (`out` is then unspecified).
 inline int stage_retime(const SushiHipRetimeSegment* seg, int n_seg, int dtype, int64_t n_in, int64_t n_out, uintptr_t out_addr, RetimeStage& out) {
-    if (dtype != SUSHI_HIP_U8 && dtype != SUSHI_HIP_F32) return SUSHI_HIP_EINVAL;
+    if (!row_dtype_ok(dtype)) return SUSHI_HIP_EINVAL;
     if (n_seg < 1 || n_in < 1 || n_out < 1) return SUSHI_HIP_EINVAL;
     for (int k = 0; k < n_seg; ++k)
         if (!segment_ok(seg[k], n_in, n_out)) return SUSHI_HIP_EINVAL;
-    const bool u8 = dtype == SUSHI_HIP_U8;
-    const int size = u8 ? 1 : 4, per = u8 ? RetimeChunk<uint8_t>::PER : RetimeChunk<float>::PER;
+    const int size = row_sample_size(dtype), per = size == 1 ? RetimeChunk<uint8_t>::PER : RetimeChunk<float>::PER;
     out.image.resize((size_t)n_seg);
     int64_t tiles = 0;
     for (int k = 0; k < n_seg; ++k) {

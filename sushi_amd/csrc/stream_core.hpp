@@ -11,6 +11,7 @@
 
 #include "../../include/sushi_hip.h"
 #include "sushi_geometry.hpp"
+#include "row_core.hpp"            // row_dtype_ok
 
 // The opaque stream handle of the C ABI: where the parts of a prepared stream live (all inside the caller's buffers).
 struct SushiHipStream {
@@ -92,7 +93,7 @@ inline StreamLayout stream_layout(int64_t n, int searchable) {
     return l;
 }
 
-inline bool stream_dtype_ok(int dtype) { return dtype == SUSHI_HIP_U8 || dtype == SUSHI_HIP_F32; }
+inline bool stream_dtype_ok(int dtype) { return row_dtype_ok(dtype); }
 
 // sushi_hip_stream_bytes
 inline size_t stream_bytes(int64_t n, int dtype, int searchable) { return n <= 0 || !stream_dtype_ok(dtype) ? 0 : stream_layout(n, searchable).total; }

@@ -105,7 +105,7 @@ void envelope_kernel(EnvelopeArgs a) {
         } else {                                             // a tile at either end of the row, or past it: sample by sample, with the clamp
             for (int32_t sm = tid; sm < n_samples; sm += ENVELOPE_THREADS) {
                 const uint32_t q = (uint32_t)sm / (uint32_t)hop;
-                stage[q * (uint32_t)stride + ((uint32_t)sm - q * (uint32_t)hop)] = to_word(envelope_at(x, a.n_in, g0 + sm));
+                stage[q * (uint32_t)stride + ((uint32_t)sm - q * (uint32_t)hop)] = to_word(row_at(x, a.n_in, g0 + sm));
             }
         }
         __syncthreads();
@@ -134,16 +134,13 @@ int sushi_hip_envelope(const void* in_dev, int dtype, int64_t n_in, int64_t in_s
     EnvelopeStage staged;
     const int rc = stage_envelope(dtype, n_in, in_start, hop, span, out_len, staged);
     if (rc != SUSHI_HIP_OK) return rc;
-    const bool u8 = dtype == SUSHI_HIP_U8;
-    const int size = u8 ? 1 : 4;
-    if (((uintptr_t)in_dev & (size - 1)) || ((uintptr_t)out_dev & (size - 1))) return SUSHI_HIP_EALIGN;
+    if (!row_aligned(in_dev, dtype) || !row_aligned(out_dev, dtype)) return SUSHI_HIP_EALIGN;
 
     hipStream_t st = (hipStream_t)hip_stream;
     EnvelopeArgs a;
     a.in = in_dev; a.n_in = n_in; a.in_start = in_start; a.hop = hop; a.span = span; a.tile = staged.tile; a.n_tiles = staged.n_tiles;
     a.out = out_dev; a.out_len = out_len;
-    if (u8) hipLaunchKernelGGL(envelope_kernel<uint8_t>, dim3(staged.grid), dim3(ENVELOPE_THREADS), 0, st, a);
-    else hipLaunchKernelGGL(envelope_kernel<float>, dim3(staged.grid), dim3(ENVELOPE_THREADS), 0, st, a);
+    row_dispatch(dtype, [&](auto t) { hipLaunchKernelGGL(envelope_kernel<decltype(t)>, dim3(staged.grid), dim3(ENVELOPE_THREADS), 0, st, a); });
     return launch_ok();
 }); }
 

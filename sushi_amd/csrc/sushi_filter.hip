@@ -60,7 +60,7 @@ void filter_kernel(FilterArgs a) {
             T v[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u)
-                if (e0 + u * FILTER_THREADS < n_stage) v[u] = filter_at(x, a.n_in, g0 + e0 + u * FILTER_THREADS);
+                if (e0 + u * FILTER_THREADS < n_stage) v[u] = row_at(x, a.n_in, g0 + e0 + u * FILTER_THREADS);
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int32_t e = e0 + u * FILTER_THREADS;
@@ -162,15 +162,12 @@ int sushi_hip_filter(const void* in_dev, int dtype, int64_t n_in, int64_t in_sta
     FilterStage staged;
     const int rc = stage_filter(in_dev, dtype, n_in, in_start, taps_dev, n_taps, out_dev, out_len, staged);
     if (rc != SUSHI_HIP_OK) return rc;
-    const bool u8 = dtype == SUSHI_HIP_U8;
-    const int size = u8 ? 1 : 4;
-    if (((uintptr_t)in_dev & (size - 1)) || ((uintptr_t)out_dev & (size - 1)) || ((uintptr_t)taps_dev & 7)) return SUSHI_HIP_EALIGN;
+    if (!row_aligned(in_dev, dtype) || !row_aligned(out_dev, dtype) || ((uintptr_t)taps_dev & 7)) return SUSHI_HIP_EALIGN;
 
     FilterArgs a;
     a.in = in_dev; a.n_in = n_in; a.in_start = in_start; a.taps = taps_dev; a.n_taps = n_taps; a.tile = staged.tile;
     a.n_tiles = staged.n_tiles; a.out = out_dev; a.out_len = out_len;
-    if (u8) launch<uint8_t>(a, staged, (hipStream_t)hip_stream);
-    else launch<float>(a, staged, (hipStream_t)hip_stream);
+    row_dispatch(dtype, [&](auto t) { launch<decltype(t)>(a, staged, (hipStream_t)hip_stream); });
     return launch_ok();
 }); }
 

@@ -82,9 +82,7 @@ int sushi_hip_retime(const void* in_dev, int dtype, int64_t n_in, const SushiHip
     RetimeStage staged;
     const int rc = stage_retime(seg_host, n_seg, dtype, n_in, n_out, (uintptr_t)out_dev, staged);
     if (rc != SUSHI_HIP_OK) return rc;
-    const bool u8 = dtype == SUSHI_HIP_U8;
-    const int size = u8 ? 1 : 4;
-    if (((uintptr_t)mem_dev & 255) || ((uintptr_t)in_dev & (size - 1)) || ((uintptr_t)out_dev & (size - 1))) return SUSHI_HIP_EALIGN;
+    if (((uintptr_t)mem_dev & 255) || !row_aligned(in_dev, dtype) || !row_aligned(out_dev, dtype)) return SUSHI_HIP_EALIGN;
     if (mem_bytes < retime_layout_bytes(n_seg)) return SUSHI_HIP_ENOSPACE;
 
     hipStream_t st = (hipStream_t)hip_stream;
@@ -94,8 +92,7 @@ int sushi_hip_retime(const void* in_dev, int dtype, int64_t n_in, const SushiHip
         return SUSHI_HIP_ELAUNCH;
     RetimeArgs a;
     a.in = in_dev; a.n_in = n_in; a.seg = (const RetimeSeg*)mem_dev; a.n_seg = n_seg; a.n_tiles = staged.n_tiles; a.out = out_dev;
-    if (u8) hipLaunchKernelGGL(retime_kernel<uint8_t>, dim3(staged.grid), dim3(RETIME_THREADS), 0, st, a);
-    else hipLaunchKernelGGL(retime_kernel<float>, dim3(staged.grid), dim3(RETIME_THREADS), 0, st, a);
+    row_dispatch(dtype, [&](auto t) { hipLaunchKernelGGL(retime_kernel<decltype(t)>, dim3(staged.grid), dim3(RETIME_THREADS), 0, st, a); });
     return launch_ok();
 }); }
 

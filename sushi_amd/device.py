@@ -19,8 +19,7 @@ import torch
 from . import _native
 from .axis import method_code
 from .common import SushiError
-
-_DTYPE_CODE = {np.dtype(np.uint8): _native.U8, np.dtype(np.float32): _native.F32}
+from .rowcheck import DTYPE_CODE as _DTYPE_CODE
 
 
 def _require_gpu(device=None):

@@ -13,10 +13,10 @@ import numpy as np
 
 from . import _native
 from .common import Record, SushiError
+from .rowcheck import device_out, device_row, host_row, row_span
 
 MAX_HOP, MAX_SPAN, MAX_WINDOW = 256, 64, 4096        # hop, span, hop * span (sushi_hip_envelope)
 
-_DTYPES = {np.dtype(np.uint8): _native.U8, np.dtype(np.float32): _native.F32}
 _HOST_SAMPLES = 1 << 22      # input samples gathered per NumPy pass of envelope_host (bounds its temporaries)
 
 
@@ -25,10 +25,7 @@ def _check(n_in, in_start, hop, span, out_len):
     in_start, hop, span, out_len = int(in_start), int(hop), int(span), int(out_len)
     if not 1 <= hop <= MAX_HOP or not 1 <= span <= MAX_SPAN or hop * span > MAX_WINDOW:
         raise SushiError("envelope: hop in 1..256, span in 1..64, hop * span <= 4096")
-    if n_in < 1 or not 0 <= in_start <= n_in - 1:
-        raise SushiError("envelope: in_start lies outside the input")
-    if not 1 <= out_len < 1 << 40:
-        raise SushiError("envelope: 1 .. 2^40 - 1 outputs")
+    row_span("envelope", n_in, in_start, out_len)
     return in_start, hop, span, out_len
 
 
@@ -38,9 +35,7 @@ def envelope_host(samples, in_start, hop, span, out_len):
     |x[clip(in_start + b * hop + t, 0, n - 1)] - c|; output i sums B_{i-a} .. B_{i-a+span-1} in that order to E.  uint8: integers,
     min(255, (4 E + W) // (2 W)); float32: float64 running sums from 0.0 (one rounding per addition), (float32)((E + E) / W).
     samples: a 1-D uint8 / float32 array.  Returns out_len samples of its dtype."""
-    x = np.asarray(samples)
-    if x.ndim != 1 or x.dtype not in _DTYPES:
-        raise SushiError("envelope: a 1-D uint8 or float32 array")
+    x = host_row("envelope", samples)
     n = x.shape[0]
     in_start, hop, span, out_len = _check(n, in_start, hop, span, out_len)
     a, w = (span - 1) // 2, hop * span
@@ -76,21 +71,17 @@ def envelope_device(tensor, in_start, hop, span, out_len, out=None, hip_stream=N
     the current torch stream of the tensor's device)."""
     import torch
     from .device import _launch
-    codes = {torch.uint8: _native.U8, torch.float32: _native.F32}
-    if not isinstance(tensor, torch.Tensor) or tensor.dim() != 1 or not tensor.is_cuda or not tensor.is_contiguous() or \
-            tensor.dtype not in codes:
-        raise SushiError("envelope: a contiguous 1-D uint8 or float32 CUDA tensor")
+    code = device_row("envelope", tensor)
     n = int(tensor.shape[0])
     in_start, hop, span, out_len = _check(n, in_start, hop, span, out_len)
     L = _native.lib()
     dev = tensor.device
     if out is None:
         out = torch.empty(out_len, dtype=tensor.dtype, device=dev)
-    elif not isinstance(out, torch.Tensor) or out.dim() != 1 or out.dtype != tensor.dtype or out.device != dev or \
-            not out.is_contiguous() or int(out.shape[0]) != out_len:
-        raise SushiError("envelope: out must be a contiguous 1-D CUDA tensor of the input's dtype and device with out_len samples")
+    else:
+        device_out("envelope", tensor, out, out_len)
     _launch("sushi_hip_envelope", dev, None,
-            lambda mem, mem_bytes, st: L.sushi_hip_envelope(tensor.data_ptr(), codes[tensor.dtype], n, in_start, hop, span,
+            lambda mem, mem_bytes, st: L.sushi_hip_envelope(tensor.data_ptr(), code, n, in_start, hop, span,
                                                             out.data_ptr(), out_len, st),
             (tensor, out), hip_stream)
     return out

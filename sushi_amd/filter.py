@@ -12,10 +12,10 @@ import numpy as np
 
 from . import _native
 from .common import SushiError
+from .rowcheck import device_out, device_row, host_row, row_span
 
 MAX_TAPS = 2047                                      # T: odd, 1 .. 2047 (sushi_hip_filter)
 
-_DTYPES = {np.dtype(np.uint8): _native.U8, np.dtype(np.float32): _native.F32}
 _HOST_OUTPUTS = 1 << 18      # outputs formed per NumPy pass of filter_host (bounds its temporaries)
 
 
@@ -24,10 +24,7 @@ def _check(n_in, in_start, n_taps, out_len):
     in_start, out_len = int(in_start), int(out_len)
     if not 1 <= n_taps <= MAX_TAPS or not n_taps & 1:
         raise SushiError("filter: an odd number of taps in 1..2047")
-    if n_in < 1 or not 0 <= in_start <= n_in - 1:
-        raise SushiError("filter: in_start lies outside the input")
-    if not 1 <= out_len < 1 << 40:
-        raise SushiError("filter: 1 .. 2^40 - 1 outputs")
+    row_span("filter", n_in, in_start, out_len)
     return in_start, out_len
 
 
@@ -45,9 +42,7 @@ def filter_host(samples, in_start, taps, out_len):
     0.0 over k = 0 .. T - 1, in that order, of h[k] * d(in_start + i + k - a), the product and the sum rounding separately.
     float32: float32(acc + 0.5); uint8: floor(acc + 128.5) held to 0 .. 255 (a NaN gives 0).  samples: a 1-D uint8 / float32
     array.  Returns out_len samples of its dtype."""
-    x = np.asarray(samples)
-    if x.ndim != 1 or x.dtype not in _DTYPES:
-        raise SushiError("filter: a 1-D uint8 or float32 array")
+    x = host_row("filter", samples)
     h = _host_taps(taps)
     n, n_taps = x.shape[0], h.shape[0]
     in_start, out_len = _check(n, in_start, n_taps, out_len)
@@ -77,10 +72,7 @@ def filter_device(tensor, in_start, taps, out_len, out=None, hip_stream=None):
     to write into; None: a new one.  Asynchronous on hip_stream (default: the current torch stream of the tensor's device)."""
     import torch
     from .device import _launch
-    codes = {torch.uint8: _native.U8, torch.float32: _native.F32}
-    if not isinstance(tensor, torch.Tensor) or tensor.dim() != 1 or not tensor.is_cuda or not tensor.is_contiguous() or \
-            tensor.dtype not in codes:
-        raise SushiError("filter: a contiguous 1-D uint8 or float32 CUDA tensor")
+    code = device_row("filter", tensor)
     dev = tensor.device
     if isinstance(taps, torch.Tensor):
         if taps.dim() != 1 or taps.dtype != torch.float64 or taps.device != dev or not taps.is_contiguous():
@@ -95,11 +87,10 @@ def filter_device(tensor, in_start, taps, out_len, out=None, hip_stream=None):
     L = _native.lib()
     if out is None:
         out = torch.empty(out_len, dtype=tensor.dtype, device=dev)
-    elif not isinstance(out, torch.Tensor) or out.dim() != 1 or out.dtype != tensor.dtype or out.device != dev or \
-            not out.is_contiguous() or int(out.shape[0]) != out_len:
-        raise SushiError("filter: out must be a contiguous 1-D CUDA tensor of the input's dtype and device with out_len samples")
+    else:
+        device_out("filter", tensor, out, out_len)
     _launch("sushi_hip_filter", dev, None,
-            lambda mem, mem_bytes, st: L.sushi_hip_filter(tensor.data_ptr(), codes[tensor.dtype], n, in_start, h.data_ptr(), n_taps,
+            lambda mem, mem_bytes, st: L.sushi_hip_filter(tensor.data_ptr(), code, n, in_start, h.data_ptr(), n_taps,
                                                           out.data_ptr(), out_len, st),
             (tensor, h, out), hip_stream)
     return out

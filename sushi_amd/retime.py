@@ -16,14 +16,13 @@ import numpy as np
 
 from . import _native
 from .common import Record, SushiError
+from .rowcheck import device_out, device_row, host_row
 
 MAX_TERM = 1 << 20           # numerator and denominator of a step (sushi_hip_retime)
 MAX_RATIO = 8                # a step lies in [1/8, 8]
 STANDARD_SPEEDS = (Fraction(1), Fraction(25, 24), Fraction(24, 25), Fraction(1001, 960), Fraction(960, 1001),
                    Fraction(1001, 1000), Fraction(1000, 1001))
 AMBIGUITY = 0.25             # the best candidate's median score must be at most this times the runner-up's
-
-_DTYPES = {np.dtype(np.uint8): _native.U8, np.dtype(np.float32): _native.F32}
 
 
 def as_ratio(speed):
@@ -94,9 +93,7 @@ def retime_host(samples, segments, out=None):
     y = x[j] + w * (x[j1] - x[j]) in float64; float32 output (float32)y, uint8 output (uint8)(y + 0.5).
     samples: a 1-D uint8 / float32 array; segments: (in_start, out_off, out_len, num, den) each.  out: an array of that dtype to
     write into (samples outside every segment keep their value); None: zeros of the smallest length that holds the segments."""
-    x = np.asarray(samples)
-    if x.ndim != 1 or x.dtype not in _DTYPES:
-        raise SushiError("retime: a 1-D uint8 or float32 array")
+    x = host_row("retime", samples)
     n = x.shape[0]
     seg, need = _segments(segments, n, None if out is None else out.shape[0])
     if out is None:
@@ -130,21 +127,17 @@ def retime_device(tensor, segments, out=None, hip_stream=None):
     holds the segments, zero outside them.  Asynchronous on hip_stream (default: the current torch stream of the tensor's device)."""
     import torch
     from .device import _launch
-    codes = {torch.uint8: _native.U8, torch.float32: _native.F32}
-    if not isinstance(tensor, torch.Tensor) or tensor.dim() != 1 or not tensor.is_cuda or not tensor.is_contiguous() or \
-            tensor.dtype not in codes:
-        raise SushiError("retime: a contiguous 1-D uint8 or float32 CUDA tensor")
+    code = device_row("retime", tensor)
     n = int(tensor.shape[0])
     seg, need = _segments(segments, n, None if out is None else int(out.shape[0]))
     L = _native.lib()
     dev = tensor.device
     if out is None:
         out = torch.zeros(need, dtype=tensor.dtype, device=dev)
-    elif not isinstance(out, torch.Tensor) or out.dim() != 1 or out.dtype != tensor.dtype or out.device != dev or \
-            not out.is_contiguous():
-        raise SushiError("retime: out must be a contiguous 1-D CUDA tensor of the input's dtype and device")
+    else:
+        device_out("retime", tensor, out)
     _launch("sushi_hip_retime", dev, L.sushi_hip_retime_bytes(seg.shape[0]),
-            lambda mem, mem_bytes, st: L.sushi_hip_retime(tensor.data_ptr(), codes[tensor.dtype], n, seg.ctypes.data, seg.shape[0],
+            lambda mem, mem_bytes, st: L.sushi_hip_retime(tensor.data_ptr(), code, n, seg.ctypes.data, seg.shape[0],
                                                           out.data_ptr(), int(out.shape[0]), mem, mem_bytes, st),
             (tensor, out), hip_stream)
     return out

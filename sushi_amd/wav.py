@@ -18,6 +18,10 @@ bit-identical; it is what the CPU tests compare with the reference-generated gol
 How a stream comes into being: every file is read by ``_load_mixes`` (one pass, one row of frames per mix), every row of frames
 becomes a stream's row in ``_build`` (the GPU or ``_build_host``; the numbers of the row's layout are ``row.row_layout``'s on both),
 and every finished row is taken over by ``_adopt``, which alone makes an instance a live stream.
+
+How one is derived from another: ``retimed``, ``envelope`` and ``filtered`` each state the new stream's layout and the call that
+writes its body, and ``_derive`` does the rest -- the refusal of a stream without a body, the GPU or NumPy, the row the GPU reads
+(``_device_row``), the new row, its pads, its host copy, ``_adopt``.
 """
 import logging
 import os
@@ -829,6 +833,45 @@ class WavStream(object):
                                 method=method, with_lines=with_lines, max_bytes=drift.MAX_BYTES if max_bytes is None else int(max_bytes),
                                 clamp=clamp, capacity=capacity)
 
+    # ------------------------------------------------------------------ one stream derived from another
+    def _device_row(self, dev):
+        """This stream's row as a tensor on `dev`: the mirror's if it lives there, else the GPU load pipeline's row if that does,
+        else an upload of self.data[0].  Neither self._dev nor self._dev_row changes."""
+        if self._dev is not None and self._dev.device == dev:
+            return self._dev.raw
+        if self._dev_row is not None and self._dev_row.device == dev:
+            return self._dev_row
+        import torch
+        return torch.from_numpy(self.data[0]).to(dev)
+
+    def _derive(self, who, plan):
+        """A new live stream made from this one's row -- retimed, envelope and filtered end here.  plan(padding_size, sample_count),
+        called once the body is known to lie inside the row, returns (sample_rate, padding_size, sample_count, on_host, on_device)
+        of the new stream and its two writers: on_host(row, new) and on_device(row, new) write the body of the new row `new`
+        (2 * padding_size + sample_count samples: an array, a tensor) from this stream's `row`.  On the GPU when there is one (the
+        new row stays in HBM for the matching), else in NumPy; both pads are then filled as the loader fills them."""
+        pad, count, total = int(self.padding_size), int(self.sample_count), int(self.data.shape[1])
+        if count < 1 or pad < 0 or pad + count > total:
+            raise SushiError('%s: the stream has no body inside its row' % who)
+        new_rate, new_pad, new_count, on_host, on_device = plan(pad, count)
+        if self._use_gpu():
+            import torch
+            dev = torch_device("cuda" if self._device is None else self._device)
+            row = self._device_row(dev)
+            with torch.cuda.device(dev):
+                dev_row = torch.empty(2 * new_pad + new_count, dtype=row.dtype, device=dev)
+                on_device(row, dev_row)
+                fill_pads(dev_row, new_pad)
+                data = dev_row.cpu().numpy().reshape(1, -1)
+        else:
+            dev_row = None
+            data = np.empty((1, 2 * new_pad + new_count), self.data.dtype)
+            on_host(self.data[0], data[0])
+            fill_pads(data[0], new_pad)
+        new = self.__class__.__new__(self.__class__)
+        new._adopt(data, dev_row, new_rate, new_count, new_pad, self._device)
+        return new
+
     # ------------------------------------------------------------------ another clock
     def retimed(self, speed):
         """This stream on the clock of a destination it plays `speed` times as fast as (sushi_amd.retime: 25/24 for PAL-sped-up
@@ -840,31 +883,13 @@ class WavStream(object):
         result are ordinary views: every search method and SpeculativeStream take them as they are."""
         from .retime import as_ratio, retime_device, retime_host, speed_segment
         s = as_ratio(speed)
-        pad, count, total = int(self.padding_size), int(self.sample_count), int(self.data.shape[1])
-        if count < 1 or pad < 0 or pad + count > total:
-            raise SushiError('retimed: the stream has no body inside its row')
-        new_count = ((count - 1) * s.numerator) // s.denominator + 1
-        segment = [speed_segment(s, pad, pad, new_count)]
-        if self._use_gpu():
-            import torch
-            dev = torch_device("cuda" if self._device is None else self._device)
-            if self._dev is not None and self._dev.device == dev:
-                row = self._dev.raw
-            elif self._dev_row is not None and self._dev_row.device == dev:
-                row = self._dev_row
-            else:
-                row = torch.from_numpy(self.data[0]).to(dev)
-            with torch.cuda.device(dev):
-                dev_row = retime_device(row, segment, out=torch.empty(2 * pad + new_count, dtype=row.dtype, device=dev))
-                fill_pads(dev_row, pad)
-                data = dev_row.cpu().numpy().reshape(1, -1)
-        else:
-            dev_row = None
-            data = retime_host(self.data[0], segment, out=np.zeros(2 * pad + new_count, self.data.dtype)).reshape(1, -1)
-            fill_pads(data[0], pad)
-        new = self.__class__.__new__(self.__class__)
-        new._adopt(data, dev_row, self.sample_rate, new_count, self.padding_size, self._device)
-        return new
+
+        def plan(pad, count):
+            new_count = ((count - 1) * s.numerator) // s.denominator + 1
+            segment = [speed_segment(s, pad, pad, new_count)]
+            return (self.sample_rate, self.padding_size, new_count,
+                    lambda row, new: retime_host(row, segment, out=new), lambda row, new: retime_device(row, segment, out=new))
+        return self._derive('retimed', plan)
 
     # ------------------------------------------------------------------ the loudness contour
     def envelope(self, hop=8, span=4):
@@ -880,32 +905,16 @@ class WavStream(object):
         (sushi_hip_envelope; the row stays in HBM for the matching), else in NumPy -- bit for bit the same.  The result is an
         ordinary stream: every search method, SpeculativeStream, retimed and estimate_speed take it as it is."""
         from .envelope import envelope_device, envelope_host, envelope_layout
-        pad, count, total = int(self.padding_size), int(self.sample_count), int(self.data.shape[1])
-        if count < 1 or pad < 0 or pad + count > total:
-            raise SushiError('envelope: the stream has no body inside its row')
-        new_rate, new_pad, new_count = envelope_layout(self.sample_rate, pad, count, hop)
-        if self._use_gpu():
-            import torch
-            dev = torch_device("cuda" if self._device is None else self._device)
-            if self._dev is not None and self._dev.device == dev:
-                row = self._dev.raw
-            elif self._dev_row is not None and self._dev_row.device == dev:
-                row = self._dev_row
-            else:
-                row = torch.from_numpy(self.data[0]).to(dev)
-            with torch.cuda.device(dev):
-                dev_row = torch.empty(2 * new_pad + new_count, dtype=row.dtype, device=dev)
-                envelope_device(row, pad, hop, span, new_count, out=dev_row[new_pad:new_pad + new_count])
-                fill_pads(dev_row, new_pad)
-                data = dev_row.cpu().numpy().reshape(1, -1)
-        else:
-            dev_row = None
-            data = np.empty((1, 2 * new_pad + new_count), self.data.dtype)
-            data[0, new_pad:new_pad + new_count] = envelope_host(self.data[0], pad, hop, span, new_count)
-            fill_pads(data[0], new_pad)
-        new = self.__class__.__new__(self.__class__)
-        new._adopt(data, dev_row, new_rate, new_count, new_pad, self._device)
-        return new
+
+        def plan(pad, count):
+            new_rate, new_pad, new_count = envelope_layout(self.sample_rate, pad, count, hop)
+            body = slice(new_pad, new_pad + new_count)
+
+            def on_host(row, new):
+                new[body] = envelope_host(row, pad, hop, span, new_count)
+            return (new_rate, new_pad, new_count, on_host,
+                    lambda row, new: envelope_device(row, pad, hop, span, new_count, out=new[body]))
+        return self._derive('envelope', plan)
 
     # ------------------------------------------------------------------ a band removed
     def filtered(self, low=None, high=None, stop=False, n_taps=255, taps=None):
@@ -920,29 +929,13 @@ class WavStream(object):
         the matching), else in NumPy -- bit for bit the same.  The result is an ordinary stream: every search method,
         SpeculativeStream, retimed and envelope take it as it is."""
         from .filter import band_taps, filter_device, filter_host
-        pad, count, total = int(self.padding_size), int(self.sample_count), int(self.data.shape[1])
-        if count < 1 or pad < 0 or pad + count > total:
-            raise SushiError('filtered: the stream has no body inside its row')
-        h = band_taps(self.sample_rate, low, high, n_taps, stop) if taps is None else np.asarray(taps, np.float64)
-        if self._use_gpu():
-            import torch
-            dev = torch_device("cuda" if self._device is None else self._device)
-            if self._dev is not None and self._dev.device == dev:
-                row = self._dev.raw
-            elif self._dev_row is not None and self._dev_row.device == dev:
-                row = self._dev_row
-            else:
-                row = torch.from_numpy(self.data[0]).to(dev)
-            with torch.cuda.device(dev):
-                dev_row = torch.empty(2 * pad + count, dtype=row.dtype, device=dev)
-                filter_device(row, pad, h, count, out=dev_row[pad:pad + count])
-                fill_pads(dev_row, pad)
-                data = dev_row.cpu().numpy().reshape(1, -1)
-        else:
-            dev_row = None
-            data = np.empty((1, 2 * pad + count), self.data.dtype)
-            data[0, pad:pad + count] = filter_host(self.data[0], pad, h, count)
-            fill_pads(data[0], pad)
-        new = self.__class__.__new__(self.__class__)
-        new._adopt(data, dev_row, self.sample_rate, count, self.padding_size, self._device)
-        return new
+
+        def plan(pad, count):
+            h = band_taps(self.sample_rate, low, high, n_taps, stop) if taps is None else np.asarray(taps, np.float64)
+            body = slice(pad, pad + count)
+
+            def on_host(row, new):
+                new[body] = filter_host(row, pad, h, count)
+            return (self.sample_rate, self.padding_size, count, on_host,
+                    lambda row, new: filter_device(row, pad, h, count, out=new[body]))
+        return self._derive('filtered', plan)

@@ -35,7 +35,7 @@ def test_every_source_file_is_in_the_build_lists():
     assert len(written) >= 14                       # (the listing saw the directory: 5 headers and 9 parts of the FFT unit)
     assert [f for f in written if not any(f in d for d in deps.values())] == []
     # the scan is per unit: two units' exact sets
-    common = {header, "sushi_common.hpp", "sushi_internal.hpp", "sushi_geometry.hpp", "stream_core.hpp"}
+    common = {header, "sushi_common.hpp", "sushi_internal.hpp", "sushi_geometry.hpp", "stream_core.hpp", "row_core.hpp"}
     generated = {os.path.relpath(p, build.CSRC) for p, _writer in build.GENERATED}
     assert len(generated) == 4 and all(f.startswith("_gen_") for f in generated)
     assert deps["sushi_load"] == common | {"sushi_load.hip", "downmix_core.hpp"}
