@@ -66,7 +66,8 @@ extern "C" {
                                      sushi_hip_track_order_margins_wide;
                                      13 (additive): SUSHI_HIP_PCM_*, sushi_hip_load_decode_format, sushi_hip_load_decode_mix_format;
                                      13 (additive): sushi_hip_envelope;
-                                     13 (additive): sushi_hip_filter */
+                                     13 (additive): sushi_hip_filter;
+                                     13 (additive): sushi_hip_level */
 
 #if defined(__GNUC__)
 #define SUSHI_HIP_API __attribute__((visibility("default")))
@@ -501,6 +502,33 @@ SUSHI_HIP_API int sushi_hip_envelope(const void* in_dev, int dtype, int64_t n_in
  * outside [1, 2047]; EALIGN: in_dev / out_dev not aligned to their sample type, taps_dev not to 8 bytes. */
 SUSHI_HIP_API int sushi_hip_filter(const void* in_dev, int dtype, int64_t n_in, int64_t in_start,
                                    const double* taps_dev, int32_t n_taps, void* out_dev, int64_t out_len, void* hip_stream);
+
+/* ---- levelling: a row divided by its local level, at its own rate (13, additive) ---------------
+ * A normalised score weights each instant by its energy.  Two mono dubs share the music-and-effects bed and carry a louder speech
+ * of their own: the unrelated speech decides the score, and the bed in the pauses between words counts for nothing; a capture
+ * through an AGC or a broadcast compressor loses the same.  This call divides every sample's deviation by the mean absolute
+ * deviation over W samples around it, in an arithmetic stated to the bit, so that the pauses count as much as the words.
+ * W = window, odd in [1, 1023]; h = (W - 1) / 2; c = sushi_hip_centre(dtype); H the type's half range (SUSHI_HIP_U8: 128.0;
+ * SUSHI_HIP_F32: 0.5); d(j) = x[clamp(j, 0, n_in - 1)] - c (SUSHI_HIP_U8: an integer; SUSHI_HIP_F32: one float64 subtraction).
+ * Output i, 0 <= i < out_len, with g = in_start + i:
+ *     E   = |d(g - h)| + |d(g - h + 1)| + ... + |d(g - h + W - 1)|
+ *           SUSHI_HIP_U8:  an exact integer (at most 128 * 1023), whichever way it is summed
+ *           SUSHI_HIP_F32: a float64 running sum from 0.0 in that order, every addition rounded once (no pairwise sum, no sliding
+ *                          update)
+ *     fw  = (floor * H) * (double)W                     two float64 multiplications, in that order
+ *     den = ((double)E + fw) * peak
+ *     q   = ((double)d(g) * (double)W) / den            one product, one division; a NaN q becomes 0; then q is held to [-1, 1]
+ *     SUSHI_HIP_F32: out = (float)(0.5 + 0.5 * q)
+ *     SUSHI_HIP_U8:  out = min(255, (int)floor(q * 128.0 + 128.5))
+ * so a NumPy restatement equals the result bit for bit.  floor, a fraction of the half range, keeps digital silence at the centre
+ * and quantisation noise from being blown up to full scale (1.0 / 128: one step of a uint8 stream); the local level times peak
+ * maps to full scale (8.0 leaves the clamp to a few samples in a million of programme material).  Reads outside the row see its edge samples.
+ * in_dev / out_dev: n_in / out_len samples of `dtype`, naturally aligned, not overlapping.  One launch, no workspace, no device
+ * allocation.  Asynchronous; stateless (any thread).  Checked before any HIP call -- EINVAL: a null pointer, an unknown dtype,
+ * n_in < 1 (or >= 2^62), in_start outside [0, n_in - 1], out_len < 1 or >= 2^40, window even or outside [1, 1023], floor or peak
+ * not finite or not > 0; EALIGN: in_dev / out_dev not aligned to their sample type. */
+SUSHI_HIP_API int sushi_hip_level(const void* in_dev, int dtype, int64_t n_in, int64_t in_start,
+                                  int32_t window, double floor, double peak, void* out_dev, int64_t out_len, void* hip_stream);
 
 /* ---- joint search: the one shift a group of score rows shares (13, additive) -----------------
  * Events of one scene share one shift, and a lone search of a short or repeated pattern may prefer a decoy in its window.  The

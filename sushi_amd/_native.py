@@ -183,6 +183,8 @@ def lib():
     L.sushi_hip_envelope.argtypes = [vp, ci, i64, i64, i32, i32, vp, i64, vp]
     L.sushi_hip_filter.restype = ci
     L.sushi_hip_filter.argtypes = [vp, ci, i64, i64, vp, i32, vp, i64, vp]
+    L.sushi_hip_level.restype = ci
+    L.sushi_hip_level.argtypes = [vp, ci, i64, i64, i32, dbl, dbl, vp, i64, vp]
     L.sushi_hip_joint_bytes.restype = sz
     L.sushi_hip_joint_bytes.argtypes = [ci, ci]
     L.sushi_hip_joint_reduce.restype = ci

@@ -72,6 +72,10 @@ UNITS = [
     # a row through a FIR filter of float64 taps about the sample type's centre: a tile's samples and the taps staged in LDS, a few
     # consecutive outputs a thread (filter_core.hpp: the arithmetic, the tile, and the call's host side; row_core.hpp as above)
     ("sushi_filter", ["-ffp-contract=off"]),    # float64: product and sum round separately, in ascending tap order, as NumPy's
+    # a row divided by its local level, the mean absolute deviation over W samples around each: float32 sums |d| in float64 over
+    # a tile staged in LDS, a few consecutive outputs a thread; uint8 takes the window sums from a prefix sum of the tile (wave
+    # scans) (level_core.hpp: the arithmetic, both tiles, and the call's host side; row_core.hpp as above)
+    ("sushi_level", ["-ffp-contract=off"]),     # float64: the sum's additions in ascending order, the quotient's operations one by one, as NumPy's
     # overlap-save FFT path; its parts, by stage, are csrc/sushi_fft_*.inc (included inside its anonymous namespace); the plan of
     # a batch (plan_core.hpp), what a handle holds about its requests and how it is staged (batch_core.hpp) and what a run decides
     # (run_policy.hpp) are host only

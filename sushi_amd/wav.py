@@ -19,7 +19,7 @@ How a stream comes into being: every file is read by ``_load_mixes`` (one pass, 
 becomes a stream's row in ``_build`` (the GPU or ``_build_host``; the numbers of the row's layout are ``row.row_layout``'s on both),
 and every finished row is taken over by ``_adopt``, which alone makes an instance a live stream.
 
-How one is derived from another: ``retimed``, ``envelope`` and ``filtered`` each state the new stream's layout and the call that
+How one is derived from another: ``retimed``, ``envelope``, ``filtered`` and ``levelled`` each state the new stream's layout and the call that
 writes its body, and ``_derive`` does the rest -- the refusal of a stream without a body, the GPU or NumPy, the row the GPU reads
 (``_device_row``), the new row, its pads, its host copy, ``_adopt``.
 """
@@ -845,7 +845,7 @@ class WavStream(object):
         return torch.from_numpy(self.data[0]).to(dev)
 
     def _derive(self, who, plan):
-        """A new live stream made from this one's row -- retimed, envelope and filtered end here.  plan(padding_size, sample_count),
+        """A new live stream made from this one's row -- retimed, envelope, filtered and levelled end here.  plan(padding_size, sample_count),
         called once the body is known to lie inside the row, returns (sample_rate, padding_size, sample_count, on_host, on_device)
         of the new stream and its two writers: on_host(row, new) and on_device(row, new) write the body of the new row `new`
         (2 * padding_size + sample_count samples: an array, a tensor) from this stream's `row`.  On the GPU when there is one (the
@@ -939,3 +939,31 @@ class WavStream(object):
             return (self.sample_rate, self.padding_size, count, on_host,
                     lambda row, new: filter_device(row, pad, h, count, out=new[body]))
         return self._derive('filtered', plan)
+
+    # ------------------------------------------------------------------ the local level divided out
+    def levelled(self, window=129, floor=1 / 128, peak=8.0):
+        """This stream with every sample divided by the local level (sushi_amd.level): a new live WavStream with
+        the same sample rate, padding_size, sample_count and sample type.  The local level is the mean absolute deviation, about
+        the sample type's nominal centre, over `window` samples around the sample (odd, up to 1023; 129 is about 10 ms at
+        12 kHz); level * peak maps to full scale and what exceeds it is clamped; `floor`, a fraction of the half range, is added
+        to the level so that digital silence stays at the centre and quantisation noise is not blown up to full scale (1 / 128:
+        one step of a uint8 stream).  What it is for: two mono dubs that share a music-and-effects bed under louder speech of
+        their own -- a normalised score weights each instant by its energy, so the unrelated speech decides it; levelled, the
+        bed in the pauses between words and syllables counts as much as the words -- and captures through an AGC or a broadcast
+        compressor.  The body is levelled with reads past the body seeing the pads and reads past the row its edge samples; both
+        pads are then filled as the loader fills them.  Source and destination of a search are levelled alike, so shifts are
+        unaffected.  filtered(...).levelled() composes (a band removed first, then the level); levelled().envelope() is nearly
+        flat by construction and therefore useless.  On the GPU when there is one (sushi_hip_level; the row stays in HBM for the
+        matching), else in NumPy -- bit for bit the same.  The result is an ordinary stream: every search method,
+        SpeculativeStream, retimed and filtered take it as it is."""
+        from .level import _check, level_device, level_host
+
+        def plan(pad, count):
+            _check(pad + count, pad, window, floor, peak, count)
+            body = slice(pad, pad + count)
+
+            def on_host(row, new):
+                new[body] = level_host(row, pad, window, floor, peak, count)
+            return (self.sample_rate, self.padding_size, count, on_host,
+                    lambda row, new: level_device(row, pad, window, floor, peak, count, out=new[body]))
+        return self._derive('levelled', plan)
