@@ -325,6 +325,16 @@ SUSHI_HIP_API int sushi_hip_batch_diagnostics(SushiHipBatch* batch, SushiHipBatc
  * feed: the worst-case bound does not form them) -- for tests and tools that look at how sharp the exclusion is.  *n_pairs
  * in: the capacity of the arrays, out: how many pairs there are.  Synchronises. */
 SUSHI_HIP_API int sushi_hip_batch_pair_bounds(SushiHipBatch* batch, float* slb_host, float* acc_host, int64_t* n_pairs);
+/* FFT path, for the tests of the bound pass: after a run that went through the pair exclusion, launch the LAST sub-batch's bound
+ * pass once more on what the run left in the workspace -- the same accumulators, norms and tables, bit for bit, whichever route is
+ * asked for, which two runs do not have (several of those are float atomic sums) -- and return every pair's bound.  by_wave: 0 four
+ * pairs a wave where the patterns allow it (the default route), 1 a wave a pair (SUSHI_HIP_SLB=wave).  pass: 0 slb_kernel over
+ * every pair; 1 slb_list_kernel over the list the second look left (band-split form only; EINVAL otherwise); 2 slb_kernel in
+ * prediction mode, votes_host[2] = pairs looked at, pairs whose bound leaves room.  Overwrites the stored bounds (a following run
+ * makes them again).  *n_pairs in: the capacity of slb_host (NULL: not wanted), out: the pairs; 0 where no run left a bound pass.
+ * Synchronises. */
+SUSHI_HIP_API int sushi_hip_batch_bounds_again(SushiHipBatch* batch, int by_wave, int pass, float* slb_host, int32_t* votes_host,
+                                               int64_t* n_pairs);
 /* FFT path, after a run, for tests and tools: where the LAST sub-batch's pattern spectra and products live in the batch's workspace
  * (packed halves, 4 bytes per bin, bin f of a whole row at sushi_hip_fft_slot_of_bin(f), of a low row at
  * sushi_hip_fft_low_slot_of_bin(f)): TSPEC [segments][N], Y [block pairs][N] -- whole rows exist only for the pairs that were
@@ -341,6 +351,16 @@ SUSHI_HIP_API int sushi_hip_batch_pair_bounds(SushiHipBatch* batch, float* slb_h
 #define SUSHI_HIP_WS_Y_LOW 3
 #define SUSHI_HIP_WS_TNORM_REST 4   /* float32 per pattern segment: the SQUARED norm of its stored halves outside the band */
 #define SUSHI_HIP_WS_TSPEC_HALF 5
+/* ... and what the pair exclusion left of the LAST sub-batch, for the tests of its passes: SLIST [block pairs] int32, the pairs the
+ * first bound left (indices inside the sub-batch, in no fixed order; an argmin run in the band-split form writes its survivors'
+ * work items over it unless SUSHI_HIP_REST_ROWS=search); SLIST2 the same behind the second look (band-split form); SCOUNT the
+ * sub-batch's eight int32 count words, [0] the entries of SLIST and [5] those of SLIST2; MARKS [block pairs] bytes, bit 0 the pair
+ * is audited, bit 1 it is listed, bit 2 by the second look's audit; PAIR_LB [block pairs] float32, +inf for an excluded pair. */
+#define SUSHI_HIP_WS_SLIST 6
+#define SUSHI_HIP_WS_SLIST2 7
+#define SUSHI_HIP_WS_SCOUNT 8
+#define SUSHI_HIP_WS_MARKS 9
+#define SUSHI_HIP_WS_PAIR_LB 10
 SUSHI_HIP_API int sushi_hip_batch_workspace_view(SushiHipBatch* batch, int which, void** ptr_dev, size_t* bytes);
 SUSHI_HIP_API void sushi_hip_batch_destroy(SushiHipBatch* batch);
 

@@ -38,6 +38,7 @@ STAGE_KERNELS = {"tspec": "tspec_real_kernel|tspec_kernel", "mac": "mac_kernel",
                  "finish": "collect_kernel+exact_tiles_kernel+unpack_keys_kernel", "bound": "bound_low_kernel|bound_kernel"}
 EXCLUSION = {"auto": 0, "always": 1, "never": 2, "band": 3, "whole": 4}        # SUSHI_HIP_EXCLUDE_*
 WS_TSPEC, WS_Y, WS_TSPEC_LOW, WS_Y_LOW, WS_TNORM_REST, WS_TSPEC_HALF = range(6)                           # SUSHI_HIP_WS_*
+WS_SLIST, WS_SLIST2, WS_SCOUNT, WS_MARKS, WS_PAIR_LB = range(6, 11)              # ... what the pair exclusion left, for its tests
 BOUND_MODEL = {"worst_case": 0, "statistical": 1}                              # SUSHI_HIP_BOUND_*
 # every kernel a stage's HIP-event span covers (profiles/pmc_traffic.json is keyed by kernel)
 STAGE_KERNEL_SETS = {"tspec": ("tspec_real_kernel", "tspec_kernel"), "mac": ("mac_kernel", "mac_long_kernel"),
@@ -165,6 +166,9 @@ def lib():
     L.sushi_hip_batch_set_bound_model.argtypes = [vp, ci]
     L.sushi_hip_batch_pair_bounds.restype = ci
     L.sushi_hip_batch_pair_bounds.argtypes = [vp, vp, vp, ctypes.POINTER(i64)]
+    if hasattr(L, "sushi_hip_batch_bounds_again"):          # (SUSHI_HIP_LIB may name a library built before the tests' seam)
+        L.sushi_hip_batch_bounds_again.restype = ci
+        L.sushi_hip_batch_bounds_again.argtypes = [vp, ci, ci, vp, vp, ctypes.POINTER(i64)]
     L.sushi_hip_batch_workspace_view.restype = ci
     L.sushi_hip_batch_workspace_view.argtypes = [vp, ci, pvp, ctypes.POINTER(sz)]
     L.sushi_hip_batch_destroy.restype = None

@@ -915,6 +915,15 @@ SUSHI_HHD int lslot_of_bin(int f) {
     const int j = b == 0 ? 0 : (b == 2 ? 1 : (b == 12 ? 2 : 3));
     return (((g * 4 + (d2 >> 2)) * 32 + 16 * kq + ((d3 << 2) | (d2 & 3))) << 2) + j;
 }
+// A low row as the INPUT of Plan<13> (the second look, bound_low_exact_kernel): register r of thread tid is index
+// in_index<13>(tid, r) = 2 tid + (r >> 3) + 1024 (r & 7) of the N/2 grid, and the band is the indices below N/8 = 2048 and from
+// 3N/8 = 6144 on: r & 7 in {0, 1} and {6, 7}, WHATEVER the thread.  Those four are m = m0 + {0, 128, 768, 896}, d1 = kq + {0, 2, 12,
+// 14} of one column (d2, d3): the four sub-positions, in order, of ONE 16-byte entry.  So a thread's eight band registers are two
+// entries, one per b = r >> 3, and the other eight are zero.  (tests/host_second_look_check.cpp holds all three to in_index and
+// lslot_of_bin for every thread and register.)
+SUSHI_HHD constexpr bool sl_in_band(int r) { return (r & 7) < 2 || (r & 7) >= 6; }
+SUSHI_HHD constexpr int sl_sub(int r) { return (r & 7) < 2 ? (r & 7) : (r & 7) - 4; }      // sub-position of register r in its entry
+SUSHI_HHD int sl_entry(int tid, int b) { return lslot_of_bin(2 * tid + b) >> 2; }           // the entry of registers 8 b + {0, 1, 6, 7}
 // B operands of the K = 16 first pass (inverse transform, times 2^-10; high halves only): element j of lane l is row
 // k = 4 (l >> 4) + j of column n = l & 15.  form 0: real parts of the result, 1: imaginary parts.
 SUSHI_HHD double dft16_low_operand(int form, int l, int j) {

@@ -11,6 +11,8 @@
 //   direct_slots                  slots of a listed transform that get a workgroup each
 //   pilot_rows_route, pilot_rows_by_search                how the band-split form's pilots get their whole rows
 //   rest_rows_route, rest_rows_by_item                    the unit of work of the survivors' pass behind them
+//   slb_route, slb_by_wave                                how many lanes put a pair's lower bound together
+//   second_look_route, second_look_plain                  which body the second look's transform kernel has
 //   rest_pair_to_form, rest_item_starts, rest_item_take   how a search's surviving pairs are cut into that pass's work items
 //   tspec_route, tspec_real                               which transform the pattern segments' spectra come from
 //                                                         (the three the device calls as well: SUSHI_HHD)
@@ -164,6 +166,30 @@ inline int rest_rows_route(const char* setting) {
     return !strcmp(setting, "search") ? REST_ROWS_BY_SEARCH : -1;
 }
 inline bool rest_rows_by_item(int route) { return route != REST_ROWS_BY_SEARCH; }
+
+// How many lanes put a pair's lower bound together (slb_kernel, slb_list_kernel).  GROUP (the default): sixteen, four pairs a wave,
+// where the four pairs' patterns have up to sixteen segments; a wave a pair otherwise.  WAVE: a wave a pair throughout
+// (slb_wave_kernel, slb_list_wave_kernel), as before the groups; every stored value has the same bits either way.  Kept for A/B
+// measurements on one build and for the tests to compare with.  `setting` is SUSHI_HIP_SLB as the environment holds it (NULL or
+// empty: the default); -1: neither route's name.
+enum { SLB_BY_GROUP = 0, SLB_BY_WAVE = 1 };
+inline int slb_route(const char* setting) {
+    if (!setting || !*setting || !strcmp(setting, "group")) return SLB_BY_GROUP;
+    return !strcmp(setting, "wave") ? SLB_BY_WAVE : -1;
+}
+inline bool slb_by_wave(int route) { return route == SLB_BY_WAVE; }
+
+// The body of the second look's transform kernel.  AHEAD (the default): bound_low_exact_kernel -- the band's registers by their
+// index, the next slot requested ahead, one barrier for the maximum.  PLAIN: the body before that one
+// (bound_low_exact_plain_kernel), whose acc[2 pr] the default's equals bit for bit; kept for A/B measurements on one build and for
+// the tests to compare with.  `setting` is SUSHI_HIP_SECOND_LOOK as the environment holds it (NULL or empty: the default); -1:
+// neither route's name.
+enum { SECOND_LOOK_AHEAD = 0, SECOND_LOOK_PLAIN = 1 };
+inline int second_look_route(const char* setting) {
+    if (!setting || !*setting || !strcmp(setting, "ahead")) return SECOND_LOOK_AHEAD;
+    return !strcmp(setting, "plain") ? SECOND_LOOK_PLAIN : -1;
+}
+inline bool second_look_plain(int route) { return route == SECOND_LOOK_PLAIN; }
 
 // THE CUT of a search's pairs into the survivors' pass's work items.  An item is a run of the search's pairs that holds at most
 // REST_ITEM_PAIRS pairs TO FORM -- listed, and not the audit pair the first pass formed already --, named by its first such

@@ -174,7 +174,11 @@ struct SushiHipBatch {
     int pilot_rows = PILOT_ROWS_BY_SEARCH;  // how the pilots' whole rows are formed (run_policy.hpp; SUSHI_HIP_PILOT_ROWS=list: pair by pair, for A/B)
     int rest_rows = REST_ROWS_BY_ITEM;      // the survivors' pass's unit of work (run_policy.hpp; SUSHI_HIP_REST_ROWS=search: a whole search, for A/B)
     int tspec = TSPEC_REAL;                 // the pattern segments' transform (run_policy.hpp; SUSHI_HIP_TSPEC=complex: the full-size complex one, for A/B)
+    int slb = SLB_BY_GROUP;                 // lanes a pair in slb_kernel / slb_list_kernel (run_policy.hpp; SUSHI_HIP_SLB=wave: a wave a pair, for A/B)
+    int second_look = SECOND_LOOK_AHEAD;    // the second look's transform kernel (run_policy.hpp; SUSHI_HIP_SECOND_LOOK=plain: the body before, for A/B)
     int bound_model = SUSHI_HIP_BOUND_WORST_CASE;   // (default) / SUSHI_HIP_BOUND_STATISTICAL: how the excluded side's roundings enter slb
+    BoundArgs last_bounds;              // what the last bound pass of a run was launched with (sushi_hip_batch_bounds_again; valid: last_bounds_method >= 0)
+    int last_bounds_method = -1;
     BoundFault fault;                   // the tests' seam (SUSHI_HIP_TEST_BOUND_FAULT; period 0, the default: none)
     // AUTO learns from its own runs (Learnt): the last run's counts come back through 16 bytes of pinned host memory behind an
     // event that is only ever QUERIED: a run never waits for an earlier one.
@@ -378,8 +382,11 @@ static BoundArgs bound_args(const RunCtx& c, const SubView& v) {
 }
 
 static int launch_slb(const RunCtx& c, const SubView& v, const BoundArgs& x, hipStream_t st) {
+    // (a workgroup is four waves: of four pairs each, or of one)
+    constexpr int per_group = 4 * (64 / SLB_GROUP);
     return launch_method(c.method, [&](auto m) {
-        hipLaunchKernelGGL(slb_kernel<decltype(m)::value>, dim3((unsigned)((v.sb.pairs + 3) / 4)), dim3(256), 0, st, x); });
+        if (slb_by_wave(c.b->slb)) hipLaunchKernelGGL(slb_wave_kernel<decltype(m)::value>, dim3((unsigned)((v.sb.pairs + 3) / 4)), dim3(256), 0, st, x);
+        else hipLaunchKernelGGL(slb_kernel<decltype(m)::value>, dim3((unsigned)((v.sb.pairs + per_group - 1) / per_group)), dim3(256), 0, st, x); });
 }
 
 // the tests' seam: the stored bounds of the batch's faulted pairs read +inf from here on (bound_fault_kernel); called behind every
@@ -511,6 +518,7 @@ static int bound_pairs(const RunCtx& c, const SubView& v, hipStream_t st, const 
     };
     if (ba.worst_case) go(std::false_type()); else go(std::true_type());
     if (launch_ok() != SUSHI_HIP_OK || launch_slb(c, v, ba, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
+    c.b->last_bounds = ba; c.b->last_bounds_method = c.method;       // (host words only: sushi_hip_batch_bounds_again)
     if (c.b->fault.period > 0) return launch_bound_fault(c, v, st);
     return SUSHI_HIP_OK;
 }
@@ -520,10 +528,12 @@ static int bound_pairs(const RunCtx& c, const SubView& v, hipStream_t st, const 
 static int second_look(const RunCtx& c, const SubView& v, hipStream_t st, BoundArgs& ba) {
     ba.list = ba.slist; ba.list_count = ba.scount;
     ba.list2 = v.slist2; ba.list2_count = v.n_slist2;
-    hipLaunchKernelGGL(bound_low_exact_kernel, dim3(256 * 4), dim3(BLE_T), 0, st, ba);
+    if (second_look_plain(c.b->second_look)) hipLaunchKernelGGL(bound_low_exact_plain_kernel, dim3(256 * 4), dim3(BLE_T), 0, st, ba);
+    else hipLaunchKernelGGL(bound_low_exact_kernel, dim3(256 * 4), dim3(BLE_T), 0, st, ba);
     if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-    if (launch_method(c.method, [&](auto m) { hipLaunchKernelGGL(slb_list_kernel<decltype(m)::value>, dim3(256 * 2), dim3(256), 0, st, ba); }) !=
-        SUSHI_HIP_OK)
+    if (launch_method(c.method, [&](auto m) {
+            if (slb_by_wave(c.b->slb)) hipLaunchKernelGGL(slb_list_wave_kernel<decltype(m)::value>, dim3(256 * 2), dim3(256), 0, st, ba);
+            else hipLaunchKernelGGL(slb_list_kernel<decltype(m)::value>, dim3(256 * 2), dim3(256), 0, st, ba); }) != SUSHI_HIP_OK)
         return SUSHI_HIP_ELAUNCH;
     // (slb_list_kernel has just redone the listed pairs' bounds: a faulted audit pair's would be sound again, and the audit blind)
     if (c.b->fault.period > 0 && launch_bound_fault(c, v, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
@@ -553,7 +563,7 @@ static int exclude_pairs(const RunCtx& c, const SubView& v, hipStream_t st, cons
     if (band && by_search && launch_mac_rows(c, v, st, ba, ROWS_FIRST) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     if (band && launch_mac_list(c, v, st, ba.plist, nullptr, v.n_sub, nullptr, by_search ? 1 : 0) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     if (launch_ifft(c, ip, (unsigned)v.n_sub, st) != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
-    hipLaunchKernelGGL(survivor_kernel, dim3((unsigned)((sb.pairs + 255) / 256)), dim3(256), 0, st, ba);
+    hipLaunchKernelGGL(survivor_kernel, dim3((unsigned)((sb.pairs + SURVIVOR_THREADS - 1) / SURVIVOR_THREADS)), dim3(SURVIVOR_THREADS), 0, st, ba);
     if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
     ip.order = ba.slist; ip.count = ba.scount; ip.audit_mark = ba.audit_mark;
     if (!band) return SUSHI_HIP_OK;
@@ -709,7 +719,7 @@ static int run_sub_threshold(RunCtx& c, const SubView& v, hipStream_t st, const 
         if ((rc = mac_and_bound(c, v, st, &band, ba)) != SUSHI_HIP_OK) return rc;
         // (no pilot pair: every pair is listed or excluded on its bound alone; the audit of the exclusion lists one excluded pair
         // of every audited search all the same)
-        hipLaunchKernelGGL(survivor_kernel, dim3((unsigned)((sb.pairs + 255) / 256)), dim3(256), 0, st, ba);
+        hipLaunchKernelGGL(survivor_kernel, dim3((unsigned)((sb.pairs + SURVIVOR_THREADS - 1) / SURVIVOR_THREADS)), dim3(SURVIVOR_THREADS), 0, st, ba);
         if (launch_ok() != SUSHI_HIP_OK) return SUSHI_HIP_ELAUNCH;
         tp.lp.list = ba.slist; tp.lp.list_count = ba.scount;
         if (band) {
@@ -891,6 +901,7 @@ static int plan_and_upload(SushiHipBatch* b, const SushiHipRequest* req_host, in
         return SUSHI_HIP_ELAUNCH;
     std::swap(b->now, b->spare);
     b->forget_learnt();
+    b->last_bounds_method = -1;
     // (the host buffer lives in the handle: the copy may still be in flight when this returns)
     b->planned = hipMemcpyAsync(b->mem + b->now->lay.desc, b->now->upload.data(), b->now->upload.size(), hipMemcpyHostToDevice, st) == hipSuccess &&
                  hipEventRecord(b->uploaded, st) == hipSuccess;
@@ -918,6 +929,8 @@ int sushi_hip_batch_create(const SushiHipStream* dst, const SushiHipStream* src,
     if ((b->pilot_rows = pilot_rows_route(getenv("SUSHI_HIP_PILOT_ROWS"))) < 0) return SUSHI_HIP_EINVAL;
     if ((b->rest_rows = rest_rows_route(getenv("SUSHI_HIP_REST_ROWS"))) < 0) return SUSHI_HIP_EINVAL;
     if ((b->tspec = tspec_route(getenv("SUSHI_HIP_TSPEC"))) < 0) return SUSHI_HIP_EINVAL;
+    if ((b->slb = slb_route(getenv("SUSHI_HIP_SLB"))) < 0) return SUSHI_HIP_EINVAL;
+    if ((b->second_look = second_look_route(getenv("SUSHI_HIP_SECOND_LOOK"))) < 0) return SUSHI_HIP_EINVAL;
     const char* m = getenv("SUSHI_HIP_BOUND_MODEL");
     if (m && !strcmp(m, "statistical")) b->bound_model = SUSHI_HIP_BOUND_STATISTICAL;
     // (the tests' seam, DESIGN.md 3.2: a value that does not parse is refused -- a typo must not turn a fault test into a no-fault test)
@@ -1106,6 +1119,46 @@ int sushi_hip_batch_pair_bounds(SushiHipBatch* b, float* slb_host, float* acc_ho
     return SUSHI_HIP_OK;
 }); }
 
+int sushi_hip_batch_bounds_again(SushiHipBatch* b, int by_wave, int pass, float* slb_host, int32_t* votes_host, int64_t* n_pairs) {
+    return c_boundary([&]() -> int {
+    if (!b || !n_pairs || pass < 0 || pass > 2 || (by_wave != 0 && by_wave != 1)) return SUSHI_HIP_EINVAL;
+    if (!b->last.ran || b->path != SUSHI_HIP_PATH_FFT || b->last_bounds_method < 0) { *n_pairs = 0; return SUSHI_HIP_OK; }
+    hipStream_t st = b->last_stream;
+    if (hipStreamSynchronize(st) != hipSuccess) return SUSHI_HIP_ELAUNCH;
+    BoundArgs ba = b->last_bounds;
+    const int64_t cap = *n_pairs;
+    *n_pairs = ba.n_pairs;
+    if (slb_host && cap < ba.n_pairs) return SUSHI_HIP_ENOSPACE;
+    int votes[VOTE_SLOTS * VOTE_STRIDE];
+    if (pass == 2) {
+        ba.band = 2;
+        if (hipMemsetAsync(ba.band_votes, 0, sizeof(votes), st) != hipSuccess) return SUSHI_HIP_ELAUNCH;
+    }
+    if (pass == 1) {
+        // (the list the transforms took: the second look's in the band-split form, which is never overwritten)
+        if (ba.band != 1) return SUSHI_HIP_EINVAL;
+        const SubView v = last_sub(b);
+        ba.list = v.slist2; ba.list_count = v.n_slist2;
+    }
+    constexpr int per_group = 4 * (64 / SLB_GROUP);
+    const int rc = launch_method(b->last_bounds_method, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        if (pass == 1 && by_wave) hipLaunchKernelGGL(slb_list_wave_kernel<M>, dim3(256 * 2), dim3(256), 0, st, ba);
+        else if (pass == 1) hipLaunchKernelGGL(slb_list_kernel<M>, dim3(256 * 2), dim3(256), 0, st, ba);
+        else if (by_wave) hipLaunchKernelGGL(slb_wave_kernel<M>, dim3((unsigned)((ba.n_pairs + 3) / 4)), dim3(256), 0, st, ba);
+        else hipLaunchKernelGGL(slb_kernel<M>, dim3((unsigned)((ba.n_pairs + per_group - 1) / per_group)), dim3(256), 0, st, ba); });
+    if (rc != SUSHI_HIP_OK) return rc;
+    if (pass == 2 && hipMemcpyAsync(votes, ba.band_votes, sizeof(votes), hipMemcpyDeviceToHost, st) != hipSuccess) return SUSHI_HIP_ELAUNCH;
+    if (slb_host && hipMemcpyAsync(slb_host, ba.slb, (size_t)ba.n_pairs * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess)
+        return SUSHI_HIP_ELAUNCH;
+    if (hipStreamSynchronize(st) != hipSuccess) return SUSHI_HIP_ELAUNCH;
+    if (pass == 2 && votes_host) {
+        votes_host[0] = votes_host[1] = 0;
+        for (int k = 0; k < VOTE_SLOTS; ++k) { votes_host[0] += votes[k * VOTE_STRIDE]; votes_host[1] += votes[k * VOTE_STRIDE + 1]; }
+    }
+    return SUSHI_HIP_OK;
+}); }
+
 int sushi_hip_batch_workspace_view(SushiHipBatch* b, int which, void** ptr_dev, size_t* bytes) {
     if (!b || !ptr_dev || !bytes) return SUSHI_HIP_EINVAL;
     *ptr_dev = nullptr; *bytes = 0;
@@ -1138,6 +1191,11 @@ int sushi_hip_batch_workspace_view(SushiHipBatch* b, int which, void** ptr_dev, 
         case SUSHI_HIP_WS_TSPEC_LOW: *ptr_dev = v.tspec_low; *bytes = (size_t)v.sb.segs * LROW_BYTES; break;
         case SUSHI_HIP_WS_Y_LOW: *ptr_dev = v.ylow; *bytes = (size_t)v.sb.pairs * LROW_BYTES; break;
         case SUSHI_HIP_WS_TNORM_REST: *ptr_dev = v.tnorm_rest; *bytes = (size_t)v.sb.segs * sizeof(float); break;
+        case SUSHI_HIP_WS_SLIST: *ptr_dev = v.slist; *bytes = (size_t)v.sb.pairs * sizeof(int); break;
+        case SUSHI_HIP_WS_SLIST2: *ptr_dev = v.slist2; *bytes = (size_t)v.sb.pairs * sizeof(int); break;
+        case SUSHI_HIP_WS_SCOUNT: *ptr_dev = v.n_slist; *bytes = (size_t)SC_WORDS * sizeof(int); break;
+        case SUSHI_HIP_WS_MARKS: *ptr_dev = v.audit_mark; *bytes = (size_t)v.sb.pairs; break;
+        case SUSHI_HIP_WS_PAIR_LB: *ptr_dev = v.pair_lb; *bytes = (size_t)v.sb.pairs * sizeof(float); break;
         default: return SUSHI_HIP_EINVAL;
     }
     return SUSHI_HIP_OK;

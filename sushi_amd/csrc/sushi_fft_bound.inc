@@ -217,11 +217,19 @@ void bound_kernel(BoundArgs a) {
 // for every p of stretch j: Ein / Din = energy / sum of the centred samples over the G-aligned span inside every such window,
 // Eout = the energy over the G-aligned span around every such window; what a window holds beyond the inner span is at most 2 G
 // samples of at most Eout - Ein energy (Cauchy-Schwarz).  A flat window anywhere in the pair makes d2lb <= 0: nothing excluded.
-template <int METHOD>
-__device__ __forceinline__ void slb_one(const BoundArgs& a, const int pr, const int lane) {
+//
+// GROUP lanes take a pair (`lane`: the lane inside its group; `live`: the group has a pair -- an idle one is given another
+// group's, loads like it and stores nothing).  GROUP = 64 is the wave a pair (slb_one: pair, search and constants wave-uniform).
+// GROUP = SLB_GROUP = 16, four pairs a wave (slb_four), for patterns of up to 16 segments: a lane looks up six stretches instead
+// of two, still in one flight; the window energies' minimum and the norm sums are taken inside the group's row of sixteen lanes
+// -- a minimum does not depend on the order, and the sums are row_reduce_f32's, what wave_reduce_f32 starts with: the whole wave's
+// sum is the first row's plus exact zeros --; and the epilogue, ~300 wave-instructions of float64 on one lane, is issued once for
+// the four pairs, on the first lane of every group.  Every stored value has the bits the wave a pair gives it.
+constexpr int SLB_GROUP = 16;
+template <int METHOD, int GROUP>
+__device__ __forceinline__ void slb_body(const BoundArgs& a, const int pr, const int lane, const bool live, const int k, const SearchDesc sd) {
     constexpr bool CC = METHOD == SUSHI_HIP_METHOD_CCOEFF_NORMED;
-    const int k = __builtin_amdgcn_readfirstlane(a.pairmap[pr]);
-    const SearchDesc sd = a.searches[k];
+    static_assert(GROUP == 64 || GROUP == SLB_GROUP, "a wave or a row of sixteen lanes");
     const FftLayout lay = fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len);
     const int64_t pairI = absolute_pair(lay, a.sub_first_pair, pr, sd);
     const int64_t qbase = pairI * FFT_STEP * (int64_t)FFT_SEG;
@@ -252,17 +260,19 @@ __device__ __forceinline__ void slb_one(const BoundArgs& a, const int pr, const 
     // lower bound of the window energies (variance sums): the stretches of COARSE_G positions that hold a valid position
     constexpr int NSB = 2 * FH / COARSE_G;
     static_assert(NSB <= 128 && (FFT_STEP * FFT_SEG) % COARSE_G == 0, "a lane looks up two stretches");
+    constexpr int NSL = slb_stretches_a_lane(GROUP);            // stretches a lane looks up: two of a wave's, six of a group's
+    static_assert(NSL * GROUP >= NSB && (GROUP == 64 ? NSL == 2 : NSL * GROUP == NSB), "the group's lanes cover the stretches");
     const int64_t plo = sd.win_start - qbase, phi = (int64_t)sd.n_pos + (sd.win_start - qbase);       // valid: plo <= pos < phi
     const double* __restrict__ c2 = a.coarse;
     const double* __restrict__ c1 = a.coarse + a.nc;
     auto clampi = [&](int64_t x) { return x < a.nc - 1 ? x : a.nc - 1; };
-    // (both stretches of a lane: unconditional loads from clamped places, the stretch's validity applied afterwards)
-    bool use[2];
-    int64_t js[2], je[2], jo0[2], jo1[2];
-    double c2e[2], c2s[2], c1e[2], c1s[2], c2o1[2], c2o0[2], c1o1[2], c1o0[2];
+    // (every stretch of a lane: unconditional loads from clamped places, the stretch's validity applied afterwards)
+    bool use[NSL];
+    int64_t js[NSL], je[NSL], jo0[NSL], jo1[NSL];
+    double c2e[NSL], c2s[NSL], c1e[NSL], c1s[NSL], c2o1[NSL], c2o0[NSL], c1o1[NSL], c1o0[NSL];
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int sb = lane + 64 * t;
+    for (int t = 0; t < NSL; ++t) {
+        const int sb = slb_stretch(lane, t, GROUP);
         const int64_t p0 = (int64_t)sb * COARSE_G;
         use[t] = sb < NSB && p0 + COARSE_G > plo && p0 < phi;
         const int64_t j = qbase / COARSE_G + sb;
@@ -277,7 +287,7 @@ __device__ __forceinline__ void slb_one(const BoundArgs& a, const int pr, const 
     __builtin_amdgcn_sched_barrier(0);          // (nothing that uses a loaded value moves above this line: one flight)
     float wl = __builtin_inff();
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
+    for (int t = 0; t < NSL; ++t) {
         if (use[t]) {
             double e = 0.0;
             if (je[t] > js[t]) {
@@ -298,21 +308,34 @@ __device__ __forceinline__ void slb_one(const BoundArgs& a, const int pr, const 
             wl = fminf(wl, fmaxf((float)e * 0.9999995f, 0.f));
         }
     }
-    const float wlb = wave_min_f32(wl);
+    auto group_min = [](float v) {
+        if constexpr (GROUP == 64) return wave_min_f32(v);
+        else return row_reduce_f32(v, [](float x, float y) { return fminf(x, y); });
+    };
+    auto group_sum = [](float v) {
+        if constexpr (GROUP == 64) return wave_sum_f32(v);
+        else return row_reduce_f32(v, [](float x, float y) { return x + y; });
+    };
+    const float wlb = group_min(wl);
     float b_rest = 0.f;
     if (a.band) {
         const float t0n = lane < n_seg ? sqrtf(tn0) * 1.000002f : 0.f;
         float pz = t0n * zn0, pa = t0n * an0, pb = t0n * bn0;
-        for (int s = lane + 64; s < n_seg; s += 64) {               // (patterns of more than 64 segments)
-            const int64_t jj = kA + s < a.nb ? kA + s : a.nb;
-            const float t = sqrtf(a.tnorm_rest[(sd.first_seg - a.sub_first_seg) + s]) * 1.000002f;
-            pz += t * a.znorm_rest[jj]; pa += t * a.znorm_rest[a.norm_stride + jj]; pb += t * a.znorm_rest[2 * a.norm_stride + jj];
+        // (a group's products go into its reduction as ROUNDED products, as the wave's do, whose loop below carries them: left to
+        // itself the compiler contracts each into the reduction's first addition, and a sum's last bit changes now and then)
+        if constexpr (GROUP != 64) asm volatile("" : "+v"(pz), "+v"(pa), "+v"(pb));
+        if constexpr (GROUP == 64) {
+            for (int s = lane + 64; s < n_seg; s += 64) {               // (patterns of more than 64 segments)
+                const int64_t jj = kA + s < a.nb ? kA + s : a.nb;
+                const float t = sqrtf(a.tnorm_rest[(sd.first_seg - a.sub_first_seg) + s]) * 1.000002f;
+                pz += t * a.znorm_rest[jj]; pa += t * a.znorm_rest[a.norm_stride + jj]; pb += t * a.znorm_rest[2 * a.norm_stride + jj];
+            }
         }
-        pz = wave_sum_f32(pz); pa = wave_sum_f32(pa); pb = wave_sum_f32(pb);
+        pz = group_sum(pz); pa = group_sum(pa); pb = group_sum(pb);
         const int passes = (n_seg + MAC_SMAX_LONG - 1) / MAC_SMAX_LONG;
         b_rest = (fmaxf(pa, pb) + 1.5e-3f * pz) * tc.mac_scale * (1.0006f + 0.0005f * (float)passes) + 1e-3f;
     }
-    if (lane == 0) {
+    if (lane == 0 && live) {
         float B = acc0, qmax = acc1;
         if (a.band) {
             // acc[1] is the low band's energy, and the rest's is at most the square of its sum of moduli -- as one sixteenth of a
@@ -387,12 +410,36 @@ __device__ __forceinline__ void slb_one(const BoundArgs& a, const int pr, const 
         }
     }
 }
+// a wave a pair
+template <int METHOD>
+__device__ __forceinline__ void slb_one(const BoundArgs& a, const int pr, const int lane) {
+    const int k = __builtin_amdgcn_readfirstlane(a.pairmap[pr]);
+    const SearchDesc sd = a.searches[k];
+    slb_body<METHOD, 64>(a, pr, lane, true, k, sd);
+}
+// A wave takes the four pairs at `first` .. `first` + 3 of `count` (`pair_at`: entry -> pair; `first` < `count`), a group of
+// sixteen lanes each; a tail's idle groups are given the first pair.  Where one of the four has a pattern of more than SLB_GROUP
+// segments -- its norms would not fit a row of lanes --, the four are taken one after the other, a wave a pair.
+template <int METHOD, class PairAt>
+__device__ __forceinline__ void slb_four(const BoundArgs& a, const int first, const int count, const PairAt pair_at, const int lane) {
+    const int entry = first + lane / SLB_GROUP;
+    const bool live = entry < count;
+    const int pr = pair_at(live ? entry : first);
+    const int k = a.pairmap[pr];
+    const SearchDesc sd = a.searches[k];
+    if (__all(fft_layout(sd.win_start, sd.n_pos, sd.tmpl_len).n_seg <= SLB_GROUP)) {
+        slb_body<METHOD, SLB_GROUP>(a, pr, lane % SLB_GROUP, live, k, sd);
+        return;
+    }
+    for (int e = first; e < first + 64 / SLB_GROUP && e < count; ++e)
+        slb_one<METHOD>(a, __builtin_amdgcn_readfirstlane(pair_at(e)), lane);
+}
 template <int METHOD>
 __global__ __launch_bounds__(256)
 void slb_kernel(BoundArgs a) {
-    const int pr = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
-    if (pr >= a.n_pairs) return;
-    slb_one<METHOD>(a, pr, threadIdx.x & 63);
+    const int first = __builtin_amdgcn_readfirstlane((blockIdx.x * 4 + (threadIdx.x >> 6)) * (64 / SLB_GROUP));
+    if (first >= a.n_pairs) return;
+    slb_four<METHOD>(a, first, a.n_pairs, [](const int e) { return e; }, threadIdx.x & 63);
 }
 // the same for the pairs of a list (the second look at what the first bound left: bound_low_exact_kernel)
 template <int METHOD>
@@ -400,6 +447,23 @@ __global__ __launch_bounds__(256)
 void slb_list_kernel(BoundArgs a) {
     const int n = *a.list_count;
     if (n > a.n_pairs / 5) return;                      // (nothing was excluded to speak of: no second look either)
+    const int step = gridDim.x * 4 * (64 / SLB_GROUP);
+    for (int first = (blockIdx.x * 4 + (threadIdx.x >> 6)) * (64 / SLB_GROUP); first < n; first += step)
+        slb_four<METHOD>(a, first, n, [&](const int e) { return a.list[e]; }, threadIdx.x & 63);
+}
+// a wave a pair throughout (SUSHI_HIP_SLB=wave: the kernels before the groups, for A/B runs on one build)
+template <int METHOD>
+__global__ __launch_bounds__(256)
+void slb_wave_kernel(BoundArgs a) {
+    const int pr = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    if (pr >= a.n_pairs) return;
+    slb_one<METHOD>(a, pr, threadIdx.x & 63);
+}
+template <int METHOD>
+__global__ __launch_bounds__(256)
+void slb_list_wave_kernel(BoundArgs a) {
+    const int n = *a.list_count;
+    if (n > a.n_pairs / 5) return;
     const int waves = gridDim.x * 4;
     for (int slot = blockIdx.x * 4 + (threadIdx.x >> 6); slot < n; slot += waves)
         slb_one<METHOD>(a, __builtin_amdgcn_readfirstlane(a.list[slot]), threadIdx.x & 63);
@@ -491,12 +555,47 @@ __device__ __forceinline__ void append_pairs(int* list, int* count, RunCounters*
     base = __shfl(base, 0, 64);
     if (add) list[base + __popcll(m & ((1ull << lane) - 1ull))] = pr;
 }
+// One reservation a WORKGROUP for the kernels that list most of what a sub-batch lists (survivor_kernel, survivor2_kernel): every
+// wave of a launch adding to the same two words is a chain of same-address atomics, which serialise in the L2 (the votes' lesson,
+// slb_one) -- 4.8 k of them in survivor_kernel's 0.085 ms at BASELINE configs[2].  Here the waves' counts meet in a few words of LDS
+// and thread 0 reserves for all of them: `n_wave` entries of the list behind `count` for this wave -> where they begin, in wave
+// order inside the workgroup; `delta_wave`, summed over the workgroup, goes to pairs_transformed (it may be negative).  Every
+// thread of a workgroup of WAVES waves calls it, the arguments wave-uniform; two barriers.  A kernel that calls it again puts a
+// barrier between the calls (the words are read behind the second one).
+template <int WAVES>
+__device__ __forceinline__ int reserve_pairs_block(int* count, RunCounters* counters, const int n_wave, const int delta_wave) {
+    __shared__ int s_n[WAVES], s_delta[WAVES];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) { s_n[w] = n_wave; s_delta[w] = delta_wave; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int before[WAVES], total = 0, delta = 0;
+#pragma unroll
+        for (int i = 0; i < WAVES; ++i) { before[i] = total; total += s_n[i]; delta += s_delta[i]; }
+        const int base = total ? atomicAdd(count, total) : 0;
+        if (delta) atomicAdd(&counters->pairs_transformed, (unsigned long long)(long long)delta);
+#pragma unroll
+        for (int i = 0; i < WAVES; ++i) s_n[i] = base + before[i];
+    }
+    __syncthreads();
+    return s_n[w];
+}
+// append_pairs with that reservation: the same entries, in lane order inside a wave and in wave order inside the workgroup
+template <int WAVES>
+__device__ __forceinline__ void append_pairs_block(int* list, int* count, RunCounters* counters, const bool add, const int pr) {
+    const unsigned long long m = __ballot(add);
+    const int lane = threadIdx.x & 63;
+    const int base = reserve_pairs_block<WAVES>(count, counters, __popcll(m), __popcll(m));
+    if (add) list[base + __popcll(m & ((1ull << lane) - 1ull))] = pr;
+}
 
 // every pair but the pilots: excluded (its lower bound is above what the search has already found: pair_lb = +inf, what
 // refine_kernel and collect_kernel skip by), or listed for ifft_kernel in the order of the L2-friendly schedule
-__global__ __launch_bounds__(256)
+// (workgroups of sixteen waves, one reservation each: 347 for the pairs of BASELINE configs[2] -- reserve_pairs_block)
+constexpr int SURVIVOR_THREADS = 1024;
+__global__ __launch_bounds__(SURVIVOR_THREADS)
 void survivor_kernel(BoundArgs a) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
+    const int b = blockIdx.x * SURVIVOR_THREADS + threadIdx.x;
     bool keep = false;
     int pr = 0;
     if (b < a.n_pairs) {
@@ -517,7 +616,7 @@ void survivor_kernel(BoundArgs a) {
         }
         if (a.audit_mark) a.audit_mark[pr] = (audit ? MARK_AUDITED : 0) | (keep ? MARK_LISTED : 0);
     }
-    append_pairs(a.slist, a.scount, a.counters, keep, pr);
+    append_pairs_block<SURVIVOR_THREADS / 64>(a.slist, a.scount, a.counters, keep, pr);
 }
 
 // The whole rows of the LISTED pairs, search by search (band-split form, the pairs the bound left): a workgroup = 256 consecutive
@@ -763,8 +862,80 @@ void mac_rows_kernel(MacRowsArgs a) {
 constexpr int BLE_LOGN = 13;
 constexpr int BLE_N = sushi_fft::Plan<BLE_LOGN>::N, BLE_T = sushi_fft::Plan<BLE_LOGN>::NT;
 static_assert(BLE_N == FN / 2, "the low band sampled at every second position");
-__global__ __launch_bounds__(BLE_T)
+// sqrt(2) x the largest sample (`mm`: its square as float bits) + bin 0's own part, signed.  The float32 transform's own error is at
+// most 1e-5 of the inputs' sum of moduli <= 1e-5 sqrt(4096) |inputs|_2 = 1e-5 sqrt(4096 / 8192) |outputs|_2 <= 6.4e-4 x the largest
+// output (Parseval over the 8192 samples): a factor, not a term that needs the row's energy
+__device__ __forceinline__ float second_look_bound(const unsigned mm, const float dc_re, const float dc_im) {
+    const float bw = 1.4142137f * sqrtf(__uint_as_float(mm)) * 1.0007f + fmaxf(dc_re, dc_im);
+    return mm >= 0x7f800000u ? __builtin_inff() : bw;
+}
+// The kernel's fixed costs per slot are what it runs on (~1200 slots a launch at BASELINE configs[2], one or two a workgroup):
+//   * which of a thread's sixteen input registers lie in the band depends on the register alone, and the eight that do are two
+//     16-byte entries of the row (fft_core.hpp sl_in_band, sl_sub, sl_entry): two loads, the other eight registers constants;
+//   * the next slot's two entries (and the pair after that one) are requested before the current slot is transformed;
+//   * the largest sample meets in ONE word of LDS -- float bits of squares order as unsigned --, an atomic a wave, one barrier:
+//     the word of the next slot is cleared in front of that barrier, the two words taking turns.
+// The same loads' values, fft_split as it is, the same maximum: acc[2 pr] keeps its bits (SUSHI_HIP_SECOND_LOOK=plain: the body
+// before this one, bound_low_exact_plain_kernel below, for A/B runs on one build).
+__global__ __launch_bounds__(BLE_T, 8)                          // (eight waves a SIMD -- four workgroups a CU, as the buffer allows: 64 registers)
 void bound_low_exact_kernel(BoundArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[sushi_fft::lds_floats<BLE_LOGN>()];
+    __shared__ unsigned red[2];
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    const int n = *a.list_count;
+    if (n > a.n_pairs / 5) return;
+    int slot = blockIdx.x;
+    if (slot >= n) return;
+    if (threadIdx.x == 0) { red[0] = 0u; red[1] = 0u; }          // (fft_split's barriers lie between this and the first atomic)
+    const sushi_fft::uint4v* __restrict__ rows = reinterpret_cast<const sushi_fft::uint4v*>(a.y);
+    int pr = a.list[slot];
+    sushi_fft::uint4v w0, w1;
+    {
+        const int t0 = threadIdx.x;
+        w0 = rows[(size_t)pr * LROWE + sushi_fft::sl_entry(t0, 0)]; w1 = rows[(size_t)pr * LROWE + sushi_fft::sl_entry(t0, 1)];
+    }
+    int slot_n = slot + gridDim.x;
+    int pr_n = slot_n < n ? a.list[slot_n] : pr;                 // (the last slot re-requests itself: unconditional loads)
+    for (int turn = 0;; turn ^= 1) {
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));                            // (per-iteration constants stay inside the iteration: hoisted, they spill)
+        const sushi_fft::uint4v n0 = rows[(size_t)pr_n * LROWE + sushi_fft::sl_entry(tid, 0)];
+        const sushi_fft::uint4v n1 = rows[(size_t)pr_n * LROWE + sushi_fft::sl_entry(tid, 1)];
+        const int slot_nn = slot_n + gridDim.x;
+        const int pr_nn = slot_nn < n ? a.list[slot_nn] : pr_n;
+        const float first_look = tid == 0 ? a.acc[2 * (size_t)pr] : 0.f;
+        const sushi_fft::Twiddles tw = sushi_fft::load_twiddles<BLE_LOGN, 1>(tid, twiddles());
+        __builtin_amdgcn_sched_barrier(0);                       // (the requests stay in front of the transform)
+        cpx v[sushi_fft::PER];
+#pragma unroll
+        for (int r = 0; r < sushi_fft::PER; ++r) {
+            if (sushi_fft::sl_in_band(r)) {
+                const h2 h = __builtin_bit_cast(h2, r < 8 ? w0[sushi_fft::sl_sub(r)] : w1[sushi_fft::sl_sub(r)]);
+                v[r] = cpx{(float)h.x, (float)h.y};
+            } else {
+                v[r] = cpx{0.f, 0.f};
+            }
+        }
+        float dc_re = 0.f, dc_im = 0.f;
+        if (tid == 0) { dc_re = v[0].x; dc_im = v[0].y; v[0] = cpx{0.f, 0.f}; }       // (bin 0: register 0 of thread 0)
+        sushi_fft::fft_split<BLE_LOGN, 1>(v, tid, lds, tw);
+        float m2 = 0.f;
+#pragma unroll
+        for (int r = 0; r < sushi_fft::PER; ++r) m2 = fmaxf(m2, v[r].x * v[r].x + v[r].y * v[r].y);
+        const unsigned wm = wave_max_u32(__float_as_uint(m2));
+        if ((tid & 63) == 0) atomicMax(&red[turn], wm);
+        if (tid == 0) red[turn ^ 1] = 0u;
+        __syncthreads();                                         // (also the barrier the transform's buffer needs before its next use)
+        // (never above the first look's: both are bounds)
+        if (tid == 0) a.acc[2 * (size_t)pr] = fminf(first_look, second_look_bound(red[turn], dc_re, dc_im));
+        slot = slot_n;
+        if (slot >= n) break;
+        pr = pr_n; w0 = n0; w1 = n1; slot_n = slot_nn; pr_n = pr_nn;
+    }
+}
+// the body before that one (SUSHI_HIP_SECOND_LOOK=plain)
+__global__ __launch_bounds__(BLE_T)
+void bound_low_exact_plain_kernel(BoundArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[sushi_fft::lds_floats<BLE_LOGN>()];
     __shared__ unsigned red[BLE_T / 64];
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
@@ -840,13 +1011,10 @@ void survivor2_kernel(BoundArgs a) {
         }
         const unsigned long long m = __ballot(keep), act = __ballot(slot < n);
         const int lane = threadIdx.x & 63;
-        const int dropped = __popcll(act) - __popcll(m);
-        int b0 = 0;
-        if (lane == 0 && m) b0 = atomicAdd(a.list2_count, __popcll(m));
-        if (lane == 0 && dropped > 0)                          // (they were counted as transformed when they were listed)
-            atomicAdd(&a.counters->pairs_transformed, (unsigned long long)0 - (unsigned long long)dropped);
-        b0 = __shfl(b0, 0, 64);
+        const int dropped = __popcll(act) - __popcll(m);          // (they were counted as transformed when they were listed)
+        const int b0 = reserve_pairs_block<4>(a.list2_count, a.counters, __popcll(m), -dropped);
         if (keep) a.list2[b0 + __popcll(m & ((1ull << lane) - 1ull))] = pr;
+        __syncthreads();                                           // (a further round writes the reservation's words again)
     }
 }
 

@@ -38,6 +38,12 @@ static_assert(FFT_CAND + 2 + AUDIT_RUNS * FFT_AUDIT <= FFT_ROW, "candidates, ove
 constexpr int TILE = 1024;                         // positions per exact-evaluation tile (aligned to the absolute grid)
 constexpr int TILES_PER_PAIR = 2 * FFT_H / TILE;
 constexpr int COARSE_G = 256;                      // granularity of the coarse prefix table (SushiHipStream.coarse)
+// The pair bound's window energies (slb_kernel): a pair's positions are SLB_STRETCHES stretches of COARSE_G, looked up by the
+// `group` lanes that take the pair -- a wave, or a row of sixteen --, lane l the stretches l, l + group, ... (one beyond the last
+// stretch is masked: a wave's last lanes have no second one).
+constexpr int SLB_STRETCHES = 2 * FFT_H / COARSE_G;
+SUSHI_GEOM_HD constexpr int slb_stretches_a_lane(int group) { return (SLB_STRETCHES + group - 1) / group; }
+SUSHI_GEOM_HD constexpr int slb_stretch(int lane, int t, int group) { return lane + group * t; }
 
 // Overlap-save layout of one search (DESIGN.md "FFT path"): its block pairs sit on the ABSOLUTE pair grid (pair I
 // starts at block FFT_STEP * I), from the pair holding the window's first position to the one holding its last.

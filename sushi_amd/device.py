@@ -592,6 +592,34 @@ class SearchBatch(object):
         with torch.cuda.device(self._mem.device):
             return torch.as_tensor(_Foreign(), device=self._mem.device).clone().view(torch.float16)
 
+    def bounds_again(self, by_wave, which=0):
+        """FFT path, after a run that went through the pair exclusion: the last sub-batch's bound pass once more on what the run
+        left (sushi_hip_batch_bounds_again) -> (slb float32[pairs], [pairs looked at, pairs with room] for which=2 else None).
+        by_wave: a wave a pair (SUSHI_HIP_SLB=wave's kernels) or the default's groups; which: 0 every pair, 1 the second look's
+        list, 2 the prediction mode.  For the tests of that pass.  Synchronises."""
+        n = ctypes.c_int64(int(self.fft_pairs))
+        slb = np.empty(int(self.fft_pairs), np.float32)
+        votes = np.zeros(2, np.int32)
+        _native.check(_native.lib().sushi_hip_batch_bounds_again(self._handle, int(bool(by_wave)), int(which), slb.ctypes.data,
+                                                                 votes.ctypes.data, ctypes.byref(n)), "sushi_hip_batch_bounds_again")
+        return slb[:n.value], ([int(votes[0]), int(votes[1])] if which == 2 else None)
+
+    def exclusion_state(self):
+        """FFT path, after a run that went through the pair exclusion: what its passes left of the last sub-batch, as NumPy copies
+        (sushi_hip_batch_workspace_view, WS_SLIST .. WS_PAIR_LB) -- `slist` / `slist2` int32[pairs] with their lengths `n_slist` /
+        `n_slist2`, `marks` uint8[pairs] (bit 0 audited, bit 1 listed, bit 2 the second look's audit), `pair_lb` float32[pairs].
+        For the tests of those passes.  Synchronises."""
+        def raw(which, dtype):
+            ptr, nbytes = ctypes.c_void_p(), ctypes.c_size_t(0)
+            _native.check(_native.lib().sushi_hip_batch_workspace_view(self._handle, int(which), ctypes.byref(ptr), ctypes.byref(nbytes)),
+                          "sushi_hip_batch_workspace_view")
+            off = ptr.value - self._mem.data_ptr()
+            assert ptr.value and 0 <= off and off + nbytes.value <= self._mem.numel()
+            return self._mem[off:off + nbytes.value].cpu().numpy().view(dtype).copy()
+        counts = raw(_native.WS_SCOUNT, np.int32)
+        return {"slist": raw(_native.WS_SLIST, np.int32), "slist2": raw(_native.WS_SLIST2, np.int32), "n_slist": int(counts[0]),
+                "n_slist2": int(counts[5]), "marks": raw(_native.WS_MARKS, np.uint8), "pair_lb": raw(_native.WS_PAIR_LB, np.float32)}
+
     def ranking_errors(self):
         """FFT path: |f32 FFT score - exact score| at every search's result position in the last run()
         (0 for searches the tile kernel finished)."""
