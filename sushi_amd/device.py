@@ -295,6 +295,17 @@ class SearchBatch(object):
     sub-batch is large enough for that to pay, in the form -- band-split or whole rows -- the streams' spectra allow), 'always'
     (that choice of form for a batch of any size), 'never', 'band' / 'whole' (one form forced) -- same results, different time; None reads
     SUSHI_HIP_EXCLUSION (the GPU test suite sets it to 'always' so that every edge case goes through the exclusion).
+
+    Streams.  Every run kind takes the stream it is enqueued on (hip_stream: a raw hipStream_t; None: the current torch stream).
+    The batch remembers the stream of its last run and whether results() has collected that run:
+      * results() waits for THAT stream -- not for whichever is current -- and makes its device-to-host copies behind it;
+      * reset() and every run kind first wait for a run that may still be pending where the library cannot order the two itself:
+        when they are given ANOTHER stream than that run's (the batch has one workspace and one set of descriptors; the header
+        says of sushi_hip_batch_reset that such a run "must have finished"), and when the batch has early records and its last
+        run() was not collected (a record says ready, not which run wrote it: a run that has not executed yet would still
+        write its own answer over the next one's cleared record);
+      * run() followed by results() on one stream -- what wav.py does, call after call -- waits for nothing it did not wait for
+        before.
     """
 
     def __init__(self, dst, src, tmpl_off, tmpl_len, win_start, n_pos, variant=None, path=None,
@@ -361,7 +372,32 @@ class SearchBatch(object):
                     _native.check(L.sushi_hip_batch_set_early_output(h, self._early.data_ptr()), "sushi_hip_batch_set_early_output")
             else:
                 self.set_packed_output(torch.empty((n, 2), dtype=torch.int32, device=dev))
+        # the stream of the last run (raw), whether that stream may still hold work of the batch's, whether results() has read
+        # that run's answer (the class docstring's rule)
+        self._last_raw, self._in_flight, self._collected = None, False, True
         self._read_info()
+
+    def _stream_of(self, raw):
+        """A torch stream for a raw one this batch ran on (the current stream itself where that is it)."""
+        cur = torch.cuda.current_stream(self.dst.device)
+        if cur.cuda_stream == raw:
+            return cur
+        return torch.cuda.ExternalStream(raw, device=self.dst.device) if raw else torch.cuda.default_stream(self.dst.device)
+
+    def _settle(self, raw):
+        """Before a re-plan or a run on the raw stream `raw`: the last run is through if it may still be pending and the library
+        cannot order the two (the class docstring's rule).  The callers ask only where the stream differs or the last run was
+        not collected: nothing on the paired path."""
+        if self._in_flight and (raw != self._last_raw or (self._early_np is not None and not self._collected)):
+            self._stream_of(self._last_raw).synchronize()
+            self._in_flight = False
+
+    def early_ready(self):
+        """The early records' ready words, int32 [n], LIVE (a view of the pinned records; None for a batch without them): non-zero
+        where the record holds an answer of the last run() by now (sushi_hip_batch_set_early_output: ready is the record's third
+        word; run() clears it, and _settle sees to it that no earlier run is left to set it).  What results() polls."""
+        e = self._early_np
+        return None if e is None else e[:, 2]
 
     def _read_info(self):
         info = _native.BatchInfo()
@@ -397,7 +433,10 @@ class SearchBatch(object):
         if req.shape[0] != self.n:
             raise SushiError("reset: a batch keeps its number of searches")
         with torch.cuda.device(self.dst.device):
-            rc = _native.lib().sushi_hip_batch_reset(self._handle, req.ctypes.data, self.n, _raw_stream(self.dst.device))
+            st = _raw_stream(self.dst.device)
+            if st != self._last_raw or not self._collected:
+                self._settle(st)                          # (the upload goes on `st`: a run pending elsewhere still reads the old descriptors)
+            rc = _native.lib().sushi_hip_batch_reset(self._handle, req.ctypes.data, self.n, st)
         if rc == _native.ENOSPACE:
             return False
         _native.check(rc, "sushi_hip_batch_reset")
@@ -438,8 +477,11 @@ class SearchBatch(object):
     def run(self, hip_stream=None):
         """One pass of the hot path over this batch (asynchronous)."""
         st = _raw_stream(self.dst.device) if hip_stream is None else hip_stream
+        if st != self._last_raw or not self._collected:
+            self._settle(st)
         if self._early_np is not None:
             self._early_np[:, 2] = 0                      # not ready: results() polls
+        self._last_raw, self._in_flight, self._collected = st, True, False
         rc = _native.lib().sushi_hip_batch_run(self._handle, self.delta, self.out_idx.data_ptr(),
                                                self.out_score.data_ptr(), st)
         _native.check(rc, "sushi_hip_batch_run")
@@ -466,6 +508,9 @@ class SearchBatch(object):
             # (capacity 0: a valid pointer all the same -- nothing is written through it)
             hp = hits.data_ptr() if hits.numel() else counts.data_ptr()
             st = _raw_stream(dev) if hip_stream is None else hip_stream
+            if st != self._last_raw or not self._collected:
+                self._settle(st)
+            self._last_raw, self._in_flight = st, True
             rc = _native.lib().sushi_hip_batch_run_threshold(self._handle, threshold, capacity, hp, counts.data_ptr(), st)
             _native.check(rc, "sushi_hip_batch_run_threshold")
         return hits, counts
@@ -514,6 +559,9 @@ class SearchBatch(object):
             hits = torch.empty((self.n, k, 2), dtype=torch.int32, device=dev)
             counts = torch.empty(self.n, dtype=torch.int32, device=dev)
             st = _raw_stream(dev) if hip_stream is None else hip_stream
+            if st != self._last_raw or not self._collected:
+                self._settle(st)
+            self._last_raw, self._in_flight = st, True
             rc = _native.lib().sushi_hip_batch_run_best(self._handle, k, sep, thr, hits.data_ptr(), counts.data_ptr(), st)
             _native.check(rc, "sushi_hip_batch_run_best")
         return hits, counts
@@ -524,26 +572,35 @@ class SearchBatch(object):
         return _hit_lists(hits.cpu().numpy(), counts.cpu().numpy())
 
     def results(self):
-        """(idx int32 ndarray, score float32 ndarray) -- synchronises."""
+        """(idx int32 ndarray, score float32 ndarray) of the last run() -- synchronises with the stream that run was given."""
+        self._collected = True
         if self._early_np is not None:
             # the answer as soon as the kernel that has it wrote it (a spin of a few dozen microseconds; a search that went on to
             # the tile stage, or a GPU that takes longer than any drop-in call does, falls through to the stream's end)
-            e = self._early_np
+            e, ready = self._early_np, self.early_ready()
             t_end = time.perf_counter() + 2e-3
-            while not e[:, 2].all():
+            while not ready.all():
                 if time.perf_counter() > t_end:
                     break
             else:
                 if not e[:, 3].any():
+                    # (_in_flight stays set: the launches behind refine_kernel may still be pending on the run's stream, and a
+                    # reset() or run() given another stream has to wait for them)
                     return e[:, 0].copy(), e[:, 1].copy().view(np.float32)
+        st = self._stream_of(_raw_stream(self.dst.device) if self._last_raw is None else self._last_raw)
         if self._host_rec is not None:
-            torch.cuda.current_stream(self.dst.device).synchronize()
+            st.synchronize()
+            self._in_flight = False
             rec = self._host_rec.numpy()
             return rec[:, 0].copy(), rec[:, 1].copy().view(np.float32)
-        if self._packed is not None:
-            rec = self._packed[:self.n].cpu().numpy()
-            return np.ascontiguousarray(rec[:, 0]), np.ascontiguousarray(rec[:, 1]).view(np.float32)
-        return self.out_idx.cpu().numpy(), self.out_score.cpu().numpy()
+        with torch.cuda.stream(st):                       # (the copies go behind the run and are waited for there)
+            if self._packed is not None:
+                rec = self._packed[:self.n].cpu().numpy()
+                out = np.ascontiguousarray(rec[:, 0]), np.ascontiguousarray(rec[:, 1]).view(np.float32)
+            else:
+                out = self.out_idx.cpu().numpy(), self.out_score.cpu().numpy()
+        self._in_flight = False
+        return out
 
     def diagnostics(self, per_search=False):
         """What the last run() did (FFT path): a dict of the SushiHipBatchDiag fields, plus -- per_search=True --
